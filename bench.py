@@ -17,7 +17,10 @@ The peak is derived from the device (CU count x 4096 bf16 FLOP/clk/CU x max cloc
 `cpu_baseline` times the CPU oracle (a port of the reference semantics, fp32) on this box's host
 cores as BASELINE.md §3 prescribes: C2 (Base) at B=8, 3 steps after one warm-up, and C1 (Tiny) at
 B=32, 10 steps.  `--check` runs the full-shape numeric check (tools/fullshape_check.py) and an
-end-to-end comparison after the timed region.
+end-to-end comparison after the timed region.  `--dump-outputs DIR` writes what the last timed step returned
+(logits, loss, aux losses, clipped gradient norm) and a fixed sample of the weights it left behind as DIR/<name>.npy
+(float32), so that two builds can be compared output for output: weights, inputs and the sample are seeded, so the
+same arguments give the same inputs on every run.
 """
 from __future__ import annotations
 
@@ -130,6 +133,42 @@ def run_parity(model, cfg, args, X):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+PARAM_SAMPLE_PER_TENSOR = 4096
+
+
+def snapshot_outputs(model, logits, loss, aux, gnorm):
+    """Host copies (float32) of what a caller of the timed train step receives from its last call, and a fixed sample
+    of the weights that step updated: every element of a parameter with <= PARAM_SAMPLE_PER_TENSOR elements, else
+    that many indices drawn by a generator seeded per parameter, in named_parameters() order."""
+    out = {"logits": logits, "loss": loss}
+    out.update({f"aux_{k}": v for k, v in aux.items()})
+    if gnorm is not None:
+        out["grad_norm"] = gnorm
+    out = {k: v.detach().float().cpu().numpy() for k, v in out.items()}
+    samples = []
+    with torch.no_grad():
+        for i, (_, p) in enumerate(model.named_parameters()):
+            flat = p.detach().reshape(-1)
+            if flat.numel() > PARAM_SAMPLE_PER_TENSOR:
+                g = torch.Generator().manual_seed(1000 + i)
+                idx = torch.randperm(flat.numel(), generator=g)[:PARAM_SAMPLE_PER_TENSOR].sort().values
+                flat = flat[idx.to(flat.device)]
+            samples.append(flat.float().cpu())
+    out["param_sample"] = torch.cat(samples).numpy()
+    return out
+
+
+def dump_outputs(arrays, dirname):
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, f"{name}.npy"), np.asarray(a, dtype=np.float32))
+
+
 def run_check(model, cfg, args, X, dev):
     """Correctness of the benchmarked shape itself, outside the timed region."""
     sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -173,7 +212,12 @@ def main() -> None:
     ap.add_argument("--graph", action="store_true",
                     help="replay the step as one hipGraph (1 GPU, no Kohonen head); the per-kernel roofline is then "
                          "taken from a short eager pass after the timed region")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (logits, loss, aux losses, gradient norm) and a fixed "
+                         "sample of the updated weights as DIR/<name>.npy, float32 (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch.distributed as dist
     from nvit_amd import ops
@@ -236,6 +280,8 @@ def main() -> None:
             logits, loss, aux, gnorm = graphed(X, y)
         barrier()
         dt = time.perf_counter() - t0
+        if args.dump_outputs and rank == 0:
+            dumped = snapshot_outputs(model, logits, loss, aux, gnorm)
         prof_steps = min(args.steps, 3)
         ops.prof_enable(True)
         ops.prof_collect()
@@ -253,6 +299,8 @@ def main() -> None:
             logits, loss, aux, gnorm = train_step(step_model, opt, X, y, 1.0, sync_grads=sync)
         barrier()
         dt = time.perf_counter() - t0
+        if args.dump_outputs and rank == 0:
+            dumped = snapshot_outputs(model, logits, loss, aux, gnorm)
         ops.prof_enable(False)
         timed_gemm_nt = ops.prof_collect()["gemm_nt"]
         prof_steps = min(args.steps, 3)
@@ -268,6 +316,8 @@ def main() -> None:
         dt = t.item()
     if not torch.isfinite(loss).item():
         raise SystemExit("non-finite loss in the timed region")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(dumped, args.dump_outputs)
     dist_info = None
     if world > 1:
         # what the communicator saw, so that a multi-GPU run answers "did RCCL see N ranks on N devices, was the
