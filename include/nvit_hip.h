@@ -133,17 +133,13 @@ int nvit_gemm_nt(int dt, const void* A, int lda, const void* B, int ldb, void* C
  *   uv[M,2F] (interleaved, as written by nvit_gemm_nt_swiglu) it writes duv[M,2F] (same layout) and, when gs != NULL
  *   (suv, natural order [u(F)|v(F)]), part[2*ceil(M/256), 2F] = per-128-row partial sums of d(suv) (natural order;
  *   reduce with nvit_colsum_reduce).  Replaces nvit_gemm_nt + nvit_swiglu_bwd.  Requires F % 256 == 0. */
-/* Tile scheduling of the persistent NT GEMM kernels: 0 = static round-robin (default, or NVIT_GEMM_SCHED=static),
- * 1 = dynamic per-XCD ticket counters (NVIT_GEMM_SCHED=dynamic): robust when other kernels (RCCL) hold some CUs. */
+/* Tile scheduling of the persistent NT GEMM kernels: 0 = static round-robin (default), 1 = dynamic per-XCD ticket
+ * counters: robust when other kernels (RCCL) hold some CUs.  The data-parallel wrapper (parallel.py) selects dynamic. */
 int nvit_set_gemm_sched(int dynamic);
-/* Kernel selection for tests / experiments (-1 = environment default).  nt_impl: 0 = 128x128 kernel only,
+/* Kernel selection for tests (-1 = the built-in default).  nt_impl: 0 = 128x128 kernel only,
  * 1 = persistent 256-row kernels for large problems (default), 2 = persistent kernels whatever the tile count;
  * tn_impl: 0 = 128x128 kernel only, 1 = persistent 256x256 kernel for eligible shapes (default). */
 int nvit_set_gemm_impl(int nt_impl, int tn_impl);
-/* Variants of the persistent weight-gradient kernel (A/B measurements).  bit 0: 1 = XCD-contiguous work-item deal
- * (default: tiles that share operand panels run on one XCD and hit its L2), 0 = round-robin (NVIT_TN_ORDER=0);
- * +2 = ring of 4 x 32 KiB stages, +4 = ring of 2 x 64 KiB stages (default; NVIT_TN_RING=4 selects the former). */
-int nvit_set_tn_order(int mode);
 int nvit_gemm_nt_fusable(int dt, int M, int N, int K);
 int nvit_gemm_nt_swiglu_bwd(int dt, const void* A, int lda, const void* B, int ldb, const void* uv, void* duv,
                             float* part, int M, int F, int K, const float* gs, float gscale, void* stream);
@@ -394,8 +390,8 @@ int nvit_xgmi_errword_alloc(void** host_ptr, void** dev_ptr);
 int nvit_xgmi_errword_free(void* host_ptr);
 
 /* Attention backward, dK/dV kernel: 1 = the hand-placed (generated-assembly) main loop where it applies (pre-scaled q,
- * the fused entry point; default, NVIT_ATTN_DKV_ASM=0 turns it off), 0 = the compiler-built kernel.  Both compute
- * bit-identical results (tests/test_gpu_ops.py). */
+ * the fused entry point; default), 0 = the compiler-built kernel.  Both compute bit-identical results
+ * (tests/test_gpu_ops.py). */
 int nvit_set_attn_dkv_asm(int on);
 
 #ifdef __cplusplus

@@ -9,7 +9,7 @@ import ctypes as C
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# (NVIT_LIB: experiments with an alternative build of the same sources, e.g. tools/overlap_probe.py; never set in product use)
+# (NVIT_LIB: experiments with an alternative build of the same sources, e.g. tools/ab_lib.sh; never set in product use)
 LIB_PATH = os.environ.get("NVIT_LIB") or os.path.join(_HERE, "libnvit_hip.so")
 
 F32, BF16, BF16_F32IN = 0, 1, 3
@@ -35,7 +35,6 @@ SIGNATURES = {
     "nvit_adamw_tick": [_vp, C.c_double, C.c_double, _vp],
     "nvit_set_gemm_sched": [_i],
     "nvit_set_gemm_impl": [_i, _i],
-    "nvit_set_tn_order": [_i],
     "nvit_ce_loss": [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp],
     "nvit_gemm_nt": [_i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp],
     "nvit_gemm_nt_fusable": [_i, _i, _i, _i],

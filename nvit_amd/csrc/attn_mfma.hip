@@ -1022,7 +1022,7 @@ __device__ __forceinline__ unsigned long long uni64(const void* p) {
 
 // The geometry of the compiler-built kernel (4 waves x 32 keys, 256 registers per wave, two workgroups per CU: one
 // workgroup's prologue / epilogue runs under the other's tile loop), the tile loop software-pipelined by the generator.
-// (A one-wave-per-SIMD form with 64 keys per wave was built as well - tools/probes/gen_attn_dkv64_asm.py, bit-exact too:
+// (A one-wave-per-SIMD form with 64 keys per wave was built as well - bit-exact too, its generator since removed:
 // its tile loop is 1.57x faster per key, but with one wave per SIMD nothing hides a workgroup's prologue and epilogue,
 // 14 of its 31 us, and the kernel ends up 7-13 % slower than the compiler-built one.)
 #include "attn_dkv32_asm.inc"
@@ -1133,13 +1133,9 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_asm32_kernel(const bf16* 
   }
 }
 
-// -1: read NVIT_ATTN_DKV_ASM on first use.  0: compiler-built kernel; 1 (default): hand-placed loop
-int g_attn_dkv_asm = -1;
+// nvit_set_attn_dkv_asm: 0 = compiler-built kernel; 1 (default) = hand-placed loop
+int g_attn_dkv_asm = 1;
 int dkv_asm_mode(float scale, float qpre) {
-  if (g_attn_dkv_asm < 0) {
-    const char* e = getenv("NVIT_ATTN_DKV_ASM");
-    g_attn_dkv_asm = (e && e[0] == '0') ? 0 : 1;
-  }
   const float c2 = scale * LOG2E / qpre;
   return fabsf(c2 - 1.0f) < 1e-6f ? g_attn_dkv_asm : 0;   // the hand-placed loops assume the pre-scaled q (c2 = 1)
 }
@@ -1175,7 +1171,7 @@ int nvit_attn_bwd_mfma(const void* dout, const void* qh, const void* kh, const v
   return NVIT_OK;
 }
 
-// (experiments / tests) 1: hand-placed dK/dV main loop where it applies (default), 0: the compiler-built kernel
+// (tests) 1: hand-placed dK/dV main loop where it applies (default), 0: the compiler-built kernel
 extern "C" int nvit_set_attn_dkv_asm(int mode) {
   g_attn_dkv_asm = mode > 0 ? 1 : 0;
   return NVIT_OK;

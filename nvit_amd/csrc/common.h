@@ -98,3 +98,16 @@ __device__ __forceinline__ void st1(T* p, float v) {
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
+
+// ---- per-device host queries, cached (one slot per device ordinal) --------------
+constexpr int NVIT_MAX_DEVICES = 16;
+// compute units of the current device; 0 when the query fails (core.hip)
+int nvit_num_cu();
+// device address of a library-owned __device__ array (HIP_SYMBOL(x)) on the current device, resolved once per device
+// into the caller's cache; nullptr when it cannot be resolved
+static inline void* nvit_symbol_address(const void* symbol, void* (&cache)[NVIT_MAX_DEVICES]) {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= NVIT_MAX_DEVICES) return nullptr;
+  if (!cache[dev] && hipGetSymbolAddress(&cache[dev], symbol) != hipSuccess) return nullptr;
+  return cache[dev];
+}

@@ -18,6 +18,15 @@ void nvit_set_error(const char* fmt, ...) {
 extern "C" const char* nvit_last_error(void) { return g_err; }
 extern "C" int nvit_version(void) { return 100; }
 
+int nvit_num_cu() {
+  static int cache[NVIT_MAX_DEVICES] = {};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= NVIT_MAX_DEVICES) return 0;
+  if (!cache[dev] && hipDeviceGetAttribute(&cache[dev], hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+    cache[dev] = 0;
+  return cache[dev];
+}
+
 // ---- event timing ----------------------------------------------------------------
 // Events are recorded on the stream the kernel is launched on, immediately before and
 // after the launch(es) of one C-ABI call; collect() synchronises them and sums per family.

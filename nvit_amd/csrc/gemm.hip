@@ -16,8 +16,6 @@
 // Operand orientation: the MFMA "A" operand is fed from the B matrix (rows = n) and the "B"
 // operand from the A matrix (cols = m), so each lane ends up with 4 CONSECUTIVE n of one
 // row m: epilogue vectors (bias, column scales) are float4 loads and stores are 8/16 bytes.
-#include <stdlib.h>
-
 #include "gemm_common.h"
 
 int nvit_gemm_nt_persistent_launch(int dt, const NtArgs& g, int tile_n, hipStream_t s);
@@ -346,14 +344,14 @@ __global__ void slab_reduce_kernel(const float* ws, int splits, int N, int K, fl
 
 }  // namespace
 
-// Kernel selection (tests and experiments; -1 = read NVIT_GEMM_NT_IMPL / NVIT_GEMM_TN_IMPL on first use).
-// nt: 0 = always the 128x128 kernel, 1 = persistent kernels for large problems (default), 2 = persistent kernels
-// whatever the tile count.  tn: 0 = always the 128x128 kernel, 1 = persistent kernel for eligible shapes (default).
-static int g_nt_impl = -1, g_tn_impl = -1;
+// Kernel selection (tests).  nt: 0 = always the 128x128 kernel, 1 = persistent kernels for large problems (default),
+// 2 = persistent kernels whatever the tile count.  tn: 0 = always the 128x128 kernel, 1 = persistent kernel for
+// eligible shapes (default).  -1 = the default.
+static int g_nt_impl = 1, g_tn_impl = 1;
 extern "C" int nvit_set_gemm_impl(int nt_impl, int tn_impl) {
   NVIT_REQUIRE(nt_impl >= -1 && nt_impl <= 2 && tn_impl >= -1 && tn_impl <= 1, "set_gemm_impl: nt in -1..2, tn in -1..1");
-  g_nt_impl = nt_impl;
-  g_tn_impl = tn_impl;
+  g_nt_impl = nt_impl < 0 ? 1 : nt_impl;
+  g_tn_impl = tn_impl < 0 ? 1 : tn_impl;
   return NVIT_OK;
 }
 
@@ -395,27 +393,14 @@ extern "C" int nvit_gemm_nt(int dt, const void* A, int lda, const void* B, int l
   const double nt_bytes = (double)es * ((double)M * K + (double)N * K) +
                           (double)(out_dt == NVIT_F32 ? 4 : 2) * M * N * (accumulate ? 2.0 : 1.0);
   ProfScope ps(dt == NVIT_F32 ? NVIT_KID_GEMM_F32 : NVIT_KID_GEMM_NT, 2.0 * M * N * K, nt_bytes, s);
-  {
-    // large problems: persistent kernels (gemm_p.hip), 256x256 tiles when N allows, else 256x128.
-    // NVIT_GEMM_NT_IMPL=0 forces the 128x128 kernel, NVIT_GEMM_NT_TILE=128|256 forces a tile width.
-    static int force_tile = -1;
-    if (g_nt_impl < 0) {
-      const char* e = getenv("NVIT_GEMM_NT_IMPL");
-      g_nt_impl = e ? atoi(e) : 1;
-    }
-    if (force_tile < 0) {
-      const char* t = getenv("NVIT_GEMM_NT_TILE");
-      force_tile = t ? atoi(t) : 0;
-    }
-    const int impl = g_nt_impl;
-    if (impl >= 1) {  // 2: persistent kernel whatever the tile count (experiments)
-      const long long t256 = (long long)cdiv(M, 256) * cdiv(N, 256), t128 = (long long)cdiv(M, 256) * cdiv(N, 128);
-      int tile = 0;
-      if (N % 256 == 0 && (t256 >= 512 || impl == 2)) tile = 256;
-      else if (t128 >= 512 || impl == 2) tile = 128;
-      if (force_tile && tile) tile = force_tile;
-      if (tile) return nvit_gemm_nt_persistent_launch(dt, g, tile, s);
-    }
+  // large problems: persistent kernels (gemm_p.hip), 256x256 tiles when N allows, else 256x128
+  // (nvit_set_gemm_impl: 0 = the 128x128 kernel only, 2 = the persistent kernels whatever the tile count).
+  if (g_nt_impl >= 1) {
+    const long long t256 = (long long)cdiv(M, 256) * cdiv(N, 256), t128 = (long long)cdiv(M, 256) * cdiv(N, 128);
+    int tile = 0;
+    if (N % 256 == 0 && (t256 >= 512 || g_nt_impl == 2)) tile = 256;
+    else if (t128 >= 512 || g_nt_impl == 2) tile = 128;
+    if (tile) return nvit_gemm_nt_persistent_launch(dt, g, tile, s);
   }
   if (dt == NVIT_BF16)
     hipLaunchKernelGGL(gemm_nt_kernel<bf16>, dim3((unsigned)blocks), dim3(256), 0, s, g);
@@ -430,15 +415,8 @@ extern "C" int nvit_gemm_nt(int dt, const void* A, int lda, const void* B, int l
 // inside a captured hipGraph did not reliably re-zero the block on replay, and 55 tiny memsets per step were 0.26 ms.
 __device__ __attribute__((aligned(256))) float nvit_tn_zero_block[64];
 static const float* tn_zero_block() {
-  static const float* cache[16] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return nullptr;
-  if (!cache[dev]) {
-    void* p = nullptr;
-    if (hipGetSymbolAddress(&p, HIP_SYMBOL(nvit_tn_zero_block)) != hipSuccess) return nullptr;
-    cache[dev] = (const float*)p;
-  }
-  return cache[dev];
+  static void* cache[NVIT_MAX_DEVICES] = {};
+  return (const float*)nvit_symbol_address(HIP_SYMBOL(nvit_tn_zero_block), cache);
 }
 
 extern "C" int nvit_gemm_tn(int dt, const void* A, int lda, const void* B, int ldb, float* G, int ldg, int Mred,
@@ -478,11 +456,7 @@ extern "C" int nvit_gemm_tn(int dt, const void* A, int lda, const void* B, int l
   ProfScope ps(dt == NVIT_F32 ? NVIT_KID_GEMM_F32 : NVIT_KID_GEMM_TN, 2.0 * Mred * (double)N * K, tn_bytes, s);
   bool done = false;
   {
-    // big 256-aligned weight shapes: persistent 256x256 kernel (gemm_tn_p.hip); NVIT_GEMM_TN_IMPL=0 disables
-    if (g_tn_impl < 0) {
-      const char* e = getenv("NVIT_GEMM_TN_IMPL");
-      g_tn_impl = e ? atoi(e) : 1;
-    }
+    // big 256-aligned weight shapes: persistent 256x256 kernel (gemm_tn_p.hip); nvit_set_gemm_impl(.., 0) disables
     if (g_tn_impl == 1 && Mred >= 4096) {
       const int rc = nvit_gemm_tn_persistent_launch(dt, A, lda, B, ldb, ws, g.zeros, Mred, N, K,
                                                     splits, s);

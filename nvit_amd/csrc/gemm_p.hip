@@ -361,27 +361,13 @@ __global__ __launch_bounds__(512) void gemm_nt_persistent_kernel(NtArgs g, int t
 // a static device array owned by the library; consecutive launches rotate through the slots, and every launch leaves
 // its slot zeroed.
 __device__ unsigned nvit_sched_slots[64][16];
-int g_gemm_sched_dynamic = -1;  // -1: read NVIT_GEMM_SCHED on first use
+bool g_gemm_sched_dynamic = false;  // nvit_set_gemm_sched
 
 unsigned* sched_slot() {
-  static unsigned* base[16] = {};
+  static void* base[NVIT_MAX_DEVICES] = {};
   static unsigned next = 0;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return nullptr;
-  if (!base[dev]) {
-    void* p = nullptr;
-    if (hipGetSymbolAddress(&p, HIP_SYMBOL(nvit_sched_slots)) != hipSuccess) return nullptr;
-    base[dev] = (unsigned*)p;
-  }
-  return base[dev] + 16 * (next++ & 63);
-}
-
-bool sched_dynamic() {
-  if (g_gemm_sched_dynamic < 0) {
-    const char* e = getenv("NVIT_GEMM_SCHED");
-    g_gemm_sched_dynamic = (e && (e[0] == 'd' || e[0] == '1')) ? 1 : 0;
-  }
-  return g_gemm_sched_dynamic == 1;
+  unsigned* p = (unsigned*)nvit_symbol_address(HIP_SYMBOL(nvit_sched_slots), base);
+  return p ? p + 16 * (next++ & 63) : nullptr;
 }
 
 template <typename T, int FM, int EPI>
@@ -404,7 +390,7 @@ int launch_p2(const NtArgs& g_in, int n_cu, hipStream_t s) {
   g.tiles_n = cdiv(g.N, Cfg::PBN);
   const int tiles_m = cdiv(g.M, Cfg::PBM);
   const int nt = g.K / (ROWB / (int)sizeof(T));
-  unsigned* sched = (CAN_DYN && sched_dynamic() && nt >= Cfg::NSLOT + 4) ? sched_slot() : nullptr;
+  unsigned* sched = (CAN_DYN && g_gemm_sched_dynamic && nt >= Cfg::NSLOT + 4) ? sched_slot() : nullptr;
   if (sched)
     hipLaunchKernelGGL((gemm_nt_persistent_kernel<T, FM, EPI, CAN_DYN>), dim3(n_cu), dim3(512), LDS_BYTES, s, g, tiles_m,
                        tiles_m * g.tiles_n, sched);
@@ -418,30 +404,24 @@ int launch_p2(const NtArgs& g_in, int n_cu, hipStream_t s) {
 template <typename T, int FM>
 int launch_p(const NtArgs& g, int n_cu, hipStream_t s) {
   const int eo = g.out_dt == NVIT_F32 ? 4 : 8;  // output elements per 16-byte chunk
-  static const bool no_stage = getenv("NVIT_GEMM_DIRECT") != nullptr;  // experiments
-  const bool staged = (g.N % eo) == 0 && (g.ldc % eo) == 0 && !no_stage;
+  const bool staged = (g.N % eo) == 0 && (g.ldc % eo) == 0;
   if (!staged) return launch_p2<T, FM, 0>(g, n_cu, s);
   return g.out_dt == NVIT_F32 ? launch_p2<T, FM, 2>(g, n_cu, s) : launch_p2<T, FM, 1>(g, n_cu, s);
 }
 
 }  // namespace
 
+// persistent grid: the CU count rounded down to a multiple of 8 (whole XCDs); 0 when the query fails
 static int p_num_cu() {
-  static int n_cu = 0;
-  if (n_cu == 0) {
-    int devid = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&devid) != hipSuccess || hipGetDeviceProperties(&prop, devid) != hipSuccess) return 0;
-    n_cu = prop.multiProcessorCount;
-    n_cu -= n_cu % 8;
-    if (n_cu < 8) n_cu = 8;
-  }
-  return n_cu;
+  int n = nvit_num_cu();
+  if (n == 0) return 0;
+  n -= n % 8;
+  return n < 8 ? 8 : n;
 }
 
-// scheduling mode of the persistent NT GEMMs: 1 = dynamic tile hand-out (see the kernel comment), 0 = static
+// scheduling mode of the persistent NT GEMMs: 1 = dynamic tile hand-out (see the kernel comment), 0 = static (default)
 extern "C" int nvit_set_gemm_sched(int dynamic) {
-  g_gemm_sched_dynamic = dynamic ? 1 : 0;
+  g_gemm_sched_dynamic = dynamic != 0;
   return NVIT_OK;
 }
 
@@ -455,17 +435,8 @@ int nvit_gemm_nt_fused_launch(const NtArgs& g, int epi, hipStream_t s) {
 
 // tile_n: 128 or 256
 int nvit_gemm_nt_persistent_launch(int dt, const NtArgs& g, int tile_n, hipStream_t s) {
-  static int n_cu = 0;
-  if (n_cu == 0) {
-    int devid = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&devid) != hipSuccess || hipGetDeviceProperties(&prop, devid) != hipSuccess)
-      NVIT_FAIL(NVIT_EINVAL, "gemm_nt: cannot query device properties");
-    n_cu = prop.multiProcessorCount;
-    n_cu -= n_cu % 8;
-    if (n_cu < 8) n_cu = 8;
-    if (const char* e = getenv("NVIT_GEMM_CUS")) n_cu = atoi(e);  // experiments: restrict the persistent grid
-  }
+  const int n_cu = p_num_cu();
+  if (n_cu == 0) NVIT_FAIL(NVIT_EINVAL, "gemm_nt: cannot query device properties");
   if (dt == NVIT_BF16) return tile_n == 256 ? launch_p<bf16, 8>(g, n_cu, s) : launch_p<bf16, 4>(g, n_cu, s);
   return tile_n == 256 ? launch_p<float, 8>(g, n_cu, s) : launch_p<float, 4>(g, n_cu, s);
 }

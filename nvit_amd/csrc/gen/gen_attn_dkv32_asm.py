@@ -20,16 +20,15 @@ usage: python3 gen_attn_dkv32_asm.py > ../attn_dkv32_asm.inc
 import os
 
 PROBE = set(filter(None, os.environ.get("GEN_PROBE", "").split(",")))
-# placement options (results stay exact).  Product = ring4,spreadtr,earlyrows,prio: the first three -1.6 % kernel cycles
-# together against none of them (profiles/r04_dkv_cycles_ring4_spread.log), prio (s_setprio 1 for the tile loop: it
-# outranks a partner wave that is in its prologue / epilogue) another -1.8 % (profiles/r04_dkv_cycles_prio.log);
-# GEN_OPT=none builds without; vsched (one transcendental per MFMA gap): +-0
-OPT = set(filter(None, (os.environ.get("GEN_OPT") or "ring4,spreadtr,earlyrows,prio").split(","))) - {"none"}
+# Placement (results stay exact): a 4-slot ring whose fetch of tile t+2 is spread over steps 0..2 of tile t, the transposed
+# fragment reads spread behind the MFMA pairs of M2, the row fragments that only the ks0 products read requested early, and
+# s_setprio 1 for the tile loop (it outranks a partner wave that is in its prologue / epilogue).  The first three are
+# -1.6 % kernel cycles together against a 3-slot ring with none of them (profiles/r04_dkv_cycles_ring4_spread.log), the
+# priority another -1.8 % (profiles/r04_dkv_cycles_prio.log); one transcendental per MFMA gap measured +-0.  The losing
+# placements were removed.
 
 SLOT = 2 * 8192 + 512      # Q tile | dO tile | -lse[64] | -delta[64]   (= DKV_SLOT of attn_mfma.hip)
-RING4 = "ring4" in OPT     # 4-slot ring: the fetch of tile t+2 is spread over steps 0..2 of tile t (it may overwrite the slot of
-                           # tile t-2 before this tile's barrier), instead of bunched into step 3 behind the barrier
-NSLOT = 4 if RING4 else 3
+NSLOT = 4                  # ring: the fetch of tile t+2 may overwrite the slot of tile t-2 before this tile's barrier
 NDMA = 6                   # DMA wave-instructions per wave per tile
 
 OP = dict(qbase=0, gbase=1, lbase=2, dbase=3, kbase=4, vbase=5, nt=6, ldg=7, ring=8, nvalid_last=9, active=10, wofs=11,
@@ -139,23 +138,6 @@ def v_atoms(zbuf, pbuf):
     return res
 
 
-def v_sched(zbuf, pbuf):
-    """The same 24 instructions as v_atoms, as 16 per-gap lists for a 16-MFMA step (GEN_OPT=vsched): at most one
-    transcendental per gap (an MFMA leaves 8 of its 16 cycles of vector issue; v_exp_f32 takes 8, the others 4-5), the two
-    32-query halves' chains interleaved so that a gap pairs an exp with a multiply or a multiply with a pack; the last two
-    gaps stay empty (the next step's first MFMAs read the packs)."""
-    Z, P = V_Z + 16 * zbuf, V_P + 8 * pbuf
-    ex = lambda qq, r: f"v_exp_f32_e32 v{Z + qq * 4 + r}, v{Z + qq * 4 + r}"
-    mu = lambda qq, r: f"v_mul_f32_e32 v{Z + 8 + qq * 4 + r}, v{Z + qq * 4 + r}, v{Z + 8 + qq * 4 + r}"
-    cp = lambda qq, i: f"v_cvt_pk_bf16_f32 v{P + qq * 2 + i}, v{Z + qq * 4 + 2 * i}, v{Z + qq * 4 + 2 * i + 1}"
-    cs = lambda qq, i: f"v_cvt_pk_bf16_f32 v{P + 4 + qq * 2 + i}, v{Z + 8 + qq * 4 + 2 * i}, v{Z + 8 + qq * 4 + 2 * i + 1}"
-    g = [[ex(0, r)] for r in range(4)]
-    g += [[ex(1, r), mu(0, r)] for r in range(4)]
-    g += [[mu(1, 0), cp(0, 0)], [mu(1, 1), cp(0, 1)], [mu(1, 2), cs(0, 0)], [mu(1, 3), cs(0, 1)]]
-    g += [[cp(1, 0), cp(1, 1)], [cs(1, 0), cs(1, 1)], [], []]
-    return g
-
-
 def row_reads(s2):
     R = V_ROW
     res = []
@@ -213,10 +195,8 @@ def dma_atoms(last):
     # the two 256-byte rows of row constants: wave 0 fetches -lse, wave 1 -delta (the waits are vmcnt(0), so the waves need
     # not issue the same number of loads)
     uid = len(out) * 1000 + len(atoms) + (500 if last else 0)
-    sel_l = [f"s_bitcmp0_b32 s{S_WOFS}, 10", f"s_cbranch_scc0 .Lnol_{uid}_%="] if RING4 else \
-            [f"s_cmp_lg_u32 s{S_WOFS}, 0", f"s_cbranch_scc1 .Lnol_{uid}_%="]
-    sel_d = [f"s_bitcmp1_b32 s{S_WOFS}, 10", f"s_cbranch_scc0 .Lnod_{uid}_%="] if RING4 else \
-            [f"s_cmp_lg_u32 s{S_WOFS}, 1024", f"s_cbranch_scc1 .Lnod_{uid}_%="]
+    sel_l = [f"s_bitcmp0_b32 s{S_WOFS}, 10", f"s_cbranch_scc0 .Lnol_{uid}_%="]
+    sel_d = [f"s_bitcmp1_b32 s{S_WOFS}, 10", f"s_cbranch_scc0 .Lnod_{uid}_%="]
     atoms.append(sel_l + pre_l +
                  [f"s_add_u32 s{S_TMP}, s{S_SLOTD}, 16384", f"s_mov_b32 m0, s{S_TMP}", "s_nop 0",
                   f"global_load_lds_dword {vl}, s[{S_L}:{S_L + 1}]", f".Lnol_{uid}_%=:"])
@@ -286,13 +266,6 @@ def place(mf, va, after=None, dma=(), v_from=0, v_keep=3, dma_keep=0):
     over all gaps."""
     after = after or {}
     nm = max(len(mf), 1)
-    sched = None
-    if va and isinstance(va[0], list):     # per-gap schedule for 16 MFMAs (v_sched); fewer MFMAs: neighbouring gaps merged
-        if len(mf) == 16:
-            sched = va
-        elif len(mf) == 8:
-            sched = [va[2 * i] + va[2 * i + 1] for i in range(8)]
-        va = [] if sched else [x for gp in va for x in gp]
     if MFMA32:
         v_keep = 1
     nv = max(nm - v_from - v_keep, 1)     # the last v_keep gaps stay free: the next step's first MFMAs read what V packs
@@ -302,9 +275,6 @@ def place(mf, va, after=None, dma=(), v_from=0, v_keep=3, dma_keep=0):
         e(m)
         for ins in after.get(i, []):
             e(ins)
-        if sched:
-            for ins in sched[i]:
-                e(ins)
         if i >= v_from:
             want = min(len(va), (len(va) * (i - v_from + 1) + nv - 1) // nv)
             while vi < want:
@@ -335,7 +305,7 @@ def stamp_sums():
             f"s_sub_u32 s{S_TMP2}, s{S_SB + 4}, s{S_SB + 2}", f"s_add_u32 s{S_ACC_BAR}, s{S_ACC_BAR}, s{S_TMP2}"]
 
 
-def step(j, do_m1=True, do_m2=True, row_next=None, tr_this=None, dma=(), pre_rows=(), dma_after=None, sums=False):
+def step(j, do_m1=True, do_m2=True, row_next=None, tr_this=None, dma=(), pre_rows=(), sums=False):
     """Step j (0..3) of a tile: group (half = j // 2, key fragment f = j % 2).  Order inside a step: M2(g-1) first - its last
     MFMA frees the transposed fragments, whose successors are requested at once - then M1(g+1), behind whose last MFMA the
     next row fragments are requested; V(g) fills the gaps from the 4th MFMA on (its inputs come from the M1 products at the
@@ -345,7 +315,7 @@ def step(j, do_m1=True, do_m2=True, row_next=None, tr_this=None, dma=(), pre_row
     f = j % 2
     m1 = m1_atoms((j + 1) % 2, (j + 1) % 2) if (do_m1 and "nom1" not in PROBE) else []
     m2 = m2_atoms((j - 1) % 2, (j - 1) % 2) if (do_m2 and "nom2" not in PROBE) else []
-    va = [] if "novalu" in PROBE else (v_sched(j % 2, j % 2) if "vsched" in OPT else v_atoms(j % 2, j % 2))
+    va = [] if "novalu" in PROBE else v_atoms(j % 2, j % 2)
     nolds = "nolds" in PROBE
     mf = m2 + m1
     after = {}
@@ -361,13 +331,10 @@ def step(j, do_m1=True, do_m2=True, row_next=None, tr_this=None, dma=(), pre_row
                 e("s_waitcnt lgkmcnt(0)")
                 for ins in extra:
                     e(ins)
-        for k, atom in (dma_after or {}).items():
-            kk = min(k, len(mf) - 1) if mf else 0
-            after[kk] = after.get(kk, []) + list(atom)
         place(mf, va, after, dma, v_from=1)
         return
     k2 = len(m2) - 1
-    if tr_this is not None and not nolds and "spreadtr" in OPT and k2 == 7:
+    if tr_this is not None and not nolds and k2 == 7:
         # the transposed fragments of d-block df are free once M2's MFMA pair df has issued: request their successors there
         # instead of all 16 behind the last pair (same order, so the counted waits of the next step hold)
         rd = tr_reads(tr_this)
@@ -385,7 +352,7 @@ def step(j, do_m1=True, do_m2=True, row_next=None, tr_this=None, dma=(), pre_row
     blk = list(pre_rows)
     if row_next is not None and not nolds:
         rr = row_reads(row_next)
-        if "earlyrows" in OPT and not pre_rows and m1:
+        if not pre_rows and m1:
             # fragments that only the ks0 products read (a[qq][0], gg[qq][0], -lse, -delta) go out behind the 4th M1 MFMA
             early = [r for i, r in enumerate(rr) if i % 6 in (0, 2, 4, 5)]
             late = [r for i, r in enumerate(rr) if i % 6 in (1, 3)]
@@ -395,9 +362,6 @@ def step(j, do_m1=True, do_m2=True, row_next=None, tr_this=None, dma=(), pre_row
         else:
             blk += rr
     k1 = len(mf) - 1
-    for k, atom in (dma_after or {}).items():
-        kk = min(k, len(mf) - 1) if mf else 0
-        after[kk] = after.get(kk, []) + list(atom)
     if blk:
         if k1 >= 0:
             after[k1] = after.get(k1, []) + blk
@@ -430,18 +394,8 @@ def barrier_block(tag, inflight=0):
     return blk
 
 
-def second_half(variant):
-    atoms = [] if variant == "N" else dma_atoms(variant == "L")
-    e(f"; step 2 ({variant})")
-    # the barrier sits behind the last MFMA of step 2; the fetch of tile t+2 overwrites the slot of tile t-1, so it goes out
-    # behind it: all of it in the gaps of step 3
-    step(2, row_next=0, tr_this=1, pre_rows=barrier_block(variant))
-    e(f"; step 3 ({variant})")
-    step(3, dma=atoms, sums=True)
-
-
-def tile_ring4(variant):
-    """One whole tile with the 4-slot ring: the fetch of tile t+2 (variant F: a full tile, L: the ragged last one, N: none left)
+def tile(variant):
+    """One whole tile: the fetch of tile t+2 (variant F: a full tile, L: the ragged last one, N: none left)
     goes out over steps 0..2 - ahead of this tile's barrier: its slot is that of tile t-2 - and the barrier waits for all but
     those NDMA_WAVE operations."""
     atoms = [] if variant == "N" else dma_atoms(variant == "L")
@@ -457,7 +411,7 @@ def tile_ring4(variant):
     step(3, sums=True)
 
 
-NDMA_WAVE = 5   # vector-memory operations per wave per tile with ring4 (4 x 1 KiB of Q / dO + one row-constant load)
+NDMA_WAVE = 5   # vector-memory operations per wave per tile (4 x 1 KiB of Q / dO + one row-constant load)
 
 
 def emit():
@@ -519,49 +473,24 @@ def emit():
     e("s_waitcnt lgkmcnt(0)")
     for m in m1_atoms(0, 0):
         e(m)
-    if "prio" in OPT:
-        e("s_setprio 1")       # the tile loop outranks a partner wave that is in its prologue / epilogue
+    e("s_setprio 1")           # the tile loop outranks a partner wave that is in its prologue / epilogue
     e(f"s_add_u32 s{S_TMP}, s{S_T}, 1")
     e(f"s_cmp_lt_u32 s{S_TMP}, s{S_NT}")
     e("s_cbranch_scc0 .Llast_tile_%=")
     e(".Ltile_loop_%=:")
-    if RING4:
-        e(f"s_cmp_lt_u32 s{S_TD}, s{S_NT}")
-        e("s_cbranch_scc0 .Lt_none_%=")
-        e(f"s_add_u32 s{S_TMP2}, s{S_TD}, 1")
-        e(f"s_cmp_eq_u32 s{S_TMP2}, s{S_NT}")
-        e("s_cbranch_scc1 .Lt_last_%=")
-        tile_ring4("F")
-        e("s_branch .Lh2_done_%=")
-        e(".Lt_last_%=:")
-        tile_ring4("L")
-        e("s_branch .Lh2_done_%=")
-        e(".Lt_none_%=:")
-        tile_ring4("N")
-        e(".Lh2_done_%=:")
-    else:
-        e("; step 0")
-        step(0, row_next=1, tr_this=0)
-        e("; step 1")
-        step(1)
-    if RING4:
-        pass
-    elif "nodma" in PROBE:
-        second_half("N")
-    else:
-        e(f"s_cmp_lt_u32 s{S_TD}, s{S_NT}")
-        e("s_cbranch_scc0 .Lh2_none_%=")
-        e(f"s_add_u32 s{S_TMP2}, s{S_TD}, 1")
-        e(f"s_cmp_eq_u32 s{S_TMP2}, s{S_NT}")
-        e("s_cbranch_scc1 .Lh2_last_%=")
-        second_half("F")
-        e("s_branch .Lh2_done_%=")
-        e(".Lh2_last_%=:")
-        second_half("L")
-        e("s_branch .Lh2_done_%=")
-        e(".Lh2_none_%=:")
-        second_half("N")
-        e(".Lh2_done_%=:")
+    e(f"s_cmp_lt_u32 s{S_TD}, s{S_NT}")
+    e("s_cbranch_scc0 .Lt_none_%=")
+    e(f"s_add_u32 s{S_TMP2}, s{S_TD}, 1")
+    e(f"s_cmp_eq_u32 s{S_TMP2}, s{S_NT}")
+    e("s_cbranch_scc1 .Lt_last_%=")
+    tile("F")
+    e("s_branch .Lh2_done_%=")
+    e(".Lt_last_%=:")
+    tile("L")
+    e("s_branch .Lh2_done_%=")
+    e(".Lt_none_%=:")
+    tile("N")
+    e(".Lh2_done_%=:")
     e(f"s_mov_b32 s{S_SLOTT}, s{S_SLOTC}")        # the next tile's transposed fragments come from the slot just switched to
     e(f"s_add_u32 s{S_T}, s{S_T}, 1")
     e(f"s_add_u32 s{S_TMP}, s{S_T}, 1")
@@ -584,8 +513,7 @@ def emit():
     for m in m2_atoms(1, 1):
         e(m)
     e(".Ldrained_%=:")
-    if "prio" in OPT:
-        e("s_setprio 0")
+    e("s_setprio 0")
     stamp(3)
     e("s_nop 15")
     e("s_nop 15")

@@ -755,13 +755,8 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const float* dout, con
 }
 
 int row_grid(int M) {
-  static int cap = 0;
-  if (cap == 0) {
-    const char* e = getenv("NVIT_ROW_GRID");   // experiments
-    cap = e ? atoi(e) : 2048;
-  }
-  int blocks = cdiv(M, ROW_WAVES);
-  return blocks > cap ? cap : blocks;
+  const int blocks = cdiv(M, ROW_WAVES);
+  return blocks > 2048 ? 2048 : blocks;
 }
 
 }  // namespace
@@ -804,11 +799,9 @@ extern "C" int nvit_lerp_fwd(int dt, const float* h, const void* y, int y_dt, co
 // SIMD): a second, one-third-full round (row kernels 14.9 -> 13.1 ms per Base step with the resident count).
 template <typename K>
 static int resident_blocks(K kernel) {
-  int dev = 0, per_cu = 0;
-  hipDeviceProp_t prop;
-  if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 0;
+  int per_cu = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, 0) != hipSuccess || per_cu < 1) return 0;
-  return per_cu * prop.multiProcessorCount;
+  return per_cu * nvit_num_cu();
 }
 
 extern "C" int nvit_lerp_bwd_blocks(int dt, int y_dt, int C, int has_add, int has_skip, int accum) {

@@ -21,7 +21,7 @@ from __future__ import annotations
 
 import math
 import os
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, Optional, Tuple
 
 import torch
 from torch import nn
@@ -96,36 +96,18 @@ class _Runtime:
         self.items = 0
         self.btable = None
         self.bitems = 0
-        # weight-gradient GEMMs run on a side HIP stream so that the HBM-bound row kernels of the data-gradient
-        # chain (lerp / SwiGLU backward) overlap them instead of queueing behind them (NVIT_SIDE_STREAM=0 disables)
-        self.use_side = os.environ.get("NVIT_SIDE_STREAM", "0") == "1"  # measured: no gain (the persistent GEMMs fill registers + LDS)
-        self.side = None
-        self._keep: List[Tensor] = []
         # bf16 mode: the two data-gradient GEMMs that used to accumulate into the fp32 residual-stream gradient (c_fc
         # and q/k/v) store bf16 once and the next lerp_bwd adds it while it reads its incoming gradient anyway
         # (nvit_lerp_bwd dout_add).  `carry` hands the q/k/v addend to the backward of the PREVIOUS block of the chain
         # built by ViT.forward: (index of the consumer, tensor); -1 = the cross-attention block.
-        self.lo_dgrad = os.environ.get("NVIT_LO_DGRAD", "1") == "1"
         self.carry = None
 
-    def on_side(self, fn, *keep):
-        """Run fn() (kernel launches only; outputs must be pre-allocated by the caller) on the side stream,
-        ordered after everything enqueued so far on the current stream.  `keep`: tensors the side work reads,
-        held until join() so the caching allocator cannot hand their memory to later main-stream kernels."""
-        if not self.use_side:
-            return fn()
-        if self.side is None:
-            self.side = torch.cuda.Stream()
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream())
-        self.side.wait_event(ev)
-        self._keep.extend(keep)
-        with torch.cuda.stream(self.side):
-            return fn()
-
     def y_dtype(self) -> torch.dtype:
-        """Storage type of the branch outputs y (att_c_proj / mlp_c_proj / out_proj results, the second LERP input)."""
-        return torch.bfloat16 if (self.dt != F32 and self.model.y_bf16) else torch.float32
+        """Storage type of the branch outputs y (att_c_proj / mlp_c_proj / out_proj results, the second LERP input).
+        bf16 mode stores them in bf16, as the reference's own autocast path does (every nn.Linear returns
+        bf16).  y only enters the stream through lam * (nrm(y) - nrm(h)) with lam ~ 0.05, so its rounding adds ~5e-6 rms
+        to a stream error of ~2e-5; the matched CPU emulation rounds y at the same point."""
+        return torch.bfloat16 if self.dt != F32 else torch.float32
 
     def grad_buf(self, params, shape) -> Tensor:
         """Destination of a parameter gradient: the data-parallel wrapper's flat bucket slice when it offers one
@@ -137,13 +119,6 @@ class _Runtime:
             if t is not None:
                 return t
         return torch.empty(shape, device=params[0].device, dtype=torch.float32)
-
-    def join(self) -> None:
-        if self.use_side and self.side is not None:
-            ev = torch.cuda.Event()
-            ev.record(self.side)
-            torch.cuda.current_stream().wait_event(ev)
-        self._keep.clear()
 
     def _build(self, device, dt: int) -> None:
         m, cfg = self.model, self.model.config
@@ -276,7 +251,7 @@ def _take_carry(rt: "_Runtime", idx: int, chained: bool, dout: Tensor):
     only valid for the very gradient tensor that node returned: anything else (a hook that replaced the gradient, a second
     consumer whose gradient autograd summed in) would silently drop or misplace it, so it is checked, not assumed.
 
-    RESTRICTION of the chained bf16 mode (NVIT_LO_DGRAD=1, the default): the gradient a chained block's backward RETURNS
+    RESTRICTION of the chained bf16 mode: the gradient a chained block's backward RETURNS
     for its input lacks the q/k/v data-gradient part, which travels through `rt.carry` to the next backward node of
     ViT.forward's chain.  A tensor hook on a block input inside ViT.forward, or `autograd.grad` that stops at one, sees
     that incomplete gradient; an early stop leaves the addend dangling, which the NEXT forward reports (it raises).
@@ -377,7 +352,7 @@ class _BlockFn(torch.autograd.Function):
         if dxn is None:
             return (None,) * 24
         dxn = dxn.contiguous()
-        lo_dgrad = rt.lo_dgrad and dt != F32
+        lo_dgrad = dt != F32
         red = ops.ReduceBatch()   # the block's six parameter-gradient reductions go out as one launch at the end
         dxn, carry_in = _take_carry(rt, idx, ctx.chained, dxn)   # q/k/v data gradient of the block after this one (bf16), or None
         # ---- MLP half + norm_skip
@@ -399,7 +374,7 @@ class _BlockFn(torch.autograd.Function):
             dxm = ops.gemm_nt(dy2_lo, sh[pre + "p.Wt"], M, 4 * C, C, out_dtype=td)
             duv, part_suv = ops.swiglu_bwd(dt, dxm, uv, suv, gscale, M, 4 * C)
         g_wp = rt.grad_buf((p_wp,), (C, 4 * C))
-        rt.on_side(lambda: ops.gemm_tn(dy2_lo, xm, g_wp, M, C, 4 * C), dy2_lo, xm)
+        ops.gemm_tn(dy2_lo, xm, g_wp, M, C, 4 * C)
         g_bp = _bias_grad(dy2_lo, M, C) if ctx.has_b else None
         d_suv = _param_grad_scaled(rt, part_suv, p_suv, 1.0, red)
         if lo_dgrad:
@@ -408,7 +383,7 @@ class _BlockFn(torch.autograd.Function):
             dh1_add = None
             ops.gemm_nt(duv, sh[pre + "fc.Wt"], M, C, 8 * C, out=dh1, accumulate=True)
         g_wfc = rt.grad_buf((p_wfc,), (8 * C, C))
-        rt.on_side(lambda: ops.gemm_tn(duv, h1_lo, g_wfc, M, 8 * C, C, perm=1), duv, h1_lo)
+        ops.gemm_tn(duv, h1_lo, g_wfc, M, 8 * C, C, perm=1)
         g_bfc = _bias_grad(duv, M, 8 * C, perm=1) if ctx.has_b else None
         # ---- attention half
         if dx is None:
@@ -420,7 +395,7 @@ class _BlockFn(torch.autograd.Function):
         d_attn_alpha = _param_grad_alpha(rt, part_lam, p_aalpha, c_a, red)
         do = ops.gemm_nt(dy_lo, sh[pre + "o.Wt"], M, C, C, out_dtype=td)
         g_wo = rt.grad_buf((p_wo,), (C, C))
-        rt.on_side(lambda: ops.gemm_tn(dy_lo, o, g_wo, M, C, C), dy_lo, o)
+        ops.gemm_tn(dy_lo, o, g_wo, M, C, C)
         g_bo = _bias_grad(dy_lo, M, C) if ctx.has_b else None
         dqkv = torch.empty((M, 3 * C), device=x.device, dtype=td)
         if impl == 1 and d == 64 and dt != F32:
@@ -440,10 +415,9 @@ class _BlockFn(torch.autograd.Function):
         else:
             ops.gemm_nt(dqkv, sh[pre + "qkv.Wt"], M, C, 3 * C, out=dx, accumulate=True)
         g_qkv = rt.grad_buf((p_wq, p_wk, p_wv), (3 * C, C))   # one stacked GEMM output = three adjacent bucket slices
-        rt.on_side(lambda: ops.gemm_tn(dqkv, x_lo, g_qkv, M, 3 * C, C), dqkv, x_lo)
+        ops.gemm_tn(dqkv, x_lo, g_qkv, M, 3 * C, C)
         g_bqkv = _bias_grad(dqkv, M, 3 * C) if ctx.has_b else None
         red.flush()
-        rt.join()
         gq, gk, gv = g_qkv[:C], g_qkv[C:2 * C], g_qkv[2 * C:]
         if ctx.has_b:
             gbq, gbk, gbv = g_bqkv[:C], g_bqkv[C:2 * C], g_bqkv[2 * C:]
@@ -894,12 +868,6 @@ class ViT(nn.Module):
         self._init_parameters()
         # runtime (not part of the state_dict)
         self.precision = os.environ.get("NVIT_PRECISION", "bf16")
-        self.attn_impl = os.environ.get("NVIT_ATTN_IMPL", "auto")
-        # bf16 mode: store the branch outputs y (the nn.Linear results that enter the LERP) in bf16, as the reference's own
-        # autocast path does (every nn.Linear returns bf16).  y only enters the stream through
-        # lam * (nrm(y) - nrm(h)) with lam ~ 0.05, so its rounding adds ~5e-6 rms to a stream error of ~2e-5.
-        # (default since round 3: -0.4..1 ms per Base step, and the matched CPU emulation rounds y at the same point)
-        self.y_bf16 = os.environ.get("NVIT_Y_BF16", "1") == "1"
         object.__setattr__(self, "_rt", _Runtime(self))
         object.__setattr__(self, "_node_sync", None)   # set by DataParallel: averages SOM nodes across ranks
         object.__setattr__(self, "_taps", None)        # tests: dict that receives the residual stream after each block
@@ -939,10 +907,9 @@ class ViT(nn.Module):
         return self
 
     def _attn_impl(self) -> int:
-        if self.attn_impl == "auto":  # MFMA flash kernels: bf16, head dim 64; otherwise the scalar-FMA kernels
-            d = self.config.n_embd // self.config.n_head
-            return 1 if (self.precision == "bf16" and d == 64) else 0
-        return int(self.attn_impl)
+        """1: the MFMA flash kernels (bf16, head dim 64); 0: the scalar-FMA kernels."""
+        d = self.config.n_embd // self.config.n_head
+        return 1 if (self.precision == "bf16" and d == 64) else 0
 
     def _prepare(self, device) -> None:
         if device.type != "cuda":
@@ -1044,8 +1011,8 @@ class ViT(nn.Module):
             # up to a block input, an exception inside backward): the gradients it did return were incomplete
             rt.carry = None
             raise RuntimeError("nvit_amd: the previous backward through ViT.forward stopped inside the block chain; in the "
-                               "chained bf16 mode (NVIT_LO_DGRAD=1) gradients at block inputs are incomplete there - set "
-                               "NVIT_LO_DGRAD=0 to differentiate up to an intermediate block input")
+                               "chained bf16 mode gradients at block inputs are incomplete there - use the fp32 mode to "
+                               "differentiate up to an intermediate block input")
         cfg = self.config
         B = img.shape[0]
         T, C = self.n_tokens, cfg.n_embd

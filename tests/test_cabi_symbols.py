@@ -89,6 +89,23 @@ def test_product_sources_carry_no_probe_switches():
     mk = open(os.path.join(csrc, "Makefile")).read()
     listed = set(re.search(r"^SRCS\s*=\s*(.*)$", mk, re.M).group(1).split())
     assert listed == {os.path.basename(f) for f in glob.glob(os.path.join(csrc, "*.hip"))}
+    # Run-time switches: a selection between a measured winner and a losing variant is not left to the environment (the
+    # losing path goes with the option).  What remains read is listed here; every line that touches the environment must
+    # name its variable literally.
+    def env_reads(paths, pattern):
+        names = set()
+        for f in paths:
+            for ln in open(f):
+                if re.search(r"\bgetenv\b|\benviron\b", ln):
+                    found = re.findall(pattern, ln)
+                    assert found, (f, ln)
+                    names.update(found)
+        return names
+    assert env_reads(files, r'\bgetenv\s*\(\s*"(\w+)"\s*\)') == {"NVIT_XGMI_BLOCKS"}
+    py_env = r'\benviron(?:\.get\s*\(|\s*\[)\s*["\'](\w+)["\']'
+    assert env_reads(glob.glob(os.path.join(root, "nvit_amd", "*.py")), py_env) == \
+        {"NVIT_LIB", "NVIT_PRECISION", "NVIT_GEMM_SCHED", "NVIT_XGMI_TIMEOUT_S"}
+    assert env_reads(glob.glob(os.path.join(csrc, "gen", "*.py")), py_env) == {"GEN_PROBE"}
 
 
 def test_generated_attention_loop_is_reproducible_and_barrier_balanced():
@@ -99,7 +116,7 @@ def test_generated_attention_loop_is_reproducible_and_barrier_balanced():
     issues the expected number of MFMAs."""
     import importlib.util, subprocess, sys
     csrc = os.path.join(ROOT, "nvit_amd", "csrc")
-    env = {k: v for k, v in os.environ.items() if k not in ("GEN_PROBE", "GEN_OPT")}
+    env = {k: v for k, v in os.environ.items() if k != "GEN_PROBE"}
     out = subprocess.run([sys.executable, os.path.join(csrc, "gen", "gen_attn_dkv32_asm.py")], capture_output=True, text=True,
                          env=env, check=True).stdout
     assert out == open(os.path.join(csrc, "attn_dkv32_asm.inc")).read(), "attn_dkv32_asm.inc is stale: make -C nvit_amd/csrc gen"

@@ -6,8 +6,7 @@ from nvit_amd import ops
 from gemm_bench import bench  # noqa
 
 dev = "cuda:0"
-import os
-CUS = int(os.environ.get("NVIT_GEMM_CUS", "256"))
+CUS = torch.cuda.get_device_properties(dev).multi_processor_count // 8 * 8   # the persistent grid
 TPC = int(os.environ.get("TILES_PER_CU", "3"))
 M, N = 256 * CUS * TPC // 3, 768
 for K in (256, 512, 768, 1536, 3072, 6144):

@@ -2,9 +2,9 @@
 """Control-flow interpreter for the generated attention-backward loops: runs the scalar instructions that steer branches
 (s_mov / s_add / s_sub / s_lshl / s_cmp_* / s_bitcmp* / s_cselect / s_cbranch_scc* / s_branch) of one wave with given
 operands and counts what it executes - s_barrier above all: every wave of a workgroup must execute the same number of
-barriers whatever its role (computing wave, wave without keys, half without a work item, first / second half), or the
-workgroup hangs.  Everything else (vector, LDS, memory instructions) is counted, not executed.
-    python3 tools/probes/asm_barrier_sim.py nvit_amd/csrc/attn_dkv_pp_asm.inc"""
+barriers whatever its role (computing wave, wave without keys), or the workgroup hangs.  Everything else (vector, LDS,
+memory instructions) is counted, not executed.
+    python3 tools/probes/asm_barrier_sim.py nvit_amd/csrc/attn_dkv32_asm.inc"""
 import re, sys, itertools
 
 
@@ -85,20 +85,19 @@ def run(ins, ops, limit=2_000_000):
 
 if __name__ == "__main__":
     ins = load(sys.argv[1])
-    pp = "pp" in sys.argv[1]
     bad = 0
     for T in (16, 49, 64, 65, 96, 128, 200, 784, 832):
         nt = (T + 63) // 64
         nvl = T - (nt - 1) * 64
         res = {}
-        roles = [(a, h, w) for a in ((3, 2, 0) if pp else (1, 0)) for h in ((0, 1) if pp else (0,)) for w in range(4)]
-        for act, half, w in roles:
-            ops = {6: nt, 9: nvl, 10: act | (half << 2), 11: w * 1024, 8: 0x10000 * half, 7: 1536}
-            res[(act, half, w)] = run(ins, ops)
+        for act in (1, 0):
+            for w in range(4):
+                ops = {6: nt, 9: nvl, 10: act, 11: w * 1024, 8: 0, 7: 1536}
+                res[(act, w)] = run(ins, ops)
         bars = {k: v["s_barrier"] for k, v in res.items()}
         ok = len(set(bars.values())) == 1
         bad += not ok
-        k0 = (3, 0, 0) if pp else (1, 0, 0)
+        k0 = (1, 0)
         print(f"T={T:4d} nt={nt:2d} nvalid_last={nvl:2d}: barriers {sorted(set(bars.values()))} {'OK' if ok else 'MISMATCH ' + str(bars)}; "
               f"computing wave: {res[k0]['mfma']} MFMA, {res[k0]['dma']} DMA, {res[k0]['ds_read']} LDS reads")
     sys.exit(1 if bad else 0)

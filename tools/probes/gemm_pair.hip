@@ -212,7 +212,6 @@ int pair_num_cu() {
     n_cu = prop.multiProcessorCount;
     n_cu -= n_cu % 8;
     if (n_cu < 8) n_cu = 8;
-    if (const char* e = getenv("NVIT_GEMM_CUS")) n_cu = atoi(e);  // experiments: restrict the persistent grid
   }
   return n_cu;
 }

@@ -1,5 +1,5 @@
 """LERP row kernels at the benchmarked shape (M = 100 352 rows of C = 768 fp32): HIP-event times and algorithmic TB/s.
-Grid sizes come from NVIT_ROW_GRID (forward) / NVIT_PART_BLOCKS (backward) when set.  python tools/rowops_bench.py"""
+python tools/rowops_bench.py"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -35,7 +35,6 @@ cases = [
     ("bwd MLP half  (addend + norm_skip) ", lambda: ops.lerp_bwd(BF16, dout, h, yb, alpha, 1.6, xs, skip, None, False, False, True, dout_add=add), 4 + 2 + 4 + 2 + 4 + 4 + 4 + 2),
     ("bwd attn half (addend + accumulate)", lambda: ops.lerp_bwd(BF16, dout, h, yb, alpha, 1.6, None, None, dh, True, False, True, dout_add=add), 4 + 2 + 4 + 2 + 4 + 4 + 2),
 ]
-print(f"NVIT_ROW_GRID={os.environ.get('NVIT_ROW_GRID', '-')} NVIT_PART_BLOCKS={os.environ.get('NVIT_PART_BLOCKS', '-')}")
 for name, fn, bpe in cases:
     us = min(t_of(fn) for _ in range(3))
     print(f"  {name}: {us:7.1f} us  {M * C * bpe / us / 1e6:6.2f} TB/s ({bpe} B/element)")

@@ -1,10 +1,10 @@
 """How much does a co-running kernel that pins a few CUs (what an RCCL all-reduce does during the data-parallel
-backward) delay the persistent GEMMs, with static vs dynamic tile scheduling?  Run once per NVIT_GEMM_SCHED value.
+backward) delay the persistent GEMMs, with static vs dynamic tile scheduling?  Runs both (nvit_set_gemm_sched).
 The hog is a torch kernel is not controllable enough, so it is a tiny HIP module compiled at run time with hipcc."""
 import ctypes, os, subprocess, sys, tempfile, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from nvit_amd import ops
+from nvit_amd import _lib, ops
 
 SRC = r'''
 #include <hip/hip_runtime.h>
@@ -52,12 +52,15 @@ def run(hog_wgs, hog_us, n=300, every=6):
     return dt / n * 1e6
 
 
-for _ in range(2):
-    run(0, 0, 50)
-base = run(0, 0)
-print(f"sched={os.environ.get('NVIT_GEMM_SCHED', 'static')}: no interference {base:.1f} us/GEMM", flush=True)
-for wgs, us in ((16, 300), (32, 300), (64, 300)):
-    t = run(wgs, us)
-    # the hog holds wgs CUs for `us` out of every 6 GEMMs: ideal cost = its share of the machine
-    ideal = base * (1 + (wgs / 256) * us / (6 * base))
-    print(f"   hog {wgs} CUs x {us} us every 6 GEMMs: {t:.1f} us/GEMM (+{(t / base - 1) * 100:.1f} %; share-of-machine ideal +{(ideal / base - 1) * 100:.1f} %)", flush=True)
+for dynamic, name in ((0, "static"), (1, "dynamic")):
+    _lib.load().nvit_set_gemm_sched(dynamic)
+    for _ in range(2):
+        run(0, 0, 50)
+    base = run(0, 0)
+    print(f"sched={name}: no interference {base:.1f} us/GEMM", flush=True)
+    for wgs, us in ((16, 300), (32, 300), (64, 300)):
+        t = run(wgs, us)
+        # the hog holds wgs CUs for `us` out of every 6 GEMMs: ideal cost = its share of the machine
+        ideal = base * (1 + (wgs / 256) * us / (6 * base))
+        print(f"   hog {wgs} CUs x {us} us every 6 GEMMs: {t:.1f} us/GEMM (+{(t / base - 1) * 100:.1f} %; share-of-machine ideal +{(ideal / base - 1) * 100:.1f} %)", flush=True)
+_lib.load().nvit_set_gemm_sched(0)
