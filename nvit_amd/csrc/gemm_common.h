@@ -247,6 +247,11 @@ __device__ __forceinline__ void nt_store_tile_staged(const NtArgs& g, f32x4 (&ac
           if (g.bias) v += *reinterpret_cast<const f32x4*>(g.bias + nb);
           if (g.colscale) v *= *reinterpret_cast<const f32x4*>(g.colscale + nb);
           if (radd) v += *reinterpret_cast<const f32x4*>(radd + nb);
+          // bf16 "+=": the old value joins the fp32 sum before the one rounding to bf16 (the header's contract, as in
+          // nt_store_tile); adding it after the scratch round trip would round the product first and the sum again
+          if constexpr (EO == 2) {
+            if (g.accumulate && mfrag < g.M) v += load4<bf16>(reinterpret_cast<const bf16*>(g.C) + (size_t)mfrag * g.ldc + nb);
+          }
         }
         const int bytecol = (jj * 16 + 4 * lg) * EO;
         const int chunk = bytecol >> 4;
@@ -270,21 +275,12 @@ __device__ __forceinline__ void nt_store_tile_staged(const NtArgs& g, f32x4 (&ac
         }
         if (m < g.M && n < g.N) {
           TO* cp = reinterpret_cast<TO*>(g.C) + (size_t)m * g.ldc + n;
-          if (g.accumulate) {
-            if constexpr (EO == 4) {
-              f32x4 v = __builtin_bit_cast(f32x4, raw);
-              v += __builtin_bit_cast(f32x4, oldv);
-              st16_nt(cp, __builtin_bit_cast(uint4, v));
-            } else {
-              const bf16x8 nv = __builtin_bit_cast(bf16x8, raw);
-              const bf16x8 ov = __builtin_bit_cast(bf16x8, ld16_nt(cp));
-              bf16x8 r;
-#pragma unroll
-              for (int e = 0; e < 8; ++e) r[e] = (bf16)((float)nv[e] + (float)ov[e]);
-              st16_nt(cp, __builtin_bit_cast(uint4, r));
-            }
+          if (EO == 4 && g.accumulate) {
+            f32x4 v = __builtin_bit_cast(f32x4, raw);
+            v += __builtin_bit_cast(f32x4, oldv);
+            st16_nt(cp, __builtin_bit_cast(uint4, v));
           } else {
-            st16_nt(cp, raw);
+            st16_nt(cp, raw);   // (bf16 "+=": the old value is already in)
           }
         }
       }

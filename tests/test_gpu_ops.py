@@ -10,6 +10,8 @@ pytestmark = pytest.mark.gpu
 
 from oracle import nvit_oracle as O
 
+import gemm_check as gc
+
 
 def dev():
     return torch.device("cuda:0")
@@ -39,19 +41,45 @@ def test_gemm_nt(dtype, M, N, K):
     cs = rnd(N, seed=4)
     period = 7
     radd = rnd(period, N, seed=5)
+    rows = gc.sample_rows(M)
+    ridx = torch.arange(M) if rows is None else rows
+
+    def bounded(out, ref, mag, what):
+        # besides the old tolerance: the fp32-accumulation bound against an fp64 reference of the same (rounded) operands
+        got = out.cpu()[ridx]
+        return gc.check_gauss(got, ref, mag, K, f"test_gemm_nt {what} {dtype} M{M} N{N} K{K}")
+
     ref = (A.float() @ B.float().t() + bias) * cs + radd[torch.arange(M) % period]
     out = ops.gemm_nt(A.to(dev()), B.to(dev()), M, N, K, bias=bias.to(dev()), colscale=cs.to(dev()),
                       rowadd=radd.to(dev()), rowadd_period=period)
     err = (out.cpu() - ref).abs().max().item()
     assert err < TOL[dtype] * math.sqrt(K) * 4, err
-    # accumulate + bf16 output
+    bounded(out, *gc.nt_ref(A, B, rows, bias, cs, radd, period), "epilogue")
+    # accumulate (fp32 output)
     base = rnd(M, N, seed=6)
     out2 = base.to(dev()).clone()
     ops.gemm_nt(A.to(dev()), B.to(dev()), M, N, K, out=out2, accumulate=True)
     ref2 = A.float() @ B.float().t() + base
     assert (out2.cpu() - ref2).abs().max().item() < TOL[dtype] * math.sqrt(K) * 4
+    bounded(out2, *gc.nt_ref(A, B, rows, old=base[ridx]), "+=")
     out3 = ops.gemm_nt(A.to(dev()), B.to(dev()), M, N, K, out_dtype=torch.bfloat16)
     assert (out3.float().cpu() - A.float() @ B.float().t()).abs().max().item() < 0.02 * math.sqrt(K) * 4
+    bounded(out3, *gc.nt_ref(A, B, rows), "bf16 out")
+    # exact data at the same shape: bit-exact results
+    d = gc.nt_exact(M, N, K, seed=7, bias=True, colscale=True, period=period, old_amax=64)
+    Ae, Be = d["A"].to(dtype), d["B"].to(dtype)
+    Ad, Bd = Ae.to(dev()), Be.to(dev())
+    ev = [d[k].to(dev()) for k in ("bias", "colscale", "rowadd")]
+    out = ops.gemm_nt(Ad, Bd, M, N, K, bias=ev[0], colscale=ev[1], rowadd=ev[2], rowadd_period=period)
+    gc.assert_exact(out.cpu()[ridx], gc.nt_ref(Ae, Be, rows, d["bias"], d["colscale"], d["rowadd"], period)[0],
+                    "exact epilogue")
+    old = gc.int_data((M, N), 64, seed=8)
+    for odt in (torch.float32, torch.bfloat16):
+        out2 = old.to(odt).to(dev()).clone()
+        ops.gemm_nt(Ad, Bd, M, N, K, out=out2, accumulate=True)
+        gc.assert_exact(out2.cpu()[ridx], gc.nt_ref(Ae, Be, rows, old=old[ridx])[0], f"exact += {odt}")
+    out3 = ops.gemm_nt(Ad, Bd, M, N, K, out_dtype=torch.bfloat16)
+    gc.assert_exact(out3.cpu()[ridx], gc.nt_ref(Ae, Be, rows)[0], "exact bf16 out")
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
@@ -69,12 +97,27 @@ def test_gemm_tn(dtype, Mred, N, K, perm):
         full = torch.zeros_like(ref)
         full[idx] = ref
         ref = full
+    k_eff = Mred + ops.tn_splits(Mred, N, K, 0 if dtype == torch.float32 else 1)
+    what = f"test_gemm_tn {dtype} Mred{Mred} N{N} K{K} perm{perm}"
     G = torch.full((N, K), 7.0, device=dev())
     ops.gemm_tn(A.to(dev()), B.to(dev()), G, Mred, N, K, perm=perm)
     tol = TOL[dtype] * math.sqrt(Mred) * 4
     assert (G.cpu() - ref).abs().max().item() < tol
+    G1 = G.cpu().clone()
+    gc.check_gauss(G1, *gc.tn_ref(A, B, Mred, perm), k_eff, what)
     ops.gemm_tn(A.to(dev()), B.to(dev()), G, Mred, N, K, perm=perm, accumulate=True)
     assert (G.cpu() - 2 * ref).abs().max().item() < 2 * tol
+    # (the "+=" adds the kernel's own first result: the reference adds exactly that)
+    gc.check_gauss(G.cpu(), *gc.tn_ref(A, B, Mred, perm, old=G1), k_eff, what + " +=")
+    # exact data at the same shape: bit-exact, plain and accumulated
+    d = gc.tn_exact(Mred, N, K, seed=3, old_amax=Mred * 16)
+    Ae, Be = d["A"].to(dtype), d["B"].to(dtype)
+    G = torch.full((N, K), 7.0, device=dev())
+    ops.gemm_tn(Ae.to(dev()), Be.to(dev()), G, Mred, N, K, perm=perm)
+    refe = gc.tn_ref(Ae, Be, Mred, perm)[0]
+    gc.assert_exact(G.cpu(), refe, "exact " + what)
+    ops.gemm_tn(Ae.to(dev()), Be.to(dev()), G, Mred, N, K, perm=perm, accumulate=True)
+    gc.assert_exact(G.cpu(), 2 * refe, "exact += " + what)
 
 
 def test_renorm_and_shadow():
