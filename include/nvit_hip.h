@@ -243,8 +243,8 @@ int nvit_scale_cols(const float* a, int lda, const float* s, float c, void* out,
 /* ---- attention ------------------------------------------------------------------------
  * O = softmax(scale * qh kh^T) vh per (b,h), non-causal, no mask (model.py:121-124 SDPA branch).
  * qh,kh,vh [B,H,T,d] type dt; o [B,T,H*d] type dt (heads merged, model.py:127); lse [B,H,T] fp32
- * (natural log of the softmax denominator, including the running max).  d in {32,64}.
- * impl: 0 = scalar-FMA reference kernel (any dt), 1 = MFMA flash kernel (bf16 only). */
+ * (natural log of the softmax denominator, including the running max).  d in {32,64,128}.
+ * impl: 0 = scalar-FMA reference kernel (any dt), 1 = MFMA flash kernel (bf16 only); both take every d above. */
 int nvit_attn_fwd(int dt, int impl, const void* qh, const void* kh, const void* vh, float scale, void* o, float* lse,
                   int B, int H, int Tq, int Tk, int d, void* stream);
 /* Same, for the nViT call sites where q and k are (sqk*c_q) * unit vectors per head (model.py:108-112): every score is
@@ -252,12 +252,13 @@ int nvit_attn_fwd(int dt, int impl, const void* qh, const void* kh, const void* 
  * probabilities relative to the bound instead of a running maximum (no per-tile max / rescale).  sqk: [H*d] fp32.
  * q_prescale > 0: qh holds q_prescale * q_hat (see nvit_gemm_nt_qknorm); the result is that of the un-scaled q.  With
  * q_prescale = scale * log2(e) the exponent of the MFMA kernel needs no multiply: the score accumulator starts at minus
- * the bound and goes straight into v_exp_f32 (one VALU instruction less per score in a VALU-bound kernel). */
+ * the bound and goes straight into v_exp_f32 (one VALU instruction less per score in a VALU-bound kernel).
+ * d in {32,64,128}, as nvit_attn_fwd. */
 int nvit_attn_fwd_bounded(int dt, int impl, const void* qh, const void* kh, const void* vh, float scale, const float* sqk,
                           float c_q, float q_prescale, void* o, float* lse, int B, int H, int Tq, int Tk, int d,
                           void* stream);
 /* delta: [2,B,H,Tq] fp32 workspace (MINUS rowsum(dO*O) and MINUS lse in log2 units - accumulator seeds of the dk/dv
- * kernel). dqh,dkh,dvh [B,H,T,d] type dt. */
+ * kernel). dqh,dkh,dvh [B,H,T,d] type dt.  d in {32,64,128}, impl as nvit_attn_fwd. */
 int nvit_attn_bwd(int dt, int impl, const void* dout, const void* qh, const void* kh, const void* vh, const void* o,
                   const float* lse, float scale, void* dqh, void* dkh, void* dvh, float* delta, int B, int H,
                   int Tq, int Tk, int d, void* stream);

@@ -1,4 +1,5 @@
-// impl 1: MFMA flash attention for gfx950 (bf16 operands, fp32 softmax/accumulate), head dim 64.
+// impl 1: MFMA flash attention for gfx950 (bf16 operands, fp32 softmax/accumulate), head dim 64 (head dims 32 and 128:
+// the templated kernels in namespace hd below, same algorithm).
 // Non-causal, unmasked, arbitrary (ragged) sequence lengths.
 //
 // Orientation (everything is computed "key-major" so that per-query softmax statistics are
@@ -1140,12 +1141,717 @@ int dkv_asm_mode(float scale, float qpre) {
   return fabsf(c2 - 1.0f) < 1e-6f ? g_attn_dkv_asm : 0;   // the hand-placed loops assume the pre-scaled q (c2 = 1)
 }
 
+// ================================================================================= head dims 32 and 128
+// The same three kernels (key-major forward with the bounded-score fast path, the UNIT variant and the online-softmax
+// fallback; recompute backward as a dq kernel and a dk/dv kernel, no atomics; XCD-affine work map) with the head dim D a
+// template parameter, instantiated at 32 and 128.  The d = 64 kernels above stay as they are (the training path, tuned
+// instruction by instruction); these share their operand layouts, MFMA shapes, DMA machine and accumulation order, and
+// re-derive what depends on D:
+//   LDS image  D = 32: 64-byte rows, taken in pairs as one 128-byte row of the d = 64 image: chunk ((row & 1) * 4 + ch)
+//                      of "row pair" row >> 1, XOR (row >> 1) & 7.
+//              D = 128: 256-byte rows of 16 chunks, chunk XOR (bit-reversed row & 7) << 1.
+//              Both are conflict-free for the 16x16x32 row reads (ds_read_b128: one LDS cycle per 16-lane group) and
+//              for the transposed reads (ds_read_b64_tr_b16: one per 32-lane half), under the bank rule
+//              bank = (byte / 4) % 64 - checked for every (row0, chunk) the kernels read.
+//   KV tile    64 keys at D = 32 (4 KiB, one DMA piece per wave), 32 keys at D = 128 (8 KiB, two pieces per wave): the ring
+//              of 3 slots stays at 24 / 48 KiB.  A DMA piece (64 lanes x 16 B) is 16 rows at D = 32 and 4 rows at D = 128.
+//   dK/dV      32 keys per wave at D = 32, 16 at D = 128 (the accumulators dK^T, dV^T are 2 x D x keys / 64 registers).
+//   Fragments  D / 32 k-steps of the score products, D / 16 output d-fragments.
+// Not here: the fused q/k-normalise epilogues and the hand-placed dK/dV loop (d = 64 only; nvit_attn_bwd_qknorm).
+namespace hd {
+
+template <int D>
+struct Geo {
+  static_assert(D == 32 || D == 128, "head dims 32 and 128 (64: the kernels above)");
+  static constexpr int ROWB = D * 2;                  // bytes per row
+  static constexpr int NCH = D / 8;                   // 16-byte chunks per row
+  static constexpr int TKV = D == 128 ? 32 : 64;      // rows per staged tile
+  static constexpr int TILE_BYTES = TKV * ROWB;       // 4 / 8 KiB
+  static constexpr int TILE_DMA = TILE_BYTES / 4096;  // 1 KiB pieces per wave per tile (4 waves)
+  static constexpr int NKS = D / 32;                  // k-steps of a product over d
+  static constexpr int NDF = D / 16;                  // 16-wide d-fragments
+  static constexpr int NKF = TKV / 16;                // 16-row fragments of a tile
+  static constexpr int NS2 = TKV / 32;                // 32-deep MFMA steps over a tile
+  static constexpr int NKW = D == 128 ? 1 : 2;        // dK/dV kernel: 16-key fragments per wave
+  static constexpr int KWG = 64 * NKW;                // dK/dV kernel: keys per workgroup
+  // waves per SIMD (__launch_bounds__) = what the registers allow without scratch (-Rpass-analysis=kernel-resource-usage):
+  // D = 32: 120 / 98 / 132 VGPRs (forward / dq / dkv), D = 128: 219 / 242 / 178; the LDS (24-26 / 48-50 KiB per workgroup)
+  // allows more in every case
+  static constexpr int OCC_FWD = D == 32 ? 4 : 2, OCC_DQ = D == 32 ? 4 : 2, OCC_DKV = D == 32 ? 3 : 2;
+  static_assert(TILE_DMA == 1 || TILE_DMA == 2, "one or two pieces per wave per tile");
+
+  __device__ static __forceinline__ int swz(int row) {   // D = 128: bit-reversed (row & 7), times 2
+    return ((row & 1) << 3) | ((row & 2) << 1) | ((row & 4) >> 1);
+  }
+  // byte offset of 16-byte chunk ch of row `row` in a tile
+  __device__ static __forceinline__ int off(int row, int ch) {
+    if constexpr (D == 32) {
+      const int v = row >> 1;
+      return v * 128 + (((((row & 1) << 2) | ch) ^ (v & 7)) << 4);
+    } else {
+      return row * ROWB + ((ch ^ swz(row)) << 4);
+    }
+  }
+  // the inverse for the DMA: lane L of 1 KiB piece p lands at p * 1024 + 16 L, which holds (row, ch)
+  __device__ static __forceinline__ void piece_lane(int p, int lane, int& row, int& ch) {
+    if constexpr (D == 32) {
+      const int v = lane >> 3, vch = (lane & 7) ^ v;   // (p * 8 + v) & 7 == v
+      row = p * 16 + 2 * v + (vch >> 2);
+      ch = vch & 3;
+    } else {
+      row = p * 4 + (lane >> 4);
+      ch = (lane & 15) ^ swz(row);
+    }
+  }
+};
+
+template <int D>
+__device__ __forceinline__ uint4 row_frag(const char* tile, int row0, int ks, int l15, int lg) {
+  return *reinterpret_cast<const uint4*>(tile + Geo<D>::off(row0 + l15, ks * 4 + lg));
+}
+// as ::tr_frag (same k-slot order), on the D-dependent image
+template <int D>
+__device__ __forceinline__ uint4 tr_frag(const char* tile, int row0, int col0, int l15, int lg) {
+  const int q = l15 >> 2, p = l15 & 3;
+  const int r0 = row0 + 4 * lg + q, r1 = r0 + 16;
+  const int ch = (col0 >> 3) + (p >> 1);
+  const int o0 = Geo<D>::off(r0, ch) + ((p & 1) << 3), o1 = Geo<D>::off(r1, ch) + ((p & 1) << 3);
+  s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(tile + o0));
+  s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(tile + o1));
+  uint2 l2 = __builtin_bit_cast(uint2, lo), h2 = __builtin_bit_cast(uint2, hi);
+  return make_uint4(l2.x, l2.y, h2.x, h2.y);
+}
+
+// Store a wave's [16 NF rows x D] accumulator-layout result (g[df][f][r] = out[row 16f + l15][col 16df + 4lg + r]) as
+// bf16 rows through a wave-private LDS scratch of 16 NF rows (the tile image): every global store writes whole rows,
+// 16 bytes per lane.  Rows >= nvalid are not written.
+template <int D, int NF>
+__device__ __forceinline__ void store_tile(const f32x4 (&g)[D / 16][NF], char* scr, bf16* dst, size_t ld, int nvalid,
+                                           int lane) {
+  using G = Geo<D>;
+  const int l15 = lane & 15, lg = lane >> 4;
+#pragma unroll
+  for (int f = 0; f < NF; ++f)
+#pragma unroll
+    for (int df = 0; df < G::NDF; ++df)
+      *reinterpret_cast<uint2*>(scr + G::off(16 * f + l15, 2 * df + (lg >> 1)) + 8 * (lg & 1)) = pack4(g[df][f]);
+  __builtin_amdgcn_wave_barrier();
+  constexpr int RPP = 64 / G::NCH;   // rows per pass
+#pragma unroll
+  for (int pass = 0; pass < 16 * NF / RPP; ++pass) {
+    const int row = pass * RPP + lane / G::NCH, chunk = lane % G::NCH;
+    const uint4 v = *reinterpret_cast<const uint4*>(scr + G::off(row, chunk));
+    if (row < nvalid) *reinterpret_cast<uint4*>(dst + (size_t)row * ld + chunk * 8) = v;
+  }
+}
+
+// lane offsets of a full tile's DMA pieces (piece i * 4 + wid), and the tile DMA with the ragged-tile clamp (rows past the
+// end re-read the last valid row: finite values, masked by the consumer)
+template <int D>
+__device__ __forceinline__ unsigned tile_voff(int i, unsigned ld_bytes, int lane, int wid) {
+  int row, ch;
+  Geo<D>::piece_lane(i * 4 + wid, lane, row, ch);
+  return (unsigned)row * ld_bytes + (unsigned)ch * 16u;
+}
+template <int D>
+__device__ __forceinline__ void tile_dma(const bf16* src, unsigned ld_bytes, int row_base, int nrows, unsigned tile_off,
+                                         int lane, int wid, const unsigned (&voff)[Geo<D>::TILE_DMA]) {
+  using G = Geo<D>;
+  const char* sb = reinterpret_cast<const char*>(src) + (size_t)row_base * ld_bytes;
+  if (row_base + G::TKV <= nrows) {
+    if constexpr (G::TILE_DMA == 2)
+      glds16s_pair(sb, voff[0], voff[1], tile_off + wid * 1024);   // pieces wid and 4 + wid: 4 KiB apart
+    else
+      glds16s(sb, voff[0], tile_off + wid * 1024);
+  } else {
+#pragma unroll
+    for (int i = 0; i < G::TILE_DMA; ++i) {
+      int row, ch;
+      G::piece_lane(i * 4 + wid, lane, row, ch);
+      row = row_base + row < nrows ? row : nrows - 1 - row_base;
+      glds16s(sb, (unsigned)row * ld_bytes + (unsigned)ch * 16u, tile_off + (i * 4 + wid) * 1024);
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------ forward (see attn_fwd_mfma_kernel)
+template <int D>
+__global__ __launch_bounds__(256, Geo<D>::OCC_FWD) void attn_fwd_kernel(const bf16* __restrict__ qh, const bf16* __restrict__ kh,
+                                                          const bf16* __restrict__ vh, float scale, float qpre,
+                                                          const float* __restrict__ sqk, float c_q, bf16* __restrict__ o,
+                                                          float* __restrict__ lse, int H, int Tq, int Tk) {
+  using G = Geo<D>;
+  constexpr int TKV = G::TKV, TB = G::TILE_BYTES, NKS = G::NKS, NDF = G::NDF, NKF = G::NKF, NS2 = G::NS2;
+  constexpr int TD = G::TILE_DMA;
+  __shared__ __attribute__((aligned(16))) char lds[3][2][TB];  // ring [slot][K|V]
+  static_assert(sizeof(lds) >= 4 * 32 * G::ROWB, "the ring doubles as the output store scratch");
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int l15 = lane & 15, lg = lane >> 4;
+  int bh, tile_;
+  work_of((Tq + 127) / 128, bh, tile_);
+  const int b = bh / H, h = bh % H;
+  const int q0 = tile_ * 128 + wid * 32;
+  const bf16* kbase = kh + (size_t)bh * Tk * D;
+  const bf16* vbase = vh + (size_t)bh * Tk * D;
+  const float c2t = scale * LOG2E;
+  const float c2 = c2t / qpre;
+  const bool unit = __builtin_amdgcn_readfirstlane(fabsf(c2 - 1.0f) < 1e-6f ? 1 : 0) != 0;
+
+  uint4 qf[2][NKS];
+  f32x4 oacc[NDF][2];
+#pragma unroll
+  for (int i = 0; i < NDF; ++i)
+#pragma unroll
+    for (int f = 0; f < 2; ++f) oacc[i][f] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  float m_[2] = {-INFINITY, -INFINITY}, l_[2] = {0.f, 0.f};
+  float tb = INFINITY;
+  if (sqk) {   // the head's max |s_d| over one wave: lanes >= 32 hold no channel at D = 32, two channels at D = 128
+    float sm;
+    if constexpr (D == 32)
+      sm = lane < 32 ? fabsf(sqk[h * D + lane] * c_q) : 0.f;
+    else
+      sm = fmaxf(fabsf(sqk[h * D + lane] * c_q), fabsf(sqk[h * D + 64 + lane] * c_q));
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) sm = fmaxf(sm, __shfl_xor(sm, off, 64));
+    tb = c2t * sm * sm;
+  }
+  const bool fast = __builtin_amdgcn_readfirstlane(tb <= BOUND_MAX ? 1 : 0) != 0;
+  f32x4 lacc[2] = {(f32x4){0.f, 0.f, 0.f, 0.f}, (f32x4){0.f, 0.f, 0.f, 0.f}};
+  const uint4 ones = make_uint4(0x3F803F80u, 0x3F803F80u, 0x3F803F80u, 0x3F803F80u);
+
+  const int nt = (Tk + TKV - 1) / TKV;
+  const unsigned ring = lds_addr(&lds[0][0][0]);
+  unsigned voff[TD];
+#pragma unroll
+  for (int i = 0; i < TD; ++i) voff[i] = tile_voff<D>(i, G::ROWB, lane, wid);
+  tile_dma<D>(kbase, G::ROWB, 0, Tk, ring, lane, wid, voff);
+  tile_dma<D>(vbase, G::ROWB, 0, Tk, ring + TB, lane, wid, voff);
+  if (nt > 1) {
+    tile_dma<D>(kbase, G::ROWB, TKV, Tk, ring + 2 * TB, lane, wid, voff);
+    tile_dma<D>(vbase, G::ROWB, TKV, Tk, ring + 3 * TB, lane, wid, voff);
+  }
+#pragma unroll
+  for (int f = 0; f < 2; ++f) {
+    int q = q0 + 16 * f + l15;
+    q = q < Tq ? q : Tq - 1;
+#pragma unroll
+    for (int ks = 0; ks < NKS; ++ks)
+      qf[f][ks] = *reinterpret_cast<const uint4*>(qh + ((size_t)bh * Tq + q) * D + ks * 32 + lg * 8);
+  }
+#pragma unroll
+  for (int f = 0; f < 2; ++f)
+#pragma unroll
+    for (int ks = 0; ks < NKS; ++ks) settle(qf[f][ks]);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  int cur = 0;
+  const bool wave_active = q0 < Tq;
+  f32x4 ntb = {-tb, -tb, -tb, -tb};
+  asm volatile("" : "+v"(ntb));
+  auto tile_body = [&](const int t, auto masked_, auto fast_, auto unit_) {
+    constexpr bool MASKED = decltype(masked_)::value;
+    constexpr bool FAST = decltype(fast_)::value;
+    constexpr bool UNIT = decltype(unit_)::value;
+    if (t + 2 < nt) {
+      const int sl = cur == 0 ? 2 : cur - 1;  // (t + 2) % 3
+      tile_dma<D>(kbase, G::ROWB, (t + 2) * TKV, Tk, ring + (2 * sl) * TB, lane, wid, voff);
+      tile_dma<D>(vbase, G::ROWB, (t + 2) * TKV, Tk, ring + (2 * sl + 1) * TB, lane, wid, voff);
+    }
+    if (wave_active) {
+      const char* kt = &lds[cur][0][0];
+      const char* vt = &lds[cur][1][0];
+      const int nvalid = MASKED ? Tk - t * TKV : TKV;
+      const int nkf = MASKED ? (nvalid + 15) >> 4 : NKF, ns2 = MASKED ? (nvalid + 31) >> 5 : NS2;
+      // S^T[kf][f]: rows = key 16kf + 4lg + r, col = query 16f + l15; FAST: probabilities relative to the bound
+      f32x4 s[NKF][2];
+#pragma unroll
+      for (int kf = 0; kf < NKF; ++kf) {
+        if (!MASKED || kf < nkf) {
+          uint4 a[NKS];
+#pragma unroll
+          for (int ks = 0; ks < NKS; ++ks) a[ks] = row_frag<D>(kt, kf * 16, ks, l15, lg);
+#pragma unroll
+          for (int f = 0; f < 2; ++f) {
+            f32x4 z = (FAST && UNIT) ? ntb : (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = 0; ks < NKS; ++ks) z = mfma16(a[ks], qf[f][ks], z);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const bool valid = !MASKED || kf * 16 + lg * 4 + r < nvalid;
+              if constexpr (FAST)
+                z[r] = valid ? (UNIT ? fast_exp2(z[r]) : fast_exp2(z[r] * c2 - tb)) : 0.f;
+              else
+                z[r] = valid ? z[r] : -INFINITY;
+            }
+            s[kf][f] = z;
+          }
+        } else {
+          s[kf][0] = (f32x4){0.f, 0.f, 0.f, 0.f};   // fragment past the end: probability 0, no work
+          s[kf][1] = s[kf][0];
+        }
+      }
+      if constexpr (!FAST) {   // online softmax: running maximum, correction of the row sums and the accumulators
+#pragma unroll
+        for (int f = 0; f < 2; ++f) {
+          float mt = -INFINITY;
+#pragma unroll
+          for (int kf = 0; kf < NKF; ++kf)
+            if (!MASKED || kf < nkf) {
+#pragma unroll
+              for (int r = 0; r < 4; ++r) mt = fmaxf(mt, s[kf][f][r]);
+            }
+          mt = fmaxf(mt, __shfl_xor(mt, 16, 64));
+          mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
+          const float mn = fmaxf(m_[f], mt);
+          const float corr = fast_exp2((m_[f] - mn) * c2);
+          m_[f] = mn;
+          const float mc = mn * c2;
+          float rs = 0.f;
+#pragma unroll
+          for (int kf = 0; kf < NKF; ++kf)
+            if (!MASKED || kf < nkf) {
+#pragma unroll
+              for (int r = 0; r < 4; ++r) {
+                const float p = fast_exp2(s[kf][f][r] * c2 - mc);
+                s[kf][f][r] = p;
+                rs += p;
+              }
+            }
+          l_[f] = l_[f] * corr + rs;
+#pragma unroll
+          for (int i = 0; i < NDF; ++i) oacc[i][f] = oacc[i][f] * corr;
+        }
+      }
+      // O^T[df][f] += V^T P^T (and FAST: the row sums l[f] += 1^T P^T)
+#pragma unroll
+      for (int s2 = 0; s2 < NS2; ++s2)
+        if (!MASKED || s2 < ns2) {
+          uint4 pf[2];
+#pragma unroll
+          for (int f = 0; f < 2; ++f) pf[f] = pack8(s[2 * s2][f], s[2 * s2 + 1][f]);
+          if constexpr (FAST) {
+#pragma unroll
+            for (int f = 0; f < 2; ++f) lacc[f] = mfma16(ones, pf[f], lacc[f]);
+          }
+#pragma unroll
+          for (int df = 0; df < NDF; ++df) {
+            const uint4 va = tr_frag<D>(vt, s2 * 32, df * 16, l15, lg);
+#pragma unroll
+            for (int f = 0; f < 2; ++f) oacc[df][f] = mfma16(va, pf[f], oacc[df][f]);
+          }
+        }
+    }
+    if (t + 2 < nt)
+      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * TD) : "memory");
+    else
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    cur = cur == 2 ? 0 : cur + 1;
+  };
+#define NVIT_RUN_TILES(FAST_, UNIT_)                                                            \
+  {                                                                                             \
+    for (int t = 0; t + 1 < nt; ++t) tile_body(t, std::false_type{}, FAST_{}, UNIT_{});         \
+    if (Tk % TKV)                                                                               \
+      tile_body(nt - 1, std::true_type{}, FAST_{}, UNIT_{});                                    \
+    else                                                                                        \
+      tile_body(nt - 1, std::false_type{}, FAST_{}, UNIT_{});                                   \
+  }
+  if (fast && unit)
+    NVIT_RUN_TILES(std::true_type, std::true_type)
+  else if (fast)
+    NVIT_RUN_TILES(std::true_type, std::false_type)
+  else
+    NVIT_RUN_TILES(std::false_type, std::false_type)
+#undef NVIT_RUN_TILES
+#pragma unroll
+  for (int f = 0; f < 2; ++f) {
+    float l, lse_v;
+    if (fast) {
+      l = lacc[f][0];
+      lse_v = (tb + log2f(l)) * (1.0f / LOG2E);
+    } else {
+      l = l_[f];
+      l += __shfl_xor(l, 16, 64);
+      l += __shfl_xor(l, 32, 64);
+      lse_v = m_[f] * (c2 * (1.0f / LOG2E)) + logf(l);
+    }
+    const int q = q0 + 16 * f + l15;
+    const float inv = 1.0f / l;
+#pragma unroll
+    for (int df = 0; df < NDF; ++df) oacc[df][f] = oacc[df][f] * inv;
+    if (q < Tq && lg == 0) lse[(size_t)bh * Tq + q] = lse_v;
+  }
+  if (wave_active)
+    store_tile<D, 2>(oacc, &lds[0][0][0] + wid * 32 * G::ROWB, o + ((size_t)b * Tq + q0) * (H * D) + h * D, (size_t)H * D,
+                     Tq - q0, lane);
+}
+
+// ------------------------------------------------------------------------------------------ dQ (see attn_bwd_dq_mfma_kernel)
+template <int D>
+__global__ __launch_bounds__(256, Geo<D>::OCC_DQ) void attn_bwd_dq_kernel(const bf16* __restrict__ dout, const bf16* __restrict__ qh,
+                                                             const bf16* __restrict__ kh, const bf16* __restrict__ vh,
+                                                             const float* __restrict__ lse, const bf16* __restrict__ og,
+                                                             float* __restrict__ delta, float scale,
+                                                             bf16* __restrict__ dqh, int H, int Tq, int Tk) {
+  using G = Geo<D>;
+  constexpr int TKV = G::TKV, TB = G::TILE_BYTES, NKS = G::NKS, NDF = G::NDF, NKF = G::NKF, NS2 = G::NS2;
+  constexpr int TD = G::TILE_DMA;
+  __shared__ __attribute__((aligned(16))) char lds[3][2][TB];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int l15 = lane & 15, lg = lane >> 4;
+  const int ntile = (Tq + 127) / 128;
+  int bh, tile_;
+  work_of(ntile, bh, tile_);
+  const int b = bh / H, h = bh % H;
+  const int q0 = tile_ * 128 + wid * 32;
+  const bf16* kbase = kh + (size_t)bh * Tk * D;
+  const bf16* vbase = vh + (size_t)bh * Tk * D;
+  const float c2 = scale * LOG2E;   // q is not pre-scaled on this path
+
+  uint4 qf[2][NKS], gf[2][NKS];
+  float lse2[2], dl[2];
+  const int nt = (Tk + TKV - 1) / TKV;
+  const unsigned ring = lds_addr(&lds[0][0][0]);
+  unsigned voff[TD];
+#pragma unroll
+  for (int i = 0; i < TD; ++i) voff[i] = tile_voff<D>(i, G::ROWB, lane, wid);
+  tile_dma<D>(kbase, G::ROWB, 0, Tk, ring, lane, wid, voff);
+  tile_dma<D>(vbase, G::ROWB, 0, Tk, ring + TB, lane, wid, voff);
+  if (nt > 1) {
+    tile_dma<D>(kbase, G::ROWB, TKV, Tk, ring + 2 * TB, lane, wid, voff);
+    tile_dma<D>(vbase, G::ROWB, TKV, Tk, ring + 3 * TB, lane, wid, voff);
+  }
+#pragma unroll
+  for (int f = 0; f < 2; ++f) {
+    const int qu = q0 + 16 * f + l15;
+    const int q = qu < Tq ? qu : Tq - 1;
+    lse2[f] = lse[(size_t)bh * Tq + q] * LOG2E;
+    float part = 0.f;
+#pragma unroll
+    for (int ks = 0; ks < NKS; ++ks) {
+      const size_t tok = ((size_t)b * Tq + q) * (H * D) + h * D + ks * 32 + lg * 8;
+      qf[f][ks] = *reinterpret_cast<const uint4*>(qh + ((size_t)bh * Tq + q) * D + ks * 32 + lg * 8);
+      gf[f][ks] = *reinterpret_cast<const uint4*>(dout + tok);
+      const uint4 of = *reinterpret_cast<const uint4*>(og + tok);
+      const bf16x8 a = __builtin_bit_cast(bf16x8, gf[f][ks]), c = __builtin_bit_cast(bf16x8, of);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) part += (float)a[e] * (float)c[e];
+    }
+    part += __shfl_xor(part, 16, 64);   // the row's D columns live on the 4 lanes l15 + 16*lg
+    part += __shfl_xor(part, 32, 64);
+    dl[f] = part;
+    if (lg == 0 && qu < Tq) {   // side buffer for the dk/dv kernel: -delta and -lse in log2 units
+      delta[(size_t)bh * Tq + qu] = -part;
+      delta[((size_t)(gridDim.x / ntile) + bh) * Tq + qu] = -lse2[f];
+    }
+  }
+  f32x4 dq[NDF][2];
+#pragma unroll
+  for (int i = 0; i < NDF; ++i)
+#pragma unroll
+    for (int f = 0; f < 2; ++f) dq[i][f] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int f = 0; f < 2; ++f) {
+    settle(lse2[f]);
+    settle(dl[f]);
+#pragma unroll
+    for (int ks = 0; ks < NKS; ++ks) {
+      settle(qf[f][ks]);
+      settle(gf[f][ks]);
+    }
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  f32x4 ndl[2];
+#pragma unroll
+  for (int f = 0; f < 2; ++f) {
+    ndl[f] = (f32x4){-dl[f], -dl[f], -dl[f], -dl[f]};
+    asm volatile("" : "+v"(ndl[f]));
+  }
+  int cur = 0;
+  const bool wave_active = q0 < Tq;
+  auto tile_body = [&](const int t, auto masked_) {
+    constexpr bool MASKED = decltype(masked_)::value;
+    if (t + 2 < nt) {
+      const int sl = cur == 0 ? 2 : cur - 1;
+      tile_dma<D>(kbase, G::ROWB, (t + 2) * TKV, Tk, ring + (2 * sl) * TB, lane, wid, voff);
+      tile_dma<D>(vbase, G::ROWB, (t + 2) * TKV, Tk, ring + (2 * sl + 1) * TB, lane, wid, voff);
+    }
+    if (wave_active) {
+      const char* kt = &lds[cur][0][0];
+      const char* vt = &lds[cur][1][0];
+      const int nvalid = MASKED ? Tk - t * TKV : TKV;
+      const int nkf = MASKED ? (nvalid + 15) >> 4 : NKF, ns2 = MASKED ? (nvalid + 31) >> 5 : NS2;
+#pragma unroll
+      for (int s2 = 0; s2 < NS2; ++s2) {
+        if (MASKED && s2 >= ns2) continue;
+        f32x4 ds_[2][2];  // [kk][f] for key frags kf = 2*s2 + kk
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk) {
+          const int kf = 2 * s2 + kk;
+          if (!MASKED || kf < nkf) {
+            uint4 a[NKS], v[NKS];
+#pragma unroll
+            for (int ks = 0; ks < NKS; ++ks) {
+              a[ks] = row_frag<D>(kt, kf * 16, ks, l15, lg);
+              v[ks] = row_frag<D>(vt, kf * 16, ks, l15, lg);
+            }
+#pragma unroll
+            for (int f = 0; f < 2; ++f) {
+              f32x4 z = {0.f, 0.f, 0.f, 0.f}, w = ndl[f];
+#pragma unroll
+              for (int ks = 0; ks < NKS; ++ks) z = mfma16(a[ks], qf[f][ks], z);   // S^T
+#pragma unroll
+              for (int ks = 0; ks < NKS; ++ks) w = mfma16(v[ks], gf[f][ks], w);   // dP^T - delta
+#pragma unroll
+              for (int r = 0; r < 4; ++r) {
+                const bool valid = !MASKED || (kf * 16 + lg * 4 + r) < nvalid;
+                const float p = valid ? fast_exp2(z[r] * c2 - lse2[f]) : 0.f;
+                ds_[kk][f][r] = p * w[r];   // the softmax scale is applied once, to the dQ accumulators
+              }
+            }
+          } else {
+            ds_[kk][0] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            ds_[kk][1] = ds_[kk][0];
+          }
+        }
+        uint4 dsf[2];
+#pragma unroll
+        for (int f = 0; f < 2; ++f) dsf[f] = pack8(ds_[0][f], ds_[1][f]);
+        // dQ^T[df][f] += K^T dS^T
+#pragma unroll
+        for (int df = 0; df < NDF; ++df) {
+          const uint4 ka = tr_frag<D>(kt, s2 * 32, df * 16, l15, lg);
+#pragma unroll
+          for (int f = 0; f < 2; ++f) dq[df][f] = mfma16(ka, dsf[f], dq[df][f]);
+        }
+      }
+    }
+    if (t + 2 < nt)
+      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * TD) : "memory");
+    else
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    cur = cur == 2 ? 0 : cur + 1;
+  };
+  for (int t = 0; t + 1 < nt; ++t) tile_body(t, std::false_type{});
+  if (Tk % TKV)
+    tile_body(nt - 1, std::true_type{});
+  else
+    tile_body(nt - 1, std::false_type{});
+#pragma unroll
+  for (int i = 0; i < NDF; ++i)
+#pragma unroll
+    for (int f = 0; f < 2; ++f) dq[i][f] = dq[i][f] * scale;
+  if (wave_active)
+    store_tile<D, 2>(dq, &lds[0][0][0] + wid * 32 * G::ROWB, dqh + ((size_t)bh * Tq + q0) * D, (size_t)D, Tq - q0, lane);
+}
+
+// ------------------------------------------------------------------------------------------ dK, dV (see attn_bwd_dkv_mfma_kernel)
+// One workgroup = 4 waves x 16 NKW keys; the query tiles of Q and dO (+ their -lse / -delta rows, 64 floats each whatever
+// the tile height) arrive by LDS-DMA into a 3-slot ring two tiles ahead.
+template <int D>
+__global__ __launch_bounds__(256, Geo<D>::OCC_DKV) void attn_bwd_dkv_kernel(const bf16* __restrict__ dout, const bf16* __restrict__ qh,
+                                                              const bf16* __restrict__ kh, const bf16* __restrict__ vh,
+                                                              const float* __restrict__ delta, float scale,
+                                                              bf16* __restrict__ dkh, bf16* __restrict__ dvh, int H, int Tq,
+                                                              int Tk) {
+  using G = Geo<D>;
+  constexpr int TKV = G::TKV, TB = G::TILE_BYTES, NKS = G::NKS, NDF = G::NDF, NKF = G::NKF, NS2 = G::NS2;
+  constexpr int TD = G::TILE_DMA, NKW = G::NKW, KWG = G::KWG;
+  constexpr int SLOT = 2 * TB + 512;   // Q tile | dO tile | -lse[64] | -delta[64]
+  __shared__ __attribute__((aligned(16))) char lds[3 * SLOT];
+  static_assert(sizeof(lds) >= 4 * 16 * NKW * G::ROWB, "the ring doubles as the output store scratch");
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int l15 = lane & 15, lg = lane >> 4;
+  const int ntile = (Tk + KWG - 1) / KWG;
+  int bh, tile_;
+  work_of(ntile, bh, tile_);
+  const int b = bh / H, h = bh % H;
+  const int k0 = tile_ * KWG + wid * 16 * NKW;
+  const bf16* qbase = qh + (size_t)bh * Tq * D;
+  const bf16* gbase = dout + (size_t)b * Tq * (H * D) + h * D;
+  const float* dbase = delta + (size_t)bh * Tq;                                // -delta, written by the dq kernel
+  const float* lbase = delta + ((size_t)(gridDim.x / ntile) + bh) * Tq;        // -lse * log2(e), written by the dq kernel
+  const float c2 = scale * LOG2E;
+  const int nt = (Tq + TKV - 1) / TKV;
+  const unsigned ring = lds_addr(&lds[0]);
+
+  const unsigned ldg_bytes = (unsigned)(H * D * 2);
+  unsigned voff_q[TD], voff_g[TD];
+#pragma unroll
+  for (int i = 0; i < TD; ++i) {
+    voff_q[i] = tile_voff<D>(i, G::ROWB, lane, wid);
+    voff_g[i] = tile_voff<D>(i, ldg_bytes, lane, wid);
+  }
+  auto tile_issue = [&](int t, int slot) {
+    const unsigned so = ring + (unsigned)slot * SLOT;
+    tile_dma<D>(qbase, G::ROWB, t * TKV, Tq, so, lane, wid, voff_q);
+    tile_dma<D>(gbase, ldg_bytes, t * TKV, Tq, so + TB, lane, wid, voff_g);
+    int q = t * TKV + lane;
+    q = q < Tq ? q : Tq - 1;
+    glds4a(lbase + q, so + 2 * TB);        // every wave writes the same 256 bytes (keeps vmcnt uniform)
+    glds4a(dbase + q, so + 2 * TB + 256);
+  };
+  tile_issue(0, 0);
+  if (nt > 1) tile_issue(1, 1);
+
+  uint4 kf_[NKW][NKS], vf_[NKW][NKS];  // K / V rows of this wave's keys (MFMA-B operands)
+#pragma unroll
+  for (int f = 0; f < NKW; ++f) {
+    int k = k0 + 16 * f + l15;
+    k = k < Tk ? k : Tk - 1;
+#pragma unroll
+    for (int ks = 0; ks < NKS; ++ks) {
+      kf_[f][ks] = *reinterpret_cast<const uint4*>(kh + ((size_t)bh * Tk + k) * D + ks * 32 + lg * 8);
+      vf_[f][ks] = *reinterpret_cast<const uint4*>(vh + ((size_t)bh * Tk + k) * D + ks * 32 + lg * 8);
+    }
+  }
+#pragma unroll
+  for (int f = 0; f < NKW; ++f)
+#pragma unroll
+    for (int ks = 0; ks < NKS; ++ks) {
+      settle(kf_[f][ks]);
+      settle(vf_[f][ks]);
+    }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+
+  f32x4 dk[NDF][NKW], dv[NDF][NKW];  // rows d = 16df + 4lg + r, col key = 16f + l15
+#pragma unroll
+  for (int i = 0; i < NDF; ++i)
+#pragma unroll
+    for (int f = 0; f < NKW; ++f) {
+      dk[i][f] = (f32x4){0.f, 0.f, 0.f, 0.f};
+      dv[i][f] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    }
+  const bool wave_active = k0 < Tk;
+  int cur = 0;
+  auto tile_body = [&](const int t, auto masked_) {
+    constexpr bool MASKED = decltype(masked_)::value;
+    if (t + 2 < nt) tile_issue(t + 2, cur == 0 ? 2 : cur - 1);
+    if (wave_active) {
+      const char* qt = &lds[cur * SLOT];
+      const char* gt = qt + TB;
+      const float* st = reinterpret_cast<const float*>(qt + 2 * TB);
+      const int nvalid = MASKED ? Tq - t * TKV : TKV;
+      const int nqf = MASKED ? (nvalid + 15) >> 4 : NKF, ns2 = MASKED ? (nvalid + 31) >> 5 : NS2;
+#pragma unroll
+      for (int s2 = 0; s2 < NS2; ++s2) {
+        if (MASKED && s2 >= ns2) continue;
+        uint2 ph[2][NKW], sh[2][NKW];  // [qq][key frag] packed bf16 P / dS of query frag 2*s2 + qq
+#pragma unroll
+        for (int qq = 0; qq < 2; ++qq) {
+          const int qfi = 2 * s2 + qq;
+          if (!MASKED || qfi < nqf) {
+            uint4 a[NKS], g[NKS];
+#pragma unroll
+            for (int ks = 0; ks < NKS; ++ks) {
+              a[ks] = row_frag<D>(qt, qfi * 16, ks, l15, lg);
+              g[ks] = row_frag<D>(gt, qfi * 16, ks, l15, lg);
+            }
+            f32x4 nl4 = *reinterpret_cast<const f32x4*>(st + qfi * 16 + 4 * lg);        // -lse (log2 units)
+            f32x4 nd4 = *reinterpret_cast<const f32x4*>(st + 64 + qfi * 16 + 4 * lg);   // -delta
+            asm volatile("" : "+v"(nd4));
+#pragma unroll
+            for (int f = 0; f < NKW; ++f) {
+              f32x4 z = {0.f, 0.f, 0.f, 0.f}, w = nd4;
+#pragma unroll
+              for (int ks = 0; ks < NKS; ++ks) z = mfma16(a[ks], kf_[f][ks], z);   // S[q][key]
+#pragma unroll
+              for (int ks = 0; ks < NKS; ++ks) w = mfma16(g[ks], vf_[f][ks], w);   // dP[q][key] - delta[q]
+              f32x4 p, dsv;
+#pragma unroll
+              for (int r = 0; r < 4; ++r) {
+                float pr = fast_exp2(z[r] * c2 + nl4[r]);
+                if (MASKED && qfi * 16 + lg * 4 + r >= nvalid) pr = 0.f;
+                p[r] = pr;
+                dsv[r] = pr * w[r];
+              }
+              ph[qq][f] = pack4(p);
+              sh[qq][f] = pack4(dsv);
+            }
+          } else {
+#pragma unroll
+            for (int f = 0; f < NKW; ++f) ph[qq][f] = sh[qq][f] = make_uint2(0u, 0u);
+          }
+        }
+        uint4 pb[NKW], sb[NKW];
+#pragma unroll
+        for (int f = 0; f < NKW; ++f) {
+          pb[f] = make_uint4(ph[0][f].x, ph[0][f].y, ph[1][f].x, ph[1][f].y);
+          sb[f] = make_uint4(sh[0][f].x, sh[0][f].y, sh[1][f].x, sh[1][f].y);
+        }
+#pragma unroll
+        for (int df = 0; df < NDF; ++df) {
+          const uint4 ga = tr_frag<D>(gt, s2 * 32, df * 16, l15, lg);  // dO^T[d][q slots]
+          const uint4 qa = tr_frag<D>(qt, s2 * 32, df * 16, l15, lg);  // Q^T[d][q slots]
+#pragma unroll
+          for (int f = 0; f < NKW; ++f) {
+            dv[df][f] = mfma16(ga, pb[f], dv[df][f]);
+            dk[df][f] = mfma16(qa, sb[f], dk[df][f]);
+          }
+        }
+      }
+    }
+    if (t + 2 < nt)
+      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * TD + 2) : "memory");
+    else
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    cur = cur == 2 ? 0 : cur + 1;
+  };
+  for (int t = 0; t + 1 < nt; ++t) tile_body(t, std::false_type{});
+  if (Tq % TKV)
+    tile_body(nt - 1, std::true_type{});
+  else
+    tile_body(nt - 1, std::false_type{});
+#pragma unroll
+  for (int i = 0; i < NDF; ++i)
+#pragma unroll
+    for (int f = 0; f < NKW; ++f) dk[i][f] = dk[i][f] * scale;
+  char* scr = &lds[0] + wid * 16 * NKW * G::ROWB;   // (the tile loop ended with a barrier: the ring is free)
+  if (wave_active) {
+    store_tile<D, NKW>(dk, scr, dkh + ((size_t)bh * Tk + k0) * D, (size_t)D, Tk - k0, lane);
+    __builtin_amdgcn_wave_barrier();
+    store_tile<D, NKW>(dv, scr, dvh + ((size_t)bh * Tk + k0) * D, (size_t)D, Tk - k0, lane);
+  }
+}
+
+template <int D>
+int launch_fwd(const void* qh, const void* kh, const void* vh, float scale, float qpre, const float* sqk, float c_q, void* o,
+               float* lse, int B, int H, int Tq, int Tk, hipStream_t s) {
+  hipLaunchKernelGGL(attn_fwd_kernel<D>, dim3((unsigned)(cdiv(Tq, 128) * B * H)), dim3(256), 0, s, (const bf16*)qh,
+                     (const bf16*)kh, (const bf16*)vh, scale, qpre, sqk, c_q, (bf16*)o, lse, H, Tq, Tk);
+  NVIT_CHECK_LAUNCH("attn_fwd_mfma");
+  return NVIT_OK;
+}
+
+template <int D>
+int launch_bwd(const void* dout, const void* qh, const void* kh, const void* vh, const void* o, const float* lse,
+               float* delta, float scale, void* dqh, void* dkh, void* dvh, int B, int H, int Tq, int Tk, hipStream_t s) {
+  hipLaunchKernelGGL(attn_bwd_dq_kernel<D>, dim3((unsigned)(cdiv(Tq, 128) * B * H)), dim3(256), 0, s, (const bf16*)dout,
+                     (const bf16*)qh, (const bf16*)kh, (const bf16*)vh, lse, (const bf16*)o, delta, scale, (bf16*)dqh, H,
+                     Tq, Tk);
+  NVIT_CHECK_LAUNCH("attn_bwd_dq_mfma");
+  hipLaunchKernelGGL(attn_bwd_dkv_kernel<D>, dim3((unsigned)(cdiv(Tk, Geo<D>::KWG) * B * H)), dim3(256), 0, s,
+                     (const bf16*)dout, (const bf16*)qh, (const bf16*)kh, (const bf16*)vh, (const float*)delta, scale,
+                     (bf16*)dkh, (bf16*)dvh, H, Tq, Tk);
+  NVIT_CHECK_LAUNCH("attn_bwd_dkv_mfma");
+  return NVIT_OK;
+}
+
+}  // namespace hd
+
 }  // namespace
 
 int nvit_attn_fwd_mfma(const void* qh, const void* kh, const void* vh, float scale, float qpre, const float* sqk,
                        float c_q, void* o, float* lse, int B, int H, int Tq, int Tk, int d, hipStream_t s) {
-  NVIT_REQUIRE(d == 64, "attn_fwd: the MFMA kernel supports head dim 64 only (got %d)", d);
+  NVIT_REQUIRE(d == 32 || d == 64 || d == 128, "attn_fwd: the MFMA kernel supports head dims 32, 64 and 128 (got %d)", d);
   NVIT_REQUIRE(qpre > 0.f, "attn_fwd: the q pre-scale must be positive (got %g)", (double)qpre);
+  if (d == 32) return hd::launch_fwd<32>(qh, kh, vh, scale, qpre, sqk, c_q, o, lse, B, H, Tq, Tk, s);
+  if (d == 128) return hd::launch_fwd<128>(qh, kh, vh, scale, qpre, sqk, c_q, o, lse, B, H, Tq, Tk, s);
   dim3 grid((unsigned)(cdiv(Tq, 128) * B * H));
   hipLaunchKernelGGL(attn_fwd_mfma_kernel, grid, dim3(256), 0, s, (const bf16*)qh, (const bf16*)kh, (const bf16*)vh,
                      scale, qpre, sqk, c_q, (bf16*)o, lse, H, Tq, Tk);
@@ -1156,8 +1862,10 @@ int nvit_attn_fwd_mfma(const void* qh, const void* kh, const void* vh, float sca
 int nvit_attn_bwd_mfma(const void* dout, const void* qh, const void* kh, const void* vh, const void* o, const float* lse,
                        float* delta, float scale, void* dqh, void* dkh, void* dvh, int B, int H, int Tq, int Tk,
                        int d, hipStream_t s) {
-  NVIT_REQUIRE(d == 64, "attn_bwd: the MFMA kernel supports head dim 64 only (got %d)", d);
+  NVIT_REQUIRE(d == 32 || d == 64 || d == 128, "attn_bwd: the MFMA kernel supports head dims 32, 64 and 128 (got %d)", d);
   NVIT_REQUIRE(o != nullptr && delta != nullptr, "attn_bwd: the attention output and the [2,B,H,Tq] side buffer are required");
+  if (d == 32) return hd::launch_bwd<32>(dout, qh, kh, vh, o, lse, delta, scale, dqh, dkh, dvh, B, H, Tq, Tk, s);
+  if (d == 128) return hd::launch_bwd<128>(dout, qh, kh, vh, o, lse, delta, scale, dqh, dkh, dvh, B, H, Tq, Tk, s);
   dim3 gq((unsigned)(cdiv(Tq, 128) * B * H)), gk((unsigned)(cdiv(Tk, 128) * B * H));
   QkFuse none{};
   none.xs = 1.0f;
@@ -1183,7 +1891,7 @@ int nvit_attn_bwd_mfma_fused(const void* dout, const void* qh, const void* kh, c
                              const float* lse, float* delta, float scale, const float* rq, const float* rk, const float* sqk,
                              float c_q, float qpre, void* dq, int ldq, void* dk, void* dv, int ldkv, float* part_q,
                              float* part_k, int B, int H, int Tq, int Tk, int d, hipStream_t s) {
-  NVIT_REQUIRE(d == 64, "attn_bwd: the MFMA kernel supports head dim 64 only (got %d)", d);
+  NVIT_REQUIRE(d == 64, "attn_bwd_qknorm: the fused kernels support head dim 64 only (got %d)", d);
   NVIT_REQUIRE(ldq % 4 == 0 && ldkv % 4 == 0, "attn_bwd: leading dims must be multiples of 4");
   NVIT_REQUIRE(o != nullptr && delta != nullptr, "attn_bwd: the attention output and the [2,B,H,Tq] side buffer are required");
   dim3 gq((unsigned)(cdiv(Tq, 128) * B * H)), gk((unsigned)(cdiv(Tk, 128) * B * H));

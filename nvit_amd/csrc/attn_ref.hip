@@ -1,7 +1,7 @@
 // impl 0: scalar-FMA attention kernels (any element type, fp32 math).  They carry the exact-f32
 // parity mode and serve as the on-device cross-check of the MFMA flash kernels (attn_mfma.hip).
 // One thread owns one query (fwd, dq) or one key (dk/dv); the other side is streamed through
-// LDS in tiles of 32 rows and read by broadcast.
+// LDS in tiles of 32 rows and read by broadcast (head dim 128: four lanes per query or key, see attn_fwd_ref_split).
 #include "common.h"
 
 namespace {
@@ -189,6 +189,181 @@ __global__ __launch_bounds__(64) void attn_bwd_dkv_ref(const T* dout, const T* q
   }
 }
 
+// Head dim 128: one thread per query would need q[128] + acc[128] live registers, more than the architectural file holds, so
+// S = 4 adjacent lanes share a query (or a key), lane j owning the channels e = S*i + j (i < D / S; the S lanes of a row
+// read S consecutive words of an LDS row: no bank conflict).  Dot products are the lane partials summed by a butterfly over
+// the S lanes (every lane ends with the same bits).  Otherwise the kernels above, statement for statement.
+constexpr int SPLIT = 4;
+__device__ __forceinline__ float split_sum(float v) {
+#pragma unroll
+  for (int o = 1; o < SPLIT; o <<= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+template <typename T, int D>
+__global__ __launch_bounds__(64) void attn_fwd_ref_split(const T* qh, const T* kh, const T* vh, float scale, T* o,
+                                                          float* lse, int H, int Tq, int Tk) {
+  constexpr int DL = D / SPLIT;
+  __shared__ float ks[TILE][D], vs[TILE][D];
+  const int bh = blockIdx.y, b = bh / H, h = bh % H;
+  const int j = threadIdx.x % SPLIT;
+  const int qi = blockIdx.x * (64 / SPLIT) + threadIdx.x / SPLIT;
+  const bool ok = qi < Tq;
+  const T* qp = qh + ((size_t)bh * Tq + (ok ? qi : 0)) * D;
+  float q[DL], acc[DL];
+#pragma unroll
+  for (int i = 0; i < DL; ++i) {
+    q[i] = (float)qp[SPLIT * i + j] * scale;
+    acc[i] = 0.f;
+  }
+  float m = -INFINITY, l = 0.f;
+  for (int k0 = 0; k0 < Tk; k0 += TILE) {
+    const int nk = min(TILE, Tk - k0);
+    for (int i = threadIdx.x; i < TILE * D; i += 64) {
+      const int r = i / D, e = i % D;
+      const bool in = r < nk;
+      ks[r][e] = in ? (float)kh[((size_t)bh * Tk + k0 + r) * D + e] : 0.f;
+      vs[r][e] = in ? (float)vh[((size_t)bh * Tk + k0 + r) * D + e] : 0.f;
+    }
+    __syncthreads();
+    for (int kk = 0; kk < nk; ++kk) {
+      float s = 0.f;
+#pragma unroll
+      for (int i = 0; i < DL; ++i) s += q[i] * ks[kk][SPLIT * i + j];
+      s = split_sum(s);
+      const float mn = fmaxf(m, s);
+      const float corr = expf(m - mn), p = expf(s - mn);
+      l = l * corr + p;
+#pragma unroll
+      for (int i = 0; i < DL; ++i) acc[i] = acc[i] * corr + p * vs[kk][SPLIT * i + j];
+      m = mn;
+    }
+    __syncthreads();
+  }
+  if (ok) {
+    const float inv = 1.0f / l;
+    T* op = o + ((size_t)b * Tq + qi) * (H * D) + h * D;
+#pragma unroll
+    for (int i = 0; i < DL; ++i) op[SPLIT * i + j] = (T)(acc[i] * inv);
+    if (j == 0) lse[(size_t)bh * Tq + qi] = m + logf(l);
+  }
+}
+
+template <typename T, int D>
+__global__ __launch_bounds__(64) void attn_bwd_dq_ref_split(const T* dout, const T* qh, const T* kh, const T* vh,
+                                                             const float* lse, const float* delta, float scale, T* dqh,
+                                                             int H, int Tq, int Tk) {
+  constexpr int DL = D / SPLIT;
+  __shared__ float ks[TILE][D], vs[TILE][D];
+  const int bh = blockIdx.y, b = bh / H, h = bh % H;
+  const int j = threadIdx.x % SPLIT;
+  const int qi = blockIdx.x * (64 / SPLIT) + threadIdx.x / SPLIT;
+  const bool ok = qi < Tq;
+  const int qc = ok ? qi : 0;
+  const T* qp = qh + ((size_t)bh * Tq + qc) * D;
+  const T* gp = dout + ((size_t)b * Tq + qc) * (H * D) + h * D;
+  float q[DL], g[DL], acc[DL];
+#pragma unroll
+  for (int i = 0; i < DL; ++i) {
+    q[i] = (float)qp[SPLIT * i + j] * scale;
+    g[i] = (float)gp[SPLIT * i + j];
+    acc[i] = 0.f;
+  }
+  const float L = lse[(size_t)bh * Tq + qc], dl = delta[(size_t)bh * Tq + qc];
+  for (int k0 = 0; k0 < Tk; k0 += TILE) {
+    const int nk = min(TILE, Tk - k0);
+    for (int i = threadIdx.x; i < TILE * D; i += 64) {
+      const int r = i / D, e = i % D;
+      const bool in = r < nk;
+      ks[r][e] = in ? (float)kh[((size_t)bh * Tk + k0 + r) * D + e] : 0.f;
+      vs[r][e] = in ? (float)vh[((size_t)bh * Tk + k0 + r) * D + e] : 0.f;
+    }
+    __syncthreads();
+    for (int kk = 0; kk < nk; ++kk) {
+      float s = 0.f, dp = 0.f;
+#pragma unroll
+      for (int i = 0; i < DL; ++i) {
+        s += q[i] * ks[kk][SPLIT * i + j];
+        dp += g[i] * vs[kk][SPLIT * i + j];
+      }
+      s = split_sum(s);
+      dp = split_sum(dp);
+      const float p = expf(s - L);
+      const float ds = p * (dp - dl) * scale;
+#pragma unroll
+      for (int i = 0; i < DL; ++i) acc[i] += ds * ks[kk][SPLIT * i + j];
+    }
+    __syncthreads();
+  }
+  if (ok) {
+    T* op = dqh + ((size_t)bh * Tq + qi) * D;
+#pragma unroll
+    for (int i = 0; i < DL; ++i) op[SPLIT * i + j] = (T)acc[i];
+  }
+}
+
+template <typename T, int D>
+__global__ __launch_bounds__(64) void attn_bwd_dkv_ref_split(const T* dout, const T* qh, const T* kh, const T* vh,
+                                                              const float* lse, const float* delta, float scale, T* dkh,
+                                                              T* dvh, int H, int Tq, int Tk) {
+  constexpr int DL = D / SPLIT;
+  __shared__ float qs[TILE][D], gs[TILE][D];
+  __shared__ float ls[TILE], ds_[TILE];
+  const int bh = blockIdx.y, b = bh / H, h = bh % H;
+  const int j = threadIdx.x % SPLIT;
+  const int ki = blockIdx.x * (64 / SPLIT) + threadIdx.x / SPLIT;
+  const bool ok = ki < Tk;
+  const int kc = ok ? ki : 0;
+  float k[DL], v[DL], dk[DL], dv[DL];
+#pragma unroll
+  for (int i = 0; i < DL; ++i) {
+    k[i] = (float)kh[((size_t)bh * Tk + kc) * D + SPLIT * i + j];
+    v[i] = (float)vh[((size_t)bh * Tk + kc) * D + SPLIT * i + j];
+    dk[i] = 0.f;
+    dv[i] = 0.f;
+  }
+  for (int q0 = 0; q0 < Tq; q0 += TILE) {
+    const int nq = min(TILE, Tq - q0);
+    for (int i = threadIdx.x; i < TILE * D; i += 64) {
+      const int r = i / D, e = i % D;
+      const bool in = r < nq;
+      qs[r][e] = in ? (float)qh[((size_t)bh * Tq + q0 + r) * D + e] : 0.f;
+      gs[r][e] = in ? (float)dout[((size_t)b * Tq + q0 + r) * (H * D) + h * D + e] : 0.f;
+    }
+    if (threadIdx.x < TILE) {
+      const bool in = threadIdx.x < nq;
+      ls[threadIdx.x] = in ? lse[(size_t)bh * Tq + q0 + threadIdx.x] : 0.f;
+      ds_[threadIdx.x] = in ? delta[(size_t)bh * Tq + q0 + threadIdx.x] : 0.f;
+    }
+    __syncthreads();
+    for (int qq = 0; qq < nq; ++qq) {
+      float s = 0.f, dp = 0.f;
+#pragma unroll
+      for (int i = 0; i < DL; ++i) {
+        s += qs[qq][SPLIT * i + j] * k[i];
+        dp += gs[qq][SPLIT * i + j] * v[i];
+      }
+      s = split_sum(s);
+      dp = split_sum(dp);
+      const float p = expf(s * scale - ls[qq]);
+      const float dsv = p * (dp - ds_[qq]) * scale;
+#pragma unroll
+      for (int i = 0; i < DL; ++i) {
+        dv[i] += p * gs[qq][SPLIT * i + j];
+        dk[i] += dsv * qs[qq][SPLIT * i + j];
+      }
+    }
+    __syncthreads();
+  }
+  if (ok) {
+#pragma unroll
+    for (int i = 0; i < DL; ++i) {
+      dkh[((size_t)bh * Tk + ki) * D + SPLIT * i + j] = (T)dk[i];
+      dvh[((size_t)bh * Tk + ki) * D + SPLIT * i + j] = (T)dv[i];
+    }
+  }
+}
+
 }  // namespace
 
 int nvit_attn_fwd_mfma(const void* qh, const void* kh, const void* vh, float scale, float qpre, const float* sqk,
@@ -224,7 +399,7 @@ extern "C" int nvit_attn_fwd_bounded(int dt, int impl, const void* qh, const voi
 
 static int attn_fwd_impl(int dt, int impl, const void* qh, const void* kh, const void* vh, float scale, const float* sqk,
                          float c_q, float qpre, void* o, float* lse, int B, int H, int Tq, int Tk, int d, void* stream) {
-  NVIT_REQUIRE(d == 32 || d == 64, "attn_fwd: head dim %d unsupported (32 or 64)", d);
+  NVIT_REQUIRE(d == 32 || d == 64 || d == 128, "attn_fwd: head dim %d unsupported (32, 64 or 128)", d);
   NVIT_REQUIRE(B > 0 && H > 0 && Tq > 0 && Tk > 0, "attn_fwd: empty problem");
   hipStream_t s = (hipStream_t)stream;
   ProfScope ps(NVIT_KID_ATTN_FWD, 4.0 * B * H * (double)Tq * Tk * d, 0.0, s);
@@ -233,12 +408,16 @@ static int attn_fwd_impl(int dt, int impl, const void* qh, const void* kh, const
     return nvit_attn_fwd_mfma(qh, kh, vh, scale, qpre, sqk, c_q, o, lse, B, H, Tq, Tk, d, s);
   }
   scale = scale / qpre;   // the scalar kernels take the multiplier of q.k directly
-  dim3 grid(cdiv(Tq, 64), B * H);
+  dim3 grid(cdiv(Tq, 64), B * H), grid_split(cdiv(Tq, 64 / SPLIT), B * H);
 #define L(T, D) \
   hipLaunchKernelGGL((attn_fwd_ref<T, D>), grid, dim3(64), 0, s, (const T*)qh, (const T*)kh, (const T*)vh, scale, (T*)o, lse, H, Tq, Tk)
-  if (dt == NVIT_F32) { if (d == 32) L(float, 32); else L(float, 64); }
-  else { if (d == 32) L(bf16, 32); else L(bf16, 64); }
+#define LS(T, D)                                                                                                       \
+  hipLaunchKernelGGL((attn_fwd_ref_split<T, D>), grid_split, dim3(64), 0, s, (const T*)qh, (const T*)kh, (const T*)vh,  \
+                     scale, (T*)o, lse, H, Tq, Tk)
+  if (dt == NVIT_F32) { if (d == 32) L(float, 32); else if (d == 64) L(float, 64); else LS(float, 128); }
+  else { if (d == 32) L(bf16, 32); else if (d == 64) L(bf16, 64); else LS(bf16, 128); }
 #undef L
+#undef LS
   NVIT_CHECK_LAUNCH("attn_fwd_ref");
   return NVIT_OK;
 }
@@ -246,7 +425,7 @@ static int attn_fwd_impl(int dt, int impl, const void* qh, const void* kh, const
 extern "C" int nvit_attn_bwd(int dt, int impl, const void* dout, const void* qh, const void* kh, const void* vh,
                              const void* o, const float* lse, float scale, void* dqh, void* dkh, void* dvh,
                              float* delta, int B, int H, int Tq, int Tk, int d, void* stream) {
-  NVIT_REQUIRE(d == 32 || d == 64, "attn_bwd: head dim %d unsupported (32 or 64)", d);
+  NVIT_REQUIRE(d == 32 || d == 64 || d == 128, "attn_bwd: head dim %d unsupported (32, 64 or 128)", d);
   NVIT_REQUIRE(B > 0 && H > 0 && Tq > 0 && Tk > 0, "attn_bwd: empty problem");
   hipStream_t s = (hipStream_t)stream;
   ProfScope ps(NVIT_KID_ATTN_BWD, 10.0 * B * H * (double)Tq * Tk * d, 0.0, s);
@@ -271,9 +450,18 @@ extern "C" int nvit_attn_bwd(int dt, int impl, const void* dout, const void* qh,
     hipLaunchKernelGGL((attn_bwd_dkv_ref<T, D>), gk, dim3(64), 0, s, (const T*)dout, (const T*)qh, (const T*)kh,      \
                        (const T*)vh, lse, delta, scale, (T*)dkh, (T*)dvh, H, Tq, Tk);                                 \
   } while (0)
-  if (dt == NVIT_F32) { if (d == 32) L(float, 32); else L(float, 64); }
-  else { if (d == 32) L(bf16, 32); else L(bf16, 64); }
+  dim3 gqs(cdiv(Tq, 64 / SPLIT), B * H), gks(cdiv(Tk, 64 / SPLIT), B * H);
+#define LS(T, D)                                                                                                      \
+  do {                                                                                                                \
+    hipLaunchKernelGGL((attn_bwd_dq_ref_split<T, D>), gqs, dim3(64), 0, s, (const T*)dout, (const T*)qh, (const T*)kh, \
+                       (const T*)vh, lse, delta, scale, (T*)dqh, H, Tq, Tk);                                          \
+    hipLaunchKernelGGL((attn_bwd_dkv_ref_split<T, D>), gks, dim3(64), 0, s, (const T*)dout, (const T*)qh,             \
+                       (const T*)kh, (const T*)vh, lse, delta, scale, (T*)dkh, (T*)dvh, H, Tq, Tk);                   \
+  } while (0)
+  if (dt == NVIT_F32) { if (d == 32) L(float, 32); else if (d == 64) L(float, 64); else LS(float, 128); }
+  else { if (d == 32) L(bf16, 32); else if (d == 64) L(bf16, 64); else LS(bf16, 128); }
 #undef L
+#undef LS
   NVIT_CHECK_LAUNCH("attn_bwd_ref");
   return NVIT_OK;
 }

@@ -32,6 +32,7 @@ from .config import ViTConfig
 from .kohonen import CosConsistencyFn, HuberFn, KohonenMap, MapSmoothnessFn
 
 Tensor = torch.Tensor
+HEAD_DIMS = (32, 64, 128)   # attention head dims n_embd // n_head the kernels cover
 
 
 def _dt_from_precision(p: str) -> int:
@@ -837,8 +838,8 @@ class ViT(nn.Module):
             raise NotImplementedError("only use_nvit=True is supported (the reference's non-nViT path crashes upstream)")
         if config.n_embd % config.n_head != 0 or config.n_embd % 64 != 0:
             raise ValueError("n_embd must be a multiple of 64 and divisible by n_head")
-        if (config.n_embd // config.n_head) not in (32, 64):
-            raise ValueError("head dim must be 32 or 64")
+        if (config.n_embd // config.n_head) not in HEAD_DIMS:
+            raise ValueError(f"head dim must be one of {HEAD_DIMS} (got {config.n_embd // config.n_head})")
         self.config = config
         self.step = 0
         self.total_steps = 0
@@ -907,9 +908,11 @@ class ViT(nn.Module):
         return self
 
     def _attn_impl(self) -> int:
-        """1: the MFMA flash kernels (bf16, head dim 64); 0: the scalar-FMA kernels."""
+        """1: the MFMA flash kernels (bf16 mode, every supported head dim: 32, 64, 128); 0: the scalar-FMA kernels (fp32
+        mode).  The fused q/k-normalise paths (GEMM epilogue, attention backward) are head dim 64 only; the other head dims
+        take the unfused route (fp32 projection, qknorm_fwd, attn_fwd bounded, attn_bwd, qknorm_bwd)."""
         d = self.config.n_embd // self.config.n_head
-        return 1 if (self.precision == "bf16" and d == 64) else 0
+        return 1 if (self.precision == "bf16" and d in HEAD_DIMS) else 0
 
     def _prepare(self, device) -> None:
         if device.type != "cuda":
