@@ -8,19 +8,24 @@ AdamW -> zero_grad -> weight re-normalisation, on one synthetic batch resident i
   python bench.py --gpus 1 --steps K --warmup W            (single GPU)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0 (see README/DESIGN for the fields).  The `roofline` object
-is for the dominant kernel family (the plain-epilogue NT MFMA GEMM): algorithmic FLOPs of its
-launches over their HIP-event durations inside the timed region; `roofline.families` lists
-EVERY MFMA family of the step (plain NT, each fused epilogue, weight-gradient TN, attention
-forward / backward) with its own achieved TFLOP/s and fraction, so the weakest one is visible.
-The peak is derived from the device (CU count x 4096 bf16 FLOP/clk/CU x max clock), both printed.
-`cpu_baseline` times the CPU oracle (a port of the reference semantics, fp32) on this box's host
-cores as BASELINE.md §3 prescribes: C2 (Base) at B=8, 3 steps after one warm-up, and C1 (Tiny) at
-B=32, 10 steps.  `--check` runs the full-shape numeric check (tools/fullshape_check.py) and an
-end-to-end comparison after the timed region.  `--dump-outputs DIR` writes what the last timed step returned
-(logits, loss, aux losses, clipped gradient norm) and a fixed sample of the weights it left behind as DIR/<name>.npy
-(float32), so that two builds can be compared output for output: weights, inputs and the sample are seeded, so the
-same arguments give the same inputs on every run.
+Prints ONE JSON line on rank 0 (see README/DESIGN for the fields).  A plain run does only what
+that line's headline needs: set up, warm up, time the steps, write --dump-outputs, print.  The
+`roofline` object is for the dominant kernel family (the plain-epilogue NT MFMA GEMM): algorithmic
+FLOPs of its launches over their HIP-event durations inside the timed region.  The peak is derived
+from the device (CU count x 4096 bf16 FLOP/clk/CU x max clock), both printed.
+`--full` adds everything that takes work of its own after the timed region:
+`roofline.families` / `kernel_ms_per_step` / `hbm_kernels` list EVERY kernel family of the step
+(plain NT, each fused epilogue, weight-gradient TN, attention forward / backward, row kernels,
+optimizer) with its own achieved figures, so the weakest one is visible, from three more steps with
+every launch timed; the stand-alone renorm kernel is timed; `parity` compares the benchmarked
+precision with the exact-f32 mode; and `cpu_baseline` times the CPU oracle (a port of the reference
+semantics, fp32) on the host cores as BASELINE.md §3 prescribes: C2 (Base) at B=8, 3 steps after one
+warm-up, and C1 (Tiny) at B=32, 10 steps.  `--check` runs the full-shape numeric check
+(tools/fullshape_check.py) and an end-to-end comparison after the timed region.  `--dump-outputs DIR`
+writes what the last timed step returned (logits, loss, aux losses, clipped gradient norm) and a fixed
+sample of the weights it left behind as DIR/<name>.npy (float32), so that two builds can be compared
+output for output: weights, inputs and the sample are seeded, so the same arguments give the same
+inputs on every run.
 """
 from __future__ import annotations
 
@@ -199,13 +204,17 @@ def main() -> None:
     ap.add_argument("--config", default="base")
     ap.add_argument("--batch", type=int, default=128, help="per-GPU batch")
     ap.add_argument("--precision", default="bf16")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure what the headline does not need: the per-family kernel "
+                         "breakdown (three more fully timed steps), the stand-alone renorm kernel, parity against the "
+                         "exact-f32 mode and the CPU oracle baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle baseline")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL); gloo for rehearsals")
     ap.add_argument("--collective", default="rccl", choices=["rccl", "xgmi"],
                     help="gradient exchange: torch.distributed all-reduce (RCCL; default) or the direct xGMI collective")
     ap.add_argument("--share-gpu", action="store_true",
                     help="rehearsal only: all ranks use cuda:0 (needs --backend gloo); not a valid benchmark")
-    ap.add_argument("--cpu-sample-batch", type=int, default=8)
+    ap.add_argument("--cpu-sample-batch", type=int, default=8, help="with --full: batch of the CPU oracle baseline")
     ap.add_argument("--check", action="store_true",
                     help="after the timed region: numeric check of every GEMM shape / epilogue and of attention at this "
                          "batch size (tools/fullshape_check.py) and bf16 B=batch logits vs the exact-f32 mode")
@@ -267,8 +276,8 @@ def main() -> None:
     for _ in range(args.warmup):
         train_step(step_model, opt, X, y, 1.0, sync_grads=sync)
     barrier()
-    prof_steps = args.steps
     timed_gemm_nt = None      # plain gemm_nt launches timed INSIDE the timed region (eager path)
+    prof, prof_steps = None, 0  # per-family breakdown from fully timed steps behind the timed region (--full)
     if args.graph:
         if world > 1:
             raise SystemExit("--graph is single-process (the data-parallel step runs eagerly)")
@@ -282,16 +291,10 @@ def main() -> None:
         dt = time.perf_counter() - t0
         if args.dump_outputs and rank == 0:
             dumped = snapshot_outputs(model, logits, loss, aux, gnorm)
-        prof_steps = min(args.steps, 3)
-        ops.prof_enable(True)
-        ops.prof_collect()
-        for _ in range(prof_steps):
-            train_step(step_model, opt, X, y, 1.0)
-        barrier()
     else:
         # timed region: HIP events only around the launches of the dominant kernel (plain gemm_nt: what `roofline.achieved`
-        # is made of); the per-family breakdown comes from `prof_steps` more steps behind it, with every launch timed
-        # (an event pair per launch costs the step 0.3-1.0 ms at ~400 launches)
+        # is made of); with --full the per-family breakdown comes from `prof_steps` more steps behind it, with every launch
+        # timed (an event pair per launch costs the step 0.3-1.0 ms at ~400 launches)
         ops.prof_select("gemm_nt")
         ops.prof_collect()
         t0 = time.perf_counter()
@@ -303,13 +306,14 @@ def main() -> None:
             dumped = snapshot_outputs(model, logits, loss, aux, gnorm)
         ops.prof_enable(False)
         timed_gemm_nt = ops.prof_collect()["gemm_nt"]
+    if args.full:
         prof_steps = min(args.steps, 3)
         ops.prof_enable(True)
         for _ in range(prof_steps):
             train_step(step_model, opt, X, y, 1.0, sync_grads=sync)
         barrier()
-    ops.prof_enable(False)
-    prof = ops.prof_collect()
+        ops.prof_enable(False)
+        prof = ops.prof_collect()
     if world > 1:
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -345,9 +349,9 @@ def main() -> None:
                      "ranks": every}
 
     # stand-alone nvit_renorm_weights (the kernel north_star singles out; the step itself uses the fused optimizer):
-    # 10 warm calls, outside the timed region
+    # 10 warm calls, outside the timed region (--full)
     renorm_warm = None
-    if rank == 0:
+    if args.full and rank == 0:
         for _ in range(3):
             normalize_matrices(model)
         torch.cuda.synchronize()
@@ -402,28 +406,7 @@ def main() -> None:
                     d["traffic_over_algorithmic"] = round(t / (f["bytes"] / f["launches"]), 3)
             return d
 
-        g = timed_gemm_nt or prof["gemm_nt"]   # plain-epilogue bf16 NT GEMMs: the dominant kernel of the step
-        ach = g["flops"] / (g["ms"] * 1e-3) / 1e12 if g["ms"] > 0 else 0.0
-        fused_keys = ("gemm_swiglu", "gemm_qknorm", "gemm_swiglu_bwd")
-        fam_ms = prof["gemm_nt"]["ms"] + sum(prof[k]["ms"] for k in fused_keys)
-        fam_fl = prof["gemm_nt"]["flops"] + sum(prof[k]["flops"] for k in fused_keys)
-        fam = fam_fl / (fam_ms * 1e-3) / 1e12 if fam_ms > 0 else 0.0
-        families = {
-            "gemm_nt_plain": fam_of("gemm_nt", "gemm_nt_persistent EPI 1/2 (bf16 / fp32 store)", pmc_key="gemm_nt_plain"),
-            "gemm_nt_swiglu": fam_of("gemm_swiglu", "gemm_nt_persistent EPI 3 (c_fc + suv + SwiGLU)", pmc_key="gemm_nt_epi3"),
-            "gemm_nt_qknorm": fam_of("gemm_qknorm", "gemm_nt_persistent EPI 4 (qkv + per-head normalise + sqk)", pmc_key="gemm_nt_epi4"),
-            "gemm_nt_swiglu_bwd": fam_of("gemm_swiglu_bwd", "gemm_nt_persistent EPI 5 (mlp_c_proj dgrad + SwiGLU backward)", pmc_key="gemm_nt_epi5"),
-            "gemm_tn_wgrad": fam_of("gemm_tn", "gemm_tn_persistent + slab_reduce (weight gradients)", pmc_key="gemm_tn"),
-            "attn_fwd": fam_of("attn_fwd", "attn_fwd_mfma (4*B*H*T^2*d)"),
-            # algorithmic backward = 10*B*H*T^2*d (five products); the two-kernel form executes 14 (S and dP twice)
-            "attn_bwd": fam_of("attn_bwd", "attn_bwd_dq_mfma + attn_bwd_dkv_mfma (10*B*H*T^2*d algorithmic)", 1.4),
-        }
-        if args.precision == "bf16":
-            # fused dual patch embedding: executed flops = 3 bf16 products per element (hi*hi + lo*hi + hi*lo)
-            families["patch_embed"] = fam_of("patchify", "patch_embed (image gather -> LDS, split-operand MFMA, bias+pos epilogue; "
-                                                         "3 x 2*M*C*(Kl+Kg) executed)")
-        families = {k: v for k, v in families.items() if v}
-        weakest = min(families, key=lambda k: families[k]["frac"]) if families else None
+        g = timed_gemm_nt or (prof or {}).get("gemm_nt")   # plain-epilogue bf16 NT GEMMs: the dominant kernel of the step
         # algorithmic bytes of an average plain gemm_nt launch: A [M,K] bf16 + B [N,K] bf16 + C [M,N] (4 B: fp32 outputs dominate)
         T = (cfg.image_size // cfg.local_patch_size) ** 2
         out = {
@@ -439,54 +422,81 @@ def main() -> None:
             "step_mfma_frac": round(value * gf / 1e3 / (world * peak), 4),
             "device": {"name": torch.cuda.get_device_name(dev), "compute_units": cus, "max_clock_mhz": round(mhz, 1),
                        "peak_bf16_tflops_from_props": round(peak, 1), "nominal_peak_bf16_tflops": NOMINAL_PEAK_BF16_TFLOPS},
-            "roofline": {"bound": "mfma", "kernel": "gemm_nt (persistent 256x256 tile, bf16 v_mfma_f32_16x16x32, LDS-DMA ring)",
-                         "achieved": round(ach, 1), "peak": round(peak, 1), "unit": "TFLOP/s",
-                         "frac": round(ach / peak, 4), "traffic": traffic, "traffic_source": traffic_src,
-                         "launches": g["launches"], "avg_launch_ms": round(g["ms"] / max(1, g["launches"]), 4),
-                         "family_achieved_incl_fused_epilogues": round(fam, 1),
-                         "families": families, "weakest_family": weakest},
-            "kernel_ms_per_step": {k: round(v["ms"] / prof_steps, 3) for k, v in prof.items() if v["launches"]},
         }
-        # HBM-bound kernels of the path: algorithmic bytes (as declared at each launch) / HIP-event time, vs 8 TB/s
-        n_upd = opt._cache["n_elems"] if getattr(opt, "_cache", None) else sum(p.numel() for p in model.parameters())
-        hbm = {}
-        for fam, label in (("rowops", "row kernels (LERP/norm_skip fwd+bwd, reductions)"),
-                           ("shadow", "bf16 operand copies of the weights")):
-            f = prof.get(fam)
-            if f and f["ms"] > 0 and f["bytes"] > 0:
-                hbm[fam] = {"what": label, "GB/s": round(f["bytes"] / (f["ms"] * 1e-3) / 1e9, 1),
-                            "frac_of_8TB/s": round(f["bytes"] / (f["ms"] * 1e-3) / 8e12, 3)}
-        f = prof.get("optim")
-        if f and f["ms"] > 0:
-            by = 32.0 * n_upd * prof_steps   # p,g,m,v read + p,m,v written + g read again for the global norm
-            hbm["optimizer+renorm"] = {"what": "clip + AdamW + normalize_matrices, 32 B/parameter",
-                                       "GB/s": round(by / (f["ms"] * 1e-3) / 1e9, 1),
-                                       "frac_of_8TB/s": round(by / (f["ms"] * 1e-3) / 8e12, 3)}
-        if renorm_warm:
-            hbm["renorm_standalone"] = renorm_warm
-        out["hbm_kernels"] = hbm
-        # plain gemm_nt launches of the step: algorithmic bytes = A + B read once, C written once, as each launch declared
-        # them (the same figure the family entry uses, so the two ratios cannot disagree)
-        if g["launches"] and g["bytes"] > 0:
-            alg = g["bytes"] / g["launches"]
-            out["roofline"]["algorithmic_bytes"] = round(alg)
-            if traffic:
-                out["roofline"]["traffic_over_algorithmic"] = round(traffic / alg, 3)
-        out["roofline"]["traffic_measured_in_run"] = False   # PMC counters come from the committed rocprofv3 passes named above
+        if g:
+            ach = g["flops"] / (g["ms"] * 1e-3) / 1e12 if g["ms"] > 0 else 0.0
+            out["roofline"] = {"bound": "mfma",
+                               "kernel": "gemm_nt (persistent 256x256 tile, bf16 v_mfma_f32_16x16x32, LDS-DMA ring)",
+                               "achieved": round(ach, 1), "peak": round(peak, 1), "unit": "TFLOP/s",
+                               "frac": round(ach / peak, 4), "traffic": traffic, "traffic_source": traffic_src,
+                               "launches": g["launches"], "avg_launch_ms": round(g["ms"] / max(1, g["launches"]), 4)}
+            # plain gemm_nt launches of the step: algorithmic bytes = A + B read once, C written once, as each launch declared
+            # them (the same figure the family entry uses, so the two ratios cannot disagree)
+            if g["launches"] and g["bytes"] > 0:
+                alg = g["bytes"] / g["launches"]
+                out["roofline"]["algorithmic_bytes"] = round(alg)
+                if traffic:
+                    out["roofline"]["traffic_over_algorithmic"] = round(traffic / alg, 3)
+            out["roofline"]["traffic_measured_in_run"] = False   # PMC counters come from the committed rocprofv3 passes named above
+        if args.full:
+            fused_keys = ("gemm_swiglu", "gemm_qknorm", "gemm_swiglu_bwd")
+            fam_ms = prof["gemm_nt"]["ms"] + sum(prof[k]["ms"] for k in fused_keys)
+            fam_fl = prof["gemm_nt"]["flops"] + sum(prof[k]["flops"] for k in fused_keys)
+            fam = fam_fl / (fam_ms * 1e-3) / 1e12 if fam_ms > 0 else 0.0
+            families = {
+                "gemm_nt_plain": fam_of("gemm_nt", "gemm_nt_persistent EPI 1/2 (bf16 / fp32 store)", pmc_key="gemm_nt_plain"),
+                "gemm_nt_swiglu": fam_of("gemm_swiglu", "gemm_nt_persistent EPI 3 (c_fc + suv + SwiGLU)", pmc_key="gemm_nt_epi3"),
+                "gemm_nt_qknorm": fam_of("gemm_qknorm", "gemm_nt_persistent EPI 4 (qkv + per-head normalise + sqk)", pmc_key="gemm_nt_epi4"),
+                "gemm_nt_swiglu_bwd": fam_of("gemm_swiglu_bwd", "gemm_nt_persistent EPI 5 (mlp_c_proj dgrad + SwiGLU backward)", pmc_key="gemm_nt_epi5"),
+                "gemm_tn_wgrad": fam_of("gemm_tn", "gemm_tn_persistent + slab_reduce (weight gradients)", pmc_key="gemm_tn"),
+                "attn_fwd": fam_of("attn_fwd", "attn_fwd_mfma (4*B*H*T^2*d)"),
+                # algorithmic backward = 10*B*H*T^2*d (five products); the two-kernel form executes 14 (S and dP twice)
+                "attn_bwd": fam_of("attn_bwd", "attn_bwd_dq_mfma + attn_bwd_dkv_mfma (10*B*H*T^2*d algorithmic)", 1.4),
+            }
+            if args.precision == "bf16":
+                # fused dual patch embedding: executed flops = 3 bf16 products per element (hi*hi + lo*hi + hi*lo)
+                families["patch_embed"] = fam_of("patchify", "patch_embed (image gather -> LDS, split-operand MFMA, bias+pos "
+                                                             "epilogue; 3 x 2*M*C*(Kl+Kg) executed)")
+            families = {k: v for k, v in families.items() if v}
+            weakest = min(families, key=lambda k: families[k]["frac"]) if families else None
+            out["roofline"].update({"family_achieved_incl_fused_epilogues": round(fam, 1),
+                                    "families": families, "weakest_family": weakest})
+            out["kernel_ms_per_step"] = {k: round(v["ms"] / prof_steps, 3) for k, v in prof.items() if v["launches"]}
+            # HBM-bound kernels of the path: algorithmic bytes (as declared at each launch) / HIP-event time, vs 8 TB/s
+            n_upd = opt._cache["n_elems"] if getattr(opt, "_cache", None) else sum(p.numel() for p in model.parameters())
+            hbm = {}
+            for fam, label in (("rowops", "row kernels (LERP/norm_skip fwd+bwd, reductions)"),
+                               ("shadow", "bf16 operand copies of the weights")):
+                f = prof.get(fam)
+                if f and f["ms"] > 0 and f["bytes"] > 0:
+                    hbm[fam] = {"what": label, "GB/s": round(f["bytes"] / (f["ms"] * 1e-3) / 1e9, 1),
+                                "frac_of_8TB/s": round(f["bytes"] / (f["ms"] * 1e-3) / 8e12, 3)}
+            f = prof.get("optim")
+            if f and f["ms"] > 0:
+                by = 32.0 * n_upd * prof_steps   # p,g,m,v read + p,m,v written + g read again for the global norm
+                hbm["optimizer+renorm"] = {"what": "clip + AdamW + normalize_matrices, 32 B/parameter",
+                                           "GB/s": round(by / (f["ms"] * 1e-3) / 1e9, 1),
+                                           "frac_of_8TB/s": round(by / (f["ms"] * 1e-3) / 8e12, 3)}
+            if renorm_warm:
+                hbm["renorm_standalone"] = renorm_warm
+            out["hbm_kernels"] = hbm
         # eager: HIP events around the plain gemm_nt launches only inside the timed region (`roofline.achieved`, `launches`,
-        # `avg_launch_ms` are from there); families / kernel_ms_per_step from `prof_steps` fully timed steps behind it
+        # `avg_launch_ms` are from there); with --full, families / kernel_ms_per_step from `prof_steps` fully timed steps
+        # behind it
         out["timed_with_event_profiling"] = "gemm_nt launches only" if timed_gemm_nt else False
-        out["family_breakdown_from"] = f"{prof_steps} fully timed steps behind the timed region"
+        if args.full:
+            out["family_breakdown_from"] = f"{prof_steps} fully timed steps behind the timed region"
         if dist_info is not None:
             out["dist"] = dist_info
-        if world == 1:
+        if args.full and world == 1:
             out["parity"] = run_parity(model, cfg, args, X)
         if args.check:
             out["check"] = run_check(model, cfg, args, X, dev)
         if args.graph:
             out["graph"] = True
-            out["roofline"]["source"] = f"{prof_steps} eager steps after the timed hipGraph replays"
-        if world == 1 and not args.no_cpu_baseline:
+            if g:
+                out["roofline"]["source"] = f"{prof_steps} eager steps after the timed hipGraph replays"
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 avail = len(os.sched_getaffinity(0))
             except AttributeError:

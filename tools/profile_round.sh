@@ -2,9 +2,9 @@
 TAG=${1:-r04}
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 D=gpurun_out/prof_$TAG
-CMD="python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline"
+CMD="python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline"
 timeout -k 10 280 rocprofv3 --kernel-trace --stats --output-format csv -d $D/trace -- $CMD > gpurun_out/prof_${TAG}_trace.log 2>&1 || exit 1
-CMD1="python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline"
+CMD1="python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline"
 timeout -k 10 280 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $D/fetch -- $CMD1 > gpurun_out/prof_${TAG}_fetch.log 2>&1 || exit 1
 timeout -k 10 280 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $D/write -- $CMD1 > gpurun_out/prof_${TAG}_write.log 2>&1 || exit 1
 timeout -k 10 280 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE --output-format csv -d $D/mfma -- $CMD1 > gpurun_out/prof_${TAG}_mfma.log 2>&1 || exit 1
