@@ -128,6 +128,8 @@ int nvit_gemm_nt(int dt, const void* A, int lda, const void* B, int ldb, void* C
  * nvit_gemm_nt_qknorm: q/k/v projections (nparts stacked [C,K] weights starting at part part0: 0=q,1=k,2=v) with
  *   the per-head L2 normalise, sqk*c_q scale and [B,H,T,64] head split done on the fp32 accumulators
  *   (model.py:99-119); rq/rk [M,H] = 1/||.||.  Requires head dim 64 and n_embd % 256 == 0.
+ *   sqk == NULL: the head split alone (plain-ViT attention, model.py:97-100): no normalise, q multiplied by
+ *   q_prescale only, k and v stored as they are; rq, rk and c_q are not used.
  * nvit_gemm_nt_swiglu_bwd: autograd of model.py:148-155 / 259-262 in one launch: dx[M,F] = A B^T (A = dL/dy of
  *   mlp_c_proj / out_proj, B = that weight's transposed shadow [F,K]) stays in the accumulators; with the saved raw
  *   uv[M,2F] (interleaved, as written by nvit_gemm_nt_swiglu) it writes duv[M,2F] (same layout) and, when gs != NULL
@@ -187,6 +189,26 @@ int nvit_lerp_bwd(int dt, const float* dout, const void* dout_add, const float* 
 int nvit_rmsnorm_fwd(const float* x, const float* w, float eps, float* out, float* rstd, int M, int C, void* stream);
 int nvit_rmsnorm_bwd(const float* dout, const float* x, const float* w, const float* rstd, float* dx, float* part_dw,
                      int nblk, int M, int C, void* stream);
+/* Residual + RMSNorm row kernels of the plain-ViT block (use_nvit=False, model.py:92-169 with the RMSNorm modules built):
+ * nvit_res_rmsnorm_fwd: out = z * rsqrt(mean(z^2) + eps) * w, z = a + y (y of type y_dt, or NULL: z = a); out fp32
+ * [M,C], out_lo (type dt, may be NULL) = cast(out), rstd [M].  z itself is not stored.
+ * nvit_res_rmsnorm_bwd: from g (+ g_add, type dt, may be NULL: a data-gradient GEMM's output) recomputes z = a + y and
+ * writes dz fp32 (added to dz if accum), dz_lo (type dt, may be NULL) = cast(dz), and per-WAVE partial sums part_dw
+ * [4*nblk, C] of d(w) (reduce with nvit_colsum_reduce).  nblk <= 4096 workgroups of 4 waves. */
+int nvit_res_rmsnorm_fwd(int dt, const float* a, const void* y, int y_dt, const float* w, float eps, float* out,
+                         void* out_lo, float* rstd, int M, int C, void* stream);
+int nvit_res_rmsnorm_bwd(int dt, const float* g, const void* g_add, const float* a, const void* y, int y_dt,
+                         const float* w, const float* rstd, float* dz, int accum, void* dz_lo, float* part_dw, int nblk,
+                         int M, int C, void* stream);
+/* nvit_res_skip_fwd: out = nrm((h + y) * skip[0] + x)  (norm_skip after a plain-ViT block, model.py:84-87,450-452);
+ * h, x fp32 [M,C], y of type y_dt; out fp32, out_lo (type dt, may be NULL) = cast(out).
+ * nvit_res_skip_bwd: dx = d(x) fp32 (written), dh = d(h + y) fp32, dh_lo (type dt, may be NULL) = cast(dh), and per-WAVE
+ * partial sums part_dskip [4*nblk] of d(skip). */
+int nvit_res_skip_fwd(int dt, const float* h, const void* y, int y_dt, const float* skip, const float* x, float* out,
+                      void* out_lo, int M, int C, void* stream);
+int nvit_res_skip_bwd(int dt, const float* dout, const float* h, const void* y, int y_dt, const float* skip,
+                      const float* x, float* dh, void* dh_lo, float* dx, float* part_dskip, int nblk, int M, int C,
+                      void* stream);
 /* Block.norm_skip on its own (model.py:84-87): out = nrm(src*skip[0] + tgt), fp32 [M,C]; backward writes dsrc, dtgt
  * (tgt == NULL / dtgt == NULL: the target term is absent, i.e. justnorm(src*skip[0]), model.py:43-44,89-90)
  * and part_dskip [nblk]. (ViT.forward uses the copy fused into nvit_lerp_fwd/bwd.) */
@@ -197,12 +219,16 @@ int nvit_norm_skip_bwd(const float* dout, const float* src, const float* tgt, co
 /* nvit_qknorm_fwd: per-head cosine normalise + learned scale + head split (model.py:104-119,231-247)
  * q/k/v sources: row-major, type dt, row stride ld* elements, C columns each.
  * qh = (sqk*c_q) * nrm_d(q) etc. written [B,H,T,d] type dt; v copied to [B,H,T,d];
- * rq, rk [M,H] fp32 = 1/||q_head||. */
+ * rq, rk [M,H] fp32 = 1/||q_head||.
+ * sqk == NULL: the head split alone (plain-ViT attention, model.py:97-100): q, k, v copied to [B,H,T,d] as they are
+ * (type conversion only); rq, rk are not written. */
 int nvit_qknorm_fwd(int dt, const void* q, int ldq, const void* k, int ldk, const void* v, int ldv,
                     const float* sqk, float c_q, void* qh, void* kh, void* vh, float* rq, float* rk, int B,
                     int T, int H, int d, void* stream);
 /* nvit_qknorm_bwd: dq/dk/dv (type dt, row strides ld*) from dqh/dkh/dvh [B,H,T,d]; part_dsqk
- * [nblk, C] partial sums of d/d(sqk*c_q). */
+ * [nblk, C] partial sums of d/d(sqk*c_q).
+ * sqk == NULL: the backward of the plain split, i.e. the head merge dq/dk/dv = dqh/dkh/dvh (dt F32 or BF16; qh, kh, rq, rk,
+ * part_dsqk and nblk are not used). */
 int nvit_qknorm_bwd(int dt, const void* dqh, const void* dkh, const void* dvh, const void* qh, const void* kh,
                     const float* rq, const float* rk, const float* sqk, float c_q, void* dq, int ldq,
                     void* dk, int ldk, void* dv, int ldv, float* part_dsqk, int nblk, int B, int T, int H,
@@ -236,7 +262,7 @@ int nvit_cast(const float* src, void* dst, int dt, int64_t n, void* stream);
  * = (in - mean) / std.  (The reference's randomised AutoAugment policy is third-party kornia code: not rebuilt.) */
 int nvit_normalize_images(const void* in, int in_is_u8_hwc, float* out, int B, int C, int H, int W, float mean, float std_,
                           void* stream);
-/* out[r,n] = a[r,n] * s[n] * c   (sz scaling model.py:466-468 and its backward) */
+/* out[r,n] = a[r,n] * s[n] * c   (sz scaling model.py:466-468 and its backward); s == NULL: out = a * c */
 int nvit_scale_cols(const float* a, int lda, const float* s, float c, void* out, int out_dt, int ldo, int R, int N,
                     void* stream);
 
@@ -249,7 +275,9 @@ int nvit_attn_fwd(int dt, int impl, const void* qh, const void* kh, const void* 
                   int B, int H, int Tq, int Tk, int d, void* stream);
 /* Same, for the nViT call sites where q and k are (sqk*c_q) * unit vectors per head (model.py:108-112): every score is
  * bounded by max_d (sqk_d*c_q)^2, and while that bound is small (it is 1 at initialisation) the MFMA kernel takes
- * probabilities relative to the bound instead of a running maximum (no per-tile max / rescale).  sqk: [H*d] fp32.
+ * probabilities relative to the bound instead of a running maximum (no per-tile max / rescale).  sqk: [H*d] fp32;
+ * NULL: no bound - the running-maximum kernel on a q pre-scaled by q_prescale (plain-ViT heads from the split-only
+ * nvit_gemm_nt_qknorm).
  * q_prescale > 0: qh holds q_prescale * q_hat (see nvit_gemm_nt_qknorm); the result is that of the un-scaled q.  With
  * q_prescale = scale * log2(e) the exponent of the MFMA kernel needs no multiply: the score accumulator starts at minus
  * the bound and goes straight into v_exp_f32 (one VALU instruction less per score in a VALU-bound kernel).
@@ -266,7 +294,8 @@ int nvit_attn_bwd(int dt, int impl, const void* dout, const void* qh, const void
 /* nvit_attn_bwd_qknorm: MFMA attention backward (bf16, d=64) with nvit_qknorm_bwd fused into the epilogues:
  * writes token-major dq/dk/dv (type bf16, row stride ld elements, head h at column h*64) and the partial sums
  * part_q [B*ceil(Tq/128), C], part_k [B*ceil(Tk/128), C] of d/d(sqk*c_q) (reduce with nvit_colsum_reduce).
- * q_prescale: the factor the producer folded into qh (see nvit_attn_fwd_bounded); gradients are those of the plain form. */
+ * q_prescale: the factor the producer folded into qh (see nvit_attn_fwd_bounded); gradients are those of the plain form.
+ * sqk == NULL (plain-ViT heads): dq/dk/dv stored token-major as they are; rq, rk, c_q, part_q, part_k are not used. */
 int nvit_attn_bwd_qknorm(int dt, const void* dout, const void* qh, const void* kh, const void* vh, const void* o,
                          const float* lse, float scale, const float* rq, const float* rk, const float* sqk, float c_q,
                          float q_prescale, void* dq, int ldq, void* dk, void* dv, int ldkv, float* part_q, float* part_k,

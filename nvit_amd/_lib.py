@@ -74,6 +74,10 @@ SIGNATURES = {
     "nvit_onehot": [_vp, _vp, _i64, _i, _vp],
     "nvit_rmsnorm_fwd": [_vp, _vp, _f, _vp, _vp, _i, _i, _vp],
     "nvit_rmsnorm_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
+    "nvit_res_rmsnorm_fwd": [_i, _vp, _vp, _i, _vp, _f, _vp, _vp, _vp, _i, _i, _vp],
+    "nvit_res_rmsnorm_bwd": [_i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp],
+    "nvit_res_skip_fwd": [_i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp],
+    "nvit_res_skip_bwd": [_i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
     "nvit_som_update": [_vp, _vp, _vp, _f, _f, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp],
     "nvit_cos_consistency_fwd": [_vp, _vp, _vp, _vp, _i, _vp, _i64, _i, _vp],
     "nvit_cos_consistency_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _vp],

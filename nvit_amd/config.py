@@ -67,6 +67,9 @@ def named_config(name: str, **over) -> ViTConfig:
         "base_k": dict(image_size=224, n_embd=768, n_layer=12, n_head=12, num_classes=1000, use_kohonen=True,
                        kohonen_nodes=512),
     }
+    # the plain-ViT baseline (use_nvit=False, the reference's nvit0_k0 profile) at the same shapes
+    for base in ("micro", "mini", "tiny", "base"):
+        table[base + "_vit"] = dict(table[base], use_nvit=False)
     kw = dict(common)
     kw.update(table[name])
     kw.update(over)

@@ -452,6 +452,8 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_mfma_kernel(const bf16* __res
 // Fused backward of  x_hat = (sqk*c_q) * x/||x||  (reference model.py:108-112) in the epilogue of the attention
 // backward kernels: g = dL/dx_hat in the accumulator layout (row = row0 + 16f + l15, d = 16df + 4lg + r).
 // Writes dL/dx (bf16, token-major) and this workgroup's partial sums of dL/d(sqk*c_q) for its head.
+// sqk == NULL (plain-ViT heads, no normalise): g is stored as it is - dL/dx of the split projection output, token-major -
+// and rn, part, c_q are not used.
 struct QkFuse {
   // (pointers first, the three 4-byte scalars together: hipcc widens the load of a scalar that is splat into a vector to 16
   //  bytes; next to a pointer that slice of the struct cannot be kept in registers and is parked in LDS for the whole
@@ -476,6 +478,7 @@ struct QkEpiLoads {
 };
 __device__ __forceinline__ void qk_bwd_epilogue_loads(QkEpiLoads& L, const bf16* xh_bh, const QkFuse& fu, int row0, int T, int H,
                                                       int b, int h, int lane) {
+  if (!fu.sqk) return;   // plain store: nothing to fetch
   const int l15 = lane & 15, lg = lane >> 4;
 #pragma unroll
   for (int f = 0; f < 2; ++f) {
@@ -502,6 +505,11 @@ __device__ __forceinline__ void qk_bwd_epilogue(f32x4 (&g)[4][2], const QkEpiLoa
                                                 int ntile, int t256, bool item_valid = true) {
   // t256: index within the 256 threads that share the work item (= threadIdx.x, or its low 8 bits in the two-item kernel)
   // lds0: the (now idle) tile ring; bytes [4096*wid, +4096) = this wave's store scratch, [16384, +1024) = column sums
+  if (!fu.sqk) {   // plain heads (uniform over the workgroup: no barrier below is skipped by part of it)
+    if (row0 < T)
+      store_tile32x64(g, lds0 + wid * 4096, fu.out + ((size_t)b * T + row0) * fu.ld + h * 64, (size_t)fu.ld, T - row0, lane);
+    return;
+  }
   const int l15 = lane & 15, lg = lane >> 4;
   float* red = reinterpret_cast<float*>(lds0 + 16384);
   f32x4 s[4], sinv[4], ds[4];

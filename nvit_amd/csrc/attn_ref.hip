@@ -389,10 +389,10 @@ extern "C" int nvit_attn_fwd(int dt, int impl, const void* qh, const void* kh, c
 // the running maximum (see attn_mfma.hip).  Same result as nvit_attn_fwd up to rounding.  q_prescale: qh holds
 // q_prescale * q_hat (the producer folded the factor into the learned scale); 1 = plain.  With q_prescale =
 // scale * log2(e) the MFMA kernel's exponent needs no multiply (the fused training path).
+// sqk == NULL: no bound (plain-ViT heads from the split-only q/k/v epilogue): the running-maximum kernel, q pre-scaled.
 extern "C" int nvit_attn_fwd_bounded(int dt, int impl, const void* qh, const void* kh, const void* vh, float scale,
                                      const float* sqk, float c_q, float q_prescale, void* o, float* lse, int B, int H,
                                      int Tq, int Tk, int d, void* stream) {
-  NVIT_REQUIRE(sqk != nullptr, "attn_fwd_bounded: sqk is NULL (use nvit_attn_fwd)");
   NVIT_REQUIRE(q_prescale > 0.f, "attn_fwd_bounded: q_prescale must be positive");
   return attn_fwd_impl(dt, impl, qh, kh, vh, scale, sqk, c_q, q_prescale, o, lse, B, H, Tq, Tk, d, stream);
 }
@@ -466,7 +466,8 @@ extern "C" int nvit_attn_bwd(int dt, int impl, const void* dout, const void* qh,
   return NVIT_OK;
 }
 
-// MFMA attention backward (bf16, d = 64) with the q/k-normalise backward fused into the epilogues.
+// MFMA attention backward (bf16, d = 64) with the q/k-normalise backward fused into the epilogues; with sqk == NULL (and
+// rq, rk, part_q, part_k unused) the epilogues store dq / dk / dv token-major as they are (plain-ViT heads).
 extern "C" int nvit_attn_bwd_qknorm(int dt, const void* dout, const void* qh, const void* kh, const void* vh,
                                     const void* o, const float* lse, float scale, const float* rq, const float* rk,
                                     const float* sqk, float c_q, float q_prescale, void* dq, int ldq, void* dk, void* dv,

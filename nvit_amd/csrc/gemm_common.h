@@ -349,16 +349,25 @@ __device__ __forceinline__ void nt_store_tile_swiglu(const NtArgs& g, f32x4 (&ac
 
 // ---- EPI 4: per-head cosine normalise + learned scale + head split fused into the q/k/v GEMM --------
 // (reference model.py:104-119, 231-247).  A wave's 64 columns are exactly one head (d = 64).
+// sqk == NULL: the head split alone (plain-ViT attention, model.py:97-100): no normalise, rq / rk not written; q still
+// leaves multiplied by q_prescale.
 template <int FMR>
 __device__ __forceinline__ void nt_store_tile_qknorm(const NtArgs& g, f32x4 (&acc)[FMR][4], int m_base, int n_base,
                                                      int lane, char* scratch) {
   const int l15 = lane & 15, lg = lane >> 4;
   const int part = g.part0 + n_base / g.Cemb;  // 0 = q, 1 = k, 2 = v
   const int c0 = n_base % g.Cemb, h = c0 >> 6;
+  const bool norm = g.sqk != nullptr;
   f32x4 sc[4];
   const float cq = part == 0 ? g.c_q * g.q_prescale : g.c_q;
+  if (norm) {
 #pragma unroll
-  for (int j = 0; j < 4; ++j) sc[j] = *reinterpret_cast<const f32x4*>(g.sqk + c0 + j * 16 + 4 * lg) * cq;
+    for (int j = 0; j < 4; ++j) sc[j] = *reinterpret_cast<const f32x4*>(g.sqk + c0 + j * 16 + 4 * lg) * cq;
+  } else {
+    const float qs = part == 0 ? g.q_prescale : 1.0f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) sc[j] = (f32x4){qs, qs, qs, qs};
+  }
   bf16* outp = reinterpret_cast<bf16*>(part == 0 ? g.qh : (part == 1 ? g.kh : g.vh));
   float* rn_out = part == 0 ? g.rq : g.rk;
   // (batch, token) of the wave tile's first row: ONE integer division per call - a division by the run-time token count
@@ -368,7 +377,7 @@ __device__ __forceinline__ void nt_store_tile_qknorm(const NtArgs& g, f32x4 (&ac
 #pragma unroll
   for (int i = 0; i < FMR; ++i) {
     float rn = 1.0f;
-    if (part < 2) {
+    if (part < 2 && norm) {
       float ss = 0.f;
 #pragma unroll
       for (int j = 0; j < 4; ++j)

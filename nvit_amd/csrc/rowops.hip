@@ -344,14 +344,18 @@ struct QkArgs {
   int B, T, H, d;
 };
 
-template <int NV, typename TI, typename T>   // TI: type of the projection outputs read, T: type of the head tensors written
+// NORM = false (sqk == NULL): the head split alone, q and k copied as they are (the plain-ViT attention, reference
+// model.py:97-100 without :104-112); rq / rk are not written.
+template <int NV, typename TI, typename T, bool NORM>   // TI: type of the projection outputs read, T: type of the head tensors written
 __global__ __launch_bounds__(256) void qknorm_fwd_kernel(QkArgs a) {
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int C = a.H * a.d, M = a.B * a.T, G = a.d >> 2;  // lanes per head
   RowVec<NV> s;
-  row_load<NV, float>(s, a.sqk, C, lane);
+  if constexpr (NORM) {
+    row_load<NV, float>(s, a.sqk, C, lane);
 #pragma unroll
-  for (int i = 0; i < NV; ++i) s.v[i] = s.v[i] * a.c_q;
+    for (int i = 0; i < NV; ++i) s.v[i] = s.v[i] * a.c_q;
+  }
   for (int m = blockIdx.x * ROW_WAVES + wid; m < M; m += gridDim.x * ROW_WAVES) {
     const int b = m / a.T, t = m % a.T;
     RowVec<NV> q, k, v;
@@ -361,20 +365,28 @@ __global__ __launch_bounds__(256) void qknorm_fwd_kernel(QkArgs a) {
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
       const int c = (i * 64 + lane) * 4;
-      float sq = q.v[i][0] * q.v[i][0] + q.v[i][1] * q.v[i][1] + q.v[i][2] * q.v[i][2] + q.v[i][3] * q.v[i][3];
-      float sk = k.v[i][0] * k.v[i][0] + k.v[i][1] * k.v[i][1] + k.v[i][2] * k.v[i][2] + k.v[i][3] * k.v[i][3];
-      sq = group_sum_dyn(sq, G);
-      sk = group_sum_dyn(sk, G);
-      if (c < C) {
-        const float rq = 1.0f / sqrtf(sq), rk = 1.0f / sqrtf(sk);
-        const int h = c / a.d, j = c % a.d;
-        const size_t dst = (((size_t)b * a.H + h) * a.T + t) * a.d + j;
-        store4<T>(reinterpret_cast<T*>(a.qh) + dst, q.v[i] * rq * s.v[i]);
-        store4<T>(reinterpret_cast<T*>(a.kh) + dst, k.v[i] * rk * s.v[i]);
-        store4<T>(reinterpret_cast<T*>(a.vh) + dst, v.v[i]);
-        if (j == 0) {
-          a.rq[(size_t)m * a.H + h] = rq;
-          a.rk[(size_t)m * a.H + h] = rk;
+      const int h = c / a.d, j = c % a.d;
+      const size_t dst = (((size_t)b * a.H + h) * a.T + t) * a.d + j;
+      if constexpr (!NORM) {
+        if (c < C) {
+          store4<T>(reinterpret_cast<T*>(a.qh) + dst, q.v[i]);
+          store4<T>(reinterpret_cast<T*>(a.kh) + dst, k.v[i]);
+          store4<T>(reinterpret_cast<T*>(a.vh) + dst, v.v[i]);
+        }
+      } else {
+        float sq = q.v[i][0] * q.v[i][0] + q.v[i][1] * q.v[i][1] + q.v[i][2] * q.v[i][2] + q.v[i][3] * q.v[i][3];
+        float sk = k.v[i][0] * k.v[i][0] + k.v[i][1] * k.v[i][1] + k.v[i][2] * k.v[i][2] + k.v[i][3] * k.v[i][3];
+        sq = group_sum_dyn(sq, G);
+        sk = group_sum_dyn(sk, G);
+        if (c < C) {
+          const float rq = 1.0f / sqrtf(sq), rk = 1.0f / sqrtf(sk);
+          store4<T>(reinterpret_cast<T*>(a.qh) + dst, q.v[i] * rq * s.v[i]);
+          store4<T>(reinterpret_cast<T*>(a.kh) + dst, k.v[i] * rk * s.v[i]);
+          store4<T>(reinterpret_cast<T*>(a.vh) + dst, v.v[i]);
+          if (j == 0) {
+            a.rq[(size_t)m * a.H + h] = rq;
+            a.rk[(size_t)m * a.H + h] = rk;
+          }
         }
       }
     }
@@ -443,6 +455,28 @@ __global__ __launch_bounds__(256) void qknorm_bwd_kernel(QkBwdArgs a) {
 #pragma unroll
     for (int w = 0; w < ROW_WAVES; ++w) t += red[w][c];
     a.part[(size_t)blockIdx.x * C + c] = t;
+  }
+}
+
+// merge_heads_kernel: the backward of the NORM = false split: dq/dk/dv (type T, row strides ld*) = dqh/dkh/dvh
+// [B,H,T,d] merged back to token-major rows.
+template <int NV, typename T>
+__global__ __launch_bounds__(256) void merge_heads_kernel(QkBwdArgs a) {
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int C = a.H * a.d, M = a.B * a.T;
+  for (int m = blockIdx.x * ROW_WAVES + wid; m < M; m += gridDim.x * ROW_WAVES) {
+    const int b = m / a.T, t = m % a.T;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int c = (i * 64 + lane) * 4;
+      if (c < C) {
+        const int h = c / a.d, j = c % a.d;
+        const size_t src = (((size_t)b * a.H + h) * a.T + t) * a.d + j;
+        store4<T>(reinterpret_cast<T*>(a.dq) + (size_t)m * a.ldq + c, load4<T>(reinterpret_cast<const T*>(a.dqh) + src));
+        store4<T>(reinterpret_cast<T*>(a.dk) + (size_t)m * a.ldk + c, load4<T>(reinterpret_cast<const T*>(a.dkh) + src));
+        store4<T>(reinterpret_cast<T*>(a.dv) + (size_t)m * a.ldv + c, load4<T>(reinterpret_cast<const T*>(a.dvh) + src));
+      }
+    }
   }
 }
 
@@ -669,7 +703,7 @@ __global__ void scale_cols_kernel(const float* a, int lda, const float* s, float
   const int n = blockIdx.x * blockDim.x + threadIdx.x;
   const int r = blockIdx.y;
   if (n >= N || r >= R) return;
-  st1<T>(out + (size_t)r * ldo + n, a[(size_t)r * lda + n] * s[n] * c);
+  st1<T>(out + (size_t)r * ldo + n, s ? a[(size_t)r * lda + n] * s[n] * c : a[(size_t)r * lda + n] * c);
 }
 
 // Input pipeline, deterministic part (reference train.py:1084-1090): ToTensor (uint8 HWC -> float CHW in [0,1]) and
@@ -752,6 +786,174 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const float* dout, con
     for (int wv_ = 0; wv_ < ROW_WAVES; ++wv_) s_ += red[wv_][c];
     part_dw[(size_t)blockIdx.x * C + c] = s_;
   }
+}
+
+// ------------------------------------------------------------------------------ residual + RMSNorm (plain-ViT blocks)
+// The use_nvit=False Block (reference model.py:92-169 with the RMSNorm modules built): a = rms_att(x);
+// h1 = a + attn(a); bm = rms_mlp(h1); h2 = bm + mlp(bm); then norm_skip: out = nrm(h2*skip + x).
+// res_rmsnorm_fwd: out = rms(a + y) * w (y = NULL: rms(a) * w), with the operand twin and rstd; a + y is not stored.
+struct ResRmsFwdArgs {
+  const float* a;
+  const void* y;
+  const float* w;
+  float eps;
+  float* out;
+  void* out_lo;
+  float* rstd;
+  int M, C;
+};
+
+template <int NV, typename TY, typename TL, bool HAS_Y>
+__global__ __launch_bounds__(256) void res_rmsnorm_fwd_kernel(ResRmsFwdArgs a) {
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  RowVec<NV> wv;
+  row_load<NV, float>(wv, a.w, a.C, lane);
+  for (int m = blockIdx.x * ROW_WAVES + wid; m < a.M; m += gridDim.x * ROW_WAVES) {
+    RowVec<NV> z;
+    row_load<NV, float>(z, a.a + (size_t)m * a.C, a.C, lane);
+    if constexpr (HAS_Y) {
+      RowVec<NV> y;
+      row_load<NV, TY>(y, reinterpret_cast<const TY*>(a.y) + (size_t)m * a.C, a.C, lane);
+#pragma unroll
+      for (int i = 0; i < NV; ++i) z.v[i] = z.v[i] + y.v[i];
+    }
+    const float rs = 1.0f / sqrtf(row_dot<NV>(z, z) / (float)a.C + a.eps);
+#pragma unroll
+    for (int i = 0; i < NV; ++i) z.v[i] = z.v[i] * rs * wv.v[i];
+    row_store<NV, float>(z, a.out + (size_t)m * a.C, a.C, lane);
+    if (a.out_lo) row_store<NV, TL>(z, reinterpret_cast<TL*>(a.out_lo) + (size_t)m * a.C, a.C, lane);
+    if (lane == 0) a.rstd[m] = rs;
+  }
+}
+
+// res_rmsnorm_bwd: gradient g (+ the addend g_add of type TL: a data-gradient GEMM's output) of out = rms(z) * w,
+// z = a + y, recomputed.  dz = rstd * (gw - zn * mean(gw * zn)), gw = g * w, zn = z * rstd; written (or added to dz with
+// accum), its type-TL copy to dz_lo; per-wave partial sums part_dw [4*nblk, C] of g * zn.
+struct ResRmsBwdArgs {
+  const float* g;
+  const void* g_add;
+  const float* a;
+  const void* y;
+  const float* w;
+  const float* rstd;
+  float* dz;
+  int accum;
+  void* dz_lo;
+  float* part_dw;
+  int M, C;
+};
+
+template <int NV, typename TY, typename TL, bool HAS_Y, bool ADD>
+__global__ __launch_bounds__(256) void res_rmsnorm_bwd_kernel(ResRmsBwdArgs a) {
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  RowVec<NV> wv, dw;
+  row_load<NV, float>(wv, a.w, a.C, lane);
+#pragma unroll
+  for (int i = 0; i < NV; ++i) dw.v[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  for (int m = blockIdx.x * ROW_WAVES + wid; m < a.M; m += gridDim.x * ROW_WAVES) {
+    RowVec<NV> z, g;
+    row_load<NV, float>(z, a.a + (size_t)m * a.C, a.C, lane);
+    row_load_f32_nt<NV>(g, a.g + (size_t)m * a.C, a.C, lane);
+    if constexpr (HAS_Y) {
+      RowVec<NV> y;
+      row_load<NV, TY>(y, reinterpret_cast<const TY*>(a.y) + (size_t)m * a.C, a.C, lane);
+#pragma unroll
+      for (int i = 0; i < NV; ++i) z.v[i] = z.v[i] + y.v[i];
+    }
+    if constexpr (ADD) {
+      RowVec<NV> ad;
+      row_load<NV, TL>(ad, reinterpret_cast<const TL*>(a.g_add) + (size_t)m * a.C, a.C, lane);
+#pragma unroll
+      for (int i = 0; i < NV; ++i) g.v[i] = g.v[i] + ad.v[i];
+    }
+    const float rs = a.rstd[m];
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      z.v[i] = z.v[i] * rs;            // zn
+      dw.v[i] += g.v[i] * z.v[i];
+      g.v[i] = g.v[i] * wv.v[i];       // gw
+    }
+    const float mean = row_dot<NV>(g, z) / (float)a.C;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) g.v[i] = (g.v[i] - z.v[i] * mean) * rs;
+    float* dz = a.dz + (size_t)m * a.C;
+    if (a.accum) {
+      RowVec<NV> old;
+      row_load<NV, float>(old, dz, a.C, lane);
+#pragma unroll
+      for (int i = 0; i < NV; ++i) g.v[i] = g.v[i] + old.v[i];
+    }
+    row_store<NV, float>(g, dz, a.C, lane);
+    if (a.dz_lo) row_store<NV, TL>(g, reinterpret_cast<TL*>(a.dz_lo) + (size_t)m * a.C, a.C, lane);
+  }
+  row_store<NV, float>(dw, a.part_dw + ((size_t)blockIdx.x * ROW_WAVES + wid) * a.C, a.C, lane);
+}
+
+// res_skip_fwd: out = nrm((h + y) * skip + x)  (norm_skip after a plain-ViT block, reference model.py:84-87,450-452).
+struct ResSkipArgs {
+  const float* dout;
+  const float* h;
+  const void* y;
+  const float* skip;
+  const float* x;
+  float* out;      // fwd: the new stream; bwd: d(x) (written)
+  void* out_lo;    // fwd: its type-TL twin; bwd: the type-TL copy of d(h + y) (may be NULL)
+  float* dh;       // bwd: d(h + y), fp32
+  float* part_dskip;
+  int M, C;
+};
+
+template <int NV, typename TY, typename TL>
+__global__ __launch_bounds__(256) void res_skip_fwd_kernel(ResSkipArgs a) {
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const float sk = a.skip[0];
+  for (int m = blockIdx.x * ROW_WAVES + wid; m < a.M; m += gridDim.x * ROW_WAVES) {
+    RowVec<NV> r, y, x;
+    row_load<NV, float>(r, a.h + (size_t)m * a.C, a.C, lane);
+    row_load<NV, TY>(y, reinterpret_cast<const TY*>(a.y) + (size_t)m * a.C, a.C, lane);
+    row_load<NV, float>(x, a.x + (size_t)m * a.C, a.C, lane);
+#pragma unroll
+    for (int i = 0; i < NV; ++i) r.v[i] = (r.v[i] + y.v[i]) * sk + x.v[i];
+    const float rs = 1.0f / sqrtf(row_dot<NV>(r, r));
+#pragma unroll
+    for (int i = 0; i < NV; ++i) r.v[i] = r.v[i] * rs;
+    row_store<NV, float>(r, a.out + (size_t)m * a.C, a.C, lane);
+    if (a.out_lo) row_store<NV, TL>(r, reinterpret_cast<TL*>(a.out_lo) + (size_t)m * a.C, a.C, lane);
+  }
+}
+
+// res_skip_bwd: dr = (g - o (o.g)) / |r|;  d(x) = dr,  d(h + y) = dr * skip,  part_dskip [4*nblk] = per-wave sums of
+// dr . (h + y).
+template <int NV, typename TY, typename TL>
+__global__ __launch_bounds__(256) void res_skip_bwd_kernel(ResSkipArgs a) {
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const float sk = a.skip[0];
+  float acc = 0.f;
+  for (int m = blockIdx.x * ROW_WAVES + wid; m < a.M; m += gridDim.x * ROW_WAVES) {
+    RowVec<NV> s, y, r, g;
+    row_load<NV, float>(s, a.h + (size_t)m * a.C, a.C, lane);
+    row_load<NV, TY>(y, reinterpret_cast<const TY*>(a.y) + (size_t)m * a.C, a.C, lane);
+    row_load<NV, float>(r, a.x + (size_t)m * a.C, a.C, lane);
+    row_load_f32_nt<NV>(g, a.dout + (size_t)m * a.C, a.C, lane);
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      s.v[i] = s.v[i] + y.v[i];
+      r.v[i] = s.v[i] * sk + r.v[i];
+    }
+    const float rs = 1.0f / sqrtf(row_dot<NV>(r, r));
+#pragma unroll
+    for (int i = 0; i < NV; ++i) r.v[i] = r.v[i] * rs;   // o
+    const float og = row_dot<NV>(r, g);
+#pragma unroll
+    for (int i = 0; i < NV; ++i) g.v[i] = (g.v[i] - r.v[i] * og) * rs;   // dr
+    acc += row_dot<NV>(g, s);
+    row_store<NV, float>(g, a.out + (size_t)m * a.C, a.C, lane);
+#pragma unroll
+    for (int i = 0; i < NV; ++i) g.v[i] = g.v[i] * sk;
+    row_store<NV, float>(g, a.dh + (size_t)m * a.C, a.C, lane);
+    if (a.out_lo) row_store<NV, TL>(g, reinterpret_cast<TL*>(a.out_lo) + (size_t)m * a.C, a.C, lane);
+  }
+  if (lane == 0) a.part_dskip[(size_t)blockIdx.x * ROW_WAVES + wid] = acc;
 }
 
 int row_grid(int M) {
@@ -920,6 +1122,114 @@ extern "C" int nvit_rmsnorm_bwd(const float* dout, const float* x, const float* 
   return NVIT_OK;
 }
 
+extern "C" int nvit_res_rmsnorm_fwd(int dt, const float* a, const void* y, int y_dt, const float* w, float eps, float* out,
+                                    void* out_lo, float* rstd, int M, int C, void* stream) {
+  NVIT_REQUIRE(C % 4 == 0 && C <= 2048 && M > 0, "res_rmsnorm_fwd: C=%d must be a multiple of 4 and <= 2048", C);
+  NVIT_REQUIRE(dt == NVIT_F32 || dt == NVIT_BF16, "res_rmsnorm_fwd: bad dt %d", dt);
+  NVIT_REQUIRE(!y || y_dt == NVIT_F32 || y_dt == NVIT_BF16, "res_rmsnorm_fwd: bad y_dt %d", y_dt);
+  ResRmsFwdArgs ar{a, y, w, eps, out, out_lo, rstd, M, C};
+  hipStream_t s = (hipStream_t)stream;
+  const int grid = row_grid(M);
+  ProfScope ps(NVIT_KID_ROWOPS, 0.0, (double)M * C * (8.0 + (y ? (y_dt == NVIT_F32 ? 4.0 : 2.0) : 0.0) +
+                                                       (out_lo ? (dt == NVIT_F32 ? 4.0 : 2.0) : 0.0)), s);
+#define NVIT_RRF_LAUNCH(TL_)                                                                                 \
+  {                                                                                                          \
+    if (!y)                                                                                                  \
+      hipLaunchKernelGGL((res_rmsnorm_fwd_kernel<NV, float, TL_, false>), dim3(grid), dim3(256), 0, s, ar);  \
+    else if (y_dt == NVIT_F32)                                                                               \
+      hipLaunchKernelGGL((res_rmsnorm_fwd_kernel<NV, float, TL_, true>), dim3(grid), dim3(256), 0, s, ar);   \
+    else                                                                                                     \
+      hipLaunchKernelGGL((res_rmsnorm_fwd_kernel<NV, bf16, TL_, true>), dim3(grid), dim3(256), 0, s, ar);    \
+  }
+  DISPATCH_NV(C, {
+    if (dt == NVIT_F32) NVIT_RRF_LAUNCH(float)
+    else NVIT_RRF_LAUNCH(bf16)
+  });
+#undef NVIT_RRF_LAUNCH
+  NVIT_CHECK_LAUNCH("res_rmsnorm_fwd");
+  return NVIT_OK;
+}
+
+extern "C" int nvit_res_rmsnorm_bwd(int dt, const float* g, const void* g_add, const float* a, const void* y, int y_dt,
+                                    const float* w, const float* rstd, float* dz, int accum, void* dz_lo, float* part_dw,
+                                    int nblk, int M, int C, void* stream) {
+  NVIT_REQUIRE(C % 4 == 0 && C <= 2048 && M > 0, "res_rmsnorm_bwd: C=%d must be a multiple of 4 and <= 2048", C);
+  NVIT_REQUIRE(nblk > 0 && nblk <= 4096, "res_rmsnorm_bwd: nblk out of range");
+  NVIT_REQUIRE(dt == NVIT_F32 || dt == NVIT_BF16, "res_rmsnorm_bwd: bad dt %d", dt);
+  NVIT_REQUIRE(!y || y_dt == NVIT_F32 || y_dt == NVIT_BF16, "res_rmsnorm_bwd: bad y_dt %d", y_dt);
+  ResRmsBwdArgs ar{g, g_add, a, y, w, rstd, dz, accum, dz_lo, part_dw, M, C};
+  hipStream_t s = (hipStream_t)stream;
+  const double tl = dt == NVIT_F32 ? 4.0 : 2.0;
+  ProfScope ps(NVIT_KID_ROWOPS, 0.0, (double)M * C * (12.0 + (y ? (y_dt == NVIT_F32 ? 4.0 : 2.0) : 0.0) +
+                                                       (g_add ? tl : 0.0) + (accum ? 4.0 : 0.0) + (dz_lo ? tl : 0.0)), s);
+#define NVIT_RRB_LAUNCH2(TL_, ADD_)                                                                               \
+  {                                                                                                               \
+    if (!y)                                                                                                       \
+      hipLaunchKernelGGL((res_rmsnorm_bwd_kernel<NV, float, TL_, false, ADD_>), dim3(nblk), dim3(256), 0, s, ar); \
+    else if (y_dt == NVIT_F32)                                                                                    \
+      hipLaunchKernelGGL((res_rmsnorm_bwd_kernel<NV, float, TL_, true, ADD_>), dim3(nblk), dim3(256), 0, s, ar);  \
+    else                                                                                                          \
+      hipLaunchKernelGGL((res_rmsnorm_bwd_kernel<NV, bf16, TL_, true, ADD_>), dim3(nblk), dim3(256), 0, s, ar);   \
+  }
+#define NVIT_RRB_LAUNCH(TL_)             \
+  {                                      \
+    if (g_add) NVIT_RRB_LAUNCH2(TL_, true) \
+    else NVIT_RRB_LAUNCH2(TL_, false)     \
+  }
+  DISPATCH_NV(C, {
+    if (dt == NVIT_F32) NVIT_RRB_LAUNCH(float)
+    else NVIT_RRB_LAUNCH(bf16)
+  });
+#undef NVIT_RRB_LAUNCH
+#undef NVIT_RRB_LAUNCH2
+  NVIT_CHECK_LAUNCH("res_rmsnorm_bwd");
+  return NVIT_OK;
+}
+
+#define NVIT_RSK_LAUNCH(KERN, GRID)                                                                   \
+  DISPATCH_NV(C, {                                                                                    \
+    if (y_dt == NVIT_F32 && dt == NVIT_F32)                                                           \
+      hipLaunchKernelGGL((KERN<NV, float, float>), dim3(GRID), dim3(256), 0, s, ar);                  \
+    else if (y_dt == NVIT_F32)                                                                        \
+      hipLaunchKernelGGL((KERN<NV, float, bf16>), dim3(GRID), dim3(256), 0, s, ar);                   \
+    else if (dt == NVIT_F32)                                                                          \
+      hipLaunchKernelGGL((KERN<NV, bf16, float>), dim3(GRID), dim3(256), 0, s, ar);                   \
+    else                                                                                              \
+      hipLaunchKernelGGL((KERN<NV, bf16, bf16>), dim3(GRID), dim3(256), 0, s, ar);                    \
+  })
+
+extern "C" int nvit_res_skip_fwd(int dt, const float* h, const void* y, int y_dt, const float* skip, const float* x,
+                                 float* out, void* out_lo, int M, int C, void* stream) {
+  NVIT_REQUIRE(C % 4 == 0 && C <= 2048 && M > 0, "res_skip_fwd: C=%d must be a multiple of 4 and <= 2048", C);
+  NVIT_REQUIRE(dt == NVIT_F32 || dt == NVIT_BF16, "res_skip_fwd: bad dt %d", dt);
+  NVIT_REQUIRE(y && (y_dt == NVIT_F32 || y_dt == NVIT_BF16), "res_skip_fwd: y missing or bad y_dt %d", y_dt);
+  ResSkipArgs ar{nullptr, h, y, skip, x, out, out_lo, nullptr, nullptr, M, C};
+  hipStream_t s = (hipStream_t)stream;
+  const int grid = row_grid(M);
+  ProfScope ps(NVIT_KID_ROWOPS, 0.0, (double)M * C * (12.0 + (y_dt == NVIT_F32 ? 4.0 : 2.0) +
+                                                       (out_lo ? (dt == NVIT_F32 ? 4.0 : 2.0) : 0.0)), s);
+  NVIT_RSK_LAUNCH(res_skip_fwd_kernel, grid);
+  NVIT_CHECK_LAUNCH("res_skip_fwd");
+  return NVIT_OK;
+}
+
+extern "C" int nvit_res_skip_bwd(int dt, const float* dout, const float* h, const void* y, int y_dt, const float* skip,
+                                 const float* x, float* dh, void* dh_lo, float* dx, float* part_dskip, int nblk, int M,
+                                 int C, void* stream) {
+  NVIT_REQUIRE(C % 4 == 0 && C <= 2048 && M > 0, "res_skip_bwd: C=%d must be a multiple of 4 and <= 2048", C);
+  NVIT_REQUIRE(nblk > 0 && nblk <= 4096, "res_skip_bwd: nblk out of range");
+  NVIT_REQUIRE(dt == NVIT_F32 || dt == NVIT_BF16, "res_skip_bwd: bad dt %d", dt);
+  NVIT_REQUIRE(y && (y_dt == NVIT_F32 || y_dt == NVIT_BF16), "res_skip_bwd: y missing or bad y_dt %d", y_dt);
+  ResSkipArgs ar{dout, h, y, skip, x, dx, dh_lo, dh, part_dskip, M, C};
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope ps(NVIT_KID_ROWOPS, 0.0, (double)M * C * (20.0 + (y_dt == NVIT_F32 ? 4.0 : 2.0) +
+                                                       (dh_lo ? (dt == NVIT_F32 ? 4.0 : 2.0) : 0.0)), s);
+  NVIT_RSK_LAUNCH(res_skip_bwd_kernel, nblk);
+  NVIT_CHECK_LAUNCH("res_skip_bwd");
+  return NVIT_OK;
+}
+#undef NVIT_RSK_LAUNCH
+
 extern "C" int nvit_qknorm_fwd(int dt, const void* q, int ldq, const void* k, int ldk, const void* v, int ldv,
                                const float* sqk, float c_q, void* qh, void* kh, void* vh, float* rq, float* rk,
                                int B, int T, int H, int d, void* stream) {
@@ -931,14 +1241,20 @@ extern "C" int nvit_qknorm_fwd(int dt, const void* q, int ldq, const void* k, in
   const int grid = row_grid(B * T);
   NVIT_REQUIRE(dt == NVIT_F32 || dt == NVIT_BF16 || dt == NVIT_BF16_F32IN, "qknorm_fwd: bad dt %d", dt);
   ProfScope ps(NVIT_KID_ROWOPS, 0.0, (double)B * T * C * (dt == NVIT_F32 ? 24.0 : dt == NVIT_BF16 ? 12.0 : 18.0), s);
-  DISPATCH_NV(C, {
-    if (dt == NVIT_F32)
-      hipLaunchKernelGGL((qknorm_fwd_kernel<NV, float, float>), dim3(grid), dim3(256), 0, s, a);
-    else if (dt == NVIT_BF16)
-      hipLaunchKernelGGL((qknorm_fwd_kernel<NV, bf16, bf16>), dim3(grid), dim3(256), 0, s, a);
-    else   // fp32 projection outputs -> bf16 head tensors: normalised from the unrounded values
-      hipLaunchKernelGGL((qknorm_fwd_kernel<NV, float, bf16>), dim3(grid), dim3(256), 0, s, a);
-  });
+#define NVIT_QKF_LAUNCH(NORM_)                                                                          \
+  DISPATCH_NV(C, {                                                                                      \
+    if (dt == NVIT_F32)                                                                                 \
+      hipLaunchKernelGGL((qknorm_fwd_kernel<NV, float, float, NORM_>), dim3(grid), dim3(256), 0, s, a); \
+    else if (dt == NVIT_BF16)                                                                           \
+      hipLaunchKernelGGL((qknorm_fwd_kernel<NV, bf16, bf16, NORM_>), dim3(grid), dim3(256), 0, s, a);   \
+    else   /* fp32 projection outputs -> bf16 head tensors: normalised from the unrounded values */     \
+      hipLaunchKernelGGL((qknorm_fwd_kernel<NV, float, bf16, NORM_>), dim3(grid), dim3(256), 0, s, a);  \
+  })
+  if (sqk)
+    NVIT_QKF_LAUNCH(true);
+  else
+    NVIT_QKF_LAUNCH(false);
+#undef NVIT_QKF_LAUNCH
   NVIT_CHECK_LAUNCH("qknorm_fwd");
   return NVIT_OK;
 }
@@ -953,6 +1269,19 @@ extern "C" int nvit_qknorm_bwd(int dt, const void* dqh, const void* dkh, const v
   NVIT_REQUIRE(nblk > 0 && nblk <= 4096, "qknorm_bwd: nblk out of range");
   QkBwdArgs a{dqh, dkh, dvh, qh, kh, rq, rk, sqk, c_q, dq, dk, dv, ldq, ldk, ldv, part_dsqk, B, T, H, d};
   hipStream_t s = (hipStream_t)stream;
+  if (!sqk) {   // split without the normalise: the backward is the head merge alone (qh, kh, rq, rk, part unused)
+    NVIT_REQUIRE(dt == NVIT_F32 || dt == NVIT_BF16, "qknorm_bwd: bad dt %d", dt);
+    ProfScope ps(NVIT_KID_ROWOPS, 0.0, (double)B * T * C * (dt == NVIT_F32 ? 24.0 : 12.0), s);
+    const int grid = row_grid(B * T);
+    DISPATCH_NV(C, {
+      if (dt == NVIT_F32)
+        hipLaunchKernelGGL((merge_heads_kernel<NV, float>), dim3(grid), dim3(256), 0, s, a);
+      else
+        hipLaunchKernelGGL((merge_heads_kernel<NV, bf16>), dim3(grid), dim3(256), 0, s, a);
+    });
+    NVIT_CHECK_LAUNCH("qknorm_bwd");
+    return NVIT_OK;
+  }
   ProfScope ps(NVIT_KID_ROWOPS, 0.0, (double)B * T * C * (dt == NVIT_F32 ? 32.0 : 16.0), s);
   DISPATCH_NV(C, {
     if (dt == NVIT_F32)

@@ -9,9 +9,10 @@ sub-modules are parameter containers only: their torch forward is never called. 
 compute goes through the C ABI in include/nvit_hip.h (nvit_amd/ops.py); there is no CPU
 or torch-operator fallback — without the HIP library or a GPU, forward() raises.
 
-Only the nViT path (`use_nvit=True`, SDPA semantics, `flash_attn` ignored) is implemented;
-the reference's non-nViT path crashes upstream and its flash_attn=True
-branch attends over the wrong axis (Q3).
+Both paths are implemented with SDPA semantics (`flash_attn` ignored: the reference's flash_attn=True branch attends
+over the wrong axis, Q3): nViT (`use_nvit=True`) and the plain-ViT baseline (`use_nvit=False`, without the Kohonen head),
+whose reference construction bug (the RMSNorm modules its forward calls are built only for nViT) is
+repaired by building `rmsnorm_att` / `rmsnorm_mlp` in both modes.
 
 Precision modes (model.precision): "bf16" = bf16 MFMA operands, fp32 accumulate, fp32
 residual stream/norms/params/grads (the performance mode); "fp32" = exact-f32 MFMA
@@ -184,7 +185,8 @@ class _Runtime:
             stack(f"h{i}.fc", [blk.c_fc], perm=1)
             stack(f"h{i}.p", [blk.mlp_c_proj])
             # suv in the interleaved (perm=1) column order of the c_fc shadow, for the fused SwiGLU epilogue
-            bent.append((blk.suv.detach().reshape(8 * C, 1), newb(f"h{i}.suv_i", 8 * C), 1, 1, None, 0, 0, 1))
+            if cfg.use_nvit:
+                bent.append((blk.suv.detach().reshape(8 * C, 1), newb(f"h{i}.suv_i", 8 * C), 1, 1, None, 0, 0, 1))
         # classifier head: transposed shadow zero-padded along classes to a multiple of the K stage
         ncls = cfg.num_classes
         Kp = ops.round_up(ncls, bk)
@@ -541,6 +543,264 @@ class _CrossFn(torch.autograd.Function):
                 g_bproj, g_bout, None)
 
 
+RMS_EPS = 1e-6   # reference RMSNorm default (model.py:171)
+
+
+def _split_heads(rt: _Runtime, q_src, ldq, k_src, ldk, v_src, ldv, B, T, H, d):
+    """Plain-ViT head split: [M, C] projection outputs (fp32) -> [B,H,T,d] head tensors of the mode's operand type."""
+    dt_in = rt.dt if rt.dt == F32 else BF16_F32IN
+    qh, kh, vh, _, _ = ops.qknorm_fwd(dt_in, q_src, ldq, k_src, ldk, v_src, ldv, None, 0.0, B, T, H, d)
+    return qh, kh, vh
+
+
+def _std_q_prescale(d: int) -> float:
+    """q pre-scale of the fused plain-ViT route: softmax scale 1/sqrt(d) times log2(e), so that the MFMA attention
+    kernels take the score in log2 units without a multiply (and the dK/dV backward takes its generated loop)."""
+    return ops.LOG2E / math.sqrt(d)
+
+
+def _merge_heads(rt: _Runtime, do, qh, kh, vh, o, lse, impl, d, qpre, fused, dq, ldq, dk, dv, ldkv, B, T, H) -> None:
+    """Attention backward with plain (unnormalised) heads into token-major dq / dk / dv (dk, dv: row stride ldkv).
+    fused (bf16, d = 64, the heads came from the split-only q/k/v epilogue): the MFMA backward stores them itself;
+    otherwise head-major gradients and the merge kernel."""
+    if fused:
+        ops.attn_bwd_qknorm(do, qh, kh, vh, o, lse, 1.0 / math.sqrt(d), None, None, None, 0.0, dq, ldq, dk, dv, ldkv,
+                            q_prescale=qpre)
+        return
+    dqh, dkh, dvh = ops.attn_bwd(rt.dt, impl, do, qh, kh, vh, o, lse, 1.0 / math.sqrt(d))
+    ops.qknorm_bwd(rt.dt, dqh, dkh, dvh, None, None, None, None, None, 0.0, dq, ldq, dk, ldkv, dv, ldkv, B, T, H, d)
+
+
+class _StdBlockFn(torch.autograd.Function):
+    """One plain-ViT block (use_nvit=False, reference Block.forward model.py:92-169 with rmsnorm_att / rmsnorm_mlp
+    built) and, with_skip, the norm_skip after it (model.py:84-87,450-452):
+        a = rms_att(x);  h1 = a + attn(a) W_o^T;  bm = rms_mlp(h1);  h2 = bm + swiglu(bm W_fc^T) W_p^T;
+        out = nrm(h2 * skip + x)   (with_skip; else out = h2).
+    Attention is softmax(q k^T / sqrt(d)) v on the running-max kernels; the SwiGLU gate scale is 1 (no suv)."""
+
+    @staticmethod
+    def forward(ctx, x, rt, idx, with_skip, want_lo, impl, skip_param, w_att, w_mlp, wq, wk, wv, wo, wfc, wp, bq, bk_,
+                bv, bo, bfc, bp):
+        cfg = rt.model.config
+        C, H = cfg.n_embd, cfg.n_head
+        d = C // H
+        M = x.shape[0]
+        T = rt.model.n_tokens
+        B = M // T
+        dt = rt.dt
+        lo = dt != F32
+        sh = rt.sh
+        pre = f"h{idx}."
+        has_b = bq is not None
+        a, a_lo, r_att = ops.res_rmsnorm_fwd(dt, x, None, w_att.detach(), RMS_EPS, want_lo=lo)
+        if not lo:
+            a_lo = a
+        fused = not has_b and impl == 1 and d == 64 and ops.fusable(dt, M, 3 * C, C)
+        if fused:
+            # q/k/v projection with the head split in the GEMM epilogue (split-only EPI 4); q leaves pre-scaled
+            qpre = _std_q_prescale(d)
+            qh, kh, vh, _, _ = ops.gemm_nt_qknorm(a_lo, sh[pre + "qkv.W"], M, C, 3, 0, None, 0.0, B, T, H, d,
+                                                  q_prescale=qpre)
+        else:
+            qpre = 1.0
+            qkv = ops.gemm_nt(a_lo, sh[pre + "qkv.W"], M, 3 * C, C, out_dtype=torch.float32, bias=sh.get(pre + "qkv.b"))
+            qh, kh, vh = _split_heads(rt, qkv, 3 * C, qkv[:, C:], 3 * C, qkv[:, 2 * C:], 3 * C, B, T, H, d)
+            del qkv
+        o, lse = ops.attn_fwd(dt, impl, qh, kh, vh, 1.0 / math.sqrt(d), q_prescale=qpre)
+        y = ops.gemm_nt(o, sh[pre + "o.W"], M, C, C, out_dtype=rt.y_dtype(), bias=sh.get(pre + "o.b"))
+        bm, bm_lo, r_mlp = ops.res_rmsnorm_fwd(dt, a, y, w_mlp.detach(), RMS_EPS, want_lo=lo)
+        if not lo:
+            bm_lo = bm
+        if not has_b and ops.fusable(dt, M, 8 * C, C):
+            uv, xm = ops.gemm_nt_swiglu(bm_lo, sh[pre + "fc.W"], M, 4 * C, C, None, 1.0)
+        else:
+            uv32 = ops.gemm_nt(bm_lo, sh[pre + "fc.W"], M, 8 * C, C, out_dtype=torch.float32, bias=sh.get(pre + "fc.b"))
+            if dt == F32:
+                uv, xm = uv32, ops.swiglu_fwd(dt, uv32, None, 1.0, M, 4 * C)
+            else:   # gate from the unrounded pre-activations; the bf16 copy is what backward reads
+                xm = ops.swiglu_fwd(BF16_F32IN, uv32, None, 1.0, M, 4 * C)
+                uv = ops.cast(uv32, dt)
+            del uv32
+        if with_skip:
+            y2 = ops.gemm_nt(xm, sh[pre + "p.W"], M, C, 4 * C, out_dtype=rt.y_dtype(), bias=sh.get(pre + "p.b"))
+            xn, xn_lo = ops.res_skip_fwd(dt, bm, y2, skip_param.detach(), x, want_lo=(lo and want_lo))
+        else:   # the block output itself: h2 = bm + y2 in the GEMM epilogue (row-add of bm)
+            y2 = ops.gemm_nt(xm, sh[pre + "p.W"], M, C, 4 * C, out_dtype=torch.float32, bias=sh.get(pre + "p.b"),
+                             rowadd=bm, rowadd_period=M)
+            xn, xn_lo = y2, (ops.cast(y2, dt) if lo and want_lo else None)
+        if xn_lo is None:
+            xn_lo = xn.new_empty(0)   # fp32 mode: callers alias the stream itself (see _lo())
+        ctx.rt, ctx.idx, ctx.with_skip, ctx.impl, ctx.has_b = rt, idx, with_skip, impl, has_b
+        ctx.fused, ctx.qpre = fused, qpre
+        ctx.dims = (B, T, C, H, d, M)
+        ctx.par = (skip_param, w_att, w_mlp, wq, wk, wv, wo, wfc, wp)   # gradient destinations
+        ctx.save_for_backward(x, a, a_lo, r_att, qh, kh, vh, o, lse, y, bm, bm_lo, r_mlp, uv, xm, y2, skip_param,
+                              w_att, w_mlp)
+        ctx.mark_non_differentiable(xn_lo)
+        ctx.set_materialize_grads(False)
+        return xn, xn_lo
+
+    @staticmethod
+    def backward(ctx, dxn, _unused):
+        if dxn is None:
+            return (None,) * 21
+        (x, a, a_lo, r_att, qh, kh, vh, o, lse, y, bm, bm_lo, r_mlp, uv, xm, y2, skip_param, w_att,
+         w_mlp) = ctx.saved_tensors
+        rt, idx, impl = ctx.rt, ctx.idx, ctx.impl
+        B, T, C, H, d, M = ctx.dims
+        p_skip, p_watt, p_wmlp, p_wq, p_wk, p_wv, p_wo, p_wfc, p_wp = ctx.par
+        dt, td = rt.dt, ops.tdtype(rt.dt)
+        lo = dt != F32
+        sh = rt.sh
+        pre = f"h{idx}."
+        dxn = dxn.contiguous()
+        red = ops.ReduceBatch()
+        # ---- norm_skip: d(h2) and the direct part of d(x)
+        if ctx.with_skip:
+            dh2, dh2_lo, dx, part_skip = ops.res_skip_bwd(dt, dxn, bm, y2, skip_param, x, want_lo=lo)
+            dskip = rt.grad_buf((p_skip,), p_skip.shape)
+            red.add(part_skip, dskip, False)
+        else:
+            dh2, dh2_lo, dx, dskip = dxn, (ops.cast(dxn, dt) if lo else None), None, None
+        dy2_lo = dh2_lo if lo else dh2
+        # ---- MLP branch
+        if ops.fusable(dt, M, 4 * C, C):
+            duv, _ = ops.gemm_nt_swiglu_bwd(dy2_lo, sh[pre + "p.Wt"], uv, M, 4 * C, C, None, 1.0)
+        else:
+            dxm = ops.gemm_nt(dy2_lo, sh[pre + "p.Wt"], M, 4 * C, C, out_dtype=td)
+            duv, _ = ops.swiglu_bwd(dt, dxm, uv, None, 1.0, M, 4 * C)
+        g_wp = ops.gemm_tn(dy2_lo, xm, rt.grad_buf((p_wp,), (C, 4 * C)), M, C, 4 * C)
+        g_bp = _bias_grad(dy2_lo, M, C) if ctx.has_b else None
+        dbm_add = ops.gemm_nt(duv, sh[pre + "fc.Wt"], M, C, 8 * C, out_dtype=td)   # added by the rms_mlp backward
+        g_wfc = ops.gemm_tn(duv, bm_lo, rt.grad_buf((p_wfc,), (8 * C, C)), M, 8 * C, C, perm=1)
+        g_bfc = _bias_grad(duv, M, 8 * C, perm=1) if ctx.has_b else None
+        # ---- rms_mlp: d(h1) = d(a + y)
+        dh1, dh1_lo, part_mlp = ops.res_rmsnorm_bwd(dt, dh2, a, y, w_mlp, r_mlp, g_add=dbm_add, want_lo=lo)
+        del dbm_add
+        g_wmlp = _param_grad_scaled(rt, part_mlp, p_wmlp, 1.0, red)
+        dy_lo = dh1_lo if lo else dh1
+        # ---- attention branch
+        do = ops.gemm_nt(dy_lo, sh[pre + "o.Wt"], M, C, C, out_dtype=td)
+        g_wo = ops.gemm_tn(dy_lo, o, rt.grad_buf((p_wo,), (C, C)), M, C, C)
+        g_bo = _bias_grad(dy_lo, M, C) if ctx.has_b else None
+        dqkv = torch.empty((M, 3 * C), device=x.device, dtype=td)
+        _merge_heads(rt, do, qh, kh, vh, o, lse, impl, d, ctx.qpre, ctx.fused, dqkv, 3 * C, dqkv[:, C:], dqkv[:, 2 * C:],
+                     3 * C, B, T, H)
+        da_add = ops.gemm_nt(dqkv, sh[pre + "qkv.Wt"], M, C, 3 * C, out_dtype=td)
+        g_qkv = rt.grad_buf((p_wq, p_wk, p_wv), (3 * C, C))
+        ops.gemm_tn(dqkv, a_lo, g_qkv, M, 3 * C, C)
+        g_bqkv = _bias_grad(dqkv, M, 3 * C) if ctx.has_b else None
+        # ---- rms_att: d(x) += rms backward of d(a) = d(h1) + q/k/v data gradient
+        dx, _, part_att = ops.res_rmsnorm_bwd(dt, dh1, x, None, w_att, r_att, g_add=da_add, dz=dx)
+        g_watt = _param_grad_scaled(rt, part_att, p_watt, 1.0, red)
+        red.flush()
+        gq, gk, gv = g_qkv[:C], g_qkv[C:2 * C], g_qkv[2 * C:]
+        if ctx.has_b:
+            gbq, gbk, gbv = g_bqkv[:C], g_bqkv[C:2 * C], g_bqkv[2 * C:]
+        else:
+            gbq = gbk = gbv = None
+        return (dx, None, None, None, None, None, dskip, g_watt, g_wmlp, gq, gk, gv, g_wo, g_wfc, g_wp, gbq, gbk, gbv,
+                g_bo, g_bfc, g_bp)
+
+
+class _StdCrossFn(torch.autograd.Function):
+    """CrossAttentionBlock.forward, plain-ViT branch (reference model.py:219-275, use_nvit=False): RMSNorm of both
+    inputs, attention with scale 1/sqrt(d), proj -> SwiGLU -> out_proj; the output is out_proj's result itself."""
+
+    @staticmethod
+    def forward(ctx, loc, glo, rt, impl, w_ln, w_gn, wq, wk, wv, wproj, wout, bq, bk_, bv, bproj, bout):
+        cfg = rt.model.config
+        C, H = cfg.n_embd, cfg.n_head
+        d = C // H
+        M = loc.shape[0]
+        T = rt.model.n_tokens
+        B = M // T
+        dt = rt.dt
+        lo = dt != F32
+        sh = rt.sh
+        has_b = bq is not None
+        ln, ln_lo, r_l = ops.res_rmsnorm_fwd(dt, loc, None, w_ln.detach(), RMS_EPS, want_lo=lo)
+        gn, gn_lo, r_g = ops.res_rmsnorm_fwd(dt, glo, None, w_gn.detach(), RMS_EPS, want_lo=lo)
+        if not lo:
+            ln_lo, gn_lo = ln, gn
+        fused = not has_b and impl == 1 and d == 64 and ops.fusable(dt, M, C, C)
+        if fused:   # split-only EPI 4 (q from the local side, k/v from the global side), q pre-scaled
+            qpre = _std_q_prescale(d)
+            bufs = ops.qk_buffers(dt, B, T, H, d, loc.device, norm=False)
+            ops.gemm_nt_qknorm(ln_lo, sh["x.q.W"], M, C, 1, 0, None, 0.0, B, T, H, d, bufs, q_prescale=qpre)
+            qh, kh, vh, _, _ = ops.gemm_nt_qknorm(gn_lo, sh["x.kv.W"], M, C, 2, 1, None, 0.0, B, T, H, d, bufs)
+        else:
+            qpre = 1.0
+            q = ops.gemm_nt(ln_lo, sh["x.q.W"], M, C, C, out_dtype=torch.float32, bias=sh.get("x.q.b"))
+            kv = ops.gemm_nt(gn_lo, sh["x.kv.W"], M, 2 * C, C, out_dtype=torch.float32, bias=sh.get("x.kv.b"))
+            qh, kh, vh = _split_heads(rt, q, C, kv, 2 * C, kv[:, C:], 2 * C, B, T, H, d)
+            del q, kv
+        o, lse = ops.attn_fwd(dt, impl, qh, kh, vh, 1.0 / math.sqrt(d), q_prescale=qpre)
+        if not has_b and ops.fusable(dt, M, 2 * C, C):
+            pr, g = ops.gemm_nt_swiglu(o, sh["x.proj.W"], M, C, C, None, 1.0)
+        else:
+            pr32 = ops.gemm_nt(o, sh["x.proj.W"], M, 2 * C, C, out_dtype=torch.float32, bias=sh.get("x.proj.b"))
+            if dt == F32:
+                pr, g = pr32, ops.swiglu_fwd(dt, pr32, None, 1.0, M, C)
+            else:
+                g = ops.swiglu_fwd(BF16_F32IN, pr32, None, 1.0, M, C)
+                pr = ops.cast(pr32, dt)
+            del pr32
+        out = ops.gemm_nt(g, sh["x.out.W"], M, C, C, out_dtype=torch.float32, bias=sh.get("x.out.b"))
+        ctx.rt, ctx.impl, ctx.has_b = rt, impl, has_b
+        ctx.fused, ctx.qpre = fused, qpre
+        ctx.dims = (B, T, C, H, d, M)
+        ctx.par = (w_ln, w_gn, wq, wk, wv, wproj, wout)
+        ctx.save_for_backward(loc, glo, ln_lo, gn_lo, r_l, r_g, qh, kh, vh, o, lse, pr, g, w_ln, w_gn)
+        ctx.set_materialize_grads(False)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        if dout is None:
+            return (None,) * 16
+        loc, glo, ln_lo, gn_lo, r_l, r_g, qh, kh, vh, o, lse, pr, g, w_ln, w_gn = ctx.saved_tensors
+        rt, impl = ctx.rt, ctx.impl
+        B, T, C, H, d, M = ctx.dims
+        p_wln, p_wgn, p_wq, p_wk, p_wv, p_wproj, p_wout = ctx.par
+        dt, td = rt.dt, ops.tdtype(rt.dt)
+        dev = loc.device
+        sh = rt.sh
+        dout = dout.contiguous()
+        red = ops.ReduceBatch()
+        dy_lo = ops.cast(dout, dt) if dt != F32 else dout
+        if ops.fusable(dt, M, C, C):
+            dpr, _ = ops.gemm_nt_swiglu_bwd(dy_lo, sh["x.out.Wt"], pr, M, C, C, None, 1.0)
+        else:
+            dg = ops.gemm_nt(dy_lo, sh["x.out.Wt"], M, C, C, out_dtype=td)
+            dpr, _ = ops.swiglu_bwd(dt, dg, pr, None, 1.0, M, C)
+        g_wout = ops.gemm_tn(dy_lo, g, rt.grad_buf((p_wout,), (C, C)), M, C, C)
+        g_bout = _bias_grad(dy_lo, M, C) if ctx.has_b else None
+        do = ops.gemm_nt(dpr, sh["x.proj.Wt"], M, C, 2 * C, out_dtype=td)
+        g_wproj = ops.gemm_tn(dpr, o, rt.grad_buf((p_wproj,), (2 * C, C)), M, 2 * C, C, perm=1)
+        g_bproj = _bias_grad(dpr, M, 2 * C, perm=1) if ctx.has_b else None
+        dq = torch.empty((M, C), device=dev, dtype=td)
+        dkv = torch.empty((M, 2 * C), device=dev, dtype=td)
+        _merge_heads(rt, do, qh, kh, vh, o, lse, impl, d, ctx.qpre, ctx.fused, dq, C, dkv, dkv[:, C:], 2 * C, B, T, H)
+        dln = ops.gemm_nt(dq, sh["x.q.Wt"], M, C, C, out_dtype=torch.float32)
+        dgn = ops.gemm_nt(dkv, sh["x.kv.Wt"], M, C, 2 * C, out_dtype=torch.float32)
+        g_wq = ops.gemm_tn(dq, ln_lo, rt.grad_buf((p_wq,), (C, C)), M, C, C)
+        g_wkv = ops.gemm_tn(dkv, gn_lo, rt.grad_buf((p_wk, p_wv), (2 * C, C)), M, 2 * C, C)
+        dloc, _, part_l = ops.res_rmsnorm_bwd(dt, dln, loc, None, w_ln, r_l)
+        dglo, _, part_g = ops.res_rmsnorm_bwd(dt, dgn, glo, None, w_gn, r_g)
+        g_wln = _param_grad_scaled(rt, part_l, p_wln, 1.0, red)
+        g_wgn = _param_grad_scaled(rt, part_g, p_wgn, 1.0, red)
+        red.flush()
+        if ctx.has_b:
+            g_bq = _bias_grad(dq, M, C)
+            g_bkv = _bias_grad(dkv, M, 2 * C)
+            gbk, gbv = g_bkv[:C], g_bkv[C:]
+        else:
+            g_bq = gbk = gbv = None
+        return (dloc, dglo, None, None, g_wln, g_wgn, g_wq, g_wkv[:C], g_wkv[C:], g_wproj, g_wout, g_bq, gbk, gbv,
+                g_bproj, g_bout)
+
+
 class _EmbedFn(torch.autograd.Function):
     """Dual patch embedding + position embeddings (reference model.py:286-304,407-415): one fused gather + MFMA kernel in
     the bf16 mode, im2col + exact-f32 GEMMs in the fp32 mode."""
@@ -570,7 +830,7 @@ class _EmbedFn(torch.autograd.Function):
             # (the split weight images are part of the shadow set, built by nvit_shadow_weights)
             loc, glo, A_l, A_g, loc_lo, glo_lo = ops.patch_embed_fwd(img, rt.sh["pe_l"], bl, posl.reshape(T, C),
                                                                      rt.sh["pe_g"], bg, posg.reshape(T, C), Pl, Pg, C,
-                                                                     twins=(C % 8 == 0))
+                                                                     twins=(C % 8 == 0 and cfg.use_nvit))
         ctx.rt = rt
         ctx.dims = (B, T, C, M, Kl, Kg)
         ctx.par = (wl, wg)
@@ -603,7 +863,7 @@ class _EmbedFn(torch.autograd.Function):
 
 
 class _HeadFn(torch.autograd.Function):
-    """mean-pool -> LayerNorm -> Linear -> * sz (reference model.py:455-456,466-468)."""
+    """mean-pool -> LayerNorm -> Linear -> * sz (reference model.py:455-456,466-468); sz None (plain ViT): no scale."""
 
     @staticmethod
     def forward(ctx, x, rt, ln_w, ln_b, wh, bh, sz):
@@ -619,7 +879,7 @@ class _HeadFn(torch.autograd.Function):
             raw = ops.gemm_nt(ln, wh.contiguous(), B, ncls, C, bias=bh)
         else:
             raw = ops.gemm_nt(ln_lo, rt.sh["head.W"], B, ncls, C, bias=bh)
-        logits = ops.scale_cols(raw, sz, c_sz, B, ncls, torch.empty_like(raw))
+        logits = ops.scale_cols(raw, sz, c_sz, B, ncls, torch.empty_like(raw)) if sz is not None else raw
         ctx.rt = rt
         ctx.dims = (B, T, C, ncls, c_sz)
         ctx.save_for_backward(pooled, ln_lo, stats, raw, ln_w, sz)
@@ -634,13 +894,16 @@ class _HeadFn(torch.autograd.Function):
         dt, td = rt.dt, ops.tdtype(rt.dt)
         dlogits = dlogits.contiguous()
         Kp = rt.sh["head.Wt"].shape[1]
-        d_sz = torch.empty_like(sz)
-        ops.colsum(dlogits, B, ncls, d_sz, False, b=raw, scale=c_sz)
-        draw = ops.scale_cols(dlogits, sz, c_sz, B, ncls, torch.empty((B, ncls), device=dev, dtype=torch.float32))
+        if sz is not None:
+            d_sz = torch.empty_like(sz)
+            ops.colsum(dlogits, B, ncls, d_sz, False, b=raw, scale=c_sz)
+            draw = ops.scale_cols(dlogits, sz, c_sz, B, ncls, torch.empty((B, ncls), device=dev, dtype=torch.float32))
+        else:
+            d_sz, draw, c_sz = None, dlogits, 1.0
         d_bh = torch.empty((ncls,), device=dev, dtype=torch.float32)
         ops.colsum_big(draw, B, ncls, d_bh, False)
         draw_lo = torch.zeros((B, Kp), device=dev, dtype=td)
-        ops.scale_cols(dlogits, sz, c_sz, B, ncls, draw_lo)
+        ops.scale_cols(dlogits, sz, c_sz, B, ncls, draw_lo)   # (sz None: a plain copy into the padded operand)
         g_pad = ops.gemm_tn(draw_lo, ln_lo, torch.empty((Kp, C), device=dev, dtype=torch.float32), B, Kp, C)
         dln = ops.gemm_nt(draw_lo, rt.sh["head.Wt"], B, C, Kp)
         d_lnw = torch.empty_like(ln_w)
@@ -737,9 +1000,11 @@ class Block(nn.Module):
         self.c_fc = nn.Linear(C, 2 * 4 * C, bias=config.bias)
         self.silu = nn.SiLU()
         self.mlp_c_proj = nn.Linear(4 * C, C, bias=config.bias)
+        # built in both modes: the reference builds them for use_nvit=True only, where they are dead, and its
+        # use_nvit=False forward, which calls them, crashes; the nViT state_dict is unchanged
+        self.rmsnorm_att = RMSNorm(C)
+        self.rmsnorm_mlp = RMSNorm(C)
         if config.use_nvit:
-            self.rmsnorm_att = RMSNorm(C)
-            self.rmsnorm_mlp = RMSNorm(C)
             bs = config.base_scale
             self.attn_alpha_init_value = torch.scalar_tensor(0.05, dtype=torch.float32)
             self.attn_alpha_init_scaling = torch.scalar_tensor(bs, dtype=torch.float32)
@@ -757,13 +1022,22 @@ class Block(nn.Module):
 
     def _args(self):
         b = lambda l: l.bias
-        return (self.skip_param, self.attn_alpha, self.mlp_alpha, self.sqk, self.suv, self.query.weight,
-                self.key.weight, self.value.weight, self.att_c_proj.weight, self.c_fc.weight, self.mlp_c_proj.weight,
-                b(self.query), b(self.key), b(self.value), b(self.att_c_proj), b(self.c_fc), b(self.mlp_c_proj))
+        if self.config.use_nvit:
+            lead = (self.skip_param, self.attn_alpha, self.mlp_alpha, self.sqk, self.suv)
+        else:
+            lead = (self.skip_param, self.rmsnorm_att.weight, self.rmsnorm_mlp.weight)
+        return lead + (self.query.weight, self.key.weight, self.value.weight, self.att_c_proj.weight, self.c_fc.weight,
+                       self.mlp_c_proj.weight, b(self.query), b(self.key), b(self.value), b(self.att_c_proj),
+                       b(self.c_fc), b(self.mlp_c_proj))
 
-    def _run(self, x: Tensor, x_lo: Tensor, with_skip: bool, chained: bool = False):
+    def _run(self, x: Tensor, x_lo: Tensor, with_skip: bool, chained: bool = False, want_lo: bool = True):
+        """-> (new stream, its MFMA-operand copy).  Plain-ViT mode: the copy is made only when `want_lo` (the blocks
+        read their normalised inputs, not the stream; only the reconstruction head after the last block needs it)."""
         model, idx = self._owner
         rt = model._rt
+        if not self.config.use_nvit:
+            xn, xn_lo = _StdBlockFn.apply(x, rt, idx, with_skip, want_lo, model._attn_impl(), *self._args())
+            return xn, (_lo(rt, xn, xn_lo) if want_lo else None)
         xn, xn_lo = _BlockFn.apply(x, x_lo, rt, idx, with_skip, model._attn_impl(), *self._args(), chained)
         return xn, _lo(rt, xn, xn_lo)
 
@@ -813,6 +1087,10 @@ class CrossAttentionBlock(nn.Module):
 
     def _args(self):
         b = lambda l: l.bias
+        if not self.config.use_nvit:
+            return (self.local_norm.weight, self.global_norm.weight, self.q_local.weight, self.k_global.weight,
+                    self.v_global.weight, self.proj.weight, self.out_proj.weight, b(self.q_local), b(self.k_global),
+                    b(self.v_global), b(self.proj), b(self.out_proj))
         return (self.attn_alpha, self.sqk, self.q_local.weight, self.k_global.weight, self.v_global.weight,
                 self.proj.weight, self.out_proj.weight, b(self.q_local), b(self.k_global), b(self.v_global),
                 b(self.proj), b(self.out_proj))
@@ -820,6 +1098,8 @@ class CrossAttentionBlock(nn.Module):
     def _run(self, loc: Tensor, glo: Tensor, loc_lo: Optional[Tensor] = None, glo_lo: Optional[Tensor] = None,
              chained: bool = False):
         model = self._owner
+        if not self.config.use_nvit:   # (the plain branch reads its RMS-normalised inputs: no operand copies needed)
+            return _StdCrossFn.apply(loc, glo, model._rt, model._attn_impl(), *self._args()), None
         x, x_lo = _CrossFn.apply(loc, glo, loc_lo, glo_lo, model._rt, model._attn_impl(), *self._args(), chained)
         return x, _lo(model._rt, x, x_lo)
 
@@ -834,8 +1114,9 @@ class CrossAttentionBlock(nn.Module):
 class ViT(nn.Module):
     def __init__(self, config: ViTConfig):
         super().__init__()
-        if not config.use_nvit:
-            raise NotImplementedError("only use_nvit=True is supported (the reference's non-nViT path crashes upstream)")
+        if not config.use_nvit and config.use_kohonen:
+            raise NotImplementedError("use_nvit=False with use_kohonen=True is not supported: the plain-ViT baseline runs "
+                                      "without the Kohonen head only (no reference run profile uses that combination)")
         if config.n_embd % config.n_head != 0 or config.n_embd % 64 != 0:
             raise ValueError("n_embd must be a multiple of 64 and divisible by n_head")
         if (config.n_embd // config.n_head) not in HEAD_DIMS:
@@ -865,7 +1146,8 @@ class ViT(nn.Module):
             "h": nn.ModuleList([Block(config) for _ in range(config.n_layer)]),
         })
         self.mlp_head = nn.Sequential(nn.LayerNorm(C), nn.Linear(C, config.num_classes))
-        self.sz = nn.Parameter(config.sz_init_scaling * torch.ones(config.num_classes, dtype=torch.float32))
+        if config.use_nvit:
+            self.sz = nn.Parameter(config.sz_init_scaling * torch.ones(config.num_classes, dtype=torch.float32))
         self._init_parameters()
         # runtime (not part of the state_dict)
         self.precision = os.environ.get("NVIT_PRECISION", "bf16")
@@ -889,8 +1171,9 @@ class ViT(nn.Module):
             elif isinstance(mod, nn.LayerNorm):
                 nn.init.ones_(mod.weight)
                 nn.init.zeros_(mod.bias)
-        with torch.no_grad():
-            self.sz.fill_(self.config.sz_init_value)
+        if self.config.use_nvit:
+            with torch.no_grad():
+                self.sz.fill_(self.config.sz_init_value)
 
     def _stacked_grads(self):
         """Weights whose gradients leave ONE weight-gradient GEMM stacked along dim 0, in that GEMM's row order (the
@@ -928,15 +1211,21 @@ class ViT(nn.Module):
     # ---- reference API
     def configure_optimizers(self, weight_decay: float, learning_rate: float, betas: Tuple[float, float],
                              device_type: str) -> torch.optim.AdamW:
-        """Same parameter groups as reference model.py:369-385 (nViT branch).  On the HIP device the optimizer is
-        FusedAdamW (torch.optim.AdamW subclass, same state_dict); the torch class is only returned for a CPU-resident
-        model, which cannot run forward anyway (no CPU path)."""
+        """Same parameter groups as reference model.py:369-385 (three with sz in nViT mode, two without).  On the HIP
+        device the optimizer is FusedAdamW (torch.optim.AdamW subclass, same state_dict); the torch class is only
+        returned for a CPU-resident model, which cannot run forward anyway (no CPU path)."""
         pd = {n: p for n, p in self.named_parameters() if p.requires_grad}
-        groups = [
-            {"params": [p for n, p in pd.items() if "sz" not in n and p.dim() >= 2], "weight_decay": weight_decay},
-            {"params": [p for n, p in pd.items() if "sz" not in n and p.dim() < 2], "weight_decay": 0.0},
-            {"params": [self.sz], "weight_decay": 0.0},
-        ]
+        if self.config.use_nvit:
+            groups = [
+                {"params": [p for n, p in pd.items() if "sz" not in n and p.dim() >= 2], "weight_decay": weight_decay},
+                {"params": [p for n, p in pd.items() if "sz" not in n and p.dim() < 2], "weight_decay": 0.0},
+                {"params": [self.sz], "weight_decay": 0.0},
+            ]
+        else:
+            groups = [
+                {"params": [p for n, p in pd.items() if p.dim() >= 2], "weight_decay": weight_decay},
+                {"params": [p for n, p in pd.items() if p.dim() < 2], "weight_decay": 0.0},
+            ]
         if device_type == "cuda":
             from .optim import FusedAdamW  # a torch.optim.AdamW whose step runs as nvit_adamw_renorm (SURVEY §8f F1)
             return FusedAdamW(groups, lr=learning_rate, betas=betas)
@@ -1026,6 +1315,8 @@ class ViT(nn.Module):
         if loc_lo.numel() == 0:   # fp32 mode (or an embedding width the twin store does not cover): no bf16 copies
             loc_lo = glo_lo = None
         aux: Dict[str, Tensor] = {}
+        if not cfg.use_nvit:
+            return self._forward_std(img, loc, glo, aux)
         if cfg.use_kohonen:
             # reference model.py:419-444
             lr = self.get_kohonen_lr(self.step)
@@ -1058,6 +1349,25 @@ class ViT(nn.Module):
                 taps[f"x{i + 1}"] = x.detach()
         logits = _HeadFn.apply(x, rt, self.mlp_head[0].weight, self.mlp_head[0].bias, self.mlp_head[1].weight,
                                self.mlp_head[1].bias, self.sz)
+        aux["reconstruction"] = _ReconFn.apply(x, x_lo, rt, img, self.reconstruction_head[0].weight,
+                                               self.reconstruction_head[0].bias)
+        return logits, aux
+
+    def _forward_std(self, img: Tensor, loc: Tensor, glo: Tensor, aux: Dict[str, Tensor]):
+        """Plain-ViT remainder of forward (use_nvit=False, reference model.py:446-470 without the Kohonen head)."""
+        rt = self._rt
+        x, _ = self.cross_attention._run(loc, glo)
+        taps = self._taps
+        if taps is not None:
+            taps["loc"], taps["glo"], taps["x0"] = loc.detach(), glo.detach(), x.detach()
+        blocks = self.transformer.h
+        x_lo = _lo(rt, x, ops.cast(x, rt.dt) if rt.dt != F32 else None) if len(blocks) == 0 else None
+        for i, blk in enumerate(blocks):
+            x, x_lo = blk._run(x, None, True, want_lo=(i == len(blocks) - 1))
+            if taps is not None:
+                taps[f"x{i + 1}"] = x.detach()
+        logits = _HeadFn.apply(x, rt, self.mlp_head[0].weight, self.mlp_head[0].bias, self.mlp_head[1].weight,
+                               self.mlp_head[1].bias, None)
         aux["reconstruction"] = _ReconFn.apply(x, x_lo, rt, img, self.reconstruction_head[0].weight,
                                                self.reconstruction_head[0].bias)
         return logits, aux

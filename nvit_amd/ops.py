@@ -101,9 +101,12 @@ def gemm_nt_swiglu_bwd(A: Tensor, B: Tensor, uv: Tensor, M: int, F: int, K: int,
     return duv, part
 
 
-def qk_buffers(dt: int, B: int, T: int, H: int, d: int, device):
+def qk_buffers(dt: int, B: int, T: int, H: int, d: int, device, norm: bool = True):
+    """qh, kh, vh [B,H,T,d] and (norm) rq, rk [B*T,H]; without the normalise rq, rk are None."""
     td = tdtype(dt)
     qh = torch.empty((B, H, T, d), device=device, dtype=td)
+    if not norm:
+        return qh, torch.empty_like(qh), torch.empty_like(qh), None, None
     return (qh, torch.empty_like(qh), torch.empty_like(qh),
             torch.empty((B * T, H), device=device, dtype=torch.float32),
             torch.empty((B * T, H), device=device, dtype=torch.float32))
@@ -118,13 +121,14 @@ def attn_q_prescale(d: int) -> float:
     return math.sqrt(d) * LOG2E
 
 
-def gemm_nt_qknorm(A: Tensor, B: Tensor, M: int, K: int, nparts: int, part0: int, sqk: Tensor, c_q: float, Bsz: int,
-                   T: int, H: int, d: int, bufs=None, q_prescale: float = 1.0):
+def gemm_nt_qknorm(A: Tensor, B: Tensor, M: int, K: int, nparts: int, part0: int, sqk: Optional[Tensor], c_q: float,
+                   Bsz: int, T: int, H: int, d: int, bufs=None, q_prescale: float = 1.0):
     """q/k/v projection(s) with the per-head normalise, sqk scale and head split fused (bf16, d=64).
+    sqk None: the head split alone (plain-ViT attention; rq, rk None).
     q_prescale: extra factor folded into the q part (pass the same value to attn_fwd / attn_bwd_qknorm)."""
     _chk_dev(A, B)
     if bufs is None:
-        bufs = qk_buffers(dt_of(A), Bsz, T, H, d, A.device)
+        bufs = qk_buffers(dt_of(A), Bsz, T, H, d, A.device, norm=sqk is not None)
     qh, kh, vh, rq, rk = bufs
     check(_lib.load().nvit_gemm_nt_qknorm(dt_of(A), _p(A), A.stride(0), _p(B), B.stride(0), M, K, nparts, part0,
                                           _p(sqk), c_q, q_prescale, _p(qh), _p(kh), _p(vh), _p(rq), _p(rk), T, H, d,
@@ -250,6 +254,98 @@ def rmsnorm_bwd(dout: Tensor, x: Tensor, w: Tensor, rstd: Tensor):
     return dx, dw
 
 
+def _chk_rows(shape, *ts, f32=(), name=""):
+    """Row-kernel operands: device tensors, contiguous, of the [M,C] (or [C]) shape the kernel indexes; `f32` must be
+    fp32, the others fp32 or bf16."""
+    for t in ts + tuple(f32):
+        if t is None:
+            continue
+        _chk_dev(t)
+        if not t.is_contiguous():
+            raise ValueError(f"{name}: operands must be contiguous")
+        if t.dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError(f"{name}: fp32 or bf16 operands expected, got {t.dtype}")
+    for t in f32:
+        if t is not None and t.dtype != torch.float32:
+            raise ValueError(f"{name}: fp32 operand expected, got {t.dtype}")
+    for t in ts + tuple(f32):
+        if t is not None and t.dim() == 2 and tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{name}: operand of shape {tuple(t.shape)}, expected {tuple(shape)}")
+
+
+def _chk_vec(C: int, *vs, name=""):
+    for v in vs:
+        _chk_dev(v)
+        if v.dtype != torch.float32 or not v.is_contiguous() or v.numel() != C:
+            raise ValueError(f"{name}: contiguous fp32 vector of {C} elements expected")
+
+
+def res_rmsnorm_fwd(dt: int, a: Tensor, y: Optional[Tensor], w: Tensor, eps: float, want_lo: bool = True):
+    """out = rms(a + y) * w (y None: rms(a) * w) -> out fp32, out_lo (type dt) | None, rstd [M]."""
+    M, Cc = a.shape
+    _chk_rows((M, Cc), y, f32=(a,), name="res_rmsnorm_fwd")
+    _chk_vec(Cc, w, name="res_rmsnorm_fwd")
+    out = torch.empty_like(a)
+    out_lo = torch.empty((M, Cc), device=a.device, dtype=tdtype(dt)) if want_lo else None
+    rstd = torch.empty((M,), device=a.device, dtype=torch.float32)
+    check(_lib.load().nvit_res_rmsnorm_fwd(dt, _p(a), _p(y), dt_of(y) if y is not None else F32, _p(w), eps, _p(out),
+                                           _p(out_lo), _p(rstd), M, Cc, _s()), "nvit_res_rmsnorm_fwd")
+    return out, out_lo, rstd
+
+
+def _row_part_blocks(M: int) -> int:
+    return min(PART_BLOCKS, math.ceil(M / 4))
+
+
+def res_rmsnorm_bwd(dt: int, g: Tensor, a: Tensor, y: Optional[Tensor], w: Tensor, rstd: Tensor,
+                    g_add: Optional[Tensor] = None, dz: Optional[Tensor] = None, want_lo: bool = False):
+    """Backward of res_rmsnorm_fwd -> dz fp32 (added to `dz` when given), dz_lo (type dt) | None, part_dw [4*nblk, C].
+    g_add: optional type-dt [M,C] addend of the incoming gradient (a data-gradient GEMM's output)."""
+    M, Cc = a.shape
+    _chk_rows((M, Cc), y, g_add, f32=(a, g, dz), name="res_rmsnorm_bwd")
+    _chk_vec(Cc, w, name="res_rmsnorm_bwd")
+    _chk_vec(M, rstd, name="res_rmsnorm_bwd")
+    if g_add is not None and g_add.dtype != tdtype(dt):
+        raise ValueError("res_rmsnorm_bwd: g_add must be a contiguous [M,C] tensor of the mode's operand type")
+    accum = dz is not None
+    if dz is None:
+        dz = torch.empty_like(a)
+    nblk = _row_part_blocks(M)
+    dz_lo = torch.empty((M, Cc), device=a.device, dtype=tdtype(dt)) if want_lo else None
+    part = torch.empty((4 * nblk, Cc), device=a.device, dtype=torch.float32)
+    check(_lib.load().nvit_res_rmsnorm_bwd(dt, _p(g), _p(g_add), _p(a), _p(y), dt_of(y) if y is not None else F32, _p(w),
+                                           _p(rstd), _p(dz), int(accum), _p(dz_lo), _p(part), nblk, M, Cc, _s()),
+          "nvit_res_rmsnorm_bwd")
+    return dz, dz_lo, part
+
+
+def res_skip_fwd(dt: int, h: Tensor, y: Tensor, skip: Tensor, x: Tensor, want_lo: bool = True):
+    """out = nrm((h + y) * skip + x) -> out fp32, out_lo (type dt) | None."""
+    M, Cc = h.shape
+    _chk_rows((M, Cc), y, f32=(h, x), name="res_skip_fwd")
+    _chk_vec(1, skip, name="res_skip_fwd")
+    out = torch.empty_like(h)
+    out_lo = torch.empty((M, Cc), device=h.device, dtype=tdtype(dt)) if want_lo else None
+    check(_lib.load().nvit_res_skip_fwd(dt, _p(h), _p(y), dt_of(y), _p(skip), _p(x), _p(out), _p(out_lo), M, Cc, _s()),
+          "nvit_res_skip_fwd")
+    return out, out_lo
+
+
+def res_skip_bwd(dt: int, dout: Tensor, h: Tensor, y: Tensor, skip: Tensor, x: Tensor, want_lo: bool = True):
+    """Backward of res_skip_fwd -> dh = d(h + y) fp32, dh_lo (type dt) | None, dx fp32, part_dskip [4*nblk]."""
+    M, Cc = h.shape
+    _chk_rows((M, Cc), y, f32=(dout, h, x), name="res_skip_bwd")
+    _chk_vec(1, skip, name="res_skip_bwd")
+    nblk = _row_part_blocks(M)
+    dh = torch.empty_like(h)
+    dx = torch.empty_like(h)
+    dh_lo = torch.empty((M, Cc), device=h.device, dtype=tdtype(dt)) if want_lo else None
+    part = torch.empty((4 * nblk,), device=h.device, dtype=torch.float32)
+    check(_lib.load().nvit_res_skip_bwd(dt, _p(dout), _p(h), _p(y), dt_of(y), _p(skip), _p(x), _p(dh), _p(dh_lo), _p(dx),
+                                        _p(part), nblk, M, Cc, _s()), "nvit_res_skip_bwd")
+    return dh, dh_lo, dx, part
+
+
 def norm_skip_fwd(src: Tensor, tgt: Optional[Tensor], skip: Tensor) -> Tensor:
     """nrm(src*skip + tgt); tgt None = justnorm(src*skip)."""
     M, Cc = src.shape
@@ -271,24 +367,29 @@ def norm_skip_bwd(dout: Tensor, src: Tensor, tgt: Optional[Tensor], skip: Tensor
     return dsrc, dtgt, dskip
 
 
-def qknorm_fwd(dt: int, q: Tensor, ldq: int, k: Tensor, ldk: int, v: Tensor, ldv: int, sqk: Tensor, c_q: float,
+def qknorm_fwd(dt: int, q: Tensor, ldq: int, k: Tensor, ldk: int, v: Tensor, ldv: int, sqk: Optional[Tensor], c_q: float,
                B: int, T: int, H: int, d: int):
-    dev = sqk.device
+    """sqk None: the head split alone (plain-ViT attention); rq, rk are then None."""
+    dev = q.device
     td = tdtype(BF16 if dt == _lib.BF16_F32IN else dt)   # BF16_F32IN: fp32 projection outputs in, bf16 head tensors out
     qh = torch.empty((B, H, T, d), device=dev, dtype=td)
     kh = torch.empty_like(qh)
     vh = torch.empty_like(qh)
-    rq = torch.empty((B * T, H), device=dev, dtype=torch.float32)
-    rk = torch.empty_like(rq)
+    if sqk is not None:
+        rq = torch.empty((B * T, H), device=dev, dtype=torch.float32)
+        rk = torch.empty_like(rq)
+    else:
+        rq = rk = None
     check(_lib.load().nvit_qknorm_fwd(dt, _p(q), ldq, _p(k), ldk, _p(v), ldv, _p(sqk), c_q, _p(qh), _p(kh), _p(vh),
                                       _p(rq), _p(rk), B, T, H, d, _s()), "nvit_qknorm_fwd")
     return qh, kh, vh, rq, rk
 
 
 def qknorm_bwd(dt: int, dqh, dkh, dvh, qh, kh, rq, rk, sqk, c_q: float, dq: Tensor, ldq: int, dk: Tensor, ldk: int,
-               dv: Tensor, ldv: int, B: int, T: int, H: int, d: int) -> Tensor:
+               dv: Tensor, ldv: int, B: int, T: int, H: int, d: int) -> Optional[Tensor]:
+    """sqk None: the head merge alone (backward of the plain split); returns None instead of the d(sqk) partials."""
     nblk = min(PART_BLOCKS, math.ceil(B * T / 4))
-    part = torch.empty((nblk, H * d), device=sqk.device, dtype=torch.float32)
+    part = torch.empty((nblk, H * d), device=dq.device, dtype=torch.float32) if sqk is not None else None
     check(_lib.load().nvit_qknorm_bwd(dt, _p(dqh), _p(dkh), _p(dvh), _p(qh), _p(kh), _p(rq), _p(rk), _p(sqk), c_q,
                                       _p(dq), ldq, _p(dk), ldk, _p(dv), ldv, _p(part), nblk, B, T, H, d, _s()),
           "nvit_qknorm_bwd")
@@ -411,16 +512,15 @@ def scale_cols(a: Tensor, s: Tensor, c: float, R: int, N: int, out: Tensor, lda:
 def attn_fwd(dt: int, impl: int, qh: Tensor, kh: Tensor, vh: Tensor, scale: float, sqk: Optional[Tensor] = None,
              c_q: float = 0.0, q_prescale: float = 1.0):
     """sqk/c_q given: q and k are (sqk*c_q) * unit vectors per head (the nViT call sites) -> bounded-score kernel path;
-    q_prescale: qh holds q_prescale * q_hat (only with sqk)."""
+    q_prescale: qh holds q_prescale * q_hat (without sqk: the running-maximum kernel on a pre-scaled q)."""
     B, H, Tq, d = qh.shape
     Tk = kh.shape[2]
     o = torch.empty((B * Tq, H * d), device=qh.device, dtype=tdtype(dt))
     lse = torch.empty((B, H, Tq), device=qh.device, dtype=torch.float32)
-    if sqk is not None:
+    if sqk is not None or q_prescale != 1.0:
         check(_lib.load().nvit_attn_fwd_bounded(dt, impl, _p(qh), _p(kh), _p(vh), scale, _p(sqk), c_q, q_prescale, _p(o),
                                                 _p(lse), B, H, Tq, Tk, d, _s()), "nvit_attn_fwd_bounded")
     else:
-        assert q_prescale == 1.0
         check(_lib.load().nvit_attn_fwd(dt, impl, _p(qh), _p(kh), _p(vh), scale, _p(o), _p(lse), B, H, Tq, Tk, d, _s()),
               "nvit_attn_fwd")
     return o, lse
@@ -443,12 +543,16 @@ def attn_bwd_qknorm(dout: Tensor, qh: Tensor, kh: Tensor, vh: Tensor, o: Tensor,
                     rq: Tensor, rk: Tensor, sqk: Tensor, c_q: float, dq: Tensor, ldq: int, dk: Tensor, dv: Tensor,
                     ldkv: int, q_prescale: float = 1.0):
     """MFMA attention backward + q/k-normalise backward in one pass (bf16, d=64).
-    Writes dq/dk/dv token-major; returns the partial sums (part_q, part_k) of d/d(sqk*c_q)."""
+    Writes dq/dk/dv token-major; returns the partial sums (part_q, part_k) of d/d(sqk*c_q).
+    sqk None (plain-ViT heads; rq, rk None): dq/dk/dv stored as they are, returns (None, None)."""
     B, H, Tq, d = qh.shape
     Tk = kh.shape[2]
     dev = qh.device
-    part_q = torch.empty((B * math.ceil(Tq / 128), H * d), device=dev, dtype=torch.float32)
-    part_k = torch.empty((B * math.ceil(Tk / 128), H * d), device=dev, dtype=torch.float32)
+    if sqk is None:
+        part_q = part_k = None
+    else:
+        part_q = torch.empty((B * math.ceil(Tq / 128), H * d), device=dev, dtype=torch.float32)
+        part_k = torch.empty((B * math.ceil(Tk / 128), H * d), device=dev, dtype=torch.float32)
     delta = torch.empty((2, B, H, Tq), device=dev, dtype=torch.float32)   # workspace: -delta | -lse*log2(e)
     check(_lib.load().nvit_attn_bwd_qknorm(BF16, _p(dout), _p(qh), _p(kh), _p(vh), _p(o), _p(lse), scale, _p(rq),
                                            _p(rk), _p(sqk), c_q, q_prescale, _p(dq), ldq, _p(dk), _p(dv), ldkv, _p(part_q),

@@ -51,7 +51,9 @@ def formula_tensor(name: str, shape: Tuple[int, ...], std: float, mean: float = 
 
 
 def param_shapes(cfg) -> Dict[str, Tuple[int, ...]]:
-    """state_dict parameter names -> shapes for an nViT-mode config."""
+    """state_dict parameter names -> shapes.  use_nvit=False: the plain-ViT set - no sz, alphas, sqk or
+    suv; RMSNorm weights on both cross-attention inputs (reference model.py:203-205)."""
+    nv = cfg.use_nvit
     C, L = cfg.n_embd, cfg.n_layer
     Pl, Pg, ch = cfg.local_patch_size, cfg.global_patch_size, cfg.channels
     T = (cfg.image_size // Pl) ** 2
@@ -59,13 +61,18 @@ def param_shapes(cfg) -> Dict[str, Tuple[int, ...]]:
     s: Dict[str, Tuple[int, ...]] = {}
     s["local_pos_embed"] = (1, T, C)
     s["global_pos_embed"] = (1, T, C)
-    s["sz"] = (cfg.num_classes,)
+    if nv:
+        s["sz"] = (cfg.num_classes,)
     s["local_patch_embed.weight"] = (C, ch, Pl, Pl)
     s["local_patch_embed.bias"] = (C,)
     s["global_patch_embed.1.weight"] = (C, ch, Pg, Pg)
     s["global_patch_embed.1.bias"] = (C,)
-    s["cross_attention.attn_alpha"] = (C,)
-    s["cross_attention.sqk"] = (C,)
+    if nv:
+        s["cross_attention.attn_alpha"] = (C,)
+        s["cross_attention.sqk"] = (C,)
+    else:
+        s["cross_attention.local_norm.weight"] = (C,)
+        s["cross_attention.global_norm.weight"] = (C,)
     for n in ("q_local", "k_global", "v_global", "out_proj"):
         s[f"cross_attention.{n}.weight"] = (C, C)
         if cfg.bias:
@@ -78,10 +85,11 @@ def param_shapes(cfg) -> Dict[str, Tuple[int, ...]]:
     for i in range(L):
         p = f"transformer.h.{i}."
         s[p + "skip_param"] = (1,)
-        s[p + "attn_alpha"] = (C,)
-        s[p + "mlp_alpha"] = (C,)
-        s[p + "sqk"] = (C,)
-        s[p + "suv"] = (8 * C,)
+        if nv:
+            s[p + "attn_alpha"] = (C,)
+            s[p + "mlp_alpha"] = (C,)
+            s[p + "sqk"] = (C,)
+            s[p + "suv"] = (8 * C,)
         for n in ("key", "query", "value", "att_c_proj"):
             s[p + n + ".weight"] = (C, C)
             if cfg.bias:
@@ -107,12 +115,14 @@ def param_shapes(cfg) -> Dict[str, Tuple[int, ...]]:
 
 
 def formula_state_dict(cfg, perturb_scalars: bool = True, salt: int = 0) -> Dict[str, torch.Tensor]:
-    """Full nViT-mode state_dict from the closed-form formula.
+    """Full state_dict (nViT or plain-ViT parameter set, see param_shapes) from the closed-form formula.
 
     Magnitudes mimic the reference's init (model.py:354-367: Linear N(0,0.02),
     *c_proj N(0,0.02/sqrt(2L)), Conv2d default bound 1/sqrt(fan_in)); learned
     scale vectors sit at their init value (model.py:68-81), optionally perturbed
-    by +-10 % so that tests exercise every per-channel gradient path.
+    by +-10 % so that tests exercise every per-channel gradient path.  The RMSNorm
+    weights are ones in nViT mode (where they are dead) and, perturbed the same way,
+    around one in plain-ViT mode (where they are live).
     """
     L = cfg.n_layer
     bs = float(cfg.base_scale)
@@ -134,8 +144,10 @@ def formula_state_dict(cfg, perturb_scalars: bool = True, salt: int = 0) -> Dict
             t = formula_tensor(name, shape, jit, 1.0, salt)
         elif leaf == "skip_param":
             t = formula_tensor(name, shape, jit, 1.0, salt)
-        elif "rmsnorm" in name:
+        elif "rmsnorm" in name and cfg.use_nvit:
             t = torch.ones(shape)
+        elif "rmsnorm" in name or name.endswith(("local_norm.weight", "global_norm.weight")):
+            t = formula_tensor(name, shape, jit, 1.0, salt)
         elif name == "mlp_head.0.weight":
             t = formula_tensor(name, shape, jit, 1.0, salt)
         elif name == "mlp_head.0.bias":

@@ -5,7 +5,7 @@ from nvit_amd import ViT
 from nvit_amd.config import named_config
 from nvit_amd.train import normalize_matrices, train_step
 from nvit_amd.weights import load_formula_weights, synthetic_batch
-cfg = named_config("base")
+cfg = named_config(sys.argv[1] if len(sys.argv) > 1 else "base")   # e.g. base_vit: the plain-ViT baseline
 dev = torch.device("cuda:0")
 m = ViT(cfg); load_formula_weights(m, cfg, perturb_scalars=False)
 m = m.to(dev).set_precision("bf16").train(); normalize_matrices(m)
