@@ -301,6 +301,24 @@ int nvit_attn_bwd_qknorm(int dt, const void* dout, const void* qh, const void* k
                          float q_prescale, void* dq, int ldq, void* dk, void* dv, int ldkv, float* part_q, float* part_k,
                          float* delta, int B, int H, int Tq, int Tk, int d, void* stream);
 
+/* ---- head-axis attention (the reference's flash_attn=True branch) -------------------------------------------
+ * flash_attn_func reads the reference's [B,H,T,d] tensors as [batch, seqlen, nheads, headdim] (model.py:121-122,252-253,
+ * SURVEY §9.1-Q3), so its softmax runs over the H heads of ONE token:
+ *   O[m, i*d:(i+1)*d] = sum_j softmax_j(scale * <q~_i, k~_j>) v_j,   i, j < H,  q~_i = (sqk*c_q)_i * nrm(q_i) (sqk != NULL)
+ * or q~ = q (sqk == NULL, plain ViT); k~ likewise.  Rows m < M; q [M, ldq], k and v [M, ldkv] fp32 (the projection GEMM
+ * outputs, token-major; self-attention: one [M,3C] buffer with ldq = ldkv = 3C).  O [M, C] contiguous, type dt (the A
+ * operand of the output projection); lse [M, H] fp32 (natural log of each softmax denominator), the only state the
+ * backward needs besides the inputs.  d in {32,64,128}; H <= NVIT_ATTN_HEADS_MAX_H. */
+#define NVIT_ATTN_HEADS_MAX_H 32
+int nvit_attn_heads_fwd(int dt, const float* q, int ldq, const float* k, const float* v, int ldkv, const float* sqk,
+                        float c_q, float scale, void* o, float* lse, int M, int H, int d, void* stream);
+/* Backward: dO [M, C] contiguous (type dt) -> dq [M, lddq], dk and dv [M, lddkv] (type dt), the normalise backward
+ * included; part_dsqk [nblk, C] fp32 partial sums of d/d(sqk*c_q), one row per workgroup, fixed order (reduce with
+ * nvit_colsum_reduce).  sqk == NULL: plain heads, part_dsqk is not written.  nblk in 1..8192 workgroups. */
+int nvit_attn_heads_bwd(int dt, const void* dout, const float* q, int ldq, const float* k, const float* v, int ldkv,
+                        const float* sqk, float c_q, float scale, const float* lse, void* dq, int lddq, void* dk,
+                        void* dv, int lddkv, float* part_dsqk, int nblk, int M, int H, int d, void* stream);
+
 /* ---- patch embedding / head / reconstruction -------------------------------------------
  * nvit_im2col: A_l [M, ch*Pl*Pl] and A_g [M, ch*Pg*Pg] (type dt, column order (c,ph,pw)) from
  * img fp32 [B,ch,S,S]; global windows are reflect-padded by (Pg-Pl)/2 and strided by Pl

@@ -17,6 +17,7 @@ KID_NAMES = ["gemm_nt", "gemm_tn", "attn_fwd", "attn_bwd", "rowops", "renorm", "
              "gemm_swiglu", "gemm_qknorm", "gemm_swiglu_bwd", "optim"]
 RENORM_ROWS_PER_ITEM = 64
 RENORM_COLS_PER_ITEM = 64
+ATTN_HEADS_MAX_H = 32   # include/nvit_hip.h NVIT_ATTN_HEADS_MAX_H
 
 _vp, _i, _f, _i64 = C.c_void_p, C.c_int, C.c_float, C.c_int64
 
@@ -63,6 +64,9 @@ SIGNATURES = {
     "nvit_attn_bwd": [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "nvit_attn_bwd_qknorm": [_i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _f, _f, _vp, _i, _vp, _vp, _i, _vp, _vp,
                              _vp, _i, _i, _i, _i, _i, _vp],
+    "nvit_attn_heads_fwd": [_i, _vp, _i, _vp, _vp, _i, _vp, _f, _f, _vp, _vp, _i, _i, _i, _vp],
+    "nvit_attn_heads_bwd": [_i, _vp, _vp, _i, _vp, _vp, _i, _vp, _f, _f, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i,
+                            _vp],
     "nvit_im2col": [_i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "nvit_patch_embed_kp": [_i],
     "nvit_patch_embed_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],

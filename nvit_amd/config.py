@@ -70,6 +70,10 @@ def named_config(name: str, **over) -> ViTConfig:
     # the plain-ViT baseline (use_nvit=False, the reference's nvit0_k0 profile) at the same shapes
     for base in ("micro", "mini", "tiny", "base"):
         table[base + "_vit"] = dict(table[base], use_nvit=False)
+    # flash_attn=True: the attention the reference's flash_attn_func call computes (softmax over the heads of each token,
+    # SURVEY §9.1-Q3); "micro_fa" is the model settings.yaml actually ships
+    for base in ("micro", "micro_k", "mini", "tiny", "base", "micro_vit"):
+        table[base + "_fa"] = dict(table[base], flash_attn=True)
     kw = dict(common)
     kw.update(table[name])
     kw.update(over)

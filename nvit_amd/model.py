@@ -9,10 +9,13 @@ sub-modules are parameter containers only: their torch forward is never called. 
 compute goes through the C ABI in include/nvit_hip.h (nvit_amd/ops.py); there is no CPU
 or torch-operator fallback — without the HIP library or a GPU, forward() raises.
 
-Both paths are implemented with SDPA semantics (`flash_attn` ignored: the reference's flash_attn=True branch attends
-over the wrong axis, Q3): nViT (`use_nvit=True`) and the plain-ViT baseline (`use_nvit=False`, without the Kohonen head),
-whose reference construction bug (the RMSNorm modules its forward calls are built only for nViT) is
-repaired by building `rmsnorm_att` / `rmsnorm_mlp` in both modes.
+Both paths are implemented: nViT (`use_nvit=True`) and the plain-ViT baseline (`use_nvit=False`, without the Kohonen head),
+each with both attention forms the reference selects by `flash_attn`.  `flash_attn=False` is SDPA over the tokens.
+`flash_attn=True` computes what the reference's flash_attn_func call computes on its [B,H,T,d] tensors, which
+flash-attn reads as [batch, seqlen, nheads, headdim]: a softmax over the H heads of each token, with no token mixing
+(nvit_attn_heads_fwd/bwd, at most 32 heads).  The plain-ViT baseline's reference construction bug
+(the RMSNorm modules its forward calls are built only for nViT) is repaired by building
+`rmsnorm_att` / `rmsnorm_mlp` in both modes.
 
 Precision modes (model.precision): "bf16" = bf16 MFMA operands, fp32 accumulate, fp32
 residual stream/norms/params/grads (the performance mode); "fp32" = exact-f32 MFMA
@@ -28,7 +31,7 @@ import torch
 from torch import nn
 
 from . import ops
-from ._lib import BF16, BF16_F32IN, F32
+from ._lib import ATTN_HEADS_MAX_H, BF16, BF16_F32IN, F32
 from .config import ViTConfig
 from .kohonen import CosConsistencyFn, HuberFn, KohonenMap, MapSmoothnessFn
 
@@ -219,6 +222,19 @@ def _attn_part_fwd(rt: _Runtime, impl: int, q_src, ldq, k_src, ldk, v_src, ldv, 
     return qh, kh, vh, rq, rk, o, lse
 
 
+def _heads_fwd(rt: _Runtime, q, ldq, k, v, ldkv, sqk, c_q, scale, H, d):
+    """The reference's flash_attn=True attention (model.py:121-122,252-253): flash_attn_func reads its [B,H,T,d] arguments
+    as [batch, seqlen, nheads, headdim], so the softmax runs over the H heads of each token.  q, k, v:
+    the fp32 token-major projection outputs; -> O [M, C] (the output projection's A operand) and lse [M, H]."""
+    return ops.attn_heads_fwd(rt.dt, q, ldq, k, v, ldkv, sqk, c_q, scale, q.shape[0], H, d)
+
+
+def _heads_bwd(rt: _Runtime, do, q, ldq, k, v, ldkv, sqk, c_q, scale, lse, dq, lddq, dk, dv, lddkv, H, d):
+    """Backward of _heads_fwd into token-major dq / dk / dv; returns the d(sqk*c_q) partials (None for plain heads)."""
+    return ops.attn_heads_bwd(rt.dt, do, q, ldq, k, v, ldkv, sqk, c_q, scale, lse, dq, lddq, dk, dv, lddkv, q.shape[0],
+                              H, d)
+
+
 def _param_grad_alpha(rt, part: Tensor, alpha: Tensor, c_a: float, batch: "ops.ReduceBatch") -> Tensor:
     g = rt.grad_buf((alpha,), alpha.shape)
     batch.add(part, g, False, kind=1, ref=alpha, scale=c_a)
@@ -291,7 +307,14 @@ class _BlockFn(torch.autograd.Function):
         c_q, c_a = 1.0 / cfg.base_scale, 0.05 / cfg.base_scale
         pre = f"h{idx}."
         has_b = bq is not None
-        if not has_b and d == 64 and ops.fusable(dt, M, 3 * C, C):
+        heads = cfg.flash_attn
+        if heads:
+            # flash_attn=True: attention over the heads of each token (see _heads_fwd); q/k/v stay token-major fp32
+            qpre = 1.0
+            qkv = ops.gemm_nt(x_lo, sh[pre + "qkv.W"], M, 3 * C, C, out_dtype=torch.float32, bias=sh.get(pre + "qkv.b"))
+            o, lse = _heads_fwd(rt, qkv, 3 * C, qkv[:, C:], qkv[:, 2 * C:], 3 * C, sqk, c_q, math.sqrt(d), H, d)
+            qh, kh, vh, rq, rk = qkv, None, None, None, None
+        elif not has_b and d == 64 and ops.fusable(dt, M, 3 * C, C):
             # q/k/v projection with the per-head normalise + sqk scale + head split in the GEMM epilogue
             # (q leaves the epilogue pre-scaled by sqrt(d)*log2(e): the attention kernels' exponent needs no multiply)
             qpre = ops.attn_q_prescale(d) if impl == 1 else 1.0
@@ -330,6 +353,7 @@ class _BlockFn(torch.autograd.Function):
         if dt == F32:
             xn_lo = xn.new_empty(0)  # placeholder: callers alias x itself in fp32 mode (see _lo())
         ctx.rt, ctx.idx, ctx.with_skip, ctx.impl, ctx.has_b = rt, idx, with_skip, impl, has_b
+        ctx.heads = heads
         ctx.chained = bool(chained)   # called from ViT.forward's block chain: the consumer of dx is our own backward node
         ctx.qpre = qpre
         ctx.dims = (B, T, C, H, d, M)
@@ -401,7 +425,11 @@ class _BlockFn(torch.autograd.Function):
         ops.gemm_tn(dy_lo, o, g_wo, M, C, C)
         g_bo = _bias_grad(dy_lo, M, C) if ctx.has_b else None
         dqkv = torch.empty((M, 3 * C), device=x.device, dtype=td)
-        if impl == 1 and d == 64 and dt != F32:
+        if ctx.heads:   # qh holds the fp32 [M, 3C] projection outputs
+            part_sqk = _heads_bwd(rt, do, qh, 3 * C, qh[:, C:], qh[:, 2 * C:], 3 * C, sqk, c_q, math.sqrt(d), lse, dqkv,
+                                  3 * C, dqkv[:, C:], dqkv[:, 2 * C:], 3 * C, H, d)
+            d_sqk = _param_grad_scaled(rt, part_sqk, p_sqk, c_q, red)
+        elif impl == 1 and d == 64 and dt != F32:
             # attention backward with the q/k-normalise backward fused into its epilogues
             part_q, part_k = ops.attn_bwd_qknorm(do, qh, kh, vh, o, lse, math.sqrt(d), rq, rk, sqk, c_q, dqkv, 3 * C,
                                                  dqkv[:, C:], dqkv[:, 2 * C:], 3 * C, q_prescale=ctx.qpre)
@@ -451,7 +479,14 @@ class _CrossFn(torch.autograd.Function):
         else:   # bf16 operand copies: handed in by the producer (patch-embedding epilogue) or cast here
             loc_lo = ops.cast(loc, dt) if loc_lo is None else loc_lo
             glo_lo = ops.cast(glo, dt) if glo_lo is None else glo_lo
-        if not has_b and d == 64 and ops.fusable(dt, M, C, C):
+        heads = cfg.flash_attn
+        if heads:   # flash_attn=True: q from token t of the local stream, k/v from token t of the global stream
+            qpre = 1.0
+            q = ops.gemm_nt(loc_lo, sh["x.q.W"], M, C, C, out_dtype=torch.float32, bias=sh.get("x.q.b"))
+            kv = ops.gemm_nt(glo_lo, sh["x.kv.W"], M, 2 * C, C, out_dtype=torch.float32, bias=sh.get("x.kv.b"))
+            o, lse = _heads_fwd(rt, q, C, kv, kv[:, C:], 2 * C, sqk, c_q, math.sqrt(d), H, d)
+            qh, kh, vh, rq, rk = q, kv, None, None, None
+        elif not has_b and d == 64 and ops.fusable(dt, M, C, C):
             bufs = ops.qk_buffers(dt, B, T, H, d, loc.device)
             qpre = ops.attn_q_prescale(d) if impl == 1 else 1.0
             ops.gemm_nt_qknorm(loc_lo, sh["x.q.W"], M, C, 1, 0, sqk, c_q, B, T, H, d, bufs, q_prescale=qpre)
@@ -479,6 +514,7 @@ class _CrossFn(torch.autograd.Function):
         if dt == F32:
             x_lo = x.new_empty(0)
         ctx.rt, ctx.impl, ctx.has_b = rt, impl, has_b
+        ctx.heads = heads
         ctx.chained = bool(chained)
         ctx.qpre = qpre
         ctx.dims = (B, T, C, H, d, M)
@@ -519,7 +555,11 @@ class _CrossFn(torch.autograd.Function):
         g_bproj = _bias_grad(dpr, M, 2 * C, perm=1) if ctx.has_b else None
         dq = torch.empty((M, C), device=dev, dtype=td)
         dkv = torch.empty((M, 2 * C), device=dev, dtype=td)
-        if impl == 1 and d == 64 and dt != F32:
+        if ctx.heads:   # qh, kh hold the fp32 q [M, C] and kv [M, 2C] projection outputs
+            part_sqk = _heads_bwd(rt, do, qh, C, kh, kh[:, C:], 2 * C, sqk, c_q, math.sqrt(d), lse, dq, C, dkv, dkv[:, C:],
+                                  2 * C, H, d)
+            d_sqk = _param_grad_scaled(rt, part_sqk, p_sqk, c_q, red)
+        elif impl == 1 and d == 64 and dt != F32:
             part_q, part_k = ops.attn_bwd_qknorm(do, qh, kh, vh, o, lse, math.sqrt(d), rq, rk, sqk, c_q, dq, C, dkv,
                                                  dkv[:, C:], 2 * C, q_prescale=ctx.qpre)
             d_sqk = _param_grad_scaled(rt, part_q, p_sqk, c_q, red, part_b=part_k)
@@ -595,8 +635,14 @@ class _StdBlockFn(torch.autograd.Function):
         a, a_lo, r_att = ops.res_rmsnorm_fwd(dt, x, None, w_att.detach(), RMS_EPS, want_lo=lo)
         if not lo:
             a_lo = a
-        fused = not has_b and impl == 1 and d == 64 and ops.fusable(dt, M, 3 * C, C)
-        if fused:
+        heads = cfg.flash_attn
+        fused = not heads and not has_b and impl == 1 and d == 64 and ops.fusable(dt, M, 3 * C, C)
+        if heads:   # flash_attn=True: attention over the heads of each token, scale 1/sqrt(d)
+            qpre = 1.0
+            qkv = ops.gemm_nt(a_lo, sh[pre + "qkv.W"], M, 3 * C, C, out_dtype=torch.float32, bias=sh.get(pre + "qkv.b"))
+            o, lse = _heads_fwd(rt, qkv, 3 * C, qkv[:, C:], qkv[:, 2 * C:], 3 * C, None, 0.0, 1.0 / math.sqrt(d), H, d)
+            qh, kh, vh = qkv, None, None
+        elif fused:
             # q/k/v projection with the head split in the GEMM epilogue (split-only EPI 4); q leaves pre-scaled
             qpre = _std_q_prescale(d)
             qh, kh, vh, _, _ = ops.gemm_nt_qknorm(a_lo, sh[pre + "qkv.W"], M, C, 3, 0, None, 0.0, B, T, H, d,
@@ -606,7 +652,8 @@ class _StdBlockFn(torch.autograd.Function):
             qkv = ops.gemm_nt(a_lo, sh[pre + "qkv.W"], M, 3 * C, C, out_dtype=torch.float32, bias=sh.get(pre + "qkv.b"))
             qh, kh, vh = _split_heads(rt, qkv, 3 * C, qkv[:, C:], 3 * C, qkv[:, 2 * C:], 3 * C, B, T, H, d)
             del qkv
-        o, lse = ops.attn_fwd(dt, impl, qh, kh, vh, 1.0 / math.sqrt(d), q_prescale=qpre)
+        if not heads:
+            o, lse = ops.attn_fwd(dt, impl, qh, kh, vh, 1.0 / math.sqrt(d), q_prescale=qpre)
         y = ops.gemm_nt(o, sh[pre + "o.W"], M, C, C, out_dtype=rt.y_dtype(), bias=sh.get(pre + "o.b"))
         bm, bm_lo, r_mlp = ops.res_rmsnorm_fwd(dt, a, y, w_mlp.detach(), RMS_EPS, want_lo=lo)
         if not lo:
@@ -631,7 +678,7 @@ class _StdBlockFn(torch.autograd.Function):
         if xn_lo is None:
             xn_lo = xn.new_empty(0)   # fp32 mode: callers alias the stream itself (see _lo())
         ctx.rt, ctx.idx, ctx.with_skip, ctx.impl, ctx.has_b = rt, idx, with_skip, impl, has_b
-        ctx.fused, ctx.qpre = fused, qpre
+        ctx.fused, ctx.qpre, ctx.heads = fused, qpre, heads
         ctx.dims = (B, T, C, H, d, M)
         ctx.par = (skip_param, w_att, w_mlp, wq, wk, wv, wo, wfc, wp)   # gradient destinations
         ctx.save_for_backward(x, a, a_lo, r_att, qh, kh, vh, o, lse, y, bm, bm_lo, r_mlp, uv, xm, y2, skip_param,
@@ -684,8 +731,12 @@ class _StdBlockFn(torch.autograd.Function):
         g_wo = ops.gemm_tn(dy_lo, o, rt.grad_buf((p_wo,), (C, C)), M, C, C)
         g_bo = _bias_grad(dy_lo, M, C) if ctx.has_b else None
         dqkv = torch.empty((M, 3 * C), device=x.device, dtype=td)
-        _merge_heads(rt, do, qh, kh, vh, o, lse, impl, d, ctx.qpre, ctx.fused, dqkv, 3 * C, dqkv[:, C:], dqkv[:, 2 * C:],
-                     3 * C, B, T, H)
+        if ctx.heads:   # qh holds the fp32 [M, 3C] projection outputs
+            _heads_bwd(rt, do, qh, 3 * C, qh[:, C:], qh[:, 2 * C:], 3 * C, None, 0.0, 1.0 / math.sqrt(d), lse, dqkv, 3 * C,
+                       dqkv[:, C:], dqkv[:, 2 * C:], 3 * C, H, d)
+        else:
+            _merge_heads(rt, do, qh, kh, vh, o, lse, impl, d, ctx.qpre, ctx.fused, dqkv, 3 * C, dqkv[:, C:],
+                         dqkv[:, 2 * C:], 3 * C, B, T, H)
         da_add = ops.gemm_nt(dqkv, sh[pre + "qkv.Wt"], M, C, 3 * C, out_dtype=td)
         g_qkv = rt.grad_buf((p_wq, p_wk, p_wv), (3 * C, C))
         ops.gemm_tn(dqkv, a_lo, g_qkv, M, 3 * C, C)
@@ -723,8 +774,15 @@ class _StdCrossFn(torch.autograd.Function):
         gn, gn_lo, r_g = ops.res_rmsnorm_fwd(dt, glo, None, w_gn.detach(), RMS_EPS, want_lo=lo)
         if not lo:
             ln_lo, gn_lo = ln, gn
-        fused = not has_b and impl == 1 and d == 64 and ops.fusable(dt, M, C, C)
-        if fused:   # split-only EPI 4 (q from the local side, k/v from the global side), q pre-scaled
+        heads = cfg.flash_attn
+        fused = not heads and not has_b and impl == 1 and d == 64 and ops.fusable(dt, M, C, C)
+        if heads:   # flash_attn=True: attention over the heads of each token, scale 1/sqrt(d)
+            qpre = 1.0
+            q = ops.gemm_nt(ln_lo, sh["x.q.W"], M, C, C, out_dtype=torch.float32, bias=sh.get("x.q.b"))
+            kv = ops.gemm_nt(gn_lo, sh["x.kv.W"], M, 2 * C, C, out_dtype=torch.float32, bias=sh.get("x.kv.b"))
+            o, lse = _heads_fwd(rt, q, C, kv, kv[:, C:], 2 * C, None, 0.0, 1.0 / math.sqrt(d), H, d)
+            qh, kh, vh = q, kv, None
+        elif fused:   # split-only EPI 4 (q from the local side, k/v from the global side), q pre-scaled
             qpre = _std_q_prescale(d)
             bufs = ops.qk_buffers(dt, B, T, H, d, loc.device, norm=False)
             ops.gemm_nt_qknorm(ln_lo, sh["x.q.W"], M, C, 1, 0, None, 0.0, B, T, H, d, bufs, q_prescale=qpre)
@@ -735,7 +793,8 @@ class _StdCrossFn(torch.autograd.Function):
             kv = ops.gemm_nt(gn_lo, sh["x.kv.W"], M, 2 * C, C, out_dtype=torch.float32, bias=sh.get("x.kv.b"))
             qh, kh, vh = _split_heads(rt, q, C, kv, 2 * C, kv[:, C:], 2 * C, B, T, H, d)
             del q, kv
-        o, lse = ops.attn_fwd(dt, impl, qh, kh, vh, 1.0 / math.sqrt(d), q_prescale=qpre)
+        if not heads:
+            o, lse = ops.attn_fwd(dt, impl, qh, kh, vh, 1.0 / math.sqrt(d), q_prescale=qpre)
         if not has_b and ops.fusable(dt, M, 2 * C, C):
             pr, g = ops.gemm_nt_swiglu(o, sh["x.proj.W"], M, C, C, None, 1.0)
         else:
@@ -748,7 +807,7 @@ class _StdCrossFn(torch.autograd.Function):
             del pr32
         out = ops.gemm_nt(g, sh["x.out.W"], M, C, C, out_dtype=torch.float32, bias=sh.get("x.out.b"))
         ctx.rt, ctx.impl, ctx.has_b = rt, impl, has_b
-        ctx.fused, ctx.qpre = fused, qpre
+        ctx.fused, ctx.qpre, ctx.heads = fused, qpre, heads
         ctx.dims = (B, T, C, H, d, M)
         ctx.par = (w_ln, w_gn, wq, wk, wv, wproj, wout)
         ctx.save_for_backward(loc, glo, ln_lo, gn_lo, r_l, r_g, qh, kh, vh, o, lse, pr, g, w_ln, w_gn)
@@ -781,7 +840,11 @@ class _StdCrossFn(torch.autograd.Function):
         g_bproj = _bias_grad(dpr, M, 2 * C, perm=1) if ctx.has_b else None
         dq = torch.empty((M, C), device=dev, dtype=td)
         dkv = torch.empty((M, 2 * C), device=dev, dtype=td)
-        _merge_heads(rt, do, qh, kh, vh, o, lse, impl, d, ctx.qpre, ctx.fused, dq, C, dkv, dkv[:, C:], 2 * C, B, T, H)
+        if ctx.heads:   # qh, kh hold the fp32 q [M, C] and kv [M, 2C] projection outputs
+            _heads_bwd(rt, do, qh, C, kh, kh[:, C:], 2 * C, None, 0.0, 1.0 / math.sqrt(d), lse, dq, C, dkv, dkv[:, C:],
+                       2 * C, H, d)
+        else:
+            _merge_heads(rt, do, qh, kh, vh, o, lse, impl, d, ctx.qpre, ctx.fused, dq, C, dkv, dkv[:, C:], 2 * C, B, T, H)
         dln = ops.gemm_nt(dq, sh["x.q.Wt"], M, C, C, out_dtype=torch.float32)
         dgn = ops.gemm_nt(dkv, sh["x.kv.Wt"], M, C, 2 * C, out_dtype=torch.float32)
         g_wq = ops.gemm_tn(dq, ln_lo, rt.grad_buf((p_wq,), (C, C)), M, C, C)
@@ -1121,6 +1184,9 @@ class ViT(nn.Module):
             raise ValueError("n_embd must be a multiple of 64 and divisible by n_head")
         if (config.n_embd // config.n_head) not in HEAD_DIMS:
             raise ValueError(f"head dim must be one of {HEAD_DIMS} (got {config.n_embd // config.n_head})")
+        if config.flash_attn and config.n_head > ATTN_HEADS_MAX_H:
+            raise ValueError(f"flash_attn=True (attention over the heads of each token) is built for at most "
+                             f"{ATTN_HEADS_MAX_H} heads (got n_head={config.n_head})")
         self.config = config
         self.step = 0
         self.total_steps = 0

@@ -560,6 +560,35 @@ def attn_bwd_qknorm(dout: Tensor, qh: Tensor, kh: Tensor, vh: Tensor, o: Tensor,
     return part_q, part_k
 
 
+def attn_heads_fwd(dt: int, q: Tensor, ldq: int, k: Tensor, v: Tensor, ldkv: int, sqk: Optional[Tensor], c_q: float,
+                   scale: float, M: int, H: int, d: int):
+    """Head-axis attention of the reference's flash_attn=True branch (softmax over the H heads of each token) from the
+    fp32 token-major projection outputs.  sqk None: plain heads.  -> O [M, C] (type dt), lse [M, H] fp32."""
+    _chk_dev(q, k, v)
+    o = torch.empty((M, H * d), device=q.device, dtype=tdtype(dt))
+    lse = torch.empty((M, H), device=q.device, dtype=torch.float32)
+    check(_lib.load().nvit_attn_heads_fwd(dt, _p(q), ldq, _p(k), _p(v), ldkv, _p(sqk), c_q, scale, _p(o), _p(lse), M, H, d,
+                                          _s()), "nvit_attn_heads_fwd")
+    return o, lse
+
+
+ATTN_HEADS_BWD_BLOCKS = 4096   # one-wave workgroups of the head-axis backward (rows of its d(sqk) partials)
+
+
+def attn_heads_bwd(dt: int, dout: Tensor, q: Tensor, ldq: int, k: Tensor, v: Tensor, ldkv: int, sqk: Optional[Tensor],
+                   c_q: float, scale: float, lse: Tensor, dq: Tensor, lddq: int, dk: Tensor, dv: Tensor, lddkv: int,
+                   M: int, H: int, d: int) -> Optional[Tensor]:
+    """Backward of attn_heads_fwd into token-major dq / dk / dv (type dt).  Returns the [nblk, C] partial sums of
+    d/d(sqk*c_q) (None without sqk)."""
+    _chk_dev(dout, q, k, v, lse, dq, dk, dv)
+    nblk = max(1, min(ATTN_HEADS_BWD_BLOCKS, M))
+    part = torch.empty((nblk, H * d), device=q.device, dtype=torch.float32) if sqk is not None else None
+    check(_lib.load().nvit_attn_heads_bwd(dt, _p(dout), _p(q), ldq, _p(k), _p(v), ldkv, _p(sqk), c_q, scale, _p(lse),
+                                          _p(dq), lddq, _p(dk), _p(dv), lddkv, _p(part), nblk, M, H, d, _s()),
+          "nvit_attn_heads_bwd")
+    return part
+
+
 # ----------------------------------------------------------------------------- embed / head
 def im2col(dt: int, img: Tensor, Pl: int, Pg: int):
     B, ch, S, _ = img.shape
