@@ -215,26 +215,6 @@ class _Runtime:
 # --------------------------------------------------------------------------------------------
 # Functional forward / backward pieces (all compute through ops.*)
 # --------------------------------------------------------------------------------------------
-def _attn_part_fwd(rt: _Runtime, impl: int, q_src, ldq, k_src, ldk, v_src, ldv, sqk, c_q, B, T, H, d):
-    dt_in = rt.dt if rt.dt == F32 else BF16_F32IN   # the projection outputs are fp32 in both modes
-    qh, kh, vh, rq, rk = ops.qknorm_fwd(dt_in, q_src, ldq, k_src, ldk, v_src, ldv, sqk, c_q, B, T, H, d)
-    o, lse = ops.attn_fwd(rt.dt, impl, qh, kh, vh, math.sqrt(d), sqk, c_q)
-    return qh, kh, vh, rq, rk, o, lse
-
-
-def _heads_fwd(rt: _Runtime, q, ldq, k, v, ldkv, sqk, c_q, scale, H, d):
-    """The reference's flash_attn=True attention (model.py:121-122,252-253): flash_attn_func reads its [B,H,T,d] arguments
-    as [batch, seqlen, nheads, headdim], so the softmax runs over the H heads of each token.  q, k, v:
-    the fp32 token-major projection outputs; -> O [M, C] (the output projection's A operand) and lse [M, H]."""
-    return ops.attn_heads_fwd(rt.dt, q, ldq, k, v, ldkv, sqk, c_q, scale, q.shape[0], H, d)
-
-
-def _heads_bwd(rt: _Runtime, do, q, ldq, k, v, ldkv, sqk, c_q, scale, lse, dq, lddq, dk, dv, lddkv, H, d):
-    """Backward of _heads_fwd into token-major dq / dk / dv; returns the d(sqk*c_q) partials (None for plain heads)."""
-    return ops.attn_heads_bwd(rt.dt, do, q, ldq, k, v, ldkv, sqk, c_q, scale, lse, dq, lddq, dk, dv, lddkv, q.shape[0],
-                              H, d)
-
-
 def _param_grad_alpha(rt, part: Tensor, alpha: Tensor, c_a: float, batch: "ops.ReduceBatch") -> Tensor:
     g = rt.grad_buf((alpha,), alpha.shape)
     batch.add(part, g, False, kind=1, ref=alpha, scale=c_a)
@@ -289,6 +269,127 @@ def _take_carry(rt: "_Runtime", idx: int, chained: bool, dout: Tensor):
     return dout, add
 
 
+RMS_EPS = 1e-6   # reference RMSNorm default (model.py:171)
+
+
+def _dims(rt: _Runtime, M: int):
+    """(B, T, C, H, d, M) of a block call over M = B*T token rows."""
+    cfg = rt.model.config
+    T = rt.model.n_tokens
+    return M // T, T, cfg.n_embd, cfg.n_head, cfg.n_embd // cfg.n_head, M
+
+
+def _qkv_cols(ts, C: int):
+    """(q, ldq, k, v, ldkv): q, k, v as column views of the stacked projection outputs, or of their gradients, `ts`:
+    one [M, 3C] tensor (self-attention) or [M, C] and [M, 2C] (cross-attention)."""
+    if len(ts) == 1:
+        qkv, = ts
+        return qkv, 3 * C, qkv[:, C:], qkv[:, 2 * C:], 3 * C
+    q, kv = ts
+    return q, C, kv, kv[:, C:], 2 * C
+
+
+def _attn_fwd(rt: _Runtime, impl: int, srcs, has_b: bool, sqk: Optional[Tensor], c_q: float, scale: float, dims):
+    """The attention of every block function, from its q/k/v projection sources to O [M, C] (the output projection's A
+    operand).  srcs: ((A, shadow prefix, parts), ...), one projection GEMM each, their output columns q | k | v in
+    order.  sqk None (c_q 0.0): plain-ViT heads, else the nViT normalise + sqk scale.  One of three routes:
+      heads  flash_attn=True: the reference's flash_attn_func reads its [B,H,T,d] arguments as [batch, seqlen, nheads,
+             headdim], so the softmax runs over the H heads of each token of the fp32 token-major
+             projections;
+      fused  no bias, d = 64 and a shape the fused GEMM takes (bf16 only; N of the FIRST projection decides): the
+             normalise (nViT) and the head split in the projection GEMM's epilogue, q pre-scaled so that the attention
+             kernels' exponent needs no multiply;
+      split  otherwise (small problems: 128x128 GEMM kernel): the projections leave the GEMM in fp32 and are normalised
+             from the unrounded values, like the fused epilogue (one rounding, at the head tensors).
+    -> o, lse, att (route, impl, q pre-scale, scale) for _attn_bwd, and the tensors it reads: the fp32 projections
+    (heads) or qh, kh, vh, rq, rk."""
+    B, T, C, H, d, M = dims
+    dt, sh = rt.dt, rt.sh
+    heads = rt.model.config.flash_attn
+    if not heads and not has_b and impl == 1 and d == 64 and ops.fusable(dt, M, srcs[0][2] * C, C):
+        route = "fused"
+        # the softmax scale (nViT: sqrt(d) on unit q, k) times log2(e); with sqk absent the running-maximum kernel runs
+        # on the pre-scaled q (and the dK/dV backward takes its generated loop)
+        qpre = ops.attn_q_prescale(d) if sqk is not None else ops.LOG2E / math.sqrt(d)
+        bufs = ops.qk_buffers(dt, B, T, H, d, srcs[0][0].device, norm=sqk is not None)
+        part0 = 0
+        for A, w, n in srcs:
+            ops.gemm_nt_qknorm(A, sh[w + ".W"], M, C, n, part0, sqk, c_q, B, T, H, d, bufs,
+                               q_prescale=(qpre if part0 == 0 else 1.0))
+            part0 += n
+    else:
+        projs = [ops.gemm_nt(A, sh[w + ".W"], M, n * C, C, out_dtype=torch.float32, bias=sh.get(w + ".b"))
+                 for A, w, n in srcs]
+        q, ldq, k, v, ldkv = _qkv_cols(projs, C)
+        if heads:
+            o, lse = ops.attn_heads_fwd(dt, q, ldq, k, v, ldkv, sqk, c_q, scale, M, H, d)
+            return o, lse, ("heads", impl, 1.0, scale), tuple(projs)
+        route, qpre = "split", 1.0
+        dt_in = dt if dt == F32 else BF16_F32IN   # the projection outputs are fp32 in both modes
+        bufs = ops.qknorm_fwd(dt_in, q, ldq, k, ldkv, v, ldkv, sqk, c_q, B, T, H, d)
+        if sqk is None:   # plain heads free the projections before O is allocated, nViT after attn_fwd (at return)
+            del projs, q, k, v
+    qh, kh, vh, _, _ = bufs
+    o, lse = ops.attn_fwd(dt, impl, qh, kh, vh, scale, sqk, c_q, q_prescale=qpre)
+    return o, lse, (route, impl, qpre, scale), bufs
+
+
+def _attn_bwd(rt: _Runtime, att, saved, do: Tensor, o: Tensor, lse: Tensor, grads, sqk: Optional[Tensor], c_q: float,
+              dims):
+    """Backward of _attn_fwd (att, saved: what it returned) into the token-major projection gradients `grads`, stacked
+    like the projection outputs.  -> (part, part_k): the d(sqk*c_q) partials for the block's ReduceBatch (part_k: the k
+    side of the fused backward, else None); (None, None) for plain heads."""
+    B, T, C, H, d, M = dims
+    dt = rt.dt
+    route, impl, qpre, scale = att
+    dq, lddq, dk, dv, lddkv = _qkv_cols(grads, C)
+    if route == "heads":
+        q, ldq, k, v, ldkv = _qkv_cols(saved, C)
+        return ops.attn_heads_bwd(dt, do, q, ldq, k, v, ldkv, sqk, c_q, scale, lse, dq, lddq, dk, dv, lddkv, M, H,
+                                  d), None
+    qh, kh, vh, rq, rk = saved
+    # attention backward with the q/k-normalise backward (nViT) fused into its epilogues, dq/dk/dv stored token-major:
+    # nViT after either forward route (the split one leaves q unscaled, qpre 1); plain heads after the fused one only
+    fused_bwd = (dt != F32 and d == 64) if sqk is not None else route == "fused"
+    if fused_bwd:
+        return ops.attn_bwd_qknorm(do, qh, kh, vh, o, lse, scale, rq, rk, sqk, c_q, dq, lddq, dk, dv, lddkv,
+                                   q_prescale=qpre)
+    dqh, dkh, dvh = ops.attn_bwd(dt, impl, do, qh, kh, vh, o, lse, scale)
+    return ops.qknorm_bwd(dt, dqh, dkh, dvh, qh, kh, rq, rk, sqk, c_q, dq, lddq, dk, lddkv, dv, lddkv, B, T, H, d), None
+
+
+def _swiglu_fwd(rt: _Runtime, A: Tensor, w: str, M: int, F: int, K: int, has_b: bool, gs: Optional[Tensor],
+                gs_fused: Optional[Tensor], gscale: float):
+    """Gated MLP input: uv = A W^T (+ bias) [M, 2F] (shadow `w`, interleaved columns) and x = swiglu(uv) [M, F] with the
+    gate scale gs * gscale (gs None: 1).  -> (uv as backward reads it, x).  The fused GEMM epilogue takes gs in the
+    shadow's interleaved column order (gs_fused), the row kernel in natural order (gs)."""
+    dt, sh = rt.dt, rt.sh
+    if not has_b and ops.fusable(dt, M, 2 * F, K):
+        return ops.gemm_nt_swiglu(A, sh[w + ".W"], M, F, K, gs_fused, gscale)
+    uv32 = ops.gemm_nt(A, sh[w + ".W"], M, 2 * F, K, out_dtype=torch.float32, bias=sh.get(w + ".b"))
+    # bf16: the gate from the unrounded pre-activations; the bf16 copy is what backward reads
+    x = ops.swiglu_fwd(dt if dt == F32 else BF16_F32IN, uv32, gs, gscale, M, F)
+    return (uv32 if dt == F32 else ops.cast(uv32, dt)), x
+
+
+def _swiglu_bwd(rt: _Runtime, dy: Tensor, w: str, uv: Tensor, M: int, F: int, K: int, gs: Optional[Tensor],
+                gscale: float):
+    """dy [M, K] through the following projection (transposed shadow `w`, [F, K]) and the SwiGLU backward: fused, the
+    gate backward runs in the GEMM epilogue (dx never reaches HBM).  -> duv [M, 2F], d(gs) partials (None without gs)."""
+    dt, sh = rt.dt, rt.sh
+    if ops.fusable(dt, M, F, K):
+        return ops.gemm_nt_swiglu_bwd(dy, sh[w + ".Wt"], uv, M, F, K, gs, gscale)
+    dx = ops.gemm_nt(dy, sh[w + ".Wt"], M, F, K, out_dtype=ops.tdtype(dt))
+    return ops.swiglu_bwd(dt, dx, uv, gs, gscale, M, F)
+
+
+def _wgrad(rt: _Runtime, dy: Tensor, a: Tensor, params, M: int, N: int, K: int, has_b: bool, perm: int = 0):
+    """Weight gradient dy^T a [N, K] of a linear into its destination (see _Runtime.grad_buf) and its bias gradient (None
+    without bias).  perm 1: the rows of an interleaved (SwiGLU) shadow."""
+    g = ops.gemm_tn(dy, a, rt.grad_buf(params, (N, K)), M, N, K, perm=perm)
+    return g, (_bias_grad(dy, M, N, perm) if has_b else None)
+
+
 class _BlockFn(torch.autograd.Function):
     """One nGPT block (+ norm_skip): reference Block.forward (model.py:92-169) followed by
     Block.norm_skip (model.py:84-87) as called at model.py:450-452."""
@@ -297,54 +398,20 @@ class _BlockFn(torch.autograd.Function):
     def forward(ctx, x, x_lo, rt, idx, with_skip, impl, skip_param, attn_alpha, mlp_alpha, sqk, suv, wq, wk, wv, wo,
                 wfc, wp, bq, bk_, bv, bo, bfc, bp, chained=False):
         cfg = rt.model.config
-        C, H = cfg.n_embd, cfg.n_head
-        d = C // H
-        M = x.shape[0]
-        T = rt.model.n_tokens
-        B = M // T
-        dt, td = rt.dt, ops.tdtype(rt.dt)
+        dims = _dims(rt, x.shape[0])
+        B, T, C, H, d, M = dims
+        dt = rt.dt
         sh = rt.sh
         c_q, c_a = 1.0 / cfg.base_scale, 0.05 / cfg.base_scale
         pre = f"h{idx}."
         has_b = bq is not None
-        heads = cfg.flash_attn
-        if heads:
-            # flash_attn=True: attention over the heads of each token (see _heads_fwd); q/k/v stay token-major fp32
-            qpre = 1.0
-            qkv = ops.gemm_nt(x_lo, sh[pre + "qkv.W"], M, 3 * C, C, out_dtype=torch.float32, bias=sh.get(pre + "qkv.b"))
-            o, lse = _heads_fwd(rt, qkv, 3 * C, qkv[:, C:], qkv[:, 2 * C:], 3 * C, sqk, c_q, math.sqrt(d), H, d)
-            qh, kh, vh, rq, rk = qkv, None, None, None, None
-        elif not has_b and d == 64 and ops.fusable(dt, M, 3 * C, C):
-            # q/k/v projection with the per-head normalise + sqk scale + head split in the GEMM epilogue
-            # (q leaves the epilogue pre-scaled by sqrt(d)*log2(e): the attention kernels' exponent needs no multiply)
-            qpre = ops.attn_q_prescale(d) if impl == 1 else 1.0
-            qh, kh, vh, rq, rk = ops.gemm_nt_qknorm(x_lo, sh[pre + "qkv.W"], M, C, 3, 0, sqk, c_q, B, T, H, d,
-                                                    q_prescale=qpre)
-            o, lse = ops.attn_fwd(dt, impl, qh, kh, vh, math.sqrt(d), sqk, c_q, q_prescale=qpre)
-        else:
-            qpre = 1.0
-            # small problems (128x128 GEMM kernel): the projections leave the GEMM in fp32 and are normalised from the
-            # unrounded values, like the fused epilogue of the big-problem path (one rounding, at the head tensors)
-            qkv = ops.gemm_nt(x_lo, sh[pre + "qkv.W"], M, 3 * C, C, out_dtype=torch.float32, bias=sh.get(pre + "qkv.b"))
-            qh, kh, vh, rq, rk, o, lse = _attn_part_fwd(rt, impl, qkv, 3 * C, qkv[:, C:], 3 * C, qkv[:, 2 * C:],
-                                                         3 * C, sqk, c_q, B, T, H, d)
-            del qkv
+        o, lse, att, att_saved = _attn_fwd(rt, impl, ((x_lo, pre + "qkv", 3),), has_b, sqk, c_q, math.sqrt(d), dims)
         y = ops.gemm_nt(o, sh[pre + "o.W"], M, C, C, out_dtype=rt.y_dtype(), bias=sh.get(pre + "o.b"))
         h1, h1_lo = ops.lerp_fwd(dt, x, y, attn_alpha, c_a, want_lo=(dt != F32))
         if dt == F32:
             h1_lo = h1
-        gscale = math.sqrt(C)
-        if not has_b and ops.fusable(dt, M, 8 * C, C):
-            # c_fc GEMM with suv scale + SwiGLU gate in the epilogue (writes raw uv for backward and x_mlp)
-            uv, xm = ops.gemm_nt_swiglu(h1_lo, sh[pre + "fc.W"], M, 4 * C, C, sh[pre + "suv_i"], gscale)
-        else:
-            uv32 = ops.gemm_nt(h1_lo, sh[pre + "fc.W"], M, 8 * C, C, out_dtype=torch.float32, bias=sh.get(pre + "fc.b"))
-            if dt == F32:
-                uv, xm = uv32, ops.swiglu_fwd(dt, uv32, suv, gscale, M, 4 * C)
-            else:   # gate from the unrounded pre-activations; the bf16 copy is what backward reads
-                xm = ops.swiglu_fwd(BF16_F32IN, uv32, suv, gscale, M, 4 * C)
-                uv = ops.cast(uv32, dt)
-            del uv32
+        # c_fc GEMM with the suv scale + SwiGLU gate (writes raw uv for backward and x_mlp)
+        uv, xm = _swiglu_fwd(rt, h1_lo, pre + "fc", M, 4 * C, C, has_b, suv, sh[pre + "suv_i"], math.sqrt(C))
         y2 = ops.gemm_nt(xm, sh[pre + "p.W"], M, C, 4 * C, out_dtype=rt.y_dtype(), bias=sh.get(pre + "p.b"))
         if with_skip:
             xn, xn_lo = ops.lerp_fwd(dt, h1, y2, mlp_alpha, c_a, skip_x=x, skip=skip_param, want_lo=(dt != F32))
@@ -352,23 +419,21 @@ class _BlockFn(torch.autograd.Function):
             xn, xn_lo = ops.lerp_fwd(dt, h1, y2, mlp_alpha, c_a, want_lo=(dt != F32))
         if dt == F32:
             xn_lo = xn.new_empty(0)  # placeholder: callers alias x itself in fp32 mode (see _lo())
-        ctx.rt, ctx.idx, ctx.with_skip, ctx.impl, ctx.has_b = rt, idx, with_skip, impl, has_b
-        ctx.heads = heads
+        ctx.rt, ctx.idx, ctx.with_skip, ctx.has_b, ctx.attn = rt, idx, with_skip, has_b, att
         ctx.chained = bool(chained)   # called from ViT.forward's block chain: the consumer of dx is our own backward node
-        ctx.qpre = qpre
-        ctx.dims = (B, T, C, H, d, M)
+        ctx.dims = dims
         ctx.par = (skip_param, attn_alpha, mlp_alpha, sqk, suv, wq, wk, wv, wo, wfc, wp)   # gradient destinations
-        ctx.save_for_backward(x, x_lo, qh, kh, vh, rq, rk, o, lse, y, h1, h1_lo, uv, xm, y2, skip_param, attn_alpha,
-                              mlp_alpha, sqk, suv)
+        ctx.save_for_backward(x, x_lo, o, lse, y, h1, h1_lo, uv, xm, y2, skip_param, attn_alpha, mlp_alpha, sqk, suv,
+                              *att_saved)
         ctx.mark_non_differentiable(xn_lo)
         ctx.set_materialize_grads(False)  # no zero-filled [M,C] gradient for the bf16 twin on every backward
         return xn, xn_lo
 
     @staticmethod
     def backward(ctx, dxn, _unused):
-        (x, x_lo, qh, kh, vh, rq, rk, o, lse, y, h1, h1_lo, uv, xm, y2, skip_param, attn_alpha, mlp_alpha, sqk,
-         suv) = ctx.saved_tensors
-        rt, idx, impl = ctx.rt, ctx.idx, ctx.impl
+        (x, x_lo, o, lse, y, h1, h1_lo, uv, xm, y2, skip_param, attn_alpha, mlp_alpha, sqk, suv,
+         *att_saved) = ctx.saved_tensors
+        rt, idx = ctx.rt, ctx.idx
         B, T, C, H, d, M = ctx.dims
         p_skip, p_aalpha, p_malpha, p_sqk, p_suv, p_wq, p_wk, p_wv, p_wo, p_wfc, p_wp = ctx.par
         cfg = rt.model.config
@@ -393,25 +458,15 @@ class _BlockFn(torch.autograd.Function):
                                                           False, True, dout_add=carry_in)
             dx, dskip = None, None
         d_mlp_alpha = _param_grad_alpha(rt, part_lam, p_malpha, c_a, red)
-        gscale = math.sqrt(C)
-        if ops.fusable(dt, M, 4 * C, C):
-            # data gradient of mlp_c_proj with the SwiGLU backward in the GEMM epilogue (dx_mlp never reaches HBM)
-            duv, part_suv = ops.gemm_nt_swiglu_bwd(dy2_lo, sh[pre + "p.Wt"], uv, M, 4 * C, C, suv, gscale)
-        else:
-            dxm = ops.gemm_nt(dy2_lo, sh[pre + "p.Wt"], M, 4 * C, C, out_dtype=td)
-            duv, part_suv = ops.swiglu_bwd(dt, dxm, uv, suv, gscale, M, 4 * C)
-        g_wp = rt.grad_buf((p_wp,), (C, 4 * C))
-        ops.gemm_tn(dy2_lo, xm, g_wp, M, C, 4 * C)
-        g_bp = _bias_grad(dy2_lo, M, C) if ctx.has_b else None
+        duv, part_suv = _swiglu_bwd(rt, dy2_lo, pre + "p", uv, M, 4 * C, C, suv, math.sqrt(C))
+        g_wp, g_bp = _wgrad(rt, dy2_lo, xm, (p_wp,), M, C, 4 * C, ctx.has_b)
         d_suv = _param_grad_scaled(rt, part_suv, p_suv, 1.0, red)
         if lo_dgrad:
             dh1_add = ops.gemm_nt(duv, sh[pre + "fc.Wt"], M, C, 8 * C, out_dtype=td)   # bf16, added by the next lerp_bwd
         else:
             dh1_add = None
             ops.gemm_nt(duv, sh[pre + "fc.Wt"], M, C, 8 * C, out=dh1, accumulate=True)
-        g_wfc = rt.grad_buf((p_wfc,), (8 * C, C))
-        ops.gemm_tn(duv, h1_lo, g_wfc, M, 8 * C, C, perm=1)
-        g_bfc = _bias_grad(duv, M, 8 * C, perm=1) if ctx.has_b else None
+        g_wfc, g_bfc = _wgrad(rt, duv, h1_lo, (p_wfc,), M, 8 * C, C, ctx.has_b, perm=1)
         # ---- attention half
         if dx is None:
             dx, _, dy_lo, _, part_lam, _ = ops.lerp_bwd(dt, dh1, x, y, attn_alpha, c_a, None, None, None, False,
@@ -421,33 +476,18 @@ class _BlockFn(torch.autograd.Function):
                                                         True, dout_add=dh1_add)
         d_attn_alpha = _param_grad_alpha(rt, part_lam, p_aalpha, c_a, red)
         do = ops.gemm_nt(dy_lo, sh[pre + "o.Wt"], M, C, C, out_dtype=td)
-        g_wo = rt.grad_buf((p_wo,), (C, C))
-        ops.gemm_tn(dy_lo, o, g_wo, M, C, C)
-        g_bo = _bias_grad(dy_lo, M, C) if ctx.has_b else None
+        g_wo, g_bo = _wgrad(rt, dy_lo, o, (p_wo,), M, C, C, ctx.has_b)
         dqkv = torch.empty((M, 3 * C), device=x.device, dtype=td)
-        if ctx.heads:   # qh holds the fp32 [M, 3C] projection outputs
-            part_sqk = _heads_bwd(rt, do, qh, 3 * C, qh[:, C:], qh[:, 2 * C:], 3 * C, sqk, c_q, math.sqrt(d), lse, dqkv,
-                                  3 * C, dqkv[:, C:], dqkv[:, 2 * C:], 3 * C, H, d)
-            d_sqk = _param_grad_scaled(rt, part_sqk, p_sqk, c_q, red)
-        elif impl == 1 and d == 64 and dt != F32:
-            # attention backward with the q/k-normalise backward fused into its epilogues
-            part_q, part_k = ops.attn_bwd_qknorm(do, qh, kh, vh, o, lse, math.sqrt(d), rq, rk, sqk, c_q, dqkv, 3 * C,
-                                                 dqkv[:, C:], dqkv[:, 2 * C:], 3 * C, q_prescale=ctx.qpre)
-            d_sqk = _param_grad_scaled(rt, part_q, p_sqk, c_q, red, part_b=part_k)
-        else:
-            dqh, dkh, dvh = ops.attn_bwd(dt, impl, do, qh, kh, vh, o, lse, math.sqrt(d))
-            part_sqk = ops.qknorm_bwd(dt, dqh, dkh, dvh, qh, kh, rq, rk, sqk, c_q, dqkv, 3 * C, dqkv[:, C:], 3 * C,
-                                      dqkv[:, 2 * C:], 3 * C, B, T, H, d)
-            d_sqk = _param_grad_scaled(rt, part_sqk, p_sqk, c_q, red)
+        part_q, part_k = _attn_bwd(rt, ctx.attn, att_saved, do, o, lse, (dqkv,), sqk, c_q, ctx.dims)
+        d_sqk = _param_grad_scaled(rt, part_q, p_sqk, c_q, red, part_b=part_k)
         if lo_dgrad and ctx.chained:
             # the consumer of dx is the backward node of the previous block (or of the cross-attention block): hand it
             # the q/k/v data gradient as a separate bf16 addend instead of read-modify-writing dx
             rt.carry = (idx - 1, dx, ops.gemm_nt(dqkv, sh[pre + "qkv.Wt"], M, C, 3 * C, out_dtype=td))
         else:
             ops.gemm_nt(dqkv, sh[pre + "qkv.Wt"], M, C, 3 * C, out=dx, accumulate=True)
-        g_qkv = rt.grad_buf((p_wq, p_wk, p_wv), (3 * C, C))   # one stacked GEMM output = three adjacent bucket slices
-        ops.gemm_tn(dqkv, x_lo, g_qkv, M, 3 * C, C)
-        g_bqkv = _bias_grad(dqkv, M, 3 * C) if ctx.has_b else None
+        # one stacked GEMM output = three adjacent bucket slices
+        g_qkv, g_bqkv = _wgrad(rt, dqkv, x_lo, (p_wq, p_wk, p_wv), M, 3 * C, C, ctx.has_b)
         red.flush()
         gq, gk, gv = g_qkv[:C], g_qkv[C:2 * C], g_qkv[2 * C:]
         if ctx.has_b:
@@ -465,12 +505,9 @@ class _CrossFn(torch.autograd.Function):
     def forward(ctx, loc, glo, loc_lo, glo_lo, rt, impl, attn_alpha, sqk, wq, wk, wv, wproj, wout, bq, bk_, bv, bproj, bout,
                 chained=False):
         cfg = rt.model.config
-        C, H = cfg.n_embd, cfg.n_head
-        d = C // H
-        M = loc.shape[0]
-        T = rt.model.n_tokens
-        B = M // T
-        dt, td = rt.dt, ops.tdtype(rt.dt)
+        dims = _dims(rt, loc.shape[0])
+        B, T, C, H, d, M = dims
+        dt = rt.dt
         sh = rt.sh
         c_q, c_a = 1.0 / cfg.base_scale, 0.05 / cfg.base_scale
         has_b = bq is not None
@@ -479,47 +516,19 @@ class _CrossFn(torch.autograd.Function):
         else:   # bf16 operand copies: handed in by the producer (patch-embedding epilogue) or cast here
             loc_lo = ops.cast(loc, dt) if loc_lo is None else loc_lo
             glo_lo = ops.cast(glo, dt) if glo_lo is None else glo_lo
-        heads = cfg.flash_attn
-        if heads:   # flash_attn=True: q from token t of the local stream, k/v from token t of the global stream
-            qpre = 1.0
-            q = ops.gemm_nt(loc_lo, sh["x.q.W"], M, C, C, out_dtype=torch.float32, bias=sh.get("x.q.b"))
-            kv = ops.gemm_nt(glo_lo, sh["x.kv.W"], M, 2 * C, C, out_dtype=torch.float32, bias=sh.get("x.kv.b"))
-            o, lse = _heads_fwd(rt, q, C, kv, kv[:, C:], 2 * C, sqk, c_q, math.sqrt(d), H, d)
-            qh, kh, vh, rq, rk = q, kv, None, None, None
-        elif not has_b and d == 64 and ops.fusable(dt, M, C, C):
-            bufs = ops.qk_buffers(dt, B, T, H, d, loc.device)
-            qpre = ops.attn_q_prescale(d) if impl == 1 else 1.0
-            ops.gemm_nt_qknorm(loc_lo, sh["x.q.W"], M, C, 1, 0, sqk, c_q, B, T, H, d, bufs, q_prescale=qpre)
-            qh, kh, vh, rq, rk = ops.gemm_nt_qknorm(glo_lo, sh["x.kv.W"], M, C, 2, 1, sqk, c_q, B, T, H, d, bufs)
-            o, lse = ops.attn_fwd(dt, impl, qh, kh, vh, math.sqrt(d), sqk, c_q, q_prescale=qpre)
-        else:
-            qpre = 1.0
-            q = ops.gemm_nt(loc_lo, sh["x.q.W"], M, C, C, out_dtype=torch.float32, bias=sh.get("x.q.b"))
-            kv = ops.gemm_nt(glo_lo, sh["x.kv.W"], M, 2 * C, C, out_dtype=torch.float32, bias=sh.get("x.kv.b"))
-            qh, kh, vh, rq, rk, o, lse = _attn_part_fwd(rt, impl, q, C, kv, 2 * C, kv[:, C:], 2 * C, sqk, c_q, B, T,
-                                                         H, d)
-            del q, kv
-        if not has_b and ops.fusable(dt, M, 2 * C, C):
-            pr, g = ops.gemm_nt_swiglu(o, sh["x.proj.W"], M, C, C, None, 1.0)
-        else:
-            pr32 = ops.gemm_nt(o, sh["x.proj.W"], M, 2 * C, C, out_dtype=torch.float32, bias=sh.get("x.proj.b"))
-            if dt == F32:
-                pr, g = pr32, ops.swiglu_fwd(dt, pr32, None, 1.0, M, C)
-            else:
-                g = ops.swiglu_fwd(BF16_F32IN, pr32, None, 1.0, M, C)
-                pr = ops.cast(pr32, dt)
-            del pr32
+        # q from the local stream, k/v from the global stream
+        o, lse, att, att_saved = _attn_fwd(rt, impl, ((loc_lo, "x.q", 1), (glo_lo, "x.kv", 2)), has_b, sqk, c_q,
+                                           math.sqrt(d), dims)
+        pr, g = _swiglu_fwd(rt, o, "x.proj", M, C, C, has_b, None, None, 1.0)
         y = ops.gemm_nt(g, sh["x.out.W"], M, C, C, out_dtype=rt.y_dtype(), bias=sh.get("x.out.b"))
         x, x_lo = ops.lerp_fwd(dt, loc, y, attn_alpha, c_a, want_lo=(dt != F32))
         if dt == F32:
             x_lo = x.new_empty(0)
-        ctx.rt, ctx.impl, ctx.has_b = rt, impl, has_b
-        ctx.heads = heads
+        ctx.rt, ctx.has_b, ctx.attn = rt, has_b, att
         ctx.chained = bool(chained)
-        ctx.qpre = qpre
-        ctx.dims = (B, T, C, H, d, M)
+        ctx.dims = dims
         ctx.par = (attn_alpha, sqk, wq, wk, wv, wproj, wout)
-        ctx.save_for_backward(loc, glo, loc_lo, glo_lo, qh, kh, vh, rq, rk, o, lse, pr, g, y, attn_alpha, sqk)
+        ctx.save_for_backward(loc, glo, loc_lo, glo_lo, o, lse, pr, g, y, attn_alpha, sqk, *att_saved)
         ctx.mark_non_differentiable(x_lo)
         ctx.set_materialize_grads(False)
         return x, x_lo
@@ -528,8 +537,8 @@ class _CrossFn(torch.autograd.Function):
     def backward(ctx, dx, _unused):
         if dx is None:
             return (None,) * 19
-        loc, glo, loc_lo, glo_lo, qh, kh, vh, rq, rk, o, lse, pr, g, y, attn_alpha, sqk = ctx.saved_tensors
-        rt, impl = ctx.rt, ctx.impl
+        loc, glo, loc_lo, glo_lo, o, lse, pr, g, y, attn_alpha, sqk, *att_saved = ctx.saved_tensors
+        rt = ctx.rt
         B, T, C, H, d, M = ctx.dims
         p_alpha, p_sqk, p_wq, p_wk, p_wv, p_wproj, p_wout = ctx.par
         cfg = rt.model.config
@@ -543,72 +552,22 @@ class _CrossFn(torch.autograd.Function):
         dloc, _, dy_lo, _, part_lam, _ = ops.lerp_bwd(dt, dx, loc, y, attn_alpha, c_a, None, None, None,
                                                       False, False, True, dout_add=carry_in)
         d_alpha = _param_grad_alpha(rt, part_lam, p_alpha, c_a, red)
-        if ops.fusable(dt, M, C, C):
-            dpr, _ = ops.gemm_nt_swiglu_bwd(dy_lo, sh["x.out.Wt"], pr, M, C, C, None, 1.0)
-        else:
-            dg = ops.gemm_nt(dy_lo, sh["x.out.Wt"], M, C, C, out_dtype=td)
-            dpr, _ = ops.swiglu_bwd(dt, dg, pr, None, 1.0, M, C)
-        g_wout = ops.gemm_tn(dy_lo, g, rt.grad_buf((p_wout,), (C, C)), M, C, C)
-        g_bout = _bias_grad(dy_lo, M, C) if ctx.has_b else None
+        dpr, _ = _swiglu_bwd(rt, dy_lo, "x.out", pr, M, C, C, None, 1.0)
+        g_wout, g_bout = _wgrad(rt, dy_lo, g, (p_wout,), M, C, C, ctx.has_b)
         do = ops.gemm_nt(dpr, sh["x.proj.Wt"], M, C, 2 * C, out_dtype=td)
-        g_wproj = ops.gemm_tn(dpr, o, rt.grad_buf((p_wproj,), (2 * C, C)), M, 2 * C, C, perm=1)
-        g_bproj = _bias_grad(dpr, M, 2 * C, perm=1) if ctx.has_b else None
+        g_wproj, g_bproj = _wgrad(rt, dpr, o, (p_wproj,), M, 2 * C, C, ctx.has_b, perm=1)
         dq = torch.empty((M, C), device=dev, dtype=td)
         dkv = torch.empty((M, 2 * C), device=dev, dtype=td)
-        if ctx.heads:   # qh, kh hold the fp32 q [M, C] and kv [M, 2C] projection outputs
-            part_sqk = _heads_bwd(rt, do, qh, C, kh, kh[:, C:], 2 * C, sqk, c_q, math.sqrt(d), lse, dq, C, dkv, dkv[:, C:],
-                                  2 * C, H, d)
-            d_sqk = _param_grad_scaled(rt, part_sqk, p_sqk, c_q, red)
-        elif impl == 1 and d == 64 and dt != F32:
-            part_q, part_k = ops.attn_bwd_qknorm(do, qh, kh, vh, o, lse, math.sqrt(d), rq, rk, sqk, c_q, dq, C, dkv,
-                                                 dkv[:, C:], 2 * C, q_prescale=ctx.qpre)
-            d_sqk = _param_grad_scaled(rt, part_q, p_sqk, c_q, red, part_b=part_k)
-        else:
-            dqh, dkh, dvh = ops.attn_bwd(dt, impl, do, qh, kh, vh, o, lse, math.sqrt(d))
-            part_sqk = ops.qknorm_bwd(dt, dqh, dkh, dvh, qh, kh, rq, rk, sqk, c_q, dq, C, dkv, 2 * C, dkv[:, C:],
-                                      2 * C, B, T, H, d)
-            d_sqk = _param_grad_scaled(rt, part_sqk, p_sqk, c_q, red)
+        part_q, part_k = _attn_bwd(rt, ctx.attn, att_saved, do, o, lse, (dq, dkv), sqk, c_q, ctx.dims)
+        d_sqk = _param_grad_scaled(rt, part_q, p_sqk, c_q, red, part_b=part_k)
         ops.gemm_nt(dq, sh["x.q.Wt"], M, C, C, out=dloc, accumulate=True)
         dglo = ops.gemm_nt(dkv, sh["x.kv.Wt"], M, C, 2 * C, out_dtype=torch.float32)
-        g_wq = ops.gemm_tn(dq, loc_lo, rt.grad_buf((p_wq,), (C, C)), M, C, C)
-        g_wkv = ops.gemm_tn(dkv, glo_lo, rt.grad_buf((p_wk, p_wv), (2 * C, C)), M, 2 * C, C)
+        g_wq, g_bq = _wgrad(rt, dq, loc_lo, (p_wq,), M, C, C, ctx.has_b)
+        g_wkv, g_bkv = _wgrad(rt, dkv, glo_lo, (p_wk, p_wv), M, 2 * C, C, ctx.has_b)
         red.flush()
-        if ctx.has_b:
-            g_bq = _bias_grad(dq, M, C)
-            g_bkv = _bias_grad(dkv, M, 2 * C)
-            gbk, gbv = g_bkv[:C], g_bkv[C:]
-        else:
-            g_bq = gbk = gbv = None
+        gbk, gbv = (g_bkv[:C], g_bkv[C:]) if ctx.has_b else (None, None)
         return (dloc, dglo, None, None, None, None, d_alpha, d_sqk, g_wq, g_wkv[:C], g_wkv[C:], g_wproj, g_wout, g_bq, gbk, gbv,
                 g_bproj, g_bout, None)
-
-
-RMS_EPS = 1e-6   # reference RMSNorm default (model.py:171)
-
-
-def _split_heads(rt: _Runtime, q_src, ldq, k_src, ldk, v_src, ldv, B, T, H, d):
-    """Plain-ViT head split: [M, C] projection outputs (fp32) -> [B,H,T,d] head tensors of the mode's operand type."""
-    dt_in = rt.dt if rt.dt == F32 else BF16_F32IN
-    qh, kh, vh, _, _ = ops.qknorm_fwd(dt_in, q_src, ldq, k_src, ldk, v_src, ldv, None, 0.0, B, T, H, d)
-    return qh, kh, vh
-
-
-def _std_q_prescale(d: int) -> float:
-    """q pre-scale of the fused plain-ViT route: softmax scale 1/sqrt(d) times log2(e), so that the MFMA attention
-    kernels take the score in log2 units without a multiply (and the dK/dV backward takes its generated loop)."""
-    return ops.LOG2E / math.sqrt(d)
-
-
-def _merge_heads(rt: _Runtime, do, qh, kh, vh, o, lse, impl, d, qpre, fused, dq, ldq, dk, dv, ldkv, B, T, H) -> None:
-    """Attention backward with plain (unnormalised) heads into token-major dq / dk / dv (dk, dv: row stride ldkv).
-    fused (bf16, d = 64, the heads came from the split-only q/k/v epilogue): the MFMA backward stores them itself;
-    otherwise head-major gradients and the merge kernel."""
-    if fused:
-        ops.attn_bwd_qknorm(do, qh, kh, vh, o, lse, 1.0 / math.sqrt(d), None, None, None, 0.0, dq, ldq, dk, dv, ldkv,
-                            q_prescale=qpre)
-        return
-    dqh, dkh, dvh = ops.attn_bwd(rt.dt, impl, do, qh, kh, vh, o, lse, 1.0 / math.sqrt(d))
-    ops.qknorm_bwd(rt.dt, dqh, dkh, dvh, None, None, None, None, None, 0.0, dq, ldq, dk, ldkv, dv, ldkv, B, T, H, d)
 
 
 class _StdBlockFn(torch.autograd.Function):
@@ -621,12 +580,8 @@ class _StdBlockFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, rt, idx, with_skip, want_lo, impl, skip_param, w_att, w_mlp, wq, wk, wv, wo, wfc, wp, bq, bk_,
                 bv, bo, bfc, bp):
-        cfg = rt.model.config
-        C, H = cfg.n_embd, cfg.n_head
-        d = C // H
-        M = x.shape[0]
-        T = rt.model.n_tokens
-        B = M // T
+        dims = _dims(rt, x.shape[0])
+        B, T, C, H, d, M = dims
         dt = rt.dt
         lo = dt != F32
         sh = rt.sh
@@ -635,39 +590,13 @@ class _StdBlockFn(torch.autograd.Function):
         a, a_lo, r_att = ops.res_rmsnorm_fwd(dt, x, None, w_att.detach(), RMS_EPS, want_lo=lo)
         if not lo:
             a_lo = a
-        heads = cfg.flash_attn
-        fused = not heads and not has_b and impl == 1 and d == 64 and ops.fusable(dt, M, 3 * C, C)
-        if heads:   # flash_attn=True: attention over the heads of each token, scale 1/sqrt(d)
-            qpre = 1.0
-            qkv = ops.gemm_nt(a_lo, sh[pre + "qkv.W"], M, 3 * C, C, out_dtype=torch.float32, bias=sh.get(pre + "qkv.b"))
-            o, lse = _heads_fwd(rt, qkv, 3 * C, qkv[:, C:], qkv[:, 2 * C:], 3 * C, None, 0.0, 1.0 / math.sqrt(d), H, d)
-            qh, kh, vh = qkv, None, None
-        elif fused:
-            # q/k/v projection with the head split in the GEMM epilogue (split-only EPI 4); q leaves pre-scaled
-            qpre = _std_q_prescale(d)
-            qh, kh, vh, _, _ = ops.gemm_nt_qknorm(a_lo, sh[pre + "qkv.W"], M, C, 3, 0, None, 0.0, B, T, H, d,
-                                                  q_prescale=qpre)
-        else:
-            qpre = 1.0
-            qkv = ops.gemm_nt(a_lo, sh[pre + "qkv.W"], M, 3 * C, C, out_dtype=torch.float32, bias=sh.get(pre + "qkv.b"))
-            qh, kh, vh = _split_heads(rt, qkv, 3 * C, qkv[:, C:], 3 * C, qkv[:, 2 * C:], 3 * C, B, T, H, d)
-            del qkv
-        if not heads:
-            o, lse = ops.attn_fwd(dt, impl, qh, kh, vh, 1.0 / math.sqrt(d), q_prescale=qpre)
+        o, lse, att, att_saved = _attn_fwd(rt, impl, ((a_lo, pre + "qkv", 3),), has_b, None, 0.0, 1.0 / math.sqrt(d),
+                                           dims)
         y = ops.gemm_nt(o, sh[pre + "o.W"], M, C, C, out_dtype=rt.y_dtype(), bias=sh.get(pre + "o.b"))
         bm, bm_lo, r_mlp = ops.res_rmsnorm_fwd(dt, a, y, w_mlp.detach(), RMS_EPS, want_lo=lo)
         if not lo:
             bm_lo = bm
-        if not has_b and ops.fusable(dt, M, 8 * C, C):
-            uv, xm = ops.gemm_nt_swiglu(bm_lo, sh[pre + "fc.W"], M, 4 * C, C, None, 1.0)
-        else:
-            uv32 = ops.gemm_nt(bm_lo, sh[pre + "fc.W"], M, 8 * C, C, out_dtype=torch.float32, bias=sh.get(pre + "fc.b"))
-            if dt == F32:
-                uv, xm = uv32, ops.swiglu_fwd(dt, uv32, None, 1.0, M, 4 * C)
-            else:   # gate from the unrounded pre-activations; the bf16 copy is what backward reads
-                xm = ops.swiglu_fwd(BF16_F32IN, uv32, None, 1.0, M, 4 * C)
-                uv = ops.cast(uv32, dt)
-            del uv32
+        uv, xm = _swiglu_fwd(rt, bm_lo, pre + "fc", M, 4 * C, C, has_b, None, None, 1.0)
         if with_skip:
             y2 = ops.gemm_nt(xm, sh[pre + "p.W"], M, C, 4 * C, out_dtype=rt.y_dtype(), bias=sh.get(pre + "p.b"))
             xn, xn_lo = ops.res_skip_fwd(dt, bm, y2, skip_param.detach(), x, want_lo=(lo and want_lo))
@@ -677,12 +606,11 @@ class _StdBlockFn(torch.autograd.Function):
             xn, xn_lo = y2, (ops.cast(y2, dt) if lo and want_lo else None)
         if xn_lo is None:
             xn_lo = xn.new_empty(0)   # fp32 mode: callers alias the stream itself (see _lo())
-        ctx.rt, ctx.idx, ctx.with_skip, ctx.impl, ctx.has_b = rt, idx, with_skip, impl, has_b
-        ctx.fused, ctx.qpre, ctx.heads = fused, qpre, heads
-        ctx.dims = (B, T, C, H, d, M)
+        ctx.rt, ctx.idx, ctx.with_skip, ctx.has_b, ctx.attn = rt, idx, with_skip, has_b, att
+        ctx.dims = dims
         ctx.par = (skip_param, w_att, w_mlp, wq, wk, wv, wo, wfc, wp)   # gradient destinations
-        ctx.save_for_backward(x, a, a_lo, r_att, qh, kh, vh, o, lse, y, bm, bm_lo, r_mlp, uv, xm, y2, skip_param,
-                              w_att, w_mlp)
+        ctx.save_for_backward(x, a, a_lo, r_att, o, lse, y, bm, bm_lo, r_mlp, uv, xm, y2, skip_param, w_att, w_mlp,
+                              *att_saved)
         ctx.mark_non_differentiable(xn_lo)
         ctx.set_materialize_grads(False)
         return xn, xn_lo
@@ -691,9 +619,9 @@ class _StdBlockFn(torch.autograd.Function):
     def backward(ctx, dxn, _unused):
         if dxn is None:
             return (None,) * 21
-        (x, a, a_lo, r_att, qh, kh, vh, o, lse, y, bm, bm_lo, r_mlp, uv, xm, y2, skip_param, w_att,
-         w_mlp) = ctx.saved_tensors
-        rt, idx, impl = ctx.rt, ctx.idx, ctx.impl
+        (x, a, a_lo, r_att, o, lse, y, bm, bm_lo, r_mlp, uv, xm, y2, skip_param, w_att, w_mlp,
+         *att_saved) = ctx.saved_tensors
+        rt, idx = ctx.rt, ctx.idx
         B, T, C, H, d, M = ctx.dims
         p_skip, p_watt, p_wmlp, p_wq, p_wk, p_wv, p_wo, p_wfc, p_wp = ctx.par
         dt, td = rt.dt, ops.tdtype(rt.dt)
@@ -711,16 +639,10 @@ class _StdBlockFn(torch.autograd.Function):
             dh2, dh2_lo, dx, dskip = dxn, (ops.cast(dxn, dt) if lo else None), None, None
         dy2_lo = dh2_lo if lo else dh2
         # ---- MLP branch
-        if ops.fusable(dt, M, 4 * C, C):
-            duv, _ = ops.gemm_nt_swiglu_bwd(dy2_lo, sh[pre + "p.Wt"], uv, M, 4 * C, C, None, 1.0)
-        else:
-            dxm = ops.gemm_nt(dy2_lo, sh[pre + "p.Wt"], M, 4 * C, C, out_dtype=td)
-            duv, _ = ops.swiglu_bwd(dt, dxm, uv, None, 1.0, M, 4 * C)
-        g_wp = ops.gemm_tn(dy2_lo, xm, rt.grad_buf((p_wp,), (C, 4 * C)), M, C, 4 * C)
-        g_bp = _bias_grad(dy2_lo, M, C) if ctx.has_b else None
+        duv, _ = _swiglu_bwd(rt, dy2_lo, pre + "p", uv, M, 4 * C, C, None, 1.0)
+        g_wp, g_bp = _wgrad(rt, dy2_lo, xm, (p_wp,), M, C, 4 * C, ctx.has_b)
         dbm_add = ops.gemm_nt(duv, sh[pre + "fc.Wt"], M, C, 8 * C, out_dtype=td)   # added by the rms_mlp backward
-        g_wfc = ops.gemm_tn(duv, bm_lo, rt.grad_buf((p_wfc,), (8 * C, C)), M, 8 * C, C, perm=1)
-        g_bfc = _bias_grad(duv, M, 8 * C, perm=1) if ctx.has_b else None
+        g_wfc, g_bfc = _wgrad(rt, duv, bm_lo, (p_wfc,), M, 8 * C, C, ctx.has_b, perm=1)
         # ---- rms_mlp: d(h1) = d(a + y)
         dh1, dh1_lo, part_mlp = ops.res_rmsnorm_bwd(dt, dh2, a, y, w_mlp, r_mlp, g_add=dbm_add, want_lo=lo)
         del dbm_add
@@ -728,19 +650,11 @@ class _StdBlockFn(torch.autograd.Function):
         dy_lo = dh1_lo if lo else dh1
         # ---- attention branch
         do = ops.gemm_nt(dy_lo, sh[pre + "o.Wt"], M, C, C, out_dtype=td)
-        g_wo = ops.gemm_tn(dy_lo, o, rt.grad_buf((p_wo,), (C, C)), M, C, C)
-        g_bo = _bias_grad(dy_lo, M, C) if ctx.has_b else None
+        g_wo, g_bo = _wgrad(rt, dy_lo, o, (p_wo,), M, C, C, ctx.has_b)
         dqkv = torch.empty((M, 3 * C), device=x.device, dtype=td)
-        if ctx.heads:   # qh holds the fp32 [M, 3C] projection outputs
-            _heads_bwd(rt, do, qh, 3 * C, qh[:, C:], qh[:, 2 * C:], 3 * C, None, 0.0, 1.0 / math.sqrt(d), lse, dqkv, 3 * C,
-                       dqkv[:, C:], dqkv[:, 2 * C:], 3 * C, H, d)
-        else:
-            _merge_heads(rt, do, qh, kh, vh, o, lse, impl, d, ctx.qpre, ctx.fused, dqkv, 3 * C, dqkv[:, C:],
-                         dqkv[:, 2 * C:], 3 * C, B, T, H)
+        _attn_bwd(rt, ctx.attn, att_saved, do, o, lse, (dqkv,), None, 0.0, ctx.dims)
         da_add = ops.gemm_nt(dqkv, sh[pre + "qkv.Wt"], M, C, 3 * C, out_dtype=td)
-        g_qkv = rt.grad_buf((p_wq, p_wk, p_wv), (3 * C, C))
-        ops.gemm_tn(dqkv, a_lo, g_qkv, M, 3 * C, C)
-        g_bqkv = _bias_grad(dqkv, M, 3 * C) if ctx.has_b else None
+        g_qkv, g_bqkv = _wgrad(rt, dqkv, a_lo, (p_wq, p_wk, p_wv), M, 3 * C, C, ctx.has_b)
         # ---- rms_att: d(x) += rms backward of d(a) = d(h1) + q/k/v data gradient
         dx, _, part_att = ops.res_rmsnorm_bwd(dt, dh1, x, None, w_att, r_att, g_add=da_add, dz=dx)
         g_watt = _param_grad_scaled(rt, part_att, p_watt, 1.0, red)
@@ -760,12 +674,8 @@ class _StdCrossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, loc, glo, rt, impl, w_ln, w_gn, wq, wk, wv, wproj, wout, bq, bk_, bv, bproj, bout):
-        cfg = rt.model.config
-        C, H = cfg.n_embd, cfg.n_head
-        d = C // H
-        M = loc.shape[0]
-        T = rt.model.n_tokens
-        B = M // T
+        dims = _dims(rt, loc.shape[0])
+        B, T, C, H, d, M = dims
         dt = rt.dt
         lo = dt != F32
         sh = rt.sh
@@ -774,43 +684,14 @@ class _StdCrossFn(torch.autograd.Function):
         gn, gn_lo, r_g = ops.res_rmsnorm_fwd(dt, glo, None, w_gn.detach(), RMS_EPS, want_lo=lo)
         if not lo:
             ln_lo, gn_lo = ln, gn
-        heads = cfg.flash_attn
-        fused = not heads and not has_b and impl == 1 and d == 64 and ops.fusable(dt, M, C, C)
-        if heads:   # flash_attn=True: attention over the heads of each token, scale 1/sqrt(d)
-            qpre = 1.0
-            q = ops.gemm_nt(ln_lo, sh["x.q.W"], M, C, C, out_dtype=torch.float32, bias=sh.get("x.q.b"))
-            kv = ops.gemm_nt(gn_lo, sh["x.kv.W"], M, 2 * C, C, out_dtype=torch.float32, bias=sh.get("x.kv.b"))
-            o, lse = _heads_fwd(rt, q, C, kv, kv[:, C:], 2 * C, None, 0.0, 1.0 / math.sqrt(d), H, d)
-            qh, kh, vh = q, kv, None
-        elif fused:   # split-only EPI 4 (q from the local side, k/v from the global side), q pre-scaled
-            qpre = _std_q_prescale(d)
-            bufs = ops.qk_buffers(dt, B, T, H, d, loc.device, norm=False)
-            ops.gemm_nt_qknorm(ln_lo, sh["x.q.W"], M, C, 1, 0, None, 0.0, B, T, H, d, bufs, q_prescale=qpre)
-            qh, kh, vh, _, _ = ops.gemm_nt_qknorm(gn_lo, sh["x.kv.W"], M, C, 2, 1, None, 0.0, B, T, H, d, bufs)
-        else:
-            qpre = 1.0
-            q = ops.gemm_nt(ln_lo, sh["x.q.W"], M, C, C, out_dtype=torch.float32, bias=sh.get("x.q.b"))
-            kv = ops.gemm_nt(gn_lo, sh["x.kv.W"], M, 2 * C, C, out_dtype=torch.float32, bias=sh.get("x.kv.b"))
-            qh, kh, vh = _split_heads(rt, q, C, kv, 2 * C, kv[:, C:], 2 * C, B, T, H, d)
-            del q, kv
-        if not heads:
-            o, lse = ops.attn_fwd(dt, impl, qh, kh, vh, 1.0 / math.sqrt(d), q_prescale=qpre)
-        if not has_b and ops.fusable(dt, M, 2 * C, C):
-            pr, g = ops.gemm_nt_swiglu(o, sh["x.proj.W"], M, C, C, None, 1.0)
-        else:
-            pr32 = ops.gemm_nt(o, sh["x.proj.W"], M, 2 * C, C, out_dtype=torch.float32, bias=sh.get("x.proj.b"))
-            if dt == F32:
-                pr, g = pr32, ops.swiglu_fwd(dt, pr32, None, 1.0, M, C)
-            else:
-                g = ops.swiglu_fwd(BF16_F32IN, pr32, None, 1.0, M, C)
-                pr = ops.cast(pr32, dt)
-            del pr32
+        o, lse, att, att_saved = _attn_fwd(rt, impl, ((ln_lo, "x.q", 1), (gn_lo, "x.kv", 2)), has_b, None, 0.0,
+                                           1.0 / math.sqrt(d), dims)
+        pr, g = _swiglu_fwd(rt, o, "x.proj", M, C, C, has_b, None, None, 1.0)
         out = ops.gemm_nt(g, sh["x.out.W"], M, C, C, out_dtype=torch.float32, bias=sh.get("x.out.b"))
-        ctx.rt, ctx.impl, ctx.has_b = rt, impl, has_b
-        ctx.fused, ctx.qpre, ctx.heads = fused, qpre, heads
-        ctx.dims = (B, T, C, H, d, M)
+        ctx.rt, ctx.has_b, ctx.attn = rt, has_b, att
+        ctx.dims = dims
         ctx.par = (w_ln, w_gn, wq, wk, wv, wproj, wout)
-        ctx.save_for_backward(loc, glo, ln_lo, gn_lo, r_l, r_g, qh, kh, vh, o, lse, pr, g, w_ln, w_gn)
+        ctx.save_for_backward(loc, glo, ln_lo, gn_lo, r_l, r_g, o, lse, pr, g, w_ln, w_gn, *att_saved)
         ctx.set_materialize_grads(False)
         return out
 
@@ -818,8 +699,8 @@ class _StdCrossFn(torch.autograd.Function):
     def backward(ctx, dout):
         if dout is None:
             return (None,) * 16
-        loc, glo, ln_lo, gn_lo, r_l, r_g, qh, kh, vh, o, lse, pr, g, w_ln, w_gn = ctx.saved_tensors
-        rt, impl = ctx.rt, ctx.impl
+        loc, glo, ln_lo, gn_lo, r_l, r_g, o, lse, pr, g, w_ln, w_gn, *att_saved = ctx.saved_tensors
+        rt = ctx.rt
         B, T, C, H, d, M = ctx.dims
         p_wln, p_wgn, p_wq, p_wk, p_wv, p_wproj, p_wout = ctx.par
         dt, td = rt.dt, ops.tdtype(rt.dt)
@@ -828,38 +709,23 @@ class _StdCrossFn(torch.autograd.Function):
         dout = dout.contiguous()
         red = ops.ReduceBatch()
         dy_lo = ops.cast(dout, dt) if dt != F32 else dout
-        if ops.fusable(dt, M, C, C):
-            dpr, _ = ops.gemm_nt_swiglu_bwd(dy_lo, sh["x.out.Wt"], pr, M, C, C, None, 1.0)
-        else:
-            dg = ops.gemm_nt(dy_lo, sh["x.out.Wt"], M, C, C, out_dtype=td)
-            dpr, _ = ops.swiglu_bwd(dt, dg, pr, None, 1.0, M, C)
-        g_wout = ops.gemm_tn(dy_lo, g, rt.grad_buf((p_wout,), (C, C)), M, C, C)
-        g_bout = _bias_grad(dy_lo, M, C) if ctx.has_b else None
+        dpr, _ = _swiglu_bwd(rt, dy_lo, "x.out", pr, M, C, C, None, 1.0)
+        g_wout, g_bout = _wgrad(rt, dy_lo, g, (p_wout,), M, C, C, ctx.has_b)
         do = ops.gemm_nt(dpr, sh["x.proj.Wt"], M, C, 2 * C, out_dtype=td)
-        g_wproj = ops.gemm_tn(dpr, o, rt.grad_buf((p_wproj,), (2 * C, C)), M, 2 * C, C, perm=1)
-        g_bproj = _bias_grad(dpr, M, 2 * C, perm=1) if ctx.has_b else None
+        g_wproj, g_bproj = _wgrad(rt, dpr, o, (p_wproj,), M, 2 * C, C, ctx.has_b, perm=1)
         dq = torch.empty((M, C), device=dev, dtype=td)
         dkv = torch.empty((M, 2 * C), device=dev, dtype=td)
-        if ctx.heads:   # qh, kh hold the fp32 q [M, C] and kv [M, 2C] projection outputs
-            _heads_bwd(rt, do, qh, C, kh, kh[:, C:], 2 * C, None, 0.0, 1.0 / math.sqrt(d), lse, dq, C, dkv, dkv[:, C:],
-                       2 * C, H, d)
-        else:
-            _merge_heads(rt, do, qh, kh, vh, o, lse, impl, d, ctx.qpre, ctx.fused, dq, C, dkv, dkv[:, C:], 2 * C, B, T, H)
+        _attn_bwd(rt, ctx.attn, att_saved, do, o, lse, (dq, dkv), None, 0.0, ctx.dims)
         dln = ops.gemm_nt(dq, sh["x.q.Wt"], M, C, C, out_dtype=torch.float32)
         dgn = ops.gemm_nt(dkv, sh["x.kv.Wt"], M, C, 2 * C, out_dtype=torch.float32)
-        g_wq = ops.gemm_tn(dq, ln_lo, rt.grad_buf((p_wq,), (C, C)), M, C, C)
-        g_wkv = ops.gemm_tn(dkv, gn_lo, rt.grad_buf((p_wk, p_wv), (2 * C, C)), M, 2 * C, C)
+        g_wq, g_bq = _wgrad(rt, dq, ln_lo, (p_wq,), M, C, C, ctx.has_b)
+        g_wkv, g_bkv = _wgrad(rt, dkv, gn_lo, (p_wk, p_wv), M, 2 * C, C, ctx.has_b)
         dloc, _, part_l = ops.res_rmsnorm_bwd(dt, dln, loc, None, w_ln, r_l)
         dglo, _, part_g = ops.res_rmsnorm_bwd(dt, dgn, glo, None, w_gn, r_g)
         g_wln = _param_grad_scaled(rt, part_l, p_wln, 1.0, red)
         g_wgn = _param_grad_scaled(rt, part_g, p_wgn, 1.0, red)
         red.flush()
-        if ctx.has_b:
-            g_bq = _bias_grad(dq, M, C)
-            g_bkv = _bias_grad(dkv, M, 2 * C)
-            gbk, gbv = g_bkv[:C], g_bkv[C:]
-        else:
-            g_bq = gbk = gbv = None
+        gbk, gbv = (g_bkv[:C], g_bkv[C:]) if ctx.has_b else (None, None)
         return (dloc, dglo, None, None, g_wln, g_wgn, g_wq, g_wkv[:C], g_wkv[C:], g_wproj, g_wout, g_bq, gbk, gbv,
                 g_bproj, g_bout)
 
