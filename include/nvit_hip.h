@@ -66,10 +66,16 @@ const char* nvit_prof_name(int kid);
  * dim=1: every row scaled to unit L2 norm (query/key/value/c_fc); dim=0: every column
  * (att_c_proj/mlp_c_proj).  fp32 in place, one read + one write per element.
  * first_item = prefix sum of work items (rows/NVIT_RENORM_ROWS_PER_ITEM for dim=1,
- * cols/NVIT_RENORM_COLS_PER_ITEM for dim=0, rounded up); total_items = sum.
- * dim=0 keeps a [rows x NVIT_RENORM_COLS_PER_ITEM] panel in the registers of a 1024-thread workgroup (rows <= 1152). */
+ * cols/NVIT_RENORM_COLS_PER_ITEM for dim=0, rounded up; cols/NVIT_RENORM_TALL_COLS_PER_ITEM for a dim=0 matrix of
+ * more than NVIT_RENORM_TALL_ROWS rows); total_items = sum.
+ * dim=0 keeps a [rows x NVIT_RENORM_COLS_PER_ITEM] panel in the registers of a 1024-thread workgroup (rows <= 1152),
+ * a [rows x NVIT_RENORM_TALL_COLS_PER_ITEM] panel for 1152 < rows <= NVIT_RENORM_MAX_ROWS_DIM0.  dim=1 takes any
+ * number of columns (rows of up to 2048 columns, a multiple of 4, stay in registers). */
 #define NVIT_RENORM_ROWS_PER_ITEM 64
 #define NVIT_RENORM_COLS_PER_ITEM 64
+#define NVIT_RENORM_TALL_ROWS 1152          /* dim=0 matrices with more rows take the narrow panel */
+#define NVIT_RENORM_TALL_COLS_PER_ITEM 32
+#define NVIT_RENORM_MAX_ROWS_DIM0 2048
 int nvit_renorm_weights(const int64_t* table, int n, int total_items, void* stream);
 
 /* nvit_shadow_weights: builds the private MFMA-operand copies of the fp32 master weights
@@ -95,13 +101,15 @@ int nvit_shadow_weights(const int64_t* table, int n, int total_items, int dt, vo
  * Trainer.normalize_matrices (train.py:935-946, 461-480, 989-990; parameter groups of model.py:369-385).
  * table: n rows of 10 int64 {p, g, m, v (fp32 device pointers), rows, cols, kind, first_item, first_chunk,
  *        f32bits(lr) | f32bits(weight_decay) << 32};  kind -1 = plain (items of 8192 elements), 1 = normalise rows
- *        (items of 16 rows; cols % 4 == 0, cols <= 1536), 0 = normalise columns (items of 32 columns, rows <= 1152);
+ *        (items of 16 rows; cols % 4 == 0, cols <= 2048), 0 = normalise columns (rows <= 2048; items of 32 columns,
+ *        of 16 columns for a matrix of more than 1152 rows);
  *        first_chunk counts 8192-element chunks of the gradient for nvit_grad_sqnorm.
  * nvit_grad_sqnorm: partial[npart] = per-workgroup sums of g*g over all gradients (npart <= 4096 workgroups).
  * nvit_adamw_renorm: clip = min(1, max_norm / (sqrt(sum partial) + 1e-6)) when partial != NULL and max_norm > 0;
  *        g *= clip; torch AdamW update (decoupled decay, bias corrections 1 - beta^t passed by the host); rows /
  *        columns of kind 1 / 0 matrices are L2-normalised before the single write-back.  gnorm_out[0] (optional)
- *        receives the pre-clip global gradient norm.  max_slab_rows = largest `rows` among kind-0 entries.
+ *        receives the pre-clip global gradient norm.  max_slab_rows sizes the LDS: the largest `rows` among kind-0
+ *        entries, and at least 1024 when a kind-1 entry has more than 1536 columns (such rows are parked in LDS).
  *        hyper (optional, 3 floats on the device): when given, the bias corrections are read from hyper[1..2] as
  *        maintained by nvit_adamw_tick (hyper[0] = step count; one call per optimizer step, before this one), so the
  *        whole step can be captured in a hipGraph and replayed; the two double arguments are then ignored. */

@@ -17,6 +17,10 @@ KID_NAMES = ["gemm_nt", "gemm_tn", "attn_fwd", "attn_bwd", "rowops", "renorm", "
              "gemm_swiglu", "gemm_qknorm", "gemm_swiglu_bwd", "optim"]
 RENORM_ROWS_PER_ITEM = 64
 RENORM_COLS_PER_ITEM = 64
+RENORM_TALL_ROWS = 1152           # column-normalised matrices with more rows take the narrow panel / slab
+RENORM_TALL_COLS_PER_ITEM = 32
+RENORM_MAX_ROWS_DIM0 = 2048
+MAX_EMBD = 2048                   # widest row the row kernels hold (lerp, norm_skip, rmsnorm, res_*, qknorm, pool_ln, ...)
 ATTN_HEADS_MAX_H = 32   # include/nvit_hip.h NVIT_ATTN_HEADS_MAX_H
 
 _vp, _i, _f, _i64 = C.c_void_p, C.c_int, C.c_float, C.c_int64

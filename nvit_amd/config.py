@@ -66,6 +66,16 @@ def named_config(name: str, **over) -> ViTConfig:
         # C5: nViT-Base + Kohonen head (512 nodes = 2 maps of 16x16)
         "base_k": dict(image_size=224, n_embd=768, n_layer=12, n_head=12, num_classes=1000, use_kohonen=True,
                        kohonen_nodes=512),
+        # widths over 1152: the tall column slab / panel of the optimizer and renorm kernels.  "wide" is the first width
+        # over the column cap on the fully fused route (head dim 64); "wide2k" is the upper limit n_embd = 2048, over the
+        # row cap too, at head dim 128; "wide_k" adds the Kohonen head
+        "wide": dict(image_size=32, n_embd=1280, n_head=20, n_layer=2, num_classes=16),
+        "wide2k": dict(image_size=32, n_embd=2048, n_head=16, n_layer=1, num_classes=16),
+        "wide_k": dict(image_size=32, n_embd=1280, n_head=20, n_layer=2, num_classes=16, use_kohonen=True,
+                       kohonen_nodes=32, kohonen_alpha=0.05),
+        # nViT-Huge-sized: ViT-H's 16 heads at n_embd = 1280 give head dim 80, which the attention kernels do not have;
+        # 20 heads of 64 is the nearest shape on the fused path
+        "huge": dict(image_size=224, n_embd=1280, n_layer=32, n_head=20, num_classes=1000),
     }
     # the plain-ViT baseline (use_nvit=False, the reference's nvit0_k0 profile) at the same shapes
     for base in ("micro", "mini", "tiny", "base"):

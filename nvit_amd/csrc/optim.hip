@@ -11,8 +11,9 @@
 //                        that normalize_matrices touches, the row / column L2 normalisation of the UPDATED weights
 //                        before they are written - each of p, g, m, v is read once and p, m, v written once
 //                        (28 B per parameter; the unfused sequence moves ~52 B and needs ~20 launches).
-// Item kinds: -1 = plain chunk of 8192 elements; 1 = 16 rows, one wave per row (row norm, dim=1);
-//             0 = slab of all rows x 32 columns kept in LDS (column norm, dim=0).
+// Item kinds: -1 = plain chunk of 8192 elements; 1 = 16 rows, one wave per row (row norm, dim=1; cols <= 2048);
+//             0 = slab of all rows x 32 columns kept in LDS (column norm, dim=0), all rows x 16 columns for matrices
+//                 of more than 1152 rows (rows <= 2048): the slab and its partial sums must fit the 160 KiB of a CU.
 // AdamW arithmetic follows torch's (decoupled weight decay, bias corrections passed in from the host in double):
 //   p *= 1 - lr*wd;  m = b1*m + (1-b1)*g;  v = b2*v + (1-b2)*g*g;  p -= (lr/bc1) * m / (sqrt(v)/sqrt(bc2) + eps).
 #include "common.h"
@@ -22,7 +23,12 @@ namespace {
 constexpr int OPT_COLS = 10;       // table columns (int64)
 constexpr int OPT_CHUNK = 8192;    // elements per plain item and per grad-norm chunk
 constexpr int OPT_ROWS_PER_ITEM = 16;  // one wave per row
-constexpr int OPT_SLAB_COLS = 32;
+constexpr int OPT_SLAB_COLS = 32;        // column slab of a matrix of at most OPT_SLAB_ROWS rows
+constexpr int OPT_SLAB_ROWS = 1152;      //   (1152 x 32 + 128 x 32 partial sums) x 4 B = 160 KiB, all of a CU's LDS
+constexpr int OPT_TALL_COLS = 16;        // column slab of a taller matrix
+constexpr int OPT_TALL_ROWS = 2048;      //   (2048 x 16 + 256 x 16 partial sums) x 4 B = 144 KiB
+constexpr int OPT_ROW_COLS = 1536;       // a row of at most this many columns stays in registers (6 float4 per lane),
+constexpr int OPT_WIDE_COLS = 2048;      //   a wider one is parked in LDS: 16 waves x 2048 x 4 B = 128 KiB
 
 struct OptRow {
   float* p;
@@ -124,13 +130,74 @@ __device__ __forceinline__ void adam4(f32x4& p, const f32x4& g, f32x4& m, f32x4&
   }
 }
 
+// kind 0: column slab [rows][SC] of updated weights in LDS, SC = 32 columns (16 for matrices of more than OPT_SLAB_ROWS
+// rows); SC / 4 threads cover the SC columns of a row, RG = 1024 / (SC / 4) row groups; the RG partial sums of a column
+// are added in row-group order by one thread.  One body for both widths (the width is a shift count): two instances
+// of it push the kernel over its 128 registers.
+__device__ __forceinline__ void adamw_col_item(const OptRow& r, int local, int tid, float* slab, const AdamArgs& a,
+                                               float clip) {
+  const int sh = r.rows <= OPT_SLAB_ROWS ? 3 : 2;  // log2 of the threads across a slab row
+  const int SC = 4 << sh, RG = 1024 >> sh;
+  static_assert(OPT_SLAB_COLS == 4 << 3 && OPT_TALL_COLS == 4 << 2, "slab widths are 4 << sh");
+  float* cred = slab + (size_t)r.rows * SC;  // [RG][SC]
+  const int c0 = local * SC;
+  const int cg = (tid & ((1 << sh) - 1)) * 4, rg = tid >> sh;
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  const bool full = c0 + cg + 3 < r.cols && (r.cols & 3) == 0;
+  for (int row = rg; row < r.rows; row += RG) {
+    const size_t off = (size_t)row * r.cols + c0 + cg;
+    f32x4 p = {0.f, 0.f, 0.f, 0.f};
+    if (full) {
+      p = *reinterpret_cast<const f32x4*>(r.p + off);
+      const f32x4 g = *reinterpret_cast<const f32x4*>(r.g + off);
+      f32x4 m = *reinterpret_cast<const f32x4*>(r.m + off);
+      f32x4 v = *reinterpret_cast<const f32x4*>(r.v + off);
+      adam4(p, g, m, v, a, r.lr, r.wd, clip);
+      *reinterpret_cast<f32x4*>(r.m + off) = m;
+      *reinterpret_cast<f32x4*>(r.v + off) = v;
+    } else {
+      for (int e = 0; e < 4; ++e)
+        if (c0 + cg + e < r.cols) {
+          float pe = r.p[off + e], me = r.m[off + e], ve = r.v[off + e];
+          adam1(pe, r.g[off + e], me, ve, a, r.lr, r.wd, clip);
+          r.m[off + e] = me;
+          r.v[off + e] = ve;
+          p[e] = pe;
+        }
+    }
+    *reinterpret_cast<f32x4*>(slab + row * SC + cg) = p;
+    acc += p * p;
+  }
+  *reinterpret_cast<f32x4*>(cred + rg * SC + cg) = acc;
+  __syncthreads();
+  if (tid < SC) {
+    float s = 0.f;
+    for (int gidx = 0; gidx < RG; ++gidx) s += cred[gidx * SC + tid];
+    cred[tid] = sqrtf(s);  // row 0 of cred is only read by thread `tid` above before this write
+  }
+  __syncthreads();
+  const f32x4 nrm = *reinterpret_cast<const f32x4*>(cred + cg);
+  for (int row = rg; row < r.rows; row += RG) {
+    const size_t off = (size_t)row * r.cols + c0 + cg;
+    const f32x4 p = *reinterpret_cast<const f32x4*>(slab + row * SC + cg) / nrm;
+    if (full)
+      *reinterpret_cast<f32x4*>(r.p + off) = p;
+    else
+      for (int e = 0; e < 4; ++e)
+        if (c0 + cg + e < r.cols) r.p[off + e] = p[e];
+  }
+  __syncthreads();
+}
+
 // 1024 threads = 16 waves, one workgroup per CU (the column slab takes most of the LDS), so the streaming items
 // still have 16 waves x 4 tensors of loads in flight per CU.
 __global__ __launch_bounds__(1024) void adamw_renorm_kernel(const int64_t* table, int n, int total_items,
                                                             const float* partial, AdamArgs a, float* gnorm_out,
                                                             const float* hyper) {
+  // dynamic LDS: the column slab and its partial sums (up to all 160 KiB of the CU, so nothing is declared statically);
+  // its first 64 bytes serve the clip-factor sum before the item loop
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  __shared__ float red[16];
+  float* red = reinterpret_cast<float*>(smem);
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   if (hyper) {  // bias corrections of the device-side step counter (nvit_adamw_tick): hipGraph replays stay correct
     a.inv_bc1 = hyper[1];
@@ -142,6 +209,7 @@ __global__ __launch_bounds__(1024) void adamw_renorm_kernel(const int64_t* table
     float s = 0.f;
     for (int i = tid; i < a.npart; i += 1024) s += partial[i];
     s = block_sum<16>(s, red);
+    __syncthreads();  // `red` is the head of the slab the item loop writes
     const float nrm = sqrtf(s);
     if (a.max_norm > 0.f) {
       const float c = a.max_norm / (nrm + 1e-6f);
@@ -177,7 +245,7 @@ __global__ __launch_bounds__(1024) void adamw_renorm_kernel(const int64_t* table
           r.v[e] = v;
         }
       }
-    } else if (r.kind == 1) {
+    } else if (r.kind == 1 && r.cols <= OPT_ROW_COLS) {
       // rows: one wave per row; the updated row stays in registers (cols <= 1536, multiple of 4) for the norm
       const int row = local * OPT_ROWS_PER_ITEM + wid;
       if (row < r.rows) {
@@ -211,57 +279,32 @@ __global__ __launch_bounds__(1024) void adamw_renorm_kernel(const int64_t* table
           if (k < kmax && c < r.cols) *reinterpret_cast<f32x4*>(r.p + off + c) = pw[k] / nrm;
         }
       }
-    } else {
-      // column slab [rows][32] of updated weights in LDS; 8 threads cover 32 columns, 128 row groups
-      float* slab = reinterpret_cast<float*>(smem);
-      float* cred = slab + (size_t)r.rows * OPT_SLAB_COLS;  // [128][32]
-      const int c0 = local * OPT_SLAB_COLS;
-      const int cg = (tid & 7) * 4, rg = tid >> 3;
-      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-      const bool full = c0 + cg + 3 < r.cols;
-      for (int row = rg; row < r.rows; row += 128) {
-        const size_t off = (size_t)row * r.cols + c0 + cg;
-        f32x4 p = {0.f, 0.f, 0.f, 0.f};
-        if (full) {
-          p = *reinterpret_cast<const f32x4*>(r.p + off);
-          const f32x4 g = *reinterpret_cast<const f32x4*>(r.g + off);
-          f32x4 m = *reinterpret_cast<const f32x4*>(r.m + off);
-          f32x4 v = *reinterpret_cast<const f32x4*>(r.v + off);
+    } else if (r.kind == 1) {
+      // wide rows (cols <= 2048): 8 float4 per lane would cost the kernel its register budget, so each wave parks its
+      // updated row in LDS (16 x cols x 4 B <= 128 KiB, see nvit_adamw_renorm) between the update and the scaled store
+      const int row = local * OPT_ROWS_PER_ITEM + wid;
+      if (row < r.rows) {
+        const size_t off = (size_t)row * r.cols;
+        float* prow = reinterpret_cast<float*>(smem) + wid * r.cols;
+        float ss = 0.f;
+        for (int c = lane * 4; c < r.cols; c += 256) {
+          f32x4 p = *reinterpret_cast<const f32x4*>(r.p + off + c);
+          const f32x4 g = *reinterpret_cast<const f32x4*>(r.g + off + c);
+          f32x4 m = *reinterpret_cast<const f32x4*>(r.m + off + c);
+          f32x4 v = *reinterpret_cast<const f32x4*>(r.v + off + c);
           adam4(p, g, m, v, a, r.lr, r.wd, clip);
-          *reinterpret_cast<f32x4*>(r.m + off) = m;
-          *reinterpret_cast<f32x4*>(r.v + off) = v;
-        } else {
-          for (int e = 0; e < 4; ++e)
-            if (c0 + cg + e < r.cols) {
-              float pe = r.p[off + e], me = r.m[off + e], ve = r.v[off + e];
-              adam1(pe, r.g[off + e], me, ve, a, r.lr, r.wd, clip);
-              r.m[off + e] = me;
-              r.v[off + e] = ve;
-              p[e] = pe;
-            }
+          *reinterpret_cast<f32x4*>(r.m + off + c) = m;
+          *reinterpret_cast<f32x4*>(r.v + off + c) = v;
+          *reinterpret_cast<f32x4*>(prow + c) = p;
+          ss += p[0] * p[0] + p[1] * p[1] + p[2] * p[2] + p[3] * p[3];
         }
-        *reinterpret_cast<f32x4*>(slab + row * 32 + cg) = p;
-        acc += p * p;
+        const float nrm = sqrtf(wave_sum(ss));
+        for (int c = lane * 4; c < r.cols; c += 256)  // every lane reads back what it wrote itself
+          *reinterpret_cast<f32x4*>(r.p + off + c) = *reinterpret_cast<const f32x4*>(prow + c) / nrm;
       }
-      *reinterpret_cast<f32x4*>(cred + rg * 32 + cg) = acc;
-      __syncthreads();
-      if (tid < 32) {
-        float s = 0.f;
-        for (int gidx = 0; gidx < 128; ++gidx) s += cred[gidx * 32 + tid];
-        cred[tid] = sqrtf(s);  // row 0 of cred is only read by thread `tid` above before this write
-      }
-      __syncthreads();
-      const f32x4 nrm = *reinterpret_cast<const f32x4*>(cred + cg);
-      for (int row = rg; row < r.rows; row += 128) {
-        const size_t off = (size_t)row * r.cols + c0 + cg;
-        const f32x4 p = *reinterpret_cast<const f32x4*>(slab + row * 32 + cg) / nrm;
-        if (full)
-          *reinterpret_cast<f32x4*>(r.p + off) = p;
-        else
-          for (int e = 0; e < 4; ++e)
-            if (c0 + cg + e < r.cols) r.p[off + e] = p[e];
-      }
-      __syncthreads();
+      __syncthreads();  // the next item may be a column slab over the same LDS
+    } else {
+      adamw_col_item(r, local, tid, reinterpret_cast<float*>(smem), a, clip);
     }
   }
 }
@@ -300,8 +343,9 @@ extern "C" int nvit_adamw_renorm(const int64_t* table, int n, int total_items, i
                                  const float* partial, int npart, float max_norm, float* gnorm_out,
                                  const float* hyper, void* stream) {
   NVIT_REQUIRE(table && n > 0 && total_items > 0, "adamw_renorm: empty table");
-  NVIT_REQUIRE(max_slab_rows >= 0 && max_slab_rows <= 1152,
-               "adamw_renorm: column-normalised matrix with %d rows exceeds the LDS slab (1152)", max_slab_rows);
+  NVIT_REQUIRE(max_slab_rows >= 0 && max_slab_rows <= OPT_TALL_ROWS,
+               "adamw_renorm: column-normalised matrix with %d rows exceeds the LDS slab (%d)", max_slab_rows,
+               OPT_TALL_ROWS);
   NVIT_REQUIRE(hyper || (bias_correction1 > 0.0 && bias_correction2 > 0.0),
                "adamw_renorm: bias corrections must be > 0");
   NVIT_REQUIRE(!partial || (npart > 0 && npart <= 4096), "adamw_renorm: bad npart");
@@ -314,7 +358,16 @@ extern "C" int nvit_adamw_renorm(const int64_t* table, int n, int total_items, i
   a.max_norm = max_norm;
   a.npart = npart;
   hipStream_t s = (hipStream_t)stream;
-  const int lds = max_slab_rows > 0 ? (max_slab_rows * OPT_SLAB_COLS + 128 * 32) * 4 : 0;
+  // slab + [row groups][slab columns] partial sums (4096 floats in both forms).  A table whose tallest matrix takes the
+  // 16-column slab may also hold one of up to OPT_SLAB_ROWS rows on the 32-column slab: size for both.  At least the 64
+  // bytes of the clip-factor sum.
+  static_assert(OPT_TALL_ROWS * OPT_TALL_COLS <= OPT_SLAB_ROWS * OPT_SLAB_COLS, "the tall slab fits the LDS of the wide one");
+  static_assert((OPT_SLAB_ROWS * OPT_SLAB_COLS + 4096) * 4 <= 160 * 1024, "slab + partial sums fit the LDS of a CU");
+  // (Rows of more than OPT_ROW_COLS columns are parked in the same LDS, 16 x cols x 4 B: the caller passes
+  // max_slab_rows >= 1024 for a table that holds such a matrix, see nvit_hip.h.)
+  static_assert(16 * OPT_WIDE_COLS <= 1024 * OPT_SLAB_COLS + 4096, "max_slab_rows = 1024 covers 16 parked wide rows");
+  const int slab_rows = max_slab_rows > OPT_SLAB_ROWS ? OPT_SLAB_ROWS : max_slab_rows;
+  const int lds = slab_rows > 0 ? (slab_rows * OPT_SLAB_COLS + 4096) * 4 : 64;
   static int lds_set = 0;
   if (lds > lds_set) {
     hipError_t e = hipFuncSetAttribute((const void*)adamw_renorm_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);

@@ -6,7 +6,8 @@
 //   dim=1 (row norms, query/key/value/c_fc): one wave per row; the second pass over the row
 //         (<= 16 KiB) is served by L1/L2.
 //   dim=0 (column norms, att_c_proj/mlp_c_proj): a workgroup keeps a [rows x 64-column] panel
-//         in registers (rows <= 1152), so the column pass needs no re-read.
+//         in registers (rows <= 1152; [rows x 32-column] for 1152 < rows <= 2048), so the column
+//         pass needs no re-read.
 //
 // shadow_kernel: builds the private MFMA-operand copies of the fp32 masters: W (optionally
 // row-permuted for the SwiGLU interleave) and W^T, cast to bf16 (or kept fp32 for the exact
@@ -28,12 +29,77 @@ __device__ __forceinline__ int table_row(const int64_t* table, int n, int stride
 
 // 1024-thread workgroups (16 waves per CU keep ~48 KiB of 16-byte loads in flight, which is what an HBM-bound
 // stream needs on this chip).  dim=1: one wave per row, the row stays in registers between the norm and the
-// scaled store (one read + one write per element, no second pass).  dim=0: [rows x 64] column panel in registers.
+// scaled store (one read + one write per element, no second pass).  dim=0: [rows x 64] column panel in registers
+// ([rows x 32] above 1152 rows).
 constexpr int RENORM_THREADS = 1024;
 constexpr int RENORM_CL = NVIT_RENORM_COLS_PER_ITEM / 4;   // lanes across a panel row (16-byte pieces)
 constexpr int RENORM_RG = RENORM_THREADS / RENORM_CL;   // row groups of the column pass
 constexpr int RENORM_NV = 8;                    // float4 per lane held in registers: rows of up to 2048 columns
 constexpr int RENORM_NR = 1152 / RENORM_RG;      // rows per thread of a column panel: matrices of up to 1152 rows
+// taller matrices (rows <= 2048): a 32-column panel, 128 row groups, 16 rows per thread - 32 float4 per thread of the
+// 64-column panel would not fit the 128 registers of a 1024-thread workgroup
+static_assert(RENORM_NR * RENORM_RG == NVIT_RENORM_TALL_ROWS, "the 64-column panel holds NVIT_RENORM_TALL_ROWS rows");
+constexpr int RENORM_TALL_RG = RENORM_THREADS / (NVIT_RENORM_TALL_COLS_PER_ITEM / 4);
+constexpr int RENORM_TALL_NR = NVIT_RENORM_MAX_ROWS_DIM0 / RENORM_TALL_RG;
+
+// dim=0: [rows x PC]-column panel (PC * 4-byte row segments) held in REGISTERS (thread = 4 columns x every RG-th row,
+// NR rows per thread): all loads go out before the reduction, only the partial sums cross LDS
+template <int PC, int NR>
+__device__ __forceinline__ void renorm_col_panel(float* W, int rows, int cols, int local, int tid, float* red) {
+  constexpr int CL = PC / 4, RG = RENORM_THREADS / CL;  // CL threads cover a panel row; RG row groups
+  static_assert(RG % 8 == 0 && 8 * PC <= RENORM_THREADS, "two-level sum: 8 parts of RG / 8 row groups");
+  const int c0 = local * PC;
+  const int cg = (tid % CL) * 4, rg = tid / CL;
+  const bool vec = c0 + cg + 3 < cols;
+  f32x4 v[NR];
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int i = 0; i < NR; ++i) {
+    const int r = rg + i * RG;
+    v[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    if (r < rows) {
+      if (vec)
+        v[i] = *reinterpret_cast<const f32x4*>(W + (size_t)r * cols + c0 + cg);
+      else
+        for (int e = 0; e < 4; ++e)
+          if (c0 + cg + e < cols) v[i][e] = W[(size_t)r * cols + c0 + cg + e];
+    }
+    acc += v[i] * v[i];
+  }
+  *reinterpret_cast<f32x4*>(red + rg * PC + cg) = acc;  // red [RG][PC]
+  __syncthreads();
+  // fixed-order two-level sum of the row-group partials: 8 parts per column, then 8
+  float* red2 = red + RG * PC;  // [8][PC] + [PC]
+  if (tid < 8 * PC) {
+    const int c = tid % PC, part = tid / PC;
+    float s = 0.f;
+#pragma unroll
+    for (int g = 0; g < RG / 8; ++g) s += red[(part * (RG / 8) + g) * PC + c];
+    red2[part * PC + c] = s;
+  }
+  __syncthreads();
+  if (tid < PC) {
+    float s = 0.f;
+#pragma unroll
+    for (int part = 0; part < 8; ++part) s += red2[part * PC + tid];
+    red2[8 * PC + tid] = sqrtf(s);
+  }
+  __syncthreads();
+  const f32x4 nrm = *reinterpret_cast<const f32x4*>(red2 + 8 * PC + cg);
+#pragma unroll
+  for (int i = 0; i < NR; ++i) {
+    const int r = rg + i * RG;
+    if (r < rows) {
+      const f32x4 o = v[i] / nrm;
+      if (vec)
+        *reinterpret_cast<f32x4*>(W + (size_t)r * cols + c0 + cg) = o;
+      else
+        for (int e = 0; e < 4; ++e)
+          if (c0 + cg + e < cols) W[(size_t)r * cols + c0 + cg + e] = o[e];
+    }
+  }
+  __syncthreads();
+}
 
 __global__ __launch_bounds__(RENORM_THREADS) void renorm_kernel(const int64_t* table, int n, int total_items) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -71,62 +137,11 @@ __global__ __launch_bounds__(RENORM_THREADS) void renorm_kernel(const int64_t* t
           for (int c = lane; c < cols; c += 64) row[c] = row[c] / nrm;
         }
       }
+    } else if (rows <= NVIT_RENORM_TALL_ROWS) {
+      renorm_col_panel<NVIT_RENORM_COLS_PER_ITEM, RENORM_NR>(W, rows, cols, local, tid, reinterpret_cast<float*>(smem));
     } else {
-      // [rows x 64]-column panel (256-byte row segments) held in REGISTERS (thread = 4 columns x every 64th row):
-      // all loads go out before the reduction, only the partial sums cross LDS
-      constexpr int PC = NVIT_RENORM_COLS_PER_ITEM;
-      float* red = reinterpret_cast<float*>(smem);  // [RENORM_RG][PC]
-      const int c0 = local * PC;
-      const int cg = (tid % RENORM_CL) * 4, rg = tid / RENORM_CL;  // RENORM_CL threads cover a panel row; RENORM_RG row groups
-      const bool vec = c0 + cg + 3 < cols;
-      f32x4 v[RENORM_NR];
-      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int i = 0; i < RENORM_NR; ++i) {
-        const int r = rg + i * RENORM_RG;
-        v[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        if (r < rows) {
-          if (vec)
-            v[i] = *reinterpret_cast<const f32x4*>(W + (size_t)r * cols + c0 + cg);
-          else
-            for (int e = 0; e < 4; ++e)
-              if (c0 + cg + e < cols) v[i][e] = W[(size_t)r * cols + c0 + cg + e];
-        }
-        acc += v[i] * v[i];
-      }
-      *reinterpret_cast<f32x4*>(red + rg * PC + cg) = acc;
-      __syncthreads();
-      // fixed-order two-level sum of the row-group partials: 8 parts per column, then 8
-      float* red2 = red + RENORM_RG * PC;  // [8][PC] + [PC]
-      if (tid < 8 * PC) {
-        const int c = tid % PC, part = tid / PC;
-        float s = 0.f;
-#pragma unroll
-        for (int g = 0; g < RENORM_RG / 8; ++g) s += red[(part * (RENORM_RG / 8) + g) * PC + c];
-        red2[part * PC + c] = s;
-      }
-      __syncthreads();
-      if (tid < PC) {
-        float s = 0.f;
-#pragma unroll
-        for (int part = 0; part < 8; ++part) s += red2[part * PC + tid];
-        red2[8 * PC + tid] = sqrtf(s);
-      }
-      __syncthreads();
-      const f32x4 nrm = *reinterpret_cast<const f32x4*>(red2 + 8 * PC + cg);
-#pragma unroll
-      for (int i = 0; i < RENORM_NR; ++i) {
-        const int r = rg + i * RENORM_RG;
-        if (r < rows) {
-          const f32x4 o = v[i] / nrm;
-          if (vec)
-            *reinterpret_cast<f32x4*>(W + (size_t)r * cols + c0 + cg) = o;
-          else
-            for (int e = 0; e < 4; ++e)
-              if (c0 + cg + e < cols) W[(size_t)r * cols + c0 + cg + e] = o[e];
-        }
-      }
-      __syncthreads();
+      renorm_col_panel<NVIT_RENORM_TALL_COLS_PER_ITEM, RENORM_TALL_NR>(W, rows, cols, local, tid,
+                                                                       reinterpret_cast<float*>(smem));
     }
   }
 }
@@ -195,7 +210,9 @@ __global__ __launch_bounds__(256) void shadow_kernel(const int64_t* table, int n
 extern "C" int nvit_renorm_weights(const int64_t* table, int n, int total_items, void* stream) {
   NVIT_REQUIRE(n > 0 && total_items > 0, "renorm: empty table");
   hipStream_t s = (hipStream_t)stream;
-  // LDS for the largest column slab: caller guarantees rows <= 1152 for dim=0 matrices.
+  // LDS: the partial sums of a column panel only; caller guarantees rows <= NVIT_RENORM_MAX_ROWS_DIM0 for dim=0 matrices.
+  static_assert((RENORM_TALL_RG + 9) * NVIT_RENORM_TALL_COLS_PER_ITEM <= (RENORM_RG + 9) * NVIT_RENORM_COLS_PER_ITEM,
+                "the tall panel's partial sums fit the LDS of the 64-column panel");
   static_assert(NVIT_RENORM_ROWS_PER_ITEM % (RENORM_THREADS / 64) == 0, "whole rounds of one row per wave");
   static const int kMaxLds = (RENORM_RG + 9) * NVIT_RENORM_COLS_PER_ITEM * 4;   // partial sums only (~18 KiB)
   static bool attr_set = false;

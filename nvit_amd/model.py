@@ -31,7 +31,7 @@ import torch
 from torch import nn
 
 from . import ops
-from ._lib import ATTN_HEADS_MAX_H, BF16, BF16_F32IN, F32
+from ._lib import ATTN_HEADS_MAX_H, BF16, BF16_F32IN, F32, MAX_EMBD
 from .config import ViTConfig
 from .kohonen import CosConsistencyFn, HuberFn, KohonenMap, MapSmoothnessFn
 
@@ -296,7 +296,7 @@ def _attn_fwd(rt: _Runtime, impl: int, srcs, has_b: bool, sqk: Optional[Tensor],
       heads  flash_attn=True: the reference's flash_attn_func reads its [B,H,T,d] arguments as [batch, seqlen, nheads,
              headdim], so the softmax runs over the H heads of each token of the fp32 token-major
              projections;
-      fused  no bias, d = 64 and a shape the fused GEMM takes (bf16 only; N of the FIRST projection decides): the
+      fused  no bias, d = 64, C % 256 == 0 and a shape the fused GEMM takes (bf16 only; N of the FIRST projection decides): the
              normalise (nViT) and the head split in the projection GEMM's epilogue, q pre-scaled so that the attention
              kernels' exponent needs no multiply;
       split  otherwise (small problems: 128x128 GEMM kernel): the projections leave the GEMM in fp32 and are normalised
@@ -306,7 +306,7 @@ def _attn_fwd(rt: _Runtime, impl: int, srcs, has_b: bool, sqk: Optional[Tensor],
     B, T, C, H, d, M = dims
     dt, sh = rt.dt, rt.sh
     heads = rt.model.config.flash_attn
-    if not heads and not has_b and impl == 1 and d == 64 and ops.fusable(dt, M, srcs[0][2] * C, C):
+    if not heads and not has_b and impl == 1 and d == 64 and C % 256 == 0 and ops.fusable(dt, M, srcs[0][2] * C, C):
         route = "fused"
         # the softmax scale (nViT: sqrt(d) on unit q, k) times log2(e); with sqk absent the running-maximum kernel runs
         # on the pre-scaled q (and the dK/dV backward takes its generated loop)
@@ -1048,6 +1048,8 @@ class ViT(nn.Module):
                                       "without the Kohonen head only (no reference run profile uses that combination)")
         if config.n_embd % config.n_head != 0 or config.n_embd % 64 != 0:
             raise ValueError("n_embd must be a multiple of 64 and divisible by n_head")
+        if config.n_embd > MAX_EMBD:
+            raise ValueError(f"n_embd must be at most {MAX_EMBD}, the widest row the row kernels hold (got {config.n_embd})")
         if (config.n_embd // config.n_head) not in HEAD_DIMS:
             raise ValueError(f"head dim must be one of {HEAD_DIMS} (got {config.n_embd // config.n_head})")
         if config.flash_attn and config.n_head > ATTN_HEADS_MAX_H:

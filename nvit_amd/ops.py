@@ -772,9 +772,14 @@ def renorm_table(mats, device) -> Tuple[Tensor, int]:
     for w, dim in mats:
         assert w.dtype == torch.float32 and w.is_contiguous() and w.dim() == 2
         r, c = w.shape
-        if dim == 0 and r > 1152:
-            raise RuntimeError(f"renorm: column-normalised matrix with {r} rows exceeds the LDS slab (1152)")
-        items = math.ceil(r / _lib.RENORM_ROWS_PER_ITEM) if dim == 1 else math.ceil(c / _lib.RENORM_COLS_PER_ITEM)
+        if dim == 0 and r > _lib.RENORM_MAX_ROWS_DIM0:
+            raise RuntimeError(f"renorm: column-normalised matrix with {r} rows exceeds the register panel "
+                               f"({_lib.RENORM_MAX_ROWS_DIM0})")
+        if dim == 1:
+            items = math.ceil(r / _lib.RENORM_ROWS_PER_ITEM)
+        else:   # the panel width follows the kernel's choice by row count
+            items = math.ceil(c / (_lib.RENORM_COLS_PER_ITEM if r <= _lib.RENORM_TALL_ROWS
+                                   else _lib.RENORM_TALL_COLS_PER_ITEM))
         rows_.append([w.data_ptr(), r, c, dim, first])
         first += items
     return torch.tensor(rows_, dtype=torch.int64).to(device), first

@@ -32,7 +32,13 @@ from .ops import _p, _s, check
 
 _CHUNK = 8192
 _ROWS_PER_ITEM = 16
-_SLAB_COLS = 32
+_SLAB_COLS = 32        # column slab of a column-normalised matrix of at most _SLAB_ROWS rows,
+_SLAB_ROWS = 1152
+_TALL_COLS = 16        # of a taller one (at most _TALL_ROWS rows): the slab must fit the LDS of a CU
+_TALL_ROWS = 2048
+_ROW_COLS = 1536       # rows of a row-normalised matrix stay in registers up to this width,
+_WIDE_COLS = 2048      # wider ones (up to this) are parked in LDS, which must then hold 16 of them:
+_WIDE_LDS_ROWS = 1024  #   the LDS of a 1024-row slab does
 _NPART = 1024
 
 
@@ -91,13 +97,17 @@ class FusedAdamW(torch.optim.AdamW):
                 else:
                     kind, r, c = -1, 1, p.numel()
                 if kind == 1:
-                    if c % 4 or c > 1536:
-                        raise RuntimeError(f"FusedAdamW: row-normalised matrix needs cols % 4 == 0 and <= 1536 (got {c})")
+                    if c % 4 or c > _WIDE_COLS:
+                        raise RuntimeError(f"FusedAdamW: row-normalised matrix needs cols % 4 == 0 and <= {_WIDE_COLS} "
+                                           f"(got {c})")
                     items = math.ceil(r / _ROWS_PER_ITEM)
+                    if c > _ROW_COLS:
+                        max_slab_rows = max(max_slab_rows, _WIDE_LDS_ROWS)
                 elif kind == 0:
-                    if r > 1152:
-                        raise RuntimeError(f"FusedAdamW: column-normalised matrix with {r} rows exceeds the LDS slab")
-                    items = math.ceil(c / _SLAB_COLS)
+                    if r > _TALL_ROWS:
+                        raise RuntimeError(f"FusedAdamW: column-normalised matrix with {r} rows exceeds the LDS slab "
+                                           f"({_TALL_ROWS})")
+                    items = math.ceil(c / (_SLAB_COLS if r <= _SLAB_ROWS else _TALL_COLS))
                     max_slab_rows = max(max_slab_rows, r)
                 else:
                     items = math.ceil(p.numel() / _CHUNK)
