@@ -50,7 +50,8 @@ const char* nvit_last_error(void);
 #define NVIT_KID_GEMM_QKNORM 11     /* bf16 NT GEMM with the q/k-normalise + head-split epilogue (nvit_gemm_nt_qknorm) */
 #define NVIT_KID_GEMM_SWIGLU_BWD 12 /* bf16 NT GEMM with the SwiGLU-backward epilogue (nvit_gemm_nt_swiglu_bwd) */
 #define NVIT_KID_OPTIM 13           /* nvit_grad_sqnorm + nvit_adamw_renorm (NVIT_KID_RENORM = stand-alone nvit_renorm_weights) */
-#define NVIT_KID_COUNT 14
+#define NVIT_KID_GEMM_SWIGLU_ACT 14 /* bf16 NT GEMM with the gate-only SwiGLU epilogue (nvit_gemm_nt_swiglu_act) */
+#define NVIT_KID_COUNT 15
 void nvit_prof_enable(int on);
 /* time only the families whose bit is set (bit k = family k of nvit_prof_name); nvit_prof_enable(1) = all, (0) = none */
 void nvit_prof_select(unsigned mask);
@@ -155,6 +156,11 @@ int nvit_gemm_nt_swiglu_bwd(int dt, const void* A, int lda, const void* B, int l
                             float* part, int M, int F, int K, const float* gs, float gscale, void* stream);
 int nvit_gemm_nt_swiglu(int dt, const void* A, int lda, const void* B, int ldb, void* uv, void* xm, int M, int F,
                         int K, const float* gs, float gscale, void* stream);
+/* nvit_gemm_nt_swiglu_act: nvit_gemm_nt_swiglu for a forward that no backward follows (no_grad / evaluation): the same
+ * kernel, operands and gate arithmetic, but only xm[M,F] is written - the raw uv[M,2F], two thirds of the epilogue's
+ * stores, is not.  xm is bit-identical to nvit_gemm_nt_swiglu's.  Same eligibility (nvit_gemm_nt_fusable(dt, M, 2F, K)). */
+int nvit_gemm_nt_swiglu_act(int dt, const void* A, int lda, const void* B, int ldb, void* xm, int M, int F, int K,
+                            const float* gs, float gscale, void* stream);
 /* q_prescale: extra factor folded into the q part (qh = q_prescale * sqk*c_q * unit vector, one rounding); pass the same
  * value to nvit_attn_fwd_bounded / nvit_attn_bwd_qknorm.  1 = plain. */
 int nvit_gemm_nt_qknorm(int dt, const void* A, int lda, const void* B, int ldb, int M, int K, int nparts, int part0,
@@ -397,6 +403,12 @@ int nvit_recon_bwd(int dt, const float* raw, const float* img, const float* g, v
  * (multiply by the upstream scalar gradient).  Labels outside [0,N) contribute 0 loss (and a plain softmax/B row). */
 int nvit_ce_loss(const float* logits, const int64_t* labels, float* rowloss, float* loss, float* dlogits, int B, int N,
                  void* stream);
+/* Evaluation metrics of one batch in one launch (reference train.py:563-575, 595-613): per row the cross-entropy of
+ * nvit_ce_loss and rank = #{j : logit_j > logit_y} + #{j < y : logit_j == logit_y} (a label outside [0,N): loss 0,
+ * never correct).  ADDS to the device accumulator acc[0..3]: the batch-mean loss, 100 * #(rank < 1) / B,
+ * 100 * #(rank < min(5,N)) / B, and 1 (the batch count) - the reference reports means over batches of per-batch
+ * values.  Fixed-order reduction, no float atomics: reproducible run to run.  Nothing goes back to the host. */
+int nvit_eval_metrics(const float* logits, const int64_t* labels, float* acc, int B, int N, void* stream);
 
 /* ---- gradient all-reduce by direct peer reads over xGMI (nvit/train.py:438-446) --------------
  * Symmetric flat fp32 buffers of n elements (n % 4 == 0), one per rank, mapped into this process (IPC); peer_ptrs is a

@@ -10,6 +10,9 @@ def __getattr__(name):
     if name in ("normalize_matrices", "train_step"):
         from . import train
         return getattr(train, name)
+    if name in ("predict", "validate", "estimate_loss"):
+        from . import evaluate
+        return getattr(evaluate, name)
     if name == "FusedAdamW":
         from . import optim
         return optim.FusedAdamW

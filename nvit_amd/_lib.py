@@ -14,7 +14,7 @@ LIB_PATH = os.environ.get("NVIT_LIB") or os.path.join(_HERE, "libnvit_hip.so")
 
 F32, BF16, BF16_F32IN = 0, 1, 3
 KID_NAMES = ["gemm_nt", "gemm_tn", "attn_fwd", "attn_bwd", "rowops", "renorm", "shadow", "patchify", "misc", "gemm_f32",
-             "gemm_swiglu", "gemm_qknorm", "gemm_swiglu_bwd", "optim"]
+             "gemm_swiglu", "gemm_qknorm", "gemm_swiglu_bwd", "optim", "gemm_swiglu_act"]
 RENORM_ROWS_PER_ITEM = 64
 RENORM_COLS_PER_ITEM = 64
 RENORM_TALL_ROWS = 1152           # column-normalised matrices with more rows take the narrow panel / slab
@@ -41,9 +41,11 @@ SIGNATURES = {
     "nvit_set_gemm_sched": [_i],
     "nvit_set_gemm_impl": [_i, _i],
     "nvit_ce_loss": [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp],
+    "nvit_eval_metrics": [_vp, _vp, _vp, _i, _i, _vp],
     "nvit_gemm_nt": [_i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp],
     "nvit_gemm_nt_fusable": [_i, _i, _i, _i],
     "nvit_gemm_nt_swiglu": [_i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _f, _vp],
+    "nvit_gemm_nt_swiglu_act": [_i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _f, _vp],
     "nvit_gemm_nt_swiglu_bwd": [_i, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _f, _vp],
     "nvit_gemm_nt_qknorm": [_i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
     "nvit_gemm_tn": [_i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _i64, _i, _i, _vp],

@@ -513,6 +513,33 @@ extern "C" int nvit_gemm_nt_swiglu(int dt, const void* A, int lda, const void* B
   return nvit_gemm_nt_fused_launch(g, 3, s);
 }
 
+// The forward-only form of nvit_gemm_nt_swiglu: the same launch without the raw uv store (EPI 6).
+extern "C" int nvit_gemm_nt_swiglu_act(int dt, const void* A, int lda, const void* B, int ldb, void* xm, int M, int F, int K,
+                                       const float* gs, float gscale, void* stream) {
+  NVIT_REQUIRE(nvit_gemm_nt_fusable(dt, M, 2 * F, K), "gemm_nt_swiglu_act: shape/dtype not eligible for the fused kernel");
+  NVIT_REQUIRE((lda * 2) % 16 == 0 && (ldb * 2) % 16 == 0 && lda >= K && ldb >= K,
+               "gemm_nt_swiglu_act: bad leading dims");
+  NVIT_REQUIRE(A && B && xm && (((uintptr_t)A | (uintptr_t)B | (uintptr_t)xm | (uintptr_t)gs) & 15) == 0,
+               "gemm_nt_swiglu_act: pointers must be non-null and 16-byte aligned");
+  NtArgs g{};
+  g.A = (const char*)A;
+  g.B = (const char*)B;
+  g.M = M;
+  g.N = 2 * F;
+  g.K = K;
+  g.lda = lda;
+  g.ldb = ldb;
+  g.out_dt = NVIT_BF16;
+  g.xm = xm;
+  g.ld_xm = F;
+  g.gs = gs;
+  g.gscale = gscale;
+  hipStream_t s = (hipStream_t)stream;
+  // algorithmic bytes: A, B read; the gated x [M,F] written (bf16)
+  ProfScope ps(NVIT_KID_GEMM_SWIGLU_ACT, 2.0 * M * (2.0 * F) * K, 2.0 * ((double)M * K + 2.0 * F * K + (double)M * F), s);
+  return nvit_gemm_nt_fused_launch(g, 6, s);
+}
+
 extern "C" int nvit_gemm_nt_swiglu_bwd(int dt, const void* A, int lda, const void* B, int ldb, const void* uv,
                                        void* duv, float* part, int M, int F, int K, const float* gs, float gscale,
                                        void* stream) {

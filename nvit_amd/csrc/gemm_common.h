@@ -18,6 +18,7 @@ struct NtArgs {
   int out_dt;
   int tiles_n;
   // --- fused SwiGLU epilogue (EPI 3): C = raw uv (interleaved u16|v16 columns), xm = (gu*u)*silu(gv*v)
+  //     (EPI 6, gate only: C is not written and may be NULL)
   void* xm;
   int ld_xm;
   const float* gs;  // suv in the interleaved column order of C (or NULL = ones)
@@ -292,7 +293,9 @@ __device__ __forceinline__ void nt_store_tile_staged(const NtArgs& g, f32x4 (&ac
 // The weight shadow interleaves u/v partners 16 columns apart (perm=1), so acc[i][2jj] (u) and
 // acc[i][2jj+1] (v) of one lane are gate partners.  Writes the raw pre-activation tile (saved for
 // backward) and the gated activation, both bf16, both as whole-row 16-byte stores via the LDS scratch.
-template <int FMR>
+// RAW = false (EPI 6, the forward-only route): pass B alone - nothing reads the raw tile without a backward, and it is
+// two thirds of this epilogue's stores.  The gate is the same statements on the same accumulators, so xm is the same bits.
+template <int FMR, bool RAW = true>
 __device__ __forceinline__ void nt_store_tile_swiglu(const NtArgs& g, f32x4 (&acc)[FMR][4], int m_base, int n_base,
                                                      int lane, char* scratch) {
   const int l15 = lane & 15, lg = lane >> 4;
@@ -311,20 +314,22 @@ __device__ __forceinline__ void nt_store_tile_swiglu(const NtArgs& g, f32x4 (&ac
 #pragma unroll
   for (int i = 0; i < FMR; ++i) {
     // pass A: raw uv, 64 columns
+    if constexpr (RAW) {
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int bytecol = (j * 16 + 4 * lg) * 2;
-      char* dst = scratch + l15 * 128 + (((bytecol >> 4) ^ (l15 & 7)) << 4) + (bytecol & 15);
-      store4<bf16>(reinterpret_cast<bf16*>(dst), acc[i][j]);
-    }
+      for (int j = 0; j < 4; ++j) {
+        const int bytecol = (j * 16 + 4 * lg) * 2;
+        char* dst = scratch + l15 * 128 + (((bytecol >> 4) ^ (l15 & 7)) << 4) + (bytecol & 15);
+        store4<bf16>(reinterpret_cast<bf16*>(dst), acc[i][j]);
+      }
 #pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      const int idx = lane + 64 * t;
-      const int row = idx >> 3, chunk = idx & 7;
-      const uint4 raw = *reinterpret_cast<const uint4*>(scratch + row * 128 + ((chunk ^ (row & 7)) << 4));
-      const int m = m_base + i * 16 + row;
-      if (m < g.M)
-        st16_nt(reinterpret_cast<bf16*>(g.C) + (size_t)m * g.ldc + n_base + chunk * 8, raw);
+      for (int t = 0; t < 2; ++t) {
+        const int idx = lane + 64 * t;
+        const int row = idx >> 3, chunk = idx & 7;
+        const uint4 raw = *reinterpret_cast<const uint4*>(scratch + row * 128 + ((chunk ^ (row & 7)) << 4));
+        const int m = m_base + i * 16 + row;
+        if (m < g.M)
+          st16_nt(reinterpret_cast<bf16*>(g.C) + (size_t)m * g.ldc + n_base + chunk * 8, raw);
+      }
     }
     // pass B: gated activation, 32 columns
 #pragma unroll

@@ -36,7 +36,8 @@ __device__ __forceinline__ void wait_vmcnt() {
 }
 
 // EPI: 0 = generic direct epilogue, 1 = LDS-staged bf16 output, 2 = LDS-staged fp32 output,
-//      3 = fused SwiGLU (bf16), 4 = fused q/k-normalise + head split (bf16), 5 = fused SwiGLU backward (bf16)
+//      3 = fused SwiGLU (bf16), 4 = fused q/k-normalise + head split (bf16), 5 = fused SwiGLU backward (bf16),
+//      6 = fused SwiGLU, gated activation only (bf16; the forward-only route: the raw tile of 3 is not stored)
 // DYN: tiles are handed out at run time instead of statically.  Each XCD owns a contiguous eighth of the (grouped)
 // tile order and a ticket counter; a workgroup's first tile is static, every further one is `Gx + ticket` inside its
 // XCD's range.  The ticket for the tile after next is drawn (one atomic by thread 0) while the current tile is being
@@ -52,7 +53,7 @@ __global__ __launch_bounds__(512) void gemm_nt_persistent_kernel(NtArgs g, int t
   constexpr int DPS = Cfg::A_DMA + Cfg::B_DMA;  // DMA wave-instructions per wave per stage
   constexpr int WROWS = 16 * FM;                // rows of a wave's sub-tile
   // global stores one wave issues in the epilogue of a tile that lies fully inside C (lower bound; 0 = unknown)
-  constexpr int NST = EPI == 1 ? 2 * FM : EPI == 2 ? 4 * FM : EPI == 3 ? 3 * FM : EPI == 4 ? 2 * FM : EPI == 5 ? 8 : 0;
+  constexpr int NST = EPI == 1 ? 2 * FM : EPI == 2 ? 4 * FM : EPI == 3 ? 3 * FM : EPI == 4 ? 2 * FM : EPI == 5 ? 8 : EPI == 6 ? FM : 0;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int EPC = 16 / sizeof(T);
   constexpr int BK = ROWB / sizeof(T);
@@ -311,6 +312,8 @@ __global__ __launch_bounds__(512) void gemm_nt_persistent_kernel(NtArgs g, int t
           nt_store_tile_qknorm<FM>(g, acc, m0 + wr * WROWS, n0 + wc * 64, lane, scratch);
         else if constexpr (EPI == 5)
           nt_store_tile_swiglu_bwd<FM>(g, acc, m0 + wr * WROWS, n0 + wc * 64, lane, scratch);
+        else if constexpr (EPI == 6)
+          nt_store_tile_swiglu<FM, false>(g, acc, m0 + wr * WROWS, n0 + wc * 64, lane, scratch);
         else
           nt_store_tile<FM>(g, acc, m0 + wr * WROWS, n0 + wc * 64, l15, lg);
       }
@@ -425,11 +428,13 @@ extern "C" int nvit_set_gemm_sched(int dynamic) {
   return NVIT_OK;
 }
 
-// fused-epilogue launches (bf16 operands, 256x256 tiles): epi = 3 (SwiGLU), 4 (q/k normalise), 5 (SwiGLU backward)
+// fused-epilogue launches (bf16 operands, 256x256 tiles): epi = 3 (SwiGLU), 4 (q/k normalise), 5 (SwiGLU backward),
+// 6 (SwiGLU, gated activation only)
 int nvit_gemm_nt_fused_launch(const NtArgs& g, int epi, hipStream_t s) {
   const int n_cu = p_num_cu();
   if (n_cu == 0) NVIT_FAIL(NVIT_EINVAL, "gemm_nt: cannot query device properties");
   if (epi == 5) return launch_p2<bf16, 8, 5>(g, n_cu, s);
+  if (epi == 6) return launch_p2<bf16, 8, 6>(g, n_cu, s);
   return epi == 3 ? launch_p2<bf16, 8, 3>(g, n_cu, s) : launch_p2<bf16, 8, 4>(g, n_cu, s);
 }
 

@@ -272,6 +272,14 @@ def _take_carry(rt: "_Runtime", idx: int, chained: bool, dout: Tensor):
 RMS_EPS = 1e-6   # reference RMSNorm default (model.py:171)
 
 
+def _lean() -> bool:
+    """True when no backward can follow the forward being built (torch.no_grad / inference_mode: estimate_loss, validate
+    and serving in the reference, train.py:482-506,577-627).  The block functions then store nothing that only their
+    backward reads and save nothing; every value they return is the same bits.  Asked where a block function is APPLIED:
+    inside an autograd.Function's forward grad mode is always off."""
+    return not torch.is_grad_enabled()
+
+
 def _dims(rt: _Runtime, M: int):
     """(B, T, C, H, d, M) of a block call over M = B*T token rows."""
     cfg = rt.model.config
@@ -289,7 +297,8 @@ def _qkv_cols(ts, C: int):
     return q, C, kv, kv[:, C:], 2 * C
 
 
-def _attn_fwd(rt: _Runtime, impl: int, srcs, has_b: bool, sqk: Optional[Tensor], c_q: float, scale: float, dims):
+def _attn_fwd(rt: _Runtime, impl: int, srcs, has_b: bool, sqk: Optional[Tensor], c_q: float, scale: float, dims,
+              lean: bool = False):
     """The attention of every block function, from its q/k/v projection sources to O [M, C] (the output projection's A
     operand).  srcs: ((A, shadow prefix, parts), ...), one projection GEMM each, their output columns q | k | v in
     order.  sqk None (c_q 0.0): plain-ViT heads, else the nViT normalise + sqk scale.  One of three routes:
@@ -302,7 +311,10 @@ def _attn_fwd(rt: _Runtime, impl: int, srcs, has_b: bool, sqk: Optional[Tensor],
       split  otherwise (small problems: 128x128 GEMM kernel): the projections leave the GEMM in fp32 and are normalised
              from the unrounded values, like the fused epilogue (one rounding, at the head tensors).
     -> o, lse, att (route, impl, q pre-scale, scale) for _attn_bwd, and the tensors it reads: the fp32 projections
-    (heads) or qh, kh, vh, rq, rk."""
+    (heads) or qh, kh, vh, rq, rk.
+    lean (a forward no backward follows): the same launches - no attention kernel takes a NULL lse, rq or rk, so those
+    small stores stay - but nothing is handed back for saving: the projections / head tensors are released here, before
+    the caller allocates the MLP's tensors, not at the end of the block."""
     B, T, C, H, d, M = dims
     dt, sh = rt.dt, rt.sh
     heads = rt.model.config.flash_attn
@@ -323,7 +335,7 @@ def _attn_fwd(rt: _Runtime, impl: int, srcs, has_b: bool, sqk: Optional[Tensor],
         q, ldq, k, v, ldkv = _qkv_cols(projs, C)
         if heads:
             o, lse = ops.attn_heads_fwd(dt, q, ldq, k, v, ldkv, sqk, c_q, scale, M, H, d)
-            return o, lse, ("heads", impl, 1.0, scale), tuple(projs)
+            return o, lse, ("heads", impl, 1.0, scale), (() if lean else tuple(projs))
         route, qpre = "split", 1.0
         dt_in = dt if dt == F32 else BF16_F32IN   # the projection outputs are fp32 in both modes
         bufs = ops.qknorm_fwd(dt_in, q, ldq, k, ldkv, v, ldkv, sqk, c_q, B, T, H, d)
@@ -331,7 +343,7 @@ def _attn_fwd(rt: _Runtime, impl: int, srcs, has_b: bool, sqk: Optional[Tensor],
             del projs, q, k, v
     qh, kh, vh, _, _ = bufs
     o, lse = ops.attn_fwd(dt, impl, qh, kh, vh, scale, sqk, c_q, q_prescale=qpre)
-    return o, lse, (route, impl, qpre, scale), bufs
+    return o, lse, (route, impl, qpre, scale), (() if lean else bufs)
 
 
 def _attn_bwd(rt: _Runtime, att, saved, do: Tensor, o: Tensor, lse: Tensor, grads, sqk: Optional[Tensor], c_q: float,
@@ -359,16 +371,22 @@ def _attn_bwd(rt: _Runtime, att, saved, do: Tensor, o: Tensor, lse: Tensor, grad
 
 
 def _swiglu_fwd(rt: _Runtime, A: Tensor, w: str, M: int, F: int, K: int, has_b: bool, gs: Optional[Tensor],
-                gs_fused: Optional[Tensor], gscale: float):
+                gs_fused: Optional[Tensor], gscale: float, lean: bool = False):
     """Gated MLP input: uv = A W^T (+ bias) [M, 2F] (shadow `w`, interleaved columns) and x = swiglu(uv) [M, F] with the
     gate scale gs * gscale (gs None: 1).  -> (uv as backward reads it, x).  The fused GEMM epilogue takes gs in the
-    shadow's interleaved column order (gs_fused), the row kernel in natural order (gs)."""
+    shadow's interleaved column order (gs_fused), the row kernel in natural order (gs).
+    lean (a forward no backward follows): uv is None - the fused GEMM does not store it (the gate-only epilogue, same
+    x bit for bit), the unfused route does not make the bf16 copy."""
     dt, sh = rt.dt, rt.sh
     if not has_b and ops.fusable(dt, M, 2 * F, K):
+        if lean:
+            return None, ops.gemm_nt_swiglu_act(A, sh[w + ".W"], M, F, K, gs_fused, gscale)
         return ops.gemm_nt_swiglu(A, sh[w + ".W"], M, F, K, gs_fused, gscale)
     uv32 = ops.gemm_nt(A, sh[w + ".W"], M, 2 * F, K, out_dtype=torch.float32, bias=sh.get(w + ".b"))
     # bf16: the gate from the unrounded pre-activations; the bf16 copy is what backward reads
     x = ops.swiglu_fwd(dt if dt == F32 else BF16_F32IN, uv32, gs, gscale, M, F)
+    if lean:
+        return None, x
     return (uv32 if dt == F32 else ops.cast(uv32, dt)), x
 
 
@@ -396,7 +414,7 @@ class _BlockFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, x_lo, rt, idx, with_skip, impl, skip_param, attn_alpha, mlp_alpha, sqk, suv, wq, wk, wv, wo,
-                wfc, wp, bq, bk_, bv, bo, bfc, bp, chained=False):
+                wfc, wp, bq, bk_, bv, bo, bfc, bp, chained=False, lean=False):
         cfg = rt.model.config
         dims = _dims(rt, x.shape[0])
         B, T, C, H, d, M = dims
@@ -405,13 +423,14 @@ class _BlockFn(torch.autograd.Function):
         c_q, c_a = 1.0 / cfg.base_scale, 0.05 / cfg.base_scale
         pre = f"h{idx}."
         has_b = bq is not None
-        o, lse, att, att_saved = _attn_fwd(rt, impl, ((x_lo, pre + "qkv", 3),), has_b, sqk, c_q, math.sqrt(d), dims)
+        o, lse, att, att_saved = _attn_fwd(rt, impl, ((x_lo, pre + "qkv", 3),), has_b, sqk, c_q, math.sqrt(d), dims,
+                                           lean)
         y = ops.gemm_nt(o, sh[pre + "o.W"], M, C, C, out_dtype=rt.y_dtype(), bias=sh.get(pre + "o.b"))
         h1, h1_lo = ops.lerp_fwd(dt, x, y, attn_alpha, c_a, want_lo=(dt != F32))
         if dt == F32:
             h1_lo = h1
         # c_fc GEMM with the suv scale + SwiGLU gate (writes raw uv for backward and x_mlp)
-        uv, xm = _swiglu_fwd(rt, h1_lo, pre + "fc", M, 4 * C, C, has_b, suv, sh[pre + "suv_i"], math.sqrt(C))
+        uv, xm = _swiglu_fwd(rt, h1_lo, pre + "fc", M, 4 * C, C, has_b, suv, sh[pre + "suv_i"], math.sqrt(C), lean)
         y2 = ops.gemm_nt(xm, sh[pre + "p.W"], M, C, 4 * C, out_dtype=rt.y_dtype(), bias=sh.get(pre + "p.b"))
         if with_skip:
             xn, xn_lo = ops.lerp_fwd(dt, h1, y2, mlp_alpha, c_a, skip_x=x, skip=skip_param, want_lo=(dt != F32))
@@ -419,6 +438,8 @@ class _BlockFn(torch.autograd.Function):
             xn, xn_lo = ops.lerp_fwd(dt, h1, y2, mlp_alpha, c_a, want_lo=(dt != F32))
         if dt == F32:
             xn_lo = xn.new_empty(0)  # placeholder: callers alias x itself in fp32 mode (see _lo())
+        if lean:   # no backward follows (see _lean()): nothing to save
+            return xn, xn_lo
         ctx.rt, ctx.idx, ctx.with_skip, ctx.has_b, ctx.attn = rt, idx, with_skip, has_b, att
         ctx.chained = bool(chained)   # called from ViT.forward's block chain: the consumer of dx is our own backward node
         ctx.dims = dims
@@ -442,7 +463,7 @@ class _BlockFn(torch.autograd.Function):
         c_q, c_a = 1.0 / cfg.base_scale, 0.05 / cfg.base_scale
         pre = f"h{idx}."
         if dxn is None:
-            return (None,) * 24
+            return (None,) * 25
         dxn = dxn.contiguous()
         lo_dgrad = dt != F32
         red = ops.ReduceBatch()   # the block's six parameter-gradient reductions go out as one launch at the end
@@ -495,7 +516,7 @@ class _BlockFn(torch.autograd.Function):
         else:
             gbq = gbk = gbv = None
         return (dx, None, None, None, None, None, dskip, d_attn_alpha, d_mlp_alpha, d_sqk, d_suv, gq, gk, gv, g_wo,
-                g_wfc, g_wp, gbq, gbk, gbv, g_bo, g_bfc, g_bp, None)
+                g_wfc, g_wp, gbq, gbk, gbv, g_bo, g_bfc, g_bp, None, None)
 
 
 class _CrossFn(torch.autograd.Function):
@@ -503,7 +524,7 @@ class _CrossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, loc, glo, loc_lo, glo_lo, rt, impl, attn_alpha, sqk, wq, wk, wv, wproj, wout, bq, bk_, bv, bproj, bout,
-                chained=False):
+                chained=False, lean=False):
         cfg = rt.model.config
         dims = _dims(rt, loc.shape[0])
         B, T, C, H, d, M = dims
@@ -518,12 +539,14 @@ class _CrossFn(torch.autograd.Function):
             glo_lo = ops.cast(glo, dt) if glo_lo is None else glo_lo
         # q from the local stream, k/v from the global stream
         o, lse, att, att_saved = _attn_fwd(rt, impl, ((loc_lo, "x.q", 1), (glo_lo, "x.kv", 2)), has_b, sqk, c_q,
-                                           math.sqrt(d), dims)
-        pr, g = _swiglu_fwd(rt, o, "x.proj", M, C, C, has_b, None, None, 1.0)
+                                           math.sqrt(d), dims, lean)
+        pr, g = _swiglu_fwd(rt, o, "x.proj", M, C, C, has_b, None, None, 1.0, lean)
         y = ops.gemm_nt(g, sh["x.out.W"], M, C, C, out_dtype=rt.y_dtype(), bias=sh.get("x.out.b"))
         x, x_lo = ops.lerp_fwd(dt, loc, y, attn_alpha, c_a, want_lo=(dt != F32))
         if dt == F32:
             x_lo = x.new_empty(0)
+        if lean:
+            return x, x_lo
         ctx.rt, ctx.has_b, ctx.attn = rt, has_b, att
         ctx.chained = bool(chained)
         ctx.dims = dims
@@ -536,7 +559,7 @@ class _CrossFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dx, _unused):
         if dx is None:
-            return (None,) * 19
+            return (None,) * 20
         loc, glo, loc_lo, glo_lo, o, lse, pr, g, y, attn_alpha, sqk, *att_saved = ctx.saved_tensors
         rt = ctx.rt
         B, T, C, H, d, M = ctx.dims
@@ -567,7 +590,7 @@ class _CrossFn(torch.autograd.Function):
         red.flush()
         gbk, gbv = (g_bkv[:C], g_bkv[C:]) if ctx.has_b else (None, None)
         return (dloc, dglo, None, None, None, None, d_alpha, d_sqk, g_wq, g_wkv[:C], g_wkv[C:], g_wproj, g_wout, g_bq, gbk, gbv,
-                g_bproj, g_bout, None)
+                g_bproj, g_bout, None, None)
 
 
 class _StdBlockFn(torch.autograd.Function):
@@ -579,7 +602,7 @@ class _StdBlockFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, rt, idx, with_skip, want_lo, impl, skip_param, w_att, w_mlp, wq, wk, wv, wo, wfc, wp, bq, bk_,
-                bv, bo, bfc, bp):
+                bv, bo, bfc, bp, lean=False):
         dims = _dims(rt, x.shape[0])
         B, T, C, H, d, M = dims
         dt = rt.dt
@@ -591,12 +614,12 @@ class _StdBlockFn(torch.autograd.Function):
         if not lo:
             a_lo = a
         o, lse, att, att_saved = _attn_fwd(rt, impl, ((a_lo, pre + "qkv", 3),), has_b, None, 0.0, 1.0 / math.sqrt(d),
-                                           dims)
+                                           dims, lean)
         y = ops.gemm_nt(o, sh[pre + "o.W"], M, C, C, out_dtype=rt.y_dtype(), bias=sh.get(pre + "o.b"))
         bm, bm_lo, r_mlp = ops.res_rmsnorm_fwd(dt, a, y, w_mlp.detach(), RMS_EPS, want_lo=lo)
         if not lo:
             bm_lo = bm
-        uv, xm = _swiglu_fwd(rt, bm_lo, pre + "fc", M, 4 * C, C, has_b, None, None, 1.0)
+        uv, xm = _swiglu_fwd(rt, bm_lo, pre + "fc", M, 4 * C, C, has_b, None, None, 1.0, lean)
         if with_skip:
             y2 = ops.gemm_nt(xm, sh[pre + "p.W"], M, C, 4 * C, out_dtype=rt.y_dtype(), bias=sh.get(pre + "p.b"))
             xn, xn_lo = ops.res_skip_fwd(dt, bm, y2, skip_param.detach(), x, want_lo=(lo and want_lo))
@@ -606,6 +629,8 @@ class _StdBlockFn(torch.autograd.Function):
             xn, xn_lo = y2, (ops.cast(y2, dt) if lo and want_lo else None)
         if xn_lo is None:
             xn_lo = xn.new_empty(0)   # fp32 mode: callers alias the stream itself (see _lo())
+        if lean:
+            return xn, xn_lo
         ctx.rt, ctx.idx, ctx.with_skip, ctx.has_b, ctx.attn = rt, idx, with_skip, has_b, att
         ctx.dims = dims
         ctx.par = (skip_param, w_att, w_mlp, wq, wk, wv, wo, wfc, wp)   # gradient destinations
@@ -618,7 +643,7 @@ class _StdBlockFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dxn, _unused):
         if dxn is None:
-            return (None,) * 21
+            return (None,) * 22
         (x, a, a_lo, r_att, o, lse, y, bm, bm_lo, r_mlp, uv, xm, y2, skip_param, w_att, w_mlp,
          *att_saved) = ctx.saved_tensors
         rt, idx = ctx.rt, ctx.idx
@@ -665,7 +690,7 @@ class _StdBlockFn(torch.autograd.Function):
         else:
             gbq = gbk = gbv = None
         return (dx, None, None, None, None, None, dskip, g_watt, g_wmlp, gq, gk, gv, g_wo, g_wfc, g_wp, gbq, gbk, gbv,
-                g_bo, g_bfc, g_bp)
+                g_bo, g_bfc, g_bp, None)
 
 
 class _StdCrossFn(torch.autograd.Function):
@@ -673,7 +698,7 @@ class _StdCrossFn(torch.autograd.Function):
     inputs, attention with scale 1/sqrt(d), proj -> SwiGLU -> out_proj; the output is out_proj's result itself."""
 
     @staticmethod
-    def forward(ctx, loc, glo, rt, impl, w_ln, w_gn, wq, wk, wv, wproj, wout, bq, bk_, bv, bproj, bout):
+    def forward(ctx, loc, glo, rt, impl, w_ln, w_gn, wq, wk, wv, wproj, wout, bq, bk_, bv, bproj, bout, lean=False):
         dims = _dims(rt, loc.shape[0])
         B, T, C, H, d, M = dims
         dt = rt.dt
@@ -685,9 +710,11 @@ class _StdCrossFn(torch.autograd.Function):
         if not lo:
             ln_lo, gn_lo = ln, gn
         o, lse, att, att_saved = _attn_fwd(rt, impl, ((ln_lo, "x.q", 1), (gn_lo, "x.kv", 2)), has_b, None, 0.0,
-                                           1.0 / math.sqrt(d), dims)
-        pr, g = _swiglu_fwd(rt, o, "x.proj", M, C, C, has_b, None, None, 1.0)
+                                           1.0 / math.sqrt(d), dims, lean)
+        pr, g = _swiglu_fwd(rt, o, "x.proj", M, C, C, has_b, None, None, 1.0, lean)
         out = ops.gemm_nt(g, sh["x.out.W"], M, C, C, out_dtype=torch.float32, bias=sh.get("x.out.b"))
+        if lean:
+            return out
         ctx.rt, ctx.has_b, ctx.attn = rt, has_b, att
         ctx.dims = dims
         ctx.par = (w_ln, w_gn, wq, wk, wv, wproj, wout)
@@ -698,7 +725,7 @@ class _StdCrossFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         if dout is None:
-            return (None,) * 16
+            return (None,) * 17
         loc, glo, ln_lo, gn_lo, r_l, r_g, o, lse, pr, g, w_ln, w_gn, *att_saved = ctx.saved_tensors
         rt = ctx.rt
         B, T, C, H, d, M = ctx.dims
@@ -727,7 +754,7 @@ class _StdCrossFn(torch.autograd.Function):
         red.flush()
         gbk, gbv = (g_bkv[:C], g_bkv[C:]) if ctx.has_b else (None, None)
         return (dloc, dglo, None, None, g_wln, g_wgn, g_wq, g_wkv[:C], g_wkv[C:], g_wproj, g_wout, g_bq, gbk, gbv,
-                g_bproj, g_bout)
+                g_bproj, g_bout, None)
 
 
 class _EmbedFn(torch.autograd.Function):
@@ -965,9 +992,9 @@ class Block(nn.Module):
         model, idx = self._owner
         rt = model._rt
         if not self.config.use_nvit:
-            xn, xn_lo = _StdBlockFn.apply(x, rt, idx, with_skip, want_lo, model._attn_impl(), *self._args())
+            xn, xn_lo = _StdBlockFn.apply(x, rt, idx, with_skip, want_lo, model._attn_impl(), *self._args(), _lean())
             return xn, (_lo(rt, xn, xn_lo) if want_lo else None)
-        xn, xn_lo = _BlockFn.apply(x, x_lo, rt, idx, with_skip, model._attn_impl(), *self._args(), chained)
+        xn, xn_lo = _BlockFn.apply(x, x_lo, rt, idx, with_skip, model._attn_impl(), *self._args(), chained, _lean())
         return xn, _lo(rt, xn, xn_lo)
 
     def norm_skip(self, source: Tensor, target: Tensor) -> Tensor:
@@ -1028,8 +1055,9 @@ class CrossAttentionBlock(nn.Module):
              chained: bool = False):
         model = self._owner
         if not self.config.use_nvit:   # (the plain branch reads its RMS-normalised inputs: no operand copies needed)
-            return _StdCrossFn.apply(loc, glo, model._rt, model._attn_impl(), *self._args()), None
-        x, x_lo = _CrossFn.apply(loc, glo, loc_lo, glo_lo, model._rt, model._attn_impl(), *self._args(), chained)
+            return _StdCrossFn.apply(loc, glo, model._rt, model._attn_impl(), *self._args(), _lean()), None
+        x, x_lo = _CrossFn.apply(loc, glo, loc_lo, glo_lo, model._rt, model._attn_impl(), *self._args(), chained,
+                                 _lean())
         return x, _lo(model._rt, x, x_lo)
 
     def forward(self, local: Tensor, global_: Tensor) -> Tensor:
@@ -1228,6 +1256,12 @@ class ViT(nn.Module):
                 + self.compute_map_smoothness(global_indices, None, False))
 
     def forward(self, img: Tensor) -> Tuple[Tensor, Dict[str, Tensor]]:
+        """(logits, aux).  Under torch.no_grad / inference_mode the block functions take their forward-only route (see
+        _lean()): the same logits and aux values bit for bit, without the stores and tensors only a backward reads."""
+        return self._forward(img, True)
+
+    def _forward(self, img: Tensor, want_recon: bool) -> Tuple[Tensor, Dict[str, Tensor]]:
+        """forward(); want_recon False (evaluate.predict) leaves the reconstruction head and aux["reconstruction"] out."""
         if self.training:
             self.step += 1
         self._prepare(img.device)
@@ -1250,7 +1284,7 @@ class ViT(nn.Module):
             loc_lo = glo_lo = None
         aux: Dict[str, Tensor] = {}
         if not cfg.use_nvit:
-            return self._forward_std(img, loc, glo, aux)
+            return self._forward_std(img, loc, glo, aux, want_recon)
         if cfg.use_kohonen:
             # reference model.py:419-444
             lr = self.get_kohonen_lr(self.step)
@@ -1283,11 +1317,12 @@ class ViT(nn.Module):
                 taps[f"x{i + 1}"] = x.detach()
         logits = _HeadFn.apply(x, rt, self.mlp_head[0].weight, self.mlp_head[0].bias, self.mlp_head[1].weight,
                                self.mlp_head[1].bias, self.sz)
-        aux["reconstruction"] = _ReconFn.apply(x, x_lo, rt, img, self.reconstruction_head[0].weight,
-                                               self.reconstruction_head[0].bias)
+        if want_recon:
+            aux["reconstruction"] = _ReconFn.apply(x, x_lo, rt, img, self.reconstruction_head[0].weight,
+                                                   self.reconstruction_head[0].bias)
         return logits, aux
 
-    def _forward_std(self, img: Tensor, loc: Tensor, glo: Tensor, aux: Dict[str, Tensor]):
+    def _forward_std(self, img: Tensor, loc: Tensor, glo: Tensor, aux: Dict[str, Tensor], want_recon: bool = True):
         """Plain-ViT remainder of forward (use_nvit=False, reference model.py:446-470 without the Kohonen head)."""
         rt = self._rt
         x, _ = self.cross_attention._run(loc, glo)
@@ -1297,11 +1332,12 @@ class ViT(nn.Module):
         blocks = self.transformer.h
         x_lo = _lo(rt, x, ops.cast(x, rt.dt) if rt.dt != F32 else None) if len(blocks) == 0 else None
         for i, blk in enumerate(blocks):
-            x, x_lo = blk._run(x, None, True, want_lo=(i == len(blocks) - 1))
+            x, x_lo = blk._run(x, None, True, want_lo=(want_recon and i == len(blocks) - 1))
             if taps is not None:
                 taps[f"x{i + 1}"] = x.detach()
         logits = _HeadFn.apply(x, rt, self.mlp_head[0].weight, self.mlp_head[0].bias, self.mlp_head[1].weight,
                                self.mlp_head[1].bias, None)
-        aux["reconstruction"] = _ReconFn.apply(x, x_lo, rt, img, self.reconstruction_head[0].weight,
-                                               self.reconstruction_head[0].bias)
+        if want_recon:
+            aux["reconstruction"] = _ReconFn.apply(x, x_lo, rt, img, self.reconstruction_head[0].weight,
+                                                   self.reconstruction_head[0].bias)
         return logits, aux

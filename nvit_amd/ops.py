@@ -90,6 +90,15 @@ def gemm_nt_swiglu(A: Tensor, B: Tensor, M: int, F: int, K: int, gs: Optional[Te
     return uv, xm
 
 
+def gemm_nt_swiglu_act(A: Tensor, B: Tensor, M: int, F: int, K: int, gs: Optional[Tensor], gscale: float) -> Tensor:
+    """xm [M,F] of gemm_nt_swiglu, bit for bit, without the raw uv store (forward-only calls; bf16)."""
+    _chk_dev(A, B)
+    xm = torch.empty((M, F), device=A.device, dtype=torch.bfloat16)
+    check(_lib.load().nvit_gemm_nt_swiglu_act(dt_of(A), _p(A), A.stride(0), _p(B), B.stride(0), _p(xm), M, F, K, _p(gs),
+                                              gscale, _s()), "nvit_gemm_nt_swiglu_act")
+    return xm
+
+
 def gemm_nt_swiglu_bwd(A: Tensor, B: Tensor, uv: Tensor, M: int, F: int, K: int, gs: Optional[Tensor], gscale: float):
     """duv [M,2F] (interleaved) and the d(suv) partials from dy [M,K] and W^T [F,K] in one launch (bf16)."""
     _chk_dev(A, B, uv)
@@ -506,6 +515,18 @@ def scale_cols(a: Tensor, s: Tensor, c: float, R: int, N: int, out: Tensor, lda:
     ldo = out.stride(0) if ldo is None else ldo
     check(_lib.load().nvit_scale_cols(_p(a), lda, _p(s), c, _p(out), dt_of(out), ldo, R, N, _s()), "nvit_scale_cols")
     return out
+
+
+def eval_metrics(logits: Tensor, y: Tensor, acc: Tensor) -> None:
+    """acc[0..3] (fp32, device) += batch-mean cross-entropy, top-1 %, top-min(5,N) %, 1 - one launch, nothing read back."""
+    _chk_dev(logits, y, acc)
+    if logits.dtype != torch.float32 or y.dtype != torch.int64 or acc.dtype != torch.float32 or acc.numel() < 4:
+        raise RuntimeError("eval_metrics: fp32 logits [B,N], int64 labels [B] and an fp32 accumulator of 4 values")
+    logits, y = logits.contiguous(), y.contiguous()
+    B, N = logits.shape
+    if y.numel() != B or not acc.is_contiguous():
+        raise RuntimeError("eval_metrics: one label per row and a contiguous accumulator")
+    check(_lib.load().nvit_eval_metrics(_p(logits), _p(y), _p(acc), B, N, _s()), "nvit_eval_metrics")
 
 
 # ----------------------------------------------------------------------------- attention

@@ -75,7 +75,13 @@ def total_loss(config, logits: torch.Tensor, aux, y: torch.Tensor, consistency_w
                smoothness_weight: float = 0.1) -> torch.Tensor:
     """Loss of the reference loop (train.py:906-926): CE, plus the weighted aux losses iff the Kohonen head is on
     (consistency/smoothness weights are settings.yaml `training.*`, the others come from the model config)."""
-    loss = CrossEntropyFn.apply(logits, y)
+    return add_aux_losses(config, CrossEntropyFn.apply(logits, y), aux, consistency_weight, smoothness_weight)
+
+
+def add_aux_losses(config, loss: torch.Tensor, aux, consistency_weight: float = 0.1,
+                   smoothness_weight: float = 0.1) -> torch.Tensor:
+    """`loss` (the cross-entropy) plus the weighted aux losses iff the Kohonen head is on: the weighting of the training
+    loss (train.py:906-926) and of the reference's estimate_loss (train.py:495-502), kept in one place."""
     if config.use_kohonen:
         loss = (loss + consistency_weight * aux["kohonen_consistency"] + smoothness_weight * aux["kohonen_smoothness"]
                 + config.local_quantization_weight * aux["local_quantization"]
