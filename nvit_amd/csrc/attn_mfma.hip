@@ -1,5 +1,5 @@
-// impl 1: MFMA flash attention for gfx950 (bf16 operands, fp32 softmax/accumulate), head dim 64 (head dims 32 and 128:
-// the templated kernels in namespace hd below, same algorithm).
+// impl 1: MFMA flash attention for gfx950 (bf16 operands, fp32 softmax/accumulate), head dims 32, 64 and 128: ONE kernel set
+// (forward, dQ, dK/dV) with the head dim D a template parameter and everything that depends on it in Geo<D>.
 // Non-causal, unmasked, arbitrary (ragged) sequence lengths.
 //
 // Orientation (everything is computed "key-major" so that per-query softmax statistics are
@@ -9,32 +9,44 @@
 //   O^T[d][q]  += V^T P^T    MFMA-B = P^T taken straight from the S^T accumulators (the k index
 //                            inside one 32-deep MFMA step is permuted consistently on both
 //                            operands), MFMA-A = V^T via ds_read_b64_tr_b16 (hardware transpose)
-// One workgroup = 4 waves x 32 queries; K/V tiles of 64 keys arrive by LDS-DMA (global_load_lds, inline asm) into a
-// 3-slot ring two tiles ahead, retired by a counted vmcnt, one barrier per tile.  LDS rows are 128 B (64 bf16)
-// with the 16-byte chunk index XOR-swizzled by (row & 7): conflict-free for both the row reads and the
-// transposed reads.  At head dim 64 these kernels are VALU-ISSUE bound, not MFMA bound (rocprofv3 PMC: VALU busy
-// ~70 % + MFMA issue ~18 % of the SIMD cycles): per score the exp / scale / pack work costs about as many issue
-// cycles as its share of the two MFMAs.  What the code below does about it: the bounded-score forward path (no
-// running maximum), row constants folded into initial accumulators, scales applied once to the accumulators, tile
-// addresses in scalar registers, and no compiler-visible load left pending across the tile loop (settle()).
+// One workgroup = 4 waves x 32 queries; K/V tiles of Geo<D>::TKV keys arrive by LDS-DMA (global_load_lds, inline asm) into
+// a 3-slot ring two tiles ahead, retired by a counted vmcnt, one barrier per tile.  At head dim 64 (the training path at
+// Base / Large) these kernels are VALU-ISSUE bound, not MFMA bound (rocprofv3 PMC: VALU busy ~70 % + MFMA issue ~18 % of
+// the SIMD cycles): per score the exp / scale / pack work costs about as many issue cycles as its share of the two MFMAs.
+// What the code below does about it: the bounded-score forward path (no running maximum), row constants folded into
+// initial accumulators, scales applied once to the accumulators, tile addresses in scalar registers, and no
+// compiler-visible load left pending across the tile loop (settle()).
 //
 // Backward (recompute, two kernels, no atomics, deterministic):
 //   dq kernel : same structure as forward; per KV tile S^T, dP^T = V dO^T, dS^T = P^T(dP^T - delta),
 //               dQ^T[d][q] += K^T dS^T   (K tile read by rows for S^T and transposed for dQ^T)
-//   dkv kernel: one workgroup = 4 waves x 32 keys; loops over 64-query tiles (Q, dO, lse, delta in
+//   dkv kernel: one workgroup = 4 waves x 16 NKW keys; loops over TKV-query tiles (Q, dO, lse, delta in
 //               LDS); S[q][key] = Q K^T, dP = dO V^T (query-major, key on the lane),
 //               dV^T[d][key] += dO^T P, dK^T[d][key] += Q^T dS  (P/dS from accumulators, Q/dO
 //               tiles read by rows and transposed).
+//
+// What depends on the head dim (Geo<D>); the operand layouts, MFMA shapes, DMA machine and accumulation order (ks
+// ascending, s2 ascending, tiles ascending) are the same at every D:
+//   LDS image  D = 64: 128-byte rows, the 16-byte chunk index XOR (row & 7).
+//              D = 32: 64-byte rows, taken in pairs as one 128-byte row of the d = 64 image: chunk ((row & 1) * 4 + ch)
+//                      of "row pair" row >> 1, XOR (row >> 1) & 7.
+//              D = 128: 256-byte rows of 16 chunks, chunk XOR (bit-reversed row & 7) << 1.
+//              All three are conflict-free for the 16x16x32 row reads (ds_read_b128: one LDS cycle per 16-lane group) and
+//              for the transposed reads (ds_read_b64_tr_b16: one per 32-lane half), under the bank rule
+//              bank = (byte / 4) % 64 - checked for every (row0, chunk) the kernels read.
+//   KV tile    64 keys at D = 32 (4 KiB, one DMA piece per wave) and D = 64 (8 KiB, two pieces per wave), 32 keys at
+//              D = 128 (8 KiB, two pieces): the ring of 3 slots is 24 / 48 / 48 KiB.  A DMA piece (64 lanes x 16 B) is 16
+//              rows at D = 32, 8 at D = 64 and 4 at D = 128.
+//   dK/dV      32 keys per wave at D = 32 and 64, 16 at D = 128 (the accumulators dK^T, dV^T are 2 x D x keys / 64
+//              registers).
+//   Fragments  D / 32 k-steps of the score products, D / 16 output d-fragments.
+// d = 64 only: the fused q/k-normalise epilogues (FUSE, QkFuse) and the hand-placed dK/dV loop (nvit_attn_bwd_qknorm).
 #include <type_traits>
 
 #include "common.h"
 
 namespace {
 
-constexpr int D = 64;         // head dim
-constexpr int ROWB = D * 2;   // bytes per LDS row
-constexpr int TKV = 64;       // rows per staged tile
-constexpr int TILE_BYTES = TKV * ROWB;  // 8 KiB
 constexpr float LOG2E = 1.4426950408889634f;
 
 typedef __attribute__((address_space(3))) s16x4* lds_s16x4_ptr;
@@ -44,7 +56,57 @@ typedef __attribute__((address_space(3))) s16x4* lds_s16x4_ptr;
 // correct limit for a softmax weight)
 __device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
 
-__device__ __forceinline__ int swz_off(int row, int chunk) { return row * ROWB + ((chunk ^ (row & 7)) << 4); }
+template <int D>
+struct Geo {
+  static_assert(D == 32 || D == 64 || D == 128, "head dims 32, 64 and 128");
+  static constexpr int ROWB = D * 2;                  // bytes per row
+  static constexpr int NCH = D / 8;                   // 16-byte chunks per row
+  static constexpr int TKV = D == 128 ? 32 : 64;      // rows per staged tile
+  static constexpr int TILE_BYTES = TKV * ROWB;       // 4 / 8 / 8 KiB
+  static constexpr int TILE_DMA = TILE_BYTES / 4096;  // 1 KiB pieces (LDS-DMA wave-instructions) per wave per tile (4 waves)
+  static constexpr int NKS = D / 32;                  // k-steps of a product over d
+  static constexpr int NDF = D / 16;                  // 16-wide d-fragments
+  static constexpr int NKF = TKV / 16;                // 16-row fragments of a tile
+  static constexpr int NS2 = TKV / 32;                // 32-deep MFMA steps over a tile
+  static constexpr int NKW = D == 128 ? 1 : 2;        // dK/dV kernel: 16-key fragments per wave
+  static constexpr int KWG = 64 * NKW;                // dK/dV kernel: keys per workgroup
+  static constexpr int DKV_SLOT = 2 * TILE_BYTES + 512;   // dK/dV ring slot: Q tile | dO tile | -lse[64] | -delta[64]
+  static constexpr int DKV_DMA = 2 * TILE_DMA + 2;        // dK/dV kernel: DMA wave-instructions per wave per tile
+  // waves per SIMD (__launch_bounds__) = what the registers allow without scratch (-Rpass-analysis=kernel-resource-usage,
+  // profiles/attn_unify_resources.txt); the LDS (24-26 / 48-50 KiB per workgroup) allows more in every case.  D = 64
+  // dK/dV: 222 VGPRs; at 3 waves the kernel spills 118.
+  static constexpr int OCC_FWD = D == 32 ? 4 : D == 64 ? 3 : 2, OCC_DQ = OCC_FWD, OCC_DKV = D == 32 ? 3 : 2;
+  static_assert(TILE_DMA == 1 || TILE_DMA == 2, "one or two pieces per wave per tile");
+
+  __device__ static __forceinline__ int swz(int row) {   // D = 128: bit-reversed (row & 7), times 2
+    return ((row & 1) << 3) | ((row & 2) << 1) | ((row & 4) >> 1);
+  }
+  // byte offset of 16-byte chunk ch of row `row` in a tile
+  __device__ static __forceinline__ int off(int row, int ch) {
+    if constexpr (D == 32) {
+      const int v = row >> 1;
+      return v * 128 + (((((row & 1) << 2) | ch) ^ (v & 7)) << 4);
+    } else if constexpr (D == 64) {
+      return row * ROWB + ((ch ^ (row & 7)) << 4);
+    } else {
+      return row * ROWB + ((ch ^ swz(row)) << 4);
+    }
+  }
+  // the inverse for the DMA: lane L of 1 KiB piece p lands at p * 1024 + 16 L, which holds (row, ch)
+  __device__ static __forceinline__ void piece_lane(int p, int lane, int& row, int& ch) {
+    if constexpr (D == 32) {
+      const int v = lane >> 3, vch = (lane & 7) ^ v;   // (p * 8 + v) & 7 == v
+      row = p * 16 + 2 * v + (vch >> 2);
+      ch = vch & 3;
+    } else if constexpr (D == 64) {
+      row = p * 8 + (lane >> 3);
+      ch = (lane & 7) ^ (row & 7);
+    } else {
+      row = p * 4 + (lane >> 4);
+      ch = (lane & 15) ^ swz(row);
+    }
+  }
+};
 
 __device__ __forceinline__ f32x4 mfma16(const uint4& a, const uint4& b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
@@ -52,11 +114,12 @@ __device__ __forceinline__ f32x4 mfma16(const uint4& a, const uint4& b, f32x4 c)
 
 // transposed fragment: element j<4 = tile[row0 + 4*lg + j][col0 + l15], j>=4 = tile[row0 + 16 + 4*lg + (j-4)][..]
 // (the k-slot order matching accumulators of two adjacent 16-row MFMA tiles used as the other operand)
+template <int D>
 __device__ __forceinline__ uint4 tr_frag(const char* tile, int row0, int col0, int l15, int lg) {
   const int q = l15 >> 2, p = l15 & 3;
   const int r0 = row0 + 4 * lg + q, r1 = r0 + 16;
   const int ch = (col0 >> 3) + (p >> 1);
-  const int o0 = swz_off(r0, ch) + ((p & 1) << 3), o1 = swz_off(r1, ch) + ((p & 1) << 3);
+  const int o0 = Geo<D>::off(r0, ch) + ((p & 1) << 3), o1 = Geo<D>::off(r1, ch) + ((p & 1) << 3);
   s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(tile + o0));
   s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(tile + o1));
   uint2 l2 = __builtin_bit_cast(uint2, lo), h2 = __builtin_bit_cast(uint2, hi);
@@ -64,8 +127,30 @@ __device__ __forceinline__ uint4 tr_frag(const char* tile, int row0, int col0, i
 }
 
 // row fragment: tile[row0 + l15][32*ks + 8*lg .. +7]
+template <int D>
 __device__ __forceinline__ uint4 row_frag(const char* tile, int row0, int ks, int l15, int lg) {
-  return *reinterpret_cast<const uint4*>(tile + swz_off(row0 + l15, ks * 4 + lg));
+  return *reinterpret_cast<const uint4*>(tile + Geo<D>::off(row0 + l15, ks * 4 + lg));
+}
+
+// A 16-row group's D / 32 row fragments and the MFMA chain over them, as NAMED values with constant k-step indices - not
+// a local array filled and walked by loops over ks: with the loop form hipcc no longer folds the lane part of the
+// fragments' LDS offsets into one loop-invariant register, and every d = 64 tile loop comes out different (and the
+// backward slower).  k-steps past D / 32 are neither read nor used.
+#define NVIT_ROW_FRAGS(D_, n, tile, row0)                                                                \
+  const uint4 n##0 = row_frag<D_>(tile, row0, 0, l15, lg),                                               \
+              n##1 = Geo<D_>::NKS > 1 ? row_frag<D_>(tile, row0, 1, l15, lg) : n##0,                     \
+              n##2 = Geo<D_>::NKS > 2 ? row_frag<D_>(tile, row0, 2, l15, lg) : n##0,                     \
+              n##3 = Geo<D_>::NKS > 2 ? row_frag<D_>(tile, row0, 3, l15, lg) : n##0
+template <int NKS>
+__device__ __forceinline__ f32x4 mfma_ks(const uint4& a0, const uint4& a1, const uint4& a2, const uint4& a3,
+                                         const uint4 (&b)[NKS], f32x4 c) {
+  c = mfma16(a0, b[0], c);
+  if constexpr (NKS > 1) c = mfma16(a1, b[1], c);
+  if constexpr (NKS > 2) {
+    c = mfma16(a2, b[2], c);
+    c = mfma16(a3, b[3], c);
+  }
+  return c;
 }
 
 __device__ __forceinline__ uint4 pack8(const f32x4& a, const f32x4& b) {
@@ -78,31 +163,34 @@ __device__ __forceinline__ uint2 pack4(const f32x4& a) {
   return __builtin_bit_cast(uint2, v);
 }
 
-// Store a wave's [32 rows x 64] result held in accumulator layout (g[df][f][r] = out[row 16f + l15][col 16df + 4lg + r])
-// as bf16 rows of 128 bytes: through a wave-private 4 KiB LDS scratch (XOR-swizzled like the K/V tiles) so that every
-// global store instruction writes whole 128-byte rows, 16 bytes per lane (4 instructions per wave), instead of eight
+// Store a wave's [16 NF rows x D] result held in accumulator layout (g[df][f][r] = out[row 16f + l15][col 16df + 4lg + r])
+// as bf16 rows: through a wave-private LDS scratch of 16 NF rows (the tile image, swizzled like the K/V tiles) so that every
+// global store instruction writes whole rows, 16 bytes per lane (4 instructions per wave at 32 x 64), instead of eight
 // instructions of 8-byte pieces that each touch a quarter of 16 different rows.  dst -> element (row 0, col 0) of the
 // tile, ld = row stride in elements, rows >= nvalid are not written.
-__device__ __forceinline__ void store_tile32x64(const f32x4 (&g)[4][2], char* scr, bf16* dst, size_t ld, int nvalid,
-                                                int lane) {
+template <int D, int NF>
+__device__ __forceinline__ void store_tile(const f32x4 (&g)[D / 16][NF], char* scr, bf16* dst, size_t ld, int nvalid,
+                                           int lane) {
+  using G = Geo<D>;
   const int l15 = lane & 15, lg = lane >> 4;
 #pragma unroll
-  for (int f = 0; f < 2; ++f)
+  for (int f = 0; f < NF; ++f)
 #pragma unroll
-    for (int df = 0; df < 4; ++df)
-      *reinterpret_cast<uint2*>(scr + swz_off(16 * f + l15, 2 * df + (lg >> 1)) + 8 * (lg & 1)) = pack4(g[df][f]);
+    for (int df = 0; df < G::NDF; ++df)
+      *reinterpret_cast<uint2*>(scr + G::off(16 * f + l15, 2 * df + (lg >> 1)) + 8 * (lg & 1)) = pack4(g[df][f]);
   __builtin_amdgcn_wave_barrier();   // DS instructions of one wave execute in order; this only pins the compiler
+  constexpr int RPP = 64 / G::NCH, LOG_NCH = D == 32 ? 2 : D == 64 ? 3 : 4;   // rows per pass; NCH = 1 << LOG_NCH
 #pragma unroll
-  for (int pass = 0; pass < 4; ++pass) {
-    const int row = pass * 8 + (lane >> 3), chunk = lane & 7;
-    const uint4 v = *reinterpret_cast<const uint4*>(scr + swz_off(row, chunk));
+  for (int pass = 0; pass < 16 * NF / RPP; ++pass) {
+    const int row = pass * RPP + (lane >> LOG_NCH), chunk = lane & (G::NCH - 1);
+    const uint4 v = *reinterpret_cast<const uint4*>(scr + G::off(row, chunk));
     if (row < nvalid) *reinterpret_cast<uint4*>(dst + (size_t)row * ld + chunk * 8) = v;
   }
 }
 
 // LDS-DMA staging (global_load_lds_dwordx4 from inline asm, see gemm_common.h for why): lane L lands at
-// lds_off + 16*L.  One wave-instruction = 8 rows of a 128-byte-row tile; the XOR swizzle is realised by
-// fetching chunk (L&7) ^ (row&7).
+// lds_off + 16*L.  One wave-instruction = one 1 KiB piece of a tile (8 rows of a 128-byte-row tile); the swizzle is
+// realised by fetching the (row, chunk) that Geo<D>::piece_lane names for the lane.
 // The source address is split into a wave-uniform 64-bit base (SGPR pair) and a 32-bit per-lane byte offset:
 // the per-tile part of the address (which tile) then lives in scalar registers and costs no VALU issue slots - these
 // kernels are VALU-issue bound (PMC: VALU + MFMA issue ~ 87 % of the SIMD cycles), so address arithmetic is not free.
@@ -136,28 +224,50 @@ __device__ __forceinline__ void glds16s_pair(const void* sbase, unsigned voff0, 
       : "v"(voff0), "v"(voff1), "s"(sb), "s"(m)
       : "memory", "scc");
 }
-// DMA one 64-row tile of `src` (row stride ld_bytes, rows clamped to nrows-1) to LDS byte offset tile_off;
-// 4 waves x 2 wave-instructions.  TILE_DMA = instructions per wave per tile.  `src`, row_base and nrows are wave
-// uniform; voff[i] = tile_voff(i, ...) are the lane's offsets inside a full tile, computed once per kernel.
-constexpr int TILE_DMA = 2;
+// DMA one TKV-row tile of `src` (row stride ld_bytes, rows clamped to nrows-1) to LDS byte offset tile_off;
+// 4 waves x TILE_DMA wave-instructions (piece i * 4 + wid).  `src`, row_base and nrows are wave uniform;
+// voff[i] = tile_voff(i, ...) are the lane's offsets inside a full tile, computed once per kernel.
+// (D = 64 keeps the statement order these helpers had before the head dim became a parameter - lane terms first, the
+//  piece index last - instead of going through piece_lane: the same values, but hipcc then builds the kernel prologues
+//  as it did, profiles/attn_unify_resources.txt.  voff arrays have two entries at every D; the second is 0 and unused
+//  where a wave has one piece per tile.)
+template <int D>
 __device__ __forceinline__ unsigned tile_voff(int i, unsigned ld_bytes, int lane, int wid) {
-  const int r8 = lane >> 3, chunk = (lane & 7) ^ r8;
-  return (unsigned)((i * 4 + wid) * 8 + r8) * ld_bytes + (unsigned)chunk * 16u;
-}
-__device__ __forceinline__ void tile_dma(const bf16* src, unsigned ld_bytes, int row_base, int nrows, unsigned tile_off,
-                                         int lane, int wid, const unsigned (&voff)[TILE_DMA]) {
-  const char* sb = reinterpret_cast<const char*>(src) + (size_t)row_base * ld_bytes;
-  if (row_base + TKV <= nrows) {
-    static_assert(TILE_DMA == 2, "glds16s_pair issues the tile's two pieces");
-    glds16s_pair(sb, voff[0], voff[1], tile_off + wid * 1024);
-  } else {   // ragged last tile: rows past the end re-read the last valid row (finite values, masked by the consumer)
+  if constexpr (D == 64) {
     const int r8 = lane >> 3, chunk = (lane & 7) ^ r8;
+    return (unsigned)((i * 4 + wid) * 8 + r8) * ld_bytes + (unsigned)chunk * 16u;
+  } else {
+    int row, ch;
+    Geo<D>::piece_lane(i * 4 + wid, lane, row, ch);
+    return (unsigned)row * ld_bytes + (unsigned)ch * 16u;
+  }
+}
+template <int D>
+__device__ __forceinline__ void tile_dma(const bf16* src, unsigned ld_bytes, int row_base, int nrows, unsigned tile_off,
+                                         int lane, int wid, const unsigned (&voff)[2]) {
+  using G = Geo<D>;
+  const char* sb = reinterpret_cast<const char*>(src) + (size_t)row_base * ld_bytes;
+  if (row_base + G::TKV <= nrows) {
+    if constexpr (G::TILE_DMA == 2)
+      glds16s_pair(sb, voff[0], voff[1], tile_off + wid * 1024);   // pieces wid and 4 + wid: 4 KiB apart
+    else
+      glds16s(sb, voff[0], tile_off + wid * 1024);
+  } else if constexpr (D == 64) {   // ragged last tile: rows past the end re-read the last valid row (finite values,
+    const int r8 = lane >> 3, chunk = (lane & 7) ^ r8;   // masked by the consumer)
 #pragma unroll
-    for (int i = 0; i < TILE_DMA; ++i) {
+    for (int i = 0; i < G::TILE_DMA; ++i) {
       const int grp = i * 4 + wid;
       int row = grp * 8 + r8;
       row = row_base + row < nrows ? row : nrows - 1 - row_base;
       glds16s(sb, (unsigned)row * ld_bytes + (unsigned)chunk * 16u, tile_off + grp * 1024);
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < G::TILE_DMA; ++i) {
+      int row, ch;
+      G::piece_lane(i * 4 + wid, lane, row, ch);
+      row = row_base + row < nrows ? row : nrows - 1 - row_base;
+      glds16s(sb, (unsigned)row * ld_bytes + (unsigned)ch * 16u, tile_off + (i * 4 + wid) * 1024);
     }
   }
 }
@@ -198,12 +308,16 @@ __device__ __forceinline__ void work_of(int ntile, int& bh, int& tile) {
 // softmax below runs.
 constexpr float BOUND_MAX = 60.0f;   // in log2 units: exp2(-2*60) is still a normal fp32 / bf16 number
 
-__global__ __launch_bounds__(256, 3) void attn_fwd_mfma_kernel(const bf16* __restrict__ qh, const bf16* __restrict__ kh,
+template <int D>
+__global__ __launch_bounds__(256, Geo<D>::OCC_FWD) void attn_fwd_mfma_kernel(const bf16* __restrict__ qh, const bf16* __restrict__ kh,
                                                              const bf16* __restrict__ vh, float scale, float qpre,
                                                              const float* __restrict__ sqk, float c_q,
                                                              bf16* __restrict__ o, float* __restrict__ lse, int H,
                                                              int Tq, int Tk) {
+  using G = Geo<D>;
+  constexpr int ROWB = G::ROWB, TKV = G::TKV, TILE_BYTES = G::TILE_BYTES, TILE_DMA = G::TILE_DMA;
   __shared__ __attribute__((aligned(16))) char lds[3][2][TILE_BYTES];  // ring [slot][K|V]
+  static_assert(sizeof(lds) >= 4 * 32 * ROWB, "the ring doubles as the output store scratch");
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int l15 = lane & 15, lg = lane >> 4;
   int bh, tile_;
@@ -219,17 +333,23 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_mfma_kernel(const bf16* __res
   const float c2 = c2t / qpre;
   const bool unit = __builtin_amdgcn_readfirstlane(fabsf(c2 - 1.0f) < 1e-6f ? 1 : 0) != 0;
 
-  uint4 qf[2][2];
-  f32x4 oacc[4][2];
+  uint4 qf[2][G::NKS];
+  f32x4 oacc[G::NDF][2];
 #pragma unroll
-  for (int i = 0; i < 4; ++i)
+  for (int i = 0; i < G::NDF; ++i)
 #pragma unroll
     for (int f = 0; f < 2; ++f) oacc[i][f] = (f32x4){0.f, 0.f, 0.f, 0.f};
   float m_[2] = {-INFINITY, -INFINITY}, l_[2] = {0.f, 0.f};
   // score bound of this head in log2 units (fast path) - wave-uniform
   float tb = INFINITY;
-  if (sqk) {
-    float sm = fabsf(sqk[h * D + lane] * c_q);
+  if (sqk) {   // the head's max |s_d| over one wave: lanes >= 32 hold no channel at D = 32, two channels at D = 128
+    float sm;
+    if constexpr (D == 32)
+      sm = lane < 32 ? fabsf(sqk[h * D + lane] * c_q) : 0.f;
+    else if constexpr (D == 64)
+      sm = fabsf(sqk[h * D + lane] * c_q);
+    else
+      sm = fmaxf(fabsf(sqk[h * D + lane] * c_q), fabsf(sqk[h * D + 64 + lane] * c_q));
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) sm = fmaxf(sm, __shfl_xor(sm, off, 64));
     tb = c2t * sm * sm;
@@ -239,14 +359,14 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_mfma_kernel(const bf16* __res
   const uint4 ones = make_uint4(0x3F803F80u, 0x3F803F80u, 0x3F803F80u, 0x3F803F80u);   // 8 x bf16 1.0
 
   const int nt = (Tk + TKV - 1) / TKV;
-  // K/V ring: LDS-DMA two tiles ahead, counted vmcnt (4 younger DMA instructions may stay in flight)
+  // K/V ring: LDS-DMA two tiles ahead, counted vmcnt (the 2 TILE_DMA younger DMA instructions may stay in flight)
   const unsigned ring = lds_addr(&lds[0][0][0]);
-  const unsigned voff[TILE_DMA] = {tile_voff(0, ROWB, lane, wid), tile_voff(1, ROWB, lane, wid)};
-  tile_dma(kbase, ROWB, 0, Tk, ring, lane, wid, voff);
-  tile_dma(vbase, ROWB, 0, Tk, ring + TILE_BYTES, lane, wid, voff);
+  const unsigned voff[2] = {tile_voff<D>(0, ROWB, lane, wid), TILE_DMA == 2 ? tile_voff<D>(1, ROWB, lane, wid) : 0u};
+  tile_dma<D>(kbase, ROWB, 0, Tk, ring, lane, wid, voff);
+  tile_dma<D>(vbase, ROWB, 0, Tk, ring + TILE_BYTES, lane, wid, voff);
   if (nt > 1) {
-    tile_dma(kbase, ROWB, TKV, Tk, ring + 2 * TILE_BYTES, lane, wid, voff);
-    tile_dma(vbase, ROWB, TKV, Tk, ring + 3 * TILE_BYTES, lane, wid, voff);
+    tile_dma<D>(kbase, ROWB, TKV, Tk, ring + 2 * TILE_BYTES, lane, wid, voff);
+    tile_dma<D>(vbase, ROWB, TKV, Tk, ring + 3 * TILE_BYTES, lane, wid, voff);
   }
   // the wave's own Q rows: requested AFTER the DMA (one memory round trip for everything) and settled before the loop
 #pragma unroll
@@ -254,13 +374,13 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_mfma_kernel(const bf16* __res
     int q = q0 + 16 * f + l15;
     q = q < Tq ? q : Tq - 1;
 #pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
+    for (int ks = 0; ks < G::NKS; ++ks)
       qf[f][ks] = *reinterpret_cast<const uint4*>(qh + ((size_t)bh * Tq + q) * D + ks * 32 + lg * 8);
   }
 #pragma unroll
   for (int f = 0; f < 2; ++f)
 #pragma unroll
-    for (int ks = 0; ks < 2; ++ks) settle(qf[f][ks]);
+    for (int ks = 0; ks < G::NKS; ++ks) settle(qf[f][ks]);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (the compiler's own wait above already drained the queue)
   __syncthreads();
   int cur = 0;
@@ -276,28 +396,27 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_mfma_kernel(const bf16* __res
     constexpr bool UNIT = decltype(unit_)::value;
     if (t + 2 < nt) {
       const int sl = cur == 0 ? 2 : cur - 1;  // (t + 2) % 3
-      tile_dma(kbase, ROWB, (t + 2) * TKV, Tk, ring + (2 * sl) * TILE_BYTES, lane, wid, voff);
-      tile_dma(vbase, ROWB, (t + 2) * TKV, Tk, ring + (2 * sl + 1) * TILE_BYTES, lane, wid, voff);
+      tile_dma<D>(kbase, ROWB, (t + 2) * TKV, Tk, ring + (2 * sl) * TILE_BYTES, lane, wid, voff);
+      tile_dma<D>(vbase, ROWB, (t + 2) * TKV, Tk, ring + (2 * sl + 1) * TILE_BYTES, lane, wid, voff);
     }
     if (wave_active && FAST) {
       const char* kt = &lds[cur][0][0];
       const char* vt = &lds[cur][1][0];
       const int nvalid = MASKED ? Tk - t * TKV : TKV;
-      const int nkf = MASKED ? (nvalid + 15) >> 4 : 4, ns2 = MASKED ? (nvalid + 31) >> 5 : 2;
-      uint4 pf[2][2];  // [s2][f]
+      const int nkf = MASKED ? (nvalid + 15) >> 4 : G::NKF, ns2 = MASKED ? (nvalid + 31) >> 5 : G::NS2;
+      uint4 pf[G::NS2][2];  // [s2][f]
 #pragma unroll
-      for (int s2 = 0; s2 < 2; ++s2) {
+      for (int s2 = 0; s2 < G::NS2; ++s2) {
         f32x4 p_[2][2];   // [kk][f], key fragment kf = 2*s2 + kk
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk) {
           const int kf = 2 * s2 + kk;
           if (!MASKED || kf < nkf) {
-            const uint4 a0 = row_frag(kt, kf * 16, 0, l15, lg), a1 = row_frag(kt, kf * 16, 1, l15, lg);
+            NVIT_ROW_FRAGS(D, a, kt, kf * 16);
 #pragma unroll
             for (int f = 0; f < 2; ++f) {
               f32x4 z = UNIT ? ntb : (f32x4){0.f, 0.f, 0.f, 0.f};
-              z = mfma16(a0, qf[f][0], z);
-              z = mfma16(a1, qf[f][1], z);
+              z = mfma_ks(a0, a1, a2, a3, qf[f], z);
 #pragma unroll
               for (int r = 0; r < 4; ++r) {
                 float p = UNIT ? fast_exp2(z[r]) : fast_exp2(z[r] * c2 - tb);
@@ -315,13 +434,13 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_mfma_kernel(const bf16* __res
       }
       // O^T[df][f] += V^T P^T, and the row sums l[f] += 1^T P^T
 #pragma unroll
-      for (int s2 = 0; s2 < 2; ++s2)
+      for (int s2 = 0; s2 < G::NS2; ++s2)
         if (!MASKED || s2 < ns2) {
 #pragma unroll
           for (int f = 0; f < 2; ++f) lacc[f] = mfma16(ones, pf[s2][f], lacc[f]);
 #pragma unroll
-          for (int df = 0; df < 4; ++df) {
-            const uint4 va = tr_frag(vt, s2 * 32, df * 16, l15, lg);
+          for (int df = 0; df < G::NDF; ++df) {
+            const uint4 va = tr_frag<D>(vt, s2 * 32, df * 16, l15, lg);
 #pragma unroll
             for (int f = 0; f < 2; ++f) oacc[df][f] = mfma16(va, pf[s2][f], oacc[df][f]);
           }
@@ -332,19 +451,15 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_mfma_kernel(const bf16* __res
       const char* vt = &lds[cur][1][0];
       const int kbase_i = t * TKV;
       const int nvalid = MASKED ? Tk - kbase_i : TKV;
-      const int nkf = MASKED ? (nvalid + 15) >> 4 : 4, ns2 = MASKED ? (nvalid + 31) >> 5 : 2;
+      const int nkf = MASKED ? (nvalid + 15) >> 4 : G::NKF, ns2 = MASKED ? (nvalid + 31) >> 5 : G::NS2;
       // S^T[kf][f] : rows = key 16kf + 4lg + r, col = query 16f + l15
-      f32x4 s[4][2];
+      f32x4 s[G::NKF][2];
 #pragma unroll
-      for (int kf = 0; kf < 4; ++kf) {
+      for (int kf = 0; kf < G::NKF; ++kf) {
         if (!MASKED || kf < nkf) {
-          const uint4 a0 = row_frag(kt, kf * 16, 0, l15, lg), a1 = row_frag(kt, kf * 16, 1, l15, lg);
+          NVIT_ROW_FRAGS(D, a, kt, kf * 16);
 #pragma unroll
-          for (int f = 0; f < 2; ++f) {
-            f32x4 z = {0.f, 0.f, 0.f, 0.f};
-            z = mfma16(a0, qf[f][0], z);
-            s[kf][f] = mfma16(a1, qf[f][1], z);
-          }
+          for (int f = 0; f < 2; ++f) s[kf][f] = mfma_ks(a0, a1, a2, a3, qf[f], (f32x4){0.f, 0.f, 0.f, 0.f});
           if constexpr (MASKED) {
 #pragma unroll
             for (int r = 0; r < 4; ++r)
@@ -358,12 +473,12 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_mfma_kernel(const bf16* __res
           s[kf][1] = s[kf][0];
         }
       }
-      uint4 pf[2][2];  // [s2][f]
+      uint4 pf[G::NS2][2];  // [s2][f]
 #pragma unroll
       for (int f = 0; f < 2; ++f) {
         float mt = -INFINITY;
 #pragma unroll
-        for (int kf = 0; kf < 4; ++kf)
+        for (int kf = 0; kf < G::NKF; ++kf)
           if (!MASKED || kf < nkf) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) mt = fmaxf(mt, s[kf][f][r]);
@@ -376,7 +491,7 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_mfma_kernel(const bf16* __res
         const float mc = mn * c2;
         float rs = 0.f;
 #pragma unroll
-        for (int kf = 0; kf < 4; ++kf)
+        for (int kf = 0; kf < G::NKF; ++kf)
           if (!MASKED || kf < nkf) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -387,23 +502,23 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_mfma_kernel(const bf16* __res
           }
         l_[f] = l_[f] * corr + rs;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) oacc[i][f] = oacc[i][f] * corr;
-        pf[0][f] = pack8(s[0][f], s[1][f]);
-        pf[1][f] = pack8(s[2][f], s[3][f]);
+        for (int i = 0; i < G::NDF; ++i) oacc[i][f] = oacc[i][f] * corr;
+#pragma unroll
+        for (int s2 = 0; s2 < G::NS2; ++s2) pf[s2][f] = pack8(s[2 * s2][f], s[2 * s2 + 1][f]);
       }
       // O^T[df][f] += V^T P^T
 #pragma unroll
-      for (int df = 0; df < 4; ++df)
+      for (int df = 0; df < G::NDF; ++df)
 #pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2)
+        for (int s2 = 0; s2 < G::NS2; ++s2)
           if (!MASKED || s2 < ns2) {
-            const uint4 va = tr_frag(vt, s2 * 32, df * 16, l15, lg);
+            const uint4 va = tr_frag<D>(vt, s2 * 32, df * 16, l15, lg);
 #pragma unroll
             for (int f = 0; f < 2; ++f) oacc[df][f] = mfma16(va, pf[s2][f], oacc[df][f]);
           }
     }
     if (t + 2 < nt)
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4) : "memory");
+      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * TILE_DMA) : "memory");
     else
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -441,16 +556,17 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_mfma_kernel(const bf16* __res
     const int q = q0 + 16 * f + l15;
     const float inv = 1.0f / l;
 #pragma unroll
-    for (int df = 0; df < 4; ++df) oacc[df][f] = oacc[df][f] * inv;
+    for (int df = 0; df < G::NDF; ++df) oacc[df][f] = oacc[df][f] * inv;
     if (q < Tq && lg == 0) lse[(size_t)bh * Tq + q] = lse_v;
   }
-  if (wave_active)   // (the tile loop ended with a barrier: the ring is free, each wave takes 4 KiB of it as scratch)
-    store_tile32x64(oacc, &lds[0][0][0] + wid * 4096, o + ((size_t)b * Tq + q0) * (H * D) + h * D, (size_t)H * D, Tq - q0,
-                    lane);
+  if (wave_active)   // (the tile loop ended with a barrier: the ring is free, each wave takes 32 rows of it as scratch)
+    store_tile<D, 2>(oacc, &lds[0][0][0] + wid * 32 * ROWB, o + ((size_t)b * Tq + q0) * (H * D) + h * D, (size_t)H * D,
+                     Tq - q0, lane);
 }
 
 // Fused backward of  x_hat = (sqk*c_q) * x/||x||  (reference model.py:108-112) in the epilogue of the attention
-// backward kernels: g = dL/dx_hat in the accumulator layout (row = row0 + 16f + l15, d = 16df + 4lg + r).
+// backward kernels, written for 64-wide heads (FUSE is instantiated at D = 64 only):
+// g = dL/dx_hat in the accumulator layout (row = row0 + 16f + l15, d = 16df + 4lg + r).
 // Writes dL/dx (bf16, token-major) and this workgroup's partial sums of dL/d(sqk*c_q) for its head.
 // sqk == NULL (plain-ViT heads, no normalise): g is stored as it is - dL/dx of the split projection output, token-major -
 // and rn, part, c_q are not used.
@@ -507,7 +623,7 @@ __device__ __forceinline__ void qk_bwd_epilogue(f32x4 (&g)[4][2], const QkEpiLoa
   // lds0: the (now idle) tile ring; bytes [4096*wid, +4096) = this wave's store scratch, [16384, +1024) = column sums
   if (!fu.sqk) {   // plain heads (uniform over the workgroup: no barrier below is skipped by part of it)
     if (row0 < T)
-      store_tile32x64(g, lds0 + wid * 4096, fu.out + ((size_t)b * T + row0) * fu.ld + h * 64, (size_t)fu.ld, T - row0, lane);
+      store_tile<64, 2>(g, lds0 + wid * 4096, fu.out + ((size_t)b * T + row0) * fu.ld + h * 64, (size_t)fu.ld, T - row0, lane);
     return;
   }
   const int l15 = lane & 15, lg = lane >> 4;
@@ -540,7 +656,7 @@ __device__ __forceinline__ void qk_bwd_epilogue(f32x4 (&g)[4][2], const QkEpiLoa
     for (int df = 0; df < 4; ++df) outv[df][f] = (sg[df] - n[df] * dot) * L.rn[f];
   }
   if (row0 < T)
-    store_tile32x64(outv, lds0 + wid * 4096, fu.out + ((size_t)b * T + row0) * fu.ld + h * 64, (size_t)fu.ld, T - row0, lane);
+    store_tile<64, 2>(outv, lds0 + wid * 4096, fu.out + ((size_t)b * T + row0) * fu.ld + h * 64, (size_t)fu.ld, T - row0, lane);
   // column sums over this workgroup's 128 rows: 16 lanes (l15) -> 4 waves -> one partial row.  The 16-lane step is the
   // butterfly (lane ^ 1, ^ 2, ^ 4, ^ 8) as DPP row exchanges - quad swaps, then the half-row and the row mirrored, which
   // pair the same partial sums as the xor pattern does (the bits are those of the butterfly: a + b == b + a) - so it costs
@@ -567,8 +683,8 @@ __device__ __forceinline__ void qk_bwd_epilogue(f32x4 (&g)[4][2], const QkEpiLoa
 }
 
 // ------------------------------------------------------------------------------------------ dQ
-template <bool FUSE>
-__global__ __launch_bounds__(256, 3) void attn_bwd_dq_mfma_kernel(const bf16* __restrict__ dout, const bf16* __restrict__ qh,
+template <int D, bool FUSE>
+__global__ __launch_bounds__(256, Geo<D>::OCC_DQ) void attn_bwd_dq_mfma_kernel(const bf16* __restrict__ dout, const bf16* __restrict__ qh,
                                                                 const bf16* __restrict__ kh, const bf16* __restrict__ vh,
                                                                 const float* __restrict__ lse,
                                                                 const bf16* __restrict__ og, float* __restrict__ delta,
@@ -577,7 +693,11 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_mfma_kernel(const bf16* __
   // This kernel also produces delta[bh][q] = <dO_q, O_q> (the softmax-backward row term) from the attention output `og`
   // (token-major like dout) and stores it, with lse in log2 units, in the [2,B,H,Tq] side buffer for the dk/dv kernel,
   // which runs after it.  (og == NULL: delta is an input and no side buffer is written - not used by the launchers.)
+  static_assert(!FUSE || D == 64, "the fused q/k-normalise epilogue is written for 64-wide heads");
+  using G = Geo<D>;
+  constexpr int ROWB = G::ROWB, TKV = G::TKV, TILE_BYTES = G::TILE_BYTES, TILE_DMA = G::TILE_DMA;
   __shared__ __attribute__((aligned(16))) char lds[3][2][TILE_BYTES];
+  static_assert(sizeof(lds) >= 4 * 32 * ROWB, "the ring doubles as the output store scratch");
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int l15 = lane & 15, lg = lane >> 4;
   int bh, tile_;
@@ -589,18 +709,18 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_mfma_kernel(const bf16* __
   const float c2 = scale * LOG2E / qpre;   // see the forward kernel: 1 when q was pre-scaled by scale * log2(e)
   const bool unit = __builtin_amdgcn_readfirstlane(fabsf(c2 - 1.0f) < 1e-6f ? 1 : 0) != 0;
 
-  uint4 qf[2][2], gf[2][2];
+  uint4 qf[2][G::NKS], gf[2][G::NKS];
   float lse2[2], dl[2];
   const int nt = (Tk + TKV - 1) / TKV;
-  // K/V ring: LDS-DMA two tiles ahead, counted vmcnt (4 younger DMA instructions may stay in flight); the prologue
+  // K/V ring: LDS-DMA two tiles ahead, counted vmcnt (2 TILE_DMA younger DMA instructions may stay in flight); the prologue
   // DMA goes out first, the wave's own rows after it, and everything is settled before the tile loop (see settle())
   const unsigned ring = lds_addr(&lds[0][0][0]);
-  const unsigned voff[TILE_DMA] = {tile_voff(0, ROWB, lane, wid), tile_voff(1, ROWB, lane, wid)};
-  tile_dma(kbase, ROWB, 0, Tk, ring, lane, wid, voff);
-  tile_dma(vbase, ROWB, 0, Tk, ring + TILE_BYTES, lane, wid, voff);
+  const unsigned voff[2] = {tile_voff<D>(0, ROWB, lane, wid), TILE_DMA == 2 ? tile_voff<D>(1, ROWB, lane, wid) : 0u};
+  tile_dma<D>(kbase, ROWB, 0, Tk, ring, lane, wid, voff);
+  tile_dma<D>(vbase, ROWB, 0, Tk, ring + TILE_BYTES, lane, wid, voff);
   if (nt > 1) {
-    tile_dma(kbase, ROWB, TKV, Tk, ring + 2 * TILE_BYTES, lane, wid, voff);
-    tile_dma(vbase, ROWB, TKV, Tk, ring + 3 * TILE_BYTES, lane, wid, voff);
+    tile_dma<D>(kbase, ROWB, TKV, Tk, ring + 2 * TILE_BYTES, lane, wid, voff);
+    tile_dma<D>(vbase, ROWB, TKV, Tk, ring + 3 * TILE_BYTES, lane, wid, voff);
   }
 #pragma unroll
   for (int f = 0; f < 2; ++f) {
@@ -608,20 +728,20 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_mfma_kernel(const bf16* __
     const int q = qu < Tq ? qu : Tq - 1;
     lse2[f] = lse[(size_t)bh * Tq + q] * LOG2E;
 #pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
+    for (int ks = 0; ks < G::NKS; ++ks) {
       qf[f][ks] = *reinterpret_cast<const uint4*>(qh + ((size_t)bh * Tq + q) * D + ks * 32 + lg * 8);
       gf[f][ks] = *reinterpret_cast<const uint4*>(dout + ((size_t)b * Tq + q) * (H * D) + h * D + ks * 32 + lg * 8);
     }
     if (og) {
       float part = 0.f;
 #pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
+      for (int ks = 0; ks < G::NKS; ++ks) {
         const uint4 of = *reinterpret_cast<const uint4*>(og + ((size_t)b * Tq + q) * (H * D) + h * D + ks * 32 + lg * 8);
         const bf16x8 a = __builtin_bit_cast(bf16x8, gf[f][ks]), c = __builtin_bit_cast(bf16x8, of);
 #pragma unroll
         for (int e = 0; e < 8; ++e) part += (float)a[e] * (float)c[e];
       }
-      part += __shfl_xor(part, 16, 64);   // the row's 64 columns live on the 4 lanes l15 + 16*lg
+      part += __shfl_xor(part, 16, 64);   // the row's D columns live on the 4 lanes l15 + 16*lg
       part += __shfl_xor(part, 32, 64);
       dl[f] = part;
       if (lg == 0 && qu < Tq) {
@@ -633,9 +753,9 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_mfma_kernel(const bf16* __
       dl[f] = -delta[(size_t)bh * Tq + q];
     }
   }
-  f32x4 dq[4][2];
+  f32x4 dq[G::NDF][2];
 #pragma unroll
-  for (int i = 0; i < 4; ++i)
+  for (int i = 0; i < G::NDF; ++i)
 #pragma unroll
     for (int f = 0; f < 2; ++f) dq[i][f] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -643,7 +763,7 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_mfma_kernel(const bf16* __
     settle(lse2[f]);
     settle(dl[f]);
 #pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
+    for (int ks = 0; ks < G::NKS; ++ks) {
       settle(qf[f][ks]);
       settle(gf[f][ks]);
     }
@@ -666,33 +786,31 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_mfma_kernel(const bf16* __
     constexpr bool UNIT = decltype(unit_)::value;
     if (t + 2 < nt) {
       const int sl = cur == 0 ? 2 : cur - 1;  // (t + 2) % 3
-      tile_dma(kbase, ROWB, (t + 2) * TKV, Tk, ring + (2 * sl) * TILE_BYTES, lane, wid, voff);
-      tile_dma(vbase, ROWB, (t + 2) * TKV, Tk, ring + (2 * sl + 1) * TILE_BYTES, lane, wid, voff);
+      tile_dma<D>(kbase, ROWB, (t + 2) * TKV, Tk, ring + (2 * sl) * TILE_BYTES, lane, wid, voff);
+      tile_dma<D>(vbase, ROWB, (t + 2) * TKV, Tk, ring + (2 * sl + 1) * TILE_BYTES, lane, wid, voff);
     }
     if (wave_active) {
       const char* kt = &lds[cur][0][0];
       const char* vt = &lds[cur][1][0];
       const int kbase_i = t * TKV;
       const int nvalid = MASKED ? Tk - kbase_i : TKV;
-      const int nkf = MASKED ? (nvalid + 15) >> 4 : 4, ns2 = MASKED ? (nvalid + 31) >> 5 : 2;
-      uint4 dsf[2][2];  // [s2][f]
+      const int nkf = MASKED ? (nvalid + 15) >> 4 : G::NKF, ns2 = MASKED ? (nvalid + 31) >> 5 : G::NS2;
+      uint4 dsf[G::NS2][2];  // [s2][f]
 #pragma unroll
-      for (int s2 = 0; s2 < 2; ++s2) {
+      for (int s2 = 0; s2 < G::NS2; ++s2) {
         if (!MASKED || s2 < ns2) {
           f32x4 ds_[2][2];  // [kk][f] for key frags kf = 2*s2 + kk
 #pragma unroll
           for (int kk = 0; kk < 2; ++kk) {
             const int kf = 2 * s2 + kk;
             if (!MASKED || kf < nkf) {
-              const uint4 a0 = row_frag(kt, kf * 16, 0, l15, lg), a1 = row_frag(kt, kf * 16, 1, l15, lg);
-              const uint4 v0 = row_frag(vt, kf * 16, 0, l15, lg), v1 = row_frag(vt, kf * 16, 1, l15, lg);
+              NVIT_ROW_FRAGS(D, a, kt, kf * 16);
+              NVIT_ROW_FRAGS(D, v, vt, kf * 16);
 #pragma unroll
               for (int f = 0; f < 2; ++f) {
                 f32x4 z = UNIT ? nls[f] : (f32x4){0.f, 0.f, 0.f, 0.f};
-                z = mfma16(a0, qf[f][0], z);
-                z = mfma16(a1, qf[f][1], z);  // S^T (UNIT: already minus lse, in log2 units)
-                f32x4 w = mfma16(v0, gf[f][0], ndl[f]);        // row constant -delta as the initial accumulator
-                w = mfma16(v1, gf[f][1], w);  // dP^T - delta
+                z = mfma_ks(a0, a1, a2, a3, qf[f], z);   // S^T (UNIT: already minus lse, in log2 units)
+                const f32x4 w = mfma_ks(v0, v1, v2, v3, gf[f], ndl[f]);   // dP^T - delta (-delta is the initial accumulator)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                   const bool valid = !MASKED || (kf * 16 + lg * 4 + r) < nvalid;
@@ -711,17 +829,17 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_mfma_kernel(const bf16* __
       }
       // dQ^T[df][f] += K^T dS^T
 #pragma unroll
-      for (int df = 0; df < 4; ++df)
+      for (int df = 0; df < G::NDF; ++df)
 #pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2)
+        for (int s2 = 0; s2 < G::NS2; ++s2)
           if (!MASKED || s2 < ns2) {
-            const uint4 ka = tr_frag(kt, s2 * 32, df * 16, l15, lg);
+            const uint4 ka = tr_frag<D>(kt, s2 * 32, df * 16, l15, lg);
 #pragma unroll
             for (int f = 0; f < 2; ++f) dq[df][f] = mfma16(ka, dsf[s2][f], dq[df][f]);
           }
     }
     if (t + 2 < nt)
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4) : "memory");
+      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * TILE_DMA) : "memory");
     else
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -741,7 +859,7 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_mfma_kernel(const bf16* __
     NVIT_RUN_TILES(std::false_type)
 #undef NVIT_RUN_TILES
 #pragma unroll
-  for (int i = 0; i < 4; ++i)
+  for (int i = 0; i < G::NDF; ++i)
 #pragma unroll
     for (int f = 0; f < 2; ++f) dq[i][f] = dq[i][f] * scale;   // d/d(q_hat): K is not pre-scaled
   if constexpr (FUSE) {
@@ -750,7 +868,7 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_mfma_kernel(const bf16* __
     qk_bwd_epilogue(dq, el, fu, q0, Tq, H, b, h, lane, wid, &lds[0][0][0], tile_, (Tq + 127) / 128, (int)threadIdx.x);
   } else {
     if (wave_active)
-      store_tile32x64(dq, &lds[0][0][0] + wid * 4096, dqh + ((size_t)bh * Tq + q0) * D, (size_t)D, Tq - q0, lane);
+      store_tile<D, 2>(dq, &lds[0][0][0] + wid * 32 * ROWB, dqh + ((size_t)bh * Tq + q0) * D, (size_t)D, Tq - q0, lane);
   }
 }
 
@@ -765,47 +883,50 @@ __device__ __forceinline__ void glds4a(const void* gsrc, unsigned lds_off) {
       : "v"(gsrc), "s"(m)
       : "memory");
 }
-// One workgroup = 4 waves x 32 keys; the 64-query tiles of Q and dO (+ their lse / delta rows) arrive by LDS-DMA into a
-// 3-slot ring two tiles ahead (counted vmcnt, one barrier per tile) - the same machine as the forward / dq kernels,
-// instead of the register-staged double buffer this kernel used before (which spilled at 3 waves per SIMD).
+// One workgroup = 4 waves x 16 NKW keys; the TKV-query tiles of Q and dO (+ their lse / delta rows, 64 floats each whatever
+// the tile height) arrive by LDS-DMA into a 3-slot ring two tiles ahead (counted vmcnt, one barrier per tile) - the same
+// machine as the forward / dq kernels, instead of the register-staged double buffer this kernel used before (which
+// spilled at 3 waves per SIMD).
 // -delta enters as the initial accumulator of the dP product, the softmax scale is applied once to the dK accumulators,
 // and P / dS are packed to bf16 as soon as a 16-query fragment is done, so only packed halves stay live.
-constexpr int DKV_SLOT = 2 * TILE_BYTES + 512;     // Q tile | dO tile | lse[64] | delta[64]
-constexpr int DKV_DMA = 2 * TILE_DMA + 2;          // DMA wave-instructions per wave per tile 
-constexpr int DKV_WAVES = 2;   // waves per SIMD the register budget is sized for (222 VGPRs; at 3 the kernel spills 118)
-
-template <bool FUSE>
-__global__ __launch_bounds__(256, DKV_WAVES) void attn_bwd_dkv_mfma_kernel(const bf16* __restrict__ dout, const bf16* __restrict__ qh,
+template <int D, bool FUSE>
+__global__ __launch_bounds__(256, Geo<D>::OCC_DKV) void attn_bwd_dkv_mfma_kernel(const bf16* __restrict__ dout, const bf16* __restrict__ qh,
                                                                  const bf16* __restrict__ kh, const bf16* __restrict__ vh,
                                                                  const float* __restrict__ lse,
                                                                  const float* __restrict__ delta, float scale,
                                                                  float qpre, bf16* __restrict__ dkh,
                                                                  bf16* __restrict__ dvh, int H, int Tq, int Tk,
                                                                  QkFuse fu) {
+  static_assert(!FUSE || D == 64, "the fused q/k-normalise epilogue is written for 64-wide heads");
+  using G = Geo<D>;
+  constexpr int ROWB = G::ROWB, TKV = G::TKV, TILE_BYTES = G::TILE_BYTES, TILE_DMA = G::TILE_DMA;
+  constexpr int NKW = G::NKW, KWG = G::KWG, DKV_SLOT = G::DKV_SLOT, DKV_DMA = G::DKV_DMA;
   __shared__ __attribute__((aligned(16))) char lds[3 * DKV_SLOT];
+  static_assert(sizeof(lds) >= 4 * 16 * NKW * ROWB, "the ring doubles as the output store scratch");
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l15 = lane & 15, lg = lane >> 4;
+  const int ntile = (Tk + KWG - 1) / KWG;
   int bh, tile_;
-  work_of((Tk + 127) / 128, bh, tile_);
+  work_of(ntile, bh, tile_);
   const int b = bh / H, h = bh % H;
-  const int k0 = tile_ * 128 + wid * 32;
+  const int k0 = tile_ * KWG + wid * 16 * NKW;
   const bf16* qbase = qh + (size_t)bh * Tq * D;
   const bf16* gbase = dout + (size_t)b * Tq * (H * D) + h * D;
   const float* dbase = delta + (size_t)bh * Tq;                                   // -delta, written by the dq kernel
-  const float* lbase = delta + ((size_t)(gridDim.x / ((Tk + 127) / 128)) + bh) * Tq;   // -lse * log2(e), written by the dq kernel
+  const float* lbase = delta + ((size_t)(gridDim.x / ntile) + bh) * Tq;   // -lse * log2(e), written by the dq kernel
   const float c2 = scale * LOG2E / qpre;   // see the forward kernel
   const bool unit = __builtin_amdgcn_readfirstlane(fabsf(c2 - 1.0f) < 1e-6f ? 1 : 0) != 0;
   const int nt = (Tq + TKV - 1) / TKV;
   const unsigned ring = lds_addr(&lds[0]);
 
   const unsigned ldg_bytes = (unsigned)(H * D * 2);
-  const unsigned voff_q[TILE_DMA] = {tile_voff(0, ROWB, lane, wid), tile_voff(1, ROWB, lane, wid)};
-  const unsigned voff_g[TILE_DMA] = {tile_voff(0, ldg_bytes, lane, wid), tile_voff(1, ldg_bytes, lane, wid)};
+  const unsigned voff_q[2] = {tile_voff<D>(0, ROWB, lane, wid), TILE_DMA == 2 ? tile_voff<D>(1, ROWB, lane, wid) : 0u};
+  const unsigned voff_g[2] = {tile_voff<D>(0, ldg_bytes, lane, wid), TILE_DMA == 2 ? tile_voff<D>(1, ldg_bytes, lane, wid) : 0u};
   auto tile_issue = [&](int t, int slot) {
     const unsigned so = ring + (unsigned)slot * DKV_SLOT;
-    tile_dma(qbase, ROWB, t * TKV, Tq, so, lane, wid, voff_q);
-    tile_dma(gbase, ldg_bytes, t * TKV, Tq, so + TILE_BYTES, lane, wid, voff_g);
+    tile_dma<D>(qbase, ROWB, t * TKV, Tq, so, lane, wid, voff_q);
+    tile_dma<D>(gbase, ldg_bytes, t * TKV, Tq, so + TILE_BYTES, lane, wid, voff_g);
     int q = t * TKV + lane;
     q = q < Tq ? q : Tq - 1;
     glds4a(lbase + q, so + 2 * TILE_BYTES);        // every wave writes the same 256 bytes (keeps vmcnt uniform)
@@ -814,36 +935,36 @@ __global__ __launch_bounds__(256, DKV_WAVES) void attn_bwd_dkv_mfma_kernel(const
   tile_issue(0, 0);
   if (nt > 1) tile_issue(1, 1);
 
-  uint4 kf_[2][2], vf_[2][2];  // [key frag][ks]: K / V rows of this wave's 32 keys (MFMA-B operands)
+  uint4 kf_[NKW][G::NKS], vf_[NKW][G::NKS];  // [key frag][ks]: K / V rows of this wave's keys (MFMA-B operands)
 #pragma unroll
-  for (int f = 0; f < 2; ++f) {
+  for (int f = 0; f < NKW; ++f) {
     int k = k0 + 16 * f + l15;
     k = k < Tk ? k : Tk - 1;
 #pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
+    for (int ks = 0; ks < G::NKS; ++ks) {
       kf_[f][ks] = *reinterpret_cast<const uint4*>(kh + ((size_t)bh * Tk + k) * D + ks * 32 + lg * 8);
       vf_[f][ks] = *reinterpret_cast<const uint4*>(vh + ((size_t)bh * Tk + k) * D + ks * 32 + lg * 8);
     }
   }
 #pragma unroll
-  for (int f = 0; f < 2; ++f)
+  for (int f = 0; f < NKW; ++f)
 #pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
+    for (int ks = 0; ks < G::NKS; ++ks) {
       settle(kf_[f][ks]);
       settle(vf_[f][ks]);
     }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
 
-  f32x4 dk[4][2], dv[4][2];  // [df][key frag]: rows d = 16df + 4lg + r, col key = l15
+  f32x4 dk[G::NDF][NKW], dv[G::NDF][NKW];  // [df][key frag]: rows d = 16df + 4lg + r, col key = 16f + l15
 #pragma unroll
-  for (int i = 0; i < 4; ++i)
+  for (int i = 0; i < G::NDF; ++i)
 #pragma unroll
-    for (int f = 0; f < 2; ++f) {
+    for (int f = 0; f < NKW; ++f) {
       dk[i][f] = (f32x4){0.f, 0.f, 0.f, 0.f};
       dv[i][f] = (f32x4){0.f, 0.f, 0.f, 0.f};
     }
-  const bool wave_active = k0 < Tk;   // a wave whose 32 keys all lie past Tk only feeds the ring and the barriers
+  const bool wave_active = k0 < Tk;   // a wave whose keys all lie past Tk only feeds the ring and the barriers
   int cur = 0;
   auto tile_body = [&](const int t, auto masked_, auto unit_) {
     constexpr bool MASKED = decltype(masked_)::value;
@@ -854,46 +975,53 @@ __global__ __launch_bounds__(256, DKV_WAVES) void attn_bwd_dkv_mfma_kernel(const
       const char* gt = qt + TILE_BYTES;
       const float* st = reinterpret_cast<const float*>(qt + 2 * TILE_BYTES);
       const int nvalid = MASKED ? Tq - t * TKV : TKV;   // queries of this tile that exist
-      const int nqf = MASKED ? (nvalid + 15) >> 4 : 4, ns2 = MASKED ? (nvalid + 31) >> 5 : 2;
-      if constexpr (!MASKED) {
+      const int nqf = MASKED ? (nvalid + 15) >> 4 : G::NKF, ns2 = MASKED ? (nvalid + 31) >> 5 : G::NS2;
+      // (D = 128: the 16 transposed fragments of a half held at once take the kernel past 256 registers - 52 bytes of scratch
+      //  per lane - so its full tiles run the just-in-time form below, as they always did)
+      if constexpr (!MASKED && D <= 64) {
         // Full tiles: every LDS read of a 32-query half (row fragments of Q and dO, -lse, -delta, transposed fragments) is
         // issued before its first MFMA, the four accumulator chains of a query fragment are interleaved, and the region
         // is fenced - hipcc otherwise issues each fragment group just in time and waits for the LDS eight times per tile
-        // (245 instead of 286 instructions per tile, 6 instead of 28 lgkmcnt waits).
+        // (at D = 64: 245 instead of 286 instructions per tile, 6 instead of 28 lgkmcnt waits).
 #pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) {
-          uint4 a[2][2], gg[2][2], ga[4], qa[4];
+        for (int s2 = 0; s2 < G::NS2; ++s2) {
+          uint4 a[2][G::NKS], gg[2][G::NKS], ga[G::NDF], qa[G::NDF];
           f32x4 nl[2], nd[2];
 #pragma unroll
           for (int qq = 0; qq < 2; ++qq) {
             const int qfi = 2 * s2 + qq;
-            a[qq][0] = row_frag(qt, qfi * 16, 0, l15, lg), a[qq][1] = row_frag(qt, qfi * 16, 1, l15, lg);
-            gg[qq][0] = row_frag(gt, qfi * 16, 0, l15, lg), gg[qq][1] = row_frag(gt, qfi * 16, 1, l15, lg);
+            a[qq][0] = row_frag<D>(qt, qfi * 16, 0, l15, lg);
+            if constexpr (G::NKS > 1) a[qq][1] = row_frag<D>(qt, qfi * 16, 1, l15, lg);
+            gg[qq][0] = row_frag<D>(gt, qfi * 16, 0, l15, lg);
+            if constexpr (G::NKS > 1) gg[qq][1] = row_frag<D>(gt, qfi * 16, 1, l15, lg);
+            static_assert(G::NKS <= 2, "the pre-issued form is compiled for D <= 64");
             nl[qq] = *reinterpret_cast<const f32x4*>(st + qfi * 16 + 4 * lg);        // -lse (log2 units) of the 4 queries
             nd[qq] = *reinterpret_cast<const f32x4*>(st + 64 + qfi * 16 + 4 * lg);   // -delta
           }
 #pragma unroll
-          for (int df = 0; df < 4; ++df) {
-            ga[df] = tr_frag(gt, s2 * 32, df * 16, l15, lg);   // dO^T[d][q slots]
-            qa[df] = tr_frag(qt, s2 * 32, df * 16, l15, lg);   // Q^T[d][q slots]
+          for (int df = 0; df < G::NDF; ++df) {
+            ga[df] = tr_frag<D>(gt, s2 * 32, df * 16, l15, lg);   // dO^T[d][q slots]
+            qa[df] = tr_frag<D>(qt, s2 * 32, df * 16, l15, lg);   // Q^T[d][q slots]
           }
           __builtin_amdgcn_sched_barrier(0);
-          uint2 ph[2][2], sh[2][2];   // [qq][key frag] packed bf16 P / dS of query frag 2*s2 + qq
+          uint2 ph[2][NKW], sh[2][NKW];   // [qq][key frag] packed bf16 P / dS of query frag 2*s2 + qq
 #pragma unroll
           for (int qq = 0; qq < 2; ++qq) {
-            f32x4 z[2], w[2];
+            f32x4 z[NKW], w[NKW];
 #pragma unroll
-            for (int f = 0; f < 2; ++f) {
+            for (int f = 0; f < NKW; ++f) {
               z[f] = mfma16(a[qq][0], kf_[f][0], UNIT ? nl[qq] : (f32x4){0.f, 0.f, 0.f, 0.f});
               w[f] = mfma16(gg[qq][0], vf_[f][0], nd[qq]);   // row constants -delta as the initial accumulator
             }
+            if constexpr (G::NKS > 1) {   // the chains of the key fragments interleaved, k-step by k-step
 #pragma unroll
-            for (int f = 0; f < 2; ++f) {
-              z[f] = mfma16(a[qq][1], kf_[f][1], z[f]);    // S[q][key] (UNIT: already minus lse, in log2 units)
-              w[f] = mfma16(gg[qq][1], vf_[f][1], w[f]);   // dP[q][key] - delta[q]
+              for (int f = 0; f < NKW; ++f) {
+                z[f] = mfma16(a[qq][1], kf_[f][1], z[f]);    // S[q][key] (UNIT: already minus lse, in log2 units)
+                w[f] = mfma16(gg[qq][1], vf_[f][1], w[f]);   // dP[q][key] - delta[q]
+              }
             }
 #pragma unroll
-            for (int f = 0; f < 2; ++f) {
+            for (int f = 0; f < NKW; ++f) {
               f32x4 p, dsv;
 #pragma unroll
               for (int r = 0; r < 4; ++r) {
@@ -904,16 +1032,16 @@ __global__ __launch_bounds__(256, DKV_WAVES) void attn_bwd_dkv_mfma_kernel(const
               sh[qq][f] = pack4(dsv);
             }
           }
-          uint4 pb[2], sb[2];
+          uint4 pb[NKW], sb[NKW];
 #pragma unroll
-          for (int f = 0; f < 2; ++f) {
+          for (int f = 0; f < NKW; ++f) {
             pb[f] = make_uint4(ph[0][f].x, ph[0][f].y, ph[1][f].x, ph[1][f].y);
             sb[f] = make_uint4(sh[0][f].x, sh[0][f].y, sh[1][f].x, sh[1][f].y);
           }
 #pragma unroll
-          for (int df = 0; df < 4; ++df)
+          for (int df = 0; df < G::NDF; ++df)
 #pragma unroll
-            for (int f = 0; f < 2; ++f) {
+            for (int f = 0; f < NKW; ++f) {
               dv[df][f] = mfma16(ga[df], pb[f], dv[df][f]);
               dk[df][f] = mfma16(qa[df], sb[f], dk[df][f]);
             }
@@ -921,26 +1049,24 @@ __global__ __launch_bounds__(256, DKV_WAVES) void attn_bwd_dkv_mfma_kernel(const
         }
       } else
 #pragma unroll
-      for (int s2 = 0; s2 < 2; ++s2) {
+      for (int s2 = 0; s2 < G::NS2; ++s2) {
         if (s2 >= ns2) continue;
-        uint2 ph[2][2], sh[2][2];  // [qq][key frag] packed bf16 P / dS of query frag qfi = 2*s2 + qq (rows 16qfi + 4lg + r)
+        uint2 ph[2][NKW], sh[2][NKW];  // [qq][key frag] packed bf16 P / dS of query frag qfi = 2*s2 + qq (rows 16qfi + 4lg + r)
 #pragma unroll
         for (int qq = 0; qq < 2; ++qq) {
           const int qfi = 2 * s2 + qq;
           if (!MASKED || qfi < nqf) {
-            const uint4 a0 = row_frag(qt, qfi * 16, 0, l15, lg), a1 = row_frag(qt, qfi * 16, 1, l15, lg);
-            const uint4 g0 = row_frag(gt, qfi * 16, 0, l15, lg), g1 = row_frag(gt, qfi * 16, 1, l15, lg);
+            NVIT_ROW_FRAGS(D, a, qt, qfi * 16);
+            NVIT_ROW_FRAGS(D, g, gt, qfi * 16);
             f32x4 nl4 = *reinterpret_cast<const f32x4*>(st + qfi * 16 + 4 * lg);   // -lse (log2 units) of the 4 queries
             f32x4 nd4 = *reinterpret_cast<const f32x4*>(st + 64 + qfi * 16 + 4 * lg);   // -delta
             asm volatile("" : "+v"(nd4));   // one register quad, read as the C operand of both key fragments' chains
             asm volatile("" : "+v"(nl4));
 #pragma unroll
-            for (int f = 0; f < 2; ++f) {
+            for (int f = 0; f < NKW; ++f) {
               f32x4 z = UNIT ? nl4 : (f32x4){0.f, 0.f, 0.f, 0.f};
-              z = mfma16(a0, kf_[f][0], z);
-              z = mfma16(a1, kf_[f][1], z);  // S[q][key] (UNIT: already minus lse, in log2 units)
-              f32x4 w = mfma16(g0, vf_[f][0], nd4);   // row constants -delta as the initial accumulator
-              w = mfma16(g1, vf_[f][1], w);           // dP[q][key] - delta[q]
+              z = mfma_ks(a0, a1, a2, a3, kf_[f], z);   // S[q][key] (UNIT: already minus lse, in log2 units)
+              const f32x4 w = mfma_ks(g0, g1, g2, g3, vf_[f], nd4);   // dP[q][key] - delta[q] (-delta: initial accumulator)
               f32x4 p, dsv;
 #pragma unroll
               for (int r = 0; r < 4; ++r) {
@@ -953,21 +1079,22 @@ __global__ __launch_bounds__(256, DKV_WAVES) void attn_bwd_dkv_mfma_kernel(const
               sh[qq][f] = pack4(dsv);
             }
           } else {
-            ph[qq][0] = ph[qq][1] = sh[qq][0] = sh[qq][1] = make_uint2(0u, 0u);
+#pragma unroll
+            for (int f = 0; f < NKW; ++f) ph[qq][f] = sh[qq][f] = make_uint2(0u, 0u);
           }
         }
-        uint4 pb[2], sb[2];
+        uint4 pb[NKW], sb[NKW];
 #pragma unroll
-        for (int f = 0; f < 2; ++f) {
+        for (int f = 0; f < NKW; ++f) {
           pb[f] = make_uint4(ph[0][f].x, ph[0][f].y, ph[1][f].x, ph[1][f].y);
           sb[f] = make_uint4(sh[0][f].x, sh[0][f].y, sh[1][f].x, sh[1][f].y);
         }
 #pragma unroll
-        for (int df = 0; df < 4; ++df) {
-          const uint4 ga = tr_frag(gt, s2 * 32, df * 16, l15, lg);  // dO^T[d][q slots]
-          const uint4 qa = tr_frag(qt, s2 * 32, df * 16, l15, lg);  // Q^T[d][q slots]
+        for (int df = 0; df < G::NDF; ++df) {
+          const uint4 ga = tr_frag<D>(gt, s2 * 32, df * 16, l15, lg);  // dO^T[d][q slots]
+          const uint4 qa = tr_frag<D>(qt, s2 * 32, df * 16, l15, lg);  // Q^T[d][q slots]
 #pragma unroll
-          for (int f = 0; f < 2; ++f) {
+          for (int f = 0; f < NKW; ++f) {
             dv[df][f] = mfma16(ga, pb[f], dv[df][f]);
             dk[df][f] = mfma16(qa, sb[f], dk[df][f]);
           }
@@ -996,22 +1123,22 @@ __global__ __launch_bounds__(256, DKV_WAVES) void attn_bwd_dkv_mfma_kernel(const
 #undef NVIT_RUN_TILES
   const float dks = scale / qpre;   // d/d(k_hat) = scale * dS^T q_hat, and the Q tiles hold qpre * q_hat
 #pragma unroll
-  for (int i = 0; i < 4; ++i)
+  for (int i = 0; i < G::NDF; ++i)
 #pragma unroll
-    for (int f = 0; f < 2; ++f) dk[i][f] = dk[i][f] * dks;
-  char* scr = &lds[0] + wid * 4096;   // (the tile loop ended with a barrier: the ring is free)
+    for (int f = 0; f < NKW; ++f) dk[i][f] = dk[i][f] * dks;
+  char* scr = &lds[0] + wid * 16 * NKW * ROWB;   // (the tile loop ended with a barrier: the ring is free)
   if constexpr (FUSE) {
     if (wave_active)
-      store_tile32x64(dv, scr, fu.out_v + ((size_t)b * Tk + k0) * fu.ld + h * 64, (size_t)fu.ld, Tk - k0, lane);
+      store_tile<64, 2>(dv, scr, fu.out_v + ((size_t)b * Tk + k0) * fu.ld + h * 64, (size_t)fu.ld, Tk - k0, lane);
     __builtin_amdgcn_wave_barrier();
     QkEpiLoads el;
     qk_bwd_epilogue_loads(el, kh + (size_t)bh * Tk * D, fu, k0, Tk, H, b, h, lane);
-    qk_bwd_epilogue(dk, el, fu, k0, Tk, H, b, h, lane, wid, &lds[0], tile_, (Tk + 127) / 128, (int)threadIdx.x);
+    qk_bwd_epilogue(dk, el, fu, k0, Tk, H, b, h, lane, wid, &lds[0], tile_, ntile, (int)threadIdx.x);
   } else {
     if (wave_active) {
-      store_tile32x64(dk, scr, dkh + ((size_t)bh * Tk + k0) * D, (size_t)D, Tk - k0, lane);
+      store_tile<D, NKW>(dk, scr, dkh + ((size_t)bh * Tk + k0) * D, (size_t)D, Tk - k0, lane);
       __builtin_amdgcn_wave_barrier();
-      store_tile32x64(dv, scr, dvh + ((size_t)bh * Tk + k0) * D, (size_t)D, Tk - k0, lane);
+      store_tile<D, NKW>(dv, scr, dvh + ((size_t)bh * Tk + k0) * D, (size_t)D, Tk - k0, lane);
     }
   }
 }
@@ -1019,7 +1146,7 @@ __global__ __launch_bounds__(256, DKV_WAVES) void attn_bwd_dkv_mfma_kernel(const
 
 // ------------------------------------------------------------------------------------------ dK, dV: hand-placed main loop
 // Same arithmetic, operand layouts and accumulation order as attn_bwd_dkv_mfma_kernel above (bit-exact against it), for
-// the pre-scaled-q case (c2 = 1), with the tile loop written as ONE generated inline-asm statement
+// the pre-scaled-q case (c2 = 1) at head dim 64, with the tile loop written as ONE generated inline-asm statement
 // (gen/gen_attn_dkv32_asm.py -> attn_dkv32_asm.inc; structure and numbers: DESIGN.md section 5, round 4).  The
 // compiler-built code around it only prepares operands and stores the result: the accumulators come back through LDS
 // (ds_write from the accumulation registers), never through compiler-visible registers.
@@ -1047,6 +1174,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_asm32_kernel(const bf16* 
   // (the q/k-normalise operands arrive as scalars and the QkFuse is put together BEHIND the loop: taken by value as one
   //  struct, part of it is parked in LDS from the first instruction on and the address of that slot lives across the loop
   //  statement - one register too many for two waves per SIMD)
+  using G = Geo<64>;
+  constexpr int D = 64, ROWB = G::ROWB, TKV = G::TKV, DKV_SLOT = G::DKV_SLOT;
   __shared__ __attribute__((aligned(16))) char lds[4 * DKV_SLOT];   // tile ring; then (its first 4 x 16 KiB) the accumulators
   static_assert(4 * DKV_SLOT >= 4 * 16384, "the hand-over area must fit the ring");
   const int tid = threadIdx.x;
@@ -1063,7 +1192,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_asm32_kernel(const bf16* 
   const int nvalid_last = Tq - (nt - 1) * TKV;
   const unsigned ldg = (unsigned)(H * D * 2);
   const int r8 = lane >> 3, chunk = (lane & 7) ^ r8;
-  const unsigned voff_q0 = tile_voff(0, ROWB, lane, wid), voff_g0 = tile_voff(0, ldg, lane, wid);
+  const unsigned voff_q0 = tile_voff<D>(0, ROWB, lane, wid), voff_g0 = tile_voff<D>(0, ldg, lane, wid);
   unsigned rows_last = 0;
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
@@ -1078,11 +1207,11 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_asm32_kernel(const bf16* 
     k = k < Tk ? k : Tk - 1;
     kvoff[f] = (unsigned)(k * D + lg * 8) * 2u;
   }
-  const unsigned a0 = (unsigned)swz_off(l15, lg), a1 = (unsigned)swz_off(l15, 4 + lg);
+  const unsigned a0 = (unsigned)G::off(l15, lg), a1 = (unsigned)G::off(l15, 4 + lg);
   unsigned tro[4];
 #pragma unroll
   for (int df = 0; df < 4; ++df)
-    tro[df] = (unsigned)(swz_off(4 * lg + (l15 >> 2), 2 * df + ((l15 & 3) >> 1)) + ((l15 & 1) << 3));
+    tro[df] = (unsigned)(G::off(4 * lg + (l15 >> 2), 2 * df + ((l15 & 3) >> 1)) + ((l15 & 1) << 3));
   const unsigned ring = lds_addr(&lds[0]);
   const unsigned dump = ring + (unsigned)wid * 16384u + (unsigned)lane * 16u;
   const unsigned long long s_q = uni64(qh + (size_t)bh * Tq * D);
@@ -1130,14 +1259,14 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_asm32_kernel(const bf16* 
   char* scr = &lds[0] + wid * 4096;
   if constexpr (FUSE) {
     if (wave_active)
-      store_tile32x64(dv, scr, fu.out_v + ((size_t)b * Tk + k0) * fu.ld + h * 64, (size_t)fu.ld, Tk - k0, lane);
+      store_tile<64, 2>(dv, scr, fu.out_v + ((size_t)b * Tk + k0) * fu.ld + h * 64, (size_t)fu.ld, Tk - k0, lane);
     __builtin_amdgcn_wave_barrier();
     qk_bwd_epilogue(dk, el, fu, k0, Tk, H, b, h, lane, wid, &lds[0], tile_, ntile, (int)threadIdx.x);
   } else {
     if (wave_active) {
-      store_tile32x64(dk, scr, dkh + ((size_t)bh * Tk + k0) * D, (size_t)D, Tk - k0, lane);
+      store_tile<64, 2>(dk, scr, dkh + ((size_t)bh * Tk + k0) * D, (size_t)D, Tk - k0, lane);
       __builtin_amdgcn_wave_barrier();
-      store_tile32x64(dv, scr, dvh + ((size_t)bh * Tk + k0) * D, (size_t)D, Tk - k0, lane);
+      store_tile<64, 2>(dv, scr, dvh + ((size_t)bh * Tk + k0) * D, (size_t)D, Tk - k0, lane);
     }
   }
 }
@@ -1149,688 +1278,10 @@ int dkv_asm_mode(float scale, float qpre) {
   return fabsf(c2 - 1.0f) < 1e-6f ? g_attn_dkv_asm : 0;   // the hand-placed loops assume the pre-scaled q (c2 = 1)
 }
 
-// ================================================================================= head dims 32 and 128
-// The same three kernels (key-major forward with the bounded-score fast path, the UNIT variant and the online-softmax
-// fallback; recompute backward as a dq kernel and a dk/dv kernel, no atomics; XCD-affine work map) with the head dim D a
-// template parameter, instantiated at 32 and 128.  The d = 64 kernels above stay as they are (the training path, tuned
-// instruction by instruction); these share their operand layouts, MFMA shapes, DMA machine and accumulation order, and
-// re-derive what depends on D:
-//   LDS image  D = 32: 64-byte rows, taken in pairs as one 128-byte row of the d = 64 image: chunk ((row & 1) * 4 + ch)
-//                      of "row pair" row >> 1, XOR (row >> 1) & 7.
-//              D = 128: 256-byte rows of 16 chunks, chunk XOR (bit-reversed row & 7) << 1.
-//              Both are conflict-free for the 16x16x32 row reads (ds_read_b128: one LDS cycle per 16-lane group) and
-//              for the transposed reads (ds_read_b64_tr_b16: one per 32-lane half), under the bank rule
-//              bank = (byte / 4) % 64 - checked for every (row0, chunk) the kernels read.
-//   KV tile    64 keys at D = 32 (4 KiB, one DMA piece per wave), 32 keys at D = 128 (8 KiB, two pieces per wave): the ring
-//              of 3 slots stays at 24 / 48 KiB.  A DMA piece (64 lanes x 16 B) is 16 rows at D = 32 and 4 rows at D = 128.
-//   dK/dV      32 keys per wave at D = 32, 16 at D = 128 (the accumulators dK^T, dV^T are 2 x D x keys / 64 registers).
-//   Fragments  D / 32 k-steps of the score products, D / 16 output d-fragments.
-// Not here: the fused q/k-normalise epilogues and the hand-placed dK/dV loop (d = 64 only; nvit_attn_bwd_qknorm).
-namespace hd {
-
-template <int D>
-struct Geo {
-  static_assert(D == 32 || D == 128, "head dims 32 and 128 (64: the kernels above)");
-  static constexpr int ROWB = D * 2;                  // bytes per row
-  static constexpr int NCH = D / 8;                   // 16-byte chunks per row
-  static constexpr int TKV = D == 128 ? 32 : 64;      // rows per staged tile
-  static constexpr int TILE_BYTES = TKV * ROWB;       // 4 / 8 KiB
-  static constexpr int TILE_DMA = TILE_BYTES / 4096;  // 1 KiB pieces per wave per tile (4 waves)
-  static constexpr int NKS = D / 32;                  // k-steps of a product over d
-  static constexpr int NDF = D / 16;                  // 16-wide d-fragments
-  static constexpr int NKF = TKV / 16;                // 16-row fragments of a tile
-  static constexpr int NS2 = TKV / 32;                // 32-deep MFMA steps over a tile
-  static constexpr int NKW = D == 128 ? 1 : 2;        // dK/dV kernel: 16-key fragments per wave
-  static constexpr int KWG = 64 * NKW;                // dK/dV kernel: keys per workgroup
-  // waves per SIMD (__launch_bounds__) = what the registers allow without scratch (-Rpass-analysis=kernel-resource-usage):
-  // D = 32: 120 / 98 / 132 VGPRs (forward / dq / dkv), D = 128: 219 / 242 / 178; the LDS (24-26 / 48-50 KiB per workgroup)
-  // allows more in every case
-  static constexpr int OCC_FWD = D == 32 ? 4 : 2, OCC_DQ = D == 32 ? 4 : 2, OCC_DKV = D == 32 ? 3 : 2;
-  static_assert(TILE_DMA == 1 || TILE_DMA == 2, "one or two pieces per wave per tile");
-
-  __device__ static __forceinline__ int swz(int row) {   // D = 128: bit-reversed (row & 7), times 2
-    return ((row & 1) << 3) | ((row & 2) << 1) | ((row & 4) >> 1);
-  }
-  // byte offset of 16-byte chunk ch of row `row` in a tile
-  __device__ static __forceinline__ int off(int row, int ch) {
-    if constexpr (D == 32) {
-      const int v = row >> 1;
-      return v * 128 + (((((row & 1) << 2) | ch) ^ (v & 7)) << 4);
-    } else {
-      return row * ROWB + ((ch ^ swz(row)) << 4);
-    }
-  }
-  // the inverse for the DMA: lane L of 1 KiB piece p lands at p * 1024 + 16 L, which holds (row, ch)
-  __device__ static __forceinline__ void piece_lane(int p, int lane, int& row, int& ch) {
-    if constexpr (D == 32) {
-      const int v = lane >> 3, vch = (lane & 7) ^ v;   // (p * 8 + v) & 7 == v
-      row = p * 16 + 2 * v + (vch >> 2);
-      ch = vch & 3;
-    } else {
-      row = p * 4 + (lane >> 4);
-      ch = (lane & 15) ^ swz(row);
-    }
-  }
-};
-
-template <int D>
-__device__ __forceinline__ uint4 row_frag(const char* tile, int row0, int ks, int l15, int lg) {
-  return *reinterpret_cast<const uint4*>(tile + Geo<D>::off(row0 + l15, ks * 4 + lg));
-}
-// as ::tr_frag (same k-slot order), on the D-dependent image
-template <int D>
-__device__ __forceinline__ uint4 tr_frag(const char* tile, int row0, int col0, int l15, int lg) {
-  const int q = l15 >> 2, p = l15 & 3;
-  const int r0 = row0 + 4 * lg + q, r1 = r0 + 16;
-  const int ch = (col0 >> 3) + (p >> 1);
-  const int o0 = Geo<D>::off(r0, ch) + ((p & 1) << 3), o1 = Geo<D>::off(r1, ch) + ((p & 1) << 3);
-  s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(tile + o0));
-  s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(tile + o1));
-  uint2 l2 = __builtin_bit_cast(uint2, lo), h2 = __builtin_bit_cast(uint2, hi);
-  return make_uint4(l2.x, l2.y, h2.x, h2.y);
-}
-
-// Store a wave's [16 NF rows x D] accumulator-layout result (g[df][f][r] = out[row 16f + l15][col 16df + 4lg + r]) as
-// bf16 rows through a wave-private LDS scratch of 16 NF rows (the tile image): every global store writes whole rows,
-// 16 bytes per lane.  Rows >= nvalid are not written.
-template <int D, int NF>
-__device__ __forceinline__ void store_tile(const f32x4 (&g)[D / 16][NF], char* scr, bf16* dst, size_t ld, int nvalid,
-                                           int lane) {
-  using G = Geo<D>;
-  const int l15 = lane & 15, lg = lane >> 4;
-#pragma unroll
-  for (int f = 0; f < NF; ++f)
-#pragma unroll
-    for (int df = 0; df < G::NDF; ++df)
-      *reinterpret_cast<uint2*>(scr + G::off(16 * f + l15, 2 * df + (lg >> 1)) + 8 * (lg & 1)) = pack4(g[df][f]);
-  __builtin_amdgcn_wave_barrier();
-  constexpr int RPP = 64 / G::NCH;   // rows per pass
-#pragma unroll
-  for (int pass = 0; pass < 16 * NF / RPP; ++pass) {
-    const int row = pass * RPP + lane / G::NCH, chunk = lane % G::NCH;
-    const uint4 v = *reinterpret_cast<const uint4*>(scr + G::off(row, chunk));
-    if (row < nvalid) *reinterpret_cast<uint4*>(dst + (size_t)row * ld + chunk * 8) = v;
-  }
-}
-
-// lane offsets of a full tile's DMA pieces (piece i * 4 + wid), and the tile DMA with the ragged-tile clamp (rows past the
-// end re-read the last valid row: finite values, masked by the consumer)
-template <int D>
-__device__ __forceinline__ unsigned tile_voff(int i, unsigned ld_bytes, int lane, int wid) {
-  int row, ch;
-  Geo<D>::piece_lane(i * 4 + wid, lane, row, ch);
-  return (unsigned)row * ld_bytes + (unsigned)ch * 16u;
-}
-template <int D>
-__device__ __forceinline__ void tile_dma(const bf16* src, unsigned ld_bytes, int row_base, int nrows, unsigned tile_off,
-                                         int lane, int wid, const unsigned (&voff)[Geo<D>::TILE_DMA]) {
-  using G = Geo<D>;
-  const char* sb = reinterpret_cast<const char*>(src) + (size_t)row_base * ld_bytes;
-  if (row_base + G::TKV <= nrows) {
-    if constexpr (G::TILE_DMA == 2)
-      glds16s_pair(sb, voff[0], voff[1], tile_off + wid * 1024);   // pieces wid and 4 + wid: 4 KiB apart
-    else
-      glds16s(sb, voff[0], tile_off + wid * 1024);
-  } else {
-#pragma unroll
-    for (int i = 0; i < G::TILE_DMA; ++i) {
-      int row, ch;
-      G::piece_lane(i * 4 + wid, lane, row, ch);
-      row = row_base + row < nrows ? row : nrows - 1 - row_base;
-      glds16s(sb, (unsigned)row * ld_bytes + (unsigned)ch * 16u, tile_off + (i * 4 + wid) * 1024);
-    }
-  }
-}
-
-// ------------------------------------------------------------------------------------------ forward (see attn_fwd_mfma_kernel)
-template <int D>
-__global__ __launch_bounds__(256, Geo<D>::OCC_FWD) void attn_fwd_kernel(const bf16* __restrict__ qh, const bf16* __restrict__ kh,
-                                                          const bf16* __restrict__ vh, float scale, float qpre,
-                                                          const float* __restrict__ sqk, float c_q, bf16* __restrict__ o,
-                                                          float* __restrict__ lse, int H, int Tq, int Tk) {
-  using G = Geo<D>;
-  constexpr int TKV = G::TKV, TB = G::TILE_BYTES, NKS = G::NKS, NDF = G::NDF, NKF = G::NKF, NS2 = G::NS2;
-  constexpr int TD = G::TILE_DMA;
-  __shared__ __attribute__((aligned(16))) char lds[3][2][TB];  // ring [slot][K|V]
-  static_assert(sizeof(lds) >= 4 * 32 * G::ROWB, "the ring doubles as the output store scratch");
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int l15 = lane & 15, lg = lane >> 4;
-  int bh, tile_;
-  work_of((Tq + 127) / 128, bh, tile_);
-  const int b = bh / H, h = bh % H;
-  const int q0 = tile_ * 128 + wid * 32;
-  const bf16* kbase = kh + (size_t)bh * Tk * D;
-  const bf16* vbase = vh + (size_t)bh * Tk * D;
-  const float c2t = scale * LOG2E;
-  const float c2 = c2t / qpre;
-  const bool unit = __builtin_amdgcn_readfirstlane(fabsf(c2 - 1.0f) < 1e-6f ? 1 : 0) != 0;
-
-  uint4 qf[2][NKS];
-  f32x4 oacc[NDF][2];
-#pragma unroll
-  for (int i = 0; i < NDF; ++i)
-#pragma unroll
-    for (int f = 0; f < 2; ++f) oacc[i][f] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  float m_[2] = {-INFINITY, -INFINITY}, l_[2] = {0.f, 0.f};
-  float tb = INFINITY;
-  if (sqk) {   // the head's max |s_d| over one wave: lanes >= 32 hold no channel at D = 32, two channels at D = 128
-    float sm;
-    if constexpr (D == 32)
-      sm = lane < 32 ? fabsf(sqk[h * D + lane] * c_q) : 0.f;
-    else
-      sm = fmaxf(fabsf(sqk[h * D + lane] * c_q), fabsf(sqk[h * D + 64 + lane] * c_q));
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) sm = fmaxf(sm, __shfl_xor(sm, off, 64));
-    tb = c2t * sm * sm;
-  }
-  const bool fast = __builtin_amdgcn_readfirstlane(tb <= BOUND_MAX ? 1 : 0) != 0;
-  f32x4 lacc[2] = {(f32x4){0.f, 0.f, 0.f, 0.f}, (f32x4){0.f, 0.f, 0.f, 0.f}};
-  const uint4 ones = make_uint4(0x3F803F80u, 0x3F803F80u, 0x3F803F80u, 0x3F803F80u);
-
-  const int nt = (Tk + TKV - 1) / TKV;
-  const unsigned ring = lds_addr(&lds[0][0][0]);
-  unsigned voff[TD];
-#pragma unroll
-  for (int i = 0; i < TD; ++i) voff[i] = tile_voff<D>(i, G::ROWB, lane, wid);
-  tile_dma<D>(kbase, G::ROWB, 0, Tk, ring, lane, wid, voff);
-  tile_dma<D>(vbase, G::ROWB, 0, Tk, ring + TB, lane, wid, voff);
-  if (nt > 1) {
-    tile_dma<D>(kbase, G::ROWB, TKV, Tk, ring + 2 * TB, lane, wid, voff);
-    tile_dma<D>(vbase, G::ROWB, TKV, Tk, ring + 3 * TB, lane, wid, voff);
-  }
-#pragma unroll
-  for (int f = 0; f < 2; ++f) {
-    int q = q0 + 16 * f + l15;
-    q = q < Tq ? q : Tq - 1;
-#pragma unroll
-    for (int ks = 0; ks < NKS; ++ks)
-      qf[f][ks] = *reinterpret_cast<const uint4*>(qh + ((size_t)bh * Tq + q) * D + ks * 32 + lg * 8);
-  }
-#pragma unroll
-  for (int f = 0; f < 2; ++f)
-#pragma unroll
-    for (int ks = 0; ks < NKS; ++ks) settle(qf[f][ks]);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  int cur = 0;
-  const bool wave_active = q0 < Tq;
-  f32x4 ntb = {-tb, -tb, -tb, -tb};
-  asm volatile("" : "+v"(ntb));
-  auto tile_body = [&](const int t, auto masked_, auto fast_, auto unit_) {
-    constexpr bool MASKED = decltype(masked_)::value;
-    constexpr bool FAST = decltype(fast_)::value;
-    constexpr bool UNIT = decltype(unit_)::value;
-    if (t + 2 < nt) {
-      const int sl = cur == 0 ? 2 : cur - 1;  // (t + 2) % 3
-      tile_dma<D>(kbase, G::ROWB, (t + 2) * TKV, Tk, ring + (2 * sl) * TB, lane, wid, voff);
-      tile_dma<D>(vbase, G::ROWB, (t + 2) * TKV, Tk, ring + (2 * sl + 1) * TB, lane, wid, voff);
-    }
-    if (wave_active) {
-      const char* kt = &lds[cur][0][0];
-      const char* vt = &lds[cur][1][0];
-      const int nvalid = MASKED ? Tk - t * TKV : TKV;
-      const int nkf = MASKED ? (nvalid + 15) >> 4 : NKF, ns2 = MASKED ? (nvalid + 31) >> 5 : NS2;
-      // S^T[kf][f]: rows = key 16kf + 4lg + r, col = query 16f + l15; FAST: probabilities relative to the bound
-      f32x4 s[NKF][2];
-#pragma unroll
-      for (int kf = 0; kf < NKF; ++kf) {
-        if (!MASKED || kf < nkf) {
-          uint4 a[NKS];
-#pragma unroll
-          for (int ks = 0; ks < NKS; ++ks) a[ks] = row_frag<D>(kt, kf * 16, ks, l15, lg);
-#pragma unroll
-          for (int f = 0; f < 2; ++f) {
-            f32x4 z = (FAST && UNIT) ? ntb : (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int ks = 0; ks < NKS; ++ks) z = mfma16(a[ks], qf[f][ks], z);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              const bool valid = !MASKED || kf * 16 + lg * 4 + r < nvalid;
-              if constexpr (FAST)
-                z[r] = valid ? (UNIT ? fast_exp2(z[r]) : fast_exp2(z[r] * c2 - tb)) : 0.f;
-              else
-                z[r] = valid ? z[r] : -INFINITY;
-            }
-            s[kf][f] = z;
-          }
-        } else {
-          s[kf][0] = (f32x4){0.f, 0.f, 0.f, 0.f};   // fragment past the end: probability 0, no work
-          s[kf][1] = s[kf][0];
-        }
-      }
-      if constexpr (!FAST) {   // online softmax: running maximum, correction of the row sums and the accumulators
-#pragma unroll
-        for (int f = 0; f < 2; ++f) {
-          float mt = -INFINITY;
-#pragma unroll
-          for (int kf = 0; kf < NKF; ++kf)
-            if (!MASKED || kf < nkf) {
-#pragma unroll
-              for (int r = 0; r < 4; ++r) mt = fmaxf(mt, s[kf][f][r]);
-            }
-          mt = fmaxf(mt, __shfl_xor(mt, 16, 64));
-          mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
-          const float mn = fmaxf(m_[f], mt);
-          const float corr = fast_exp2((m_[f] - mn) * c2);
-          m_[f] = mn;
-          const float mc = mn * c2;
-          float rs = 0.f;
-#pragma unroll
-          for (int kf = 0; kf < NKF; ++kf)
-            if (!MASKED || kf < nkf) {
-#pragma unroll
-              for (int r = 0; r < 4; ++r) {
-                const float p = fast_exp2(s[kf][f][r] * c2 - mc);
-                s[kf][f][r] = p;
-                rs += p;
-              }
-            }
-          l_[f] = l_[f] * corr + rs;
-#pragma unroll
-          for (int i = 0; i < NDF; ++i) oacc[i][f] = oacc[i][f] * corr;
-        }
-      }
-      // O^T[df][f] += V^T P^T (and FAST: the row sums l[f] += 1^T P^T)
-#pragma unroll
-      for (int s2 = 0; s2 < NS2; ++s2)
-        if (!MASKED || s2 < ns2) {
-          uint4 pf[2];
-#pragma unroll
-          for (int f = 0; f < 2; ++f) pf[f] = pack8(s[2 * s2][f], s[2 * s2 + 1][f]);
-          if constexpr (FAST) {
-#pragma unroll
-            for (int f = 0; f < 2; ++f) lacc[f] = mfma16(ones, pf[f], lacc[f]);
-          }
-#pragma unroll
-          for (int df = 0; df < NDF; ++df) {
-            const uint4 va = tr_frag<D>(vt, s2 * 32, df * 16, l15, lg);
-#pragma unroll
-            for (int f = 0; f < 2; ++f) oacc[df][f] = mfma16(va, pf[f], oacc[df][f]);
-          }
-        }
-    }
-    if (t + 2 < nt)
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * TD) : "memory");
-    else
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    cur = cur == 2 ? 0 : cur + 1;
-  };
-#define NVIT_RUN_TILES(FAST_, UNIT_)                                                            \
-  {                                                                                             \
-    for (int t = 0; t + 1 < nt; ++t) tile_body(t, std::false_type{}, FAST_{}, UNIT_{});         \
-    if (Tk % TKV)                                                                               \
-      tile_body(nt - 1, std::true_type{}, FAST_{}, UNIT_{});                                    \
-    else                                                                                        \
-      tile_body(nt - 1, std::false_type{}, FAST_{}, UNIT_{});                                   \
-  }
-  if (fast && unit)
-    NVIT_RUN_TILES(std::true_type, std::true_type)
-  else if (fast)
-    NVIT_RUN_TILES(std::true_type, std::false_type)
-  else
-    NVIT_RUN_TILES(std::false_type, std::false_type)
-#undef NVIT_RUN_TILES
-#pragma unroll
-  for (int f = 0; f < 2; ++f) {
-    float l, lse_v;
-    if (fast) {
-      l = lacc[f][0];
-      lse_v = (tb + log2f(l)) * (1.0f / LOG2E);
-    } else {
-      l = l_[f];
-      l += __shfl_xor(l, 16, 64);
-      l += __shfl_xor(l, 32, 64);
-      lse_v = m_[f] * (c2 * (1.0f / LOG2E)) + logf(l);
-    }
-    const int q = q0 + 16 * f + l15;
-    const float inv = 1.0f / l;
-#pragma unroll
-    for (int df = 0; df < NDF; ++df) oacc[df][f] = oacc[df][f] * inv;
-    if (q < Tq && lg == 0) lse[(size_t)bh * Tq + q] = lse_v;
-  }
-  if (wave_active)
-    store_tile<D, 2>(oacc, &lds[0][0][0] + wid * 32 * G::ROWB, o + ((size_t)b * Tq + q0) * (H * D) + h * D, (size_t)H * D,
-                     Tq - q0, lane);
-}
-
-// ------------------------------------------------------------------------------------------ dQ (see attn_bwd_dq_mfma_kernel)
-template <int D>
-__global__ __launch_bounds__(256, Geo<D>::OCC_DQ) void attn_bwd_dq_kernel(const bf16* __restrict__ dout, const bf16* __restrict__ qh,
-                                                             const bf16* __restrict__ kh, const bf16* __restrict__ vh,
-                                                             const float* __restrict__ lse, const bf16* __restrict__ og,
-                                                             float* __restrict__ delta, float scale,
-                                                             bf16* __restrict__ dqh, int H, int Tq, int Tk) {
-  using G = Geo<D>;
-  constexpr int TKV = G::TKV, TB = G::TILE_BYTES, NKS = G::NKS, NDF = G::NDF, NKF = G::NKF, NS2 = G::NS2;
-  constexpr int TD = G::TILE_DMA;
-  __shared__ __attribute__((aligned(16))) char lds[3][2][TB];
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int l15 = lane & 15, lg = lane >> 4;
-  const int ntile = (Tq + 127) / 128;
-  int bh, tile_;
-  work_of(ntile, bh, tile_);
-  const int b = bh / H, h = bh % H;
-  const int q0 = tile_ * 128 + wid * 32;
-  const bf16* kbase = kh + (size_t)bh * Tk * D;
-  const bf16* vbase = vh + (size_t)bh * Tk * D;
-  const float c2 = scale * LOG2E;   // q is not pre-scaled on this path
-
-  uint4 qf[2][NKS], gf[2][NKS];
-  float lse2[2], dl[2];
-  const int nt = (Tk + TKV - 1) / TKV;
-  const unsigned ring = lds_addr(&lds[0][0][0]);
-  unsigned voff[TD];
-#pragma unroll
-  for (int i = 0; i < TD; ++i) voff[i] = tile_voff<D>(i, G::ROWB, lane, wid);
-  tile_dma<D>(kbase, G::ROWB, 0, Tk, ring, lane, wid, voff);
-  tile_dma<D>(vbase, G::ROWB, 0, Tk, ring + TB, lane, wid, voff);
-  if (nt > 1) {
-    tile_dma<D>(kbase, G::ROWB, TKV, Tk, ring + 2 * TB, lane, wid, voff);
-    tile_dma<D>(vbase, G::ROWB, TKV, Tk, ring + 3 * TB, lane, wid, voff);
-  }
-#pragma unroll
-  for (int f = 0; f < 2; ++f) {
-    const int qu = q0 + 16 * f + l15;
-    const int q = qu < Tq ? qu : Tq - 1;
-    lse2[f] = lse[(size_t)bh * Tq + q] * LOG2E;
-    float part = 0.f;
-#pragma unroll
-    for (int ks = 0; ks < NKS; ++ks) {
-      const size_t tok = ((size_t)b * Tq + q) * (H * D) + h * D + ks * 32 + lg * 8;
-      qf[f][ks] = *reinterpret_cast<const uint4*>(qh + ((size_t)bh * Tq + q) * D + ks * 32 + lg * 8);
-      gf[f][ks] = *reinterpret_cast<const uint4*>(dout + tok);
-      const uint4 of = *reinterpret_cast<const uint4*>(og + tok);
-      const bf16x8 a = __builtin_bit_cast(bf16x8, gf[f][ks]), c = __builtin_bit_cast(bf16x8, of);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) part += (float)a[e] * (float)c[e];
-    }
-    part += __shfl_xor(part, 16, 64);   // the row's D columns live on the 4 lanes l15 + 16*lg
-    part += __shfl_xor(part, 32, 64);
-    dl[f] = part;
-    if (lg == 0 && qu < Tq) {   // side buffer for the dk/dv kernel: -delta and -lse in log2 units
-      delta[(size_t)bh * Tq + qu] = -part;
-      delta[((size_t)(gridDim.x / ntile) + bh) * Tq + qu] = -lse2[f];
-    }
-  }
-  f32x4 dq[NDF][2];
-#pragma unroll
-  for (int i = 0; i < NDF; ++i)
-#pragma unroll
-    for (int f = 0; f < 2; ++f) dq[i][f] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int f = 0; f < 2; ++f) {
-    settle(lse2[f]);
-    settle(dl[f]);
-#pragma unroll
-    for (int ks = 0; ks < NKS; ++ks) {
-      settle(qf[f][ks]);
-      settle(gf[f][ks]);
-    }
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  f32x4 ndl[2];
-#pragma unroll
-  for (int f = 0; f < 2; ++f) {
-    ndl[f] = (f32x4){-dl[f], -dl[f], -dl[f], -dl[f]};
-    asm volatile("" : "+v"(ndl[f]));
-  }
-  int cur = 0;
-  const bool wave_active = q0 < Tq;
-  auto tile_body = [&](const int t, auto masked_) {
-    constexpr bool MASKED = decltype(masked_)::value;
-    if (t + 2 < nt) {
-      const int sl = cur == 0 ? 2 : cur - 1;
-      tile_dma<D>(kbase, G::ROWB, (t + 2) * TKV, Tk, ring + (2 * sl) * TB, lane, wid, voff);
-      tile_dma<D>(vbase, G::ROWB, (t + 2) * TKV, Tk, ring + (2 * sl + 1) * TB, lane, wid, voff);
-    }
-    if (wave_active) {
-      const char* kt = &lds[cur][0][0];
-      const char* vt = &lds[cur][1][0];
-      const int nvalid = MASKED ? Tk - t * TKV : TKV;
-      const int nkf = MASKED ? (nvalid + 15) >> 4 : NKF, ns2 = MASKED ? (nvalid + 31) >> 5 : NS2;
-#pragma unroll
-      for (int s2 = 0; s2 < NS2; ++s2) {
-        if (MASKED && s2 >= ns2) continue;
-        f32x4 ds_[2][2];  // [kk][f] for key frags kf = 2*s2 + kk
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-          const int kf = 2 * s2 + kk;
-          if (!MASKED || kf < nkf) {
-            uint4 a[NKS], v[NKS];
-#pragma unroll
-            for (int ks = 0; ks < NKS; ++ks) {
-              a[ks] = row_frag<D>(kt, kf * 16, ks, l15, lg);
-              v[ks] = row_frag<D>(vt, kf * 16, ks, l15, lg);
-            }
-#pragma unroll
-            for (int f = 0; f < 2; ++f) {
-              f32x4 z = {0.f, 0.f, 0.f, 0.f}, w = ndl[f];
-#pragma unroll
-              for (int ks = 0; ks < NKS; ++ks) z = mfma16(a[ks], qf[f][ks], z);   // S^T
-#pragma unroll
-              for (int ks = 0; ks < NKS; ++ks) w = mfma16(v[ks], gf[f][ks], w);   // dP^T - delta
-#pragma unroll
-              for (int r = 0; r < 4; ++r) {
-                const bool valid = !MASKED || (kf * 16 + lg * 4 + r) < nvalid;
-                const float p = valid ? fast_exp2(z[r] * c2 - lse2[f]) : 0.f;
-                ds_[kk][f][r] = p * w[r];   // the softmax scale is applied once, to the dQ accumulators
-              }
-            }
-          } else {
-            ds_[kk][0] = (f32x4){0.f, 0.f, 0.f, 0.f};
-            ds_[kk][1] = ds_[kk][0];
-          }
-        }
-        uint4 dsf[2];
-#pragma unroll
-        for (int f = 0; f < 2; ++f) dsf[f] = pack8(ds_[0][f], ds_[1][f]);
-        // dQ^T[df][f] += K^T dS^T
-#pragma unroll
-        for (int df = 0; df < NDF; ++df) {
-          const uint4 ka = tr_frag<D>(kt, s2 * 32, df * 16, l15, lg);
-#pragma unroll
-          for (int f = 0; f < 2; ++f) dq[df][f] = mfma16(ka, dsf[f], dq[df][f]);
-        }
-      }
-    }
-    if (t + 2 < nt)
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * TD) : "memory");
-    else
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    cur = cur == 2 ? 0 : cur + 1;
-  };
-  for (int t = 0; t + 1 < nt; ++t) tile_body(t, std::false_type{});
-  if (Tk % TKV)
-    tile_body(nt - 1, std::true_type{});
-  else
-    tile_body(nt - 1, std::false_type{});
-#pragma unroll
-  for (int i = 0; i < NDF; ++i)
-#pragma unroll
-    for (int f = 0; f < 2; ++f) dq[i][f] = dq[i][f] * scale;
-  if (wave_active)
-    store_tile<D, 2>(dq, &lds[0][0][0] + wid * 32 * G::ROWB, dqh + ((size_t)bh * Tq + q0) * D, (size_t)D, Tq - q0, lane);
-}
-
-// ------------------------------------------------------------------------------------------ dK, dV (see attn_bwd_dkv_mfma_kernel)
-// One workgroup = 4 waves x 16 NKW keys; the query tiles of Q and dO (+ their -lse / -delta rows, 64 floats each whatever
-// the tile height) arrive by LDS-DMA into a 3-slot ring two tiles ahead.
-template <int D>
-__global__ __launch_bounds__(256, Geo<D>::OCC_DKV) void attn_bwd_dkv_kernel(const bf16* __restrict__ dout, const bf16* __restrict__ qh,
-                                                              const bf16* __restrict__ kh, const bf16* __restrict__ vh,
-                                                              const float* __restrict__ delta, float scale,
-                                                              bf16* __restrict__ dkh, bf16* __restrict__ dvh, int H, int Tq,
-                                                              int Tk) {
-  using G = Geo<D>;
-  constexpr int TKV = G::TKV, TB = G::TILE_BYTES, NKS = G::NKS, NDF = G::NDF, NKF = G::NKF, NS2 = G::NS2;
-  constexpr int TD = G::TILE_DMA, NKW = G::NKW, KWG = G::KWG;
-  constexpr int SLOT = 2 * TB + 512;   // Q tile | dO tile | -lse[64] | -delta[64]
-  __shared__ __attribute__((aligned(16))) char lds[3 * SLOT];
-  static_assert(sizeof(lds) >= 4 * 16 * NKW * G::ROWB, "the ring doubles as the output store scratch");
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int l15 = lane & 15, lg = lane >> 4;
-  const int ntile = (Tk + KWG - 1) / KWG;
-  int bh, tile_;
-  work_of(ntile, bh, tile_);
-  const int b = bh / H, h = bh % H;
-  const int k0 = tile_ * KWG + wid * 16 * NKW;
-  const bf16* qbase = qh + (size_t)bh * Tq * D;
-  const bf16* gbase = dout + (size_t)b * Tq * (H * D) + h * D;
-  const float* dbase = delta + (size_t)bh * Tq;                                // -delta, written by the dq kernel
-  const float* lbase = delta + ((size_t)(gridDim.x / ntile) + bh) * Tq;        // -lse * log2(e), written by the dq kernel
-  const float c2 = scale * LOG2E;
-  const int nt = (Tq + TKV - 1) / TKV;
-  const unsigned ring = lds_addr(&lds[0]);
-
-  const unsigned ldg_bytes = (unsigned)(H * D * 2);
-  unsigned voff_q[TD], voff_g[TD];
-#pragma unroll
-  for (int i = 0; i < TD; ++i) {
-    voff_q[i] = tile_voff<D>(i, G::ROWB, lane, wid);
-    voff_g[i] = tile_voff<D>(i, ldg_bytes, lane, wid);
-  }
-  auto tile_issue = [&](int t, int slot) {
-    const unsigned so = ring + (unsigned)slot * SLOT;
-    tile_dma<D>(qbase, G::ROWB, t * TKV, Tq, so, lane, wid, voff_q);
-    tile_dma<D>(gbase, ldg_bytes, t * TKV, Tq, so + TB, lane, wid, voff_g);
-    int q = t * TKV + lane;
-    q = q < Tq ? q : Tq - 1;
-    glds4a(lbase + q, so + 2 * TB);        // every wave writes the same 256 bytes (keeps vmcnt uniform)
-    glds4a(dbase + q, so + 2 * TB + 256);
-  };
-  tile_issue(0, 0);
-  if (nt > 1) tile_issue(1, 1);
-
-  uint4 kf_[NKW][NKS], vf_[NKW][NKS];  // K / V rows of this wave's keys (MFMA-B operands)
-#pragma unroll
-  for (int f = 0; f < NKW; ++f) {
-    int k = k0 + 16 * f + l15;
-    k = k < Tk ? k : Tk - 1;
-#pragma unroll
-    for (int ks = 0; ks < NKS; ++ks) {
-      kf_[f][ks] = *reinterpret_cast<const uint4*>(kh + ((size_t)bh * Tk + k) * D + ks * 32 + lg * 8);
-      vf_[f][ks] = *reinterpret_cast<const uint4*>(vh + ((size_t)bh * Tk + k) * D + ks * 32 + lg * 8);
-    }
-  }
-#pragma unroll
-  for (int f = 0; f < NKW; ++f)
-#pragma unroll
-    for (int ks = 0; ks < NKS; ++ks) {
-      settle(kf_[f][ks]);
-      settle(vf_[f][ks]);
-    }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-
-  f32x4 dk[NDF][NKW], dv[NDF][NKW];  // rows d = 16df + 4lg + r, col key = 16f + l15
-#pragma unroll
-  for (int i = 0; i < NDF; ++i)
-#pragma unroll
-    for (int f = 0; f < NKW; ++f) {
-      dk[i][f] = (f32x4){0.f, 0.f, 0.f, 0.f};
-      dv[i][f] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    }
-  const bool wave_active = k0 < Tk;
-  int cur = 0;
-  auto tile_body = [&](const int t, auto masked_) {
-    constexpr bool MASKED = decltype(masked_)::value;
-    if (t + 2 < nt) tile_issue(t + 2, cur == 0 ? 2 : cur - 1);
-    if (wave_active) {
-      const char* qt = &lds[cur * SLOT];
-      const char* gt = qt + TB;
-      const float* st = reinterpret_cast<const float*>(qt + 2 * TB);
-      const int nvalid = MASKED ? Tq - t * TKV : TKV;
-      const int nqf = MASKED ? (nvalid + 15) >> 4 : NKF, ns2 = MASKED ? (nvalid + 31) >> 5 : NS2;
-#pragma unroll
-      for (int s2 = 0; s2 < NS2; ++s2) {
-        if (MASKED && s2 >= ns2) continue;
-        uint2 ph[2][NKW], sh[2][NKW];  // [qq][key frag] packed bf16 P / dS of query frag 2*s2 + qq
-#pragma unroll
-        for (int qq = 0; qq < 2; ++qq) {
-          const int qfi = 2 * s2 + qq;
-          if (!MASKED || qfi < nqf) {
-            uint4 a[NKS], g[NKS];
-#pragma unroll
-            for (int ks = 0; ks < NKS; ++ks) {
-              a[ks] = row_frag<D>(qt, qfi * 16, ks, l15, lg);
-              g[ks] = row_frag<D>(gt, qfi * 16, ks, l15, lg);
-            }
-            f32x4 nl4 = *reinterpret_cast<const f32x4*>(st + qfi * 16 + 4 * lg);        // -lse (log2 units)
-            f32x4 nd4 = *reinterpret_cast<const f32x4*>(st + 64 + qfi * 16 + 4 * lg);   // -delta
-            asm volatile("" : "+v"(nd4));
-#pragma unroll
-            for (int f = 0; f < NKW; ++f) {
-              f32x4 z = {0.f, 0.f, 0.f, 0.f}, w = nd4;
-#pragma unroll
-              for (int ks = 0; ks < NKS; ++ks) z = mfma16(a[ks], kf_[f][ks], z);   // S[q][key]
-#pragma unroll
-              for (int ks = 0; ks < NKS; ++ks) w = mfma16(g[ks], vf_[f][ks], w);   // dP[q][key] - delta[q]
-              f32x4 p, dsv;
-#pragma unroll
-              for (int r = 0; r < 4; ++r) {
-                float pr = fast_exp2(z[r] * c2 + nl4[r]);
-                if (MASKED && qfi * 16 + lg * 4 + r >= nvalid) pr = 0.f;
-                p[r] = pr;
-                dsv[r] = pr * w[r];
-              }
-              ph[qq][f] = pack4(p);
-              sh[qq][f] = pack4(dsv);
-            }
-          } else {
-#pragma unroll
-            for (int f = 0; f < NKW; ++f) ph[qq][f] = sh[qq][f] = make_uint2(0u, 0u);
-          }
-        }
-        uint4 pb[NKW], sb[NKW];
-#pragma unroll
-        for (int f = 0; f < NKW; ++f) {
-          pb[f] = make_uint4(ph[0][f].x, ph[0][f].y, ph[1][f].x, ph[1][f].y);
-          sb[f] = make_uint4(sh[0][f].x, sh[0][f].y, sh[1][f].x, sh[1][f].y);
-        }
-#pragma unroll
-        for (int df = 0; df < NDF; ++df) {
-          const uint4 ga = tr_frag<D>(gt, s2 * 32, df * 16, l15, lg);  // dO^T[d][q slots]
-          const uint4 qa = tr_frag<D>(qt, s2 * 32, df * 16, l15, lg);  // Q^T[d][q slots]
-#pragma unroll
-          for (int f = 0; f < NKW; ++f) {
-            dv[df][f] = mfma16(ga, pb[f], dv[df][f]);
-            dk[df][f] = mfma16(qa, sb[f], dk[df][f]);
-          }
-        }
-      }
-    }
-    if (t + 2 < nt)
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * TD + 2) : "memory");
-    else
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    cur = cur == 2 ? 0 : cur + 1;
-  };
-  for (int t = 0; t + 1 < nt; ++t) tile_body(t, std::false_type{});
-  if (Tq % TKV)
-    tile_body(nt - 1, std::true_type{});
-  else
-    tile_body(nt - 1, std::false_type{});
-#pragma unroll
-  for (int i = 0; i < NDF; ++i)
-#pragma unroll
-    for (int f = 0; f < NKW; ++f) dk[i][f] = dk[i][f] * scale;
-  char* scr = &lds[0] + wid * 16 * NKW * G::ROWB;   // (the tile loop ended with a barrier: the ring is free)
-  if (wave_active) {
-    store_tile<D, NKW>(dk, scr, dkh + ((size_t)bh * Tk + k0) * D, (size_t)D, Tk - k0, lane);
-    __builtin_amdgcn_wave_barrier();
-    store_tile<D, NKW>(dv, scr, dvh + ((size_t)bh * Tk + k0) * D, (size_t)D, Tk - k0, lane);
-  }
-}
-
 template <int D>
 int launch_fwd(const void* qh, const void* kh, const void* vh, float scale, float qpre, const float* sqk, float c_q, void* o,
                float* lse, int B, int H, int Tq, int Tk, hipStream_t s) {
-  hipLaunchKernelGGL(attn_fwd_kernel<D>, dim3((unsigned)(cdiv(Tq, 128) * B * H)), dim3(256), 0, s, (const bf16*)qh,
+  hipLaunchKernelGGL(attn_fwd_mfma_kernel<D>, dim3((unsigned)(cdiv(Tq, 128) * B * H)), dim3(256), 0, s, (const bf16*)qh,
                      (const bf16*)kh, (const bf16*)vh, scale, qpre, sqk, c_q, (bf16*)o, lse, H, Tq, Tk);
   NVIT_CHECK_LAUNCH("attn_fwd_mfma");
   return NVIT_OK;
@@ -1839,18 +1290,18 @@ int launch_fwd(const void* qh, const void* kh, const void* vh, float scale, floa
 template <int D>
 int launch_bwd(const void* dout, const void* qh, const void* kh, const void* vh, const void* o, const float* lse,
                float* delta, float scale, void* dqh, void* dkh, void* dvh, int B, int H, int Tq, int Tk, hipStream_t s) {
-  hipLaunchKernelGGL(attn_bwd_dq_kernel<D>, dim3((unsigned)(cdiv(Tq, 128) * B * H)), dim3(256), 0, s, (const bf16*)dout,
-                     (const bf16*)qh, (const bf16*)kh, (const bf16*)vh, lse, (const bf16*)o, delta, scale, (bf16*)dqh, H,
-                     Tq, Tk);
+  dim3 gq((unsigned)(cdiv(Tq, 128) * B * H)), gk((unsigned)(cdiv(Tk, Geo<D>::KWG) * B * H));
+  QkFuse none{};
+  none.xs = 1.0f;
+  hipLaunchKernelGGL((attn_bwd_dq_mfma_kernel<D, false>), gq, dim3(256), 0, s, (const bf16*)dout, (const bf16*)qh,
+                     (const bf16*)kh, (const bf16*)vh, lse, (const bf16*)o, delta, scale, 1.0f, (bf16*)dqh, H, Tq, Tk,
+                     none);
   NVIT_CHECK_LAUNCH("attn_bwd_dq_mfma");
-  hipLaunchKernelGGL(attn_bwd_dkv_kernel<D>, dim3((unsigned)(cdiv(Tk, Geo<D>::KWG) * B * H)), dim3(256), 0, s,
-                     (const bf16*)dout, (const bf16*)qh, (const bf16*)kh, (const bf16*)vh, (const float*)delta, scale,
-                     (bf16*)dkh, (bf16*)dvh, H, Tq, Tk);
+  hipLaunchKernelGGL((attn_bwd_dkv_mfma_kernel<D, false>), gk, dim3(256), 0, s, (const bf16*)dout, (const bf16*)qh,
+                     (const bf16*)kh, (const bf16*)vh, lse, delta, scale, 1.0f, (bf16*)dkh, (bf16*)dvh, H, Tq, Tk, none);
   NVIT_CHECK_LAUNCH("attn_bwd_dkv_mfma");
   return NVIT_OK;
 }
-
-}  // namespace hd
 
 }  // namespace
 
@@ -1858,13 +1309,11 @@ int nvit_attn_fwd_mfma(const void* qh, const void* kh, const void* vh, float sca
                        float c_q, void* o, float* lse, int B, int H, int Tq, int Tk, int d, hipStream_t s) {
   NVIT_REQUIRE(d == 32 || d == 64 || d == 128, "attn_fwd: the MFMA kernel supports head dims 32, 64 and 128 (got %d)", d);
   NVIT_REQUIRE(qpre > 0.f, "attn_fwd: the q pre-scale must be positive (got %g)", (double)qpre);
-  if (d == 32) return hd::launch_fwd<32>(qh, kh, vh, scale, qpre, sqk, c_q, o, lse, B, H, Tq, Tk, s);
-  if (d == 128) return hd::launch_fwd<128>(qh, kh, vh, scale, qpre, sqk, c_q, o, lse, B, H, Tq, Tk, s);
-  dim3 grid((unsigned)(cdiv(Tq, 128) * B * H));
-  hipLaunchKernelGGL(attn_fwd_mfma_kernel, grid, dim3(256), 0, s, (const bf16*)qh, (const bf16*)kh, (const bf16*)vh,
-                     scale, qpre, sqk, c_q, (bf16*)o, lse, H, Tq, Tk);
-  NVIT_CHECK_LAUNCH("attn_fwd_mfma");
-  return NVIT_OK;
+  switch (d) {
+    case 32: return launch_fwd<32>(qh, kh, vh, scale, qpre, sqk, c_q, o, lse, B, H, Tq, Tk, s);
+    case 64: return launch_fwd<64>(qh, kh, vh, scale, qpre, sqk, c_q, o, lse, B, H, Tq, Tk, s);
+    default: return launch_fwd<128>(qh, kh, vh, scale, qpre, sqk, c_q, o, lse, B, H, Tq, Tk, s);
+  }
 }
 
 int nvit_attn_bwd_mfma(const void* dout, const void* qh, const void* kh, const void* vh, const void* o, const float* lse,
@@ -1872,19 +1321,11 @@ int nvit_attn_bwd_mfma(const void* dout, const void* qh, const void* kh, const v
                        int d, hipStream_t s) {
   NVIT_REQUIRE(d == 32 || d == 64 || d == 128, "attn_bwd: the MFMA kernel supports head dims 32, 64 and 128 (got %d)", d);
   NVIT_REQUIRE(o != nullptr && delta != nullptr, "attn_bwd: the attention output and the [2,B,H,Tq] side buffer are required");
-  if (d == 32) return hd::launch_bwd<32>(dout, qh, kh, vh, o, lse, delta, scale, dqh, dkh, dvh, B, H, Tq, Tk, s);
-  if (d == 128) return hd::launch_bwd<128>(dout, qh, kh, vh, o, lse, delta, scale, dqh, dkh, dvh, B, H, Tq, Tk, s);
-  dim3 gq((unsigned)(cdiv(Tq, 128) * B * H)), gk((unsigned)(cdiv(Tk, 128) * B * H));
-  QkFuse none{};
-  none.xs = 1.0f;
-  hipLaunchKernelGGL(attn_bwd_dq_mfma_kernel<false>, gq, dim3(256), 0, s, (const bf16*)dout, (const bf16*)qh,
-                     (const bf16*)kh, (const bf16*)vh, lse, (const bf16*)o, delta, scale, 1.0f, (bf16*)dqh, H, Tq, Tk,
-                     none);
-  NVIT_CHECK_LAUNCH("attn_bwd_dq_mfma");
-  hipLaunchKernelGGL(attn_bwd_dkv_mfma_kernel<false>, gk, dim3(256), 0, s, (const bf16*)dout, (const bf16*)qh,
-                     (const bf16*)kh, (const bf16*)vh, lse, delta, scale, 1.0f, (bf16*)dkh, (bf16*)dvh, H, Tq, Tk, none);
-  NVIT_CHECK_LAUNCH("attn_bwd_dkv_mfma");
-  return NVIT_OK;
+  switch (d) {
+    case 32: return launch_bwd<32>(dout, qh, kh, vh, o, lse, delta, scale, dqh, dkh, dvh, B, H, Tq, Tk, s);
+    case 64: return launch_bwd<64>(dout, qh, kh, vh, o, lse, delta, scale, dqh, dkh, dvh, B, H, Tq, Tk, s);
+    default: return launch_bwd<128>(dout, qh, kh, vh, o, lse, delta, scale, dqh, dkh, dvh, B, H, Tq, Tk, s);
+  }
 }
 
 // (tests) 1: hand-placed dK/dV main loop where it applies (default), 0: the compiler-built kernel
@@ -1906,7 +1347,7 @@ int nvit_attn_bwd_mfma_fused(const void* dout, const void* qh, const void* kh, c
   NVIT_REQUIRE(qpre > 0.f, "attn_bwd: the q pre-scale must be positive (got %g)", (double)qpre);
   QkFuse fq{rq, sqk, (bf16*)dq, nullptr, part_q, c_q, 1.0f / qpre, ldq};
   QkFuse fk{rk, sqk, (bf16*)dk, (bf16*)dv, part_k, c_q, 1.0f, ldkv};
-  hipLaunchKernelGGL(attn_bwd_dq_mfma_kernel<true>, gq, dim3(256), 0, s, (const bf16*)dout, (const bf16*)qh,
+  hipLaunchKernelGGL((attn_bwd_dq_mfma_kernel<64, true>), gq, dim3(256), 0, s, (const bf16*)dout, (const bf16*)qh,
                      (const bf16*)kh, (const bf16*)vh, lse, (const bf16*)o, delta, scale, qpre, (bf16*)nullptr, H, Tq, Tk,
                      fq);
   NVIT_CHECK_LAUNCH("attn_bwd_dq_mfma_fused");
@@ -1916,7 +1357,7 @@ int nvit_attn_bwd_mfma_fused(const void* dout, const void* qh, const void* kh, c
                        (const bf16*)kh, (const bf16*)vh, delta, scale, qpre, (bf16*)nullptr, (bf16*)nullptr, H, Tq, Tk, fk.rn,
                        fk.sqk, fk.c_q, fk.out, fk.out_v, fk.ld, fk.part, fk.xs);
   else
-    hipLaunchKernelGGL(attn_bwd_dkv_mfma_kernel<true>, gk, dim3(256), 0, s, (const bf16*)dout, (const bf16*)qh,
+    hipLaunchKernelGGL((attn_bwd_dkv_mfma_kernel<64, true>), gk, dim3(256), 0, s, (const bf16*)dout, (const bf16*)qh,
                        (const bf16*)kh, (const bf16*)vh, lse, delta, scale, qpre, (bf16*)nullptr, (bf16*)nullptr, H, Tq,
                        Tk, fk);
   NVIT_CHECK_LAUNCH("attn_bwd_dkv_mfma_fused");

@@ -1,7 +1,7 @@
 """Attention at head dims 32 and 128: the MFMA kernels (impl 1) and the scalar-FMA kernels (impl 0, d = 128) against
 fp32 SDPA math with the bars of test_gpu_ops.py::test_attention / test_attention_bounded_scores, on ragged and degenerate
-lengths, with operands inside NaN padding and outputs inside sentinel padding; bitwise run-to-run reproducibility; and
-the model at d = 128 and d = 32 against the CPU oracle with the bars of test_gpu_model.py."""
+lengths, with operands inside NaN padding and outputs inside sentinel padding; bitwise run-to-run reproducibility (also
+at d = 64); and the model at d = 128 and d = 32 against the CPU oracle with the bars of test_gpu_model.py."""
 import math
 
 import pytest
@@ -109,9 +109,19 @@ CASES = ([(torch.bfloat16, 1, d, B, H, T) for d in (32, 128) for (B, H, T) in SH
 
 @pytest.mark.parametrize("dtype,impl,d,B,H,T", CASES)
 def test_attention_head_dim(dtype, impl, d, B, H, T):
+    _check_head_dim(dtype, impl, d, B, H, T, math.sqrt(d))
+
+
+@pytest.mark.parametrize("d", [32, 128])
+def test_attention_head_dim_unit_scale(d):
+    """scale * log2(e) == 1 with q not pre-scaled: the backward kernels take their UNIT variant (-lse as the initial
+    accumulator of the score product), which the generic entry reaches at no other scale.  Same reference and bars."""
+    _check_head_dim(torch.bfloat16, 1, d, 2, 2, 130, math.log(2.0))
+
+
+def _check_head_dim(dtype, impl, d, B, H, T, scale):
     from nvit_amd.ops import dt_of
     q, k, v, g = _inputs(dtype, B, H, T, d)
-    scale = math.sqrt(d)
     # (the reference runs in fp64 on the same operands: at d = 128 an fp32 evaluation of the same formula is itself
     #  1.8e-6 - 3.3e-6 away from the exact result on these inputs, at or above the fp32 bar of 2e-6)
     qf, kf, vf = (t.double().requires_grad_(True) for t in (q, k, v))
@@ -180,7 +190,7 @@ def test_attention_bounded_scores_head_dim(d, B, H, T, smul, prescale):
     assert (lse3.cpu() - lse3_ref).abs().max().item() < lse_tol
 
 
-@pytest.mark.parametrize("d", [32, 128])
+@pytest.mark.parametrize("d", [32, 64, 128])
 def test_attention_head_dim_bitwise_reproducible(d):
     from nvit_amd import ops
     from nvit_amd._lib import BF16
