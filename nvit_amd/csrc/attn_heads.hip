@@ -13,7 +13,7 @@
 //
 // q, k, v are read as fp32 (the unrounded projection GEMM outputs, as the unfused SDPA route reads them): the normalise
 // runs on the unrounded values and bf16 appears only in what is stored (O, dq, dk, dv).
-#include "common.h"
+#include "dispatch.h"
 
 namespace {
 
@@ -246,21 +246,16 @@ __global__ __launch_bounds__(64) void attn_heads_bwd_kernel(HeadsArgs a) {
 
 }  // namespace
 
-#define NVIT_HEADS_DISPATCH(C, d, ...)                              \
-  do {                                                              \
-    if ((C) <= 256) { constexpr int NV = 1; NVIT_HEADS_D(d, __VA_ARGS__); }        \
-    else if ((C) <= 512) { constexpr int NV = 2; NVIT_HEADS_D(d, __VA_ARGS__); }   \
-    else if ((C) <= 768) { constexpr int NV = 3; NVIT_HEADS_D(d, __VA_ARGS__); }   \
-    else if ((C) <= 1024) { constexpr int NV = 4; NVIT_HEADS_D(d, __VA_ARGS__); }  \
-    else if ((C) <= 2048) { constexpr int NV = 8; NVIT_HEADS_D(d, __VA_ARGS__); }  \
-    else { constexpr int NV = 16; NVIT_HEADS_D(d, __VA_ARGS__); }                  \
-  } while (0)
-#define NVIT_HEADS_D(d, ...)                              \
-  do {                                                    \
-    if ((d) == 32) { constexpr int D = 32; __VA_ARGS__; }       \
-    else if ((d) == 64) { constexpr int D = 64; __VA_ARGS__; }  \
-    else { constexpr int D = 128; __VA_ARGS__; }                \
-  } while (0)
+// (NV, D, T, NORM) of a call: rows up to 16 vectors per lane, the head dim, the element type of o / dout and the
+// gradients, and whether q and k are normalised here (sqk given)
+template <typename F>
+static auto with_heads_types(int C, int d, int dt, bool norm, F&& f) {
+  return with_row_vecs<16>(C, [&](auto nv) {
+    return with_head_dim(d, [&](auto hd) {
+      return with_elem(dt, [&](auto t) { return with_bool(norm, [&](auto nm) { return f(nv, hd, t, nm); }); });
+    });
+  });
+}
 
 static int heads_check(int dt, int M, int H, int d, int ldq, int ldkv) {
   NVIT_REQUIRE(dt == NVIT_F32 || dt == NVIT_BF16, "attn_heads: bad dt %d", dt);
@@ -286,16 +281,10 @@ extern "C" int nvit_attn_heads_fwd(int dt, const float* q, int ldq, const float*
   const size_t shm = (size_t)2 * C * sizeof(float);
   const double esz = dt == NVIT_F32 ? 4.0 : 2.0;
   ProfScope ps(NVIT_KID_ATTN_FWD, 4.0 * M * H * C, (double)M * C * (12.0 + esz) + 4.0 * M * H, s);
-#define NVIT_HF_LAUNCH(T_, NORM_) \
-  hipLaunchKernelGGL((attn_heads_fwd_kernel<NV, D, T_, NORM_>), dim3(grid), dim3(64), shm, s, a)
-  NVIT_HEADS_DISPATCH(C, d, {
-    if (dt == NVIT_F32) {
-      if (sqk) NVIT_HF_LAUNCH(float, true); else NVIT_HF_LAUNCH(float, false);
-    } else {
-      if (sqk) NVIT_HF_LAUNCH(bf16, true); else NVIT_HF_LAUNCH(bf16, false);
-    }
+  const auto kernel = with_heads_types(C, d, dt, sqk != nullptr, [](auto nv, auto hd, auto t, auto nm) {
+    return &attn_heads_fwd_kernel<nv, hd, tag_t<decltype(t)>, nm>;
   });
-#undef NVIT_HF_LAUNCH
+  launch(kernel, dim3(grid), dim3(64), shm, s, a);
   NVIT_CHECK_LAUNCH("attn_heads_fwd");
   return NVIT_OK;
 }
@@ -316,16 +305,10 @@ extern "C" int nvit_attn_heads_bwd(int dt, const void* dout, const float* q, int
   const size_t shm = ((size_t)2 * C + 3 * H * H + 2 * H) * sizeof(float);
   const double esz = dt == NVIT_F32 ? 4.0 : 2.0;
   ProfScope ps(NVIT_KID_ATTN_BWD, 8.0 * M * H * C, (double)M * C * (12.0 + 4.0 * esz) + 4.0 * M * H, s);
-#define NVIT_HB_LAUNCH(T_, NORM_) \
-  hipLaunchKernelGGL((attn_heads_bwd_kernel<NV, D, T_, NORM_>), dim3(nblk), dim3(64), shm, s, a)
-  NVIT_HEADS_DISPATCH(C, d, {
-    if (dt == NVIT_F32) {
-      if (sqk) NVIT_HB_LAUNCH(float, true); else NVIT_HB_LAUNCH(float, false);
-    } else {
-      if (sqk) NVIT_HB_LAUNCH(bf16, true); else NVIT_HB_LAUNCH(bf16, false);
-    }
+  const auto kernel = with_heads_types(C, d, dt, sqk != nullptr, [](auto nv, auto hd, auto t, auto nm) {
+    return &attn_heads_bwd_kernel<nv, hd, tag_t<decltype(t)>, nm>;
   });
-#undef NVIT_HB_LAUNCH
+  launch(kernel, dim3(nblk), dim3(64), shm, s, a);
   NVIT_CHECK_LAUNCH("attn_heads_bwd");
   return NVIT_OK;
 }

@@ -43,7 +43,7 @@
 // d = 64 only: the fused q/k-normalise epilogues (FUSE, QkFuse) and the hand-placed dK/dV loop (nvit_attn_bwd_qknorm).
 #include <type_traits>
 
-#include "common.h"
+#include "attn_mfma.h"
 
 namespace {
 
@@ -1163,7 +1163,6 @@ __device__ __forceinline__ unsigned long long uni64(const void* p) {
 // 14 of its 31 us, and the kernel ends up 7-13 % slower than the compiler-built one.)
 #include "attn_dkv32_asm.inc"
 
-template <bool FUSE>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_asm32_kernel(const bf16* __restrict__ dout, const bf16* __restrict__ qh,
                                                                   const bf16* __restrict__ kh, const bf16* __restrict__ vh,
                                                                   const float* __restrict__ delta, float scale, float qpre,
@@ -1171,6 +1170,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_asm32_kernel(const bf16* 
                                                                   int Tq, int Tk, const float* fu_rn, const float* fu_sqk,
                                                                   float fu_cq, bf16* fu_out, bf16* fu_outv, int fu_ld,
                                                                   float* fu_part, float fu_xs) {
+  // (always with the fused q/k-normalise epilogue: dkh and dvh are unused, kept so that the argument layout stays as the
+  //  generated loop was tuned with it)
   // (the q/k-normalise operands arrive as scalars and the QkFuse is put together BEHIND the loop: taken by value as one
   //  struct, part of it is parked in LDS from the first instruction on and the address of that slot lives across the loop
   //  statement - one register too many for two waves per SIMD)
@@ -1238,7 +1239,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_asm32_kernel(const bf16* 
   const QkFuse fu{fu_rn, fu_sqk, fu_out, fu_outv, fu_part, fu_cq, fu_xs, fu_ld};
   const bool wave_active = k0 < Tk;
   QkEpiLoads el;
-  if constexpr (FUSE) qk_bwd_epilogue_loads(el, kh + (size_t)bh * Tk * D, fu, k0, Tk, H, b, h, lane);
+  qk_bwd_epilogue_loads(el, kh + (size_t)bh * Tk * D, fu, k0, Tk, H, b, h, lane);
   f32x4 dk[4][2], dv[4][2];
   if (wave_active) {
     const char* mine = &lds[0] + wid * 16384 + lane * 16;
@@ -1257,18 +1258,10 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_asm32_kernel(const bf16* 
 #pragma unroll
     for (int f = 0; f < 2; ++f) dk[i][f] = dk[i][f] * dks;
   char* scr = &lds[0] + wid * 4096;
-  if constexpr (FUSE) {
-    if (wave_active)
-      store_tile<64, 2>(dv, scr, fu.out_v + ((size_t)b * Tk + k0) * fu.ld + h * 64, (size_t)fu.ld, Tk - k0, lane);
-    __builtin_amdgcn_wave_barrier();
-    qk_bwd_epilogue(dk, el, fu, k0, Tk, H, b, h, lane, wid, &lds[0], tile_, ntile, (int)threadIdx.x);
-  } else {
-    if (wave_active) {
-      store_tile<64, 2>(dk, scr, dkh + ((size_t)bh * Tk + k0) * D, (size_t)D, Tk - k0, lane);
-      __builtin_amdgcn_wave_barrier();
-      store_tile<64, 2>(dv, scr, dvh + ((size_t)bh * Tk + k0) * D, (size_t)D, Tk - k0, lane);
-    }
-  }
+  if (wave_active)
+    store_tile<64, 2>(dv, scr, fu.out_v + ((size_t)b * Tk + k0) * fu.ld + h * 64, (size_t)fu.ld, Tk - k0, lane);
+  __builtin_amdgcn_wave_barrier();
+  qk_bwd_epilogue(dk, el, fu, k0, Tk, H, b, h, lane, wid, &lds[0], tile_, ntile, (int)threadIdx.x);
 }
 
 // nvit_set_attn_dkv_asm: 0 = compiler-built kernel; 1 (default) = hand-placed loop
@@ -1353,7 +1346,7 @@ int nvit_attn_bwd_mfma_fused(const void* dout, const void* qh, const void* kh, c
   NVIT_CHECK_LAUNCH("attn_bwd_dq_mfma_fused");
   const int mode = dkv_asm_mode(scale, qpre);
   if (mode == 1)
-    hipLaunchKernelGGL(attn_bwd_dkv_asm32_kernel<true>, gk, dim3(256), 0, s, (const bf16*)dout, (const bf16*)qh,
+    hipLaunchKernelGGL(attn_bwd_dkv_asm32_kernel, gk, dim3(256), 0, s, (const bf16*)dout, (const bf16*)qh,
                        (const bf16*)kh, (const bf16*)vh, delta, scale, qpre, (bf16*)nullptr, (bf16*)nullptr, H, Tq, Tk, fk.rn,
                        fk.sqk, fk.c_q, fk.out, fk.out_v, fk.ld, fk.part, fk.xs);
   else

@@ -1,46 +1,76 @@
 // impl 0: scalar-FMA attention kernels (any element type, fp32 math).  They carry the exact-f32
 // parity mode and serve as the on-device cross-check of the MFMA flash kernels (attn_mfma.hip).
-// One thread owns one query (fwd, dq) or one key (dk/dv); the other side is streamed through
-// LDS in tiles of 32 rows and read by broadcast (head dim 128: four lanes per query or key, see attn_fwd_ref_split).
-#include "common.h"
+// S lanes own one query (fwd, dq) or one key (dk/dv); the other side is streamed through
+// LDS in tiles of 32 rows and read by broadcast.
+#include "attn_mfma.h"
+#include "dispatch.h"
 
 namespace {
 
 constexpr int TILE = 32;
 
+// Lanes per query (or key).  One lane per row up to head dim 64.  At 128 one thread would need q[128] + acc[128] live
+// registers, more than the architectural file holds, so S = 4 adjacent lanes share a row, lane j owning the channels
+// e = S*i + j (i < D / S; the S lanes of a row read S consecutive words of an LDS row: no bank conflict).  Dot products are
+// the lane partials summed by a butterfly over the S lanes (every lane ends with the same bits); at S = 1 that is the plain
+// sum over e in order.
+constexpr int lanes_per_row(int D) { return D > 64 ? 4 : 1; }
+
+template <int S>
+__device__ __forceinline__ float split_sum(float v) {
+#pragma unroll
+  for (int o = 1; o < S; o <<= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// Fills two [TILE][D] LDS tiles as fp32 from rows row_a.. of a and row_b.. of b (row strides lda, ldb elements); rows from
+// n on are zero.  The caller puts the barriers around it.
 template <typename T, int D>
+__device__ __forceinline__ void stage_tiles(float (&as)[TILE][D], float (&bs)[TILE][D], const T* a, size_t row_a, int lda,
+                                            const T* b, size_t row_b, int ldb, int n) {
+  for (int i = threadIdx.x; i < TILE * D; i += 64) {
+    const int r = i / D, e = i % D;
+    float av = 0.f, bv = 0.f;
+    if (r < n) {   // one branch, both loads in flight before the first LDS store
+      av = (float)a[(row_a + r) * lda + e];
+      bv = (float)b[(row_b + r) * ldb + e];
+    }
+    as[r][e] = av;
+    bs[r][e] = bv;
+  }
+}
+
+template <typename T, int D, int S>
 __global__ __launch_bounds__(64) void attn_fwd_ref(const T* qh, const T* kh, const T* vh, float scale, T* o,
                                                     float* lse, int H, int Tq, int Tk) {
+  constexpr int DL = D / S;
   __shared__ float ks[TILE][D], vs[TILE][D];
   const int bh = blockIdx.y, b = bh / H, h = bh % H;
-  const int qi = blockIdx.x * 64 + threadIdx.x;
+  const int j = threadIdx.x % S;
+  const int qi = blockIdx.x * (64 / S) + threadIdx.x / S;
   const bool ok = qi < Tq;
   const T* qp = qh + ((size_t)bh * Tq + (ok ? qi : 0)) * D;
-  float q[D], acc[D];
+  float q[DL], acc[DL];
 #pragma unroll
-  for (int e = 0; e < D; ++e) {
-    q[e] = (float)qp[e] * scale;
-    acc[e] = 0.f;
+  for (int i = 0; i < DL; ++i) {
+    q[i] = (float)qp[S * i + j] * scale;
+    acc[i] = 0.f;
   }
   float m = -INFINITY, l = 0.f;
   for (int k0 = 0; k0 < Tk; k0 += TILE) {
     const int nk = min(TILE, Tk - k0);
-    for (int i = threadIdx.x; i < TILE * D; i += 64) {
-      const int r = i / D, e = i % D;
-      const bool in = r < nk;
-      ks[r][e] = in ? (float)kh[((size_t)bh * Tk + k0 + r) * D + e] : 0.f;
-      vs[r][e] = in ? (float)vh[((size_t)bh * Tk + k0 + r) * D + e] : 0.f;
-    }
+    stage_tiles<T, D>(ks, vs, kh, (size_t)bh * Tk + k0, D, vh, (size_t)bh * Tk + k0, D, nk);
     __syncthreads();
-    for (int j = 0; j < nk; ++j) {
+    for (int kk = 0; kk < nk; ++kk) {
       float s = 0.f;
 #pragma unroll
-      for (int e = 0; e < D; ++e) s += q[e] * ks[j][e];
+      for (int i = 0; i < DL; ++i) s += q[i] * ks[kk][S * i + j];
+      s = split_sum<S>(s);
       const float mn = fmaxf(m, s);
       const float corr = expf(m - mn), p = expf(s - mn);
       l = l * corr + p;
 #pragma unroll
-      for (int e = 0; e < D; ++e) acc[e] = acc[e] * corr + p * vs[j][e];
+      for (int i = 0; i < DL; ++i) acc[i] = acc[i] * corr + p * vs[kk][S * i + j];
       m = mn;
     }
     __syncthreads();
@@ -49,8 +79,8 @@ __global__ __launch_bounds__(64) void attn_fwd_ref(const T* qh, const T* kh, con
     const float inv = 1.0f / l;
     T* op = o + ((size_t)b * Tq + qi) * (H * D) + h * D;
 #pragma unroll
-    for (int e = 0; e < D; ++e) op[e] = (T)(acc[e] * inv);
-    lse[(size_t)bh * Tq + qi] = m + logf(l);
+    for (int i = 0; i < DL; ++i) op[S * i + j] = (T)(acc[i] * inv);
+    if (j == 0) lse[(size_t)bh * Tq + qi] = m + logf(l);
   }
 }
 
@@ -82,182 +112,15 @@ __global__ __launch_bounds__(256) void attn_delta_kernel(const T* dout, const T*
   }
 }
 
-template <typename T, int D>
+template <typename T, int D, int S>
 __global__ __launch_bounds__(64) void attn_bwd_dq_ref(const T* dout, const T* qh, const T* kh, const T* vh,
                                                        const float* lse, const float* delta, float scale, T* dqh,
                                                        int H, int Tq, int Tk) {
+  constexpr int DL = D / S;
   __shared__ float ks[TILE][D], vs[TILE][D];
   const int bh = blockIdx.y, b = bh / H, h = bh % H;
-  const int qi = blockIdx.x * 64 + threadIdx.x;
-  const bool ok = qi < Tq;
-  const int qc = ok ? qi : 0;
-  const T* qp = qh + ((size_t)bh * Tq + qc) * D;
-  const T* gp = dout + ((size_t)b * Tq + qc) * (H * D) + h * D;
-  float q[D], g[D], acc[D];
-#pragma unroll
-  for (int e = 0; e < D; ++e) {
-    q[e] = (float)qp[e] * scale;
-    g[e] = (float)gp[e];
-    acc[e] = 0.f;
-  }
-  const float L = lse[(size_t)bh * Tq + qc], dl = delta[(size_t)bh * Tq + qc];
-  for (int k0 = 0; k0 < Tk; k0 += TILE) {
-    const int nk = min(TILE, Tk - k0);
-    for (int i = threadIdx.x; i < TILE * D; i += 64) {
-      const int r = i / D, e = i % D;
-      const bool in = r < nk;
-      ks[r][e] = in ? (float)kh[((size_t)bh * Tk + k0 + r) * D + e] : 0.f;
-      vs[r][e] = in ? (float)vh[((size_t)bh * Tk + k0 + r) * D + e] : 0.f;
-    }
-    __syncthreads();
-    for (int j = 0; j < nk; ++j) {
-      float s = 0.f, dp = 0.f;
-#pragma unroll
-      for (int e = 0; e < D; ++e) {
-        s += q[e] * ks[j][e];
-        dp += g[e] * vs[j][e];
-      }
-      const float p = expf(s - L);
-      const float ds = p * (dp - dl) * scale;
-#pragma unroll
-      for (int e = 0; e < D; ++e) acc[e] += ds * ks[j][e];
-    }
-    __syncthreads();
-  }
-  if (ok) {
-    T* op = dqh + ((size_t)bh * Tq + qi) * D;
-#pragma unroll
-    for (int e = 0; e < D; ++e) op[e] = (T)acc[e];
-  }
-}
-
-template <typename T, int D>
-__global__ __launch_bounds__(64) void attn_bwd_dkv_ref(const T* dout, const T* qh, const T* kh, const T* vh,
-                                                        const float* lse, const float* delta, float scale, T* dkh,
-                                                        T* dvh, int H, int Tq, int Tk) {
-  __shared__ float qs[TILE][D], gs[TILE][D];
-  __shared__ float ls[TILE], ds_[TILE];
-  const int bh = blockIdx.y, b = bh / H, h = bh % H;
-  const int ki = blockIdx.x * 64 + threadIdx.x;
-  const bool ok = ki < Tk;
-  const int kc = ok ? ki : 0;
-  float k[D], v[D], dk[D], dv[D];
-#pragma unroll
-  for (int e = 0; e < D; ++e) {
-    k[e] = (float)kh[((size_t)bh * Tk + kc) * D + e];
-    v[e] = (float)vh[((size_t)bh * Tk + kc) * D + e];
-    dk[e] = 0.f;
-    dv[e] = 0.f;
-  }
-  for (int q0 = 0; q0 < Tq; q0 += TILE) {
-    const int nq = min(TILE, Tq - q0);
-    for (int i = threadIdx.x; i < TILE * D; i += 64) {
-      const int r = i / D, e = i % D;
-      const bool in = r < nq;
-      qs[r][e] = in ? (float)qh[((size_t)bh * Tq + q0 + r) * D + e] : 0.f;
-      gs[r][e] = in ? (float)dout[((size_t)b * Tq + q0 + r) * (H * D) + h * D + e] : 0.f;
-    }
-    if (threadIdx.x < TILE) {
-      const bool in = threadIdx.x < nq;
-      ls[threadIdx.x] = in ? lse[(size_t)bh * Tq + q0 + threadIdx.x] : 0.f;
-      ds_[threadIdx.x] = in ? delta[(size_t)bh * Tq + q0 + threadIdx.x] : 0.f;
-    }
-    __syncthreads();
-    for (int j = 0; j < nq; ++j) {
-      float s = 0.f, dp = 0.f;
-#pragma unroll
-      for (int e = 0; e < D; ++e) {
-        s += qs[j][e] * k[e];
-        dp += gs[j][e] * v[e];
-      }
-      const float p = expf(s * scale - ls[j]);
-      const float dsv = p * (dp - ds_[j]) * scale;
-#pragma unroll
-      for (int e = 0; e < D; ++e) {
-        dv[e] += p * gs[j][e];
-        dk[e] += dsv * qs[j][e];
-      }
-    }
-    __syncthreads();
-  }
-  if (ok) {
-#pragma unroll
-    for (int e = 0; e < D; ++e) {
-      dkh[((size_t)bh * Tk + ki) * D + e] = (T)dk[e];
-      dvh[((size_t)bh * Tk + ki) * D + e] = (T)dv[e];
-    }
-  }
-}
-
-// Head dim 128: one thread per query would need q[128] + acc[128] live registers, more than the architectural file holds, so
-// S = 4 adjacent lanes share a query (or a key), lane j owning the channels e = S*i + j (i < D / S; the S lanes of a row
-// read S consecutive words of an LDS row: no bank conflict).  Dot products are the lane partials summed by a butterfly over
-// the S lanes (every lane ends with the same bits).  Otherwise the kernels above, statement for statement.
-constexpr int SPLIT = 4;
-__device__ __forceinline__ float split_sum(float v) {
-#pragma unroll
-  for (int o = 1; o < SPLIT; o <<= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-template <typename T, int D>
-__global__ __launch_bounds__(64) void attn_fwd_ref_split(const T* qh, const T* kh, const T* vh, float scale, T* o,
-                                                          float* lse, int H, int Tq, int Tk) {
-  constexpr int DL = D / SPLIT;
-  __shared__ float ks[TILE][D], vs[TILE][D];
-  const int bh = blockIdx.y, b = bh / H, h = bh % H;
-  const int j = threadIdx.x % SPLIT;
-  const int qi = blockIdx.x * (64 / SPLIT) + threadIdx.x / SPLIT;
-  const bool ok = qi < Tq;
-  const T* qp = qh + ((size_t)bh * Tq + (ok ? qi : 0)) * D;
-  float q[DL], acc[DL];
-#pragma unroll
-  for (int i = 0; i < DL; ++i) {
-    q[i] = (float)qp[SPLIT * i + j] * scale;
-    acc[i] = 0.f;
-  }
-  float m = -INFINITY, l = 0.f;
-  for (int k0 = 0; k0 < Tk; k0 += TILE) {
-    const int nk = min(TILE, Tk - k0);
-    for (int i = threadIdx.x; i < TILE * D; i += 64) {
-      const int r = i / D, e = i % D;
-      const bool in = r < nk;
-      ks[r][e] = in ? (float)kh[((size_t)bh * Tk + k0 + r) * D + e] : 0.f;
-      vs[r][e] = in ? (float)vh[((size_t)bh * Tk + k0 + r) * D + e] : 0.f;
-    }
-    __syncthreads();
-    for (int kk = 0; kk < nk; ++kk) {
-      float s = 0.f;
-#pragma unroll
-      for (int i = 0; i < DL; ++i) s += q[i] * ks[kk][SPLIT * i + j];
-      s = split_sum(s);
-      const float mn = fmaxf(m, s);
-      const float corr = expf(m - mn), p = expf(s - mn);
-      l = l * corr + p;
-#pragma unroll
-      for (int i = 0; i < DL; ++i) acc[i] = acc[i] * corr + p * vs[kk][SPLIT * i + j];
-      m = mn;
-    }
-    __syncthreads();
-  }
-  if (ok) {
-    const float inv = 1.0f / l;
-    T* op = o + ((size_t)b * Tq + qi) * (H * D) + h * D;
-#pragma unroll
-    for (int i = 0; i < DL; ++i) op[SPLIT * i + j] = (T)(acc[i] * inv);
-    if (j == 0) lse[(size_t)bh * Tq + qi] = m + logf(l);
-  }
-}
-
-template <typename T, int D>
-__global__ __launch_bounds__(64) void attn_bwd_dq_ref_split(const T* dout, const T* qh, const T* kh, const T* vh,
-                                                             const float* lse, const float* delta, float scale, T* dqh,
-                                                             int H, int Tq, int Tk) {
-  constexpr int DL = D / SPLIT;
-  __shared__ float ks[TILE][D], vs[TILE][D];
-  const int bh = blockIdx.y, b = bh / H, h = bh % H;
-  const int j = threadIdx.x % SPLIT;
-  const int qi = blockIdx.x * (64 / SPLIT) + threadIdx.x / SPLIT;
+  const int j = threadIdx.x % S;
+  const int qi = blockIdx.x * (64 / S) + threadIdx.x / S;
   const bool ok = qi < Tq;
   const int qc = ok ? qi : 0;
   const T* qp = qh + ((size_t)bh * Tq + qc) * D;
@@ -265,71 +128,61 @@ __global__ __launch_bounds__(64) void attn_bwd_dq_ref_split(const T* dout, const
   float q[DL], g[DL], acc[DL];
 #pragma unroll
   for (int i = 0; i < DL; ++i) {
-    q[i] = (float)qp[SPLIT * i + j] * scale;
-    g[i] = (float)gp[SPLIT * i + j];
+    q[i] = (float)qp[S * i + j] * scale;
+    g[i] = (float)gp[S * i + j];
     acc[i] = 0.f;
   }
   const float L = lse[(size_t)bh * Tq + qc], dl = delta[(size_t)bh * Tq + qc];
   for (int k0 = 0; k0 < Tk; k0 += TILE) {
     const int nk = min(TILE, Tk - k0);
-    for (int i = threadIdx.x; i < TILE * D; i += 64) {
-      const int r = i / D, e = i % D;
-      const bool in = r < nk;
-      ks[r][e] = in ? (float)kh[((size_t)bh * Tk + k0 + r) * D + e] : 0.f;
-      vs[r][e] = in ? (float)vh[((size_t)bh * Tk + k0 + r) * D + e] : 0.f;
-    }
+    stage_tiles<T, D>(ks, vs, kh, (size_t)bh * Tk + k0, D, vh, (size_t)bh * Tk + k0, D, nk);
     __syncthreads();
     for (int kk = 0; kk < nk; ++kk) {
       float s = 0.f, dp = 0.f;
 #pragma unroll
       for (int i = 0; i < DL; ++i) {
-        s += q[i] * ks[kk][SPLIT * i + j];
-        dp += g[i] * vs[kk][SPLIT * i + j];
+        s += q[i] * ks[kk][S * i + j];
+        dp += g[i] * vs[kk][S * i + j];
       }
-      s = split_sum(s);
-      dp = split_sum(dp);
+      s = split_sum<S>(s);
+      dp = split_sum<S>(dp);
       const float p = expf(s - L);
       const float ds = p * (dp - dl) * scale;
 #pragma unroll
-      for (int i = 0; i < DL; ++i) acc[i] += ds * ks[kk][SPLIT * i + j];
+      for (int i = 0; i < DL; ++i) acc[i] += ds * ks[kk][S * i + j];
     }
     __syncthreads();
   }
   if (ok) {
     T* op = dqh + ((size_t)bh * Tq + qi) * D;
 #pragma unroll
-    for (int i = 0; i < DL; ++i) op[SPLIT * i + j] = (T)acc[i];
+    for (int i = 0; i < DL; ++i) op[S * i + j] = (T)acc[i];
   }
 }
 
-template <typename T, int D>
-__global__ __launch_bounds__(64) void attn_bwd_dkv_ref_split(const T* dout, const T* qh, const T* kh, const T* vh,
-                                                              const float* lse, const float* delta, float scale, T* dkh,
-                                                              T* dvh, int H, int Tq, int Tk) {
-  constexpr int DL = D / SPLIT;
+template <typename T, int D, int S>
+__global__ __launch_bounds__(64) void attn_bwd_dkv_ref(const T* dout, const T* qh, const T* kh, const T* vh,
+                                                        const float* lse, const float* delta, float scale, T* dkh,
+                                                        T* dvh, int H, int Tq, int Tk) {
+  constexpr int DL = D / S;
   __shared__ float qs[TILE][D], gs[TILE][D];
   __shared__ float ls[TILE], ds_[TILE];
   const int bh = blockIdx.y, b = bh / H, h = bh % H;
-  const int j = threadIdx.x % SPLIT;
-  const int ki = blockIdx.x * (64 / SPLIT) + threadIdx.x / SPLIT;
+  const int j = threadIdx.x % S;
+  const int ki = blockIdx.x * (64 / S) + threadIdx.x / S;
   const bool ok = ki < Tk;
   const int kc = ok ? ki : 0;
   float k[DL], v[DL], dk[DL], dv[DL];
 #pragma unroll
   for (int i = 0; i < DL; ++i) {
-    k[i] = (float)kh[((size_t)bh * Tk + kc) * D + SPLIT * i + j];
-    v[i] = (float)vh[((size_t)bh * Tk + kc) * D + SPLIT * i + j];
+    k[i] = (float)kh[((size_t)bh * Tk + kc) * D + S * i + j];
+    v[i] = (float)vh[((size_t)bh * Tk + kc) * D + S * i + j];
     dk[i] = 0.f;
     dv[i] = 0.f;
   }
   for (int q0 = 0; q0 < Tq; q0 += TILE) {
     const int nq = min(TILE, Tq - q0);
-    for (int i = threadIdx.x; i < TILE * D; i += 64) {
-      const int r = i / D, e = i % D;
-      const bool in = r < nq;
-      qs[r][e] = in ? (float)qh[((size_t)bh * Tq + q0 + r) * D + e] : 0.f;
-      gs[r][e] = in ? (float)dout[((size_t)b * Tq + q0 + r) * (H * D) + h * D + e] : 0.f;
-    }
+    stage_tiles<T, D>(qs, gs, qh, (size_t)bh * Tq + q0, D, dout + h * D, (size_t)b * Tq + q0, H * D, nq);
     if (threadIdx.x < TILE) {
       const bool in = threadIdx.x < nq;
       ls[threadIdx.x] = in ? lse[(size_t)bh * Tq + q0 + threadIdx.x] : 0.f;
@@ -340,17 +193,17 @@ __global__ __launch_bounds__(64) void attn_bwd_dkv_ref_split(const T* dout, cons
       float s = 0.f, dp = 0.f;
 #pragma unroll
       for (int i = 0; i < DL; ++i) {
-        s += qs[qq][SPLIT * i + j] * k[i];
-        dp += gs[qq][SPLIT * i + j] * v[i];
+        s += qs[qq][S * i + j] * k[i];
+        dp += gs[qq][S * i + j] * v[i];
       }
-      s = split_sum(s);
-      dp = split_sum(dp);
+      s = split_sum<S>(s);
+      dp = split_sum<S>(dp);
       const float p = expf(s * scale - ls[qq]);
       const float dsv = p * (dp - ds_[qq]) * scale;
 #pragma unroll
       for (int i = 0; i < DL; ++i) {
-        dv[i] += p * gs[qq][SPLIT * i + j];
-        dk[i] += dsv * qs[qq][SPLIT * i + j];
+        dv[i] += p * gs[qq][S * i + j];
+        dk[i] += dsv * qs[qq][S * i + j];
       }
     }
     __syncthreads();
@@ -358,24 +211,13 @@ __global__ __launch_bounds__(64) void attn_bwd_dkv_ref_split(const T* dout, cons
   if (ok) {
 #pragma unroll
     for (int i = 0; i < DL; ++i) {
-      dkh[((size_t)bh * Tk + ki) * D + SPLIT * i + j] = (T)dk[i];
-      dvh[((size_t)bh * Tk + ki) * D + SPLIT * i + j] = (T)dv[i];
+      dkh[((size_t)bh * Tk + ki) * D + S * i + j] = (T)dk[i];
+      dvh[((size_t)bh * Tk + ki) * D + S * i + j] = (T)dv[i];
     }
   }
 }
 
 }  // namespace
-
-int nvit_attn_fwd_mfma(const void* qh, const void* kh, const void* vh, float scale, float qpre, const float* sqk,
-                       float c_q, void* o, float* lse, int B, int H, int Tq, int Tk, int d, hipStream_t s);
-int nvit_attn_bwd_mfma(const void* dout, const void* qh, const void* kh, const void* vh, const void* o, const float* lse,
-                       float* delta, float scale, void* dqh, void* dkh, void* dvh, int B, int H, int Tq, int Tk,
-                       int d, hipStream_t s);
-
-int nvit_attn_bwd_mfma_fused(const void* dout, const void* qh, const void* kh, const void* vh, const void* o,
-                             const float* lse, float* delta, float scale, const float* rq, const float* rk, const float* sqk,
-                             float c_q, float qpre, void* dq, int ldq, void* dk, void* dv, int ldkv, float* part_q,
-                             float* part_k, int B, int H, int Tq, int Tk, int d, hipStream_t s);
 
 static int attn_fwd_impl(int dt, int impl, const void* qh, const void* kh, const void* vh, float scale, const float* sqk,
                          float c_q, float qpre, void* o, float* lse, int B, int H, int Tq, int Tk, int d, void* stream);
@@ -408,16 +250,14 @@ static int attn_fwd_impl(int dt, int impl, const void* qh, const void* kh, const
     return nvit_attn_fwd_mfma(qh, kh, vh, scale, qpre, sqk, c_q, o, lse, B, H, Tq, Tk, d, s);
   }
   scale = scale / qpre;   // the scalar kernels take the multiplier of q.k directly
-  dim3 grid(cdiv(Tq, 64), B * H), grid_split(cdiv(Tq, 64 / SPLIT), B * H);
-#define L(T, D) \
-  hipLaunchKernelGGL((attn_fwd_ref<T, D>), grid, dim3(64), 0, s, (const T*)qh, (const T*)kh, (const T*)vh, scale, (T*)o, lse, H, Tq, Tk)
-#define LS(T, D)                                                                                                       \
-  hipLaunchKernelGGL((attn_fwd_ref_split<T, D>), grid_split, dim3(64), 0, s, (const T*)qh, (const T*)kh, (const T*)vh,  \
-                     scale, (T*)o, lse, H, Tq, Tk)
-  if (dt == NVIT_F32) { if (d == 32) L(float, 32); else if (d == 64) L(float, 64); else LS(float, 128); }
-  else { if (d == 32) L(bf16, 32); else if (d == 64) L(bf16, 64); else LS(bf16, 128); }
-#undef L
-#undef LS
+  with_elem(dt, [&](auto t) {
+    with_head_dim(d, [&](auto hd) {
+      using T = tag_t<decltype(t)>;
+      constexpr int S = lanes_per_row(hd);
+      launch(attn_fwd_ref<T, hd, S>, dim3(cdiv(Tq, 64 / S), B * H), dim3(64), 0, s, (const T*)qh, (const T*)kh,
+             (const T*)vh, scale, (T*)o, lse, H, Tq, Tk);
+    });
+  });
   NVIT_CHECK_LAUNCH("attn_fwd_ref");
   return NVIT_OK;
 }
@@ -435,33 +275,21 @@ extern "C" int nvit_attn_bwd(int dt, int impl, const void* dout, const void* qh,
     return nvit_attn_bwd_mfma(dout, qh, kh, vh, o, lse, delta, scale, dqh, dkh, dvh, B, H, Tq, Tk, d, s);
   }
   const long long total = (long long)B * Tq * ((H * d) / 8);
-  if (dt == NVIT_F32)
-    hipLaunchKernelGGL(attn_delta_kernel<float>, dim3(cdiv(total, 256)), dim3(256), 0, s, (const float*)dout,
-                       (const float*)o, delta, B, H, Tq, d);
-  else
-    hipLaunchKernelGGL(attn_delta_kernel<bf16>, dim3(cdiv(total, 256)), dim3(256), 0, s, (const bf16*)dout,
-                       (const bf16*)o, delta, B, H, Tq, d);
+  with_elem(dt, [&](auto t) {
+    using T = tag_t<decltype(t)>;
+    launch(attn_delta_kernel<T>, dim3(cdiv(total, 256)), dim3(256), 0, s, (const T*)dout, (const T*)o, delta, B, H, Tq, d);
+  });
   NVIT_CHECK_LAUNCH("attn_delta");
-  dim3 gq(cdiv(Tq, 64), B * H), gk(cdiv(Tk, 64), B * H);
-#define L(T, D)                                                                                                       \
-  do {                                                                                                                \
-    hipLaunchKernelGGL((attn_bwd_dq_ref<T, D>), gq, dim3(64), 0, s, (const T*)dout, (const T*)qh, (const T*)kh,       \
-                       (const T*)vh, lse, delta, scale, (T*)dqh, H, Tq, Tk);                                          \
-    hipLaunchKernelGGL((attn_bwd_dkv_ref<T, D>), gk, dim3(64), 0, s, (const T*)dout, (const T*)qh, (const T*)kh,      \
-                       (const T*)vh, lse, delta, scale, (T*)dkh, (T*)dvh, H, Tq, Tk);                                 \
-  } while (0)
-  dim3 gqs(cdiv(Tq, 64 / SPLIT), B * H), gks(cdiv(Tk, 64 / SPLIT), B * H);
-#define LS(T, D)                                                                                                      \
-  do {                                                                                                                \
-    hipLaunchKernelGGL((attn_bwd_dq_ref_split<T, D>), gqs, dim3(64), 0, s, (const T*)dout, (const T*)qh, (const T*)kh, \
-                       (const T*)vh, lse, delta, scale, (T*)dqh, H, Tq, Tk);                                          \
-    hipLaunchKernelGGL((attn_bwd_dkv_ref_split<T, D>), gks, dim3(64), 0, s, (const T*)dout, (const T*)qh,             \
-                       (const T*)kh, (const T*)vh, lse, delta, scale, (T*)dkh, (T*)dvh, H, Tq, Tk);                   \
-  } while (0)
-  if (dt == NVIT_F32) { if (d == 32) L(float, 32); else if (d == 64) L(float, 64); else LS(float, 128); }
-  else { if (d == 32) L(bf16, 32); else if (d == 64) L(bf16, 64); else LS(bf16, 128); }
-#undef L
-#undef LS
+  with_elem(dt, [&](auto t) {
+    with_head_dim(d, [&](auto hd) {
+      using T = tag_t<decltype(t)>;
+      constexpr int S = lanes_per_row(hd);
+      launch(attn_bwd_dq_ref<T, hd, S>, dim3(cdiv(Tq, 64 / S), B * H), dim3(64), 0, s, (const T*)dout, (const T*)qh,
+             (const T*)kh, (const T*)vh, lse, delta, scale, (T*)dqh, H, Tq, Tk);
+      launch(attn_bwd_dkv_ref<T, hd, S>, dim3(cdiv(Tk, 64 / S), B * H), dim3(64), 0, s, (const T*)dout, (const T*)qh,
+             (const T*)kh, (const T*)vh, lse, delta, scale, (T*)dkh, (T*)dvh, H, Tq, Tk);
+    });
+  });
   NVIT_CHECK_LAUNCH("attn_bwd_ref");
   return NVIT_OK;
 }

@@ -18,12 +18,6 @@
 // row m: epilogue vectors (bias, column scales) are float4 loads and stores are 8/16 bytes.
 #include "gemm_common.h"
 
-int nvit_gemm_nt_persistent_launch(int dt, const NtArgs& g, int tile_n, hipStream_t s);
-int nvit_gemm_nt_fused_launch(const NtArgs& g, int epi, hipStream_t s);
-
-int nvit_gemm_tn_persistent_launch(int dt, const void* A, int lda, const void* B, int ldb, float* ws,
-                                   const float* zeros, int Mred, int N, int K, int splits, hipStream_t s);
-
 namespace {
 
 constexpr int BM = 128, BN = 128;

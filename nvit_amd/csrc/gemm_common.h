@@ -37,6 +37,12 @@ struct NtArgs {
   float* part;        // [2*tiles_m, 2*Fh] column partials of d(suv) per 128-row wave tile (or NULL)
 };
 
+// persistent-GEMM launchers for the C ABI functions in gemm.hip (defined in gemm_p.hip and gemm_tn_p.hip)
+int nvit_gemm_nt_persistent_launch(int dt, const NtArgs& g, int tile_n, hipStream_t s);
+int nvit_gemm_nt_fused_launch(const NtArgs& g, int epi, hipStream_t s);
+int nvit_gemm_tn_persistent_launch(int dt, const void* A, int lda, const void* B, int ldb, float* ws,
+                                   const float* zeros, int Mred, int N, int K, int splits, hipStream_t s);
+
 template <typename T>
 struct Mma;
 template <>

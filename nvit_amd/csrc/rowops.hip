@@ -3,7 +3,7 @@
 // column reductions that turn per-block partial sums into parameter gradients.
 // HBM-bound: one wave owns one row (16-byte loads, all reductions by lane shuffles), rows are
 // grid-strided, per-column partial sums stay in registers until the wave's last row.
-#include "common.h"
+#include "dispatch.h"
 
 namespace {
 
@@ -963,14 +963,38 @@ int row_grid(int M) {
 
 }  // namespace
 
-#define DISPATCH_NV(C, ...)                     \
-  do {                                          \
-    if ((C) <= 256) { constexpr int NV = 1; __VA_ARGS__; }       \
-    else if ((C) <= 512) { constexpr int NV = 2; __VA_ARGS__; }  \
-    else if ((C) <= 768) { constexpr int NV = 3; __VA_ARGS__; }  \
-    else if ((C) <= 1024) { constexpr int NV = 4; __VA_ARGS__; } \
-    else { constexpr int NV = 8; __VA_ARGS__; }                  \
-  } while (0)
+// ---- run-time options -> template instantiation.  Each family picks its kernel in ONE selector built from dispatch.h; the
+// entry points launch through the pointer it returns (families whose kernels take typed pointers launch inside it). ----
+
+// (NV, TY, TL) of the row kernels that read y as y_dt and write their low-precision copy as dt
+template <typename F>
+static auto with_row_types(int C, int y_dt, int dt, F&& f) {
+  return with_row_vecs<8>(C, [&](auto nv) {
+    return with_elem(y_dt, [&](auto ty) { return with_elem(dt, [&](auto tl) { return f(nv, ty, tl); }); });
+  });
+}
+
+// (type read, type written) of a dt that may be NVIT_BF16_F32IN: fp32 in, bf16 out, computed from the unrounded values
+template <typename F>
+static auto with_in_out_elems(int dt, F&& f) {
+  if (dt == NVIT_F32) return f(type_tag<float>{}, type_tag<float>{});
+  if (dt == NVIT_BF16) return f(type_tag<bf16>{}, type_tag<bf16>{});
+  return f(type_tag<float>{}, type_tag<bf16>{});
+}
+
+// The lerp_bwd instantiation for a call's options: nvit_lerp_bwd launches it and nvit_lerp_bwd_blocks sizes that launch's
+// grid from its occupancy, so both go through here.
+static auto lerp_bwd_select(int C, int y_dt, int dt, bool has_add, bool has_skip, bool accum) -> void (*)(LerpBwdArgs) {
+  return with_row_types(C, y_dt, dt, [&](auto nv, auto ty, auto tl) {
+    return with_bool(has_add, [&](auto add) {
+      return with_bool(has_skip, [&](auto skip) {
+        return with_bool(accum, [&](auto acc) {
+          return &lerp_bwd_kernel<nv, tag_t<decltype(ty)>, tag_t<decltype(tl)>, add, skip, acc>;
+        });
+      });
+    });
+  });
+}
 
 extern "C" int nvit_lerp_fwd(int dt, const float* h, const void* y, int y_dt, const float* alpha, float c_a,
                              const float* skip_x, const float* skip, float* out, void* out_lo, int M, int C,
@@ -981,16 +1005,10 @@ extern "C" int nvit_lerp_fwd(int dt, const float* h, const void* y, int y_dt, co
   hipStream_t s = (hipStream_t)stream;
   const int grid = row_grid(M);
   ProfScope ps(NVIT_KID_ROWOPS, 0.0, (double)M * C * (skip_x ? 16.0 : 12.0), s);
-  DISPATCH_NV(C, {
-    if (y_dt == NVIT_F32 && dt == NVIT_F32)
-      hipLaunchKernelGGL((lerp_fwd_kernel<NV, float, float>), dim3(grid), dim3(256), 0, s, a);
-    else if (y_dt == NVIT_F32)
-      hipLaunchKernelGGL((lerp_fwd_kernel<NV, float, bf16>), dim3(grid), dim3(256), 0, s, a);
-    else if (dt == NVIT_F32)
-      hipLaunchKernelGGL((lerp_fwd_kernel<NV, bf16, float>), dim3(grid), dim3(256), 0, s, a);
-    else
-      hipLaunchKernelGGL((lerp_fwd_kernel<NV, bf16, bf16>), dim3(grid), dim3(256), 0, s, a);
+  const auto kernel = with_row_types(C, y_dt, dt, [](auto nv, auto ty, auto tl) {
+    return &lerp_fwd_kernel<nv, tag_t<decltype(ty)>, tag_t<decltype(tl)>>;
   });
+  launch(kernel, dim3(grid), dim3(256), 0, s, a);
   NVIT_CHECK_LAUNCH("lerp_fwd");
   return NVIT_OK;
 }
@@ -999,8 +1017,7 @@ extern "C" int nvit_lerp_fwd(int dt, const float* h, const void* y, int y_dt, co
 // blocks per CU from the occupancy query).  The kernel walks its rows with a grid stride, so a grid of exactly this many
 // blocks keeps every SIMD busy to the end; the round-2 default of 1024 blocks ran as 768 + 256 at C = 768 (3 waves per
 // SIMD): a second, one-third-full round (row kernels 14.9 -> 13.1 ms per Base step with the resident count).
-template <typename K>
-static int resident_blocks(K kernel) {
+static int resident_blocks(void (*kernel)(LerpBwdArgs)) {
   int per_cu = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, 0) != hipSuccess || per_cu < 1) return 0;
   return per_cu * nvit_num_cu();
@@ -1008,27 +1025,7 @@ static int resident_blocks(K kernel) {
 
 extern "C" int nvit_lerp_bwd_blocks(int dt, int y_dt, int C, int has_add, int has_skip, int accum) {
   if (C % 4 != 0 || C <= 0 || C > 2048) return 0;
-  int n = 0;
-#define NVIT_LB_Q3(TY_, TL_, ADD_)                                                                   \
-  {                                                                                                  \
-    if (has_skip && accum) n = resident_blocks(lerp_bwd_kernel<NV, TY_, TL_, ADD_, true, true>);     \
-    else if (has_skip) n = resident_blocks(lerp_bwd_kernel<NV, TY_, TL_, ADD_, true, false>);        \
-    else if (accum) n = resident_blocks(lerp_bwd_kernel<NV, TY_, TL_, ADD_, false, true>);           \
-    else n = resident_blocks(lerp_bwd_kernel<NV, TY_, TL_, ADD_, false, false>);                     \
-  }
-#define NVIT_LB_Q(TY_, TL_)                \
-  {                                        \
-    if (has_add) NVIT_LB_Q3(TY_, TL_, true) \
-    else NVIT_LB_Q3(TY_, TL_, false)       \
-  }
-  DISPATCH_NV(C, {
-    if (y_dt == NVIT_F32 && dt == NVIT_F32) NVIT_LB_Q(float, float)
-    else if (y_dt == NVIT_F32) NVIT_LB_Q(float, bf16)
-    else if (dt == NVIT_F32) NVIT_LB_Q(bf16, float)
-    else NVIT_LB_Q(bf16, bf16)
-  });
-#undef NVIT_LB_Q
-#undef NVIT_LB_Q3
+  const int n = resident_blocks(lerp_bwd_select(C, y_dt, dt, has_add, has_skip, accum));
   return n > 4096 ? 4096 : n;
 }
 
@@ -1045,36 +1042,7 @@ extern "C" int nvit_lerp_bwd(int dt, const float* dout, const void* dout_add, co
   const double lb_bytes = (double)M * C * (4.0 + 4.0 + (y_dt == NVIT_F32 ? 4.0 : 2.0) + 4.0 + (dy ? 4.0 : 0.0) + (dy_lo ? (dt == NVIT_F32 ? 4.0 : 2.0) : 0.0) +
                                            (skip_x ? 8.0 : 0.0) + (accum_dh ? 4.0 : 0.0) + (dout_add ? 2.0 : 0.0));
   ProfScope ps(NVIT_KID_ROWOPS, 0.0, lb_bytes, s);
-#define NVIT_LERP_BWD_LAUNCH3(TY_, TL_, ADD_)                                                                          \
-  {                                                                                                                    \
-    if (skip_x && accum_dh)                                                                                            \
-      hipLaunchKernelGGL((lerp_bwd_kernel<NV, TY_, TL_, ADD_, true, true>), dim3(nblk), dim3(256), 0, s, a);           \
-    else if (skip_x)                                                                                                   \
-      hipLaunchKernelGGL((lerp_bwd_kernel<NV, TY_, TL_, ADD_, true, false>), dim3(nblk), dim3(256), 0, s, a);          \
-    else if (accum_dh)                                                                                                 \
-      hipLaunchKernelGGL((lerp_bwd_kernel<NV, TY_, TL_, ADD_, false, true>), dim3(nblk), dim3(256), 0, s, a);          \
-    else                                                                                                               \
-      hipLaunchKernelGGL((lerp_bwd_kernel<NV, TY_, TL_, ADD_, false, false>), dim3(nblk), dim3(256), 0, s, a);         \
-  }
-#define NVIT_LERP_BWD_LAUNCH(TY_, TL_)          \
-  {                                             \
-    if (dout_add)                               \
-      NVIT_LERP_BWD_LAUNCH3(TY_, TL_, true)     \
-    else                                        \
-      NVIT_LERP_BWD_LAUNCH3(TY_, TL_, false)    \
-  }
-  DISPATCH_NV(C, {
-    if (y_dt == NVIT_F32 && dt == NVIT_F32)
-      NVIT_LERP_BWD_LAUNCH(float, float)
-    else if (y_dt == NVIT_F32)
-      NVIT_LERP_BWD_LAUNCH(float, bf16)
-    else if (dt == NVIT_F32)
-      NVIT_LERP_BWD_LAUNCH(bf16, float)
-    else
-      NVIT_LERP_BWD_LAUNCH(bf16, bf16)
-  });
-#undef NVIT_LERP_BWD_LAUNCH
-#undef NVIT_LERP_BWD_LAUNCH3
+  launch(lerp_bwd_select(C, y_dt, dt, dout_add != nullptr, skip_x != nullptr, accum_dh != 0), dim3(nblk), dim3(256), 0, s, a);
   NVIT_CHECK_LAUNCH("lerp_bwd");
   return NVIT_OK;
 }
@@ -1084,7 +1052,7 @@ extern "C" int nvit_norm_skip_fwd(const float* src, const float* tgt, const floa
   NVIT_REQUIRE(C % 4 == 0 && C <= 2048 && M > 0, "norm_skip_fwd: C=%d must be a multiple of 4 and <= 2048", C);
   hipStream_t s = (hipStream_t)stream;
   const int grid = row_grid(M);
-  DISPATCH_NV(C, { hipLaunchKernelGGL((norm_skip_fwd_kernel<NV>), dim3(grid), dim3(256), 0, s, src, tgt, skip, out, M, C); });
+  with_row_vecs<8>(C, [&](auto nv) { launch(norm_skip_fwd_kernel<nv>, dim3(grid), dim3(256), 0, s, src, tgt, skip, out, M, C); });
   NVIT_CHECK_LAUNCH("norm_skip_fwd");
   return NVIT_OK;
 }
@@ -1093,9 +1061,8 @@ extern "C" int nvit_norm_skip_bwd(const float* dout, const float* src, const flo
                                   float* dtgt, float* part_dskip, int nblk, int M, int C, void* stream) {
   NVIT_REQUIRE(C % 4 == 0 && C <= 2048 && M > 0 && nblk > 0 && nblk <= 4096, "norm_skip_bwd: bad arguments");
   hipStream_t s = (hipStream_t)stream;
-  DISPATCH_NV(C, {
-    hipLaunchKernelGGL((norm_skip_bwd_kernel<NV>), dim3(nblk), dim3(256), 0, s, dout, src, tgt, skip, dsrc, dtgt,
-                       part_dskip, M, C);
+  with_row_vecs<8>(C, [&](auto nv) {
+    launch(norm_skip_bwd_kernel<nv>, dim3(nblk), dim3(256), 0, s, dout, src, tgt, skip, dsrc, dtgt, part_dskip, M, C);
   });
   NVIT_CHECK_LAUNCH("norm_skip_bwd");
   return NVIT_OK;
@@ -1106,7 +1073,7 @@ extern "C" int nvit_rmsnorm_fwd(const float* x, const float* w, float eps, float
   NVIT_REQUIRE(C % 4 == 0 && C <= 2048 && M > 0, "rmsnorm_fwd: C=%d must be a multiple of 4 and <= 2048", C);
   hipStream_t s = (hipStream_t)stream;
   const int grid = row_grid(M);
-  DISPATCH_NV(C, { hipLaunchKernelGGL((rmsnorm_fwd_kernel<NV>), dim3(grid), dim3(256), 0, s, x, w, eps, out, rstd, M, C); });
+  with_row_vecs<8>(C, [&](auto nv) { launch(rmsnorm_fwd_kernel<nv>, dim3(grid), dim3(256), 0, s, x, w, eps, out, rstd, M, C); });
   NVIT_CHECK_LAUNCH("rmsnorm_fwd");
   return NVIT_OK;
 }
@@ -1115,8 +1082,8 @@ extern "C" int nvit_rmsnorm_bwd(const float* dout, const float* x, const float* 
                                 float* part_dw, int nblk, int M, int C, void* stream) {
   NVIT_REQUIRE(C % 4 == 0 && C <= 2048 && M > 0 && nblk > 0 && nblk <= 4096, "rmsnorm_bwd: bad arguments");
   hipStream_t s = (hipStream_t)stream;
-  DISPATCH_NV(C, {
-    hipLaunchKernelGGL((rmsnorm_bwd_kernel<NV>), dim3(nblk), dim3(256), 0, s, dout, x, w, rstd, dx, part_dw, M, C);
+  with_row_vecs<8>(C, [&](auto nv) {
+    launch(rmsnorm_bwd_kernel<nv>, dim3(nblk), dim3(256), 0, s, dout, x, w, rstd, dx, part_dw, M, C);
   });
   NVIT_CHECK_LAUNCH("rmsnorm_bwd");
   return NVIT_OK;
@@ -1132,20 +1099,14 @@ extern "C" int nvit_res_rmsnorm_fwd(int dt, const float* a, const void* y, int y
   const int grid = row_grid(M);
   ProfScope ps(NVIT_KID_ROWOPS, 0.0, (double)M * C * (8.0 + (y ? (y_dt == NVIT_F32 ? 4.0 : 2.0) : 0.0) +
                                                        (out_lo ? (dt == NVIT_F32 ? 4.0 : 2.0) : 0.0)), s);
-#define NVIT_RRF_LAUNCH(TL_)                                                                                 \
-  {                                                                                                          \
-    if (!y)                                                                                                  \
-      hipLaunchKernelGGL((res_rmsnorm_fwd_kernel<NV, float, TL_, false>), dim3(grid), dim3(256), 0, s, ar);  \
-    else if (y_dt == NVIT_F32)                                                                               \
-      hipLaunchKernelGGL((res_rmsnorm_fwd_kernel<NV, float, TL_, true>), dim3(grid), dim3(256), 0, s, ar);   \
-    else                                                                                                     \
-      hipLaunchKernelGGL((res_rmsnorm_fwd_kernel<NV, bf16, TL_, true>), dim3(grid), dim3(256), 0, s, ar);    \
-  }
-  DISPATCH_NV(C, {
-    if (dt == NVIT_F32) NVIT_RRF_LAUNCH(float)
-    else NVIT_RRF_LAUNCH(bf16)
+  const auto kernel = with_row_vecs<8>(C, [&](auto nv) {
+    return with_elem(dt, [&](auto tl) {
+      using TL = tag_t<decltype(tl)>;
+      if (!y) return &res_rmsnorm_fwd_kernel<nv, float, TL, false>;   // without y, TY is float: no <bf16, false> is built
+      return with_elem(y_dt, [&](auto ty) { return &res_rmsnorm_fwd_kernel<nv, tag_t<decltype(ty)>, TL, true>; });
+    });
   });
-#undef NVIT_RRF_LAUNCH
+  launch(kernel, dim3(grid), dim3(256), 0, s, ar);
   NVIT_CHECK_LAUNCH("res_rmsnorm_fwd");
   return NVIT_OK;
 }
@@ -1162,41 +1123,19 @@ extern "C" int nvit_res_rmsnorm_bwd(int dt, const float* g, const void* g_add, c
   const double tl = dt == NVIT_F32 ? 4.0 : 2.0;
   ProfScope ps(NVIT_KID_ROWOPS, 0.0, (double)M * C * (12.0 + (y ? (y_dt == NVIT_F32 ? 4.0 : 2.0) : 0.0) +
                                                        (g_add ? tl : 0.0) + (accum ? 4.0 : 0.0) + (dz_lo ? tl : 0.0)), s);
-#define NVIT_RRB_LAUNCH2(TL_, ADD_)                                                                               \
-  {                                                                                                               \
-    if (!y)                                                                                                       \
-      hipLaunchKernelGGL((res_rmsnorm_bwd_kernel<NV, float, TL_, false, ADD_>), dim3(nblk), dim3(256), 0, s, ar); \
-    else if (y_dt == NVIT_F32)                                                                                    \
-      hipLaunchKernelGGL((res_rmsnorm_bwd_kernel<NV, float, TL_, true, ADD_>), dim3(nblk), dim3(256), 0, s, ar);  \
-    else                                                                                                          \
-      hipLaunchKernelGGL((res_rmsnorm_bwd_kernel<NV, bf16, TL_, true, ADD_>), dim3(nblk), dim3(256), 0, s, ar);   \
-  }
-#define NVIT_RRB_LAUNCH(TL_)             \
-  {                                      \
-    if (g_add) NVIT_RRB_LAUNCH2(TL_, true) \
-    else NVIT_RRB_LAUNCH2(TL_, false)     \
-  }
-  DISPATCH_NV(C, {
-    if (dt == NVIT_F32) NVIT_RRB_LAUNCH(float)
-    else NVIT_RRB_LAUNCH(bf16)
+  const auto kernel = with_row_vecs<8>(C, [&](auto nv) {
+    return with_elem(dt, [&](auto tlo) {
+      return with_bool(g_add != nullptr, [&](auto add) {
+        using TL = tag_t<decltype(tlo)>;
+        if (!y) return &res_rmsnorm_bwd_kernel<nv, float, TL, false, add>;   // as in the forward: TY is float without y
+        return with_elem(y_dt, [&](auto ty) { return &res_rmsnorm_bwd_kernel<nv, tag_t<decltype(ty)>, TL, true, add>; });
+      });
+    });
   });
-#undef NVIT_RRB_LAUNCH
-#undef NVIT_RRB_LAUNCH2
+  launch(kernel, dim3(nblk), dim3(256), 0, s, ar);
   NVIT_CHECK_LAUNCH("res_rmsnorm_bwd");
   return NVIT_OK;
 }
-
-#define NVIT_RSK_LAUNCH(KERN, GRID)                                                                   \
-  DISPATCH_NV(C, {                                                                                    \
-    if (y_dt == NVIT_F32 && dt == NVIT_F32)                                                           \
-      hipLaunchKernelGGL((KERN<NV, float, float>), dim3(GRID), dim3(256), 0, s, ar);                  \
-    else if (y_dt == NVIT_F32)                                                                        \
-      hipLaunchKernelGGL((KERN<NV, float, bf16>), dim3(GRID), dim3(256), 0, s, ar);                   \
-    else if (dt == NVIT_F32)                                                                          \
-      hipLaunchKernelGGL((KERN<NV, bf16, float>), dim3(GRID), dim3(256), 0, s, ar);                   \
-    else                                                                                              \
-      hipLaunchKernelGGL((KERN<NV, bf16, bf16>), dim3(GRID), dim3(256), 0, s, ar);                    \
-  })
 
 extern "C" int nvit_res_skip_fwd(int dt, const float* h, const void* y, int y_dt, const float* skip, const float* x,
                                  float* out, void* out_lo, int M, int C, void* stream) {
@@ -1208,7 +1147,10 @@ extern "C" int nvit_res_skip_fwd(int dt, const float* h, const void* y, int y_dt
   const int grid = row_grid(M);
   ProfScope ps(NVIT_KID_ROWOPS, 0.0, (double)M * C * (12.0 + (y_dt == NVIT_F32 ? 4.0 : 2.0) +
                                                        (out_lo ? (dt == NVIT_F32 ? 4.0 : 2.0) : 0.0)), s);
-  NVIT_RSK_LAUNCH(res_skip_fwd_kernel, grid);
+  const auto kernel = with_row_types(C, y_dt, dt, [](auto nv, auto ty, auto tl) {
+    return &res_skip_fwd_kernel<nv, tag_t<decltype(ty)>, tag_t<decltype(tl)>>;
+  });
+  launch(kernel, dim3(grid), dim3(256), 0, s, ar);
   NVIT_CHECK_LAUNCH("res_skip_fwd");
   return NVIT_OK;
 }
@@ -1224,11 +1166,13 @@ extern "C" int nvit_res_skip_bwd(int dt, const float* dout, const float* h, cons
   hipStream_t s = (hipStream_t)stream;
   ProfScope ps(NVIT_KID_ROWOPS, 0.0, (double)M * C * (20.0 + (y_dt == NVIT_F32 ? 4.0 : 2.0) +
                                                        (dh_lo ? (dt == NVIT_F32 ? 4.0 : 2.0) : 0.0)), s);
-  NVIT_RSK_LAUNCH(res_skip_bwd_kernel, nblk);
+  const auto kernel = with_row_types(C, y_dt, dt, [](auto nv, auto ty, auto tl) {
+    return &res_skip_bwd_kernel<nv, tag_t<decltype(ty)>, tag_t<decltype(tl)>>;
+  });
+  launch(kernel, dim3(nblk), dim3(256), 0, s, ar);
   NVIT_CHECK_LAUNCH("res_skip_bwd");
   return NVIT_OK;
 }
-#undef NVIT_RSK_LAUNCH
 
 extern "C" int nvit_qknorm_fwd(int dt, const void* q, int ldq, const void* k, int ldk, const void* v, int ldv,
                                const float* sqk, float c_q, void* qh, void* kh, void* vh, float* rq, float* rk,
@@ -1241,20 +1185,14 @@ extern "C" int nvit_qknorm_fwd(int dt, const void* q, int ldq, const void* k, in
   const int grid = row_grid(B * T);
   NVIT_REQUIRE(dt == NVIT_F32 || dt == NVIT_BF16 || dt == NVIT_BF16_F32IN, "qknorm_fwd: bad dt %d", dt);
   ProfScope ps(NVIT_KID_ROWOPS, 0.0, (double)B * T * C * (dt == NVIT_F32 ? 24.0 : dt == NVIT_BF16 ? 12.0 : 18.0), s);
-#define NVIT_QKF_LAUNCH(NORM_)                                                                          \
-  DISPATCH_NV(C, {                                                                                      \
-    if (dt == NVIT_F32)                                                                                 \
-      hipLaunchKernelGGL((qknorm_fwd_kernel<NV, float, float, NORM_>), dim3(grid), dim3(256), 0, s, a); \
-    else if (dt == NVIT_BF16)                                                                           \
-      hipLaunchKernelGGL((qknorm_fwd_kernel<NV, bf16, bf16, NORM_>), dim3(grid), dim3(256), 0, s, a);   \
-    else   /* fp32 projection outputs -> bf16 head tensors: normalised from the unrounded values */     \
-      hipLaunchKernelGGL((qknorm_fwd_kernel<NV, float, bf16, NORM_>), dim3(grid), dim3(256), 0, s, a);  \
-  })
-  if (sqk)
-    NVIT_QKF_LAUNCH(true);
-  else
-    NVIT_QKF_LAUNCH(false);
-#undef NVIT_QKF_LAUNCH
+  const auto kernel = with_row_vecs<8>(C, [&](auto nv) {
+    return with_bool(sqk != nullptr, [&](auto norm) {
+      return with_in_out_elems(dt, [&](auto ti, auto to) {
+        return &qknorm_fwd_kernel<nv, tag_t<decltype(ti)>, tag_t<decltype(to)>, norm>;
+      });
+    });
+  });
+  launch(kernel, dim3(grid), dim3(256), 0, s, a);
   NVIT_CHECK_LAUNCH("qknorm_fwd");
   return NVIT_OK;
 }
@@ -1273,22 +1211,18 @@ extern "C" int nvit_qknorm_bwd(int dt, const void* dqh, const void* dkh, const v
     NVIT_REQUIRE(dt == NVIT_F32 || dt == NVIT_BF16, "qknorm_bwd: bad dt %d", dt);
     ProfScope ps(NVIT_KID_ROWOPS, 0.0, (double)B * T * C * (dt == NVIT_F32 ? 24.0 : 12.0), s);
     const int grid = row_grid(B * T);
-    DISPATCH_NV(C, {
-      if (dt == NVIT_F32)
-        hipLaunchKernelGGL((merge_heads_kernel<NV, float>), dim3(grid), dim3(256), 0, s, a);
-      else
-        hipLaunchKernelGGL((merge_heads_kernel<NV, bf16>), dim3(grid), dim3(256), 0, s, a);
+    const auto kernel = with_row_vecs<8>(C, [&](auto nv) {
+      return with_elem(dt, [&](auto t) { return &merge_heads_kernel<nv, tag_t<decltype(t)>>; });
     });
+    launch(kernel, dim3(grid), dim3(256), 0, s, a);
     NVIT_CHECK_LAUNCH("qknorm_bwd");
     return NVIT_OK;
   }
   ProfScope ps(NVIT_KID_ROWOPS, 0.0, (double)B * T * C * (dt == NVIT_F32 ? 32.0 : 16.0), s);
-  DISPATCH_NV(C, {
-    if (dt == NVIT_F32)
-      hipLaunchKernelGGL((qknorm_bwd_kernel<NV, float>), dim3(nblk), dim3(256), 0, s, a);
-    else
-      hipLaunchKernelGGL((qknorm_bwd_kernel<NV, bf16>), dim3(nblk), dim3(256), 0, s, a);
+  const auto kernel = with_row_vecs<8>(C, [&](auto nv) {
+    return with_elem(dt, [&](auto t) { return &qknorm_bwd_kernel<nv, tag_t<decltype(t)>>; });
   });
+  launch(kernel, dim3(nblk), dim3(256), 0, s, a);
   NVIT_CHECK_LAUNCH("qknorm_bwd");
   return NVIT_OK;
 }
@@ -1308,12 +1242,12 @@ extern "C" int nvit_swiglu_fwd(int dt, const void* uv, const float* suv, float g
   dim3 grid(cdiv(F, 1024), cdiv(M, rpb));
   NVIT_REQUIRE(dt == NVIT_F32 || dt == NVIT_BF16 || dt == NVIT_BF16_F32IN, "swiglu_fwd: bad dt %d", dt);
   ProfScope ps(NVIT_KID_ROWOPS, 0.0, (double)M * F * (dt == NVIT_F32 ? 12.0 : dt == NVIT_BF16 ? 6.0 : 10.0), s);
-  if (dt == NVIT_F32)
-    hipLaunchKernelGGL((swiglu_fwd_kernel<float, float>), grid, dim3(256), 0, s, (const float*)uv, suv, gscale, (float*)x, M, F, rpb);
-  else if (dt == NVIT_BF16)
-    hipLaunchKernelGGL((swiglu_fwd_kernel<bf16, bf16>), grid, dim3(256), 0, s, (const bf16*)uv, suv, gscale, (bf16*)x, M, F, rpb);
-  else   // fp32 pre-activations -> bf16 gated output: gated from the unrounded values (like the fused GEMM epilogue)
-    hipLaunchKernelGGL((swiglu_fwd_kernel<float, bf16>), grid, dim3(256), 0, s, (const float*)uv, suv, gscale, (bf16*)x, M, F, rpb);
+  // NVIT_BF16_F32IN: gated from the unrounded pre-activations (like the fused GEMM epilogue)
+  with_in_out_elems(dt, [&](auto ti, auto to) {
+    using TI = tag_t<decltype(ti)>;
+    using T = tag_t<decltype(to)>;
+    launch(swiglu_fwd_kernel<TI, T>, grid, dim3(256), 0, s, (const TI*)uv, suv, gscale, (T*)x, M, F, rpb);
+  });
   NVIT_CHECK_LAUNCH("swiglu_fwd");
   return NVIT_OK;
 }
@@ -1325,12 +1259,11 @@ extern "C" int nvit_swiglu_bwd(int dt, const void* dx, const void* uv, const flo
   hipStream_t s = (hipStream_t)stream;
   dim3 grid(cdiv(F, 1024), cdiv(M, rows_per_blk));
   ProfScope ps(NVIT_KID_ROWOPS, 0.0, (double)M * F * 5.0 * (dt == NVIT_F32 ? 4 : 2), s);
-  if (dt == NVIT_F32)
-    hipLaunchKernelGGL(swiglu_bwd_kernel<float>, grid, dim3(256), 0, s, (const float*)dx, (const float*)uv, suv, gscale,
-                       (float*)duv, suv ? part_dsuv : nullptr, M, F, rows_per_blk);
-  else
-    hipLaunchKernelGGL(swiglu_bwd_kernel<bf16>, grid, dim3(256), 0, s, (const bf16*)dx, (const bf16*)uv, suv, gscale,
-                       (bf16*)duv, suv ? part_dsuv : nullptr, M, F, rows_per_blk);
+  with_elem(dt, [&](auto t) {
+    using T = tag_t<decltype(t)>;
+    launch(swiglu_bwd_kernel<T>, grid, dim3(256), 0, s, (const T*)dx, (const T*)uv, suv, gscale, (T*)duv,
+           suv ? part_dsuv : nullptr, M, F, rows_per_blk);
+  });
   NVIT_CHECK_LAUNCH("swiglu_bwd");
   return NVIT_OK;
 }
@@ -1382,13 +1315,13 @@ extern "C" int nvit_colsum(const void* a, int a_dt, int lda, const void* b, int 
   hipStream_t s = (hipStream_t)stream;
   const int per = period > 0 ? period : 1;
   dim3 grid(cdiv(N, 128), per);
-#define CS(TA, TB) \
-  hipLaunchKernelGGL((colsum_kernel<TA, TB>), grid, dim3(128), 0, s, (const TA*)a, lda, (const TB*)b, ldb, R, N, per, out, accumulate, scale)
-  if (a_dt == NVIT_F32 && (b_dt == NVIT_F32 || !b)) CS(float, float);
-  else if (a_dt == NVIT_F32) CS(float, bf16);
-  else if (b_dt == NVIT_F32 || !b) CS(bf16, float);
-  else CS(bf16, bf16);
-#undef CS
+  with_elem(a_dt, [&](auto ta) {
+    with_elem(b ? b_dt : NVIT_F32, [&](auto tb) {   // no b: the <TA, float> kernel
+      using TA = tag_t<decltype(ta)>;
+      using TB = tag_t<decltype(tb)>;
+      launch(colsum_kernel<TA, TB>, grid, dim3(128), 0, s, (const TA*)a, lda, (const TB*)b, ldb, R, N, per, out, accumulate, scale);
+    });
+  });
   NVIT_CHECK_LAUNCH("colsum");
   return NVIT_OK;
 }
@@ -1400,10 +1333,10 @@ extern "C" int nvit_cast(const float* src, void* dst, int dt, int64_t n, void* s
   int blocks = cdiv(n4, 256);
   if (blocks > 4096) blocks = 4096;
   if (blocks < 1) return NVIT_OK;
-  if (dt == NVIT_F32)
-    hipLaunchKernelGGL(cast_kernel<float>, dim3(blocks), dim3(256), 0, s, src, (float*)dst, n4);
-  else
-    hipLaunchKernelGGL(cast_kernel<bf16>, dim3(blocks), dim3(256), 0, s, src, (bf16*)dst, n4);
+  with_elem(dt, [&](auto t) {
+    using T = tag_t<decltype(t)>;
+    launch(cast_kernel<T>, dim3(blocks), dim3(256), 0, s, src, (T*)dst, n4);
+  });
   NVIT_CHECK_LAUNCH("cast");
   return NVIT_OK;
 }
@@ -1433,10 +1366,10 @@ extern "C" int nvit_scale_cols(const float* a, int lda, const float* sc, float c
                                int R, int N, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   dim3 grid(cdiv(N, 128), R);
-  if (out_dt == NVIT_F32)
-    hipLaunchKernelGGL(scale_cols_kernel<float>, grid, dim3(128), 0, s, a, lda, sc, c, (float*)out, ldo, R, N);
-  else
-    hipLaunchKernelGGL(scale_cols_kernel<bf16>, grid, dim3(128), 0, s, a, lda, sc, c, (bf16*)out, ldo, R, N);
+  with_elem(out_dt, [&](auto t) {
+    using T = tag_t<decltype(t)>;
+    launch(scale_cols_kernel<T>, grid, dim3(128), 0, s, a, lda, sc, c, (T*)out, ldo, R, N);
+  });
   NVIT_CHECK_LAUNCH("scale_cols");
   return NVIT_OK;
 }

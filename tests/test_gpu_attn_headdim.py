@@ -1,7 +1,8 @@
 """Attention at head dims 32 and 128: the MFMA kernels (impl 1) and the scalar-FMA kernels (impl 0, d = 128) against
 fp32 SDPA math with the bars of test_gpu_ops.py::test_attention / test_attention_bounded_scores, on ragged and degenerate
-lengths, with operands inside NaN padding and outputs inside sentinel padding; bitwise run-to-run reproducibility (also
-at d = 64); and the model at d = 128 and d = 32 against the CPU oracle with the bars of test_gpu_model.py."""
+lengths (impl 0 also with Tq != Tk, at every head dim), with operands inside NaN padding and outputs inside sentinel
+padding; bitwise run-to-run reproducibility (also at d = 64); and the model at d = 128 and d = 32 against the CPU oracle
+with the bars of test_gpu_model.py."""
 import math
 
 import pytest
@@ -62,16 +63,16 @@ def output(shape, dtype):
 def run_fwd(dt, impl, q, k, v, scale, sqk=None, c_q=0.0, q_prescale=1.0):
     """nvit_attn_fwd / nvit_attn_fwd_bounded on padded operands and outputs; returns (o, lse) as plain tensors."""
     from nvit_amd import _lib, ops
-    B, H, T, d = q.shape
+    (B, H, Tq, d), Tk = q.shape, k.shape[2]
     qp, kp, vp = operand(q), operand(k), operand(v)
-    o, lse = output((B * T, H * d), q.dtype), output((B, H, T), torch.float32)
+    o, lse = output((B * Tq, H * d), q.dtype), output((B, H, Tq), torch.float32)
     lib = _lib.load()
     if sqk is None:
-        rc = lib.nvit_attn_fwd(dt, impl, qp.ptr(), kp.ptr(), vp.ptr(), scale, o.ptr(), lse.ptr(), B, H, T, T, d, ops._s())
+        rc = lib.nvit_attn_fwd(dt, impl, qp.ptr(), kp.ptr(), vp.ptr(), scale, o.ptr(), lse.ptr(), B, H, Tq, Tk, d, ops._s())
     else:
         sp = operand(sqk)
         rc = lib.nvit_attn_fwd_bounded(dt, impl, qp.ptr(), kp.ptr(), vp.ptr(), scale, sp.ptr(), c_q, q_prescale, o.ptr(),
-                                       lse.ptr(), B, H, T, T, d, ops._s())
+                                       lse.ptr(), B, H, Tq, Tk, d, ops._s())
     ops.check(rc, "nvit_attn_fwd")
     torch.cuda.synchronize()
     assert o.margins_intact() and lse.margins_intact()
@@ -80,12 +81,12 @@ def run_fwd(dt, impl, q, k, v, scale, sqk=None, c_q=0.0, q_prescale=1.0):
 
 def run_bwd(dt, impl, g_tok, q, k, v, o, lse, scale):
     from nvit_amd import _lib, ops
-    B, H, T, d = q.shape
+    (B, H, Tq, d), Tk = q.shape, k.shape[2]
     gp, qp, kp, vp, op, lp = (operand(x) for x in (g_tok, q, k, v, o, lse))
-    dq, dk, dv = (output((B, H, T, d), q.dtype) for _ in range(3))
-    delta = Padded((2, B, H, T), torch.float32, float("nan"))   # workspace: written before it is read
+    dq, dk, dv = (output((B, H, T, d), q.dtype) for T in (Tq, Tk, Tk))
+    delta = Padded((2, B, H, Tq), torch.float32, float("nan"))   # workspace: written before it is read
     rc = _lib.load().nvit_attn_bwd(dt, impl, gp.ptr(), qp.ptr(), kp.ptr(), vp.ptr(), op.ptr(), lp.ptr(), scale, dq.ptr(),
-                                   dk.ptr(), dv.ptr(), delta.ptr(), B, H, T, T, d, ops._s())
+                                   dk.ptr(), dv.ptr(), delta.ptr(), B, H, Tq, Tk, d, ops._s())
     ops.check(rc, "nvit_attn_bwd")
     torch.cuda.synchronize()
     for x in (dq, dk, dv):
@@ -93,11 +94,12 @@ def run_bwd(dt, impl, g_tok, q, k, v, o, lse, scale):
     return dq.t.clone(), dk.t.clone(), dv.t.clone()
 
 
-def _inputs(dtype, B, H, T, d):
+def _inputs(dtype, B, H, T, d, Tk=None):
     # |q|=|k|=1.3 per head: logits up to sqrt(d)*1.69 (as test_attention)
+    Tk = T if Tk is None else Tk
     q = (1.3 * torch.nn.functional.normalize(rnd(B, H, T, d, seed=1), dim=-1)).to(dtype)
-    k = (1.3 * torch.nn.functional.normalize(rnd(B, H, T, d, seed=2), dim=-1)).to(dtype)
-    v = rnd(B, H, T, d, seed=3).to(dtype)
+    k = (1.3 * torch.nn.functional.normalize(rnd(B, H, Tk, d, seed=2), dim=-1)).to(dtype)
+    v = rnd(B, H, Tk, d, seed=3).to(dtype)
     g = rnd(B, H, T, d, seed=4).to(dtype)
     return q, k, v, g
 
@@ -119,9 +121,21 @@ def test_attention_head_dim_unit_scale(d):
     _check_head_dim(torch.bfloat16, 1, d, 2, 2, 130, math.log(2.0))
 
 
-def _check_head_dim(dtype, impl, d, B, H, T, scale):
+# Tk = 33: a full 32-key LDS tile and a one-key tile.  Tq = 65: a full 64-row workgroup and one with a single live row (at
+# d = 128, four lanes per row, five workgroups of 16 rows).  Tq = 1: the single query.  B, H > 1: the b / h indexing.
+UNEQUAL = [(dt, d, B, H, Tq, Tk) for d in (32, 64, 128) for dt in (torch.float32, torch.bfloat16)
+           for (B, H, Tq, Tk) in [(2, 2, 17, 33), (2, 2, 65, 32), (2, 3, 1, 40)]]
+
+
+@pytest.mark.parametrize("dtype,d,B,H,Tq,Tk", UNEQUAL)
+def test_attention_scalar_unequal_lengths(dtype, d, B, H, Tq, Tk):
+    """impl 0 forward and backward with Tq != Tk: same fp64 reference, padding harness and bars as above."""
+    _check_head_dim(dtype, 0, d, B, H, Tq, math.sqrt(d), Tk=Tk)
+
+
+def _check_head_dim(dtype, impl, d, B, H, T, scale, Tk=None):
     from nvit_amd.ops import dt_of
-    q, k, v, g = _inputs(dtype, B, H, T, d)
+    q, k, v, g = _inputs(dtype, B, H, T, d, Tk)
     # (the reference runs in fp64 on the same operands: at d = 128 an fp32 evaluation of the same formula is itself
     #  1.8e-6 - 3.3e-6 away from the exact result on these inputs, at or above the fp32 bar of 2e-6)
     qf, kf, vf = (t.double().requires_grad_(True) for t in (q, k, v))
