@@ -40,7 +40,8 @@ __global__ __launch_bounds__(256) void bmu_kernel(const float* S, const float* n
         bi = oi;
       }
     }
-    if (lane == 0) idx[m] = bi;
+    // no d < best ever held (a row of NaN or +inf distances): index 0, as torch.argmin gives, never an out-of-range row
+    if (lane == 0) idx[m] = bi < N ? bi : 0;
   }
 }
 

@@ -691,7 +691,12 @@ def som_bmu(x: Tensor, nodes: Tensor) -> Tensor:
     """x [M,C] fp32, nodes [N,C] fp32 -> idx [M] int64 (exact-f32 MFMA score GEMM + argmin kernel)."""
     M, Cc = x.shape
     N = nodes.shape[0]
-    scores = gemm_nt(x, nodes, M, N, Cc)                      # fp32 operands -> v_mfma_f32_16x16x4_f32
+    Kp = round_up(Cc, bk_of(F32))
+    xs, ns = x, nodes
+    if Kp != Cc:   # the GEMM takes K in whole LDS rows of 32 floats: zero columns add nothing to x . node
+        xs = torch.nn.functional.pad(x, (0, Kp - Cc))
+        ns = torch.nn.functional.pad(nodes, (0, Kp - Cc))
+    scores = gemm_nt(xs, ns, M, N, Kp)                        # fp32 operands -> v_mfma_f32_16x16x4_f32
     nn_ws = torch.empty((N,), device=x.device, dtype=torch.float32)
     idx = torch.empty((M,), device=x.device, dtype=torch.int64)
     check(_lib.load().nvit_som_bmu(_p(scores), _p(nodes), _p(nn_ws), M, N, Cc, _p(idx), _s()), "nvit_som_bmu")
@@ -705,6 +710,14 @@ def gather_rows(nodes: Tensor, idx: Tensor) -> Tensor:
     return out
 
 
+def onehot(idx: Tensor, N: int) -> Tensor:
+    """fp32 [M, N] rows with a single 1 at idx[m] (N a multiple of 4)."""
+    M = idx.numel()
+    oh = torch.empty((M, N), device=idx.device, dtype=torch.float32)
+    check(_lib.load().nvit_onehot(_p(idx), _p(oh), M, N, _s()), "nvit_onehot")
+    return oh
+
+
 def scatter_rows(dout: Tensor, idx: Tensor, N: int) -> Tensor:
     """dnodes[n] = sum of dout rows with idx == n.  All tokens may pick the same node (they do at init: the BMU of a
     small-norm patch is the smallest-norm node), so instead of a per-node loop this is onehot(idx)^T . dout on the
@@ -714,9 +727,7 @@ def scatter_rows(dout: Tensor, idx: Tensor, N: int) -> Tensor:
     if N % 4 != 0 or Cc % 4 != 0:
         check(_lib.load().nvit_scatter_rows(_p(dout), _p(idx), _p(dn), M, N, Cc, _s()), "nvit_scatter_rows")
         return dn
-    oh = torch.empty((M, N), device=dout.device, dtype=torch.float32)
-    check(_lib.load().nvit_onehot(_p(idx), _p(oh), M, N, _s()), "nvit_onehot")
-    return gemm_tn(oh, dout.float().contiguous(), dn, M, N, Cc)
+    return gemm_tn(onehot(idx, N), dout.float().contiguous(), dn, M, N, Cc)
 
 
 def som_update(nodes: Tensor, x: Tensor, idx: Tensor, lr_alpha: float, sigma: float, gm: int, gn: int, B: int,
