@@ -166,6 +166,23 @@ int nvit_gemm_nt_swiglu_act(int dt, const void* A, int lda, const void* B, int l
 int nvit_gemm_nt_qknorm(int dt, const void* A, int lda, const void* B, int ldb, int M, int K, int nparts, int part0,
                         const float* sqk, float c_q, float q_prescale, void* qh, void* kh, void* vh, float* rq, float* rk,
                         int T, int H, int d, void* stream);
+/* The three fused forward GEMMs with a bias (fp32, 16-byte aligned; NULL = none, and then they ARE their siblings above,
+ * which forward here).  bias[n] is added to the fp32 accumulator of output column n FIRST, before anything else in the
+ * epilogue, so every later step sees A B^T + bias:
+ *   _swiglu_bias / _swiglu_act_bias: bias[2F] in the interleaved (perm=1, u16|v16) column order of the weight shadow, like
+ *     gs.  The raw uv that is stored (the pre-activation nvit_gemm_nt_swiglu_bwd / nvit_swiglu_bwd differentiate) includes
+ *     it, and the gate is computed from the same biased sums: xm of the two forms stays bit-identical.
+ *   _qknorm_bias: bias[nparts*C], the stacked biases of exactly the nparts projections of this launch, indexed by the
+ *     launch's own output column (NOT offset by part0).  Added for every part (v too) before the sum of squares; the
+ *     normalise, rq/rk, the sqk*c_q scale, q_prescale and the head split (also with sqk == NULL) run on the biased sums.
+ * Same eligibility (nvit_gemm_nt_fusable) and the same kernel-family ids as the siblings. */
+int nvit_gemm_nt_swiglu_bias(int dt, const void* A, int lda, const void* B, int ldb, void* uv, void* xm, int M, int F,
+                             int K, const float* gs, float gscale, const float* bias, void* stream);
+int nvit_gemm_nt_swiglu_act_bias(int dt, const void* A, int lda, const void* B, int ldb, void* xm, int M, int F, int K,
+                                 const float* gs, float gscale, const float* bias, void* stream);
+int nvit_gemm_nt_qknorm_bias(int dt, const void* A, int lda, const void* B, int ldb, int M, int K, int nparts, int part0,
+                             const float* sqk, float c_q, float q_prescale, void* qh, void* kh, void* vh, float* rq,
+                             float* rk, int T, int H, int d, const float* bias, void* stream);
 
 /* nvit_gemm_tn: weight gradient  G[N,K] (+)= sum_m A[m,N-col] * B[m,K-col]  over Mred rows.
  * A [Mred, N] (lda), B [Mred, K] (ldb) of type dt.  Split over `splits` row chunks into the

@@ -48,6 +48,10 @@ SIGNATURES = {
     "nvit_gemm_nt_swiglu_act": [_i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _f, _vp],
     "nvit_gemm_nt_swiglu_bwd": [_i, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _f, _vp],
     "nvit_gemm_nt_qknorm": [_i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
+    "nvit_gemm_nt_swiglu_bias": [_i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _f, _vp, _vp],
+    "nvit_gemm_nt_swiglu_act_bias": [_i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _f, _vp, _vp],
+    "nvit_gemm_nt_qknorm_bias": [_i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp,
+                                 _vp],
     "nvit_gemm_tn": [_i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _i64, _i, _i, _vp],
     "nvit_lerp_fwd": [_i, _vp, _vp, _i, _vp, _f, _vp, _vp, _vp, _vp, _i, _i, _vp],
     "nvit_lerp_bwd_blocks": [_i, _i, _i, _i, _i, _i],

@@ -77,6 +77,8 @@ def named_config(name: str, **over) -> ViTConfig:
         # 20 heads of 64 is the nearest shape on the fused path
         "huge": dict(image_size=224, n_embd=1280, n_layer=32, n_head=20, num_classes=1000),
     }
+    # Base with biases on every linear (the reference's shipped settings carry bias: true; stock ViT checkpoints too)
+    table["base_b"] = dict(table["base"], bias=True)
     # the plain-ViT baseline (use_nvit=False, the reference's nvit0_k0 profile) at the same shapes
     for base in ("micro", "mini", "tiny", "base"):
         table[base + "_vit"] = dict(table[base], use_nvit=False)

@@ -480,11 +480,11 @@ extern "C" int nvit_gemm_nt_fusable(int dt, int M, int N, int K) {
   return (dt == NVIT_BF16 && M >= 1 && N % 256 == 0 && K % 64 == 0) ? 1 : 0;
 }
 
-extern "C" int nvit_gemm_nt_swiglu(int dt, const void* A, int lda, const void* B, int ldb, void* uv, void* xm, int M,
-                                   int F, int K, const float* gs, float gscale, void* stream) {
+extern "C" int nvit_gemm_nt_swiglu_bias(int dt, const void* A, int lda, const void* B, int ldb, void* uv, void* xm, int M,
+                                        int F, int K, const float* gs, float gscale, const float* bias, void* stream) {
   NVIT_REQUIRE(nvit_gemm_nt_fusable(dt, M, 2 * F, K), "gemm_nt_swiglu: shape/dtype not eligible for the fused kernel");
   NVIT_REQUIRE((lda * 2) % 16 == 0 && (ldb * 2) % 16 == 0 && lda >= K && ldb >= K, "gemm_nt_swiglu: bad leading dims");
-  NVIT_REQUIRE((((uintptr_t)A | (uintptr_t)B | (uintptr_t)uv | (uintptr_t)xm | (uintptr_t)gs) & 15) == 0,
+  NVIT_REQUIRE((((uintptr_t)A | (uintptr_t)B | (uintptr_t)uv | (uintptr_t)xm | (uintptr_t)gs | (uintptr_t)bias) & 15) == 0,
                "gemm_nt_swiglu: pointers must be 16-byte aligned");
   NtArgs g{};
   g.A = (const char*)A;
@@ -501,19 +501,25 @@ extern "C" int nvit_gemm_nt_swiglu(int dt, const void* A, int lda, const void* B
   g.ld_xm = F;
   g.gs = gs;
   g.gscale = gscale;
+  g.bias = bias;
   hipStream_t s = (hipStream_t)stream;
   // algorithmic bytes: A, B read; raw uv [M,2F] and gated x [M,F] written (bf16)
   ProfScope ps(NVIT_KID_GEMM_SWIGLU, 2.0 * M * (2.0 * F) * K, 2.0 * ((double)M * K + 2.0 * F * K + 3.0 * M * F), s);
   return nvit_gemm_nt_fused_launch(g, 3, s);
 }
 
+extern "C" int nvit_gemm_nt_swiglu(int dt, const void* A, int lda, const void* B, int ldb, void* uv, void* xm, int M,
+                                   int F, int K, const float* gs, float gscale, void* stream) {
+  return nvit_gemm_nt_swiglu_bias(dt, A, lda, B, ldb, uv, xm, M, F, K, gs, gscale, nullptr, stream);
+}
+
 // The forward-only form of nvit_gemm_nt_swiglu: the same launch without the raw uv store (EPI 6).
-extern "C" int nvit_gemm_nt_swiglu_act(int dt, const void* A, int lda, const void* B, int ldb, void* xm, int M, int F, int K,
-                                       const float* gs, float gscale, void* stream) {
+extern "C" int nvit_gemm_nt_swiglu_act_bias(int dt, const void* A, int lda, const void* B, int ldb, void* xm, int M, int F,
+                                            int K, const float* gs, float gscale, const float* bias, void* stream) {
   NVIT_REQUIRE(nvit_gemm_nt_fusable(dt, M, 2 * F, K), "gemm_nt_swiglu_act: shape/dtype not eligible for the fused kernel");
   NVIT_REQUIRE((lda * 2) % 16 == 0 && (ldb * 2) % 16 == 0 && lda >= K && ldb >= K,
                "gemm_nt_swiglu_act: bad leading dims");
-  NVIT_REQUIRE(A && B && xm && (((uintptr_t)A | (uintptr_t)B | (uintptr_t)xm | (uintptr_t)gs) & 15) == 0,
+  NVIT_REQUIRE(A && B && xm && (((uintptr_t)A | (uintptr_t)B | (uintptr_t)xm | (uintptr_t)gs | (uintptr_t)bias) & 15) == 0,
                "gemm_nt_swiglu_act: pointers must be non-null and 16-byte aligned");
   NtArgs g{};
   g.A = (const char*)A;
@@ -528,10 +534,16 @@ extern "C" int nvit_gemm_nt_swiglu_act(int dt, const void* A, int lda, const voi
   g.ld_xm = F;
   g.gs = gs;
   g.gscale = gscale;
+  g.bias = bias;
   hipStream_t s = (hipStream_t)stream;
   // algorithmic bytes: A, B read; the gated x [M,F] written (bf16)
   ProfScope ps(NVIT_KID_GEMM_SWIGLU_ACT, 2.0 * M * (2.0 * F) * K, 2.0 * ((double)M * K + 2.0 * F * K + (double)M * F), s);
   return nvit_gemm_nt_fused_launch(g, 6, s);
+}
+
+extern "C" int nvit_gemm_nt_swiglu_act(int dt, const void* A, int lda, const void* B, int ldb, void* xm, int M, int F, int K,
+                                       const float* gs, float gscale, void* stream) {
+  return nvit_gemm_nt_swiglu_act_bias(dt, A, lda, B, ldb, xm, M, F, K, gs, gscale, nullptr, stream);
 }
 
 extern "C" int nvit_gemm_nt_swiglu_bwd(int dt, const void* A, int lda, const void* B, int ldb, const void* uv,
@@ -567,9 +579,10 @@ extern "C" int nvit_gemm_nt_swiglu_bwd(int dt, const void* A, int lda, const voi
   return nvit_gemm_nt_fused_launch(g, 5, s);
 }
 
-extern "C" int nvit_gemm_nt_qknorm(int dt, const void* A, int lda, const void* B, int ldb, int M, int K, int nparts,
-                                   int part0, const float* sqk, float c_q, float q_prescale, void* qh, void* kh, void* vh,
-                                   float* rq, float* rk, int T, int H, int d, void* stream) {
+extern "C" int nvit_gemm_nt_qknorm_bias(int dt, const void* A, int lda, const void* B, int ldb, int M, int K, int nparts,
+                                        int part0, const float* sqk, float c_q, float q_prescale, void* qh, void* kh,
+                                        void* vh, float* rq, float* rk, int T, int H, int d, const float* bias,
+                                        void* stream) {
   const int C = H * d;
   NVIT_REQUIRE(d == 64 && C % 256 == 0 && nparts >= 1 && part0 >= 0 && part0 + nparts <= 3,
                "gemm_nt_qknorm: needs head dim 64 and n_embd %% 256 == 0");
@@ -577,7 +590,8 @@ extern "C" int nvit_gemm_nt_qknorm(int dt, const void* A, int lda, const void* B
   NVIT_REQUIRE((lda * 2) % 16 == 0 && (ldb * 2) % 16 == 0 && lda >= K && ldb >= K, "gemm_nt_qknorm: bad leading dims");
   NVIT_REQUIRE(M % T == 0, "gemm_nt_qknorm: M must be a multiple of T");
   NVIT_REQUIRE(q_prescale > 0.f, "gemm_nt_qknorm: q_prescale must be positive");
-  NVIT_REQUIRE((((uintptr_t)A | (uintptr_t)B | (uintptr_t)qh | (uintptr_t)kh | (uintptr_t)vh | (uintptr_t)sqk) & 15) == 0,
+  NVIT_REQUIRE((((uintptr_t)A | (uintptr_t)B | (uintptr_t)qh | (uintptr_t)kh | (uintptr_t)vh | (uintptr_t)sqk |
+                 (uintptr_t)bias) & 15) == 0,
                "gemm_nt_qknorm: pointers must be 16-byte aligned");
   NtArgs g{};
   g.A = (const char*)A;
@@ -600,9 +614,17 @@ extern "C" int nvit_gemm_nt_qknorm(int dt, const void* A, int lda, const void* B
   g.Cemb = C;
   g.Ttok = T;
   g.H = H;
+  g.bias = bias;
   hipStream_t s = (hipStream_t)stream;
   // algorithmic bytes: A, B read; nparts head tensors [M,C] written (bf16)
   ProfScope ps(NVIT_KID_GEMM_QKNORM, 2.0 * M * (double)(nparts * C) * K,
                2.0 * ((double)M * K + (double)nparts * C * K + (double)nparts * M * C), s);
   return nvit_gemm_nt_fused_launch(g, 4, s);
+}
+
+extern "C" int nvit_gemm_nt_qknorm(int dt, const void* A, int lda, const void* B, int ldb, int M, int K, int nparts,
+                                   int part0, const float* sqk, float c_q, float q_prescale, void* qh, void* kh, void* vh,
+                                   float* rq, float* rk, int T, int H, int d, void* stream) {
+  return nvit_gemm_nt_qknorm_bias(dt, A, lda, B, ldb, M, K, nparts, part0, sqk, c_q, q_prescale, qh, kh, vh, rq, rk, T, H,
+                                  d, nullptr, stream);
 }

@@ -295,10 +295,27 @@ __device__ __forceinline__ void nt_store_tile_staged(const NtArgs& g, f32x4 (&ac
   }
 }
 
+// Bias of the fused epilogues (EPI 3, 4, 6): acc[i][j] += bias[n_base + 16j + 4*lg .. +3], on the fp32 accumulators and
+// before anything else in the epilogue, so everything downstream (raw tile, gate, norm, scale) sees A B^T + bias.  bias
+// is indexed by the launch's own output column (the interleaved order of a perm=1 shadow; the stacked order of the
+// nparts projections of a q/k/v launch).  One 16-byte load per column block, all consumed before the tile's first store:
+// nothing of them is outstanding at the counted s_waitcnt after the epilogue.  bias == NULL (wave-uniform): nothing.
+template <int FMR>
+__device__ __forceinline__ void nt_add_bias(const NtArgs& g, f32x4 (&acc)[FMR][4], int n_base, int lg) {
+  if (!g.bias) return;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const f32x4 b = *reinterpret_cast<const f32x4*>(g.bias + n_base + j * 16 + 4 * lg);
+#pragma unroll
+    for (int i = 0; i < FMR; ++i) acc[i][j] += b;
+  }
+}
+
 // ---- EPI 3: SwiGLU fused into the c_fc / proj GEMM (reference model.py:148-154, 259-261) -----------
 // The weight shadow interleaves u/v partners 16 columns apart (perm=1), so acc[i][2jj] (u) and
 // acc[i][2jj+1] (v) of one lane are gate partners.  Writes the raw pre-activation tile (saved for
 // backward) and the gated activation, both bf16, both as whole-row 16-byte stores via the LDS scratch.
+// With a bias (interleaved order, like gs) the raw tile is A B^T + bias and the gate is computed from the same sums.
 // RAW = false (EPI 6, the forward-only route): pass B alone - nothing reads the raw tile without a backward, and it is
 // two thirds of this epilogue's stores.  The gate is the same statements on the same accumulators, so xm is the same bits.
 template <int FMR, bool RAW = true>
@@ -317,6 +334,7 @@ __device__ __forceinline__ void nt_store_tile_swiglu(const NtArgs& g, f32x4 (&ac
       gv[jj] = gu[jj];
     }
   }
+  nt_add_bias<FMR>(g, acc, n_base, lg);
 #pragma unroll
   for (int i = 0; i < FMR; ++i) {
     // pass A: raw uv, 64 columns
@@ -361,7 +379,8 @@ __device__ __forceinline__ void nt_store_tile_swiglu(const NtArgs& g, f32x4 (&ac
 // ---- EPI 4: per-head cosine normalise + learned scale + head split fused into the q/k/v GEMM --------
 // (reference model.py:104-119, 231-247).  A wave's 64 columns are exactly one head (d = 64).
 // sqk == NULL: the head split alone (plain-ViT attention, model.py:97-100): no normalise, rq / rk not written; q still
-// leaves multiplied by q_prescale.
+// leaves multiplied by q_prescale.  A bias (all parts, v too; indexed by the launch's own column, not by part0) joins the
+// accumulators before the sum of squares.
 template <int FMR>
 __device__ __forceinline__ void nt_store_tile_qknorm(const NtArgs& g, f32x4 (&acc)[FMR][4], int m_base, int n_base,
                                                      int lane, char* scratch) {
@@ -385,6 +404,7 @@ __device__ __forceinline__ void nt_store_tile_qknorm(const NtArgs& g, f32x4 (&ac
   // per stored row (16 per lane per tile, ~30 VALU instructions each) was as much VALU work as the rest of this epilogue
   // (round 4: -2 % on the q/k/v GEMM, interleaved A/B)
   const int b_base = m_base / g.Ttok, t_base = m_base - b_base * g.Ttok;
+  nt_add_bias<FMR>(g, acc, n_base, lg);
 #pragma unroll
   for (int i = 0; i < FMR; ++i) {
     float rn = 1.0f;

@@ -297,7 +297,7 @@ def _qkv_cols(ts, C: int):
     return q, C, kv, kv[:, C:], 2 * C
 
 
-def _attn_fwd(rt: _Runtime, impl: int, srcs, has_b: bool, sqk: Optional[Tensor], c_q: float, scale: float, dims,
+def _attn_fwd(rt: _Runtime, impl: int, srcs, sqk: Optional[Tensor], c_q: float, scale: float, dims,
               lean: bool = False):
     """The attention of every block function, from its q/k/v projection sources to O [M, C] (the output projection's A
     operand).  srcs: ((A, shadow prefix, parts), ...), one projection GEMM each, their output columns q | k | v in
@@ -305,9 +305,9 @@ def _attn_fwd(rt: _Runtime, impl: int, srcs, has_b: bool, sqk: Optional[Tensor],
       heads  flash_attn=True: the reference's flash_attn_func reads its [B,H,T,d] arguments as [batch, seqlen, nheads,
              headdim], so the softmax runs over the H heads of each token of the fp32 token-major
              projections;
-      fused  no bias, d = 64, C % 256 == 0 and a shape the fused GEMM takes (bf16 only; N of the FIRST projection decides): the
-             normalise (nViT) and the head split in the projection GEMM's epilogue, q pre-scaled so that the attention
-             kernels' exponent needs no multiply;
+      fused  d = 64, C % 256 == 0 and a shape the fused GEMM takes (bf16 only; N of the FIRST projection decides): the
+             bias (if any), the normalise (nViT) and the head split in the projection GEMM's epilogue, q pre-scaled so
+             that the attention kernels' exponent needs no multiply;
       split  otherwise (small problems: 128x128 GEMM kernel): the projections leave the GEMM in fp32 and are normalised
              from the unrounded values, like the fused epilogue (one rounding, at the head tensors).
     -> o, lse, att (route, impl, q pre-scale, scale) for _attn_bwd, and the tensors it reads: the fp32 projections
@@ -318,7 +318,7 @@ def _attn_fwd(rt: _Runtime, impl: int, srcs, has_b: bool, sqk: Optional[Tensor],
     B, T, C, H, d, M = dims
     dt, sh = rt.dt, rt.sh
     heads = rt.model.config.flash_attn
-    if not heads and not has_b and impl == 1 and d == 64 and C % 256 == 0 and ops.fusable(dt, M, srcs[0][2] * C, C):
+    if not heads and impl == 1 and d == 64 and C % 256 == 0 and ops.fusable(dt, M, srcs[0][2] * C, C):
         route = "fused"
         # the softmax scale (nViT: sqrt(d) on unit q, k) times log2(e); with sqk absent the running-maximum kernel runs
         # on the pre-scaled q (and the dK/dV backward takes its generated loop)
@@ -327,7 +327,7 @@ def _attn_fwd(rt: _Runtime, impl: int, srcs, has_b: bool, sqk: Optional[Tensor],
         part0 = 0
         for A, w, n in srcs:
             ops.gemm_nt_qknorm(A, sh[w + ".W"], M, C, n, part0, sqk, c_q, B, T, H, d, bufs,
-                               q_prescale=(qpre if part0 == 0 else 1.0))
+                               q_prescale=(qpre if part0 == 0 else 1.0), bias=sh.get(w + ".b"))
             part0 += n
     else:
         projs = [ops.gemm_nt(A, sh[w + ".W"], M, n * C, C, out_dtype=torch.float32, bias=sh.get(w + ".b"))
@@ -370,19 +370,21 @@ def _attn_bwd(rt: _Runtime, att, saved, do: Tensor, o: Tensor, lse: Tensor, grad
     return ops.qknorm_bwd(dt, dqh, dkh, dvh, qh, kh, rq, rk, sqk, c_q, dq, lddq, dk, lddkv, dv, lddkv, B, T, H, d), None
 
 
-def _swiglu_fwd(rt: _Runtime, A: Tensor, w: str, M: int, F: int, K: int, has_b: bool, gs: Optional[Tensor],
+def _swiglu_fwd(rt: _Runtime, A: Tensor, w: str, M: int, F: int, K: int, gs: Optional[Tensor],
                 gs_fused: Optional[Tensor], gscale: float, lean: bool = False):
     """Gated MLP input: uv = A W^T (+ bias) [M, 2F] (shadow `w`, interleaved columns) and x = swiglu(uv) [M, F] with the
     gate scale gs * gscale (gs None: 1).  -> (uv as backward reads it, x).  The fused GEMM epilogue takes gs in the
-    shadow's interleaved column order (gs_fused), the row kernel in natural order (gs).
+    shadow's interleaved column order (gs_fused), the row kernel in natural order (gs); the bias shadow is interleaved
+    for both and joins the sums in either route's GEMM epilogue, so the saved uv includes it.
     lean (a forward no backward follows): uv is None - the fused GEMM does not store it (the gate-only epilogue, same
     x bit for bit), the unfused route does not make the bf16 copy."""
     dt, sh = rt.dt, rt.sh
-    if not has_b and ops.fusable(dt, M, 2 * F, K):
+    bias = sh.get(w + ".b")   # in the shadow's interleaved column order
+    if ops.fusable(dt, M, 2 * F, K):
         if lean:
-            return None, ops.gemm_nt_swiglu_act(A, sh[w + ".W"], M, F, K, gs_fused, gscale)
-        return ops.gemm_nt_swiglu(A, sh[w + ".W"], M, F, K, gs_fused, gscale)
-    uv32 = ops.gemm_nt(A, sh[w + ".W"], M, 2 * F, K, out_dtype=torch.float32, bias=sh.get(w + ".b"))
+            return None, ops.gemm_nt_swiglu_act(A, sh[w + ".W"], M, F, K, gs_fused, gscale, bias=bias)
+        return ops.gemm_nt_swiglu(A, sh[w + ".W"], M, F, K, gs_fused, gscale, bias=bias)
+    uv32 = ops.gemm_nt(A, sh[w + ".W"], M, 2 * F, K, out_dtype=torch.float32, bias=bias)
     # bf16: the gate from the unrounded pre-activations; the bf16 copy is what backward reads
     x = ops.swiglu_fwd(dt if dt == F32 else BF16_F32IN, uv32, gs, gscale, M, F)
     if lean:
@@ -423,14 +425,14 @@ class _BlockFn(torch.autograd.Function):
         c_q, c_a = 1.0 / cfg.base_scale, 0.05 / cfg.base_scale
         pre = f"h{idx}."
         has_b = bq is not None
-        o, lse, att, att_saved = _attn_fwd(rt, impl, ((x_lo, pre + "qkv", 3),), has_b, sqk, c_q, math.sqrt(d), dims,
+        o, lse, att, att_saved = _attn_fwd(rt, impl, ((x_lo, pre + "qkv", 3),), sqk, c_q, math.sqrt(d), dims,
                                            lean)
         y = ops.gemm_nt(o, sh[pre + "o.W"], M, C, C, out_dtype=rt.y_dtype(), bias=sh.get(pre + "o.b"))
         h1, h1_lo = ops.lerp_fwd(dt, x, y, attn_alpha, c_a, want_lo=(dt != F32))
         if dt == F32:
             h1_lo = h1
         # c_fc GEMM with the suv scale + SwiGLU gate (writes raw uv for backward and x_mlp)
-        uv, xm = _swiglu_fwd(rt, h1_lo, pre + "fc", M, 4 * C, C, has_b, suv, sh[pre + "suv_i"], math.sqrt(C), lean)
+        uv, xm = _swiglu_fwd(rt, h1_lo, pre + "fc", M, 4 * C, C, suv, sh[pre + "suv_i"], math.sqrt(C), lean)
         y2 = ops.gemm_nt(xm, sh[pre + "p.W"], M, C, 4 * C, out_dtype=rt.y_dtype(), bias=sh.get(pre + "p.b"))
         if with_skip:
             xn, xn_lo = ops.lerp_fwd(dt, h1, y2, mlp_alpha, c_a, skip_x=x, skip=skip_param, want_lo=(dt != F32))
@@ -538,9 +540,9 @@ class _CrossFn(torch.autograd.Function):
             loc_lo = ops.cast(loc, dt) if loc_lo is None else loc_lo
             glo_lo = ops.cast(glo, dt) if glo_lo is None else glo_lo
         # q from the local stream, k/v from the global stream
-        o, lse, att, att_saved = _attn_fwd(rt, impl, ((loc_lo, "x.q", 1), (glo_lo, "x.kv", 2)), has_b, sqk, c_q,
+        o, lse, att, att_saved = _attn_fwd(rt, impl, ((loc_lo, "x.q", 1), (glo_lo, "x.kv", 2)), sqk, c_q,
                                            math.sqrt(d), dims, lean)
-        pr, g = _swiglu_fwd(rt, o, "x.proj", M, C, C, has_b, None, None, 1.0, lean)
+        pr, g = _swiglu_fwd(rt, o, "x.proj", M, C, C, None, None, 1.0, lean)
         y = ops.gemm_nt(g, sh["x.out.W"], M, C, C, out_dtype=rt.y_dtype(), bias=sh.get("x.out.b"))
         x, x_lo = ops.lerp_fwd(dt, loc, y, attn_alpha, c_a, want_lo=(dt != F32))
         if dt == F32:
@@ -613,13 +615,13 @@ class _StdBlockFn(torch.autograd.Function):
         a, a_lo, r_att = ops.res_rmsnorm_fwd(dt, x, None, w_att.detach(), RMS_EPS, want_lo=lo)
         if not lo:
             a_lo = a
-        o, lse, att, att_saved = _attn_fwd(rt, impl, ((a_lo, pre + "qkv", 3),), has_b, None, 0.0, 1.0 / math.sqrt(d),
+        o, lse, att, att_saved = _attn_fwd(rt, impl, ((a_lo, pre + "qkv", 3),), None, 0.0, 1.0 / math.sqrt(d),
                                            dims, lean)
         y = ops.gemm_nt(o, sh[pre + "o.W"], M, C, C, out_dtype=rt.y_dtype(), bias=sh.get(pre + "o.b"))
         bm, bm_lo, r_mlp = ops.res_rmsnorm_fwd(dt, a, y, w_mlp.detach(), RMS_EPS, want_lo=lo)
         if not lo:
             bm_lo = bm
-        uv, xm = _swiglu_fwd(rt, bm_lo, pre + "fc", M, 4 * C, C, has_b, None, None, 1.0, lean)
+        uv, xm = _swiglu_fwd(rt, bm_lo, pre + "fc", M, 4 * C, C, None, None, 1.0, lean)
         if with_skip:
             y2 = ops.gemm_nt(xm, sh[pre + "p.W"], M, C, 4 * C, out_dtype=rt.y_dtype(), bias=sh.get(pre + "p.b"))
             xn, xn_lo = ops.res_skip_fwd(dt, bm, y2, skip_param.detach(), x, want_lo=(lo and want_lo))
@@ -709,9 +711,9 @@ class _StdCrossFn(torch.autograd.Function):
         gn, gn_lo, r_g = ops.res_rmsnorm_fwd(dt, glo, None, w_gn.detach(), RMS_EPS, want_lo=lo)
         if not lo:
             ln_lo, gn_lo = ln, gn
-        o, lse, att, att_saved = _attn_fwd(rt, impl, ((ln_lo, "x.q", 1), (gn_lo, "x.kv", 2)), has_b, None, 0.0,
+        o, lse, att, att_saved = _attn_fwd(rt, impl, ((ln_lo, "x.q", 1), (gn_lo, "x.kv", 2)), None, 0.0,
                                            1.0 / math.sqrt(d), dims, lean)
-        pr, g = _swiglu_fwd(rt, o, "x.proj", M, C, C, has_b, None, None, 1.0, lean)
+        pr, g = _swiglu_fwd(rt, o, "x.proj", M, C, C, None, None, 1.0, lean)
         out = ops.gemm_nt(g, sh["x.out.W"], M, C, C, out_dtype=torch.float32, bias=sh.get("x.out.b"))
         if lean:
             return out

@@ -80,22 +80,37 @@ def fusable(dt: int, M: int, N: int, K: int) -> bool:
     return bool(_lib.load().nvit_gemm_nt_fusable(dt, M, N, K)) and M * N >= FUSE_MIN_ELEMS
 
 
-def gemm_nt_swiglu(A: Tensor, B: Tensor, M: int, F: int, K: int, gs: Optional[Tensor], gscale: float):
-    """uv [M,2F] (raw, interleaved) and xm [M,F] = swiglu(uv) in one launch (bf16)."""
+def _chk_fused_bias(bias: Optional[Tensor], n: int, ref: Tensor, what: str) -> None:
+    """The bias of a fused-epilogue GEMM: contiguous fp32 [n] on the operands' device (the kernel reads it unchecked)."""
+    if bias is None:
+        return
+    if (bias.dtype != torch.float32 or bias.dim() != 1 or bias.numel() != n or not bias.is_contiguous()
+            or bias.device != ref.device):
+        raise ValueError(f"{what}: bias must be a contiguous fp32 tensor of {n} elements on {ref.device}, got "
+                         f"{bias.dtype} {tuple(bias.shape)} stride {bias.stride()} on {bias.device}")
+
+
+def gemm_nt_swiglu(A: Tensor, B: Tensor, M: int, F: int, K: int, gs: Optional[Tensor], gscale: float, *,
+                   bias: Optional[Tensor] = None):
+    """uv [M,2F] (raw, interleaved) and xm [M,F] = swiglu(uv) in one launch (bf16).
+    bias: fp32 [2F] in the interleaved column order of B (like gs), part of uv."""
     _chk_dev(A, B)
+    _chk_fused_bias(bias, 2 * F, A, "gemm_nt_swiglu")
     uv = torch.empty((M, 2 * F), device=A.device, dtype=torch.bfloat16)
     xm = torch.empty((M, F), device=A.device, dtype=torch.bfloat16)
-    check(_lib.load().nvit_gemm_nt_swiglu(dt_of(A), _p(A), A.stride(0), _p(B), B.stride(0), _p(uv), _p(xm), M, F, K,
-                                          _p(gs), gscale, _s()), "nvit_gemm_nt_swiglu")
+    check(_lib.load().nvit_gemm_nt_swiglu_bias(dt_of(A), _p(A), A.stride(0), _p(B), B.stride(0), _p(uv), _p(xm), M, F, K,
+                                               _p(gs), gscale, _p(bias), _s()), "nvit_gemm_nt_swiglu_bias")
     return uv, xm
 
 
-def gemm_nt_swiglu_act(A: Tensor, B: Tensor, M: int, F: int, K: int, gs: Optional[Tensor], gscale: float) -> Tensor:
+def gemm_nt_swiglu_act(A: Tensor, B: Tensor, M: int, F: int, K: int, gs: Optional[Tensor], gscale: float, *,
+                       bias: Optional[Tensor] = None) -> Tensor:
     """xm [M,F] of gemm_nt_swiglu, bit for bit, without the raw uv store (forward-only calls; bf16)."""
     _chk_dev(A, B)
+    _chk_fused_bias(bias, 2 * F, A, "gemm_nt_swiglu_act")
     xm = torch.empty((M, F), device=A.device, dtype=torch.bfloat16)
-    check(_lib.load().nvit_gemm_nt_swiglu_act(dt_of(A), _p(A), A.stride(0), _p(B), B.stride(0), _p(xm), M, F, K, _p(gs),
-                                              gscale, _s()), "nvit_gemm_nt_swiglu_act")
+    check(_lib.load().nvit_gemm_nt_swiglu_act_bias(dt_of(A), _p(A), A.stride(0), _p(B), B.stride(0), _p(xm), M, F, K,
+                                                   _p(gs), gscale, _p(bias), _s()), "nvit_gemm_nt_swiglu_act_bias")
     return xm
 
 
@@ -131,17 +146,20 @@ def attn_q_prescale(d: int) -> float:
 
 
 def gemm_nt_qknorm(A: Tensor, B: Tensor, M: int, K: int, nparts: int, part0: int, sqk: Optional[Tensor], c_q: float,
-                   Bsz: int, T: int, H: int, d: int, bufs=None, q_prescale: float = 1.0):
+                   Bsz: int, T: int, H: int, d: int, bufs=None, q_prescale: float = 1.0, *,
+                   bias: Optional[Tensor] = None):
     """q/k/v projection(s) with the per-head normalise, sqk scale and head split fused (bf16, d=64).
     sqk None: the head split alone (plain-ViT attention; rq, rk None).
-    q_prescale: extra factor folded into the q part (pass the same value to attn_fwd / attn_bwd_qknorm)."""
+    q_prescale: extra factor folded into the q part (pass the same value to attn_fwd / attn_bwd_qknorm).
+    bias: fp32 [nparts*H*d], the stacked biases of this launch's projections, added before the normalise."""
     _chk_dev(A, B)
+    _chk_fused_bias(bias, nparts * H * d, A, "gemm_nt_qknorm")
     if bufs is None:
         bufs = qk_buffers(dt_of(A), Bsz, T, H, d, A.device, norm=sqk is not None)
     qh, kh, vh, rq, rk = bufs
-    check(_lib.load().nvit_gemm_nt_qknorm(dt_of(A), _p(A), A.stride(0), _p(B), B.stride(0), M, K, nparts, part0,
-                                          _p(sqk), c_q, q_prescale, _p(qh), _p(kh), _p(vh), _p(rq), _p(rk), T, H, d,
-                                          _s()), "nvit_gemm_nt_qknorm")
+    check(_lib.load().nvit_gemm_nt_qknorm_bias(dt_of(A), _p(A), A.stride(0), _p(B), B.stride(0), M, K, nparts, part0,
+                                               _p(sqk), c_q, q_prescale, _p(qh), _p(kh), _p(vh), _p(rq), _p(rk), T, H,
+                                               d, _p(bias), _s()), "nvit_gemm_nt_qknorm_bias")
     return bufs
 
 
