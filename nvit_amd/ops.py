@@ -217,6 +217,17 @@ def gemm_tn(A: Tensor, B: Tensor, G: Tensor, Mred: int, N: int, K: int, perm: in
 # ----------------------------------------------------------------------------- row ops
 _LERP_BWD_BLOCKS: dict = {}
 PART_BLOCKS = 1024   # workgroups of the backward row kernels
+MAX_PART_BLOCKS = 4096   # the most a backward row kernel accepts
+
+
+def _part_blocks(nblk: Optional[int], default: int, name: str) -> int:
+    """Workgroups of a backward row kernel: the wrapper's own choice, or the caller's `nblk` as given (tests use it to
+    make a wave walk several rows at a small M; the partial arrays are sized from it)."""
+    if nblk is None:
+        return default
+    if isinstance(nblk, bool) or not isinstance(nblk, int) or not 1 <= nblk <= MAX_PART_BLOCKS:
+        raise ValueError(f"{name}: nblk must be an integer in 1..{MAX_PART_BLOCKS}, got {nblk!r}")
+    return nblk
 
 
 def lerp_fwd(dt: int, h: Tensor, y: Tensor, alpha: Tensor, c_a: float, skip_x: Optional[Tensor] = None,
@@ -231,9 +242,10 @@ def lerp_fwd(dt: int, h: Tensor, y: Tensor, alpha: Tensor, c_a: float, skip_x: O
 
 def lerp_bwd(dt: int, dout: Tensor, h: Tensor, y: Tensor, alpha: Tensor, c_a: float, skip_x: Optional[Tensor],
              skip: Optional[Tensor], dh: Optional[Tensor], accum_dh: bool, want_dy_f32: bool, want_dy_lo: bool,
-             dout_add: Optional[Tensor] = None):
+             dout_add: Optional[Tensor] = None, *, nblk: Optional[int] = None):
     """-> dh, dy_f32|None, dy_lo|None, dskip_x|None, part_dlam [4*nblk,C], part_dskip|None.
-    dout_add: optional bf16 [M,C] added to dout inside the kernel (a data-gradient GEMM's output)."""
+    dout_add: optional bf16 [M,C] added to dout inside the kernel (a data-gradient GEMM's output).
+    nblk: workgroups to launch instead of the resident count (1..4096)."""
     if dout_add is not None and (dout_add.dtype != torch.bfloat16 or dout_add.shape != h.shape or not dout_add.is_contiguous()):
         raise ValueError("lerp_bwd: dout_add must be a contiguous bf16 [M,C] tensor")
     M, Cc = h.shape
@@ -248,7 +260,7 @@ def lerp_bwd(dt: int, dout: Tensor, h: Tensor, y: Tensor, alpha: Tensor, c_a: fl
     if nres is None:
         nres = int(_lib.load().nvit_lerp_bwd_blocks(dt, dt_of(y), Cc, int(key[3]), int(key[4]), int(key[5]))) or PART_BLOCKS
         _LERP_BWD_BLOCKS[key] = nres
-    nblk = min(nres, math.ceil(M / 4))
+    nblk = _part_blocks(nblk, min(nres, math.ceil(M / 4)), "lerp_bwd")
     dy = torch.empty_like(h) if want_dy_f32 else None
     dy_lo = torch.empty((M, Cc), device=dev, dtype=tdtype(dt)) if want_dy_lo else None
     dskip_x = torch.empty_like(h) if skip_x is not None else None
@@ -268,10 +280,10 @@ def rmsnorm_fwd(x: Tensor, w: Tensor, eps: float):
     return out, rstd
 
 
-def rmsnorm_bwd(dout: Tensor, x: Tensor, w: Tensor, rstd: Tensor):
+def rmsnorm_bwd(dout: Tensor, x: Tensor, w: Tensor, rstd: Tensor, *, nblk: Optional[int] = None):
     """-> dx [M,C], dw [C]"""
     M, Cc = x.shape
-    nblk = min(PART_BLOCKS, math.ceil(M / 4))
+    nblk = _part_blocks(nblk, min(PART_BLOCKS, math.ceil(M / 4)), "rmsnorm_bwd")
     dx = torch.empty_like(x)
     part = torch.empty((nblk, Cc), device=x.device, dtype=torch.float32)
     check(_lib.load().nvit_rmsnorm_bwd(_p(dout), _p(x), _p(w), _p(rstd), _p(dx), _p(part), nblk, M, Cc, _s()),
@@ -325,7 +337,8 @@ def _row_part_blocks(M: int) -> int:
 
 
 def res_rmsnorm_bwd(dt: int, g: Tensor, a: Tensor, y: Optional[Tensor], w: Tensor, rstd: Tensor,
-                    g_add: Optional[Tensor] = None, dz: Optional[Tensor] = None, want_lo: bool = False):
+                    g_add: Optional[Tensor] = None, dz: Optional[Tensor] = None, want_lo: bool = False, *,
+                    nblk: Optional[int] = None):
     """Backward of res_rmsnorm_fwd -> dz fp32 (added to `dz` when given), dz_lo (type dt) | None, part_dw [4*nblk, C].
     g_add: optional type-dt [M,C] addend of the incoming gradient (a data-gradient GEMM's output)."""
     M, Cc = a.shape
@@ -337,7 +350,7 @@ def res_rmsnorm_bwd(dt: int, g: Tensor, a: Tensor, y: Optional[Tensor], w: Tenso
     accum = dz is not None
     if dz is None:
         dz = torch.empty_like(a)
-    nblk = _row_part_blocks(M)
+    nblk = _part_blocks(nblk, _row_part_blocks(M), "res_rmsnorm_bwd")
     dz_lo = torch.empty((M, Cc), device=a.device, dtype=tdtype(dt)) if want_lo else None
     part = torch.empty((4 * nblk, Cc), device=a.device, dtype=torch.float32)
     check(_lib.load().nvit_res_rmsnorm_bwd(dt, _p(g), _p(g_add), _p(a), _p(y), dt_of(y) if y is not None else F32, _p(w),
@@ -358,12 +371,13 @@ def res_skip_fwd(dt: int, h: Tensor, y: Tensor, skip: Tensor, x: Tensor, want_lo
     return out, out_lo
 
 
-def res_skip_bwd(dt: int, dout: Tensor, h: Tensor, y: Tensor, skip: Tensor, x: Tensor, want_lo: bool = True):
+def res_skip_bwd(dt: int, dout: Tensor, h: Tensor, y: Tensor, skip: Tensor, x: Tensor, want_lo: bool = True, *,
+                 nblk: Optional[int] = None):
     """Backward of res_skip_fwd -> dh = d(h + y) fp32, dh_lo (type dt) | None, dx fp32, part_dskip [4*nblk]."""
     M, Cc = h.shape
     _chk_rows((M, Cc), y, f32=(dout, h, x), name="res_skip_bwd")
     _chk_vec(1, skip, name="res_skip_bwd")
-    nblk = _row_part_blocks(M)
+    nblk = _part_blocks(nblk, _row_part_blocks(M), "res_skip_bwd")
     dh = torch.empty_like(h)
     dx = torch.empty_like(h)
     dh_lo = torch.empty((M, Cc), device=h.device, dtype=tdtype(dt)) if want_lo else None
@@ -381,9 +395,9 @@ def norm_skip_fwd(src: Tensor, tgt: Optional[Tensor], skip: Tensor) -> Tensor:
     return out
 
 
-def norm_skip_bwd(dout: Tensor, src: Tensor, tgt: Optional[Tensor], skip: Tensor):
+def norm_skip_bwd(dout: Tensor, src: Tensor, tgt: Optional[Tensor], skip: Tensor, *, nblk: Optional[int] = None):
     M, Cc = src.shape
-    nblk = min(PART_BLOCKS, math.ceil(M / 4))
+    nblk = _part_blocks(nblk, min(PART_BLOCKS, math.ceil(M / 4)), "norm_skip_bwd")
     dsrc = torch.empty_like(src)
     dtgt = torch.empty_like(src) if tgt is not None else None
     part = torch.empty((nblk,), device=src.device, dtype=torch.float32)
@@ -413,9 +427,9 @@ def qknorm_fwd(dt: int, q: Tensor, ldq: int, k: Tensor, ldk: int, v: Tensor, ldv
 
 
 def qknorm_bwd(dt: int, dqh, dkh, dvh, qh, kh, rq, rk, sqk, c_q: float, dq: Tensor, ldq: int, dk: Tensor, ldk: int,
-               dv: Tensor, ldv: int, B: int, T: int, H: int, d: int) -> Optional[Tensor]:
+               dv: Tensor, ldv: int, B: int, T: int, H: int, d: int, *, nblk: Optional[int] = None) -> Optional[Tensor]:
     """sqk None: the head merge alone (backward of the plain split); returns None instead of the d(sqk) partials."""
-    nblk = min(PART_BLOCKS, math.ceil(B * T / 4))
+    nblk = _part_blocks(nblk, min(PART_BLOCKS, math.ceil(B * T / 4)), "qknorm_bwd")
     part = torch.empty((nblk, H * d), device=dq.device, dtype=torch.float32) if sqk is not None else None
     check(_lib.load().nvit_qknorm_bwd(dt, _p(dqh), _p(dkh), _p(dvh), _p(qh), _p(kh), _p(rq), _p(rk), _p(sqk), c_q,
                                       _p(dq), ldq, _p(dk), ldk, _p(dv), ldv, _p(part), nblk, B, T, H, d, _s()),

@@ -270,8 +270,9 @@ def test_lerp_fwd_bwd(C, with_skip):
 @pytest.mark.parametrize("with_skip", [False, True])
 def test_lerp_bwd_bf16_addend_and_accumulate(C, with_skip):
     """The backward row kernel as the bf16 step calls it: y stored in bf16, the incoming gradient = an fp32 tensor + a
-    bf16 addend (the data-gradient GEMM's output), dh accumulated onto an existing tensor, dy written in bf16 only; W =
-    ceil(C / 256) waves share a row (1, 3, 4 and 5 here), ragged row count, against fp64 autograd on the same values."""
+    bf16 addend (the data-gradient GEMM's output), dh accumulated onto an existing tensor, dy written in bf16 only; one
+    wave owns a row with NV = 1, 3, 4 and 8 float4 groups per lane at these widths, ragged row count, against fp64
+    autograd on the same values."""
     ops = ops_()
     from nvit_amd._lib import BF16
     M = 517

@@ -415,8 +415,9 @@ def test_training_learns_in_bf16():
 def test_bf16_fused_route_vs_unfused_and_fp64(bias):
     """A shape that takes the fused epilogues (split-only q/k/v, SwiGLU forward and backward with gate scale 1, the
     MFMA attention backward's plain store) in bf16: logits and every parameter gradient against the float64
-    restatement, and against the same model with the fusions switched off.  With bias the q/k/v and c_fc GEMMs keep
-    their bias epilogues; the SwiGLU backward epilogue still runs."""
+    restatement, and against the same model with the fusions switched off.  With bias the fused q/k/v and c_fc GEMMs
+    add it inside their head-split and SwiGLU epilogues (the same fused kernels as without); the SwiGLU backward
+    epilogue runs as well."""
     cfg = named_config("mini_vit", n_embd=256, n_head=4, bias=bias)
     batch = 112
     X, y = synthetic_batch(cfg, batch)
