@@ -7,10 +7,10 @@ def __getattr__(name):
     if name in ("ViT", "Block", "CrossAttentionBlock", "RMSNorm"):
         from . import model
         return getattr(model, name)
-    if name in ("normalize_matrices", "train_step"):
+    if name in ("normalize_matrices", "train_step", "GraphedTrainStep"):
         from . import train
         return getattr(train, name)
-    if name in ("predict", "validate", "estimate_loss"):
+    if name in ("predict", "validate", "estimate_loss", "GraphedEval"):
         from . import evaluate
         return getattr(evaluate, name)
     if name == "FusedAdamW":

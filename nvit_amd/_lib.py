@@ -93,6 +93,7 @@ SIGNATURES = {
     "nvit_res_skip_fwd": [_i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp],
     "nvit_res_skip_bwd": [_i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
     "nvit_som_update": [_vp, _vp, _vp, _f, _f, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp],
+    "nvit_som_update_dev": [_vp, _vp, _vp, _vp, _f, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp],
     "nvit_cos_consistency_fwd": [_vp, _vp, _vp, _vp, _i, _vp, _i64, _i, _vp],
     "nvit_cos_consistency_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _vp],
     "nvit_huber_fwd": [_vp, _vp, _vp, _i, _vp, _i64, _vp],

@@ -109,10 +109,17 @@ __global__ void onehot_kernel(const long long* idx, float* out, long long M, int
 }
 
 // pooled sample vectors v[i][c] = mean(flat_i[c*T .. c*T+T-1]), flat_i = x[i] viewed as T*C floats; and the
-// update strengths s[i][node] = la * exp(-d2(node, bmu_i) / (2 sigma^2)), d2 = periodic grid distance^2
+// update strengths s[i][node] = la * exp(-d2(node, bmu_i) / (2 sigma^2)), d2 = periodic grid distance^2.
+// LA_DEV: la is read from la_dev[0] (device memory, rewritten by the host between replays of a captured step: a kernel
+// argument would be frozen at its capture-time value), else it is the argument la_arg.  The load is volatile so that it
+// is a per-lane vector load; every lane reads the same address.  The arithmetic is the same either way.
+template <bool LA_DEV>
 __global__ void som_prepare_kernel(const float* x, const long long* idx, float* v, float* strength, int B, int T, int C,
-                                   int Nn, int gm, int gn, float la, float inv2s2, int periodic) {
+                                   int Nn, int gm, int gn, float la_arg, const float* la_dev, float inv2s2,
+                                   int periodic) {
   const int i = blockIdx.x;
+  float la = la_arg;
+  if constexpr (LA_DEV) la = *reinterpret_cast<const volatile float*>(la_dev);
   for (int c = threadIdx.x; c < C; c += blockDim.x) {
     const float* p = x + ((size_t)i * T * C) + (size_t)c * T;
     float s = 0.f;
@@ -236,6 +243,12 @@ __global__ void sum_scale_kernel(const float* part, int n, float scale, float bi
 }
 
 // ---- map smoothness: mean over tokens and 8 neighbours of ||node[idx] - node[nb]||  (model.py:503-561)
+// zeroes the histogram ahead of hist_kernel.  A kernel, not hipMemsetAsync: a memset node of a captured hipGraph does not
+// reliably re-zero its block on replay (see the zero page in gemm.hip), and the captured Kohonen step replays this.
+__global__ void zero_i32_kernel(int* p, int n) {
+  for (int i = threadIdx.x; i < n; i += blockDim.x) p[i] = 0;
+}
+
 // Histogram of the BMU indices.  Early in training most tokens pick the same node, so one atomic per token would
 // serialise on a single address (measured 0.54 ms for 100k tokens): each wave first groups equal values with ballots
 // (one LDS add per distinct value), each workgroup then flushes its LDS bins with one global atomic per non-empty bin.
@@ -378,18 +391,41 @@ extern "C" int nvit_onehot(const int64_t* idx, float* out, int64_t M, int N, voi
   return NVIT_OK;
 }
 
-extern "C" int nvit_som_update(float* nodes, const float* x, const int64_t* idx, float lr_alpha, float sigma, int gm,
-                               int gn, int periodic, float* v_ws, float* s_ws, int B, int T, int C, void* stream) {
+namespace {
+
+// the two launches of nvit_som_update / nvit_som_update_dev: la_dev NULL = the rate by value
+int som_update_launch(float* nodes, const float* x, const int64_t* idx, float la, const float* la_dev, float sigma, int gm,
+                      int gn, int periodic, float* v_ws, float* s_ws, int B, int T, int C, hipStream_t s) {
   const int Nn = gm * gn;
   NVIT_REQUIRE(B > 0 && T > 0 && C > 0 && Nn > 0 && (int64_t)B <= (int64_t)B * T, "som_update: bad shape");
-  hipStream_t s = (hipStream_t)stream;
   ProfScope ps(NVIT_KID_MISC, 0.0, (double)B * T * C * 4.0, s);
-  hipLaunchKernelGGL(som_prepare_kernel, dim3(B), dim3(256), 0, s, x, (const long long*)idx, v_ws, s_ws, B, T, C, Nn, gm,
-                     gn, lr_alpha, 1.0f / (2.0f * sigma * sigma), periodic);
+  const float inv2s2 = 1.0f / (2.0f * sigma * sigma);
+  if (la_dev)
+    hipLaunchKernelGGL(som_prepare_kernel<true>, dim3(B), dim3(256), 0, s, x, (const long long*)idx, v_ws, s_ws, B, T, C,
+                       Nn, gm, gn, 0.0f, la_dev, inv2s2, periodic);
+  else
+    hipLaunchKernelGGL(som_prepare_kernel<false>, dim3(B), dim3(256), 0, s, x, (const long long*)idx, v_ws, s_ws, B, T, C,
+                       Nn, gm, gn, la, (const float*)nullptr, inv2s2, periodic);
   NVIT_CHECK_LAUNCH("som_prepare");
   hipLaunchKernelGGL(som_update_kernel, dim3(Nn), dim3(256), 0, s, nodes, v_ws, s_ws, B, C, Nn);
   NVIT_CHECK_LAUNCH("som_update");
   return NVIT_OK;
+}
+
+}  // namespace
+
+extern "C" int nvit_som_update(float* nodes, const float* x, const int64_t* idx, float lr_alpha, float sigma, int gm,
+                               int gn, int periodic, float* v_ws, float* s_ws, int B, int T, int C, void* stream) {
+  return som_update_launch(nodes, x, idx, lr_alpha, nullptr, sigma, gm, gn, periodic, v_ws, s_ws, B, T, C,
+                           (hipStream_t)stream);
+}
+
+extern "C" int nvit_som_update_dev(float* nodes, const float* x, const int64_t* idx, const float* lr_alpha, float sigma,
+                                   int gm, int gn, int periodic, float* v_ws, float* s_ws, int B, int T, int C,
+                                   void* stream) {
+  NVIT_REQUIRE(lr_alpha != nullptr, "som_update_dev: lr_alpha must point to one float in device memory");
+  return som_update_launch(nodes, x, idx, 0.0f, lr_alpha, sigma, gm, gn, periodic, v_ws, s_ws, B, T, C,
+                           (hipStream_t)stream);
 }
 
 extern "C" int nvit_cos_consistency_fwd(const float* a, const float* b, float* stats, float* part, int nblk, float* loss,
@@ -436,8 +472,8 @@ extern "C" int nvit_som_smooth_fwd(const float* nodes, const int64_t* idx, int* 
                                    int Nn, int C, int map_size, void* stream) {
   NVIT_REQUIRE(map_size * map_size == Nn, "som_smooth: nodes per map must be a perfect square");
   hipStream_t s = (hipStream_t)stream;
-  hipError_t e = hipMemsetAsync(cnt, 0, sizeof(int) * Nn, s);
-  if (e != hipSuccess) NVIT_FAIL((int)e, "som_smooth: memset: %s", hipGetErrorString(e));
+  hipLaunchKernelGGL(zero_i32_kernel, dim3(1), dim3(256), 0, s, cnt, Nn);
+  NVIT_CHECK_LAUNCH("som_smooth_zero");
   {
     long long hb = (M + 255) / 256;
     if (hb > 256) hb = 256;

@@ -103,3 +103,122 @@ def estimate_loss(model, batches: Iterable[Tuple[Tensor, Tensor]], eval_iters: i
         if total is None:
             raise ValueError("estimate_loss: no batches")
         return total.item() / n
+
+
+class GraphedEval:
+    """`predict`, `validate` and `estimate_loss` with the forward of one batch shape captured as hipGraphs and replayed:
+    a small model's evaluation is bound by its few hundred launches per batch, like its train step (GraphedTrainStep).
+
+    Two graphs are captured for the shape, dtype and device of (X, y).  `predict` and `validate` share one: the
+    forward-only route without the reconstruction head, nvit_eval_metrics adding into a device accumulator that
+    `validate` zeroes once per call, and the stacked Kohonen terms adding into a second one (`predict` ignores both
+    and returns a copy of the logits).  `estimate_loss` has its own, because with the Kohonen head its forward runs the
+    reconstruction head: it zeroes a per-batch accumulator, runs nvit_eval_metrics, weights the aux terms
+    (train.add_aux_losses, with the two weights given here) and adds the batch's loss to the running total.  These are
+    the fp32 additions of the module-level functions in their order, so every result is bit-identical to theirs.  A
+    batch of another shape, dtype or device (the short last batch of a loader) runs eagerly through the same code.
+
+    The weight shadows are rebuilt inside the captured forward, so weight changes between calls (training) are picked
+    up.  Every call restores the model's `training` flag and leaves `model.step` and the SOM nodes alone.  The object is
+    invalid after `model.set_precision(...)` and after anything that reallocates the parameters or the SOM nodes
+    (`model.to(...)`, loading a state dict by assignment, a resize): the graphs hold their addresses; build a new one.
+    """
+
+    def __init__(self, model, X: Tensor, y: Tensor, consistency_weight: float = 0.1, smoothness_weight: float = 0.1):
+        self.model = model
+        self.cw, self.sw = consistency_weight, smoothness_weight
+        with _eval_mode(model) as m:   # (refuses a CPU-resident model before anything is changed)
+            if X.device.type != "cuda" or y.device != X.device:
+                raise RuntimeError("GraphedEval: inputs must live on the HIP device")
+            self.X, self.y = X.clone(), y.clone()
+            dev = X.device
+            self._acc = torch.zeros(4, device=dev, dtype=torch.float32)
+            self._aux_acc = torch.zeros(len(_KOHONEN_KEYS), device=dev, dtype=torch.float32)
+            self._bacc = torch.zeros(4, device=dev, dtype=torch.float32)
+            self._total = torch.zeros((), device=dev, dtype=torch.float32)
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):   # builds every cache (shadow tables, LDS attributes) ahead of the capture
+                self._metrics_batch(m, self.X, self.y)
+                self._loss_batch(m, self.X, self.y)
+            torch.cuda.current_stream().wait_stream(side)
+            torch.cuda.synchronize()
+            self._g_metrics, self._g_loss = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self._g_metrics, stream=side):
+                self._logits = self._metrics_batch(m, self.X, self.y)
+            with torch.cuda.graph(self._g_loss, stream=side):
+                self._loss_batch(m, self.X, self.y)
+
+    # ---- one batch, eagerly or under capture: the loop bodies of validate / estimate_loss on this object's accumulators
+    def _metrics_batch(self, m, X: Tensor, y: Tensor) -> Tensor:
+        logits, aux = m._forward(X, False)
+        ops.eval_metrics(logits, y, self._acc)
+        if m.config.use_kohonen:
+            self._aux_acc += torch.stack([aux[k].reshape(()) for _, k in _KOHONEN_KEYS])
+        return logits
+
+    def _loss_batch(self, m, X: Tensor, y: Tensor) -> None:
+        logits, aux = m._forward(X, m.config.use_kohonen)
+        self._bacc.zero_()
+        ops.eval_metrics(logits, y, self._bacc)
+        self._total += add_aux_losses(m.config, self._bacc[0], aux, self.cw, self.sw)
+
+    def _fits(self, X: Tensor, y: Tensor) -> bool:
+        return (X.shape == self.X.shape and X.dtype == self.X.dtype and X.device == self.X.device
+                and y.shape == self.y.shape and y.dtype == self.y.dtype and y.device == self.y.device)
+
+    def _load(self, X: Tensor, y: Tensor) -> None:
+        self.X.copy_(X, non_blocking=True)
+        self.y.copy_(y, non_blocking=True)
+
+    def predict(self, X: Tensor) -> Tensor:
+        """evaluate.predict(model, X); a new tensor."""
+        if not (X.shape == self.X.shape and X.dtype == self.X.dtype and X.device == self.X.device):
+            return predict(self.model, X)
+        with _eval_mode(self.model):
+            self.X.copy_(X, non_blocking=True)
+            self._g_metrics.replay()
+            return self._logits.clone()
+
+    def validate(self, batches: Iterable[Tuple[Tensor, Tensor]]) -> Dict[str, float]:
+        """evaluate.validate(model, batches)."""
+        with _eval_mode(self.model) as m:
+            koh = m.config.use_kohonen
+            self._acc.zero_()
+            self._aux_acc.zero_()
+            n = 0
+            for X, y in batches:
+                if self._fits(X, y):
+                    self._load(X, y)
+                    self._g_metrics.replay()
+                else:
+                    self._metrics_batch(m, X, y)
+                n += 1
+            if n == 0:
+                raise ValueError("validate: no batches")
+            host = torch.cat([self._acc, self._aux_acc]).tolist()   # the call's one synchronisation
+        n = host[3]
+        out = {"val/loss": host[0] / n, "val/top1_accuracy": host[1] / n, "val/top5_accuracy": host[2] / n}
+        if koh:
+            out.update({name: host[4 + i] / n for i, (name, _) in enumerate(_KOHONEN_KEYS)})
+        return out
+
+    def estimate_loss(self, batches: Iterable[Tuple[Tensor, Tensor]], eval_iters: int) -> float:
+        """evaluate.estimate_loss(model, batches, eval_iters) with the weights given to the constructor."""
+        if eval_iters < 1:
+            raise ValueError("estimate_loss: eval_iters must be at least 1")
+        with _eval_mode(self.model) as m:
+            self._total.zero_()
+            n = 0
+            for X, y in batches:
+                if n >= eval_iters:
+                    break
+                if self._fits(X, y):
+                    self._load(X, y)
+                    self._g_loss.replay()
+                else:
+                    self._loss_batch(m, X, y)
+                n += 1
+            if n == 0:
+                raise ValueError("estimate_loss: no batches")
+            return self._total.item() / n

@@ -97,6 +97,9 @@ class KohonenMap(nn.Module):
             offsets = [[-self.m, -self.n], [self.m, self.n], [-self.m, 0], [self.m, 0], [0, -self.n], [0, self.n],
                        [-self.m, self.n], [self.m, -self.n]]
             self.register_buffer("offsets", torch.tensor(offsets))
+        # set only while train.GraphedTrainStep captures a step: a 1-element fp32 device tensor that update_nodes hands
+        # to the kernel in place of learning_rate * alpha (the captured launch reads it on every replay)
+        object.__setattr__(self, "_rate_dev", None)
 
     def get_neighborhood_distances(self, bmu_loc: Tensor) -> Tensor:
         """Squared grid distance of every node to `bmu_loc` ([2]: row, col); on the periodic map the minimum over the
@@ -129,5 +132,6 @@ class KohonenMap(nn.Module):
         if x.dim() != 3:
             raise ValueError("update_nodes expects x of shape [B, T, C]")
         B, T, _ = x.shape
+        rate = self._rate_dev if self._rate_dev is not None else float(learning_rate) * float(self.alpha)
         ops.som_update(self.nodes.data, x.detach().contiguous().float(), winning_indices.reshape(-1).contiguous(),
-                       float(learning_rate) * float(self.alpha), self.sigma, self.m, self.n, B, T, periodic=self.periodic)
+                       rate, self.sigma, self.m, self.n, B, T, periodic=self.periodic)

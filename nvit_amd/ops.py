@@ -762,11 +762,24 @@ def scatter_rows(dout: Tensor, idx: Tensor, N: int) -> Tensor:
     return gemm_tn(onehot(idx, N), dout.float().contiguous(), dn, M, N, Cc)
 
 
-def som_update(nodes: Tensor, x: Tensor, idx: Tensor, lr_alpha: float, sigma: float, gm: int, gn: int, B: int,
+def som_update(nodes: Tensor, x: Tensor, idx: Tensor, lr_alpha, sigma: float, gm: int, gn: int, B: int,
                T: int, periodic: bool = True) -> None:
+    """KohonenMap.update_nodes for the whole batch, in place on nodes.  lr_alpha (learning rate x the map's alpha): a
+    Python float, passed by value (nvit_som_update), or a 1-element fp32 tensor on the nodes' device that the kernel reads
+    when it runs (nvit_som_update_dev: a captured step whose host rewrites the rate between replays).  Equal values
+    give equal bits."""
+    dev_rate = isinstance(lr_alpha, Tensor)
+    if dev_rate and (lr_alpha.dtype != torch.float32 or lr_alpha.numel() != 1 or not lr_alpha.is_cuda
+                     or lr_alpha.device != nodes.device):
+        raise ValueError(f"som_update: a tensor lr_alpha must be one fp32 element on the nodes' device ({nodes.device}), "
+                         f"got {lr_alpha.dtype} {tuple(lr_alpha.shape)} on {lr_alpha.device}")
     Cc = nodes.shape[1]
     v_ws = torch.empty((B, Cc), device=nodes.device, dtype=torch.float32)
     s_ws = torch.empty((B, gm * gn), device=nodes.device, dtype=torch.float32)
+    if dev_rate:
+        check(_lib.load().nvit_som_update_dev(_p(nodes), _p(x), _p(idx), _p(lr_alpha), sigma, gm, gn, int(periodic),
+                                              _p(v_ws), _p(s_ws), B, T, Cc, _s()), "nvit_som_update_dev")
+        return
     check(_lib.load().nvit_som_update(_p(nodes), _p(x), _p(idx), lr_alpha, sigma, gm, gn, int(periodic), _p(v_ws), _p(s_ws),
                                       B, T, Cc, _s()), "nvit_som_update")
 

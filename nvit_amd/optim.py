@@ -71,6 +71,7 @@ class FusedAdamW(torch.optim.AdamW):
         rows: List[List[int]] = []
         key = []
         hypers: List[int] = []   # per row: lr | weight_decay bits (column 9 of the table)
+        groups: List[int] = []   # per row: index of its param group
         first_item = first_chunk = 0
         max_slab_rows = 0
         beta_eps = None
@@ -118,6 +119,7 @@ class FusedAdamW(torch.optim.AdamW):
                              r, c, kind, first_item, first_chunk, hyper])
                 key.append((p.data_ptr(), g.data_ptr(), kind))
                 hypers.append(hyper)
+                groups.append(gi)
                 first_item += items
                 first_chunk += math.ceil(p.numel() / _CHUNK)
         key = tuple(key)
@@ -156,6 +158,7 @@ class FusedAdamW(torch.optim.AdamW):
             self._cache = {
                 "key": key,
                 "hypers": hypers,
+                "groups": groups,
                 "table": table,
                 "n": len(rows), "items": first_item, "chunks": first_chunk, "slab": max_slab_rows,
                 "partial": torch.empty(_NPART, device=dev, dtype=torch.float32),
@@ -217,8 +220,8 @@ class FusedAdamW(torch.optim.AdamW):
                 t = v
         return t or 0
 
-    def _write_hyper_column(self, hypers: List[int]) -> None:
-        c = self._cache
+    def _write_hyper_column(self, hypers: List[int], c=None) -> None:
+        c = self._cache if c is None else c
         hcol = torch.tensor(hypers, dtype=torch.int64)
         if c["staged"]:
             torch.cuda.current_stream().synchronize()   # no replay may be reading the staging buffer while it changes
@@ -236,23 +239,21 @@ class FusedAdamW(torch.optim.AdamW):
             self._hyper_ev.record()
         c["hypers"] = list(hypers)
 
-    def rewrite_hyper(self) -> None:
+    def rewrite_hyper(self, cache=None) -> None:
         """Push the param groups' current lr / weight_decay into the device table in place (same addresses, so a
-        captured step picks them up on its next replay)."""
-        c = self._cache
+        captured step picks them up on its next replay).  cache: the table a captured step was recorded with
+        (GraphedTrainStep keeps it: an eager step taken after the capture builds a table of its own)."""
+        c = self._cache if cache is None else cache
         if c is None:
             return
         col = []
-        for group in self.param_groups:
+        for gi in c["groups"]:
+            group = self.param_groups[gi]
             hyper = _f32_bits(group["lr"]) | (_f32_bits(group["weight_decay"]) << 32)
             if hyper >= 1 << 63:
                 hyper -= 1 << 64
-            for p in group["params"]:
-                if p.grad is not None:
-                    col.append(hyper)
-        if len(col) != c["n"]:
-            raise RuntimeError("FusedAdamW.rewrite_hyper: parameter set changed since the table was built")
-        self._write_hyper_column(col)
+            col.append(hyper)
+        self._write_hyper_column(col, c)
 
     def reserve_staging(self) -> None:
         """Pinned host image for the parameter table, allocated ahead of a hipGraph capture."""

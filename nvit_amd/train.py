@@ -119,18 +119,24 @@ class GraphedTrainStep:
     """The whole train step (forward, loss, backward, clip + AdamW + renorm) captured once as a hipGraph and replayed.
 
     SURVEY.md §8f F2: for C1-sized models the eager step is bound by ~600 kernel launches, not by the GPU.  Needs the
-    FusedAdamW optimizer (its step counter and bias corrections live on the device, so replays stay correct), a
-    model without the Kohonen head (its SOM schedule is host state), a fixed batch shape and a single process
-    (the data-parallel wrapper launches RCCL work from autograd hooks and stays eager).  The learning rate is the one
-    in the optimizer's param groups at capture time; `set_lr` rewrites it on the device between replays.
+    FusedAdamW optimizer (its step counter and bias corrections live on the device, so replays stay correct), a fixed
+    batch shape and a single process (the data-parallel wrapper launches RCCL work from autograd hooks and stays
+    eager).  The learning rate is the one in the optimizer's param groups at capture time; `set_lr` rewrites it on the
+    device between replays.
+
+    The Kohonen head's SOM schedule stays host state (`model.step`, `get_kohonen_lr`): the captured SOM updates read
+    their rate (learning rate x the map's alpha, what the eager call passes by value) from one device float per map
+    (nvit_som_update_dev), which `__call__` rewrites from a pinned host twin ahead of every replay.  Only the capture
+    pass takes that route; the warm-up steps and any eager `train_step` on the same model pass the rate by value.
+    After N calls `model.step`, the optimizer's step count, the weights and the SOM nodes are those of N eager steps.
+    The model's `training` flag at capture time is part of the graph.  Like the eager step, a call leaves every
+    `p.grad` None (the graph keeps its own gradient buffers), so eager and graphed steps can alternate on one model.
     """
 
     def __init__(self, model, optimizer, X: torch.Tensor, y: torch.Tensor, grad_clip: float = 1.0, warmup: int = 3):
         m = _unwrap(model)
         if not isinstance(optimizer, FusedAdamW):
             raise RuntimeError("GraphedTrainStep needs the FusedAdamW returned by ViT.configure_optimizers")
-        if m.config.use_kohonen:
-            raise RuntimeError("GraphedTrainStep: the Kohonen head keeps host-side step state; run it eagerly")
         if hasattr(model, "module"):
             raise RuntimeError("GraphedTrainStep: wrap the bare model (data-parallel steps run eagerly)")
         if X.device.type != "cuda":
@@ -146,27 +152,64 @@ class GraphedTrainStep:
         torch.cuda.synchronize()
         optimizer.zero_grad(set_to_none=True)
         optimizer.reserve_staging()
+        # SOM rates: one device float per map and their pinned host twin, guarded by an event (the copy queued by the
+        # previous call must have read the twin before it is overwritten)
+        self._maps = [m.local_kohonen, m.global_kohonen] if m.config.use_kohonen else []
+        self._steps = bool(m.training)   # the captured forward is the training one: each replay is one model.step
+        if self._maps:
+            self._rate_dev = torch.zeros(len(self._maps), device=X.device, dtype=torch.float32)
+            self._rate_pin = torch.zeros(len(self._maps), dtype=torch.float32).pin_memory()
+            self._rate_ev = torch.cuda.Event()
+        step0 = m.step
         self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph, stream=side):
-            logits, aux = model(self.X)
-            loss = total_loss(m.config, logits, aux, self.y)
-            loss.backward()
-            gnorm = optimizer.step_fused(model, grad_clip)
+        try:
+            for i, km in enumerate(self._maps):
+                object.__setattr__(km, "_rate_dev", self._rate_dev[i:i + 1])
+            with torch.cuda.graph(self.graph, stream=side):
+                logits, aux = model(self.X)
+                loss = total_loss(m.config, logits, aux, self.y)
+                loss.backward()
+                gnorm = optimizer.step_fused(model, grad_clip)
+        finally:
+            for km in self._maps:
+                object.__setattr__(km, "_rate_dev", None)
         self.logits, self.loss = logits.detach(), loss.detach()
         self.aux = {k: v.detach() for k, v in aux.items()}
         self.gnorm = gnorm
-        optimizer.note_replay(-1)   # the capture pass records the step but does not execute it
+        optimizer.note_replay(-1)   # the capture pass records the step but does not execute it,
+        m.step = step0              # nor is it a step of the SOM schedule
+        # the graph's gradient buffers and optimizer table stay alive here; the parameters are left as the eager step
+        # leaves them (grad None), so an eager step on this model does not accumulate into a replay's gradients
+        self._grads = [p.grad for p in m.parameters() if p.grad is not None]
+        self._table = optimizer._cache
+        optimizer.zero_grad(set_to_none=True)
 
     def set_lr(self, lr: float) -> None:
         for group in self.optimizer.param_groups:
             group["lr"] = lr
-        self.optimizer.rewrite_hyper()
+        self.optimizer.rewrite_hyper(self._table)
+
+    def _advance_som(self) -> None:
+        """model.step += 1 and, per map, the rate the eager forward of that step would pass by value, sent to the device
+        scalars on the current stream (ahead of the replay)."""
+        m = _unwrap(self.model)
+        if self._steps:
+            m.step += 1
+        if not self._maps:
+            return
+        lr = m.get_kohonen_lr(m.step)
+        self._rate_ev.synchronize()
+        for i, km in enumerate(self._maps):
+            self._rate_pin[i] = float(lr) * float(km.alpha)   # rounded to fp32 as the by-value argument is
+        self._rate_dev.copy_(self._rate_pin, non_blocking=True)
+        self._rate_ev.record()
 
     def __call__(self, X: torch.Tensor, y: torch.Tensor):
         """One optimizer step on (X, y); returns (logits, loss, aux, grad_norm) as static device tensors that the
         next call overwrites."""
         self.X.copy_(X, non_blocking=True)
         self.y.copy_(y, non_blocking=True)
+        self._advance_som()
         self.graph.replay()
         self.optimizer.note_replay()
         return self.logits, self.loss, self.aux, (self.gnorm[0] if self.gnorm is not None else None)

@@ -3,6 +3,11 @@
 
     python tools/eval_bench.py --config base --batch 128 --precision bf16
     python tools/eval_bench.py --config base --batch 128 --against ../other_tree --out profiles/x.json
+    python tools/eval_bench.py --config micro_k --batch 512 --graph
+
+`--graph` times `nvit_amd.GraphedEval(model, X, y).predict(X)` instead: the forward replayed as a hipGraph.  That is the
+forward without the reconstruction head plus a copy of the logits, so its logits sum equals the plain run's while its
+work is slightly less than `model(X)`'s; a tree without GraphedEval fails the round.
 
 Only the public API is used, so the same file measures any tree of this project that has been built: `--against DIR`
 measures this tree and the one at DIR in alternation (round 1 here, round 1 there, round 2 here, ...), which is how
@@ -34,16 +39,21 @@ def worker(args) -> None:
     m = ViT(cfg)
     load_formula_weights(m, cfg)
     m = m.to("cuda:0").set_precision(args.precision).eval()
-    X = synthetic_batch(cfg, args.batch)[0].to("cuda:0")
+    X, y = (t.to("cuda:0") for t in synthetic_batch(cfg, args.batch))
+    if args.graph:
+        from nvit_amd import GraphedEval
+        step = GraphedEval(m, X, y).predict
+    else:
+        step = lambda x: m(x)[0]
     with torch.no_grad():
         for _ in range(args.warmup):
-            logits = m(X)[0]
+            logits = step(X)
         torch.cuda.synchronize()
         windows = []
         for _ in range(args.windows):
             n, t0 = 0, time.perf_counter()
             while True:
-                logits = m(X)[0]
+                logits = step(X)
                 n += 1
                 if n % 4 == 0 or args.window == 0:
                     torch.cuda.synchronize()
@@ -64,6 +74,8 @@ def run_round(args, tree: str) -> dict:
     cmd = ["timeout", "-k", "10", str(args.step_timeout), sys.executable, os.path.abspath(__file__), "--worker",
            "--tree", tree, "--config", args.config, "--batch", str(args.batch), "--precision", args.precision,
            "--warmup", str(args.warmup), "--window", str(args.window), "--windows", str(args.windows)]
+    if args.graph:
+        cmd.append("--graph")
     r = subprocess.run(cmd, capture_output=True, text=True)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("EVAL_BENCH ")]
     if r.returncode != 0 or not lines:
@@ -90,6 +102,7 @@ def main() -> int:
     ap.add_argument("--window", type=float, default=1.5, help="least seconds of a timed window")
     ap.add_argument("--windows", type=int, default=3, help="timed windows per round")
     ap.add_argument("--step-timeout", type=int, default=300, help="time limit of one round, seconds")
+    ap.add_argument("--graph", action="store_true", help="time GraphedEval.predict (the forward replayed as a hipGraph)")
     ap.add_argument("--against", default=None, help="a second built tree of this project, measured in alternation")
     ap.add_argument("--out", default=None, help="also write the JSON object to this file")
     ap.add_argument("--tree", default=HERE, help=argparse.SUPPRESS)
@@ -111,7 +124,7 @@ def main() -> int:
         if failed:
             break
     out = {"what": "forward-only throughput: eval(), torch.no_grad(), model(X); ms per batch = fastest window of a round",
-           "config": args.config, "batch": args.batch, "precision": args.precision, "window_s": args.window,
+           "graph": args.graph, "config": args.config, "batch": args.batch, "precision": args.precision, "window_s": args.window,
            "windows_per_round": args.windows, "warmup": args.warmup}
     for k, _ in trees:
         if rounds[k]:
