@@ -265,6 +265,29 @@ int nvit_qknorm_bwd(int dt, const void* dqh, const void* dkh, const void* dvh, c
                     void* dk, int ldk, void* dv, int ldv, float* part_dsqk, int nblk, int B, int T, int H,
                     int d, void* stream);
 
+/* ---- zero-padded heads: head dims d that are no power of two on the dp = 128 attention kernels ----
+ * The head tensors are [B,H,T,dp] with columns d..dp-1 stored as zeros (no score, no output column < d and no gradient
+ * column < d changes); nvit_attn_fwd / _fwd_bounded / _bwd then run at head dim dp with the scale of the REAL d.
+ * dp = 128, d % 8 == 0, 0 < d < dp, H*d <= 2048, any B*T >= 1.  Deterministic, no atomics.
+ * nvit_heads_pad_fwd: nvit_qknorm_fwd from fp32 projections (dt NVIT_F32: fp32 head tensors, NVIT_BF16_F32IN: bf16)
+ *   into qh, kh, vh [B,H,T,dp]; EVERY pad column is stored (as +0) on every launch.  sqk (compact [H*d]) given: the sum
+ *   of squares over the d real columns from the unrounded projections, rq, rk [M,H], and - sqk_pad not NULL - sqk_pad
+ *   [H*dp] = sqk with zero pads (what nvit_attn_fwd_bounded indexes at head dim dp).  sqk NULL: the split alone.
+ * nvit_heads_pad_bwd: nvit_qknorm_bwd (same formulas; sqk NULL: the merge alone) reading the first d columns of
+ *   dqh, dkh, dvh, qh, kh [B,H,T,dp] (type dt); dq/dk/dv token-major (type dt, row strides ld*), part_dsqk [nblk, H*d]
+ *   in compact channel order.
+ * nvit_pad_cols:   dst [M, H*dp] = src [M, H*d] with zero pads (dO; O for the dQ kernel's rowsum(dO*O) over dp columns).
+ * nvit_unpad_cols: dst [M, H*d] = the first d columns of every head of src [M, H*dp] (O for the output projection). */
+int nvit_heads_pad_fwd(int dt, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
+                       const float* sqk, float c_q, void* qh, void* kh, void* vh, float* rq, float* rk,
+                       float* sqk_pad, int B, int T, int H, int d, int dp, void* stream);
+int nvit_heads_pad_bwd(int dt, const void* dqh, const void* dkh, const void* dvh, const void* qh, const void* kh,
+                       const float* rq, const float* rk, const float* sqk, float c_q, void* dq, int ldq,
+                       void* dk, int ldk, void* dv, int ldv, float* part_dsqk, int nblk, int B, int T, int H,
+                       int d, int dp, void* stream);
+int nvit_pad_cols(int dt, const void* src, void* dst, int M, int H, int d, int dp, void* stream);
+int nvit_unpad_cols(int dt, const void* src, void* dst, int M, int H, int d, int dp, void* stream);
+
 /* nvit_swiglu_fwd: x[m,j] = (gu*u) * silu(gv*v), u = uv[m, 32*(j/16) + j%16], v = uv[m, 32*(j/16)+16+j%16]
  * (interleaved GEMM output, see perm=1), gu = gscale*suv[j], gv = gscale*suv[F+j]; suv may be NULL (=1)
  * (model.py:148-154 with gscale = sqrt(C); cross-attention gate model.py:259-261 with suv=NULL). */

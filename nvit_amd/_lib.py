@@ -61,6 +61,11 @@ SIGNATURES = {
     "nvit_qknorm_fwd": [_i, _vp, _i, _vp, _i, _vp, _i, _vp, _f, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "nvit_qknorm_bwd": [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i,
                         _i, _i, _vp],
+    "nvit_heads_pad_fwd": [_i, _vp, _i, _vp, _i, _vp, _i, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
+    "nvit_heads_pad_bwd": [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i,
+                           _i, _i, _i, _vp],
+    "nvit_pad_cols": [_i, _vp, _vp, _i, _i, _i, _i, _vp],
+    "nvit_unpad_cols": [_i, _vp, _vp, _i, _i, _i, _i, _vp],
     "nvit_swiglu_fwd": [_i, _vp, _vp, _f, _vp, _i, _i, _vp],
     "nvit_swiglu_bwd": [_i, _vp, _vp, _vp, _f, _vp, _vp, _i, _i, _i, _vp],
     "nvit_colsum_reduce_multi": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp],

@@ -73,9 +73,18 @@ def named_config(name: str, **over) -> ViTConfig:
         "wide2k": dict(image_size=32, n_embd=2048, n_head=16, n_layer=1, num_classes=16),
         "wide_k": dict(image_size=32, n_embd=1280, n_head=20, n_layer=2, num_classes=16, use_kohonen=True,
                        kohonen_nodes=32, kohonen_alpha=0.05),
-        # nViT-Huge-sized: ViT-H's 16 heads at n_embd = 1280 give head dim 80, which the attention kernels do not have;
-        # 20 heads of 64 is the nearest shape on the fused path
+        # nViT-Huge-sized on the fused path: 20 heads of 64 at n_embd = 1280.  ViT-H's own 16 heads give head dim 80, which
+        # runs on the zero-padded 128-wide attention heads: "huge16" below
         "huge": dict(image_size=224, n_embd=1280, n_layer=32, n_head=20, num_classes=1000),
+        # head dims 72 / 80 / 88 / 104 (SO400M, ViT-H, ViT-g, ViT-G) on zero-padded 128-wide attention heads: small parity
+        # configs (a ragged token count, the Kohonen head, biases, the plain-ViT baseline) and the true ViT-H geometry
+        "hd80": dict(image_size=56, n_embd=320, n_head=4, n_layer=2, num_classes=16),
+        "hd80_k": dict(image_size=32, n_embd=320, n_head=4, n_layer=2, num_classes=16, use_kohonen=True,
+                       kohonen_nodes=32, kohonen_alpha=0.05),
+        "hd72": dict(image_size=32, n_embd=576, n_head=8, n_layer=1, num_classes=16),
+        "hd104_b": dict(image_size=32, n_embd=832, n_head=8, n_layer=1, num_classes=16, bias=True),
+        "hd88_vit": dict(image_size=32, n_embd=704, n_head=8, n_layer=1, num_classes=16, use_nvit=False),
+        "huge16": dict(image_size=224, n_embd=1280, n_layer=32, n_head=16, num_classes=1000),
     }
     # Base with biases on every linear (the reference's shipped settings carry bias: true; stock ViT checkpoints too)
     table["base_b"] = dict(table["base"], bias=True)

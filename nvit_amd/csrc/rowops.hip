@@ -480,6 +480,157 @@ __global__ __launch_bounds__(256) void merge_heads_kernel(QkBwdArgs a) {
   }
 }
 
+// ------------------------------------------------------------------------------ zero-padded heads
+// Head dims d < 128 that are no power of two (72, 80, 88, 104) run on the D = 128 attention kernels: the head tensors are
+// [B,H,T,PAD_D] with columns d..PAD_D-1 stored as zeros, which change no score, no output column < d and no gradient
+// column < d.  These kernels index a row in PADDED coordinates: lane l of pass p owns columns pc..pc+3 of the H*PAD_D
+// wide padded row, pc = p*256 + 4l, so a head is always one aligned group of 32 lanes (two heads per pass) whatever d is,
+// and the lanes with pc % PAD_D >= d load nothing and store the zeros.
+constexpr int PAD_D = 128;
+
+struct PadSplitArgs {
+  const float *q, *k, *v;   // fp32 projection outputs
+  int ldq, ldk, ldv;
+  const float* sqk;
+  float c_q;
+  void *qh, *kh, *vh;
+  float *rq, *rk;
+  float* sqk_pad;   // [H*PAD_D]: sqk with zero pads, for nvit_attn_fwd_bounded at D = PAD_D (NORM only; may be NULL)
+  int B, T, H, d;
+};
+
+__device__ __forceinline__ float dot4(f32x4 a, f32x4 b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2] + a[3] * b[3]; }
+
+// heads_pad_fwd_kernel: qknorm_fwd_kernel (NORM: normalise from the unrounded projections, one rounding at the head
+// tensors; !NORM: the split alone) into zero-padded head tensors.  Every launch stores every pad column.
+template <typename T, bool NORM>
+__global__ __launch_bounds__(256) void heads_pad_fwd_kernel(PadSplitArgs a) {
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int M = a.B * a.T, HP = a.H * PAD_D;
+  const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+  if constexpr (NORM) {
+    if (a.sqk_pad && blockIdx.x == 0) {
+      for (int pc = threadIdx.x * 4; pc < HP; pc += 1024) {
+        const int h = pc / PAD_D, j = pc % PAD_D;
+        store4<float>(a.sqk_pad + pc, j < a.d ? load4<float>(a.sqk + h * a.d + j) : z);
+      }
+    }
+  }
+  for (int m = blockIdx.x * ROW_WAVES + wid; m < M; m += gridDim.x * ROW_WAVES) {
+    const int b = m / a.T, t = m % a.T;
+    for (int p0 = 0; p0 < HP; p0 += 256) {
+      const int pc = p0 + lane * 4;
+      const int h = pc / PAD_D, j = pc % PAD_D;
+      const bool in = pc < HP, live = in && j < a.d;
+      const int c = h * a.d + j;
+      f32x4 q = live ? load4<float>(a.q + (size_t)m * a.ldq + c) : z;
+      f32x4 k = live ? load4<float>(a.k + (size_t)m * a.ldk + c) : z;
+      const f32x4 v = live ? load4<float>(a.v + (size_t)m * a.ldv + c) : z;
+      if constexpr (NORM) {
+        const f32x4 s = live ? load4<float>(a.sqk + c) * a.c_q : z;
+        const float sq = group_sum<32>(dot4(q, q)), sk = group_sum<32>(dot4(k, k));
+        const float rq = 1.0f / sqrtf(sq), rk = 1.0f / sqrtf(sk);
+        q = live ? q * rq * s : z;   // (the pads are zeros even where a head's norm is 0 or not finite)
+        k = live ? k * rk * s : z;
+        if (in && j == 0) {
+          a.rq[(size_t)m * a.H + h] = rq;
+          a.rk[(size_t)m * a.H + h] = rk;
+        }
+      }
+      if (in) {
+        const size_t dst = (((size_t)b * a.H + h) * a.T + t) * PAD_D + j;
+        store4<T>(reinterpret_cast<T*>(a.qh) + dst, q);
+        store4<T>(reinterpret_cast<T*>(a.kh) + dst, k);
+        store4<T>(reinterpret_cast<T*>(a.vh) + dst, v);
+      }
+    }
+  }
+}
+
+// heads_pad_bwd_kernel: qknorm_bwd_kernel (NORM; same formulas) / merge_heads_kernel (!NORM) from the first d columns of
+// zero-padded dqh/dkh/dvh (the pad columns are never read).  The d(sqk*c_q) partials of a wave accumulate in its own LDS
+// row of C floats (dynamic LDS: ROW_WAVES * C floats with NORM, none without) in compact channel order.
+template <typename T, bool NORM>
+__global__ __launch_bounds__(256) void heads_pad_bwd_kernel(QkBwdArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float pad_red[];
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int C = a.H * a.d, M = a.B * a.T, HP = a.H * PAD_D;
+  const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+  float* red = pad_red + wid * C;
+  if constexpr (NORM) {
+    for (int c = threadIdx.x; c < ROW_WAVES * C; c += 256) pad_red[c] = 0.f;
+    __syncthreads();
+  }
+  for (int m = blockIdx.x * ROW_WAVES + wid; m < M; m += gridDim.x * ROW_WAVES) {
+    const int b = m / a.T, t = m % a.T;
+    for (int p0 = 0; p0 < HP; p0 += 256) {
+      const int pc = p0 + lane * 4;
+      const int h = pc / PAD_D, j = pc % PAD_D;
+      const bool live = pc < HP && j < a.d;
+      const int c = h * a.d + j;
+      const size_t src = (((size_t)b * a.H + h) * a.T + t) * PAD_D + j;
+      const f32x4 gq = live ? load4<T>(reinterpret_cast<const T*>(a.dqh) + src) : z;
+      const f32x4 gk = live ? load4<T>(reinterpret_cast<const T*>(a.dkh) + src) : z;
+      if constexpr (!NORM) {
+        if (live) {
+          store4<T>(reinterpret_cast<T*>(a.dq) + (size_t)m * a.ldq + c, gq);
+          store4<T>(reinterpret_cast<T*>(a.dk) + (size_t)m * a.ldk + c, gk);
+          store4<T>(reinterpret_cast<T*>(a.dv) + (size_t)m * a.ldv + c, load4<T>(reinterpret_cast<const T*>(a.dvh) + src));
+        }
+      } else {
+        const f32x4 s = live ? load4<float>(a.sqk + c) * a.c_q : z;
+        f32x4 sinv;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) sinv[e] = s[e] != 0.f ? 1.0f / s[e] : 0.f;
+        const f32x4 nq = live ? load4<T>(reinterpret_cast<const T*>(a.qh) + src) * sinv : z;   // unit vector
+        const f32x4 nk = live ? load4<T>(reinterpret_cast<const T*>(a.kh) + src) * sinv : z;
+        const f32x4 sgq = gq * s, sgk = gk * s;
+        const float dq_ = group_sum<32>(dot4(sgq, nq)), dk_ = group_sum<32>(dot4(sgk, nk));
+        if (live) {
+          f32x4* r = reinterpret_cast<f32x4*>(red + c);   // this lane alone owns columns c..c+3 of the wave's row
+          *r = *r + (gq * nq + gk * nk);
+          const float rq = a.rq[(size_t)m * a.H + h], rk = a.rk[(size_t)m * a.H + h];
+          store4<T>(reinterpret_cast<T*>(a.dq) + (size_t)m * a.ldq + c, (sgq - nq * dq_) * rq);
+          store4<T>(reinterpret_cast<T*>(a.dk) + (size_t)m * a.ldk + c, (sgk - nk * dk_) * rk);
+          store4<T>(reinterpret_cast<T*>(a.dv) + (size_t)m * a.ldv + c, load4<T>(reinterpret_cast<const T*>(a.dvh) + src));
+        }
+      }
+    }
+  }
+  if constexpr (NORM) {
+    __syncthreads();
+    for (int c = threadIdx.x; c < C; c += 256) {
+      float t = 0.f;
+#pragma unroll
+      for (int w = 0; w < ROW_WAVES; ++w) t += pad_red[w * C + c];
+      a.part[(size_t)blockIdx.x * C + c] = t;
+    }
+  }
+}
+
+// pad_cols_kernel: dst [M, H*PAD_D] = src [M, H*d] with zero pads (dO, and O rebuilt for the dQ kernel's delta);
+// unpad_cols_kernel: dst [M, H*d] = the first d columns of every head of src [M, H*PAD_D] (O for the output projection).
+// One thread per group of 4 destination elements.
+template <typename T>
+__global__ __launch_bounds__(256) void pad_cols_kernel(const T* src, T* dst, int M, int H, int d) {
+  const size_t G = (size_t)H * (PAD_D / 4), total = (size_t)M * G;
+  for (size_t g = (size_t)blockIdx.x * 256 + threadIdx.x; g < total; g += (size_t)gridDim.x * 256) {
+    const size_t m = g / G;
+    const int pc = (int)(g % G) * 4, h = pc / PAD_D, j = pc % PAD_D;
+    const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+    store4<T>(dst + g * 4, j < d ? load4<T>(src + m * ((size_t)H * d) + h * d + j) : z);
+  }
+}
+template <typename T>
+__global__ __launch_bounds__(256) void unpad_cols_kernel(const T* src, T* dst, int M, int H, int d) {
+  const size_t G = (size_t)H * d / 4, total = (size_t)M * G;
+  for (size_t g = (size_t)blockIdx.x * 256 + threadIdx.x; g < total; g += (size_t)gridDim.x * 256) {
+    const size_t m = g / G;
+    const int c = (int)(g % G) * 4, h = c / d, j = c % d;
+    store4<T>(dst + g * 4, load4<T>(src + m * ((size_t)H * PAD_D) + h * PAD_D + j));
+  }
+}
+
 // ------------------------------------------------------------------------------ SwiGLU
 // thread owns 4 consecutive output columns j..j+3 (inside one 16-group), loops over a row range.
 template <typename TI, typename T>   // TI: type of the pre-activations read, T: type of the gated output
@@ -1224,6 +1375,91 @@ extern "C" int nvit_qknorm_bwd(int dt, const void* dqh, const void* dkh, const v
   });
   launch(kernel, dim3(nblk), dim3(256), 0, s, a);
   NVIT_CHECK_LAUNCH("qknorm_bwd");
+  return NVIT_OK;
+}
+
+// ---- zero-padded heads (head dims that run on the dp = 128 attention kernels) ----
+static bool pad_dims_ok(int H, int d, int dp) {
+  return dp == PAD_D && d > 0 && d < dp && d % 8 == 0 && H > 0 && H * d <= 2048;
+}
+
+extern "C" int nvit_heads_pad_fwd(int dt, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
+                                  const float* sqk, float c_q, void* qh, void* kh, void* vh, float* rq, float* rk,
+                                  float* sqk_pad, int B, int T, int H, int d, int dp, void* stream) {
+  const int C = H * d;
+  NVIT_REQUIRE(pad_dims_ok(H, d, dp), "heads_pad_fwd: needs dp = 128, head dim %d a multiple of 8 below dp, H*d <= 2048", d);
+  NVIT_REQUIRE(B > 0 && T > 0 && ldq % 4 == 0 && ldk % 4 == 0 && ldv % 4 == 0 && ldq >= C && ldk >= C && ldv >= C,
+               "heads_pad_fwd: bad shape/ld");
+  NVIT_REQUIRE(dt == NVIT_F32 || dt == NVIT_BF16_F32IN, "heads_pad_fwd: dt %d (fp32 projections in: F32 or BF16_F32IN)", dt);
+  NVIT_REQUIRE(q && k && v && qh && kh && vh && (!sqk || (rq && rk)), "heads_pad_fwd: missing pointer");
+  PadSplitArgs a{q, k, v, ldq, ldk, ldv, sqk, c_q, qh, kh, vh, rq, rk, sqk_pad, B, T, H, d};
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope ps(NVIT_KID_ROWOPS, 0.0, (double)B * T * 3.0 * (C * 4.0 + H * dp * (dt == NVIT_F32 ? 4.0 : 2.0)), s);
+  const auto kernel = with_bool(sqk != nullptr, [&](auto norm) {
+    return with_elem(dt, [&](auto to) { return &heads_pad_fwd_kernel<tag_t<decltype(to)>, norm>; });
+  });
+  launch(kernel, dim3(row_grid(B * T)), dim3(256), 0, s, a);
+  NVIT_CHECK_LAUNCH("heads_pad_fwd");
+  return NVIT_OK;
+}
+
+extern "C" int nvit_heads_pad_bwd(int dt, const void* dqh, const void* dkh, const void* dvh, const void* qh,
+                                  const void* kh, const float* rq, const float* rk, const float* sqk, float c_q,
+                                  void* dq, int ldq, void* dk, int ldk, void* dv, int ldv, float* part_dsqk, int nblk,
+                                  int B, int T, int H, int d, int dp, void* stream) {
+  const int C = H * d;
+  NVIT_REQUIRE(pad_dims_ok(H, d, dp), "heads_pad_bwd: needs dp = 128, head dim %d a multiple of 8 below dp, H*d <= 2048", d);
+  NVIT_REQUIRE(B > 0 && T > 0 && ldq % 4 == 0 && ldk % 4 == 0 && ldv % 4 == 0 && ldq >= C && ldk >= C && ldv >= C,
+               "heads_pad_bwd: bad shape/ld");
+  NVIT_REQUIRE(dt == NVIT_F32 || dt == NVIT_BF16, "heads_pad_bwd: bad dt %d", dt);
+  NVIT_REQUIRE(dqh && dkh && dvh && dq && dk && dv, "heads_pad_bwd: missing pointer");
+  QkBwdArgs a{dqh, dkh, dvh, qh, kh, rq, rk, sqk, c_q, dq, dk, dv, ldq, ldk, ldv, part_dsqk, B, T, H, d};
+  hipStream_t s = (hipStream_t)stream;
+  const double eb = dt == NVIT_F32 ? 4.0 : 2.0;
+  if (!sqk) {   // the head merge alone (qh, kh, rq, rk, part_dsqk and nblk are not used)
+    ProfScope ps(NVIT_KID_ROWOPS, 0.0, (double)B * T * C * 6.0 * eb, s);
+    const auto kernel = with_elem(dt, [&](auto t) { return &heads_pad_bwd_kernel<tag_t<decltype(t)>, false>; });
+    launch(kernel, dim3(row_grid(B * T)), dim3(256), 0, s, a);
+    NVIT_CHECK_LAUNCH("heads_pad_bwd");
+    return NVIT_OK;
+  }
+  NVIT_REQUIRE(qh && kh && rq && rk && part_dsqk, "heads_pad_bwd: missing pointer");
+  NVIT_REQUIRE(nblk > 0 && nblk <= 4096, "heads_pad_bwd: nblk out of range");
+  ProfScope ps(NVIT_KID_ROWOPS, 0.0, (double)B * T * C * 8.0 * eb, s);
+  const auto kernel = with_elem(dt, [&](auto t) { return &heads_pad_bwd_kernel<tag_t<decltype(t)>, true>; });
+  launch(kernel, dim3(nblk), dim3(256), (size_t)ROW_WAVES * C * sizeof(float), s, a);
+  NVIT_CHECK_LAUNCH("heads_pad_bwd");
+  return NVIT_OK;
+}
+
+static int pad_copy_grid(size_t groups) {
+  const size_t blocks = (groups + 255) / 256;
+  return (int)(blocks > 8192 ? 8192 : blocks);
+}
+
+extern "C" int nvit_pad_cols(int dt, const void* src, void* dst, int M, int H, int d, int dp, void* stream) {
+  NVIT_REQUIRE(pad_dims_ok(H, d, dp) && M > 0 && src && dst, "pad_cols: needs dp = 128, head dim %d a multiple of 8 below dp, H*d <= 2048", d);
+  NVIT_REQUIRE(dt == NVIT_F32 || dt == NVIT_BF16, "pad_cols: bad dt %d", dt);
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope ps(NVIT_KID_ROWOPS, 0.0, (double)M * H * (d + dp) * (dt == NVIT_F32 ? 4.0 : 2.0), s);
+  with_elem(dt, [&](auto t) {
+    using T = tag_t<decltype(t)>;
+    launch(pad_cols_kernel<T>, dim3(pad_copy_grid((size_t)M * H * (dp / 4))), dim3(256), 0, s, (const T*)src, (T*)dst, M, H, d);
+  });
+  NVIT_CHECK_LAUNCH("pad_cols");
+  return NVIT_OK;
+}
+
+extern "C" int nvit_unpad_cols(int dt, const void* src, void* dst, int M, int H, int d, int dp, void* stream) {
+  NVIT_REQUIRE(pad_dims_ok(H, d, dp) && M > 0 && src && dst, "unpad_cols: needs dp = 128, head dim %d a multiple of 8 below dp, H*d <= 2048", d);
+  NVIT_REQUIRE(dt == NVIT_F32 || dt == NVIT_BF16, "unpad_cols: bad dt %d", dt);
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope ps(NVIT_KID_ROWOPS, 0.0, (double)M * H * d * 2.0 * (dt == NVIT_F32 ? 4.0 : 2.0), s);
+  with_elem(dt, [&](auto t) {
+    using T = tag_t<decltype(t)>;
+    launch(unpad_cols_kernel<T>, dim3(pad_copy_grid((size_t)M * H * d / 4)), dim3(256), 0, s, (const T*)src, (T*)dst, M, H, d);
+  });
+  NVIT_CHECK_LAUNCH("unpad_cols");
   return NVIT_OK;
 }
 

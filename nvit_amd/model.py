@@ -37,6 +37,8 @@ from .kohonen import CosConsistencyFn, HuberFn, KohonenMap, MapSmoothnessFn
 
 Tensor = torch.Tensor
 HEAD_DIMS = (32, 64, 128)   # attention head dims n_embd // n_head the kernels cover
+# head dims that run on the 128-wide kernels with head tensors whose columns d..127 are stored zeros (_attn_fwd, "padded")
+PADDED_HEAD_DIMS = (72, 80, 88, 104)
 
 
 def _dt_from_precision(p: str) -> int:
@@ -301,7 +303,7 @@ def _attn_fwd(rt: _Runtime, impl: int, srcs, sqk: Optional[Tensor], c_q: float, 
               lean: bool = False):
     """The attention of every block function, from its q/k/v projection sources to O [M, C] (the output projection's A
     operand).  srcs: ((A, shadow prefix, parts), ...), one projection GEMM each, their output columns q | k | v in
-    order.  sqk None (c_q 0.0): plain-ViT heads, else the nViT normalise + sqk scale.  One of three routes:
+    order.  sqk None (c_q 0.0): plain-ViT heads, else the nViT normalise + sqk scale.  One of four routes:
       heads  flash_attn=True: the reference's flash_attn_func reads its [B,H,T,d] arguments as [batch, seqlen, nheads,
              headdim], so the softmax runs over the H heads of each token of the fp32 token-major
              projections;
@@ -309,7 +311,11 @@ def _attn_fwd(rt: _Runtime, impl: int, srcs, sqk: Optional[Tensor], c_q: float, 
              bias (if any), the normalise (nViT) and the head split in the projection GEMM's epilogue, q pre-scaled so
              that the attention kernels' exponent needs no multiply;
       split  otherwise (small problems: 128x128 GEMM kernel): the projections leave the GEMM in fp32 and are normalised
-             from the unrounded values, like the fused epilogue (one rounding, at the head tensors).
+             from the unrounded values, like the fused epilogue (one rounding, at the head tensors);
+      padded d in PADDED_HEAD_DIMS: the split route into head tensors [B,H,T,128] whose columns d..127 are stored zeros
+             (heads_pad_fwd, which also pads sqk for the score bound): the attention kernels run at head dim 128 with
+             the scale of the real d, and O [M, H*128] is compacted to [M, C].  Zero columns change no score, no output
+             column < d and no gradient column < d.
     -> o, lse, att (route, impl, q pre-scale, scale) for _attn_bwd, and the tensors it reads: the fp32 projections
     (heads) or qh, kh, vh, rq, rk.
     lean (a forward no backward follows): the same launches - no attention kernel takes a NULL lse, rq or rk, so those
@@ -318,6 +324,16 @@ def _attn_fwd(rt: _Runtime, impl: int, srcs, sqk: Optional[Tensor], c_q: float, 
     B, T, C, H, d, M = dims
     dt, sh = rt.dt, rt.sh
     heads = rt.model.config.flash_attn
+    if d in PADDED_HEAD_DIMS:   # (never with flash_attn: refused at construction)
+        projs = [ops.gemm_nt(A, sh[w + ".W"], M, n * C, C, out_dtype=torch.float32, bias=sh.get(w + ".b"))
+                 for A, w, n in srcs]
+        q, ldq, k, v, ldkv = _qkv_cols(projs, C)
+        qh, kh, vh, rq, rk, sqk_p = ops.heads_pad_fwd(dt if dt == F32 else BF16_F32IN, q, ldq, k, ldkv, v, ldkv, sqk,
+                                                      c_q, B, T, H, d)
+        del projs, q, k, v
+        o_p, lse = ops.attn_fwd(dt, impl, qh, kh, vh, scale, sqk_p, c_q)
+        o = ops.unpad_cols(o_p, M, H, d)
+        return o, lse, ("padded", impl, 1.0, scale), (() if lean else (qh, kh, vh, rq, rk))
     if not heads and impl == 1 and d == 64 and C % 256 == 0 and ops.fusable(dt, M, srcs[0][2] * C, C):
         route = "fused"
         # the softmax scale (nViT: sqrt(d) on unit q, k) times log2(e); with sqk absent the running-maximum kernel runs
@@ -360,6 +376,15 @@ def _attn_bwd(rt: _Runtime, att, saved, do: Tensor, o: Tensor, lse: Tensor, grad
         return ops.attn_heads_bwd(dt, do, q, ldq, k, v, ldkv, sqk, c_q, scale, lse, dq, lddq, dk, dv, lddkv, M, H,
                                   d), None
     qh, kh, vh, rq, rk = saved
+    if route == "padded":
+        # dO and O zero-padded to the head tensors' width (the dQ kernel's delta = rowsum(dO*O) runs over all 128
+        # columns; the padded O is rebuilt from the compact one, not kept from the forward), attn_bwd at 128, then the
+        # merge, which reads the first d columns of each gradient only
+        do_p, o_p = ops.pad_cols(do, M, H, d), ops.pad_cols(o, M, H, d)
+        dqh, dkh, dvh = ops.attn_bwd(dt, impl, do_p, qh, kh, vh, o_p, lse, scale)
+        del do_p, o_p
+        return ops.heads_pad_bwd(dt, dqh, dkh, dvh, qh, kh, rq, rk, sqk, c_q, dq, lddq, dk, lddkv, dv, lddkv, B, T, H,
+                                 d), None
     # attention backward with the q/k-normalise backward (nViT) fused into its epilogues, dq/dk/dv stored token-major:
     # nViT after either forward route (the split one leaves q unscaled, qpre 1); plain heads after the fused one only
     fused_bwd = (dt != F32 and d == 64) if sqk is not None else route == "fused"
@@ -1080,8 +1105,12 @@ class ViT(nn.Module):
             raise ValueError("n_embd must be a multiple of 64 and divisible by n_head")
         if config.n_embd > MAX_EMBD:
             raise ValueError(f"n_embd must be at most {MAX_EMBD}, the widest row the row kernels hold (got {config.n_embd})")
-        if (config.n_embd // config.n_head) not in HEAD_DIMS:
-            raise ValueError(f"head dim must be one of {HEAD_DIMS} (got {config.n_embd // config.n_head})")
+        if (config.n_embd // config.n_head) not in HEAD_DIMS + PADDED_HEAD_DIMS:
+            raise ValueError(f"head dim must be one of {HEAD_DIMS} or, zero-padded to 128, one of {PADDED_HEAD_DIMS} "
+                             f"(got {config.n_embd // config.n_head})")
+        if config.flash_attn and (config.n_embd // config.n_head) in PADDED_HEAD_DIMS:
+            raise ValueError(f"flash_attn=True (attention over the heads of each token) is built for head dims {HEAD_DIMS}; "
+                             f"head dim {config.n_embd // config.n_head} runs with flash_attn=False only")
         if config.flash_attn and config.n_head > ATTN_HEADS_MAX_H:
             raise ValueError(f"flash_attn=True (attention over the heads of each token) is built for at most "
                              f"{ATTN_HEADS_MAX_H} heads (got n_head={config.n_head})")
@@ -1155,11 +1184,12 @@ class ViT(nn.Module):
         return self
 
     def _attn_impl(self) -> int:
-        """1: the MFMA flash kernels (bf16 mode, every supported head dim: 32, 64, 128); 0: the scalar-FMA kernels (fp32
-        mode).  The fused q/k-normalise paths (GEMM epilogue, attention backward) are head dim 64 only; the other head dims
-        take the unfused route (fp32 projection, qknorm_fwd, attn_fwd bounded, attn_bwd, qknorm_bwd)."""
+        """1: the MFMA flash kernels (bf16 mode, every supported head dim: 32, 64, 128, and the PADDED_HEAD_DIMS, which
+        run them at 128); 0: the scalar-FMA kernels (fp32 mode).  The fused q/k-normalise paths (GEMM epilogue, attention
+        backward) are head dim 64 only; the other head dims take the unfused route (fp32 projection, qknorm_fwd, attn_fwd
+        bounded, attn_bwd, qknorm_bwd; the padded dims its zero-padding twins)."""
         d = self.config.n_embd // self.config.n_head
-        return 1 if (self.precision == "bf16" and d in HEAD_DIMS) else 0
+        return 1 if (self.precision == "bf16" and d in HEAD_DIMS + PADDED_HEAD_DIMS) else 0
 
     def _prepare(self, device) -> None:
         if device.type != "cuda":

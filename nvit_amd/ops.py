@@ -437,6 +437,79 @@ def qknorm_bwd(dt: int, dqh, dkh, dvh, qh, kh, rq, rk, sqk, c_q: float, dq: Tens
     return part
 
 
+PAD_HEAD_DIM = 128   # dp: the attention head dim the zero-padded head tensors run at (include/nvit_hip.h)
+
+
+def _pad_out(out, shape, dtype, device, name: str) -> Tensor:
+    """An `out=` buffer of the padded-head ops (tests hand in pre-filled ones), checked, or a fresh torch.empty."""
+    if out is None:
+        return torch.empty(shape, device=device, dtype=dtype)
+    if tuple(out.shape) != tuple(shape) or out.dtype != dtype or out.device != device or not out.is_contiguous():
+        raise ValueError(f"{name}: out must be a contiguous {dtype} tensor of shape {tuple(shape)} on {device}, got "
+                         f"{out.dtype} {tuple(out.shape)} on {out.device}")
+    return out
+
+
+def heads_pad_fwd(dt: int, q: Tensor, ldq: int, k: Tensor, ldk: int, v: Tensor, ldv: int, sqk: Optional[Tensor],
+                  c_q: float, B: int, T: int, H: int, d: int, *, out=None):
+    """qknorm_fwd from fp32 projections (dt F32 or BF16_F32IN) into zero-padded head tensors [B,H,T,PAD_HEAD_DIM]: every
+    pad column is stored as zero on every call.  -> qh, kh, vh, rq, rk, sqk_pad ([H*PAD_HEAD_DIM], sqk with zero pads);
+    sqk None: the split alone, rq = rk = sqk_pad = None.  out: optional (qh, kh, vh, rq, rk, sqk_pad) buffers."""
+    _chk_dev(q, k, v, sqk)
+    if q.dtype != torch.float32 or k.dtype != torch.float32 or v.dtype != torch.float32:
+        raise TypeError("heads_pad_fwd: the projections are fp32")
+    dev, dp = q.device, PAD_HEAD_DIM
+    td = tdtype(BF16 if dt == _lib.BF16_F32IN else dt)
+    o = tuple(out) if out is not None else (None,) * 6
+    qh = _pad_out(o[0], (B, H, T, dp), td, dev, "heads_pad_fwd")
+    kh = _pad_out(o[1], (B, H, T, dp), td, dev, "heads_pad_fwd")
+    vh = _pad_out(o[2], (B, H, T, dp), td, dev, "heads_pad_fwd")
+    if sqk is not None:
+        rq = _pad_out(o[3], (B * T, H), torch.float32, dev, "heads_pad_fwd")
+        rk = _pad_out(o[4], (B * T, H), torch.float32, dev, "heads_pad_fwd")
+        sqk_pad = _pad_out(o[5], (H * dp,), torch.float32, dev, "heads_pad_fwd")
+    else:
+        rq = rk = sqk_pad = None
+    check(_lib.load().nvit_heads_pad_fwd(dt, _p(q), ldq, _p(k), ldk, _p(v), ldv, _p(sqk), c_q, _p(qh), _p(kh), _p(vh),
+                                         _p(rq), _p(rk), _p(sqk_pad), B, T, H, d, dp, _s()), "nvit_heads_pad_fwd")
+    return qh, kh, vh, rq, rk, sqk_pad
+
+
+def heads_pad_bwd(dt: int, dqh, dkh, dvh, qh, kh, rq, rk, sqk, c_q: float, dq: Tensor, ldq: int, dk: Tensor, ldk: int,
+                  dv: Tensor, ldv: int, B: int, T: int, H: int, d: int, *, nblk: Optional[int] = None,
+                  out: Optional[Tensor] = None) -> Optional[Tensor]:
+    """qknorm_bwd from the first d columns of zero-padded dqh, dkh, dvh [B,H,T,PAD_HEAD_DIM] into token-major dq/dk/dv
+    (type dt) -> the d(sqk*c_q) partials [nblk, H*d] in compact channel order (out: optional buffer for them); sqk None:
+    the head merge alone, returns None."""
+    _chk_dev(dqh, dkh, dvh, dq, dk, dv)
+    nblk = _part_blocks(nblk, min(PART_BLOCKS, math.ceil(B * T / 4)), "heads_pad_bwd")
+    part = _pad_out(out, (nblk, H * d), torch.float32, dq.device, "heads_pad_bwd") if sqk is not None else None
+    check(_lib.load().nvit_heads_pad_bwd(dt, _p(dqh), _p(dkh), _p(dvh), _p(qh), _p(kh), _p(rq), _p(rk), _p(sqk), c_q,
+                                         _p(dq), ldq, _p(dk), ldk, _p(dv), ldv, _p(part), nblk, B, T, H, d,
+                                         PAD_HEAD_DIM, _s()), "nvit_heads_pad_bwd")
+    return part
+
+
+def pad_cols(src: Tensor, M: int, H: int, d: int, *, out: Optional[Tensor] = None) -> Tensor:
+    """[M, H*d] -> [M, H*PAD_HEAD_DIM] with zero pads (dO, and O rebuilt for the attention backward)."""
+    _chk_dev(src)
+    if tuple(src.shape) != (M, H * d) or not src.is_contiguous():
+        raise ValueError(f"pad_cols: src must be a contiguous [{M}, {H * d}] tensor, got {tuple(src.shape)}")
+    dst = _pad_out(out, (M, H * PAD_HEAD_DIM), src.dtype, src.device, "pad_cols")
+    check(_lib.load().nvit_pad_cols(dt_of(src), _p(src), _p(dst), M, H, d, PAD_HEAD_DIM, _s()), "nvit_pad_cols")
+    return dst
+
+
+def unpad_cols(src: Tensor, M: int, H: int, d: int, *, out: Optional[Tensor] = None) -> Tensor:
+    """[M, H*PAD_HEAD_DIM] -> [M, H*d]: the first d columns of every head (O for the output projection)."""
+    _chk_dev(src)
+    if tuple(src.shape) != (M, H * PAD_HEAD_DIM) or not src.is_contiguous():
+        raise ValueError(f"unpad_cols: src must be a contiguous [{M}, {H * PAD_HEAD_DIM}] tensor, got {tuple(src.shape)}")
+    dst = _pad_out(out, (M, H * d), src.dtype, src.device, "unpad_cols")
+    check(_lib.load().nvit_unpad_cols(dt_of(src), _p(src), _p(dst), M, H, d, PAD_HEAD_DIM, _s()), "nvit_unpad_cols")
+    return dst
+
+
 def swiglu_fwd(dt: int, uv: Tensor, suv: Optional[Tensor], gscale: float, M: int, F: int) -> Tensor:
     """dt = BF16_F32IN: fp32 pre-activations in, bf16 gated output."""
     x = torch.empty((M, F), device=uv.device, dtype=tdtype(BF16 if dt == _lib.BF16_F32IN else dt))
