@@ -119,6 +119,20 @@ int nvit_grad_sqnorm(const int64_t* table, int n, int total_chunks, float* parti
 int nvit_adamw_renorm(const int64_t* table, int n, int total_items, int max_slab_rows, float beta1, float beta2,
                       float eps, double bias_correction1, double bias_correction2, const float* partial, int npart,
                       float max_norm, float* gnorm_out, const float* hyper, void* stream);
+/* The same step, left out when the gradients are not finite (GradScaler.step of the reference, train.py:930-942).
+ * Order: nvit_grad_sqnorm, nvit_adamw_tick_guarded, nvit_adamw_renorm_guarded.
+ * skip_state: 2 floats on the device, zeroed by the caller once: {the last step was skipped (0 / 1), steps skipped}.
+ * nvit_adamw_tick_guarded: one workgroup sums partial[npart] and decides for the whole step.  Finite sum: hyper[0..2]
+ *        advance as in nvit_adamw_tick and skip_state[0] = 0.  Inf or NaN (also a squared norm that overflows fp32):
+ *        hyper is left alone, skip_state[0] = 1, skip_state[1] += 1.
+ * nvit_adamw_renorm_guarded: nvit_adamw_renorm with partial, gnorm_out and hyper required; gnorm_out[0] is always
+ *        stored (max_norm = 0 switches the clipping off, not the norm); then every workgroup reads skip_state[0] and
+ *        returns when it is set, so p, m and v stay bit-identical.  An applied step gives the bits of nvit_adamw_renorm. */
+int nvit_adamw_tick_guarded(float* hyper, double beta1, double beta2, const float* partial, int npart,
+                            float* skip_state, void* stream);
+int nvit_adamw_renorm_guarded(const int64_t* table, int n, int total_items, int max_slab_rows, float beta1, float beta2,
+                              float eps, const float* partial, int npart, float max_norm, float* gnorm_out,
+                              const float* hyper, const float* skip_state, void* stream);
 
 /* ---- GEMMs ------------------------------------------------------------------------
  * nvit_gemm_nt: C[M,N] = A[M,K] * B[N,K]^T  (nn.Linear: model.py:99-101,130,148,155,...)

@@ -11,6 +11,9 @@
 //                        that normalize_matrices touches, the row / column L2 normalisation of the UPDATED weights
 //                        before they are written - each of p, g, m, v is read once and p, m, v written once
 //                        (28 B per parameter; the unfused sequence moves ~52 B and needs ~20 launches).
+// With skip_nonfinite (the reference's GradScaler, train.py:930-942, leaves out the step of a batch whose gradients hold
+// inf or NaN) the order is grad_sqnorm, adamw_tick_guarded_kernel, adamw_renorm_kernel<const float*>: the tick sums the
+// partials once, decides, and leaves a flag; the update returns before its item loop when the flag is set.
 // Item kinds: -1 = plain chunk of 8192 elements; 1 = 16 rows, one wave per row (row norm, dim=1; cols <= 2048);
 //             0 = slab of all rows x 32 columns kept in LDS (column norm, dim=0), all rows x 16 columns for matrices
 //                 of more than 1152 rows (rows <= 2048): the slab and its partial sums must fit the 160 KiB of a CU.
@@ -191,9 +194,17 @@ __device__ __forceinline__ void adamw_col_item(const OptRow& r, int local, int t
 
 // 1024 threads = 16 waves, one workgroup per CU (the column slab takes most of the LDS), so the streaming items
 // still have 16 waves x 4 tensors of loads in flight per CU.
+// One template, two instantiations: <> is the step as it always was (same parameters, same body), <const float*> takes
+// the skip state as a trailing parameter (skip_nonfinite).  There, after the norm, every workgroup reads the one flag
+// that nvit_adamw_tick_guarded wrote and returns before the item loop when it is set.  The flag is a single word
+// written by an earlier launch, so the decision is the same in every workgroup and thread (no workgroup updates while
+// another returns), and it is taken after block_sum's barriers, with none pending.  The workgroup's own sum must NOT
+// decide: the clip factor is what it is for, and a sum near FLT_MAX is finite in one order and infinite in another.
+template <class... Skip>
 __global__ __launch_bounds__(1024) void adamw_renorm_kernel(const int64_t* table, int n, int total_items,
                                                             const float* partial, AdamArgs a, float* gnorm_out,
-                                                            const float* hyper) {
+                                                            const float* hyper, Skip... skip_state) {
+  static_assert(sizeof...(Skip) <= 1, "at most the skip state");
   // dynamic LDS: the column slab and its partial sums (up to all 160 KiB of the CU, so nothing is declared statically);
   // its first 64 bytes serve the clip-factor sum before the item loop
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -216,6 +227,10 @@ __global__ __launch_bounds__(1024) void adamw_renorm_kernel(const int64_t* table
       clip = c < 1.0f ? c : 1.0f;
     }
     if (gnorm_out && blockIdx.x == 0 && tid == 0) gnorm_out[0] = nrm;
+  }
+  if constexpr (sizeof...(Skip) == 1) {
+    const float* const flag[] = {skip_state...};
+    if (flag[0][0] != 0.f) return;  // grid-uniform: p, m, v stay bit-identical, gnorm_out holds the inf / NaN norm
   }
   for (int item = blockIdx.x; item < total_items; item += gridDim.x) {
     const int mi = opt_find(table, n, 7, item);
@@ -310,11 +325,34 @@ __global__ __launch_bounds__(1024) void adamw_renorm_kernel(const int64_t* table
 }
 
 // hyper[0] = step count t (after the increment), hyper[1] = 1/(1-b1^t), hyper[2] = 1/sqrt(1-b2^t)
-__global__ void adamw_tick_kernel(float* hyper, double b1, double b2) {
+__device__ __forceinline__ void adamw_tick(float* hyper, double b1, double b2) {
   const double t = (double)hyper[0] + 1.0;
   hyper[0] = (float)t;
   hyper[1] = (float)(1.0 / (1.0 - pow(b1, t)));
   hyper[2] = (float)(1.0 / sqrt(1.0 - pow(b2, t)));
+}
+
+__global__ void adamw_tick_kernel(float* hyper, double b1, double b2) { adamw_tick(hyper, b1, b2); }
+
+// One workgroup: sums the norm partials (in the order adamw_renorm_kernel sums them, so the norm that kernel reports is
+// non-finite exactly when the step is skipped) and takes the decision of the whole step once.  Finite: the tick, and
+// skip_state[0] = 0.  Inf or NaN (a gradient holds one, or the squared norm overflows fp32): hyper stays as it is,
+// skip_state[0] = 1 and skip_state[1], the count of skipped steps, goes up by one.
+__global__ __launch_bounds__(1024) void adamw_tick_guarded_kernel(float* hyper, double b1, double b2,
+                                                                  const float* partial, int npart, float* skip_state) {
+  __shared__ float red[16];
+  float s = 0.f;
+  for (int i = threadIdx.x; i < npart; i += 1024) s += partial[i];
+  s = block_sum<16>(s, red);
+  if (threadIdx.x != 0) return;
+  const bool finite = (__float_as_uint(s) & 0x7f800000u) != 0x7f800000u;  // exponent all ones: inf or NaN
+  if (finite) {
+    adamw_tick(hyper, b1, b2);
+    skip_state[0] = 0.f;
+  } else {
+    skip_state[0] = 1.f;
+    skip_state[1] += 1.f;
+  }
 }
 
 }  // namespace
@@ -338,10 +376,11 @@ extern "C" int nvit_grad_sqnorm(const int64_t* table, int n, int total_chunks, f
   return NVIT_OK;
 }
 
-extern "C" int nvit_adamw_renorm(const int64_t* table, int n, int total_items, int max_slab_rows, float beta1,
-                                 float beta2, float eps, double bias_correction1, double bias_correction2,
-                                 const float* partial, int npart, float max_norm, float* gnorm_out,
-                                 const float* hyper, void* stream) {
+// skip_state == NULL: nvit_adamw_renorm; otherwise the guarded kernel (nvit_adamw_renorm_guarded)
+static int adamw_renorm_launch(const int64_t* table, int n, int total_items, int max_slab_rows, float beta1,
+                               float beta2, float eps, double bias_correction1, double bias_correction2,
+                               const float* partial, int npart, float max_norm, float* gnorm_out,
+                               const float* hyper, const float* skip_state, void* stream) {
   NVIT_REQUIRE(table && n > 0 && total_items > 0, "adamw_renorm: empty table");
   NVIT_REQUIRE(max_slab_rows >= 0 && max_slab_rows <= OPT_TALL_ROWS,
                "adamw_renorm: column-normalised matrix with %d rows exceeds the LDS slab (%d)", max_slab_rows,
@@ -368,15 +407,49 @@ extern "C" int nvit_adamw_renorm(const int64_t* table, int n, int total_items, i
   static_assert(16 * OPT_WIDE_COLS <= 1024 * OPT_SLAB_COLS + 4096, "max_slab_rows = 1024 covers 16 parked wide rows");
   const int slab_rows = max_slab_rows > OPT_SLAB_ROWS ? OPT_SLAB_ROWS : max_slab_rows;
   const int lds = slab_rows > 0 ? (slab_rows * OPT_SLAB_COLS + 4096) * 4 : 64;
-  static int lds_set = 0;
-  if (lds > lds_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)adamw_renorm_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  static int lds_set[2] = {0, 0};  // per kernel
+  const int which = skip_state ? 1 : 0;
+  if (lds > lds_set[which]) {
+    const void* fn = skip_state ? (const void*)adamw_renorm_kernel<const float*> : (const void*)adamw_renorm_kernel<>;
+    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (e != hipSuccess) NVIT_FAIL((int)e, "adamw_renorm: cannot raise LDS limit: %s", hipGetErrorString(e));
-    lds_set = lds;
+    lds_set[which] = lds;
   }
   int grid = total_items < 2048 ? total_items : 2048;
   ProfScope ps(NVIT_KID_OPTIM, 0.0, 0.0, s);
-  hipLaunchKernelGGL(adamw_renorm_kernel, dim3(grid), dim3(1024), lds, s, table, n, total_items, partial, a, gnorm_out, hyper);
+  if (skip_state)
+    hipLaunchKernelGGL(adamw_renorm_kernel<const float*>, dim3(grid), dim3(1024), lds, s, table, n, total_items, partial, a,
+                       gnorm_out, hyper, skip_state);
+  else
+    hipLaunchKernelGGL(adamw_renorm_kernel<>, dim3(grid), dim3(1024), lds, s, table, n, total_items, partial, a, gnorm_out, hyper);
   NVIT_CHECK_LAUNCH("adamw_renorm");
   return NVIT_OK;
+}
+
+extern "C" int nvit_adamw_renorm(const int64_t* table, int n, int total_items, int max_slab_rows, float beta1,
+                                 float beta2, float eps, double bias_correction1, double bias_correction2,
+                                 const float* partial, int npart, float max_norm, float* gnorm_out,
+                                 const float* hyper, void* stream) {
+  return adamw_renorm_launch(table, n, total_items, max_slab_rows, beta1, beta2, eps, bias_correction1,
+                             bias_correction2, partial, npart, max_norm, gnorm_out, hyper, nullptr, stream);
+}
+
+extern "C" int nvit_adamw_tick_guarded(float* hyper, double beta1, double beta2, const float* partial, int npart,
+                                       float* skip_state, void* stream) {
+  NVIT_REQUIRE(hyper && beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0, "adamw_tick_guarded: bad arguments");
+  NVIT_REQUIRE(partial && skip_state && npart > 0 && npart <= 4096, "adamw_tick_guarded: bad partials or skip state");
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(adamw_tick_guarded_kernel, dim3(1), dim3(1024), 0, s, hyper, beta1, beta2, partial, npart,
+                     skip_state);
+  NVIT_CHECK_LAUNCH("adamw_tick_guarded");
+  return NVIT_OK;
+}
+
+extern "C" int nvit_adamw_renorm_guarded(const int64_t* table, int n, int total_items, int max_slab_rows, float beta1,
+                                         float beta2, float eps, const float* partial, int npart, float max_norm,
+                                         float* gnorm_out, const float* hyper, const float* skip_state, void* stream) {
+  NVIT_REQUIRE(partial && gnorm_out && hyper && skip_state,
+               "adamw_renorm_guarded: needs the norm partials, gnorm_out, the device step counter and the skip state");
+  return adamw_renorm_launch(table, n, total_items, max_slab_rows, beta1, beta2, eps, 0.0, 0.0, partial, npart, max_norm,
+                             gnorm_out, hyper, skip_state, stream);
 }

@@ -9,7 +9,8 @@ is how a step runs on the MI355X: `step_fused(model, grad_clip)` performs
     (train.py:935-941)                     (train.py:942-944)  (train.py:461-480, 989-990)
 
 in two HIP launches (`nvit_grad_sqnorm`, `nvit_adamw_renorm`) over a device-side parameter table, reading each of
-p, g, m, v once and writing p, m, v once.  Plain `step()` (no clip, no renorm) uses the same kernel, so code that
+p, g, m, v once and writing p, m, v once; with `skip_nonfinite=True` a guarded tick between them decides, on the device,
+whether the step is applied at all (GradScaler.step of the reference, train.py:930-942).  Plain `step()` (no clip, no renorm) uses the same kernel, so code that
 calls `optimizer.step()` followed by `normalize_matrices(model)` gives identical weights.  There is no torch
 fallback: the parameters must live on the HIP device.
 
@@ -56,6 +57,8 @@ class FusedAdamW(torch.optim.AdamW):
         self._staging = None  # pinned host image of the device table
         self._hyper_pin = None   # pinned image of the lr/weight_decay column (eager lr schedules)
         self._hyper_ev = None
+        self._skip_state = None   # device float[2], see skip_state
+        self._guarded = False     # a skip_nonfinite step has run: only the device knows how many steps were applied
 
     # ------------------------------------------------------------------ state
     def _ensure_state(self, p: torch.Tensor) -> Dict:
@@ -171,9 +174,19 @@ class FusedAdamW(torch.optim.AdamW):
 
     # ------------------------------------------------------------------ steps
     @torch.no_grad()
-    def step_fused(self, model=None, grad_clip: float = 0.0) -> Optional[torch.Tensor]:
+    def step_fused(self, model=None, grad_clip: float = 0.0, skip_nonfinite: bool = False) -> Optional[torch.Tensor]:
         """clip (if grad_clip > 0) + AdamW + (if `model` is given) normalize_matrices; returns the pre-clip grad norm
-        as a 1-element device tensor when clipping is on."""
+        as a 1-element device tensor when clipping or skip_nonfinite is on.
+
+        skip_nonfinite=True is what GradScaler.step does for the reference (train.py:930-942): a step whose gradients
+        hold inf or NaN is left out.  Three launches: nvit_grad_sqnorm (always, also with grad_clip == 0), the guarded
+        tick, which sums the norm partials, decides once and writes `skip_state`, and the guarded update, in which every
+        workgroup reads that one flag.  A skipped step leaves every parameter, exp_avg, exp_avg_sq and the step counter
+        bit-identical and returns the inf / NaN norm; an applied step gives the bits of the unguarded step.  Two things to
+        know: gradients whose squared norm overflows fp32 (norm above ~1.8e19) count as non-finite although every
+        element is finite; and the reference re-runs normalize_matrices on the unchanged weights after a skipped step
+        (a change of at most an ulp), while here nothing moves.  Under DataParallel every rank holds the same averaged
+        gradients when this runs, hence takes the same decision."""
         dims: Dict[int, int] = {}
         if model is not None:
             m = model.module if hasattr(model, "module") else model
@@ -195,9 +208,22 @@ class FusedAdamW(torch.optim.AdamW):
                 dev, non_blocking=True)
         # the step counter lives on the device (bias corrections are computed there), so a captured step replays
         # correctly; the host mirror only feeds state_dict()
+        clip = grad_clip is not None and grad_clip > 0.0
+        if skip_nonfinite:
+            skip = self.skip_state
+            self._guarded = True
+            self._t += 1   # as if applied; state_dict() reads the count of applied steps back from the device
+            check(lib.nvit_grad_sqnorm(_p(c["table"]), c["n"], c["chunks"], _p(c["partial"]), _NPART, _s()),
+                  "nvit_grad_sqnorm")
+            check(lib.nvit_adamw_tick_guarded(_p(self._hyper), b1, b2, _p(c["partial"]), _NPART, _p(skip), _s()),
+                  "nvit_adamw_tick_guarded")
+            check(lib.nvit_adamw_renorm_guarded(_p(c["table"]), c["n"], c["items"], c["slab"], b1, b2, eps,
+                                                _p(c["partial"]), _NPART, float(grad_clip) if clip else 0.0,
+                                                _p(c["gnorm"]), _p(self._hyper), _p(skip), _s()),
+                  "nvit_adamw_renorm_guarded")
+            return c["gnorm"]
         check(lib.nvit_adamw_tick(_p(self._hyper), b1, b2, _s()), "nvit_adamw_tick")
         self._t += 1
-        clip = grad_clip is not None and grad_clip > 0.0
         if clip:
             check(lib.nvit_grad_sqnorm(_p(c["table"]), c["n"], c["chunks"], _p(c["partial"]), _NPART, _s()),
                   "nvit_grad_sqnorm")
@@ -207,6 +233,24 @@ class FusedAdamW(torch.optim.AdamW):
                                     _p(self._hyper), _s()),
               "nvit_adamw_renorm")
         return c["gnorm"] if clip else None
+
+    # ------------------------------------------------------------------ skipped steps
+    @property
+    def skip_state(self) -> torch.Tensor:
+        """fp32 device tensor [2]: (the last skip_nonfinite step was skipped: 0 / 1, steps skipped so far).  Written by
+        the guarded tick only; reading it on the host synchronises."""
+        if self._skip_state is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("FusedAdamW: take one skip_nonfinite step (or read skip_state) before capturing one")
+            dev = next(p.device for group in self.param_groups for p in group["params"])
+            if dev.type != "cuda":
+                raise RuntimeError("FusedAdamW: parameters must live on the HIP device")
+            self._skip_state = torch.zeros(2, device=dev, dtype=torch.float32)
+        return self._skip_state
+
+    def skipped_steps(self) -> int:
+        """Steps that skip_nonfinite left out so far (one host synchronisation)."""
+        return 0 if self._skip_state is None else int(self._skip_state[1].item())
 
     # ------------------------------------------------------------------ step counter <-> torch's per-parameter state
     def _loaded_step(self) -> int:
@@ -266,6 +310,9 @@ class FusedAdamW(torch.optim.AdamW):
         self._t += n
 
     def _sync_state_steps(self) -> None:
+        if self._guarded and self._hyper is not None:
+            # skipped steps are known to the device alone: hyper[0] counts the applied ones (the one synchronisation)
+            self._t = int(self._hyper[0].item())
         for st in self.state.values():
             if "exp_avg" in st:
                 st["step"] = torch.tensor(float(self._t), dtype=torch.float32)

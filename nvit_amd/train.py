@@ -6,11 +6,14 @@ place — but ONE persistent HIP launch instead of ~30 torch kernels per block.
 
 `train_step` reproduces the call sequence of the reference hot loop
 (train.py:898-946,989-990): forward -> cross_entropy -> backward -> clip_grad_norm_(1.0) ->
-AdamW.step -> zero_grad(set_to_none) -> normalize_matrices.  With the FusedAdamW that
+AdamW.step -> zero_grad(set_to_none) -> normalize_matrices, with the loop's gradient accumulation
+(`accumulation_steps`) and its GradScaler's skipped step (`skip_nonfinite`) as options.  With the FusedAdamW that
 `configure_optimizers` returns, clip + AdamW + renorm run as two HIP launches (optim.py, SURVEY.md §8f F1);
 with a plain torch optimizer the three steps run separately, same result.
 """
 from __future__ import annotations
+
+from contextlib import nullcontext
 
 import torch
 
@@ -90,17 +93,76 @@ def add_aux_losses(config, loss: torch.Tensor, aux, consistency_weight: float = 
     return loss
 
 
+def _check_step_args(optimizer, X, accumulation_steps, skip_nonfinite) -> None:
+    """The argument checks of train_step / GraphedTrainStep: ValueError, before any device work."""
+    n = accumulation_steps
+    if not isinstance(n, int) or isinstance(n, bool) or n < 1:
+        raise ValueError(f"accumulation_steps must be an int >= 1 (got {n!r})")
+    if X.shape[0] % n:
+        raise ValueError(f"accumulation_steps={n} does not divide the batch of {X.shape[0]} rows")
+    if skip_nonfinite and not isinstance(optimizer, FusedAdamW):
+        raise ValueError("skip_nonfinite=True needs the FusedAdamW returned by ViT.configure_optimizers")
+
+
+def _forward_backward(model, X, y, n: int, before_micro=None):
+    """The n forward/backward passes of one optimizer step (reference train.py:898-928); returns (logits, loss, aux),
+    all attached for n == 1 (exactly the single pass, no division is launched) and detached sums for n > 1.
+    before_micro(i), if given, runs ahead of micro-step i (GraphedTrainStep hands the SOM maps their rate there)."""
+    cfg = _unwrap(model).config
+    if n == 1:
+        if before_micro is not None:
+            before_micro(0)
+        logits, aux = model(X)
+        loss = total_loss(cfg, logits, aux, y)
+        loss.backward()
+        return logits, loss, aux
+    b = X.shape[0] // n
+    no_sync = getattr(model, "no_sync", None)
+    parts, loss, aux = [], None, None
+    for i in range(n):
+        if before_micro is not None:
+            before_micro(i)
+        # data parallel: only the last micro-step communicates (train.py:899-902)
+        with (no_sync() if no_sync is not None and i < n - 1 else nullcontext()):
+            logits_i, aux_i = model(X[i * b:(i + 1) * b])
+            loss_i = total_loss(cfg, logits_i, aux_i, y[i * b:(i + 1) * b]) / n
+            loss_i.backward()
+        parts.append(logits_i.detach())
+        scaled = {k: v.detach() / n for k, v in aux_i.items()}
+        loss = loss_i.detach() if loss is None else loss + loss_i.detach()
+        aux = scaled if aux is None else {k: aux[k] + scaled[k] for k in aux}
+    return torch.cat(parts), loss, aux
+
+
 def train_step(model, optimizer, X: torch.Tensor, y: torch.Tensor, grad_clip: float = 1.0,
-               sync_grads=None):
-    """One optimizer step in the reference's order; returns (logits, loss, aux, grad_norm)."""
-    logits, aux = model(X)
-    loss = total_loss(_unwrap(model).config, logits, aux, y)
-    loss.backward()
+               sync_grads=None, *, accumulation_steps: int = 1, skip_nonfinite: bool = False):
+    """One optimizer step in the reference's order; returns (logits, loss, aux, grad_norm).
+
+    accumulation_steps = N > 1 (`training.gradient_accumulation_steps`, train.py:898-928): the batch (a multiple of N
+    rows) is cut into N micro-batches, micro-batch i being rows [i*b, (i+1)*b); each runs a training forward, then
+    total_loss / N, then backward, and the gradients add up in autograd; one optimizer step follows.  `model.step`
+    advances by N, and the Kohonen head updates its SOM nodes N times, each at the rate of its own `model.step`.  A
+    model with a `no_sync()` (DataParallel) runs micro-steps 0..N-2 inside it; `sync_grads` is called once, after the
+    last backward.  Returned: the N logits concatenated [N*b, classes], loss = the sum of the N scaled losses in
+    micro-step order, aux[k] = the sum of aux_i[k] / N, grad_norm as for N = 1.  The reference feeds the SAME (X, y)
+    to all N micro-steps (train.py:885-905 fetches once per iteration); X.repeat(N, 1, 1, 1), y.repeat(N) reproduces
+    that.
+
+    skip_nonfinite=True (the reference runs GradScaler for bf16 too, train.py:135-136, 930-942): a step whose
+    gradients hold inf or NaN - in any micro-batch - is left out on the device, weights, moments and step count
+    untouched; see FusedAdamW.step_fused.  grad_norm is then returned also with grad_clip == 0, and is inf / NaN for a
+    skipped step; `optimizer.skipped_steps()` counts them.  Under DataParallel every rank sees the same averaged
+    gradients, hence the same decision.  Needs FusedAdamW.
+
+    Wrong accumulation_steps (no int, < 1, no divisor of the batch) or skip_nonfinite with another optimizer raise
+    ValueError before any device work."""
+    _check_step_args(optimizer, X, accumulation_steps, skip_nonfinite)
+    logits, loss, aux = _forward_backward(model, X, y, accumulation_steps)
     if sync_grads is not None:
         sync_grads()
     if isinstance(optimizer, FusedAdamW):
-        # clip + AdamW + normalize_matrices in two launches (nvit_grad_sqnorm, nvit_adamw_renorm)
-        gnorm = optimizer.step_fused(model, grad_clip)
+        # clip + AdamW + normalize_matrices in two launches (nvit_grad_sqnorm, nvit_adamw_renorm); three when guarded
+        gnorm = optimizer.step_fused(model, grad_clip, skip_nonfinite=skip_nonfinite)
         if gnorm is not None:
             gnorm = gnorm[0].clone()
         optimizer.zero_grad(set_to_none=True)
@@ -131,9 +193,18 @@ class GraphedTrainStep:
     After N calls `model.step`, the optimizer's step count, the weights and the SOM nodes are those of N eager steps.
     The model's `training` flag at capture time is part of the graph.  Like the eager step, a call leaves every
     `p.grad` None (the graph keeps its own gradient buffers), so eager and graphed steps can alternate on one model.
+
+    accumulation_steps = N and skip_nonfinite mean what they mean for `train_step`.  The N forward/backward passes and
+    the one optimizer step are ONE graph over a static X of N*b rows; the SOM rates are then N x maps device floats
+    (micro-step i of the capture hands each map its own element), filled from get_kohonen_lr(step+1 .. step+N) ahead
+    of a replay, and a call advances `model.step` by N.  With skip_nonfinite the replay itself leaves a non-finite step
+    out (no host code runs between backward and update, so only the device can): `optimizer.skipped_steps()` and
+    `state_dict()` read the counts back.
     """
 
-    def __init__(self, model, optimizer, X: torch.Tensor, y: torch.Tensor, grad_clip: float = 1.0, warmup: int = 3):
+    def __init__(self, model, optimizer, X: torch.Tensor, y: torch.Tensor, grad_clip: float = 1.0, warmup: int = 3,
+                 *, accumulation_steps: int = 1, skip_nonfinite: bool = False):
+        _check_step_args(optimizer, X, accumulation_steps, skip_nonfinite)
         m = _unwrap(model)
         if not isinstance(optimizer, FusedAdamW):
             raise RuntimeError("GraphedTrainStep needs the FusedAdamW returned by ViT.configure_optimizers")
@@ -142,34 +213,38 @@ class GraphedTrainStep:
         if X.device.type != "cuda":
             raise RuntimeError("GraphedTrainStep: inputs must live on the HIP device")
         self.model, self.optimizer, self.grad_clip = model, optimizer, grad_clip
+        self.accumulation_steps, self.skip_nonfinite = accumulation_steps, bool(skip_nonfinite)
+        N = accumulation_steps
         self.X, self.y = X.clone(), y.clone()
         side = torch.cuda.Stream()   # warm-up and capture share one stream: autograd's gradient accumulators are
         side.wait_stream(torch.cuda.current_stream())   # bound to the stream they are first used on
         with torch.cuda.stream(side):
             for _ in range(max(1, warmup)):   # builds every cache (shadow/renorm tables, LDS attributes, workspaces)
-                train_step(model, optimizer, self.X, self.y, grad_clip)
+                train_step(model, optimizer, self.X, self.y, grad_clip, accumulation_steps=N,
+                           skip_nonfinite=self.skip_nonfinite)
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         optimizer.zero_grad(set_to_none=True)
         optimizer.reserve_staging()
-        # SOM rates: one device float per map and their pinned host twin, guarded by an event (the copy queued by the
-        # previous call must have read the twin before it is overwritten)
+        # SOM rates: one device float per micro-step and map and their pinned host twin, guarded by an event (the copy
+        # queued by the previous call must have read the twin before it is overwritten)
         self._maps = [m.local_kohonen, m.global_kohonen] if m.config.use_kohonen else []
-        self._steps = bool(m.training)   # the captured forward is the training one: each replay is one model.step
+        self._steps = bool(m.training)   # the captured forwards are training ones: a replay is N model.steps
         if self._maps:
-            self._rate_dev = torch.zeros(len(self._maps), device=X.device, dtype=torch.float32)
-            self._rate_pin = torch.zeros(len(self._maps), dtype=torch.float32).pin_memory()
+            self._rate_dev = torch.zeros(N, len(self._maps), device=X.device, dtype=torch.float32)
+            self._rate_pin = torch.zeros(N, len(self._maps), dtype=torch.float32).pin_memory()
             self._rate_ev = torch.cuda.Event()
         step0 = m.step
         self.graph = torch.cuda.CUDAGraph()
+
+        def hand_rates(i):
+            for j, km in enumerate(self._maps):
+                object.__setattr__(km, "_rate_dev", self._rate_dev[i, j:j + 1])
+
         try:
-            for i, km in enumerate(self._maps):
-                object.__setattr__(km, "_rate_dev", self._rate_dev[i:i + 1])
             with torch.cuda.graph(self.graph, stream=side):
-                logits, aux = model(self.X)
-                loss = total_loss(m.config, logits, aux, self.y)
-                loss.backward()
-                gnorm = optimizer.step_fused(model, grad_clip)
+                logits, loss, aux = _forward_backward(model, self.X, self.y, N, hand_rates)
+                gnorm = optimizer.step_fused(model, grad_clip, skip_nonfinite=self.skip_nonfinite)
         finally:
             for km in self._maps:
                 object.__setattr__(km, "_rate_dev", None)
@@ -190,17 +265,19 @@ class GraphedTrainStep:
         self.optimizer.rewrite_hyper(self._table)
 
     def _advance_som(self) -> None:
-        """model.step += 1 and, per map, the rate the eager forward of that step would pass by value, sent to the device
-        scalars on the current stream (ahead of the replay)."""
+        """model.step += 1 per micro-step and, per micro-step and map, the rate the eager forward of that step would
+        pass by value, sent to the device scalars on the current stream (ahead of the replay)."""
         m = _unwrap(self.model)
+        step0 = m.step
         if self._steps:
-            m.step += 1
+            m.step += self.accumulation_steps
         if not self._maps:
             return
-        lr = m.get_kohonen_lr(m.step)
         self._rate_ev.synchronize()
-        for i, km in enumerate(self._maps):
-            self._rate_pin[i] = float(lr) * float(km.alpha)   # rounded to fp32 as the by-value argument is
+        for i in range(self.accumulation_steps):
+            lr = m.get_kohonen_lr(step0 + i + 1 if self._steps else step0)
+            for j, km in enumerate(self._maps):
+                self._rate_pin[i, j] = float(lr) * float(km.alpha)   # rounded to fp32 as the by-value argument is
         self._rate_dev.copy_(self._rate_pin, non_blocking=True)
         self._rate_ev.record()
 
