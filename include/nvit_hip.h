@@ -266,7 +266,9 @@ int nvit_norm_skip_bwd(const float* dout, const float* src, const float* tgt, co
  * qh = (sqk*c_q) * nrm_d(q) etc. written [B,H,T,d] type dt; v copied to [B,H,T,d];
  * rq, rk [M,H] fp32 = 1/||q_head||.
  * sqk == NULL: the head split alone (plain-ViT attention, model.py:97-100): q, k, v copied to [B,H,T,d] as they are
- * (type conversion only); rq, rk are not written. */
+ * (type conversion only); rq, rk are not written.
+ * d in {16, 32, 64, 128}, H*d <= 2048.  nvit_qknorm_bwd and nvit_heads_pad_bwd below run one kernel (heads_merge_kernel,
+ * templated on the stored head width: here d itself); the forward has a kernel per layout. */
 int nvit_qknorm_fwd(int dt, const void* q, int ldq, const void* k, int ldk, const void* v, int ldv,
                     const float* sqk, float c_q, void* qh, void* kh, void* vh, float* rq, float* rk, int B,
                     int T, int H, int d, void* stream);
@@ -283,6 +285,7 @@ int nvit_qknorm_bwd(int dt, const void* dqh, const void* dkh, const void* dvh, c
  * The head tensors are [B,H,T,dp] with columns d..dp-1 stored as zeros (no score, no output column < d and no gradient
  * column < d changes); nvit_attn_fwd / _fwd_bounded / _bwd then run at head dim dp with the scale of the REAL d.
  * dp = 128, d % 8 == 0, 0 < d < dp, H*d <= 2048, any B*T >= 1.  Deterministic, no atomics.
+ * The backward kernel is that of nvit_qknorm_bwd at stored head width dp; lanes on a pad column load nothing.
  * nvit_heads_pad_fwd: nvit_qknorm_fwd from fp32 projections (dt NVIT_F32: fp32 head tensors, NVIT_BF16_F32IN: bf16)
  *   into qh, kh, vh [B,H,T,dp]; EVERY pad column is stored (as +0) on every launch.  sqk (compact [H*d]) given: the sum
  *   of squares over the d real columns from the unrounded projections, rq, rk [M,H], and - sqk_pad not NULL - sqk_pad

@@ -58,6 +58,13 @@ static inline auto with_head_dim(int d, F&& f) {
   return f(int_c<128>{});
 }
 
+// stored head width of the head split / merge kernels; the entry points have rejected anything but 16, 32, 64 and 128
+template <typename F>
+static inline auto with_head_width(int dp, F&& f) {
+  if (dp == 16) return f(int_c<16>{});
+  return with_head_dim(dp, f);
+}
+
 // Launches through a kernel pointer that a selector returned.  The caller checks the launch (NVIT_CHECK_LAUNCH).
 template <typename... P>
 static inline void launch(void (*kernel)(P...), dim3 grid, dim3 block, size_t shmem, hipStream_t s,

@@ -333,19 +333,45 @@ __global__ __launch_bounds__(256) void norm_skip_bwd_kernel(const float* dout, c
   if (threadIdx.x == 0) part_dskip[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
 }
 
-// ------------------------------------------------------------------------------ q/k normalise
+// ------------------------------------------------------------------------------ head split / merge (+ q/k normalise)
+// Compact heads (d = 16, 32, 64, 128) are stored d wide.  Head dims d < 128 that are no power of two (72, 80, 88, 104) run
+// on the D = 128 attention kernels: their head tensors are [B,H,T,PAD_D] with columns d..PAD_D-1 stored as zeros, which
+// change no score, no output column < d and no gradient column < d.  DP is the stored head width, d <= DP the real one.
+// heads_pad_fwd_kernel and heads_merge_kernel index a row in STORED coordinates: lane l of pass p owns columns pc..pc+3 of
+// the H*DP wide stored row, pc = p*256 + 4l, so a head is always one aligned group of DP/4 lanes whatever d is, and the
+// lanes with pc % DP >= d load nothing and store the zeros.  With d == DP every lane inside the row is live and the stored
+// column is the token-major one: heads_merge_kernel is the backward of both layouts.  The forward keeps a kernel per
+// layout: the compact one issues all of a row's loads before any arithmetic, which the pass loop lost to at d = 128.
+constexpr int PAD_D = 128;
+
 struct QkArgs {
-  const void *q, *k, *v;
+  const void *q, *k, *v;   // projection outputs, token-major with row strides ld*
   int ldq, ldk, ldv;
   const float* sqk;
   float c_q;
   void *qh, *kh, *vh;
   float *rq, *rk;
+  float* sqk_pad;   // padded heads only: [H*PAD_D], sqk with zero pads, for nvit_attn_fwd_bounded at D = PAD_D (NORM; may be NULL)
   int B, T, H, d;
 };
 
-// NORM = false (sqk == NULL): the head split alone, q and k copied as they are (the plain-ViT attention, reference
-// model.py:97-100 without :104-112); rq / rk are not written.
+// A lane's four terms of a head's dot product, in two roundings: one fma chain, or every product rounded before the
+// sum.  Which dot product takes which is part of every output's bits (profiles/heads_unify_bitwise.log) and differs
+// between the layouts: sq sums and dk_ chains everywhere, sk chains on compact heads and sums on padded ones, dq_ the
+// other way round.  The order of the chain is load-bearing too - term 1 first, then 0, 2, 3 - do not tidy it.  Giving
+// both layouts one rounding is a numerical change of its own.
+__device__ __forceinline__ float dot4_fma(f32x4 a, f32x4 b) {
+  return __builtin_fmaf(a[3], b[3], __builtin_fmaf(a[2], b[2], __builtin_fmaf(a[0], b[0], a[1] * b[1])));
+}
+__device__ __forceinline__ float dot4_sum(f32x4 a, f32x4 b) {
+#pragma clang fp contract(off)
+  return a[0] * b[0] + a[1] * b[1] + a[2] * b[2] + a[3] * b[3];
+}
+
+// qknorm_fwd_kernel: qh/kh/vh [B,H,T,d] (compact) from token-major q/k/v; the row sits in NV register vectors.  NORM: q and
+// k normalised per head from the unrounded projections and scaled by sqk*c_q, one rounding at the head tensors, rq / rk
+// [M,H] = the inverse norms.  NORM = false (sqk == NULL): the head split alone, q and k copied as they are (the plain-ViT
+// attention, reference model.py:97-100 without :104-112); rq / rk are not written.
 template <int NV, typename TI, typename T, bool NORM>   // TI: type of the projection outputs read, T: type of the head tensors written
 __global__ __launch_bounds__(256) void qknorm_fwd_kernel(QkArgs a) {
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
@@ -374,10 +400,7 @@ __global__ __launch_bounds__(256) void qknorm_fwd_kernel(QkArgs a) {
           store4<T>(reinterpret_cast<T*>(a.vh) + dst, v.v[i]);
         }
       } else {
-        float sq = q.v[i][0] * q.v[i][0] + q.v[i][1] * q.v[i][1] + q.v[i][2] * q.v[i][2] + q.v[i][3] * q.v[i][3];
-        float sk = k.v[i][0] * k.v[i][0] + k.v[i][1] * k.v[i][1] + k.v[i][2] * k.v[i][2] + k.v[i][3] * k.v[i][3];
-        sq = group_sum_dyn(sq, G);
-        sk = group_sum_dyn(sk, G);
+        const float sq = group_sum_dyn(dot4_sum(q.v[i], q.v[i]), G), sk = group_sum_dyn(dot4_fma(k.v[i], k.v[i]), G);
         if (c < C) {
           const float rq = 1.0f / sqrtf(sq), rk = 1.0f / sqrtf(sk);
           store4<T>(reinterpret_cast<T*>(a.qh) + dst, q.v[i] * rq * s.v[i]);
@@ -393,120 +416,14 @@ __global__ __launch_bounds__(256) void qknorm_fwd_kernel(QkArgs a) {
   }
 }
 
-struct QkBwdArgs {
-  const void *dqh, *dkh, *dvh, *qh, *kh;
-  const float *rq, *rk, *sqk;
-  float c_q;
-  void *dq, *dk, *dv;
-  int ldq, ldk, ldv;
-  float* part;
-  int B, T, H, d;
-};
-
-template <int NV, typename T>
-__global__ __launch_bounds__(256) void qknorm_bwd_kernel(QkBwdArgs a) {
-  __shared__ float red[ROW_WAVES][NV * 256];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int C = a.H * a.d, M = a.B * a.T, G = a.d >> 2;
-  RowVec<NV> s, sinv, ds;
-  row_load<NV, float>(s, a.sqk, C, lane);
-#pragma unroll
-  for (int i = 0; i < NV; ++i) {
-    s.v[i] = s.v[i] * a.c_q;
-    ds.v[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int e = 0; e < 4; ++e) sinv.v[i][e] = s.v[i][e] != 0.f ? 1.0f / s.v[i][e] : 0.f;
-  }
-  for (int m = blockIdx.x * ROW_WAVES + wid; m < M; m += gridDim.x * ROW_WAVES) {
-    const int b = m / a.T, t = m % a.T;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const int c = (i * 64 + lane) * 4;
-      const bool ok = c < C;
-      const int h = ok ? c / a.d : 0, j = ok ? c % a.d : 0;
-      const size_t src = (((size_t)b * a.H + h) * a.T + t) * a.d + j;
-      const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-      const f32x4 gq = ok ? load4<T>(reinterpret_cast<const T*>(a.dqh) + src) : z;
-      const f32x4 gk = ok ? load4<T>(reinterpret_cast<const T*>(a.dkh) + src) : z;
-      const f32x4 nq = ok ? load4<T>(reinterpret_cast<const T*>(a.qh) + src) * sinv.v[i] : z;  // unit vector
-      const f32x4 nk = ok ? load4<T>(reinterpret_cast<const T*>(a.kh) + src) * sinv.v[i] : z;
-      ds.v[i] += gq * nq + gk * nk;
-      const f32x4 sgq = gq * s.v[i], sgk = gk * s.v[i];
-      float dq_ = sgq[0] * nq[0] + sgq[1] * nq[1] + sgq[2] * nq[2] + sgq[3] * nq[3];
-      float dk_ = sgk[0] * nk[0] + sgk[1] * nk[1] + sgk[2] * nk[2] + sgk[3] * nk[3];
-      dq_ = group_sum_dyn(dq_, G);
-      dk_ = group_sum_dyn(dk_, G);
-      if (ok) {
-        const float rq = a.rq[(size_t)m * a.H + h], rk = a.rk[(size_t)m * a.H + h];
-        store4<T>(reinterpret_cast<T*>(a.dq) + (size_t)m * a.ldq + c, (sgq - nq * dq_) * rq);
-        store4<T>(reinterpret_cast<T*>(a.dk) + (size_t)m * a.ldk + c, (sgk - nk * dk_) * rk);
-        store4<T>(reinterpret_cast<T*>(a.dv) + (size_t)m * a.ldv + c,
-                  load4<T>(reinterpret_cast<const T*>(a.dvh) + src));
-      }
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < NV; ++i)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) red[wid][(i * 64 + lane) * 4 + e] = ds.v[i][e];
-  __syncthreads();
-  for (int c = threadIdx.x; c < C; c += 256) {
-    float t = 0.f;
-#pragma unroll
-    for (int w = 0; w < ROW_WAVES; ++w) t += red[w][c];
-    a.part[(size_t)blockIdx.x * C + c] = t;
-  }
-}
-
-// merge_heads_kernel: the backward of the NORM = false split: dq/dk/dv (type T, row strides ld*) = dqh/dkh/dvh
-// [B,H,T,d] merged back to token-major rows.
-template <int NV, typename T>
-__global__ __launch_bounds__(256) void merge_heads_kernel(QkBwdArgs a) {
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int C = a.H * a.d, M = a.B * a.T;
-  for (int m = blockIdx.x * ROW_WAVES + wid; m < M; m += gridDim.x * ROW_WAVES) {
-    const int b = m / a.T, t = m % a.T;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const int c = (i * 64 + lane) * 4;
-      if (c < C) {
-        const int h = c / a.d, j = c % a.d;
-        const size_t src = (((size_t)b * a.H + h) * a.T + t) * a.d + j;
-        store4<T>(reinterpret_cast<T*>(a.dq) + (size_t)m * a.ldq + c, load4<T>(reinterpret_cast<const T*>(a.dqh) + src));
-        store4<T>(reinterpret_cast<T*>(a.dk) + (size_t)m * a.ldk + c, load4<T>(reinterpret_cast<const T*>(a.dkh) + src));
-        store4<T>(reinterpret_cast<T*>(a.dv) + (size_t)m * a.ldv + c, load4<T>(reinterpret_cast<const T*>(a.dvh) + src));
-      }
-    }
-  }
-}
-
-// ------------------------------------------------------------------------------ zero-padded heads
-// Head dims d < 128 that are no power of two (72, 80, 88, 104) run on the D = 128 attention kernels: the head tensors are
-// [B,H,T,PAD_D] with columns d..PAD_D-1 stored as zeros, which change no score, no output column < d and no gradient
-// column < d.  These kernels index a row in PADDED coordinates: lane l of pass p owns columns pc..pc+3 of the H*PAD_D
-// wide padded row, pc = p*256 + 4l, so a head is always one aligned group of 32 lanes (two heads per pass) whatever d is,
-// and the lanes with pc % PAD_D >= d load nothing and store the zeros.
-constexpr int PAD_D = 128;
-
-struct PadSplitArgs {
-  const float *q, *k, *v;   // fp32 projection outputs
-  int ldq, ldk, ldv;
-  const float* sqk;
-  float c_q;
-  void *qh, *kh, *vh;
-  float *rq, *rk;
-  float* sqk_pad;   // [H*PAD_D]: sqk with zero pads, for nvit_attn_fwd_bounded at D = PAD_D (NORM only; may be NULL)
-  int B, T, H, d;
-};
-
-__device__ __forceinline__ float dot4(f32x4 a, f32x4 b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2] + a[3] * b[3]; }
-
-// heads_pad_fwd_kernel: qknorm_fwd_kernel (NORM: normalise from the unrounded projections, one rounding at the head
-// tensors; !NORM: the split alone) into zero-padded head tensors.  Every launch stores every pad column.
+// heads_pad_fwd_kernel: qknorm_fwd_kernel from fp32 projections into zero-padded head tensors [B,H,T,PAD_D].  Every launch
+// stores every pad column.
 template <typename T, bool NORM>
-__global__ __launch_bounds__(256) void heads_pad_fwd_kernel(PadSplitArgs a) {
+__global__ __launch_bounds__(256) void heads_pad_fwd_kernel(QkArgs a) {
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int M = a.B * a.T, HP = a.H * PAD_D;
+  const float *aq = reinterpret_cast<const float*>(a.q), *ak = reinterpret_cast<const float*>(a.k),
+              *av = reinterpret_cast<const float*>(a.v);
   const f32x4 z = {0.f, 0.f, 0.f, 0.f};
   if constexpr (NORM) {
     if (a.sqk_pad && blockIdx.x == 0) {
@@ -523,12 +440,12 @@ __global__ __launch_bounds__(256) void heads_pad_fwd_kernel(PadSplitArgs a) {
       const int h = pc / PAD_D, j = pc % PAD_D;
       const bool in = pc < HP, live = in && j < a.d;
       const int c = h * a.d + j;
-      f32x4 q = live ? load4<float>(a.q + (size_t)m * a.ldq + c) : z;
-      f32x4 k = live ? load4<float>(a.k + (size_t)m * a.ldk + c) : z;
-      const f32x4 v = live ? load4<float>(a.v + (size_t)m * a.ldv + c) : z;
+      f32x4 q = live ? load4<float>(aq + (size_t)m * a.ldq + c) : z;
+      f32x4 k = live ? load4<float>(ak + (size_t)m * a.ldk + c) : z;
+      const f32x4 v = live ? load4<float>(av + (size_t)m * a.ldv + c) : z;
       if constexpr (NORM) {
         const f32x4 s = live ? load4<float>(a.sqk + c) * a.c_q : z;
-        const float sq = group_sum<32>(dot4(q, q)), sk = group_sum<32>(dot4(k, k));
+        const float sq = group_sum<32>(dot4_sum(q, q)), sk = group_sum<32>(dot4_sum(k, k));
         const float rq = 1.0f / sqrtf(sq), rk = 1.0f / sqrtf(sk);
         q = live ? q * rq * s : z;   // (the pads are zeros even where a head's norm is 0 or not finite)
         k = live ? k * rk * s : z;
@@ -547,45 +464,84 @@ __global__ __launch_bounds__(256) void heads_pad_fwd_kernel(PadSplitArgs a) {
   }
 }
 
-// heads_pad_bwd_kernel: qknorm_bwd_kernel (NORM; same formulas) / merge_heads_kernel (!NORM) from the first d columns of
-// zero-padded dqh/dkh/dvh (the pad columns are never read).  The d(sqk*c_q) partials of a wave accumulate in its own LDS
-// row of C floats (dynamic LDS: ROW_WAVES * C floats with NORM, none without) in compact channel order.
-template <typename T, bool NORM>
-__global__ __launch_bounds__(256) void heads_pad_bwd_kernel(QkBwdArgs a) {
-  extern __shared__ __attribute__((aligned(16))) float pad_red[];
+struct QkBwdArgs {
+  const void *dqh, *dkh, *dvh, *qh, *kh;
+  const float *rq, *rk, *sqk;
+  float c_q;
+  void *dq, *dk, *dv;
+  int ldq, ldk, ldv;
+  float* part;
+  int B, T, H, d;
+};
+
+// heads_merge_kernel: the backward of both forward kernels: dq/dk/dv (type T, row strides ld*) from the first d columns of
+// every head of dqh/dkh/dvh [B,H,T,DP] (pad columns are never read).  NORM = false: the head merge alone, two passes
+// of a row per loop iteration; NORM: one pass per iteration, through
+// the normalise as well, and part [gridDim.x, C] = each workgroup's d(sqk*c_q).  Dynamic LDS with NORM, (ROW_WAVES + 2) * C
+// floats (at most 48 KiB), none without: a wave accumulates its partials in its own row of C floats, and s = sqk*c_q and
+// 1/s are computed once per workgroup into two more, all in token-major channel order.
+template <int DP, typename T, bool NORM>
+__global__ __launch_bounds__(256) void heads_merge_kernel(QkBwdArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float merge_red[];
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int C = a.H * a.d, M = a.B * a.T, HP = a.H * PAD_D;
+  const int C = a.H * a.d, M = a.B * a.T, HP = a.H * DP;
   const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-  float* red = pad_red + wid * C;
+  float* red = merge_red + wid * C;
+  const float *s_row = merge_red + ROW_WAVES * C, *sinv_row = s_row + C;
   if constexpr (NORM) {
-    for (int c = threadIdx.x; c < ROW_WAVES * C; c += 256) pad_red[c] = 0.f;
+    for (int c = threadIdx.x; c < ROW_WAVES * C; c += 256) merge_red[c] = 0.f;
+    for (int c = threadIdx.x; c < C; c += 256) {
+      const float s = a.sqk[c] * a.c_q;
+      merge_red[ROW_WAVES * C + c] = s;
+      merge_red[(ROW_WAVES + 1) * C + c] = s != 0.f ? 1.0f / s : 0.f;
+    }
     __syncthreads();
   }
   for (int m = blockIdx.x * ROW_WAVES + wid; m < M; m += gridDim.x * ROW_WAVES) {
     const int b = m / a.T, t = m % a.T;
-    for (int p0 = 0; p0 < HP; p0 += 256) {
-      const int pc = p0 + lane * 4;
-      const int h = pc / PAD_D, j = pc % PAD_D;
-      const bool live = pc < HP && j < a.d;
-      const int c = h * a.d + j;
-      const size_t src = (((size_t)b * a.H + h) * a.T + t) * PAD_D + j;
-      const f32x4 gq = live ? load4<T>(reinterpret_cast<const T*>(a.dqh) + src) : z;
-      const f32x4 gk = live ? load4<T>(reinterpret_cast<const T*>(a.dkh) + src) : z;
-      if constexpr (!NORM) {
-        if (live) {
-          store4<T>(reinterpret_cast<T*>(a.dq) + (size_t)m * a.ldq + c, gq);
-          store4<T>(reinterpret_cast<T*>(a.dk) + (size_t)m * a.ldk + c, gk);
-          store4<T>(reinterpret_cast<T*>(a.dv) + (size_t)m * a.ldv + c, load4<T>(reinterpret_cast<const T*>(a.dvh) + src));
-        }
-      } else {
-        const f32x4 s = live ? load4<float>(a.sqk + c) * a.c_q : z;
-        f32x4 sinv;
+    if constexpr (!NORM) {
+      // The merge alone: the loads of two passes go out before the first store.  Loads and stores share one in-order
+      // counter, so a load behind a store waits for that store's acknowledgement too; one pass per iteration lost 6 % to
+      // the compile-time unrolled kernel this one replaced at d = 64 (profiles/heads_unify_ab.log).
+      for (int p0 = 0; p0 < HP; p0 += 512) {
+        f32x4 g[2][3];
+        int c[2];
+        bool live[2];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) sinv[e] = s[e] != 0.f ? 1.0f / s[e] : 0.f;
+        for (int u = 0; u < 2; ++u) {
+          const int pc = p0 + u * 256 + lane * 4;
+          const int h = pc / DP, j = pc % DP;
+          live[u] = pc < HP && j < a.d;
+          c[u] = h * a.d + j;
+          const size_t src = (((size_t)b * a.H + h) * a.T + t) * DP + j;
+          g[u][0] = live[u] ? load4<T>(reinterpret_cast<const T*>(a.dqh) + src) : z;
+          g[u][1] = live[u] ? load4<T>(reinterpret_cast<const T*>(a.dkh) + src) : z;
+          g[u][2] = live[u] ? load4<T>(reinterpret_cast<const T*>(a.dvh) + src) : z;
+        }
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+          if (live[u]) {
+            store4<T>(reinterpret_cast<T*>(a.dq) + (size_t)m * a.ldq + c[u], g[u][0]);
+            store4<T>(reinterpret_cast<T*>(a.dk) + (size_t)m * a.ldk + c[u], g[u][1]);
+            store4<T>(reinterpret_cast<T*>(a.dv) + (size_t)m * a.ldv + c[u], g[u][2]);
+          }
+        }
+      }
+    } else {
+      for (int p0 = 0; p0 < HP; p0 += 256) {
+        const int pc = p0 + lane * 4;
+        const int h = pc / DP, j = pc % DP;
+        const bool live = pc < HP && j < a.d;
+        const int c = h * a.d + j;
+        const size_t src = (((size_t)b * a.H + h) * a.T + t) * DP + j;
+        const f32x4 gq = live ? load4<T>(reinterpret_cast<const T*>(a.dqh) + src) : z;
+        const f32x4 gk = live ? load4<T>(reinterpret_cast<const T*>(a.dkh) + src) : z;
+        const f32x4 s = live ? load4<float>(s_row + c) : z, sinv = live ? load4<float>(sinv_row + c) : z;
         const f32x4 nq = live ? load4<T>(reinterpret_cast<const T*>(a.qh) + src) * sinv : z;   // unit vector
         const f32x4 nk = live ? load4<T>(reinterpret_cast<const T*>(a.kh) + src) * sinv : z;
         const f32x4 sgq = gq * s, sgk = gk * s;
-        const float dq_ = group_sum<32>(dot4(sgq, nq)), dk_ = group_sum<32>(dot4(sgk, nk));
+        const float dq_ = group_sum<DP / 4>(a.d == DP ? dot4_sum(sgq, nq) : dot4_fma(sgq, nq));
+        const float dk_ = group_sum<DP / 4>(dot4_fma(sgk, nk));
         if (live) {
           f32x4* r = reinterpret_cast<f32x4*>(red + c);   // this lane alone owns columns c..c+3 of the wave's row
           *r = *r + (gq * nq + gk * nk);
@@ -602,7 +558,7 @@ __global__ __launch_bounds__(256) void heads_pad_bwd_kernel(QkBwdArgs a) {
     for (int c = threadIdx.x; c < C; c += 256) {
       float t = 0.f;
 #pragma unroll
-      for (int w = 0; w < ROW_WAVES; ++w) t += pad_red[w * C + c];
+      for (int w = 0; w < ROW_WAVES; ++w) t += merge_red[w * C + c];
       a.part[(size_t)blockIdx.x * C + c] = t;
     }
   }
@@ -1325,25 +1281,45 @@ extern "C" int nvit_res_skip_bwd(int dt, const float* dout, const float* h, cons
   return NVIT_OK;
 }
 
+// ---- head split / merge: compact heads (nvit_qknorm_*) and zero-padded ones (nvit_heads_pad_*, dp = 128) ----
+// Each entry point checks its own arguments and opens its ProfScope; these pick the instantiation and launch it (NORM when
+// sqk is given).  dp: the stored head width (a.d: compact heads).
+static void heads_split_launch(int dt, const QkArgs& a, int dp, hipStream_t s) {
+  const bool norm = a.sqk != nullptr;
+  const auto kernel = dp == a.d ? with_row_vecs<8>(a.H * a.d, [&](auto nv) {
+    return with_bool(norm, [&](auto nm) {
+      return with_in_out_elems(dt, [&](auto ti, auto to) {
+        return &qknorm_fwd_kernel<nv, tag_t<decltype(ti)>, tag_t<decltype(to)>, nm>;
+      });
+    });
+  }) : with_bool(norm, [&](auto nm) {
+    return with_elem(dt, [&](auto to) { return &heads_pad_fwd_kernel<tag_t<decltype(to)>, nm>; });
+  });
+  launch(kernel, dim3(row_grid(a.B * a.T)), dim3(256), 0, s, a);
+}
+
+// with the normalise: nblk workgroups, one row of part each; the merge alone: a row grid (nblk unused)
+static void heads_merge_launch(int dt, const QkBwdArgs& a, int dp, int nblk, hipStream_t s) {
+  const bool norm = a.sqk != nullptr;
+  const auto kernel = with_head_width(dp, [&](auto w) {
+    return with_bool(norm, [&](auto nm) {
+      return with_elem(dt, [&](auto t) { return &heads_merge_kernel<w, tag_t<decltype(t)>, nm>; });
+    });
+  });
+  launch(kernel, dim3(norm ? nblk : row_grid(a.B * a.T)), dim3(256),
+         norm ? (size_t)(ROW_WAVES + 2) * a.H * a.d * sizeof(float) : 0, s, a);
+}
+
 extern "C" int nvit_qknorm_fwd(int dt, const void* q, int ldq, const void* k, int ldk, const void* v, int ldv,
                                const float* sqk, float c_q, void* qh, void* kh, void* vh, float* rq, float* rk,
                                int B, int T, int H, int d, void* stream) {
   const int C = H * d;
   NVIT_REQUIRE(d == 16 || d == 32 || d == 64 || d == 128, "qknorm_fwd: head dim %d unsupported", d);
   NVIT_REQUIRE(C <= 2048 && ldq % 4 == 0 && ldk % 4 == 0 && ldv % 4 == 0, "qknorm_fwd: bad C/ld");
-  QkArgs a{q, k, v, ldq, ldk, ldv, sqk, c_q, qh, kh, vh, rq, rk, B, T, H, d};
-  hipStream_t s = (hipStream_t)stream;
-  const int grid = row_grid(B * T);
   NVIT_REQUIRE(dt == NVIT_F32 || dt == NVIT_BF16 || dt == NVIT_BF16_F32IN, "qknorm_fwd: bad dt %d", dt);
+  hipStream_t s = (hipStream_t)stream;
   ProfScope ps(NVIT_KID_ROWOPS, 0.0, (double)B * T * C * (dt == NVIT_F32 ? 24.0 : dt == NVIT_BF16 ? 12.0 : 18.0), s);
-  const auto kernel = with_row_vecs<8>(C, [&](auto nv) {
-    return with_bool(sqk != nullptr, [&](auto norm) {
-      return with_in_out_elems(dt, [&](auto ti, auto to) {
-        return &qknorm_fwd_kernel<nv, tag_t<decltype(ti)>, tag_t<decltype(to)>, norm>;
-      });
-    });
-  });
-  launch(kernel, dim3(grid), dim3(256), 0, s, a);
+  heads_split_launch(dt, QkArgs{q, k, v, ldq, ldk, ldv, sqk, c_q, qh, kh, vh, rq, rk, nullptr, B, T, H, d}, d, s);
   NVIT_CHECK_LAUNCH("qknorm_fwd");
   return NVIT_OK;
 }
@@ -1356,29 +1332,17 @@ extern "C" int nvit_qknorm_bwd(int dt, const void* dqh, const void* dkh, const v
   NVIT_REQUIRE(d == 16 || d == 32 || d == 64 || d == 128, "qknorm_bwd: head dim %d unsupported", d);
   NVIT_REQUIRE(C <= 2048 && ldq % 4 == 0 && ldk % 4 == 0 && ldv % 4 == 0, "qknorm_bwd: bad C/ld");
   NVIT_REQUIRE(nblk > 0 && nblk <= 4096, "qknorm_bwd: nblk out of range");
-  QkBwdArgs a{dqh, dkh, dvh, qh, kh, rq, rk, sqk, c_q, dq, dk, dv, ldq, ldk, ldv, part_dsqk, B, T, H, d};
+  // split without the normalise: the backward is the head merge alone (qh, kh, rq, rk, part unused)
+  NVIT_REQUIRE(sqk || dt == NVIT_F32 || dt == NVIT_BF16, "qknorm_bwd: bad dt %d", dt);
   hipStream_t s = (hipStream_t)stream;
-  if (!sqk) {   // split without the normalise: the backward is the head merge alone (qh, kh, rq, rk, part unused)
-    NVIT_REQUIRE(dt == NVIT_F32 || dt == NVIT_BF16, "qknorm_bwd: bad dt %d", dt);
-    ProfScope ps(NVIT_KID_ROWOPS, 0.0, (double)B * T * C * (dt == NVIT_F32 ? 24.0 : 12.0), s);
-    const int grid = row_grid(B * T);
-    const auto kernel = with_row_vecs<8>(C, [&](auto nv) {
-      return with_elem(dt, [&](auto t) { return &merge_heads_kernel<nv, tag_t<decltype(t)>>; });
-    });
-    launch(kernel, dim3(grid), dim3(256), 0, s, a);
-    NVIT_CHECK_LAUNCH("qknorm_bwd");
-    return NVIT_OK;
-  }
-  ProfScope ps(NVIT_KID_ROWOPS, 0.0, (double)B * T * C * (dt == NVIT_F32 ? 32.0 : 16.0), s);
-  const auto kernel = with_row_vecs<8>(C, [&](auto nv) {
-    return with_elem(dt, [&](auto t) { return &qknorm_bwd_kernel<nv, tag_t<decltype(t)>>; });
-  });
-  launch(kernel, dim3(nblk), dim3(256), 0, s, a);
+  const double eb = dt == NVIT_F32 ? 4.0 : 2.0;
+  ProfScope ps(NVIT_KID_ROWOPS, 0.0, (double)B * T * C * (sqk ? 8.0 : 6.0) * eb, s);
+  heads_merge_launch(dt, QkBwdArgs{dqh, dkh, dvh, qh, kh, rq, rk, sqk, c_q, dq, dk, dv, ldq, ldk, ldv, part_dsqk, B, T, H, d},
+                     d, nblk, s);
   NVIT_CHECK_LAUNCH("qknorm_bwd");
   return NVIT_OK;
 }
 
-// ---- zero-padded heads (head dims that run on the dp = 128 attention kernels) ----
 static bool pad_dims_ok(int H, int d, int dp) {
   return dp == PAD_D && d > 0 && d < dp && d % 8 == 0 && H > 0 && H * d <= 2048;
 }
@@ -1392,13 +1356,9 @@ extern "C" int nvit_heads_pad_fwd(int dt, const float* q, int ldq, const float* 
                "heads_pad_fwd: bad shape/ld");
   NVIT_REQUIRE(dt == NVIT_F32 || dt == NVIT_BF16_F32IN, "heads_pad_fwd: dt %d (fp32 projections in: F32 or BF16_F32IN)", dt);
   NVIT_REQUIRE(q && k && v && qh && kh && vh && (!sqk || (rq && rk)), "heads_pad_fwd: missing pointer");
-  PadSplitArgs a{q, k, v, ldq, ldk, ldv, sqk, c_q, qh, kh, vh, rq, rk, sqk_pad, B, T, H, d};
   hipStream_t s = (hipStream_t)stream;
   ProfScope ps(NVIT_KID_ROWOPS, 0.0, (double)B * T * 3.0 * (C * 4.0 + H * dp * (dt == NVIT_F32 ? 4.0 : 2.0)), s);
-  const auto kernel = with_bool(sqk != nullptr, [&](auto norm) {
-    return with_elem(dt, [&](auto to) { return &heads_pad_fwd_kernel<tag_t<decltype(to)>, norm>; });
-  });
-  launch(kernel, dim3(row_grid(B * T)), dim3(256), 0, s, a);
+  heads_split_launch(dt, QkArgs{q, k, v, ldq, ldk, ldv, sqk, c_q, qh, kh, vh, rq, rk, sqk_pad, B, T, H, d}, dp, s);
   NVIT_CHECK_LAUNCH("heads_pad_fwd");
   return NVIT_OK;
 }
@@ -1413,21 +1373,15 @@ extern "C" int nvit_heads_pad_bwd(int dt, const void* dqh, const void* dkh, cons
                "heads_pad_bwd: bad shape/ld");
   NVIT_REQUIRE(dt == NVIT_F32 || dt == NVIT_BF16, "heads_pad_bwd: bad dt %d", dt);
   NVIT_REQUIRE(dqh && dkh && dvh && dq && dk && dv, "heads_pad_bwd: missing pointer");
-  QkBwdArgs a{dqh, dkh, dvh, qh, kh, rq, rk, sqk, c_q, dq, dk, dv, ldq, ldk, ldv, part_dsqk, B, T, H, d};
+  if (sqk) {   // (the head merge alone uses no qh, kh, rq, rk, part_dsqk or nblk)
+    NVIT_REQUIRE(qh && kh && rq && rk && part_dsqk, "heads_pad_bwd: missing pointer");
+    NVIT_REQUIRE(nblk > 0 && nblk <= 4096, "heads_pad_bwd: nblk out of range");
+  }
   hipStream_t s = (hipStream_t)stream;
   const double eb = dt == NVIT_F32 ? 4.0 : 2.0;
-  if (!sqk) {   // the head merge alone (qh, kh, rq, rk, part_dsqk and nblk are not used)
-    ProfScope ps(NVIT_KID_ROWOPS, 0.0, (double)B * T * C * 6.0 * eb, s);
-    const auto kernel = with_elem(dt, [&](auto t) { return &heads_pad_bwd_kernel<tag_t<decltype(t)>, false>; });
-    launch(kernel, dim3(row_grid(B * T)), dim3(256), 0, s, a);
-    NVIT_CHECK_LAUNCH("heads_pad_bwd");
-    return NVIT_OK;
-  }
-  NVIT_REQUIRE(qh && kh && rq && rk && part_dsqk, "heads_pad_bwd: missing pointer");
-  NVIT_REQUIRE(nblk > 0 && nblk <= 4096, "heads_pad_bwd: nblk out of range");
-  ProfScope ps(NVIT_KID_ROWOPS, 0.0, (double)B * T * C * 8.0 * eb, s);
-  const auto kernel = with_elem(dt, [&](auto t) { return &heads_pad_bwd_kernel<tag_t<decltype(t)>, true>; });
-  launch(kernel, dim3(nblk), dim3(256), (size_t)ROW_WAVES * C * sizeof(float), s, a);
+  ProfScope ps(NVIT_KID_ROWOPS, 0.0, (double)B * T * C * (sqk ? 8.0 : 6.0) * eb, s);
+  heads_merge_launch(dt, QkBwdArgs{dqh, dkh, dvh, qh, kh, rq, rk, sqk, c_q, dq, dk, dv, ldq, ldk, ldv, part_dsqk, B, T, H, d},
+                     dp, nblk, s);
   NVIT_CHECK_LAUNCH("heads_pad_bwd");
   return NVIT_OK;
 }

@@ -37,7 +37,7 @@ from .kohonen import CosConsistencyFn, HuberFn, KohonenMap, MapSmoothnessFn
 
 Tensor = torch.Tensor
 HEAD_DIMS = (32, 64, 128)   # attention head dims n_embd // n_head the kernels cover
-# head dims that run on the 128-wide kernels with head tensors whose columns d..127 are stored zeros (_attn_fwd, "padded")
+# head dims that run on the 128-wide kernels with head tensors whose columns d..127 are stored zeros (_attn_fwd, "split")
 PADDED_HEAD_DIMS = (72, 80, 88, 104)
 
 
@@ -303,7 +303,7 @@ def _attn_fwd(rt: _Runtime, impl: int, srcs, sqk: Optional[Tensor], c_q: float, 
               lean: bool = False):
     """The attention of every block function, from its q/k/v projection sources to O [M, C] (the output projection's A
     operand).  srcs: ((A, shadow prefix, parts), ...), one projection GEMM each, their output columns q | k | v in
-    order.  sqk None (c_q 0.0): plain-ViT heads, else the nViT normalise + sqk scale.  One of four routes:
+    order.  sqk None (c_q 0.0): plain-ViT heads, else the nViT normalise + sqk scale.  One of three routes:
       heads  flash_attn=True: the reference's flash_attn_func reads its [B,H,T,d] arguments as [batch, seqlen, nheads,
              headdim], so the softmax runs over the H heads of each token of the fp32 token-major
              projections;
@@ -311,11 +311,11 @@ def _attn_fwd(rt: _Runtime, impl: int, srcs, sqk: Optional[Tensor], c_q: float, 
              bias (if any), the normalise (nViT) and the head split in the projection GEMM's epilogue, q pre-scaled so
              that the attention kernels' exponent needs no multiply;
       split  otherwise (small problems: 128x128 GEMM kernel): the projections leave the GEMM in fp32 and are normalised
-             from the unrounded values, like the fused epilogue (one rounding, at the head tensors);
-      padded d in PADDED_HEAD_DIMS: the split route into head tensors [B,H,T,128] whose columns d..127 are stored zeros
-             (heads_pad_fwd, which also pads sqk for the score bound): the attention kernels run at head dim 128 with
-             the scale of the real d, and O [M, H*128] is compacted to [M, C].  Zero columns change no score, no output
-             column < d and no gradient column < d.
+             from the unrounded values, like the fused epilogue (one rounding, at the head tensors).  The head tensors
+             are [B,H,T,dp]: dp = d, or for d in PADDED_HEAD_DIMS dp = 128 with columns d..127 stored zeros
+             (heads_pad_fwd, which also pads sqk for the score bound): the attention kernels then run at head dim 128
+             with the scale of the real d, and O [M, H*128] is compacted to [M, C].  Zero columns change no score, no
+             output column < d and no gradient column < d.
     -> o, lse, att (route, impl, q pre-scale, scale) for _attn_bwd, and the tensors it reads: the fp32 projections
     (heads) or qh, kh, vh, rq, rk.
     lean (a forward no backward follows): the same launches - no attention kernel takes a NULL lse, rq or rk, so those
@@ -324,16 +324,8 @@ def _attn_fwd(rt: _Runtime, impl: int, srcs, sqk: Optional[Tensor], c_q: float, 
     B, T, C, H, d, M = dims
     dt, sh = rt.dt, rt.sh
     heads = rt.model.config.flash_attn
-    if d in PADDED_HEAD_DIMS:   # (never with flash_attn: refused at construction)
-        projs = [ops.gemm_nt(A, sh[w + ".W"], M, n * C, C, out_dtype=torch.float32, bias=sh.get(w + ".b"))
-                 for A, w, n in srcs]
-        q, ldq, k, v, ldkv = _qkv_cols(projs, C)
-        qh, kh, vh, rq, rk, sqk_p = ops.heads_pad_fwd(dt if dt == F32 else BF16_F32IN, q, ldq, k, ldkv, v, ldkv, sqk,
-                                                      c_q, B, T, H, d)
-        del projs, q, k, v
-        o_p, lse = ops.attn_fwd(dt, impl, qh, kh, vh, scale, sqk_p, c_q)
-        o = ops.unpad_cols(o_p, M, H, d)
-        return o, lse, ("padded", impl, 1.0, scale), (() if lean else (qh, kh, vh, rq, rk))
+    dp = ops.PAD_HEAD_DIM if d in PADDED_HEAD_DIMS else d   # (padded never with flash_attn: refused at construction)
+    sqk_a = sqk   # as the attention kernel's score bound reads it
     if not heads and impl == 1 and d == 64 and C % 256 == 0 and ops.fusable(dt, M, srcs[0][2] * C, C):
         route = "fused"
         # the softmax scale (nViT: sqrt(d) on unit q, k) times log2(e); with sqk absent the running-maximum kernel runs
@@ -354,12 +346,18 @@ def _attn_fwd(rt: _Runtime, impl: int, srcs, sqk: Optional[Tensor], c_q: float, 
             return o, lse, ("heads", impl, 1.0, scale), (() if lean else tuple(projs))
         route, qpre = "split", 1.0
         dt_in = dt if dt == F32 else BF16_F32IN   # the projection outputs are fp32 in both modes
-        bufs = ops.qknorm_fwd(dt_in, q, ldq, k, ldkv, v, ldkv, sqk, c_q, B, T, H, d)
-        if sqk is None:   # plain heads free the projections before O is allocated, nViT after attn_fwd (at return)
+        if dp != d:
+            *bufs, sqk_a = ops.heads_pad_fwd(dt_in, q, ldq, k, ldkv, v, ldkv, sqk, c_q, B, T, H, d)
+        else:
+            bufs = ops.qknorm_fwd(dt_in, q, ldq, k, ldkv, v, ldkv, sqk, c_q, B, T, H, d)
+        # plain and padded heads free the projections before O is allocated, compact nViT after attn_fwd (at return)
+        if sqk is None or dp != d:
             del projs, q, k, v
     qh, kh, vh, _, _ = bufs
-    o, lse = ops.attn_fwd(dt, impl, qh, kh, vh, scale, sqk, c_q, q_prescale=qpre)
-    return o, lse, (route, impl, qpre, scale), (() if lean else bufs)
+    o, lse = ops.attn_fwd(dt, impl, qh, kh, vh, scale, sqk_a, c_q, q_prescale=qpre)
+    if dp != d:
+        o = ops.unpad_cols(o, M, H, d)
+    return o, lse, (route, impl, qpre, scale), (() if lean else tuple(bufs))
 
 
 def _attn_bwd(rt: _Runtime, att, saved, do: Tensor, o: Tensor, lse: Tensor, grads, sqk: Optional[Tensor], c_q: float,
@@ -376,23 +374,22 @@ def _attn_bwd(rt: _Runtime, att, saved, do: Tensor, o: Tensor, lse: Tensor, grad
         return ops.attn_heads_bwd(dt, do, q, ldq, k, v, ldkv, sqk, c_q, scale, lse, dq, lddq, dk, dv, lddkv, M, H,
                                   d), None
     qh, kh, vh, rq, rk = saved
-    if route == "padded":
-        # dO and O zero-padded to the head tensors' width (the dQ kernel's delta = rowsum(dO*O) runs over all 128
-        # columns; the padded O is rebuilt from the compact one, not kept from the forward), attn_bwd at 128, then the
-        # merge, which reads the first d columns of each gradient only
-        do_p, o_p = ops.pad_cols(do, M, H, d), ops.pad_cols(o, M, H, d)
-        dqh, dkh, dvh = ops.attn_bwd(dt, impl, do_p, qh, kh, vh, o_p, lse, scale)
-        del do_p, o_p
-        return ops.heads_pad_bwd(dt, dqh, dkh, dvh, qh, kh, rq, rk, sqk, c_q, dq, lddq, dk, lddkv, dv, lddkv, B, T, H,
-                                 d), None
     # attention backward with the q/k-normalise backward (nViT) fused into its epilogues, dq/dk/dv stored token-major:
     # nViT after either forward route (the split one leaves q unscaled, qpre 1); plain heads after the fused one only
     fused_bwd = (dt != F32 and d == 64) if sqk is not None else route == "fused"
     if fused_bwd:
         return ops.attn_bwd_qknorm(do, qh, kh, vh, o, lse, scale, rq, rk, sqk, c_q, dq, lddq, dk, dv, lddkv,
                                    q_prescale=qpre)
+    dp = ops.PAD_HEAD_DIM if d in PADDED_HEAD_DIMS else d
+    if dp != d:
+        # dO and O zero-padded to the head tensors' width (the dQ kernel's delta = rowsum(dO*O) runs over all 128
+        # columns; the padded O is rebuilt from the compact one, not kept from the forward), attn_bwd at 128, then the
+        # merge, which reads the first d columns of each gradient only
+        do, o = ops.pad_cols(do, M, H, d), ops.pad_cols(o, M, H, d)
     dqh, dkh, dvh = ops.attn_bwd(dt, impl, do, qh, kh, vh, o, lse, scale)
-    return ops.qknorm_bwd(dt, dqh, dkh, dvh, qh, kh, rq, rk, sqk, c_q, dq, lddq, dk, lddkv, dv, lddkv, B, T, H, d), None
+    del do, o   # (padded: the two copies are released before the merge)
+    merge = ops.heads_pad_bwd if dp != d else ops.qknorm_bwd
+    return merge(dt, dqh, dkh, dvh, qh, kh, rq, rk, sqk, c_q, dq, lddq, dk, lddkv, dv, lddkv, B, T, H, d), None
 
 
 def _swiglu_fwd(rt: _Runtime, A: Tensor, w: str, M: int, F: int, K: int, gs: Optional[Tensor],

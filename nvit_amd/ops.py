@@ -408,35 +408,6 @@ def norm_skip_bwd(dout: Tensor, src: Tensor, tgt: Optional[Tensor], skip: Tensor
     return dsrc, dtgt, dskip
 
 
-def qknorm_fwd(dt: int, q: Tensor, ldq: int, k: Tensor, ldk: int, v: Tensor, ldv: int, sqk: Optional[Tensor], c_q: float,
-               B: int, T: int, H: int, d: int):
-    """sqk None: the head split alone (plain-ViT attention); rq, rk are then None."""
-    dev = q.device
-    td = tdtype(BF16 if dt == _lib.BF16_F32IN else dt)   # BF16_F32IN: fp32 projection outputs in, bf16 head tensors out
-    qh = torch.empty((B, H, T, d), device=dev, dtype=td)
-    kh = torch.empty_like(qh)
-    vh = torch.empty_like(qh)
-    if sqk is not None:
-        rq = torch.empty((B * T, H), device=dev, dtype=torch.float32)
-        rk = torch.empty_like(rq)
-    else:
-        rq = rk = None
-    check(_lib.load().nvit_qknorm_fwd(dt, _p(q), ldq, _p(k), ldk, _p(v), ldv, _p(sqk), c_q, _p(qh), _p(kh), _p(vh),
-                                      _p(rq), _p(rk), B, T, H, d, _s()), "nvit_qknorm_fwd")
-    return qh, kh, vh, rq, rk
-
-
-def qknorm_bwd(dt: int, dqh, dkh, dvh, qh, kh, rq, rk, sqk, c_q: float, dq: Tensor, ldq: int, dk: Tensor, ldk: int,
-               dv: Tensor, ldv: int, B: int, T: int, H: int, d: int, *, nblk: Optional[int] = None) -> Optional[Tensor]:
-    """sqk None: the head merge alone (backward of the plain split); returns None instead of the d(sqk) partials."""
-    nblk = _part_blocks(nblk, min(PART_BLOCKS, math.ceil(B * T / 4)), "qknorm_bwd")
-    part = torch.empty((nblk, H * d), device=dq.device, dtype=torch.float32) if sqk is not None else None
-    check(_lib.load().nvit_qknorm_bwd(dt, _p(dqh), _p(dkh), _p(dvh), _p(qh), _p(kh), _p(rq), _p(rk), _p(sqk), c_q,
-                                      _p(dq), ldq, _p(dk), ldk, _p(dv), ldv, _p(part), nblk, B, T, H, d, _s()),
-          "nvit_qknorm_bwd")
-    return part
-
-
 PAD_HEAD_DIM = 128   # dp: the attention head dim the zero-padded head tensors run at (include/nvit_hip.h)
 
 
@@ -450,6 +421,44 @@ def _pad_out(out, shape, dtype, device, name: str) -> Tensor:
     return out
 
 
+def _heads_split(name: str, dp: int, dt: int, q, ldq, k, ldk, v, ldv, sqk, c_q, B, T, H, d, out, mid=(), post=()):
+    """nvit_<name>: the head split (+ q/k normalise when sqk is given) into head tensors [B,H,T,dp] (out: optional buffers,
+    or None).  mid / post: what this entry point takes before B and behind d.  -> qh, kh, vh, rq, rk."""
+    dev = q.device
+    td = tdtype(BF16 if dt == _lib.BF16_F32IN else dt)   # BF16_F32IN: fp32 projection outputs in, bf16 head tensors out
+    o = tuple(out) if out is not None else (None,) * 5
+    qh, kh, vh = (_pad_out(o[i], (B, H, T, dp), td, dev, name) for i in range(3))
+    rq, rk = (_pad_out(o[i], (B * T, H), torch.float32, dev, name) for i in (3, 4)) if sqk is not None else (None, None)
+    check(getattr(_lib.load(), "nvit_" + name)(dt, _p(q), ldq, _p(k), ldk, _p(v), ldv, _p(sqk), c_q, _p(qh), _p(kh), _p(vh),
+                                               _p(rq), _p(rk), *mid, B, T, H, d, *post, _s()), "nvit_" + name)
+    return qh, kh, vh, rq, rk
+
+
+def _heads_merge(name: str, dt: int, dqh, dkh, dvh, qh, kh, rq, rk, sqk, c_q, dq, ldq, dk, ldk, dv, ldv, B, T, H, d, nblk,
+                 out, post=()) -> Optional[Tensor]:
+    """nvit_<name>: the backward of _heads_split into token-major dq/dk/dv (type dt) -> the d(sqk*c_q) partials
+    [nblk, H*d] (out: optional buffer), or None for the head merge alone (sqk None).  post: what it takes behind d."""
+    nblk = _part_blocks(nblk, min(PART_BLOCKS, math.ceil(B * T / 4)), name)
+    part = _pad_out(out, (nblk, H * d), torch.float32, dq.device, name) if sqk is not None else None
+    check(getattr(_lib.load(), "nvit_" + name)(dt, _p(dqh), _p(dkh), _p(dvh), _p(qh), _p(kh), _p(rq), _p(rk), _p(sqk), c_q,
+                                               _p(dq), ldq, _p(dk), ldk, _p(dv), ldv, _p(part), nblk, B, T, H, d, *post,
+                                               _s()), "nvit_" + name)
+    return part
+
+
+def qknorm_fwd(dt: int, q: Tensor, ldq: int, k: Tensor, ldk: int, v: Tensor, ldv: int, sqk: Optional[Tensor], c_q: float,
+               B: int, T: int, H: int, d: int):
+    """sqk None: the head split alone (plain-ViT attention); rq, rk are then None."""
+    return _heads_split("qknorm_fwd", d, dt, q, ldq, k, ldk, v, ldv, sqk, c_q, B, T, H, d, None)
+
+
+def qknorm_bwd(dt: int, dqh, dkh, dvh, qh, kh, rq, rk, sqk, c_q: float, dq: Tensor, ldq: int, dk: Tensor, ldk: int,
+               dv: Tensor, ldv: int, B: int, T: int, H: int, d: int, *, nblk: Optional[int] = None) -> Optional[Tensor]:
+    """sqk None: the head merge alone (backward of the plain split); returns None instead of the d(sqk) partials."""
+    return _heads_merge("qknorm_bwd", dt, dqh, dkh, dvh, qh, kh, rq, rk, sqk, c_q, dq, ldq, dk, ldk, dv, ldv, B, T, H, d,
+                        nblk, None)
+
+
 def heads_pad_fwd(dt: int, q: Tensor, ldq: int, k: Tensor, ldk: int, v: Tensor, ldv: int, sqk: Optional[Tensor],
                   c_q: float, B: int, T: int, H: int, d: int, *, out=None):
     """qknorm_fwd from fp32 projections (dt F32 or BF16_F32IN) into zero-padded head tensors [B,H,T,PAD_HEAD_DIM]: every
@@ -458,21 +467,11 @@ def heads_pad_fwd(dt: int, q: Tensor, ldq: int, k: Tensor, ldk: int, v: Tensor, 
     _chk_dev(q, k, v, sqk)
     if q.dtype != torch.float32 or k.dtype != torch.float32 or v.dtype != torch.float32:
         raise TypeError("heads_pad_fwd: the projections are fp32")
-    dev, dp = q.device, PAD_HEAD_DIM
-    td = tdtype(BF16 if dt == _lib.BF16_F32IN else dt)
+    dp = PAD_HEAD_DIM
     o = tuple(out) if out is not None else (None,) * 6
-    qh = _pad_out(o[0], (B, H, T, dp), td, dev, "heads_pad_fwd")
-    kh = _pad_out(o[1], (B, H, T, dp), td, dev, "heads_pad_fwd")
-    vh = _pad_out(o[2], (B, H, T, dp), td, dev, "heads_pad_fwd")
-    if sqk is not None:
-        rq = _pad_out(o[3], (B * T, H), torch.float32, dev, "heads_pad_fwd")
-        rk = _pad_out(o[4], (B * T, H), torch.float32, dev, "heads_pad_fwd")
-        sqk_pad = _pad_out(o[5], (H * dp,), torch.float32, dev, "heads_pad_fwd")
-    else:
-        rq = rk = sqk_pad = None
-    check(_lib.load().nvit_heads_pad_fwd(dt, _p(q), ldq, _p(k), ldk, _p(v), ldv, _p(sqk), c_q, _p(qh), _p(kh), _p(vh),
-                                         _p(rq), _p(rk), _p(sqk_pad), B, T, H, d, dp, _s()), "nvit_heads_pad_fwd")
-    return qh, kh, vh, rq, rk, sqk_pad
+    sqk_pad = _pad_out(o[5], (H * dp,), torch.float32, q.device, "heads_pad_fwd") if sqk is not None else None
+    return (*_heads_split("heads_pad_fwd", dp, dt, q, ldq, k, ldk, v, ldv, sqk, c_q, B, T, H, d, o, (_p(sqk_pad),), (dp,)),
+            sqk_pad)
 
 
 def heads_pad_bwd(dt: int, dqh, dkh, dvh, qh, kh, rq, rk, sqk, c_q: float, dq: Tensor, ldq: int, dk: Tensor, ldk: int,
@@ -482,12 +481,8 @@ def heads_pad_bwd(dt: int, dqh, dkh, dvh, qh, kh, rq, rk, sqk, c_q: float, dq: T
     (type dt) -> the d(sqk*c_q) partials [nblk, H*d] in compact channel order (out: optional buffer for them); sqk None:
     the head merge alone, returns None."""
     _chk_dev(dqh, dkh, dvh, dq, dk, dv)
-    nblk = _part_blocks(nblk, min(PART_BLOCKS, math.ceil(B * T / 4)), "heads_pad_bwd")
-    part = _pad_out(out, (nblk, H * d), torch.float32, dq.device, "heads_pad_bwd") if sqk is not None else None
-    check(_lib.load().nvit_heads_pad_bwd(dt, _p(dqh), _p(dkh), _p(dvh), _p(qh), _p(kh), _p(rq), _p(rk), _p(sqk), c_q,
-                                         _p(dq), ldq, _p(dk), ldk, _p(dv), ldv, _p(part), nblk, B, T, H, d,
-                                         PAD_HEAD_DIM, _s()), "nvit_heads_pad_bwd")
-    return part
+    return _heads_merge("heads_pad_bwd", dt, dqh, dkh, dvh, qh, kh, rq, rk, sqk, c_q, dq, ldq, dk, ldk, dv, ldv, B, T, H, d,
+                        nblk, out, (PAD_HEAD_DIM,))
 
 
 def pad_cols(src: Tensor, M: int, H: int, d: int, *, out: Optional[Tensor] = None) -> Tensor:

@@ -43,7 +43,7 @@ MULTI = (37, 3)                         # (M, nblk): 12 waves, 3 or 4 rows per w
 MULTI_WIDTHS = [260, 1028]
 ONE_BLOCK = (9, 1)                      # (M, nblk): 4 waves, 2 or 3 rows per wave
 STRIDE_M, STRIDE_C = 8197, 64           # forward grids cap at 2048 workgroups of 4 rows: 8192 rows per sweep
-QK_HEADS = [(1, 16), (3, 16), (2, 32), (12, 64), (5, 128), (16, 128)]
+QK_HEADS = [(1, 16), (3, 16), (2, 32), (5, 64), (12, 64), (5, 128), (16, 128)]   # (5, 64): a partly filled second pass
 QK_BT = (2, 19)
 QK_MULTI = (5, 128)
 QK_STRIDE = (1, 8197, 2, 32)            # (B, T, H, d)

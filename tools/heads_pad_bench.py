@@ -1,7 +1,7 @@
 """The zero-padded-head row kernels at the ViT-H shape (M = 64 x 784 = 50 176 rows, C = 1280 = 16 heads of 80, bf16 mode)
-next to the kernels they stand in for at C = 2048 = 16 heads of 128, in one process: HIP-event times and algorithmic TB/s
-(the bytes the operation needs: the real columns read, every stored column written, pads included).
-python tools/heads_pad_bench.py"""
+next to the same kernels on compact heads (16 heads of 32, 64 and 128), in one process: HIP-event times and algorithmic
+TB/s (the bytes the operation needs: the real columns read, every stored column written, pads included).
+python tools/heads_pad_bench.py     (A/B against another build of the library: NVIT_LIB, as tools/rowops_ab.sh does)"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -70,10 +70,16 @@ def plain(d):
     print(f"qknorm, d = {d} (C = {C}), M = {M}:")
     report("qknorm_fwd (normalise)    ", lambda: ops.qknorm_fwd(BF16_F32IN, qkv, 3 * C, qkv[:, C:], 3 * C, qkv[:, 2 * C:], 3 * C,
                                                                 sqk, 32.0, B, T, H, d), M * C * 18 + small)
+    report("qknorm_fwd (split only)   ", lambda: ops.qknorm_fwd(BF16_F32IN, qkv, 3 * C, qkv[:, C:], 3 * C, qkv[:, 2 * C:], 3 * C,
+                                                                None, 0.0, B, T, H, d), M * C * 18)
     report("qknorm_bwd (normalise)    ", lambda: ops.qknorm_bwd(BF16, gh[0], gh[1], gh[2], qh, kh, rq, rk, sqk, 32.0, dqkv, 3 * C,
                                                                 dqkv[:, C:], 3 * C, dqkv[:, 2 * C:], 3 * C, B, T, H, d),
            M * C * 16 + small)
+    report("qknorm_bwd (merge only)   ", lambda: ops.qknorm_bwd(BF16, gh[0], gh[1], gh[2], None, None, None, None, None, 0.0,
+                                                                dqkv, 3 * C, dqkv[:, C:], 3 * C, dqkv[:, 2 * C:], 3 * C, B, T,
+                                                                H, d), M * C * 12)
 
 
 padded(80)
-plain(128)
+for d in (32, 64, 128):
+    plain(d)
