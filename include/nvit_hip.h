@@ -330,9 +330,25 @@ int nvit_colsum(const void* a, int a_dt, int lda, const void* b, int b_dt, int l
 int nvit_cast(const float* src, void* dst, int dt, int64_t n, void* stream);
 /* Input pipeline, deterministic part (train.py:1084-1090): ToTensor + kornia Normalize(mean, std) in one pass.
  * in: uint8 [B,H,W,C] (in_is_u8_hwc = 1; scaled by 1/255 first) or fp32 [B,C,H,W] already in [0,1]; out fp32 [B,C,H,W]
- * = (in - mean) / std.  (The reference's randomised AutoAugment policy is third-party kornia code: not rebuilt.) */
+ * = (in - mean) / std.  (The randomised half of that pipeline: nvit_augment_draw / nvit_augment_apply below.) */
 int nvit_normalize_images(const void* in, int in_is_u8_hwc, float* out, int B, int C, int H, int W, float mean, float std_,
                           void* stream);
+/* On-device AutoAugment: the randomised half of the input pipeline, two launches per batch, no host
+ * synchronisation, capturable in a hipGraph.  The ops are Pillow's, bit for bit (tests/augment_ref.py).
+ * nvit_augment_draw: params int32 [B,2,8] = per image two ops, each (op id, seven arguments).  One Philox4x32-10 call per
+ * image, key = seed, counter = (first_index + i, *step): r0 picks one of the P sub-policies, r1/r2 gate its two ops
+ * against their probabilities (an op left out becomes Identity), bits 0/1 of r3 are their signs.  policy: device int32
+ * [P,2,3] = (op id, probability as fp32 bits, magnitude index 0..9); argtab: device int32 [15,10,2,8], the parameter row
+ * of every (op, magnitude index, sign) at this image size (the host computes it in fp64).  *step is a device int64 that
+ * the kernel reads and then advances by one, so a graph replay draws fresh parameters. */
+int nvit_augment_draw(const int* policy, int P, uint64_t seed, int64_t* step, int64_t first_index, const int* argtab,
+                      int* params, int B, void* stream);
+/* nvit_augment_apply: in uint8 [B,H,W,C], C in {1,3}; per image the two ops of params in sequence, the second on the
+ * complete result of the first.  out_f32 (may be NULL): fp32 [B,C,H,W] = (x/255 - mean) / std with the arithmetic of
+ * nvit_normalize_images (needs W % 4 == 0); out_u8 (may be NULL): the augmented uint8 [B,H,W,C].  ws: caller-provided
+ * workspace of ws_bytes >= 2 * B * round_up(H*W*C, 256) bytes. */
+int nvit_augment_apply(const void* in, const int* params, float* out_f32, void* out_u8, void* ws, int64_t ws_bytes, int B,
+                       int H, int W, int C, float mean, float std_, void* stream);
 /* out[r,n] = a[r,n] * s[n] * c   (sz scaling model.py:466-468 and its backward); s == NULL: out = a * c */
 int nvit_scale_cols(const float* a, int lda, const float* s, float c, void* out, int out_dt, int ldo, int R, int N,
                     void* stream);

@@ -13,6 +13,9 @@ def __getattr__(name):
     if name in ("predict", "validate", "estimate_loss", "GraphedEval"):
         from . import evaluate
         return getattr(evaluate, name)
+    if name in ("AutoAugment", "AugmentedBatch"):
+        from . import augment
+        return getattr(augment, name)
     if name == "FusedAdamW":
         from . import optim
         return optim.FusedAdamW

@@ -1,0 +1,318 @@
+// On-device AutoAugment input pipeline: uint8 [B,H,W,C] batch in, the model's fp32 [B,C,H,W] input
+// out, in two launches that a hipGraph can capture.
+//
+//   nvit_augment_draw   one workgroup: Philox4x32-10 per image -> int32 [B,2,8] parameter table (op id + 7 arguments);
+//                       the step counter is a device int64 that the kernel itself advances.
+//   nvit_augment_apply  one workgroup per image: the two ops in sequence, then ToTensor + Normalize with exactly
+//                       nvit_normalize_images' arithmetic.
+//
+// The ops are Pillow's (the AutoAugment paper's released code), restated in integers and contraction-free fp32/fp64 so
+// that the result is bit-identical to Pillow's: tests/augment_ref.py is the numpy twin, tests/golden/augment_pil.npz the
+// Pillow fixture.  Everything that depends on the whole image goes through one mechanism: a per-channel 256-bin
+// histogram in LDS (gray mean of Contrast, min/max of AutoContrast, the cumulative table of Equalize), from which a
+// 256-entry per-channel lookup table is built; the pointwise ops build the same table without the histogram.  Only the
+// affine ops, Color (needs the pixel's three channels) and Sharpness (3x3 stencil) read the image directly.
+// An op reads one complete image and writes another: the intermediate images live in a caller-provided global workspace
+// (two per image, each used by this workgroup only, so they stay in L2), which makes one code path for every image size.
+#include "common.h"
+
+// a fused a + f*b changes truncations by one level: nothing in this file contracts, except normalize4 below.  (Plain
+// operators on purpose: the __fmul_rn/__fadd_rn of the HIP headers are inline a*b / a+b compiled under the headers' own
+// default contraction, and the compiler does fuse a pair of them.)
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int AUG_THREADS = 1024;
+constexpr int AUG_HIST_COPIES = 4;   // waves spread over four histogram copies: a low-contrast image hits few bins
+constexpr int AUG_ROW = 8;           // ints per op in the parameter table
+constexpr int AUG_NOPS = 15;
+constexpr int AUG_NMAG = 10;
+
+enum AugOp { OP_IDENTITY = 0, OP_SHEAR_X, OP_SHEAR_Y, OP_TRANSLATE_X, OP_TRANSLATE_Y, OP_ROTATE, OP_BRIGHTNESS, OP_COLOR,
+             OP_CONTRAST, OP_SHARPNESS, OP_POSTERIZE, OP_SOLARIZE, OP_AUTOCONTRAST, OP_EQUALIZE, OP_INVERT };
+
+// ------------------------------------------------------------------------------------------------ Philox4x32-10
+struct Philox4 {
+  unsigned v[4];
+};
+__device__ __forceinline__ Philox4 philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0,
+                                                 unsigned k1) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
+    const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1;
+    c1 = (unsigned)p1;
+    c3 = (unsigned)p0;
+    c0 = n0;
+    c2 = n2;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  return Philox4{{c0, c1, c2, c3}};
+}
+
+// policy: int32 [P,2,3] = (op, probability as fp32 bits, magnitude index); argtab: int32 [15,10,2,8], the parameter row
+// of every (op, magnitude index, sign) for this image size, computed by the host in fp64.
+__global__ __launch_bounds__(256) void augment_draw_kernel(const int* __restrict__ policy, int P,
+                                                           unsigned long long seed, long long* step_ctr,
+                                                           long long first_index, const int* __restrict__ argtab,
+                                                           int* __restrict__ params, int B) {
+  const unsigned long long step = (unsigned long long)*step_ctr;
+  for (int i = threadIdx.x; i < B; i += blockDim.x) {
+    const unsigned long long g = (unsigned long long)(first_index + i);
+    const Philox4 r = philox4x32_10((unsigned)g, (unsigned)(g >> 32), (unsigned)step, (unsigned)(step >> 32),
+                                    (unsigned)seed, (unsigned)(seed >> 32));
+    const int sub = (int)(((unsigned long long)r.v[0] * (unsigned long long)P) >> 32);
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const int* e = policy + (sub * 2 + k) * 3;
+      const float u = (float)(r.v[1 + k] >> 8) * 0x1p-24f;   // exact: 24 bits
+      const bool on = u < __int_as_float(e[1]);
+      const int sign = (r.v[3] >> k) & 1;
+      const int* src = argtab + ((e[0] * AUG_NMAG + e[2]) * 2 + sign) * AUG_ROW;
+      int* dst = params + ((size_t)i * 2 + k) * AUG_ROW;
+#pragma unroll
+      for (int j = 0; j < AUG_ROW; ++j) dst[j] = on ? src[j] : 0;   // off: Identity
+    }
+  }
+  __syncthreads();   // every thread has read the counter
+  if (threadIdx.x == 0) *step_ctr = (long long)(step + 1);
+}
+
+// ------------------------------------------------------------------------------------------------ the ops
+__device__ __forceinline__ int gray_of(int r, int g, int b) { return (19595 * r + 38470 * g + 7471 * b + 0x8000) >> 16; }
+
+// (uint8) clamp(deg + f * (x - deg), 0, 255): fp32, multiply then add, truncating (Pillow's ImagingBlend)
+__device__ __forceinline__ unsigned char blend(int deg, int x, float f) {
+  const float t = (float)deg + f * (float)(x - deg);   // two roundings (file-wide contract(off))
+  return (unsigned char)(t <= 0.f ? 0 : (t >= 255.f ? 255 : (int)t));
+}
+
+struct AugShared {
+  unsigned hist[AUG_HIST_COPIES][3][256];
+  unsigned char lut[3][256];
+  int lo[3], hi[3];
+  int mean;
+};
+
+// Per-channel histograms of src into sh.hist[0] (channel 0 holds the gray histogram when `of_gray`).
+__device__ void histogram(AugShared& sh, const unsigned char* src, int N, int C, bool of_gray) {
+  unsigned* h = &sh.hist[0][0][0];
+  for (int i = threadIdx.x; i < AUG_HIST_COPIES * 3 * 256; i += AUG_THREADS) h[i] = 0;
+  __syncthreads();
+  unsigned(*mine)[256] = sh.hist[(threadIdx.x >> 6) & (AUG_HIST_COPIES - 1)];
+  if (of_gray) {
+    for (int p = threadIdx.x; p < N; p += AUG_THREADS) {
+      const unsigned char* q = src + (size_t)p * C;
+      atomicAdd(&mine[0][C == 3 ? gray_of(q[0], q[1], q[2]) : q[0]], 1u);
+    }
+  } else {
+    for (int i = threadIdx.x; i < N * C; i += AUG_THREADS) atomicAdd(&mine[i % C][src[i]], 1u);
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < 3 * 256; i += AUG_THREADS) {
+    unsigned s = h[i];
+#pragma unroll
+    for (int k = 1; k < AUG_HIST_COPIES; ++k) s += h[k * 3 * 256 + i];
+    h[i] = s;
+  }
+  __syncthreads();
+}
+
+// One op: src (complete image, uint8 HWC) -> dst.  id and a[] are uniform over the workgroup.
+__device__ void apply_op(AugShared& sh, const unsigned char* src, unsigned char* dst, int id, const int* a, int H, int W,
+                         int C) {
+  const int N = H * W;
+  const int tid = threadIdx.x;
+  if (id >= OP_SHEAR_X && id <= OP_ROTATE) {
+    // Pillow's affine_fixed: 16.16 output-to-input coefficients, nearest, fill 0
+    const int a0 = a[0], a1 = a[1], a2 = a[2], a3 = a[3], a4 = a[4], a5 = a[5];
+    for (int p = tid; p < N; p += AUG_THREADS) {
+      const int y = p / W, x = p - y * W;
+      const int xin = (a2 + a1 * y + a0 * x) >> 16, yin = (a5 + a4 * y + a3 * x) >> 16;
+      const bool ok = xin >= 0 && xin < W && yin >= 0 && yin < H;
+      const unsigned char* q = src + (ok ? (size_t)yin * W + xin : (size_t)0) * C;   // always inside the image
+      for (int c = 0; c < C; ++c) dst[(size_t)p * C + c] = ok ? q[c] : (unsigned char)0;
+    }
+    return;
+  }
+  const float f = __int_as_float(a[0]);
+  if (id == OP_COLOR) {
+    for (int p = tid; p < N; p += AUG_THREADS) {
+      const unsigned char* q = src + (size_t)p * C;
+      if (C == 3) {
+        const int r = q[0], g = q[1], b = q[2], gr = gray_of(r, g, b);
+        dst[(size_t)p * 3 + 0] = blend(gr, r, f);
+        dst[(size_t)p * 3 + 1] = blend(gr, g, f);
+        dst[(size_t)p * 3 + 2] = blend(gr, b, f);
+      } else {
+        dst[p] = q[0];   // the gray of a one-channel image is the channel itself
+      }
+    }
+    return;
+  }
+  if (id == OP_SHARPNESS) {
+    // Pillow's SMOOTH: (1,1,1,1,5,1,1,1,1)/13 rounded, border pixels unchanged
+    for (int i = tid; i < N * C; i += AUG_THREADS) {
+      const int p = i / C, c = i - p * C;
+      const int y = p / W, x = p - y * W;
+      const int v = src[i];
+      int deg = v;
+      if (y > 0 && y < H - 1 && x > 0 && x < W - 1) {
+        int acc = 4 * v;
+#pragma unroll
+        for (int dy = -1; dy <= 1; ++dy)
+#pragma unroll
+          for (int dx = -1; dx <= 1; ++dx) acc += src[((size_t)(y + dy) * W + (x + dx)) * C + c];
+        deg = (2 * acc + 13) / 26;
+      }
+      dst[i] = blend(deg, v, f);
+    }
+    return;
+  }
+  // ---- the rest is a per-channel lookup table
+  if (id == OP_CONTRAST || id == OP_AUTOCONTRAST || id == OP_EQUALIZE) {
+    histogram(sh, src, N, C, id == OP_CONTRAST);
+    if (id == OP_CONTRAST) {
+      if (tid == 0) {
+        unsigned long long s = 0;
+        for (int i = 0; i < 256; ++i) s += (unsigned long long)i * sh.hist[0][0][i];
+        sh.mean = (int)((2 * s + (unsigned long long)N) / (2ull * N));
+      }
+    } else if (tid < C) {
+      const unsigned* h = sh.hist[0][tid];
+      int lo = 256, hi = -1;
+      for (int i = 0; i < 256; ++i)
+        if (h[i]) {
+          if (lo == 256) lo = i;
+          hi = i;
+        }
+      sh.lo[tid] = lo;
+      sh.hi[tid] = hi;
+      if (id == OP_EQUALIZE) {
+        // Pillow's ImageOps.equalize: step from the histogram without its last occupied bin
+        const unsigned step = ((unsigned)N - h[hi]) / 255u;
+        unsigned n = step / 2;
+        for (int i = 0; i < 256; ++i) {
+          unsigned v = i;
+          if (step != 0 && hi > lo) {
+            v = n / step;
+            v = v > 255u ? 255u : v;
+          }
+          sh.lut[tid][i] = (unsigned char)v;
+          n += h[i];
+        }
+      }
+    }
+    __syncthreads();
+  }
+  if (id != OP_EQUALIZE) {
+    for (int t = tid; t < C * 256; t += AUG_THREADS) {
+      const int c = t >> 8, i = t & 255;
+      int v = i;
+      switch (id) {
+        case OP_BRIGHTNESS: v = blend(0, i, f); break;
+        case OP_CONTRAST: v = blend(sh.mean, i, f); break;
+        case OP_POSTERIZE: v = i & ~(0xFF >> a[0]); break;
+        case OP_SOLARIZE: v = i >= a[0] ? 255 - i : i; break;
+        case OP_INVERT: v = 255 - i; break;
+        case OP_AUTOCONTRAST: {
+          const int lo = sh.lo[c], hi = sh.hi[c];
+          if (hi > lo) {
+            // Pillow computes this table in Python floats (fp64)
+            const double scale = 255.0 / (double)(hi - lo);
+            const double off = (double)-lo * scale;
+            const double d = (double)i * scale + off;
+            v = d <= 0.0 ? 0 : (d >= 255.0 ? 255 : (int)d);
+          }
+          break;
+        }
+        default: break;
+      }
+      sh.lut[c][i] = (unsigned char)v;
+    }
+  }
+  __syncthreads();
+  for (int i = tid; i < N * C; i += AUG_THREADS) dst[i] = sh.lut[i % C][src[i]];
+}
+
+// ToTensor + Normalize of four pixels, written as nvit_normalize_images writes it (rowops.hip) and compiled, like it,
+// under the compiler's default contraction, so that the two give the same bits.
+__device__ __forceinline__ f32x4 normalize4(const unsigned char* p, int C, float mean, float inv_std) {
+#pragma clang fp contract(fast)
+  f32x4 v;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) v[e] = (float)p[(size_t)e * C] * (1.0f / 255.0f);
+  return (v - mean) * inv_std;
+}
+
+__global__ __launch_bounds__(AUG_THREADS) void augment_apply_kernel(const unsigned char* in,
+                                                                    const int* __restrict__ params, float* out_f32,
+                                                                    unsigned char* out_u8, unsigned char* ws,
+                                                                    size_t ws_stride, int B, int H, int W, int C, float mean,
+                                                                    float inv_std) {
+  __shared__ AugShared sh;
+  const int b = blockIdx.x;
+  const size_t n = (size_t)H * W * C;
+  const unsigned char* cur = in + (size_t)b * n;
+  unsigned char* buf[2] = {ws + (size_t)(2 * b) * ws_stride, ws + (size_t)(2 * b + 1) * ws_stride};
+  for (int k = 0; k < 2; ++k) {
+    const int* row = params + ((size_t)b * 2 + k) * AUG_ROW;
+    const int id = row[0];
+    if (id <= OP_IDENTITY || id >= AUG_NOPS) continue;   // Identity; ids come from the host's tables, which know no others
+    apply_op(sh, cur, buf[k], id, row + 1, H, W, C);
+    cur = buf[k];
+    __syncthreads();   // the op's stores are visible to the workgroup before the next pass reads them
+  }
+  if (out_u8) {
+    unsigned char* o = out_u8 + (size_t)b * n;
+    for (size_t i = threadIdx.x; i < n; i += AUG_THREADS) o[i] = cur[i];
+  }
+  if (out_f32) {
+    const int w4 = W / 4, n4 = C * H * w4;
+    for (int i = threadIdx.x; i < n4; i += AUG_THREADS) {
+      const int x4 = (i % w4) * 4;
+      int r = i / w4;
+      const int y = r % H, c = r / H;
+      *reinterpret_cast<f32x4*>(out_f32 + (((size_t)b * C + c) * H + y) * W + x4) =
+          normalize4(cur + ((size_t)y * W + x4) * C + c, C, mean, inv_std);
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" int nvit_augment_draw(const int* policy, int P, uint64_t seed, int64_t* step, int64_t first_index,
+                                 const int* argtab, int* params, int B, void* stream) {
+  NVIT_REQUIRE(policy && step && argtab && params && P > 0 && B > 0 && first_index >= 0,
+               "augment_draw: bad arguments");
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope ps(NVIT_KID_PATCHIFY, 0.0, (double)B * 2.0 * AUG_ROW * 4.0, s);
+  hipLaunchKernelGGL(augment_draw_kernel, dim3(1), dim3(256), 0, s, policy, P, (unsigned long long)seed,
+                     (long long*)step, (long long)first_index, argtab, params, B);
+  NVIT_CHECK_LAUNCH("augment_draw");
+  return NVIT_OK;
+}
+
+extern "C" int nvit_augment_apply(const void* in, const int* params, float* out_f32, void* out_u8, void* ws,
+                                  int64_t ws_bytes, int B, int H, int W, int C, float mean, float std_, void* stream) {
+  NVIT_REQUIRE(in && params && ws && (out_f32 || out_u8) && B > 0 && H > 0 && W > 0 && (C == 1 || C == 3),
+               "augment_apply: bad arguments (C must be 1 or 3)");
+  // 16.16 coordinates and the 32-bit histogram sums stay in range
+  NVIT_REQUIRE(H <= 4096 && W <= 4096, "augment_apply: images up to 4096 x 4096");
+  const size_t stride = ((size_t)H * W * C + 255) / 256 * 256;
+  NVIT_REQUIRE(ws_bytes >= 0 && (size_t)ws_bytes >= 2 * (size_t)B * stride,
+               "augment_apply: workspace needs 2 * B * round_up(H*W*C, 256) bytes");
+  if (out_f32) {
+    NVIT_REQUIRE(W % 4 == 0 && std_ != 0.f && ((uintptr_t)out_f32 & 15) == 0,
+                 "augment_apply: fp32 output needs W %% 4 == 0, std != 0 and a 16-byte aligned pointer");
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const double n = (double)B * H * W * C;
+  ProfScope ps(NVIT_KID_PATCHIFY, 0.0, n * (out_f32 ? 5.0 : 2.0), s);
+  hipLaunchKernelGGL(augment_apply_kernel, dim3(B), dim3(AUG_THREADS), 0, s, (const unsigned char*)in, params, out_f32,
+                     (unsigned char*)out_u8, (unsigned char*)ws, stride, B, H, W, C, mean, 1.0f / std_);
+  NVIT_CHECK_LAUNCH("augment_apply");
+  return NVIT_OK;
+}

@@ -18,6 +18,7 @@ from contextlib import nullcontext
 import torch
 
 from . import ops
+from .augment import AugmentedBatch
 from .optim import FusedAdamW
 
 _RENORM_ROWS = ("query", "key", "value", "c_fc")     # dim=1
@@ -154,9 +155,16 @@ def train_step(model, optimizer, X: torch.Tensor, y: torch.Tensor, grad_clip: fl
     skipped step; `optimizer.skipped_steps()` counts them.  Under DataParallel every rank sees the same averaged
     gradients, hence the same decision.  Needs FusedAdamW.
 
+    X may be an `AutoAugment.batch(u8)` (augment.py): the uint8 [B,H,W,C] batch together with the augmentation that
+    turns it into the model's input.  Its two launches (draw, apply) then run ahead of the forward, once for the whole
+    batch, before any accumulation split; the augmentation's step counter advances by one per call.  A tensor X takes
+    exactly the launches it always took.
+
     Wrong accumulation_steps (no int, < 1, no divisor of the batch) or skip_nonfinite with another optimizer raise
     ValueError before any device work."""
     _check_step_args(optimizer, X, accumulation_steps, skip_nonfinite)
+    if isinstance(X, AugmentedBatch):
+        X = X.augmented()   # two launches for the whole batch, ahead of any accumulation split
     logits, loss, aux = _forward_backward(model, X, y, accumulation_steps)
     if sync_grads is not None:
         sync_grads()
@@ -200,6 +208,12 @@ class GraphedTrainStep:
     of a replay, and a call advances `model.step` by N.  With skip_nonfinite the replay itself leaves a non-finite step
     out (no host code runs between backward and update, so only the device can): `optimizer.skipped_steps()` and
     `state_dict()` read the counts back.
+
+    With X an `AutoAugment.batch(u8)` the static input buffer is the uint8 batch and the augmentation's two launches
+    are captured ahead of the forward: its step counter is a device int64 that the draw kernel advances itself, so
+    every replay draws fresh parameters with no host code in between.  The warm-up steps are steps of the augmentation
+    too (they advance its counter, as they advance the weights); the capture pass is not.  Calls then take the uint8
+    batch (or another `batch(u8)` of the same augmentation).
     """
 
     def __init__(self, model, optimizer, X: torch.Tensor, y: torch.Tensor, grad_clip: float = 1.0, warmup: int = 3,
@@ -212,6 +226,9 @@ class GraphedTrainStep:
             raise RuntimeError("GraphedTrainStep: wrap the bare model (data-parallel steps run eagerly)")
         if X.device.type != "cuda":
             raise RuntimeError("GraphedTrainStep: inputs must live on the HIP device")
+        self.augment = X.augment if isinstance(X, AugmentedBatch) else None
+        if self.augment is not None:
+            X = X.u8
         self.model, self.optimizer, self.grad_clip = model, optimizer, grad_clip
         self.accumulation_steps, self.skip_nonfinite = accumulation_steps, bool(skip_nonfinite)
         N = accumulation_steps
@@ -220,7 +237,7 @@ class GraphedTrainStep:
         side.wait_stream(torch.cuda.current_stream())   # bound to the stream they are first used on
         with torch.cuda.stream(side):
             for _ in range(max(1, warmup)):   # builds every cache (shadow/renorm tables, LDS attributes, workspaces)
-                train_step(model, optimizer, self.X, self.y, grad_clip, accumulation_steps=N,
+                train_step(model, optimizer, self._input(), self.y, grad_clip, accumulation_steps=N,
                            skip_nonfinite=self.skip_nonfinite)
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
@@ -243,7 +260,8 @@ class GraphedTrainStep:
 
         try:
             with torch.cuda.graph(self.graph, stream=side):
-                logits, loss, aux = _forward_backward(model, self.X, self.y, N, hand_rates)
+                Xin = self.augment(self.X) if self.augment is not None else self.X
+                logits, loss, aux = _forward_backward(model, Xin, self.y, N, hand_rates)
                 gnorm = optimizer.step_fused(model, grad_clip, skip_nonfinite=self.skip_nonfinite)
         finally:
             for km in self._maps:
@@ -258,6 +276,9 @@ class GraphedTrainStep:
         self._grads = [p.grad for p in m.parameters() if p.grad is not None]
         self._table = optimizer._cache
         optimizer.zero_grad(set_to_none=True)
+
+    def _input(self):
+        return self.augment.batch(self.X) if self.augment is not None else self.X
 
     def set_lr(self, lr: float) -> None:
         for group in self.optimizer.param_groups:
@@ -284,6 +305,10 @@ class GraphedTrainStep:
     def __call__(self, X: torch.Tensor, y: torch.Tensor):
         """One optimizer step on (X, y); returns (logits, loss, aux, grad_norm) as static device tensors that the
         next call overwrites."""
+        if isinstance(X, AugmentedBatch):
+            if X.augment is not self.augment:
+                raise ValueError("GraphedTrainStep: this graph was captured with another augmentation (or none)")
+            X = X.u8
         self.X.copy_(X, non_blocking=True)
         self.y.copy_(y, non_blocking=True)
         self._advance_som()
