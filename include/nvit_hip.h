@@ -349,6 +349,23 @@ int nvit_augment_draw(const int* policy, int P, uint64_t seed, int64_t* step, in
  * workspace of ws_bytes >= 2 * B * round_up(H*W*C, 256) bytes. */
 int nvit_augment_apply(const void* in, const int* params, float* out_f32, void* out_u8, void* ws, int64_t ws_bytes, int B,
                        int H, int W, int C, float mean, float std_, void* stream);
+/* On-device Mixup / CutMix (tests/mix_ref.py): rows p and B-1-p of the batch form pair p (the middle row of
+ * an odd batch is its own partner and stays unmixed).
+ * nvit_mix_draw: one Philox4x32-10 call per pair, key = seed with a domain constant xor-ed into its high word, counter =
+ * (first_index + p, *step): r0 gates the pair against prob, r1 picks CutMix against switch_prob (only when both modes are
+ * on), r2 indexes the mode's quantile table (q_mix / q_cut: device fp32 [1025], the Beta(alpha,alpha) quantile at k/1024,
+ * computed by the host in fp64; NULL switches the mode off) and interpolates lambda linearly, r3 is the box centre.  The
+ * CutMix box and its corrected lambda (timm's rand_bbox, correct_lam) are computed in fp64.  Written: table int32 [B,8] =
+ * (mode 0 none / 1 Mixup / 2 CutMix, lambda as fp32 bits, y0, y1, x0, x1, partner row, 0), lam fp32 [B] and
+ * y2 int64 [B] = labels[partner]; both rows of a pair carry the same lambda and box.  *step is a device int64 that the
+ * kernel reads and then advances by one, as nvit_augment_draw does. */
+int nvit_mix_draw(uint64_t seed, int64_t* step, int64_t first_index, const float* q_mix, const float* q_cut, float prob,
+                  float switch_prob, const int64_t* labels, int* table, float* lam, int64_t* y2, int B, int H, int W,
+                  void* stream);
+/* nvit_mix_apply: in, out fp32 [B,C,H,W], W % 4 == 0; out may be in (in place).  Mixup: out_i = lam * x_i + (1 - lam) * x_j
+ * (two rounded products, one add); CutMix: rows i and j exchange the pixels of [y0,y1) x [x0,x1) in every channel.  A row
+ * of mode 0, a row that is its own partner, and a row whose partner does not name it back with the same mode is copied. */
+int nvit_mix_apply(const float* in, const int* table, float* out, int B, int C, int H, int W, void* stream);
 /* out[r,n] = a[r,n] * s[n] * c   (sz scaling model.py:466-468 and its backward); s == NULL: out = a * c */
 int nvit_scale_cols(const float* a, int lda, const float* s, float c, void* out, int out_dt, int ldo, int R, int N,
                     void* stream);
@@ -481,6 +498,13 @@ int nvit_recon_bwd(int dt, const float* raw, const float* img, const float* g, v
  * (multiply by the upstream scalar gradient).  Labels outside [0,N) contribute 0 loss (and a plain softmax/B row). */
 int nvit_ce_loss(const float* logits, const int64_t* labels, float* rowloss, float* loss, float* dlogits, int B, int N,
                  void* stream);
+/* The same with a soft target (Mixup / CutMix / label smoothing, timm's mixup_target): row b's target is
+ * t = (1 - smoothing) * (lam[b] * e[labels[b]] + (1 - lam[b]) * e[labels2[b]]) + smoothing / N; rowloss[b] =
+ * logsumexp(row) - (1 - smoothing) * (lam * row[label] + (1 - lam) * row[label2]) - smoothing * mean(row); loss[0] = mean;
+ * dlogits = (softmax - t) / B.  lam: device fp32 [B]; 0 <= smoothing < 1.  With lam = 1 and smoothing = 0 the three outputs
+ * have the bits of nvit_ce_loss.  A label outside [0,N) contributes no term to the target. */
+int nvit_ce_loss_soft(const float* logits, const int64_t* labels, const int64_t* labels2, const float* lam, float smoothing,
+                      float* rowloss, float* loss, float* dlogits, int B, int N, void* stream);
 /* Evaluation metrics of one batch in one launch (reference train.py:563-575, 595-613): per row the cross-entropy of
  * nvit_ce_loss and rank = #{j : logit_j > logit_y} + #{j < y : logit_j == logit_y} (a label outside [0,N): loss 0,
  * never correct).  ADDS to the device accumulator acc[0..3]: the batch-mean loss, 100 * #(rank < 1) / B,

@@ -16,6 +16,9 @@ def __getattr__(name):
     if name in ("AutoAugment", "AugmentedBatch"):
         from . import augment
         return getattr(augment, name)
+    if name in ("Mixup", "MixedBatch", "MixedTargets"):
+        from . import mix
+        return getattr(mix, name)
     if name == "FusedAdamW":
         from . import optim
         return optim.FusedAdamW

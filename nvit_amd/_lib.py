@@ -43,6 +43,7 @@ SIGNATURES = {
     "nvit_set_gemm_sched": [_i],
     "nvit_set_gemm_impl": [_i, _i],
     "nvit_ce_loss": [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp],
+    "nvit_ce_loss_soft": [_vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _i, _i, _vp],
     "nvit_eval_metrics": [_vp, _vp, _vp, _i, _i, _vp],
     "nvit_gemm_nt": [_i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp],
     "nvit_gemm_nt_fusable": [_i, _i, _i, _i],
@@ -77,6 +78,8 @@ SIGNATURES = {
     "nvit_normalize_images": [_vp, _i, _vp, _i, _i, _i, _i, _f, _f, _vp],
     "nvit_augment_draw": [_vp, _i, C.c_uint64, _vp, _i64, _vp, _vp, _i, _vp],
     "nvit_augment_apply": [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _f, _f, _vp],
+    "nvit_mix_draw": [C.c_uint64, _vp, _i64, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
+    "nvit_mix_apply": [_vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "nvit_scale_cols": [_vp, _i, _vp, _f, _vp, _i, _i, _i, _i, _vp],
     "nvit_attn_fwd": [_i, _i, _vp, _vp, _vp, _f, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "nvit_attn_fwd_bounded": [_i, _i, _vp, _vp, _vp, _f, _vp, _f, _f, _vp, _vp, _i, _i, _i, _i, _i, _vp],

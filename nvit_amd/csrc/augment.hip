@@ -14,6 +14,11 @@
 // affine ops, Color (needs the pixel's three channels) and Sharpness (3x3 stencil) read the image directly.
 // An op reads one complete image and writes another: the intermediate images live in a caller-provided global workspace
 // (two per image, each used by this workgroup only, so they stay in L2), which makes one code path for every image size.
+//
+// Further down, the batch-level mixing that follows it (Mixup / CutMix, tests/mix_ref.py is the numpy twin), here for the
+// Philox and for the file-wide contract(off):
+//   nvit_mix_draw       one workgroup, one thread per pair of rows -> int32 [B,8] table, lambda and the partner's label
+//   nvit_mix_apply      fp32 [B,C,H,W] -> fp32 [B,C,H,W], float4 streaming over (pair, chunk of the image)
 #include "common.h"
 
 // a fused a + f*b changes truncations by one level: nothing in this file contracts, except normalize4 below.  (Plain
@@ -281,7 +286,175 @@ __global__ __launch_bounds__(AUG_THREADS) void augment_apply_kernel(const unsign
   }
 }
 
+// ------------------------------------------------------------------------------------------------ Mixup / CutMix
+// (tests/mix_ref.py is the numpy twin.)  Rows i and B-1-i of the batch form pair i.
+constexpr int MIX_ROW = 8;                  // mode, lambda bits, y0, y1, x0, x1, partner row, 0
+constexpr unsigned MIX_DOMAIN = 0x4D495821u;   // xor-ed into the key's high word: not AutoAugment's stream
+constexpr int MIX_KNOTS = 1024;             // the quantile tables hold MIX_KNOTS + 1 floats
+enum MixMode { MIX_NONE = 0, MIX_MIXUP = 1, MIX_CUTMIX = 2 };
+
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// q_mix / q_cut: the Beta(alpha, alpha) quantile at k/1024, k = 0..1024, of the mode's alpha; NULL = mode off.
+__global__ __launch_bounds__(256) void mix_draw_kernel(unsigned long long seed, long long* step_ctr, long long first_index,
+                                                       const float* __restrict__ q_mix, const float* __restrict__ q_cut,
+                                                       float prob, float switch_prob, const int64_t* __restrict__ labels,
+                                                       int* __restrict__ table, float* __restrict__ lam_out,
+                                                       int64_t* __restrict__ y2, int B, int H, int W) {
+  const unsigned long long step = (unsigned long long)*step_ctr;
+  const int npairs = (B + 1) / 2;
+  for (int p = threadIdx.x; p < npairs; p += blockDim.x) {
+    const int i = p, j = B - 1 - p;
+    const unsigned long long g = (unsigned long long)(first_index + p);
+    const Philox4 r = philox4x32_10((unsigned)g, (unsigned)(g >> 32), (unsigned)step, (unsigned)(step >> 32),
+                                    (unsigned)seed, (unsigned)(seed >> 32) ^ MIX_DOMAIN);
+    const bool gate = (float)(r.v[0] >> 8) * 0x1p-24f < prob;   // exact: 24 bits
+    const bool sw = (float)(r.v[1] >> 8) * 0x1p-24f < switch_prob;
+    const bool cut = q_cut && (!q_mix || sw);
+    const float* q = cut ? q_cut : q_mix;
+    int mode = MIX_NONE, y0 = 0, y1 = 0, x0 = 0, x1 = 0;
+    float lam = 1.0f;
+    if (gate && q && i != j) {
+      const unsigned u = r.v[2] >> 8;
+      const int k = (int)(u >> 14);                           // 0..1023
+      const float f = (float)(u & 0x3FFFu) * 0x1p-14f;        // exact
+      lam = q[k] + f * (q[k + 1] - q[k]);                     // three roundings (file-wide contract(off))
+      mode = MIX_MIXUP;
+      if (cut) {
+        // timm's rand_bbox with correct_lam, in fp64
+        const int cy = (int)(((r.v[3] & 0xFFFFu) * (unsigned)H) >> 16), cx = (int)(((r.v[3] >> 16) * (unsigned)W) >> 16);
+        const double ratio = __dsqrt_rn((double)(1.0f - lam));
+        const int cut_h = (int)((double)H * ratio), cut_w = (int)((double)W * ratio);
+        y0 = clampi(cy - cut_h / 2, 0, H);
+        y1 = clampi(cy + cut_h / 2, 0, H);
+        x0 = clampi(cx - cut_w / 2, 0, W);
+        x1 = clampi(cx + cut_w / 2, 0, W);
+        lam = (float)(1.0 - (double)((y1 - y0) * (x1 - x0)) / (double)(H * W));
+        mode = MIX_CUTMIX;
+      }
+    }
+    const int64_t yi = labels[i], yj = labels[j];
+    for (int s = 0; s < (i == j ? 1 : 2); ++s) {
+      const int b = s ? j : i;
+      int* row = table + (size_t)b * MIX_ROW;
+      row[0] = mode;
+      row[1] = __float_as_int(lam);
+      row[2] = y0;
+      row[3] = y1;
+      row[4] = x0;
+      row[5] = x1;
+      row[6] = s ? i : j;
+      row[7] = 0;
+      lam_out[b] = lam;
+      y2[b] = s ? yi : yj;
+    }
+  }
+  __syncthreads();   // every thread has read the counter
+  if (threadIdx.x == 0) *step_ctr = (long long)(step + 1);
+}
+
+constexpr int MIX_THREADS = 256;
+constexpr int MIX_PER_THREAD = 4;   // float4s of each of the two images per thread: 8 independent 16-byte loads in flight
+
+// Grid (chunks of an image, rows).  The workgroups of row b serve the pair (b, partner) when b is its lower row and
+// return at once when b is the upper one; a row that is not mixed (mode 0, its own partner, or a table whose partner
+// does not name it back) is copied, or left alone in place.  Every element is read and written by one thread, so
+// out == in is allowed.
+__global__ __launch_bounds__(MIX_THREADS) void mix_apply_kernel(const float* in, const int* __restrict__ table, float* out,
+                                                                int B, int n4, int H, int w4) {
+  const int b = blockIdx.y;
+  const int* row = table + (size_t)b * MIX_ROW;
+  const int mode = row[0], j = row[6];
+  const bool paired = (mode == MIX_MIXUP || mode == MIX_CUTMIX) && j >= 0 && j < B && j != b &&
+                      table[(size_t)j * MIX_ROW + 6] == b && table[(size_t)j * MIX_ROW] == mode;
+  const int base = blockIdx.x * (MIX_THREADS * MIX_PER_THREAD) + threadIdx.x;
+  const size_t img = (size_t)n4 * 4;
+  if (!paired) {
+    if (in == out) return;
+    const f32x4* src = reinterpret_cast<const f32x4*>(in + (size_t)b * img);
+    f32x4* dst = reinterpret_cast<f32x4*>(out + (size_t)b * img);
+#pragma unroll
+    for (int k = 0; k < MIX_PER_THREAD; ++k) {
+      const int i = base + k * MIX_THREADS;
+      if (i < n4) dst[i] = src[i];
+    }
+    return;
+  }
+  if (j < b) return;   // the lower row's workgroups write both images
+  const f32x4* a_in = reinterpret_cast<const f32x4*>(in + (size_t)b * img);
+  const f32x4* b_in = reinterpret_cast<const f32x4*>(in + (size_t)j * img);
+  f32x4* a_out = reinterpret_cast<f32x4*>(out + (size_t)b * img);
+  f32x4* b_out = reinterpret_cast<f32x4*>(out + (size_t)j * img);
+  f32x4 va[MIX_PER_THREAD], vb[MIX_PER_THREAD];
+#pragma unroll
+  for (int k = 0; k < MIX_PER_THREAD; ++k) {
+    const int i = base + k * MIX_THREADS;
+    if (i < n4) {
+      va[k] = a_in[i];
+      vb[k] = b_in[i];
+    }
+  }
+  if (mode == MIX_MIXUP) {
+    const float lam = __int_as_float(row[1]), om = 1.0f - lam;
+#pragma unroll
+    for (int k = 0; k < MIX_PER_THREAD; ++k) {
+      const int i = base + k * MIX_THREADS;
+      if (i < n4) {
+        a_out[i] = lam * va[k] + om * vb[k];   // two rounded products and one add (file-wide contract(off))
+        b_out[i] = lam * vb[k] + om * va[k];
+      }
+    }
+  } else {
+    const int y0 = row[2], y1 = row[3], x0 = row[4], x1 = row[5];
+#pragma unroll
+    for (int k = 0; k < MIX_PER_THREAD; ++k) {
+      const int i = base + k * MIX_THREADS;
+      if (i < n4) {
+        const int x = (i % w4) * 4, y = (i / w4) % H;
+        const bool in_rows = y >= y0 && y < y1;
+        f32x4 oa, ob;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const bool inside = in_rows && x + e >= x0 && x + e < x1;
+          oa[e] = inside ? vb[k][e] : va[k][e];
+          ob[e] = inside ? va[k][e] : vb[k][e];
+        }
+        a_out[i] = oa;
+        b_out[i] = ob;
+      }
+    }
+  }
+}
+
 }  // namespace
+
+extern "C" int nvit_mix_draw(uint64_t seed, int64_t* step, int64_t first_index, const float* q_mix, const float* q_cut,
+                             float prob, float switch_prob, const int64_t* labels, int* table, float* lam, int64_t* y2,
+                             int B, int H, int W, void* stream) {
+  NVIT_REQUIRE(step && labels && table && lam && y2 && B > 0 && first_index >= 0, "mix_draw: bad arguments");
+  NVIT_REQUIRE(H > 0 && W > 0 && H <= 4096 && W <= 4096, "mix_draw: images up to 4096 x 4096");
+  NVIT_REQUIRE(prob >= 0.f && prob <= 1.f && switch_prob >= 0.f && switch_prob <= 1.f, "mix_draw: probabilities in [0,1]");
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope ps(NVIT_KID_PATCHIFY, 0.0, (double)B * (MIX_ROW * 4.0 + 20.0), s);
+  hipLaunchKernelGGL(mix_draw_kernel, dim3(1), dim3(256), 0, s, (unsigned long long)seed, (long long*)step,
+                     (long long)first_index, q_mix, q_cut, prob, switch_prob, labels, table, lam, y2, B, H, W);
+  NVIT_CHECK_LAUNCH("mix_draw");
+  return NVIT_OK;
+}
+
+extern "C" int nvit_mix_apply(const float* in, const int* table, float* out, int B, int C, int H, int W, void* stream) {
+  NVIT_REQUIRE(in && table && out && B > 0 && B <= 65535 && C > 0 && H > 0 && W > 0, "mix_apply: bad arguments");
+  NVIT_REQUIRE(W % 4 == 0 && ((uintptr_t)in & 15) == 0 && ((uintptr_t)out & 15) == 0,
+               "mix_apply: needs W %% 4 == 0 and 16-byte aligned pointers");
+  const long long n4 = (long long)C * H * (W / 4);
+  NVIT_REQUIRE(n4 <= (1ll << 28), "mix_apply: image too large");
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope ps(NVIT_KID_PATCHIFY, 0.0, (double)B * (double)n4 * 32.0, s);
+  const int chunks = (int)cdiv(n4, (long long)(MIX_THREADS * MIX_PER_THREAD));
+  hipLaunchKernelGGL(mix_apply_kernel, dim3(chunks, B), dim3(MIX_THREADS), 0, s, in, table, out, B, (int)n4, H, W / 4);
+  NVIT_CHECK_LAUNCH("mix_apply");
+  return NVIT_OK;
+}
 
 extern "C" int nvit_augment_draw(const int* policy, int P, uint64_t seed, int64_t* step, int64_t first_index,
                                  const int* argtab, int* params, int B, void* stream) {

@@ -289,6 +289,56 @@ __global__ __launch_bounds__(256) void ce_rows_kernel(const float* logits, const
   for (int n = tid; n < N; n += 256) drow[n] = (expf(row[n] - mx) * inv - (n == lab ? 1.0f : 0.0f)) * invB;
 }
 
+// Soft-target cross-entropy (Mixup / CutMix / label smoothing): the target of row b is
+// t = (1-eps) * (lam * e[y] + (1-lam) * e[y2]) + eps / N (timm's mixup_target), the row loss
+// lse - (1-eps) * (lam * z[y] + (1-lam) * z[y2]) - eps * mean(z), the gradient (softmax - t) / B.  Same structure as
+// ce_rows_kernel, and the arithmetic is ordered so that lam = 1, eps = 0 gives its bits: every extra term is then
+// exactly 0 or 1, with or without contraction.  A label outside [0,N) contributes no term.
+__global__ __launch_bounds__(256) void ce_soft_rows_kernel(const float* logits, const int64_t* labels,
+                                                           const int64_t* labels2, const float* lam_rows, float eps,
+                                                           float* rowloss, float* dlogits, int B, int N) {
+  __shared__ float red[4];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const float* row = logits + (size_t)b * N;
+  float mx = -INFINITY;
+  for (int n = tid; n < N; n += 256) mx = fmaxf(mx, row[n]);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+  if (lane == 0) red[wid] = mx;
+  __syncthreads();
+  mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  __syncthreads();
+  float s = 0.f;
+  for (int n = tid; n < N; n += 256) s += expf(row[n] - mx);
+  s = wave_sum(s);
+  if (lane == 0) red[wid] = s;
+  __syncthreads();
+  s = red[0] + red[1] + red[2] + red[3];
+  float mean = 0.f;
+  if (eps != 0.f) {   // uniform over the launch
+    __syncthreads();
+    float z = 0.f;
+    for (int n = tid; n < N; n += 256) z += row[n];
+    z = wave_sum(z);
+    if (lane == 0) red[wid] = z;
+    __syncthreads();
+    mean = (red[0] + red[1] + red[2] + red[3]) / (float)N;
+  }
+  const int lab = (int)labels[b], lab2 = (int)labels2[b];
+  const bool ok = lab >= 0 && lab < N, ok2 = lab2 >= 0 && lab2 < N;
+  const float lam = lam_rows[b], om = 1.0f - lam, keep = 1.0f - eps, epsN = eps / (float)N;
+  const float lse = mx + logf(s);
+  if (tid == 0) rowloss[b] = lse - keep * (lam * (ok ? row[lab] : 0.f) + om * (ok2 ? row[lab2] : 0.f)) - eps * mean;
+  const float inv = 1.0f / s, invB = 1.0f / (float)B;
+  float* drow = dlogits + (size_t)b * N;
+  for (int n = tid; n < N; n += 256) {
+    const float t = (lam * (n == lab ? 1.0f : 0.0f) + om * (n == lab2 ? 1.0f : 0.0f)) * keep + epsN;
+    // one rounding for p * inv - t, written out: it is what the compiler makes of ce_rows_kernel's expression (the
+    // bit-for-bit test in tests/test_gpu_mix.py holds the two together)
+    drow[n] = fmaf(expf(row[n] - mx), inv, -t) * invB;
+  }
+}
+
 __global__ __launch_bounds__(256) void ce_mean_kernel(const float* rowloss, float* loss, int B) {
   __shared__ float red[4];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -380,5 +430,19 @@ extern "C" int nvit_ce_loss(const float* logits, const int64_t* labels, float* r
   hipLaunchKernelGGL(ce_rows_kernel, dim3(B), dim3(256), 0, s, logits, labels, rowloss, dlogits, B, N);
   hipLaunchKernelGGL(ce_mean_kernel, dim3(1), dim3(256), 0, s, rowloss, loss, B);
   NVIT_CHECK_LAUNCH("ce_loss");
+  return NVIT_OK;
+}
+
+extern "C" int nvit_ce_loss_soft(const float* logits, const int64_t* labels, const int64_t* labels2, const float* lam,
+                                 float smoothing, float* rowloss, float* loss, float* dlogits, int B, int N,
+                                 void* stream) {
+  NVIT_REQUIRE(logits && labels && labels2 && lam && rowloss && loss && dlogits && B > 0 && N > 0,
+               "ce_loss_soft: bad arguments");
+  NVIT_REQUIRE(smoothing >= 0.f && smoothing < 1.f, "ce_loss_soft: smoothing must be in [0,1)");
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(ce_soft_rows_kernel, dim3(B), dim3(256), 0, s, logits, labels, labels2, lam, smoothing, rowloss,
+                     dlogits, B, N);
+  hipLaunchKernelGGL(ce_mean_kernel, dim3(1), dim3(256), 0, s, rowloss, loss, B);
+  NVIT_CHECK_LAUNCH("ce_loss_soft");
   return NVIT_OK;
 }

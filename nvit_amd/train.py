@@ -19,6 +19,7 @@ import torch
 
 from . import ops
 from .augment import AugmentedBatch
+from .mix import MixedBatch, MixedTargets
 from .optim import FusedAdamW
 
 _RENORM_ROWS = ("query", "key", "value", "c_fc")     # dim=1
@@ -53,10 +54,15 @@ def normalize_matrices(model) -> None:
 
 
 class CrossEntropyFn(torch.autograd.Function):
-    """F.cross_entropy(logits, y) (reference train.py:906) as one HIP pass that also produces the gradient."""
+    """F.cross_entropy(logits, y) (reference train.py:906) as one HIP pass that also produces the gradient.  y: int64
+    labels (nvit_ce_loss), or the `MixedTargets` of a Mixup (mix.py): two labels and a lambda per row plus label
+    smoothing, timm's mixup_target (nvit_ce_loss_soft)."""
 
     @staticmethod
     def forward(ctx, logits, y):
+        soft = y if isinstance(y, MixedTargets) else None
+        if soft is not None:
+            y = soft.y
         if logits.device.type != "cuda" or logits.dtype != torch.float32 or y.dtype != torch.int64:
             raise RuntimeError("CrossEntropyFn: fp32 logits and int64 labels on the HIP device (no CPU path)")
         logits = logits.contiguous()
@@ -64,8 +70,16 @@ class CrossEntropyFn(torch.autograd.Function):
         rowloss = torch.empty(B, device=logits.device, dtype=torch.float32)
         loss = torch.empty(1, device=logits.device, dtype=torch.float32)
         dlogits = torch.empty_like(logits)
-        ops.check(ops._lib.load().nvit_ce_loss(ops._p(logits), ops._p(y.contiguous()), ops._p(rowloss), ops._p(loss),
-                                               ops._p(dlogits), B, N, ops._s()), "nvit_ce_loss")
+        if soft is not None:
+            if soft.y.shape[0] != B:
+                raise ValueError(f"CrossEntropyFn: {soft.y.shape[0]} targets for {B} rows of logits")
+            ops._chk_dev(soft.y2, soft.lam)
+            ops.check(ops._lib.load().nvit_ce_loss_soft(ops._p(logits), ops._p(y.contiguous()), ops._p(soft.y2.contiguous()),
+                                                        ops._p(soft.lam.contiguous()), soft.smoothing, ops._p(rowloss),
+                                                        ops._p(loss), ops._p(dlogits), B, N, ops._s()), "nvit_ce_loss_soft")
+        else:
+            ops.check(ops._lib.load().nvit_ce_loss(ops._p(logits), ops._p(y.contiguous()), ops._p(rowloss), ops._p(loss),
+                                                   ops._p(dlogits), B, N, ops._s()), "nvit_ce_loss")
         ctx.save_for_backward(dlogits)
         return loss[0]
 
@@ -78,7 +92,8 @@ class CrossEntropyFn(torch.autograd.Function):
 def total_loss(config, logits: torch.Tensor, aux, y: torch.Tensor, consistency_weight: float = 0.1,
                smoothness_weight: float = 0.1) -> torch.Tensor:
     """Loss of the reference loop (train.py:906-926): CE, plus the weighted aux losses iff the Kohonen head is on
-    (consistency/smoothness weights are settings.yaml `training.*`, the others come from the model config)."""
+    (consistency/smoothness weights are settings.yaml `training.*`, the others come from the model config).  y: int64
+    labels or a `MixedTargets` (the soft-target cross-entropy)."""
     return add_aux_losses(config, CrossEntropyFn.apply(logits, y), aux, consistency_weight, smoothness_weight)
 
 
@@ -103,6 +118,16 @@ def _check_step_args(optimizer, X, accumulation_steps, skip_nonfinite) -> None:
         raise ValueError(f"accumulation_steps={n} does not divide the batch of {X.shape[0]} rows")
     if skip_nonfinite and not isinstance(optimizer, FusedAdamW):
         raise ValueError("skip_nonfinite=True needs the FusedAdamW returned by ViT.configure_optimizers")
+
+
+def _unwrap_input(X):
+    """X of a step -> (Mixup or None, AutoAugment or None, the tensor underneath)."""
+    mix = aug = None
+    if isinstance(X, MixedBatch):
+        mix, X = X.mix, X.X
+    if isinstance(X, AugmentedBatch):
+        aug, X = X.augment, X.u8
+    return mix, aug, X
 
 
 def _forward_backward(model, X, y, n: int, before_micro=None):
@@ -160,10 +185,18 @@ def train_step(model, optimizer, X: torch.Tensor, y: torch.Tensor, grad_clip: fl
     batch, before any accumulation split; the augmentation's step counter advances by one per call.  A tensor X takes
     exactly the launches it always took.
 
+    X may also be a `Mixup.batch(X)` (mix.py) around a tensor or around an `AutoAugment.batch(u8)`: Mixup / CutMix with
+    label smoothing.  Its draw and apply run once for the whole batch, after the augmentation's launches and ahead of the
+    forward; the loss is then the soft-target cross-entropy of the drawn `MixedTargets`, and under accumulation
+    micro-batch i takes rows [i*b, (i+1)*b) of the mixed batch and of the targets (a row's partner may lie in another
+    micro-batch; the targets carry the partner's label).  The returned logits belong to the mixed batch.
+
     Wrong accumulation_steps (no int, < 1, no divisor of the batch) or skip_nonfinite with another optimizer raise
     ValueError before any device work."""
     _check_step_args(optimizer, X, accumulation_steps, skip_nonfinite)
-    if isinstance(X, AugmentedBatch):
+    if isinstance(X, MixedBatch):
+        X, y = X.mixed(y)   # the augmentation's launches if any, then draw + apply, ahead of any accumulation split
+    elif isinstance(X, AugmentedBatch):
         X = X.augmented()   # two launches for the whole batch, ahead of any accumulation split
     logits, loss, aux = _forward_backward(model, X, y, accumulation_steps)
     if sync_grads is not None:
@@ -214,6 +247,11 @@ class GraphedTrainStep:
     every replay draws fresh parameters with no host code in between.  The warm-up steps are steps of the augmentation
     too (they advance its counter, as they advance the weights); the capture pass is not.  Calls then take the uint8
     batch (or another `batch(u8)` of the same augmentation).
+
+    With X a `Mixup.batch(...)` (around a tensor or around an `AutoAugment.batch(u8)`) the static inputs stay the raw X
+    (or uint8 batch) and y; the Mixup's draw and apply are captured ahead of the forward and after the augmentation, and
+    the same rule holds for its counter: warm-up steps advance it, the capture pass does not, every replay does.  Calls
+    take the raw batch or a `batch(...)` of the same Mixup; one of another Mixup raises ValueError.
     """
 
     def __init__(self, model, optimizer, X: torch.Tensor, y: torch.Tensor, grad_clip: float = 1.0, warmup: int = 3,
@@ -226,9 +264,9 @@ class GraphedTrainStep:
             raise RuntimeError("GraphedTrainStep: wrap the bare model (data-parallel steps run eagerly)")
         if X.device.type != "cuda":
             raise RuntimeError("GraphedTrainStep: inputs must live on the HIP device")
-        self.augment = X.augment if isinstance(X, AugmentedBatch) else None
-        if self.augment is not None:
-            X = X.u8
+        if isinstance(X, MixedBatch):
+            X.check_labels(y)
+        self.mix, self.augment, X = _unwrap_input(X)
         self.model, self.optimizer, self.grad_clip = model, optimizer, grad_clip
         self.accumulation_steps, self.skip_nonfinite = accumulation_steps, bool(skip_nonfinite)
         N = accumulation_steps
@@ -260,8 +298,10 @@ class GraphedTrainStep:
 
         try:
             with torch.cuda.graph(self.graph, stream=side):
-                Xin = self.augment(self.X) if self.augment is not None else self.X
-                logits, loss, aux = _forward_backward(model, Xin, self.y, N, hand_rates)
+                Xin, yin = (self.augment(self.X) if self.augment is not None else self.X), self.y
+                if self.mix is not None:
+                    Xin, yin = self.mix(Xin, yin, inplace=self.augment is not None)
+                logits, loss, aux = _forward_backward(model, Xin, yin, N, hand_rates)
                 gnorm = optimizer.step_fused(model, grad_clip, skip_nonfinite=self.skip_nonfinite)
         finally:
             for km in self._maps:
@@ -278,7 +318,8 @@ class GraphedTrainStep:
         optimizer.zero_grad(set_to_none=True)
 
     def _input(self):
-        return self.augment.batch(self.X) if self.augment is not None else self.X
+        X = self.augment.batch(self.X) if self.augment is not None else self.X
+        return self.mix.batch(X) if self.mix is not None else X
 
     def set_lr(self, lr: float) -> None:
         for group in self.optimizer.param_groups:
@@ -305,6 +346,10 @@ class GraphedTrainStep:
     def __call__(self, X: torch.Tensor, y: torch.Tensor):
         """One optimizer step on (X, y); returns (logits, loss, aux, grad_norm) as static device tensors that the
         next call overwrites."""
+        if isinstance(X, MixedBatch):
+            if X.mix is not self.mix:
+                raise ValueError("GraphedTrainStep: this graph was captured with another Mixup (or none)")
+            X = X.X
         if isinstance(X, AugmentedBatch):
             if X.augment is not self.augment:
                 raise ValueError("GraphedTrainStep: this graph was captured with another augmentation (or none)")
