@@ -69,9 +69,10 @@ const char* nvit_prof_name(int kid);
  * first_item = prefix sum of work items (rows/NVIT_RENORM_ROWS_PER_ITEM for dim=1,
  * cols/NVIT_RENORM_COLS_PER_ITEM for dim=0, rounded up; cols/NVIT_RENORM_TALL_COLS_PER_ITEM for a dim=0 matrix of
  * more than NVIT_RENORM_TALL_ROWS rows); total_items = sum.
- * dim=0 keeps a [rows x NVIT_RENORM_COLS_PER_ITEM] panel in the registers of a 1024-thread workgroup (rows <= 1152),
- * a [rows x NVIT_RENORM_TALL_COLS_PER_ITEM] panel for 1152 < rows <= NVIT_RENORM_MAX_ROWS_DIM0.  dim=1 takes any
- * number of columns (rows of up to 2048 columns, a multiple of 4, stay in registers). */
+ * dim=0 keeps a [rows x NVIT_RENORM_COLS_PER_ITEM] panel in the registers of a 1024-thread workgroup (rows <=
+ * NVIT_RENORM_TALL_ROWS), a [rows x NVIT_RENORM_TALL_COLS_PER_ITEM] panel for taller matrices of up to
+ * NVIT_RENORM_MAX_ROWS_DIM0 rows.  dim=1 takes any number of columns (rows of up to NVIT_MAX_EMBD columns, a multiple of
+ * 4, stay in registers). */
 #define NVIT_RENORM_ROWS_PER_ITEM 64
 #define NVIT_RENORM_COLS_PER_ITEM 64
 #define NVIT_RENORM_TALL_ROWS 1152          /* dim=0 matrices with more rows take the narrow panel */
@@ -93,27 +94,42 @@ int nvit_renorm_weights(const int64_t* table, int n, int total_items, void* stre
  *         columns 32j..32j+31 of src become the 128-byte slice [hi32 | lo32] at dst column 64j, hi = bf16(src),
  *         lo = bf16(src - hi) - the weight operand of nvit_patch_embed_fwd.  The padding columns of the last
  *         slice are NOT written: allocate dst zeroed.
- *   Work items are 64x64 tiles: tiles_c = ceil(max(cols,dst_cols)/64) tile columns,
- *   ceil(max(rows,dstT_cols)/64) tile rows; first_item = prefix sum; total_items = sum.
+ *   Work items are square tiles of NVIT_SHADOW_TILE elements a side: tiles_c = ceil(max(cols,dst_cols)/NVIT_SHADOW_TILE)
+ *   tile columns, ceil(max(rows,dstT_cols)/NVIT_SHADOW_TILE) tile rows; first_item = prefix sum; total_items = sum.
  * Element type of dst/dstT is `dt`. */
+#define NVIT_SHADOW_TILE 64
 int nvit_shadow_weights(const int64_t* table, int n, int total_items, int dt, void* stream);
 
 /* Optimizer step fused with the re-normalisation: replaces clip_grad_norm_ + AdamW.step +
  * Trainer.normalize_matrices (train.py:935-946, 461-480, 989-990; parameter groups of model.py:369-385).
- * table: n rows of 10 int64 {p, g, m, v (fp32 device pointers), rows, cols, kind, first_item, first_chunk,
- *        f32bits(lr) | f32bits(weight_decay) << 32};  kind -1 = plain (items of 8192 elements), 1 = normalise rows
- *        (items of 16 rows; cols % 4 == 0, cols <= 2048), 0 = normalise columns (rows <= 2048; items of 32 columns,
- *        of 16 columns for a matrix of more than 1152 rows);
- *        first_chunk counts 8192-element chunks of the gradient for nvit_grad_sqnorm.
- * nvit_grad_sqnorm: partial[npart] = per-workgroup sums of g*g over all gradients (npart <= 4096 workgroups).
+ * table: n rows of NVIT_OPT_TABLE_COLS int64 {p, g, m, v (fp32 device pointers), rows, cols, kind, first_item,
+ *        first_chunk, f32bits(lr) | f32bits(weight_decay) << 32};  kind -1 = plain (items of NVIT_OPT_CHUNK elements),
+ *        1 = normalise rows (items of NVIT_OPT_ROWS_PER_ITEM rows; cols % 4 == 0, cols <= NVIT_OPT_WIDE_COLS), 0 =
+ *        normalise columns (rows <= NVIT_OPT_TALL_ROWS; items of NVIT_OPT_SLAB_COLS columns, of NVIT_OPT_TALL_COLS
+ *        columns for a matrix of more than NVIT_OPT_SLAB_ROWS rows);
+ *        first_chunk counts NVIT_OPT_CHUNK-element chunks of the gradient for nvit_grad_sqnorm.
+ * nvit_grad_sqnorm: partial[npart] = per-workgroup sums of g*g over all gradients (npart <= NVIT_OPT_MAX_PART
+ *        workgroups).
  * nvit_adamw_renorm: clip = min(1, max_norm / (sqrt(sum partial) + 1e-6)) when partial != NULL and max_norm > 0;
  *        g *= clip; torch AdamW update (decoupled decay, bias corrections 1 - beta^t passed by the host); rows /
  *        columns of kind 1 / 0 matrices are L2-normalised before the single write-back.  gnorm_out[0] (optional)
  *        receives the pre-clip global gradient norm.  max_slab_rows sizes the LDS: the largest `rows` among kind-0
- *        entries, and at least 1024 when a kind-1 entry has more than 1536 columns (such rows are parked in LDS).
+ *        entries, and at least NVIT_OPT_WIDE_LDS_ROWS when a kind-1 entry has more than NVIT_OPT_ROW_COLS columns (such
+ *        rows are parked in LDS).
  *        hyper (optional, 3 floats on the device): when given, the bias corrections are read from hyper[1..2] as
  *        maintained by nvit_adamw_tick (hyper[0] = step count; one call per optimizer step, before this one), so the
  *        whole step can be captured in a hipGraph and replayed; the two double arguments are then ignored. */
+#define NVIT_OPT_TABLE_COLS 10
+#define NVIT_OPT_CHUNK 8192          /* elements per plain item and per grad-norm chunk */
+#define NVIT_OPT_ROWS_PER_ITEM 16
+#define NVIT_OPT_SLAB_COLS 32        /* column slab of a kind-0 matrix of at most NVIT_OPT_SLAB_ROWS rows, */
+#define NVIT_OPT_SLAB_ROWS 1152
+#define NVIT_OPT_TALL_COLS 16        /* of a taller one (at most NVIT_OPT_TALL_ROWS rows) */
+#define NVIT_OPT_TALL_ROWS 2048
+#define NVIT_OPT_ROW_COLS 1536       /* a kind-1 row of at most this many columns stays in registers, */
+#define NVIT_OPT_WIDE_COLS 2048      /* a wider one (up to this) is parked in LDS, */
+#define NVIT_OPT_WIDE_LDS_ROWS 1024  /* which is then sized as for a slab of this many rows */
+#define NVIT_OPT_MAX_PART 4096
 int nvit_adamw_tick(float* hyper, double beta1, double beta2, void* stream);
 int nvit_grad_sqnorm(const int64_t* table, int n, int total_chunks, float* partial, int npart, void* stream);
 int nvit_adamw_renorm(const int64_t* table, int n, int total_items, int max_slab_rows, float beta1, float beta2,
@@ -156,8 +172,11 @@ int nvit_gemm_nt(int dt, const void* A, int lda, const void* B, int ldb, void* C
  * nvit_gemm_nt_swiglu_bwd: autograd of model.py:148-155 / 259-262 in one launch: dx[M,F] = A B^T (A = dL/dy of
  *   mlp_c_proj / out_proj, B = that weight's transposed shadow [F,K]) stays in the accumulators; with the saved raw
  *   uv[M,2F] (interleaved, as written by nvit_gemm_nt_swiglu) it writes duv[M,2F] (same layout) and, when gs != NULL
- *   (suv, natural order [u(F)|v(F)]), part[2*ceil(M/256), 2F] = per-128-row partial sums of d(suv) (natural order;
- *   reduce with nvit_colsum_reduce).  Replaces nvit_gemm_nt + nvit_swiglu_bwd.  Requires F % 256 == 0. */
+ *   (suv, natural order [u(F)|v(F)]), part[R, 2F] = partial sums of d(suv) over NVIT_SWIGLU_BWD_PART_ROWS rows each, for
+ *   whole row tiles: R = ceil(M / NVIT_SWIGLU_BWD_TILE_ROWS) * NVIT_SWIGLU_BWD_TILE_ROWS / NVIT_SWIGLU_BWD_PART_ROWS (natural
+ *   order; reduce with nvit_colsum_reduce).  Replaces nvit_gemm_nt + nvit_swiglu_bwd.  Requires F % 256 == 0. */
+#define NVIT_SWIGLU_BWD_TILE_ROWS 256
+#define NVIT_SWIGLU_BWD_PART_ROWS 128
 /* Tile scheduling of the persistent NT GEMM kernels: 0 = static round-robin (default), 1 = dynamic per-XCD ticket
  * counters: robust when other kernels (RCCL) hold some CUs.  The data-parallel wrapper (parallel.py) selects dynamic. */
 int nvit_set_gemm_sched(int dynamic);
@@ -210,13 +229,19 @@ int nvit_gemm_tn(int dt, const void* A, int lda, const void* B, int ldb, float* 
 /* ---- row-wise fused ops on the fp32 residual stream --------------------------------
  * nvit_lerp_fwd: out = nrm(nrm(h) + |alpha*c_a| * (nrm(y) - nrm(h)))   (model.py:134-142,159-167)
  * if skip_x != NULL additionally out = nrm(out*skip[0] + skip_x)         (norm_skip, model.py:84-87,452)
- * h, skip_x fp32 [M,C]; y of type y_dt; out fp32; out_lo (type dt, may be NULL) = cast(out). */
+ * h, skip_x fp32 [M,C]; y of type y_dt; out fp32; out_lo (type dt, may be NULL) = cast(out).
+ * Every row kernel of this section (and nvit_pool_ln_*, nvit_scatter_rows) holds a row of at most NVIT_MAX_EMBD columns.
+ * The backward kernels that leave per-workgroup partial sums take nblk <= NVIT_MAX_PART_BLOCKS workgroups; those that
+ * leave them per WAVE write NVIT_ROW_WAVES rows per workgroup. */
+#define NVIT_MAX_EMBD 2048
+#define NVIT_MAX_PART_BLOCKS 4096
+#define NVIT_ROW_WAVES 4
 int nvit_lerp_fwd(int dt, const float* h, const void* y, int y_dt, const float* alpha, float c_a,
                   const float* skip_x, const float* skip, float* out, void* out_lo, int M, int C, void* stream);
 /* nvit_lerp_bwd: given dout, recomputes the forward and writes dh (fp32; += if accum_dh), dy (fp32
  * and/or type-dt copy, either may be NULL), dskip_x (fp32, written, only if skip_x), and per-WAVE
- * partial sums part_dlam [4*nblk, C] (d/d|alpha*c_a|) and part_dskip [4*nblk] (if skip_x).
- * nblk = number of 4-wave workgroups the caller sizes the partial buffers for (<= 4096).
+ * partial sums part_dlam [NVIT_ROW_WAVES*nblk, C] (d/d|alpha*c_a|) and part_dskip [NVIT_ROW_WAVES*nblk] (if skip_x).
+ * nblk = number of workgroups the caller sizes the partial buffers for (<= NVIT_MAX_PART_BLOCKS).
  * dout_add (bf16 [M,C] or NULL): the incoming gradient is dout + dout_add - lets the data-gradient GEMM that produced
  * dout_add store bf16 once instead of read-modify-writing the fp32 dout (the reference's autocast nn.Linear hands its
  * input gradient back in bf16 as well). */
@@ -239,7 +264,7 @@ int nvit_rmsnorm_bwd(const float* dout, const float* x, const float* w, const fl
  * [M,C], out_lo (type dt, may be NULL) = cast(out), rstd [M].  z itself is not stored.
  * nvit_res_rmsnorm_bwd: from g (+ g_add, type dt, may be NULL: a data-gradient GEMM's output) recomputes z = a + y and
  * writes dz fp32 (added to dz if accum), dz_lo (type dt, may be NULL) = cast(dz), and per-WAVE partial sums part_dw
- * [4*nblk, C] of d(w) (reduce with nvit_colsum_reduce).  nblk <= 4096 workgroups of 4 waves. */
+ * [NVIT_ROW_WAVES*nblk, C] of d(w) (reduce with nvit_colsum_reduce).  nblk <= NVIT_MAX_PART_BLOCKS workgroups. */
 int nvit_res_rmsnorm_fwd(int dt, const float* a, const void* y, int y_dt, const float* w, float eps, float* out,
                          void* out_lo, float* rstd, int M, int C, void* stream);
 int nvit_res_rmsnorm_bwd(int dt, const float* g, const void* g_add, const float* a, const void* y, int y_dt,
@@ -248,7 +273,7 @@ int nvit_res_rmsnorm_bwd(int dt, const float* g, const void* g_add, const float*
 /* nvit_res_skip_fwd: out = nrm((h + y) * skip[0] + x)  (norm_skip after a plain-ViT block, model.py:84-87,450-452);
  * h, x fp32 [M,C], y of type y_dt; out fp32, out_lo (type dt, may be NULL) = cast(out).
  * nvit_res_skip_bwd: dx = d(x) fp32 (written), dh = d(h + y) fp32, dh_lo (type dt, may be NULL) = cast(dh), and per-WAVE
- * partial sums part_dskip [4*nblk] of d(skip). */
+ * partial sums part_dskip [NVIT_ROW_WAVES*nblk] of d(skip). */
 int nvit_res_skip_fwd(int dt, const float* h, const void* y, int y_dt, const float* skip, const float* x, float* out,
                       void* out_lo, int M, int C, void* stream);
 int nvit_res_skip_bwd(int dt, const float* dout, const float* h, const void* y, int y_dt, const float* skip,
@@ -267,8 +292,8 @@ int nvit_norm_skip_bwd(const float* dout, const float* src, const float* tgt, co
  * rq, rk [M,H] fp32 = 1/||q_head||.
  * sqk == NULL: the head split alone (plain-ViT attention, model.py:97-100): q, k, v copied to [B,H,T,d] as they are
  * (type conversion only); rq, rk are not written.
- * d in {16, 32, 64, 128}, H*d <= 2048.  nvit_qknorm_bwd and nvit_heads_pad_bwd below run one kernel (heads_merge_kernel,
- * templated on the stored head width: here d itself); the forward has a kernel per layout. */
+ * d in {16, 32, 64, 128}, H*d <= NVIT_MAX_EMBD.  nvit_qknorm_bwd and nvit_heads_pad_bwd below run one kernel
+ * (heads_merge_kernel, templated on the stored head width: here d itself); the forward has a kernel per layout. */
 int nvit_qknorm_fwd(int dt, const void* q, int ldq, const void* k, int ldk, const void* v, int ldv,
                     const float* sqk, float c_q, void* qh, void* kh, void* vh, float* rq, float* rk, int B,
                     int T, int H, int d, void* stream);
@@ -281,10 +306,10 @@ int nvit_qknorm_bwd(int dt, const void* dqh, const void* dkh, const void* dvh, c
                     void* dk, int ldk, void* dv, int ldv, float* part_dsqk, int nblk, int B, int T, int H,
                     int d, void* stream);
 
-/* ---- zero-padded heads: head dims d that are no power of two on the dp = 128 attention kernels ----
+/* ---- zero-padded heads: head dims d that are no power of two on the dp = NVIT_PAD_HEAD_DIM attention kernels ----
  * The head tensors are [B,H,T,dp] with columns d..dp-1 stored as zeros (no score, no output column < d and no gradient
  * column < d changes); nvit_attn_fwd / _fwd_bounded / _bwd then run at head dim dp with the scale of the REAL d.
- * dp = 128, d % 8 == 0, 0 < d < dp, H*d <= 2048, any B*T >= 1.  Deterministic, no atomics.
+ * dp = NVIT_PAD_HEAD_DIM, d % 8 == 0, 0 < d < dp, H*d <= NVIT_MAX_EMBD, any B*T >= 1.  Deterministic, no atomics.
  * The backward kernel is that of nvit_qknorm_bwd at stored head width dp; lanes on a pad column load nothing.
  * nvit_heads_pad_fwd: nvit_qknorm_fwd from fp32 projections (dt NVIT_F32: fp32 head tensors, NVIT_BF16_F32IN: bf16)
  *   into qh, kh, vh [B,H,T,dp]; EVERY pad column is stored (as +0) on every launch.  sqk (compact [H*d]) given: the sum
@@ -295,6 +320,7 @@ int nvit_qknorm_bwd(int dt, const void* dqh, const void* dkh, const void* dvh, c
  *   in compact channel order.
  * nvit_pad_cols:   dst [M, H*dp] = src [M, H*d] with zero pads (dO; O for the dQ kernel's rowsum(dO*O) over dp columns).
  * nvit_unpad_cols: dst [M, H*d] = the first d columns of every head of src [M, H*dp] (O for the output projection). */
+#define NVIT_PAD_HEAD_DIM 128
 int nvit_heads_pad_fwd(int dt, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
                        const float* sqk, float c_q, void* qh, void* kh, void* vh, float* rq, float* rk,
                        float* sqk_pad, int B, int T, int H, int d, int dp, void* stream);
@@ -318,8 +344,10 @@ int nvit_swiglu_bwd(int dt, const void* dx, const void* uv, const float* suv, fl
  * (d|alpha c_a| -> d alpha); kind 2: plain*scale written to out[perm1(n)] (SwiGLU interleave -> natural order). */
 int nvit_colsum_reduce(const float* part, int nblk, int N, float* out, int accumulate, int kind, const float* ref,
                        float scale, void* stream);
-/* nvit_colsum_reduce_multi: up to 8 such reductions in ONE launch (host arrays of n entries; pointers as int64).  An item
- * may name a second partial array part_b (0 = none) whose reduced, scaled sum is added after the first one's. */
+/* nvit_colsum_reduce_multi: up to NVIT_COLSUM_REDUCE_MAX_ITEMS such reductions in ONE launch (host arrays of n entries;
+ * pointers as int64).  An item may name a second partial array part_b (0 = none) whose reduced, scaled sum is added after
+ * the first one's. */
+#define NVIT_COLSUM_REDUCE_MAX_ITEMS 8
 int nvit_colsum_reduce_multi(const int64_t* part, const int* nblk, const int64_t* part_b, const int* nblk_b, const int* N,
                              const int64_t* out, const int* accumulate, const int* kind, const int64_t* ref,
                              const float* scale, int n, void* stream);
@@ -335,12 +363,18 @@ int nvit_normalize_images(const void* in, int in_is_u8_hwc, float* out, int B, i
                           void* stream);
 /* On-device AutoAugment: the randomised half of the input pipeline, two launches per batch, no host
  * synchronisation, capturable in a hipGraph.  The ops are Pillow's, bit for bit (tests/augment_ref.py).
- * nvit_augment_draw: params int32 [B,2,8] = per image two ops, each (op id, seven arguments).  One Philox4x32-10 call per
- * image, key = seed, counter = (first_index + i, *step): r0 picks one of the P sub-policies, r1/r2 gate its two ops
- * against their probabilities (an op left out becomes Identity), bits 0/1 of r3 are their signs.  policy: device int32
- * [P,2,3] = (op id, probability as fp32 bits, magnitude index 0..9); argtab: device int32 [15,10,2,8], the parameter row
- * of every (op, magnitude index, sign) at this image size (the host computes it in fp64).  *step is a device int64 that
- * the kernel reads and then advances by one, so a graph replay draws fresh parameters. */
+ * nvit_augment_draw: params int32 [B,2,NVIT_AUG_ROW] = per image two ops, each (op id, seven arguments).  One
+ * Philox4x32-10 call per image, key = seed, counter = (first_index + i, *step): r0 picks one of the P sub-policies, r1/r2
+ * gate its two ops against their probabilities (an op left out becomes Identity), bits 0/1 of r3 are their signs.
+ * policy: device int32 [P,2,3] = (op id, probability as fp32 bits, magnitude index below NVIT_AUG_NMAG); argtab: device
+ * int32 [NVIT_AUG_NOPS,NVIT_AUG_NMAG,2,NVIT_AUG_ROW], the parameter row of every (op, magnitude index, sign) at this
+ * image size (the host computes it in fp64).  *step is a device int64 that the kernel reads and then advances by one, so
+ * a graph replay draws fresh parameters.  Image sides of nvit_augment_apply / nvit_mix_* are at most NVIT_AUG_MAX_SIDE
+ * (16.16 coordinates in 32 bits). */
+#define NVIT_AUG_ROW 8
+#define NVIT_AUG_NOPS 15
+#define NVIT_AUG_NMAG 10
+#define NVIT_AUG_MAX_SIDE 4096
 int nvit_augment_draw(const int* policy, int P, uint64_t seed, int64_t* step, int64_t first_index, const int* argtab,
                       int* params, int B, void* stream);
 /* nvit_augment_apply: in uint8 [B,H,W,C], C in {1,3}; per image the two ops of params in sequence, the second on the
@@ -353,12 +387,15 @@ int nvit_augment_apply(const void* in, const int* params, float* out_f32, void* 
  * an odd batch is its own partner and stays unmixed).
  * nvit_mix_draw: one Philox4x32-10 call per pair, key = seed with a domain constant xor-ed into its high word, counter =
  * (first_index + p, *step): r0 gates the pair against prob, r1 picks CutMix against switch_prob (only when both modes are
- * on), r2 indexes the mode's quantile table (q_mix / q_cut: device fp32 [1025], the Beta(alpha,alpha) quantile at k/1024,
- * computed by the host in fp64; NULL switches the mode off) and interpolates lambda linearly, r3 is the box centre.  The
- * CutMix box and its corrected lambda (timm's rand_bbox, correct_lam) are computed in fp64.  Written: table int32 [B,8] =
+ * on), r2 indexes the mode's quantile table (q_mix / q_cut: device fp32 [NVIT_MIX_KNOTS + 1], the Beta(alpha,alpha) quantile
+ * at k/NVIT_MIX_KNOTS, computed by the host in fp64; NULL switches the mode off) and interpolates lambda linearly, r3 is
+ * the box centre.  The CutMix box and its corrected lambda (timm's rand_bbox, correct_lam) are computed in fp64.
+ * Written: table int32 [B,NVIT_MIX_ROW] =
  * (mode 0 none / 1 Mixup / 2 CutMix, lambda as fp32 bits, y0, y1, x0, x1, partner row, 0), lam fp32 [B] and
  * y2 int64 [B] = labels[partner]; both rows of a pair carry the same lambda and box.  *step is a device int64 that the
  * kernel reads and then advances by one, as nvit_augment_draw does. */
+#define NVIT_MIX_ROW 8
+#define NVIT_MIX_KNOTS 1024
 int nvit_mix_draw(uint64_t seed, int64_t* step, int64_t first_index, const float* q_mix, const float* q_cut, float prob,
                   float switch_prob, const int64_t* labels, int* table, float* lam, int64_t* y2, int B, int H, int W,
                   void* stream);
@@ -397,9 +434,11 @@ int nvit_attn_bwd(int dt, int impl, const void* dout, const void* qh, const void
 
 /* nvit_attn_bwd_qknorm: MFMA attention backward (bf16, d=64) with nvit_qknorm_bwd fused into the epilogues:
  * writes token-major dq/dk/dv (type bf16, row stride ld elements, head h at column h*64) and the partial sums
- * part_q [B*ceil(Tq/128), C], part_k [B*ceil(Tk/128), C] of d/d(sqk*c_q) (reduce with nvit_colsum_reduce).
+ * part_q [B*ceil(Tq/NVIT_ATTN_BWD_PART_ROWS), C], part_k [B*ceil(Tk/NVIT_ATTN_BWD_PART_ROWS), C] of d/d(sqk*c_q) (reduce
+ * with nvit_colsum_reduce).
  * q_prescale: the factor the producer folded into qh (see nvit_attn_fwd_bounded); gradients are those of the plain form.
  * sqk == NULL (plain-ViT heads): dq/dk/dv stored token-major as they are; rq, rk, c_q, part_q, part_k are not used. */
+#define NVIT_ATTN_BWD_PART_ROWS 128
 int nvit_attn_bwd_qknorm(int dt, const void* dout, const void* qh, const void* kh, const void* vh, const void* o,
                          const float* lse, float scale, const float* rq, const float* rk, const float* sqk, float c_q,
                          float q_prescale, void* dq, int ldq, void* dk, void* dv, int ldkv, float* part_q, float* part_k,
@@ -418,7 +457,9 @@ int nvit_attn_heads_fwd(int dt, const float* q, int ldq, const float* k, const f
                         float c_q, float scale, void* o, float* lse, int M, int H, int d, void* stream);
 /* Backward: dO [M, C] contiguous (type dt) -> dq [M, lddq], dk and dv [M, lddkv] (type dt), the normalise backward
  * included; part_dsqk [nblk, C] fp32 partial sums of d/d(sqk*c_q), one row per workgroup, fixed order (reduce with
- * nvit_colsum_reduce).  sqk == NULL: plain heads, part_dsqk is not written.  nblk in 1..8192 workgroups. */
+ * nvit_colsum_reduce).  sqk == NULL: plain heads, part_dsqk is not written.  nblk in 1..NVIT_ATTN_HEADS_BWD_MAX_BLOCKS
+ * workgroups. */
+#define NVIT_ATTN_HEADS_BWD_MAX_BLOCKS 8192
 int nvit_attn_heads_bwd(int dt, const void* dout, const float* q, int ldq, const float* k, const float* v, int ldkv,
                         const float* sqk, float c_q, float scale, const float* lse, void* dq, int lddq, void* dk,
                         void* dv, int lddkv, float* part_dsqk, int nblk, int M, int H, int d, void* stream);
@@ -435,9 +476,13 @@ int nvit_im2col(int dt, const float* img, void* A_l, void* A_g, int B, int ch, i
  * Patches are gathered from img fp32 [B,ch,S,S] into LDS (same geometry rules as nvit_im2col), split into bf16
  * hi + lo on the fly and multiplied on the bf16 MFMA as hi*hi + lo*hi + hi*lo (fp32-accurate to ~2^-16 relative).
  * w_l / w_g: split weight images [C, 2*Kp] from nvit_shadow_weights (perm 2), Kp = nvit_patch_embed_kp(ch*P*P).
- * a_l / a_g: optional bf16 [ceil(M/256)*256, Kp] outputs = the rounded patch rows (columns >= K zero), the saved
- * operand of the weight-gradient GEMM; NULL to skip.  lo_l / lo_g: optional bf16 [M, C] twins of out_l / out_g (the
- * operands of the q and k/v projections; needs C % 8 == 0); NULL to skip.  b_l / b_g may be NULL. */
+ *   nvit_patch_embed_kp(K) = K rounded up to whole stages of NVIT_PATCH_EMBED_K_STEP patch elements.
+ * a_l / a_g: optional bf16 [M rounded up to whole NVIT_PATCH_EMBED_TILE_ROWS, Kp] outputs = the rounded patch rows
+ * (columns >= K zero), the saved operand of the weight-gradient GEMM; NULL to skip.  lo_l / lo_g: optional bf16 [M, C]
+ * twins of out_l / out_g (the operands of the q and k/v projections; needs C % 8 == 0); NULL to skip.  b_l / b_g may be
+ * NULL. */
+#define NVIT_PATCH_EMBED_K_STEP 32
+#define NVIT_PATCH_EMBED_TILE_ROWS 256
 int nvit_patch_embed_kp(int K);
 int nvit_patch_embed_fwd(const float* img, const void* w_l, const float* b_l, const float* pos_l, float* out_l, void* lo_l,
                          void* a_l, const void* w_g, const float* b_g, const float* pos_g, float* out_g, void* lo_g,

@@ -7,21 +7,43 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # (NVIT_LIB: experiments with an alternative build of the same sources, e.g. tools/ab_lib.sh; never set in product use)
 LIB_PATH = os.environ.get("NVIT_LIB") or os.path.join(_HERE, "libnvit_hip.so")
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "nvit_hip.h")
+
+
+def _header_constants() -> dict:
+    """Every `#define NVIT_<NAME> <integer>` of the C header, read from its text: importing needs no built library."""
+    try:
+        with open(HEADER_PATH) as f:
+            return {name: int(value) for name, value in re.findall(r"#define NVIT_(\w+)\s+(-?\d+)", f.read())}
+    except OSError as e:
+        raise ImportError(f"nvit_amd: cannot read the C header that holds the kernels' layout constants: {e}") from None
+
+
+HEADER = _header_constants()   # name without the NVIT_ prefix -> value
+
+
+def const(name: str) -> int:
+    """NVIT_<name> of include/nvit_hip.h, where every number that host and kernels share is written; for use at import."""
+    if name not in HEADER:
+        raise ImportError(f"nvit_amd: {HEADER_PATH} has no integer `#define NVIT_{name}`")
+    return HEADER[name]
+
 
 F32, BF16, BF16_F32IN = 0, 1, 3
 KID_NAMES = ["gemm_nt", "gemm_tn", "attn_fwd", "attn_bwd", "rowops", "renorm", "shadow", "patchify", "misc", "gemm_f32",
              "gemm_swiglu", "gemm_qknorm", "gemm_swiglu_bwd", "optim", "gemm_swiglu_act"]
-RENORM_ROWS_PER_ITEM = 64
-RENORM_COLS_PER_ITEM = 64
-RENORM_TALL_ROWS = 1152           # column-normalised matrices with more rows take the narrow panel / slab
-RENORM_TALL_COLS_PER_ITEM = 32
-RENORM_MAX_ROWS_DIM0 = 2048
-MAX_EMBD = 2048                   # widest row the row kernels hold (lerp, norm_skip, rmsnorm, res_*, qknorm, pool_ln, ...)
-ATTN_HEADS_MAX_H = 32   # include/nvit_hip.h NVIT_ATTN_HEADS_MAX_H
+RENORM_ROWS_PER_ITEM = const("RENORM_ROWS_PER_ITEM")
+RENORM_COLS_PER_ITEM = const("RENORM_COLS_PER_ITEM")
+RENORM_TALL_ROWS = const("RENORM_TALL_ROWS")   # column-normalised matrices with more rows take the narrow panel
+RENORM_TALL_COLS_PER_ITEM = const("RENORM_TALL_COLS_PER_ITEM")
+RENORM_MAX_ROWS_DIM0 = const("RENORM_MAX_ROWS_DIM0")
+MAX_EMBD = const("MAX_EMBD")   # widest row the row kernels hold (lerp, norm_skip, rmsnorm, res_*, qknorm, pool_ln, ...)
+ATTN_HEADS_MAX_H = const("ATTN_HEADS_MAX_H")
 
 _vp, _i, _f, _i64 = C.c_void_p, C.c_int, C.c_float, C.c_int64
 

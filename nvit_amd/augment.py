@@ -28,9 +28,10 @@ OPS = ("Identity", "ShearX", "ShearY", "TranslateX", "TranslateY", "Rotate", "Br
 _ID = {n: i for i, n in enumerate(OPS)}
 _AFFINE = ("ShearX", "ShearY", "TranslateX", "TranslateY", "Rotate")
 _ENHANCE = ("Brightness", "Color", "Contrast", "Sharpness")
-N_MAGNITUDES = 10
-ROW = 8           # ints per op in the parameter table: id + seven arguments
-MAX_SIDE = 4096   # nvit_augment_apply: 16.16 coordinates in 32 bits
+N_MAGNITUDES = _lib.const("AUG_NMAG")
+ROW = _lib.const("AUG_ROW")             # ints per op in the parameter table: id + seven arguments
+MAX_SIDE = _lib.const("AUG_MAX_SIDE")   # nvit_augment_apply: 16.16 coordinates in 32 bits
+assert len(OPS) == _lib.const("AUG_NOPS"), "the op ids of nvit_augment_apply (include/nvit_hip.h NVIT_AUG_NOPS)"
 
 
 def _sub(a, pa, ma, b, pb, mb):
@@ -241,7 +242,54 @@ class AugmentedBatch:
         return self.augment(self.u8)
 
 
-class AutoAugment:
+class DeviceStepCounter:
+    """What the counter-based draws (AutoAugment, Mixup) share: seed, first_index and the step counter, a device int64 that
+    the draw kernel advances (a host int until `.to(device)`); `state_dict()` is (seed, step)."""
+
+    def __init__(self, seed: int, first_index: int):
+        for what, v, hi in (("seed", seed, 2 ** 64), ("first_index", first_index, 2 ** 62)):
+            if isinstance(v, bool) or not isinstance(v, int):
+                raise TypeError(f"{what} must be an int")
+            if not 0 <= v < hi:
+                raise ValueError(f"{what} must be in [0, {hi})")
+        self.seed, self.first_index = seed, first_index
+        self.device: Optional[torch.device] = None
+        self._step_host = 0          # until .to(device)
+        self._step: Optional[Tensor] = None
+
+    def _step_to(self, device) -> torch.device:   # the common half of `.to(device)`: the counter moves, keeping its count
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError(f"{type(self).__name__} runs on the HIP device (no CPU path)")
+        step = self.step
+        self.device = device
+        self._step = torch.tensor([step], dtype=torch.int64).to(device)
+        return device
+
+    @property
+    def step(self) -> int:
+        """Steps drawn so far (reads the device counter: synchronises)."""
+        return self._step_host if self._step is None else int(self._step.item())
+
+    def state_dict(self) -> dict:
+        return {"seed": self.seed, "step": self.step}
+
+    def load_state_dict(self, state: dict) -> None:
+        seed, step = int(state["seed"]), int(state["step"])
+        if not 0 <= seed < 2 ** 64 or not 0 <= step < 2 ** 63:
+            raise ValueError(f"{type(self).__name__}.load_state_dict: seed or step out of range")
+        self.seed = seed
+        if self._step is None:
+            self._step_host = step
+        else:
+            self._step.fill_(step)   # in place: a captured graph holds this address
+
+    def _need_device(self):
+        if self._step is None:
+            raise RuntimeError(f"{type(self).__name__}: call .to(device) first (it runs on the HIP device, no CPU path)")
+
+
+class AutoAugment(DeviceStepCounter):
     """AutoAugment(policy="cifar10", seed=0, first_index=0, mean=0.5, std=0.5).to(device)
 
     policy: "cifar10", "imagenet" (the published tables, 25 sub-policies each), "cifar100" (the CIFAR-10 table: the
@@ -255,54 +303,20 @@ class AutoAugment:
 
     def __init__(self, policy="cifar10", seed: int = 0, first_index: int = 0, mean: float = 0.5, std: float = 0.5):
         self.policy = validate_policy(policy)
-        for what, v, hi in (("seed", seed, 2 ** 64), ("first_index", first_index, 2 ** 62)):
-            if isinstance(v, bool) or not isinstance(v, int):
-                raise TypeError(f"{what} must be an int")
-            if not 0 <= v < hi:
-                raise ValueError(f"{what} must be in [0, {hi})")
+        super().__init__(seed, first_index)
         if std == 0:
             raise ValueError("std must not be 0")
-        self.seed, self.first_index, self.mean, self.std = seed, first_index, float(mean), float(std)
-        self.device: Optional[torch.device] = None
-        self._step_host = 0          # until .to(device)
-        self._step: Optional[Tensor] = None
+        self.mean, self.std = float(mean), float(std)
         self._policy_dev: Optional[Tensor] = None
         self._argtabs = {}
 
     # ------------------------------------------------------------------ device state
     def to(self, device) -> "AutoAugment":
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise RuntimeError("AutoAugment runs on the HIP device (no CPU path)")
-        step = self.step
-        self.device = device
+        device = self._step_to(device)
         rows = [[_ID[n], _f32_bits(p), m] for sub in self.policy for (n, p, m) in sub]
         self._policy_dev = torch.tensor(rows, dtype=torch.int32).view(len(self.policy), 2, 3).to(device)
-        self._step = torch.tensor([step], dtype=torch.int64).to(device)
         self._argtabs = {}
         return self
-
-    @property
-    def step(self) -> int:
-        """Steps drawn so far (reads the device counter: synchronises)."""
-        return self._step_host if self._step is None else int(self._step.item())
-
-    def state_dict(self) -> dict:
-        return {"seed": self.seed, "step": self.step}
-
-    def load_state_dict(self, state: dict) -> None:
-        seed, step = int(state["seed"]), int(state["step"])
-        if not 0 <= seed < 2 ** 64 or not 0 <= step < 2 ** 63:
-            raise ValueError("AutoAugment.load_state_dict: seed or step out of range")
-        self.seed = seed
-        if self._step is None:
-            self._step_host = step
-        else:
-            self._step.fill_(step)   # in place: a captured graph holds this address
-
-    def _need_device(self):
-        if self._step is None:
-            raise RuntimeError("AutoAugment: call .to(device) first (it runs on the HIP device, no CPU path)")
 
     def _argtab(self, H: int, W: int) -> Tensor:
         t = self._argtabs.get((H, W))

@@ -297,7 +297,7 @@ extern "C" int nvit_attn_heads_bwd(int dt, const void* dout, const float* q, int
   if (rc != NVIT_OK) return rc;
   const int C = H * d;
   NVIT_REQUIRE(lddq >= C && lddkv >= C && lddq % 4 == 0 && lddkv % 4 == 0, "attn_heads_bwd: bad output ld");
-  NVIT_REQUIRE(nblk > 0 && nblk <= 8192, "attn_heads_bwd: nblk %d out of range", nblk);
+  NVIT_REQUIRE(nblk > 0 && nblk <= NVIT_ATTN_HEADS_BWD_MAX_BLOCKS, "attn_heads_bwd: nblk %d out of range", nblk);
   NVIT_REQUIRE(!sqk || part_dsqk, "attn_heads_bwd: part_dsqk is required with sqk");
   HeadsArgs a{q, k, v, ldq, ldkv, sqk, c_q, scale, dout, nullptr, const_cast<float*>(lse), dq, dk, dv, lddq, lddkv,
               part_dsqk, M, H};

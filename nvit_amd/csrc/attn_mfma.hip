@@ -1328,7 +1328,7 @@ extern "C" int nvit_set_attn_dkv_asm(int mode) {
 }
 
 // attention backward with the q/k-normalise backward fused into the epilogues: writes token-major dq/dk/dv
-// (row stride ld) and the partial sums part_q [B*ceil(Tq/128), C], part_k [B*ceil(Tk/128), C].
+// (row stride ld) and the partial sums part_q, part_k: one row per workgroup, NVIT_ATTN_BWD_PART_ROWS tokens each.
 int nvit_attn_bwd_mfma_fused(const void* dout, const void* qh, const void* kh, const void* vh, const void* o,
                              const float* lse, float* delta, float scale, const float* rq, const float* rk, const float* sqk,
                              float c_q, float qpre, void* dq, int ldq, void* dk, void* dv, int ldkv, float* part_q,
@@ -1336,6 +1336,7 @@ int nvit_attn_bwd_mfma_fused(const void* dout, const void* qh, const void* kh, c
   NVIT_REQUIRE(d == 64, "attn_bwd_qknorm: the fused kernels support head dim 64 only (got %d)", d);
   NVIT_REQUIRE(ldq % 4 == 0 && ldkv % 4 == 0, "attn_bwd: leading dims must be multiples of 4");
   NVIT_REQUIRE(o != nullptr && delta != nullptr, "attn_bwd: the attention output and the [2,B,H,Tq] side buffer are required");
+  static_assert(Geo<64>::KWG == NVIT_ATTN_BWD_PART_ROWS, "one partial row per workgroup of the dQ and dK/dV kernels");
   dim3 gq((unsigned)(cdiv(Tq, 128) * B * H)), gk((unsigned)(cdiv(Tk, 128) * B * H));
   NVIT_REQUIRE(qpre > 0.f, "attn_bwd: the q pre-scale must be positive (got %g)", (double)qpre);
   QkFuse fq{rq, sqk, (bf16*)dq, nullptr, part_q, c_q, 1.0f / qpre, ldq};

@@ -30,9 +30,9 @@ namespace {
 
 constexpr int AUG_THREADS = 1024;
 constexpr int AUG_HIST_COPIES = 4;   // waves spread over four histogram copies: a low-contrast image hits few bins
-constexpr int AUG_ROW = 8;           // ints per op in the parameter table
-constexpr int AUG_NOPS = 15;
-constexpr int AUG_NMAG = 10;
+constexpr int AUG_ROW = NVIT_AUG_ROW;           // ints per op in the parameter table
+constexpr int AUG_NOPS = NVIT_AUG_NOPS;
+constexpr int AUG_NMAG = NVIT_AUG_NMAG;
 
 enum AugOp { OP_IDENTITY = 0, OP_SHEAR_X, OP_SHEAR_Y, OP_TRANSLATE_X, OP_TRANSLATE_Y, OP_ROTATE, OP_BRIGHTNESS, OP_COLOR,
              OP_CONTRAST, OP_SHARPNESS, OP_POSTERIZE, OP_SOLARIZE, OP_AUTOCONTRAST, OP_EQUALIZE, OP_INVERT };
@@ -288,14 +288,14 @@ __global__ __launch_bounds__(AUG_THREADS) void augment_apply_kernel(const unsign
 
 // ------------------------------------------------------------------------------------------------ Mixup / CutMix
 // (tests/mix_ref.py is the numpy twin.)  Rows i and B-1-i of the batch form pair i.
-constexpr int MIX_ROW = 8;                  // mode, lambda bits, y0, y1, x0, x1, partner row, 0
+constexpr int MIX_ROW = NVIT_MIX_ROW;                  // mode, lambda bits, y0, y1, x0, x1, partner row, 0
 constexpr unsigned MIX_DOMAIN = 0x4D495821u;   // xor-ed into the key's high word: not AutoAugment's stream
-constexpr int MIX_KNOTS = 1024;             // the quantile tables hold MIX_KNOTS + 1 floats
+constexpr int MIX_KNOTS = NVIT_MIX_KNOTS;             // the quantile tables hold MIX_KNOTS + 1 floats
 enum MixMode { MIX_NONE = 0, MIX_MIXUP = 1, MIX_CUTMIX = 2 };
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
-// q_mix / q_cut: the Beta(alpha, alpha) quantile at k/1024, k = 0..1024, of the mode's alpha; NULL = mode off.
+// q_mix / q_cut: the Beta(alpha, alpha) quantile at k/MIX_KNOTS, k = 0..MIX_KNOTS, of the mode's alpha; NULL = mode off.
 __global__ __launch_bounds__(256) void mix_draw_kernel(unsigned long long seed, long long* step_ctr, long long first_index,
                                                        const float* __restrict__ q_mix, const float* __restrict__ q_cut,
                                                        float prob, float switch_prob, const int64_t* __restrict__ labels,
@@ -432,7 +432,7 @@ extern "C" int nvit_mix_draw(uint64_t seed, int64_t* step, int64_t first_index, 
                              float prob, float switch_prob, const int64_t* labels, int* table, float* lam, int64_t* y2,
                              int B, int H, int W, void* stream) {
   NVIT_REQUIRE(step && labels && table && lam && y2 && B > 0 && first_index >= 0, "mix_draw: bad arguments");
-  NVIT_REQUIRE(H > 0 && W > 0 && H <= 4096 && W <= 4096, "mix_draw: images up to 4096 x 4096");
+  NVIT_REQUIRE(H > 0 && W > 0 && H <= NVIT_AUG_MAX_SIDE && W <= NVIT_AUG_MAX_SIDE, "mix_draw: sides up to %d", NVIT_AUG_MAX_SIDE);
   NVIT_REQUIRE(prob >= 0.f && prob <= 1.f && switch_prob >= 0.f && switch_prob <= 1.f, "mix_draw: probabilities in [0,1]");
   hipStream_t s = (hipStream_t)stream;
   ProfScope ps(NVIT_KID_PATCHIFY, 0.0, (double)B * (MIX_ROW * 4.0 + 20.0), s);
@@ -473,7 +473,7 @@ extern "C" int nvit_augment_apply(const void* in, const int* params, float* out_
   NVIT_REQUIRE(in && params && ws && (out_f32 || out_u8) && B > 0 && H > 0 && W > 0 && (C == 1 || C == 3),
                "augment_apply: bad arguments (C must be 1 or 3)");
   // 16.16 coordinates and the 32-bit histogram sums stay in range
-  NVIT_REQUIRE(H <= 4096 && W <= 4096, "augment_apply: images up to 4096 x 4096");
+  NVIT_REQUIRE(H <= NVIT_AUG_MAX_SIDE && W <= NVIT_AUG_MAX_SIDE, "augment_apply: sides up to %d", NVIT_AUG_MAX_SIDE);
   const size_t stride = ((size_t)H * W * C + 255) / 256 * 256;
   NVIT_REQUIRE(ws_bytes >= 0 && (size_t)ws_bytes >= 2 * (size_t)B * stride,
                "augment_apply: workspace needs 2 * B * round_up(H*W*C, 256) bytes");

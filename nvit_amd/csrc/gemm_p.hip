@@ -45,6 +45,8 @@ __device__ __forceinline__ void wait_vmcnt() {
 // kernels hold some CUs (the RCCL all-reduce of the data-parallel step), workgroups that start late simply take fewer
 // tiles instead of delaying the whole launch by their start offset.  The last workgroup out resets the counters, so
 // a launch leaves them at zero (hipGraph-replay safe).
+static_assert(PCfg<4>::PBM == NVIT_SWIGLU_BWD_TILE_ROWS && PCfg<8>::PBM == NVIT_SWIGLU_BWD_TILE_ROWS &&
+              NVIT_SWIGLU_BWD_PART_ROWS == 1 << 7, "the SwiGLU-backward epilogue's part rows: m_base >> 7 over whole row tiles");
 template <typename T, int FM, int EPI, bool DYN>
 __global__ __launch_bounds__(512) void gemm_nt_persistent_kernel(NtArgs g, int tiles_m, int ntiles, unsigned* sched) {
   using Cfg = PCfg<FM>;

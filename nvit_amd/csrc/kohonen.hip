@@ -57,7 +57,7 @@ __global__ void gather_rows_kernel(const float* nodes, const long long* idx, flo
 
 // dnodes[n][c] = sum over rows m with idx[m] == n of dout[m][c], rows visited in increasing m (deterministic).
 // One workgroup per node: the index array is scanned 256 entries at a time (one compare per thread, wave ballots
-// through LDS), then every thread walks the set bits in order and accumulates its columns (C <= 2048).
+// through LDS), then every thread walks the set bits in order and accumulates its columns (C <= NVIT_MAX_EMBD).
 __global__ __launch_bounds__(256) void scatter_rows_kernel(const float* dout, const long long* idx, float* dnodes,
                                                            long long M, int C) {
   __shared__ unsigned long long masks[4];
@@ -375,7 +375,7 @@ extern "C" int nvit_scatter_rows(const float* dout, const int64_t* idx, float* d
                                  void* stream) {
   hipStream_t s = (hipStream_t)stream;
   ProfScope ps(NVIT_KID_MISC, 0.0, (double)M * C * 4.0, s);
-  NVIT_REQUIRE(C <= 2048, "scatter_rows: C must be <= 2048");
+  NVIT_REQUIRE(C <= NVIT_MAX_EMBD, "scatter_rows: C must be <= %d", NVIT_MAX_EMBD);
   hipLaunchKernelGGL(scatter_rows_kernel, dim3(N), dim3(256), 0, s, dout, (const long long*)idx, dnodes, (long long)M,
                      C);
   NVIT_CHECK_LAUNCH("scatter_rows");
@@ -430,7 +430,7 @@ extern "C" int nvit_som_update_dev(float* nodes, const float* x, const int64_t* 
 
 extern "C" int nvit_cos_consistency_fwd(const float* a, const float* b, float* stats, float* part, int nblk, float* loss,
                                         int64_t M, int C, void* stream) {
-  NVIT_REQUIRE(C % 4 == 0 && nblk > 0 && nblk <= 4096, "cos_consistency_fwd: bad arguments");
+  NVIT_REQUIRE(C % 4 == 0 && nblk > 0 && nblk <= NVIT_MAX_PART_BLOCKS, "cos_consistency_fwd: bad arguments");
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(cos_fwd_kernel, dim3(nblk), dim3(256), 0, s, a, b, part, stats, (int)M, C);
   NVIT_CHECK_LAUNCH("cos_fwd");
@@ -449,7 +449,7 @@ extern "C" int nvit_cos_consistency_bwd(const float* a, const float* b, const fl
 
 extern "C" int nvit_huber_fwd(const float* a, const float* b, float* part, int nblk, float* loss, int64_t n,
                               void* stream) {
-  NVIT_REQUIRE(n % 4 == 0 && nblk > 0 && nblk <= 4096, "huber_fwd: bad arguments");
+  NVIT_REQUIRE(n % 4 == 0 && nblk > 0 && nblk <= NVIT_MAX_PART_BLOCKS, "huber_fwd: bad arguments");
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(huber_fwd_kernel, dim3(nblk), dim3(256), 0, s, a, b, part, (long long)(n / 4));
   NVIT_CHECK_LAUNCH("huber_fwd");

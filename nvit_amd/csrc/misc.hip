@@ -215,7 +215,7 @@ extern "C" int nvit_im2col(int dt, const float* img, void* A_l, void* A_g, int B
 extern "C" int nvit_pool_ln_fwd(int dt, const float* x, const float* w, const float* b, float eps, float* pooled,
                                 float* ln, void* ln_lo, float* stats, float* ws, int nchunk, int B, int T, int C,
                                 void* stream) {
-  NVIT_REQUIRE(C % 4 == 0 && C <= 2048 && nchunk > 0, "pool_ln_fwd: bad C=%d", C);
+  NVIT_REQUIRE(C % 4 == 0 && C <= NVIT_MAX_EMBD && nchunk > 0, "pool_ln_fwd: bad C=%d", C);
   hipStream_t s = (hipStream_t)stream;
   ProfScope ps(NVIT_KID_MISC, 0.0, (double)B * T * C * 4.0, s);
   hipLaunchKernelGGL(pool_partial_kernel, dim3(nchunk, B), dim3(256), 0, s, x, ws, nchunk, T, C);
@@ -230,7 +230,7 @@ extern "C" int nvit_pool_ln_fwd(int dt, const float* x, const float* w, const fl
 
 extern "C" int nvit_pool_ln_bwd(const float* dln, const float* pooled, const float* w, const float* stats, float* dx,
                                 float* dw, float* db, int accumulate, int B, int T, int C, void* stream) {
-  NVIT_REQUIRE(C <= 2048, "pool_ln_bwd: bad C=%d", C);
+  NVIT_REQUIRE(C <= NVIT_MAX_EMBD, "pool_ln_bwd: bad C=%d", C);
   hipStream_t s = (hipStream_t)stream;
   ProfScope ps(NVIT_KID_MISC, 0.0, (double)B * T * C * 4.0, s);
   int nchunk = cdiv(2048, B);
@@ -244,7 +244,7 @@ extern "C" int nvit_pool_ln_bwd(const float* dln, const float* pooled, const flo
 
 extern "C" int nvit_recon_loss(const float* raw, const float* img, float* part, int nblk, float* loss, int B, int ch,
                                int S, int P, void* stream) {
-  NVIT_REQUIRE(nblk > 0 && nblk <= 4096 && S % P == 0, "recon_loss: bad arguments");
+  NVIT_REQUIRE(nblk > 0 && nblk <= NVIT_MAX_PART_BLOCKS && S % P == 0, "recon_loss: bad arguments");
   hipStream_t s = (hipStream_t)stream;
   ProfScope ps(NVIT_KID_MISC, 0.0, (double)B * ch * S * S * 8.0, s);
   hipLaunchKernelGGL(recon_partial_kernel, dim3(nblk), dim3(256), 0, s, raw, img, part, B, ch, S, P);

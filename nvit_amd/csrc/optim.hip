@@ -14,24 +14,25 @@
 // With skip_nonfinite (the reference's GradScaler, train.py:930-942, leaves out the step of a batch whose gradients hold
 // inf or NaN) the order is grad_sqnorm, adamw_tick_guarded_kernel, adamw_renorm_kernel<const float*>: the tick sums the
 // partials once, decides, and leaves a flag; the update returns before its item loop when the flag is set.
-// Item kinds: -1 = plain chunk of 8192 elements; 1 = 16 rows, one wave per row (row norm, dim=1; cols <= 2048);
-//             0 = slab of all rows x 32 columns kept in LDS (column norm, dim=0), all rows x 16 columns for matrices
-//                 of more than 1152 rows (rows <= 2048): the slab and its partial sums must fit the 160 KiB of a CU.
+// Item kinds: -1 = plain chunk of OPT_CHUNK elements; 1 = OPT_ROWS_PER_ITEM rows, one wave per row (row norm, dim=1; cols
+//             <= OPT_WIDE_COLS); 0 = slab of all rows x OPT_SLAB_COLS columns kept in LDS (column norm, dim=0), x OPT_TALL_COLS
+//             above OPT_SLAB_ROWS rows (rows <= OPT_TALL_ROWS): the slab and its partial sums must fit the 160 KiB of a CU.
 // AdamW arithmetic follows torch's (decoupled weight decay, bias corrections passed in from the host in double):
 //   p *= 1 - lr*wd;  m = b1*m + (1-b1)*g;  v = b2*v + (1-b2)*g*g;  p -= (lr/bc1) * m / (sqrt(v)/sqrt(bc2) + eps).
 #include "common.h"
 
 namespace {
 
-constexpr int OPT_COLS = 10;       // table columns (int64)
-constexpr int OPT_CHUNK = 8192;    // elements per plain item and per grad-norm chunk
-constexpr int OPT_ROWS_PER_ITEM = 16;  // one wave per row
-constexpr int OPT_SLAB_COLS = 32;        // column slab of a matrix of at most OPT_SLAB_ROWS rows
-constexpr int OPT_SLAB_ROWS = 1152;      //   (1152 x 32 + 128 x 32 partial sums) x 4 B = 160 KiB, all of a CU's LDS
-constexpr int OPT_TALL_COLS = 16;        // column slab of a taller matrix
-constexpr int OPT_TALL_ROWS = 2048;      //   (2048 x 16 + 256 x 16 partial sums) x 4 B = 144 KiB
-constexpr int OPT_ROW_COLS = 1536;       // a row of at most this many columns stays in registers (6 float4 per lane),
-constexpr int OPT_WIDE_COLS = 2048;      //   a wider one is parked in LDS: 16 waves x 2048 x 4 B = 128 KiB
+constexpr int OPT_COLS = NVIT_OPT_TABLE_COLS;  // table columns (int64)
+constexpr int OPT_CHUNK = NVIT_OPT_CHUNK;      // elements per plain item and per grad-norm chunk
+constexpr int OPT_ROWS_PER_ITEM = NVIT_OPT_ROWS_PER_ITEM;  // one wave per row
+constexpr int OPT_SLAB_COLS = NVIT_OPT_SLAB_COLS;  // column slab of a matrix of at most OPT_SLAB_ROWS rows
+constexpr int OPT_SLAB_ROWS = NVIT_OPT_SLAB_ROWS;  //   (1152 x 32 + 128 x 32 partial sums) x 4 B = 160 KiB, all of a CU's LDS
+constexpr int OPT_TALL_COLS = NVIT_OPT_TALL_COLS;  // column slab of a taller matrix
+constexpr int OPT_TALL_ROWS = NVIT_OPT_TALL_ROWS;  //   (2048 x 16 + 256 x 16 partial sums) x 4 B = 144 KiB
+constexpr int OPT_ROW_COLS = NVIT_OPT_ROW_COLS;    // a row of at most this many columns stays in registers (6 float4 per lane),
+constexpr int OPT_WIDE_COLS = NVIT_OPT_WIDE_COLS;  //   a wider one is parked in LDS: 16 waves x 2048 x 4 B = 128 KiB
+static_assert(OPT_ROWS_PER_ITEM == 1024 / 64 && OPT_ROW_COLS == 6 * 64 * 4, "a wave per row, 6 float4 per lane of it");
 
 struct OptRow {
   float* p;
@@ -261,7 +262,7 @@ __global__ __launch_bounds__(1024) void adamw_renorm_kernel(const int64_t* table
         }
       }
     } else if (r.kind == 1 && r.cols <= OPT_ROW_COLS) {
-      // rows: one wave per row; the updated row stays in registers (cols <= 1536, multiple of 4) for the norm
+      // rows: one wave per row; the updated row stays in registers (cols <= OPT_ROW_COLS, multiple of 4) for the norm
       const int row = local * OPT_ROWS_PER_ITEM + wid;
       if (row < r.rows) {
         const size_t off = (size_t)row * r.cols;
@@ -295,7 +296,7 @@ __global__ __launch_bounds__(1024) void adamw_renorm_kernel(const int64_t* table
         }
       }
     } else if (r.kind == 1) {
-      // wide rows (cols <= 2048): 8 float4 per lane would cost the kernel its register budget, so each wave parks its
+      // wide rows (cols <= OPT_WIDE_COLS): 8 float4 per lane would cost the kernel its register budget, so each wave parks its
       // updated row in LDS (16 x cols x 4 B <= 128 KiB, see nvit_adamw_renorm) between the update and the scaled store
       const int row = local * OPT_ROWS_PER_ITEM + wid;
       if (row < r.rows) {
@@ -367,7 +368,7 @@ extern "C" int nvit_adamw_tick(float* hyper, double beta1, double beta2, void* s
 
 extern "C" int nvit_grad_sqnorm(const int64_t* table, int n, int total_chunks, float* partial, int npart,
                                 void* stream) {
-  NVIT_REQUIRE(table && partial && n > 0 && total_chunks > 0 && npart > 0 && npart <= 4096,
+  NVIT_REQUIRE(table && partial && n > 0 && total_chunks > 0 && npart > 0 && npart <= NVIT_OPT_MAX_PART,
                "grad_sqnorm: bad arguments");
   hipStream_t s = (hipStream_t)stream;
   ProfScope ps(NVIT_KID_OPTIM, 0.0, (double)total_chunks * OPT_CHUNK * 4.0, s);
@@ -387,7 +388,7 @@ static int adamw_renorm_launch(const int64_t* table, int n, int total_items, int
                OPT_TALL_ROWS);
   NVIT_REQUIRE(hyper || (bias_correction1 > 0.0 && bias_correction2 > 0.0),
                "adamw_renorm: bias corrections must be > 0");
-  NVIT_REQUIRE(!partial || (npart > 0 && npart <= 4096), "adamw_renorm: bad npart");
+  NVIT_REQUIRE(!partial || (npart > 0 && npart <= NVIT_OPT_MAX_PART), "adamw_renorm: bad npart");
   AdamArgs a;
   a.b1 = beta1;
   a.b2 = beta2;
@@ -403,8 +404,9 @@ static int adamw_renorm_launch(const int64_t* table, int n, int total_items, int
   static_assert(OPT_TALL_ROWS * OPT_TALL_COLS <= OPT_SLAB_ROWS * OPT_SLAB_COLS, "the tall slab fits the LDS of the wide one");
   static_assert((OPT_SLAB_ROWS * OPT_SLAB_COLS + 4096) * 4 <= 160 * 1024, "slab + partial sums fit the LDS of a CU");
   // (Rows of more than OPT_ROW_COLS columns are parked in the same LDS, 16 x cols x 4 B: the caller passes
-  // max_slab_rows >= 1024 for a table that holds such a matrix, see nvit_hip.h.)
-  static_assert(16 * OPT_WIDE_COLS <= 1024 * OPT_SLAB_COLS + 4096, "max_slab_rows = 1024 covers 16 parked wide rows");
+  // max_slab_rows >= NVIT_OPT_WIDE_LDS_ROWS for a table that holds such a matrix, see nvit_hip.h.)
+  static_assert(OPT_ROWS_PER_ITEM * OPT_WIDE_COLS <= NVIT_OPT_WIDE_LDS_ROWS * OPT_SLAB_COLS + 4096 &&
+                NVIT_OPT_WIDE_LDS_ROWS <= OPT_SLAB_ROWS, "max_slab_rows = NVIT_OPT_WIDE_LDS_ROWS covers an item's parked rows");
   const int slab_rows = max_slab_rows > OPT_SLAB_ROWS ? OPT_SLAB_ROWS : max_slab_rows;
   const int lds = slab_rows > 0 ? (slab_rows * OPT_SLAB_COLS + 4096) * 4 : 64;
   static int lds_set[2] = {0, 0};  // per kernel
@@ -437,7 +439,7 @@ extern "C" int nvit_adamw_renorm(const int64_t* table, int n, int total_items, i
 extern "C" int nvit_adamw_tick_guarded(float* hyper, double beta1, double beta2, const float* partial, int npart,
                                        float* skip_state, void* stream) {
   NVIT_REQUIRE(hyper && beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0, "adamw_tick_guarded: bad arguments");
-  NVIT_REQUIRE(partial && skip_state && npart > 0 && npart <= 4096, "adamw_tick_guarded: bad partials or skip state");
+  NVIT_REQUIRE(partial && skip_state && npart > 0 && npart <= NVIT_OPT_MAX_PART, "adamw_tick_guarded: bad partials or skip state");
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(adamw_tick_guarded_kernel, dim3(1), dim3(1024), 0, s, hyper, beta1, beta2, partial, npart,
                      skip_state);

@@ -14,7 +14,8 @@
 
 namespace {
 
-constexpr int PE_TM = 256, PE_TN = 256;
+constexpr int PE_TM = NVIT_PATCH_EMBED_TILE_ROWS, PE_TN = 256;
+static_assert(NVIT_PATCH_EMBED_K_STEP == 1 << 5, "stages of 32 patch elements (Kp >> 5)");
 constexpr int PE_A_BYTES = PE_TM * 128, PE_W_BYTES = PE_TN * 128, PE_SLOT = PE_A_BYTES + PE_W_BYTES;
 constexpr int PE_LDS = 2 * PE_SLOT;  // 128 KiB ring; the epilogue scratch (8 x 2 KiB) reuses slot 0
 
@@ -241,7 +242,7 @@ __global__ __launch_bounds__(512) void patch_embed_kernel(PeArgs g) {
 }  // namespace
 
 // Padded patch length of the operand images (a whole number of 32-element stages).
-extern "C" int nvit_patch_embed_kp(int K) { return (K + 31) / 32 * 32; }
+extern "C" int nvit_patch_embed_kp(int K) { return cdiv(K, NVIT_PATCH_EMBED_K_STEP) * NVIT_PATCH_EMBED_K_STEP; }
 
 extern "C" int nvit_patch_embed_fwd(const float* img, const void* w_l, const float* b_l, const float* pos_l, float* out_l,
                                     void* lo_l, void* a_l, const void* w_g, const float* b_g, const float* pos_g,

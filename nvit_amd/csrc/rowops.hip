@@ -7,7 +7,8 @@
 
 namespace {
 
-constexpr int ROW_WAVES = 4;  // waves (rows in flight) per 256-thread workgroup
+constexpr int ROW_WAVES = NVIT_ROW_WAVES;  // waves (rows in flight) per 256-thread workgroup
+static_assert(ROW_WAVES * 64 == 256, "the row kernels launch 256 threads");
 
 // Each lane owns NV float4 groups of a row: columns (i*64 + lane)*4 .. +3, i < NV, while < C.
 template <int NV>
@@ -342,7 +343,7 @@ __global__ __launch_bounds__(256) void norm_skip_bwd_kernel(const float* dout, c
 // lanes with pc % DP >= d load nothing and store the zeros.  With d == DP every lane inside the row is live and the stored
 // column is the token-major one: heads_merge_kernel is the backward of both layouts.  The forward keeps a kernel per
 // layout: the compact one issues all of a row's loads before any arithmetic, which the pass loop lost to at d = 128.
-constexpr int PAD_D = 128;
+constexpr int PAD_D = NVIT_PAD_HEAD_DIM;
 
 struct QkArgs {
   const void *q, *k, *v;   // projection outputs, token-major with row strides ld*
@@ -691,7 +692,7 @@ __global__ __launch_bounds__(1024) void colsum_reduce_kernel(const float* part, 
 // Several reductions of the kind above in ONE launch (the six parameter-gradient reductions of a block's backward were
 // six ~12 us launches on the critical stream, 0.9 ms per Base step).  An item may have a second partial array whose
 // reduced, scaled sum is added after the first one's (fixed order: e.g. the q and k contributions to d sqk).
-constexpr int CSR_MAX_ITEMS = 8;
+constexpr int CSR_MAX_ITEMS = NVIT_COLSUM_REDUCE_MAX_ITEMS;
 struct CsrItem {
   const float* part;
   const float* part_b;   // optional second partial array (same N), or NULL
@@ -1106,7 +1107,7 @@ static auto lerp_bwd_select(int C, int y_dt, int dt, bool has_add, bool has_skip
 extern "C" int nvit_lerp_fwd(int dt, const float* h, const void* y, int y_dt, const float* alpha, float c_a,
                              const float* skip_x, const float* skip, float* out, void* out_lo, int M, int C,
                              void* stream) {
-  NVIT_REQUIRE(C % 4 == 0 && C <= 2048 && M > 0, "lerp_fwd: C=%d must be a multiple of 4 and <= 2048", C);
+  NVIT_REQUIRE(C % 4 == 0 && C <= NVIT_MAX_EMBD && M > 0, "lerp_fwd: C=%d must be a multiple of 4 and <= %d", C, NVIT_MAX_EMBD);
   NVIT_REQUIRE(!skip_x || skip, "lerp_fwd: skip_x without skip");
   LerpFwdArgs a{h, y, alpha, c_a, skip_x, skip, out, out_lo, M, C};
   hipStream_t s = (hipStream_t)stream;
@@ -1131,17 +1132,17 @@ static int resident_blocks(void (*kernel)(LerpBwdArgs)) {
 }
 
 extern "C" int nvit_lerp_bwd_blocks(int dt, int y_dt, int C, int has_add, int has_skip, int accum) {
-  if (C % 4 != 0 || C <= 0 || C > 2048) return 0;
+  if (C % 4 != 0 || C <= 0 || C > NVIT_MAX_EMBD) return 0;
   const int n = resident_blocks(lerp_bwd_select(C, y_dt, dt, has_add, has_skip, accum));
-  return n > 4096 ? 4096 : n;
+  return n > NVIT_MAX_PART_BLOCKS ? NVIT_MAX_PART_BLOCKS : n;
 }
 
 extern "C" int nvit_lerp_bwd(int dt, const float* dout, const void* dout_add, const float* h, const void* y, int y_dt, const float* alpha,
                              float c_a, const float* skip_x, const float* skip, float* dh, int accum_dh, float* dy,
                              void* dy_lo, float* dskip_x, float* part_dlam, float* part_dskip, int nblk, int M,
                              int C, void* stream) {
-  NVIT_REQUIRE(C % 4 == 0 && C <= 2048 && M > 0, "lerp_bwd: C=%d must be a multiple of 4 and <= 2048", C);
-  NVIT_REQUIRE(nblk > 0 && nblk <= 4096, "lerp_bwd: nblk out of range");
+  NVIT_REQUIRE(C % 4 == 0 && C <= NVIT_MAX_EMBD && M > 0, "lerp_bwd: C=%d must be a multiple of 4 and <= %d", C, NVIT_MAX_EMBD);
+  NVIT_REQUIRE(nblk > 0 && nblk <= NVIT_MAX_PART_BLOCKS, "lerp_bwd: nblk out of range");
   NVIT_REQUIRE(!skip_x || (skip && dskip_x && part_dskip), "lerp_bwd: skip buffers missing");
   LerpBwdArgs a{dout, (const bf16*)dout_add, h, y, alpha, c_a, skip_x, skip, dh, accum_dh, dy, dy_lo, dskip_x, part_dlam, part_dskip, M, C};
   hipStream_t s = (hipStream_t)stream;
@@ -1156,7 +1157,7 @@ extern "C" int nvit_lerp_bwd(int dt, const float* dout, const void* dout_add, co
 
 extern "C" int nvit_norm_skip_fwd(const float* src, const float* tgt, const float* skip, float* out, int M, int C,
                                   void* stream) {
-  NVIT_REQUIRE(C % 4 == 0 && C <= 2048 && M > 0, "norm_skip_fwd: C=%d must be a multiple of 4 and <= 2048", C);
+  NVIT_REQUIRE(C % 4 == 0 && C <= NVIT_MAX_EMBD && M > 0, "norm_skip_fwd: C=%d must be a multiple of 4 and <= %d", C, NVIT_MAX_EMBD);
   hipStream_t s = (hipStream_t)stream;
   const int grid = row_grid(M);
   with_row_vecs<8>(C, [&](auto nv) { launch(norm_skip_fwd_kernel<nv>, dim3(grid), dim3(256), 0, s, src, tgt, skip, out, M, C); });
@@ -1166,7 +1167,7 @@ extern "C" int nvit_norm_skip_fwd(const float* src, const float* tgt, const floa
 
 extern "C" int nvit_norm_skip_bwd(const float* dout, const float* src, const float* tgt, const float* skip, float* dsrc,
                                   float* dtgt, float* part_dskip, int nblk, int M, int C, void* stream) {
-  NVIT_REQUIRE(C % 4 == 0 && C <= 2048 && M > 0 && nblk > 0 && nblk <= 4096, "norm_skip_bwd: bad arguments");
+  NVIT_REQUIRE(C % 4 == 0 && C <= NVIT_MAX_EMBD && M > 0 && nblk > 0 && nblk <= NVIT_MAX_PART_BLOCKS, "norm_skip_bwd: bad arguments");
   hipStream_t s = (hipStream_t)stream;
   with_row_vecs<8>(C, [&](auto nv) {
     launch(norm_skip_bwd_kernel<nv>, dim3(nblk), dim3(256), 0, s, dout, src, tgt, skip, dsrc, dtgt, part_dskip, M, C);
@@ -1177,7 +1178,7 @@ extern "C" int nvit_norm_skip_bwd(const float* dout, const float* src, const flo
 
 extern "C" int nvit_rmsnorm_fwd(const float* x, const float* w, float eps, float* out, float* rstd, int M, int C,
                                 void* stream) {
-  NVIT_REQUIRE(C % 4 == 0 && C <= 2048 && M > 0, "rmsnorm_fwd: C=%d must be a multiple of 4 and <= 2048", C);
+  NVIT_REQUIRE(C % 4 == 0 && C <= NVIT_MAX_EMBD && M > 0, "rmsnorm_fwd: C=%d must be a multiple of 4 and <= %d", C, NVIT_MAX_EMBD);
   hipStream_t s = (hipStream_t)stream;
   const int grid = row_grid(M);
   with_row_vecs<8>(C, [&](auto nv) { launch(rmsnorm_fwd_kernel<nv>, dim3(grid), dim3(256), 0, s, x, w, eps, out, rstd, M, C); });
@@ -1187,7 +1188,7 @@ extern "C" int nvit_rmsnorm_fwd(const float* x, const float* w, float eps, float
 
 extern "C" int nvit_rmsnorm_bwd(const float* dout, const float* x, const float* w, const float* rstd, float* dx,
                                 float* part_dw, int nblk, int M, int C, void* stream) {
-  NVIT_REQUIRE(C % 4 == 0 && C <= 2048 && M > 0 && nblk > 0 && nblk <= 4096, "rmsnorm_bwd: bad arguments");
+  NVIT_REQUIRE(C % 4 == 0 && C <= NVIT_MAX_EMBD && M > 0 && nblk > 0 && nblk <= NVIT_MAX_PART_BLOCKS, "rmsnorm_bwd: bad arguments");
   hipStream_t s = (hipStream_t)stream;
   with_row_vecs<8>(C, [&](auto nv) {
     launch(rmsnorm_bwd_kernel<nv>, dim3(nblk), dim3(256), 0, s, dout, x, w, rstd, dx, part_dw, M, C);
@@ -1198,7 +1199,7 @@ extern "C" int nvit_rmsnorm_bwd(const float* dout, const float* x, const float* 
 
 extern "C" int nvit_res_rmsnorm_fwd(int dt, const float* a, const void* y, int y_dt, const float* w, float eps, float* out,
                                     void* out_lo, float* rstd, int M, int C, void* stream) {
-  NVIT_REQUIRE(C % 4 == 0 && C <= 2048 && M > 0, "res_rmsnorm_fwd: C=%d must be a multiple of 4 and <= 2048", C);
+  NVIT_REQUIRE(C % 4 == 0 && C <= NVIT_MAX_EMBD && M > 0, "res_rmsnorm_fwd: C=%d must be a multiple of 4 and <= %d", C, NVIT_MAX_EMBD);
   NVIT_REQUIRE(dt == NVIT_F32 || dt == NVIT_BF16, "res_rmsnorm_fwd: bad dt %d", dt);
   NVIT_REQUIRE(!y || y_dt == NVIT_F32 || y_dt == NVIT_BF16, "res_rmsnorm_fwd: bad y_dt %d", y_dt);
   ResRmsFwdArgs ar{a, y, w, eps, out, out_lo, rstd, M, C};
@@ -1221,8 +1222,8 @@ extern "C" int nvit_res_rmsnorm_fwd(int dt, const float* a, const void* y, int y
 extern "C" int nvit_res_rmsnorm_bwd(int dt, const float* g, const void* g_add, const float* a, const void* y, int y_dt,
                                     const float* w, const float* rstd, float* dz, int accum, void* dz_lo, float* part_dw,
                                     int nblk, int M, int C, void* stream) {
-  NVIT_REQUIRE(C % 4 == 0 && C <= 2048 && M > 0, "res_rmsnorm_bwd: C=%d must be a multiple of 4 and <= 2048", C);
-  NVIT_REQUIRE(nblk > 0 && nblk <= 4096, "res_rmsnorm_bwd: nblk out of range");
+  NVIT_REQUIRE(C % 4 == 0 && C <= NVIT_MAX_EMBD && M > 0, "res_rmsnorm_bwd: C=%d must be a multiple of 4 and <= %d", C, NVIT_MAX_EMBD);
+  NVIT_REQUIRE(nblk > 0 && nblk <= NVIT_MAX_PART_BLOCKS, "res_rmsnorm_bwd: nblk out of range");
   NVIT_REQUIRE(dt == NVIT_F32 || dt == NVIT_BF16, "res_rmsnorm_bwd: bad dt %d", dt);
   NVIT_REQUIRE(!y || y_dt == NVIT_F32 || y_dt == NVIT_BF16, "res_rmsnorm_bwd: bad y_dt %d", y_dt);
   ResRmsBwdArgs ar{g, g_add, a, y, w, rstd, dz, accum, dz_lo, part_dw, M, C};
@@ -1246,7 +1247,7 @@ extern "C" int nvit_res_rmsnorm_bwd(int dt, const float* g, const void* g_add, c
 
 extern "C" int nvit_res_skip_fwd(int dt, const float* h, const void* y, int y_dt, const float* skip, const float* x,
                                  float* out, void* out_lo, int M, int C, void* stream) {
-  NVIT_REQUIRE(C % 4 == 0 && C <= 2048 && M > 0, "res_skip_fwd: C=%d must be a multiple of 4 and <= 2048", C);
+  NVIT_REQUIRE(C % 4 == 0 && C <= NVIT_MAX_EMBD && M > 0, "res_skip_fwd: C=%d must be a multiple of 4 and <= %d", C, NVIT_MAX_EMBD);
   NVIT_REQUIRE(dt == NVIT_F32 || dt == NVIT_BF16, "res_skip_fwd: bad dt %d", dt);
   NVIT_REQUIRE(y && (y_dt == NVIT_F32 || y_dt == NVIT_BF16), "res_skip_fwd: y missing or bad y_dt %d", y_dt);
   ResSkipArgs ar{nullptr, h, y, skip, x, out, out_lo, nullptr, nullptr, M, C};
@@ -1265,8 +1266,8 @@ extern "C" int nvit_res_skip_fwd(int dt, const float* h, const void* y, int y_dt
 extern "C" int nvit_res_skip_bwd(int dt, const float* dout, const float* h, const void* y, int y_dt, const float* skip,
                                  const float* x, float* dh, void* dh_lo, float* dx, float* part_dskip, int nblk, int M,
                                  int C, void* stream) {
-  NVIT_REQUIRE(C % 4 == 0 && C <= 2048 && M > 0, "res_skip_bwd: C=%d must be a multiple of 4 and <= 2048", C);
-  NVIT_REQUIRE(nblk > 0 && nblk <= 4096, "res_skip_bwd: nblk out of range");
+  NVIT_REQUIRE(C % 4 == 0 && C <= NVIT_MAX_EMBD && M > 0, "res_skip_bwd: C=%d must be a multiple of 4 and <= %d", C, NVIT_MAX_EMBD);
+  NVIT_REQUIRE(nblk > 0 && nblk <= NVIT_MAX_PART_BLOCKS, "res_skip_bwd: nblk out of range");
   NVIT_REQUIRE(dt == NVIT_F32 || dt == NVIT_BF16, "res_skip_bwd: bad dt %d", dt);
   NVIT_REQUIRE(y && (y_dt == NVIT_F32 || y_dt == NVIT_BF16), "res_skip_bwd: y missing or bad y_dt %d", y_dt);
   ResSkipArgs ar{dout, h, y, skip, x, dx, dh_lo, dh, part_dskip, M, C};
@@ -1281,7 +1282,7 @@ extern "C" int nvit_res_skip_bwd(int dt, const float* dout, const float* h, cons
   return NVIT_OK;
 }
 
-// ---- head split / merge: compact heads (nvit_qknorm_*) and zero-padded ones (nvit_heads_pad_*, dp = 128) ----
+// ---- head split / merge: compact heads (nvit_qknorm_*) and zero-padded ones (nvit_heads_pad_*, dp = PAD_D) ----
 // Each entry point checks its own arguments and opens its ProfScope; these pick the instantiation and launch it (NORM when
 // sqk is given).  dp: the stored head width (a.d: compact heads).
 static void heads_split_launch(int dt, const QkArgs& a, int dp, hipStream_t s) {
@@ -1315,7 +1316,7 @@ extern "C" int nvit_qknorm_fwd(int dt, const void* q, int ldq, const void* k, in
                                int B, int T, int H, int d, void* stream) {
   const int C = H * d;
   NVIT_REQUIRE(d == 16 || d == 32 || d == 64 || d == 128, "qknorm_fwd: head dim %d unsupported", d);
-  NVIT_REQUIRE(C <= 2048 && ldq % 4 == 0 && ldk % 4 == 0 && ldv % 4 == 0, "qknorm_fwd: bad C/ld");
+  NVIT_REQUIRE(C <= NVIT_MAX_EMBD && ldq % 4 == 0 && ldk % 4 == 0 && ldv % 4 == 0, "qknorm_fwd: bad C/ld");
   NVIT_REQUIRE(dt == NVIT_F32 || dt == NVIT_BF16 || dt == NVIT_BF16_F32IN, "qknorm_fwd: bad dt %d", dt);
   hipStream_t s = (hipStream_t)stream;
   ProfScope ps(NVIT_KID_ROWOPS, 0.0, (double)B * T * C * (dt == NVIT_F32 ? 24.0 : dt == NVIT_BF16 ? 12.0 : 18.0), s);
@@ -1330,8 +1331,8 @@ extern "C" int nvit_qknorm_bwd(int dt, const void* dqh, const void* dkh, const v
                                int B, int T, int H, int d, void* stream) {
   const int C = H * d;
   NVIT_REQUIRE(d == 16 || d == 32 || d == 64 || d == 128, "qknorm_bwd: head dim %d unsupported", d);
-  NVIT_REQUIRE(C <= 2048 && ldq % 4 == 0 && ldk % 4 == 0 && ldv % 4 == 0, "qknorm_bwd: bad C/ld");
-  NVIT_REQUIRE(nblk > 0 && nblk <= 4096, "qknorm_bwd: nblk out of range");
+  NVIT_REQUIRE(C <= NVIT_MAX_EMBD && ldq % 4 == 0 && ldk % 4 == 0 && ldv % 4 == 0, "qknorm_bwd: bad C/ld");
+  NVIT_REQUIRE(nblk > 0 && nblk <= NVIT_MAX_PART_BLOCKS, "qknorm_bwd: nblk out of range");
   // split without the normalise: the backward is the head merge alone (qh, kh, rq, rk, part unused)
   NVIT_REQUIRE(sqk || dt == NVIT_F32 || dt == NVIT_BF16, "qknorm_bwd: bad dt %d", dt);
   hipStream_t s = (hipStream_t)stream;
@@ -1344,14 +1345,14 @@ extern "C" int nvit_qknorm_bwd(int dt, const void* dqh, const void* dkh, const v
 }
 
 static bool pad_dims_ok(int H, int d, int dp) {
-  return dp == PAD_D && d > 0 && d < dp && d % 8 == 0 && H > 0 && H * d <= 2048;
+  return dp == PAD_D && d > 0 && d < dp && d % 8 == 0 && H > 0 && H * d <= NVIT_MAX_EMBD;
 }
 
 extern "C" int nvit_heads_pad_fwd(int dt, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
                                   const float* sqk, float c_q, void* qh, void* kh, void* vh, float* rq, float* rk,
                                   float* sqk_pad, int B, int T, int H, int d, int dp, void* stream) {
   const int C = H * d;
-  NVIT_REQUIRE(pad_dims_ok(H, d, dp), "heads_pad_fwd: needs dp = 128, head dim %d a multiple of 8 below dp, H*d <= 2048", d);
+  NVIT_REQUIRE(pad_dims_ok(H, d, dp), "heads_pad_fwd: needs dp = %d, head dim %d a multiple of 8 below dp, H*d <= %d", PAD_D, d, NVIT_MAX_EMBD);
   NVIT_REQUIRE(B > 0 && T > 0 && ldq % 4 == 0 && ldk % 4 == 0 && ldv % 4 == 0 && ldq >= C && ldk >= C && ldv >= C,
                "heads_pad_fwd: bad shape/ld");
   NVIT_REQUIRE(dt == NVIT_F32 || dt == NVIT_BF16_F32IN, "heads_pad_fwd: dt %d (fp32 projections in: F32 or BF16_F32IN)", dt);
@@ -1368,14 +1369,14 @@ extern "C" int nvit_heads_pad_bwd(int dt, const void* dqh, const void* dkh, cons
                                   void* dq, int ldq, void* dk, int ldk, void* dv, int ldv, float* part_dsqk, int nblk,
                                   int B, int T, int H, int d, int dp, void* stream) {
   const int C = H * d;
-  NVIT_REQUIRE(pad_dims_ok(H, d, dp), "heads_pad_bwd: needs dp = 128, head dim %d a multiple of 8 below dp, H*d <= 2048", d);
+  NVIT_REQUIRE(pad_dims_ok(H, d, dp), "heads_pad_bwd: needs dp = %d, head dim %d a multiple of 8 below dp, H*d <= %d", PAD_D, d, NVIT_MAX_EMBD);
   NVIT_REQUIRE(B > 0 && T > 0 && ldq % 4 == 0 && ldk % 4 == 0 && ldv % 4 == 0 && ldq >= C && ldk >= C && ldv >= C,
                "heads_pad_bwd: bad shape/ld");
   NVIT_REQUIRE(dt == NVIT_F32 || dt == NVIT_BF16, "heads_pad_bwd: bad dt %d", dt);
   NVIT_REQUIRE(dqh && dkh && dvh && dq && dk && dv, "heads_pad_bwd: missing pointer");
   if (sqk) {   // (the head merge alone uses no qh, kh, rq, rk, part_dsqk or nblk)
     NVIT_REQUIRE(qh && kh && rq && rk && part_dsqk, "heads_pad_bwd: missing pointer");
-    NVIT_REQUIRE(nblk > 0 && nblk <= 4096, "heads_pad_bwd: nblk out of range");
+    NVIT_REQUIRE(nblk > 0 && nblk <= NVIT_MAX_PART_BLOCKS, "heads_pad_bwd: nblk out of range");
   }
   hipStream_t s = (hipStream_t)stream;
   const double eb = dt == NVIT_F32 ? 4.0 : 2.0;
@@ -1392,7 +1393,7 @@ static int pad_copy_grid(size_t groups) {
 }
 
 extern "C" int nvit_pad_cols(int dt, const void* src, void* dst, int M, int H, int d, int dp, void* stream) {
-  NVIT_REQUIRE(pad_dims_ok(H, d, dp) && M > 0 && src && dst, "pad_cols: needs dp = 128, head dim %d a multiple of 8 below dp, H*d <= 2048", d);
+  NVIT_REQUIRE(pad_dims_ok(H, d, dp) && M > 0 && src && dst, "pad_cols: needs dp = %d, head dim %d a multiple of 8 below dp, H*d <= %d", PAD_D, d, NVIT_MAX_EMBD);
   NVIT_REQUIRE(dt == NVIT_F32 || dt == NVIT_BF16, "pad_cols: bad dt %d", dt);
   hipStream_t s = (hipStream_t)stream;
   ProfScope ps(NVIT_KID_ROWOPS, 0.0, (double)M * H * (d + dp) * (dt == NVIT_F32 ? 4.0 : 2.0), s);
@@ -1405,7 +1406,7 @@ extern "C" int nvit_pad_cols(int dt, const void* src, void* dst, int M, int H, i
 }
 
 extern "C" int nvit_unpad_cols(int dt, const void* src, void* dst, int M, int H, int d, int dp, void* stream) {
-  NVIT_REQUIRE(pad_dims_ok(H, d, dp) && M > 0 && src && dst, "unpad_cols: needs dp = 128, head dim %d a multiple of 8 below dp, H*d <= 2048", d);
+  NVIT_REQUIRE(pad_dims_ok(H, d, dp) && M > 0 && src && dst, "unpad_cols: needs dp = %d, head dim %d a multiple of 8 below dp, H*d <= %d", PAD_D, d, NVIT_MAX_EMBD);
   NVIT_REQUIRE(dt == NVIT_F32 || dt == NVIT_BF16, "unpad_cols: bad dt %d", dt);
   hipStream_t s = (hipStream_t)stream;
   ProfScope ps(NVIT_KID_ROWOPS, 0.0, (double)M * H * d * 2.0 * (dt == NVIT_F32 ? 4.0 : 2.0), s);

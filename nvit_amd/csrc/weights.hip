@@ -5,9 +5,9 @@
 // minimum traffic (one HBM read + one write per element):
 //   dim=1 (row norms, query/key/value/c_fc): one wave per row; the second pass over the row
 //         (<= 16 KiB) is served by L1/L2.
-//   dim=0 (column norms, att_c_proj/mlp_c_proj): a workgroup keeps a [rows x 64-column] panel
-//         in registers (rows <= 1152; [rows x 32-column] for 1152 < rows <= 2048), so the column
-//         pass needs no re-read.
+//   dim=0 (column norms, att_c_proj/mlp_c_proj): a workgroup keeps a [rows x NVIT_RENORM_COLS_PER_ITEM] panel
+//         in registers (rows <= NVIT_RENORM_TALL_ROWS; [rows x NVIT_RENORM_TALL_COLS_PER_ITEM] for taller matrices
+//         of up to NVIT_RENORM_MAX_ROWS_DIM0 rows), so the column pass needs no re-read.
 //
 // shadow_kernel: builds the private MFMA-operand copies of the fp32 masters: W (optionally
 // row-permuted for the SwiGLU interleave) and W^T, cast to bf16 (or kept fp32 for the exact
@@ -29,15 +29,15 @@ __device__ __forceinline__ int table_row(const int64_t* table, int n, int stride
 
 // 1024-thread workgroups (16 waves per CU keep ~48 KiB of 16-byte loads in flight, which is what an HBM-bound
 // stream needs on this chip).  dim=1: one wave per row, the row stays in registers between the norm and the
-// scaled store (one read + one write per element, no second pass).  dim=0: [rows x 64] column panel in registers
-// ([rows x 32] above 1152 rows).
+// scaled store (one read + one write per element, no second pass).  dim=0: the column panel in registers (the
+// narrow one above NVIT_RENORM_TALL_ROWS rows).
 constexpr int RENORM_THREADS = 1024;
 constexpr int RENORM_CL = NVIT_RENORM_COLS_PER_ITEM / 4;   // lanes across a panel row (16-byte pieces)
 constexpr int RENORM_RG = RENORM_THREADS / RENORM_CL;   // row groups of the column pass
-constexpr int RENORM_NV = 8;                    // float4 per lane held in registers: rows of up to 2048 columns
-constexpr int RENORM_NR = 1152 / RENORM_RG;      // rows per thread of a column panel: matrices of up to 1152 rows
-// taller matrices (rows <= 2048): a 32-column panel, 128 row groups, 16 rows per thread - 32 float4 per thread of the
-// 64-column panel would not fit the 128 registers of a 1024-thread workgroup
+constexpr int RENORM_NV = NVIT_MAX_EMBD / 256;   // float4 per lane held in registers: rows of up to NVIT_MAX_EMBD columns
+constexpr int RENORM_NR = NVIT_RENORM_TALL_ROWS / RENORM_RG;   // rows per thread of a column panel
+// taller matrices (rows <= NVIT_RENORM_MAX_ROWS_DIM0): the narrow panel, 128 row groups, 16 rows per thread - 32 float4
+// per thread of the wide panel would not fit the 128 registers of a 1024-thread workgroup
 static_assert(RENORM_NR * RENORM_RG == NVIT_RENORM_TALL_ROWS, "the 64-column panel holds NVIT_RENORM_TALL_ROWS rows");
 constexpr int RENORM_TALL_RG = RENORM_THREADS / (NVIT_RENORM_TALL_COLS_PER_ITEM / 4);
 constexpr int RENORM_TALL_NR = NVIT_RENORM_MAX_ROWS_DIM0 / RENORM_TALL_RG;
@@ -153,6 +153,7 @@ __device__ __forceinline__ int shadow_perm_row(int perm, int s, int F) {
 }
 
 // table row: {src, rows, cols, dst, dst_ld, dst_cols, dstT, dstT_ld, dstT_cols, perm, first_item, tiles_c}
+static_assert(NVIT_SHADOW_TILE == 64, "shadow_kernel walks 64 x 64 tiles through tile[64][65]");
 template <typename T>
 __global__ __launch_bounds__(256) void shadow_kernel(const int64_t* table, int n, int total_items) {
   __shared__ float tile[64][65];

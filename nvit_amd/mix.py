@@ -8,8 +8,8 @@ CutMix box and timm's `mixup_target` for the target.
 
 The draw is the counter-based generator of augment.py (Philox4x32-10; key = seed with a domain constant in its high
 word, counter = (first_index + pair, step)); the step counter lives on the device and the draw kernel advances it, so a
-replayed graph draws afresh.  lambda ~ Beta(alpha, alpha) comes from a 1025-knot quantile table that the host computes
-in fp64 (`beta_quantile_table`) and the kernel interpolates linearly: no transcendental runs on the device.
+replayed graph draws afresh.  lambda ~ Beta(alpha, alpha) comes from a quantile table of KNOTS + 1 values that the host
+computes in fp64 (`beta_quantile_table`) and the kernel interpolates linearly: no transcendental runs on the device.
 """
 from __future__ import annotations
 
@@ -22,13 +22,13 @@ import torch
 
 from . import _lib
 from ._lib import check
-from .augment import MAX_SIDE, AugmentedBatch
+from .augment import MAX_SIDE, AugmentedBatch, DeviceStepCounter, _f32_bits
 from .ops import _chk_dev, _p, _s
 
 Tensor = torch.Tensor
 
-KNOTS = 1024            # the quantile table holds KNOTS + 1 values: Q[k] = F^-1(k / KNOTS)
-ROW = 8                 # ints per row of the table: mode, lambda bits, y0, y1, x0, x1, partner row, 0
+KNOTS = _lib.const("MIX_KNOTS")   # the quantile table holds KNOTS + 1 values: Q[k] = F^-1(k / KNOTS)
+ROW = _lib.const("MIX_ROW")       # ints per row of the table: mode, lambda bits, y0, y1, x0, x1, partner row, 0
 MODE_NONE, MODE_MIXUP, MODE_CUTMIX = 0, 1, 2
 ALPHA_MIN, ALPHA_MAX = 0.1, 4.0
 
@@ -70,9 +70,9 @@ def _log_pdf_cdf(a: float, lnB: float, t: float):
 
 @functools.lru_cache(maxsize=None)
 def beta_quantile_table(alpha: float) -> tuple:
-    """Q[k] = the k/1024 quantile of Beta(alpha, alpha), k = 0..1024, in fp64: 1025 floats, Q[0] = 0, Q[512] = 1/2,
-    Q[1024] = 1, Q[1024 - k] = 1 - Q[k].  The lower half is solved in t = log x (where the small quantiles of a small
-    alpha live: 7e-28 at alpha = 0.1) by Newton steps on log I_x = log p, kept inside a bisection bracket; I_x is the
+    """Q[k] = the k/KNOTS quantile of Beta(alpha, alpha), k = 0..KNOTS, in fp64: Q[0] = 0, Q[KNOTS / 2] = 1/2, Q[KNOTS] = 1,
+    Q[KNOTS - k] = 1 - Q[k].  The lower half is solved in t = log x (where the small quantiles of a small alpha live:
+    7e-28 at alpha = 0.1) by Newton steps on log I_x = log p, kept inside a bisection bracket; I_x is the
     continued-fraction regularised incomplete beta.  Plain Python floats; accurate to a few ulp."""
     a = float(alpha)
     if not ALPHA_MIN <= a <= ALPHA_MAX:
@@ -124,10 +124,6 @@ def beta_quantile_table(alpha: float) -> tuple:
 
 def _f32(v: float) -> float:
     return struct.unpack("<f", struct.pack("<f", v))[0]
-
-
-def _f32_bits(v: float) -> int:
-    return struct.unpack("<i", struct.pack("<f", v))[0]
 
 
 # ---------------------------------------------------------------------------------------------- argument checks
@@ -239,7 +235,7 @@ class MixedBatch:
         return self.mix(self.X, y)
 
 
-class Mixup:
+class Mixup(DeviceStepCounter):
     """Mixup(mixup_alpha=0.8, cutmix_alpha=1.0, prob=1.0, switch_prob=0.5, label_smoothing=0.1, seed=0,
     first_index=0).to(device)
 
@@ -260,15 +256,7 @@ class Mixup:
         self.prob = _check_unit("prob", prob)
         self.switch_prob = _check_unit("switch_prob", switch_prob)
         self.label_smoothing = _check_unit("label_smoothing", label_smoothing, open_top=True)
-        for what, v, hi in (("seed", seed, 2 ** 64), ("first_index", first_index, 2 ** 62)):
-            if isinstance(v, bool) or not isinstance(v, int):
-                raise TypeError(f"{what} must be an int")
-            if not 0 <= v < hi:
-                raise ValueError(f"{what} must be in [0, {hi})")
-        self.seed, self.first_index = seed, first_index
-        self.device: Optional[torch.device] = None
-        self._step_host = 0          # until .to(device)
-        self._step: Optional[Tensor] = None
+        super().__init__(seed, first_index)
         self._q_mix: Optional[Tensor] = None
         self._q_cut: Optional[Tensor] = None
 
@@ -278,11 +266,7 @@ class Mixup:
 
     # ------------------------------------------------------------------ device state
     def to(self, device) -> "Mixup":
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise RuntimeError("Mixup runs on the HIP device (no CPU path)")
-        step = self.step
-        self.device = device
+        device = self._step_to(device)
 
         def table(alpha):
             if alpha == 0:
@@ -290,30 +274,7 @@ class Mixup:
             return torch.tensor(beta_quantile_table(alpha), dtype=torch.float64).to(torch.float32).to(device)
 
         self._q_mix, self._q_cut = table(self.mixup_alpha), table(self.cutmix_alpha)
-        self._step = torch.tensor([step], dtype=torch.int64).to(device)
         return self
-
-    @property
-    def step(self) -> int:
-        """Steps drawn so far (reads the device counter: synchronises)."""
-        return self._step_host if self._step is None else int(self._step.item())
-
-    def state_dict(self) -> dict:
-        return {"seed": self.seed, "step": self.step}
-
-    def load_state_dict(self, state: dict) -> None:
-        seed, step = int(state["seed"]), int(state["step"])
-        if not 0 <= seed < 2 ** 64 or not 0 <= step < 2 ** 63:
-            raise ValueError("Mixup.load_state_dict: seed or step out of range")
-        self.seed = seed
-        if self._step is None:
-            self._step_host = step
-        else:
-            self._step.fill_(step)   # in place: a captured graph holds this address
-
-    def _need_device(self):
-        if self._step is None:
-            raise RuntimeError("Mixup: call .to(device) first (it runs on the HIP device, no CPU path)")
 
     # ------------------------------------------------------------------ the two launches
     def draw(self, y: Tensor, H: int, W: int):

@@ -16,6 +16,17 @@ from . import _lib
 from ._lib import BF16, F32, check
 
 Tensor = torch.Tensor
+# layout numbers shared with the kernels: each is written once, in include/nvit_hip.h
+MAX_PART_BLOCKS = _lib.const("MAX_PART_BLOCKS")   # the most workgroups a backward row kernel accepts
+ROW_WAVES = _lib.const("ROW_WAVES")   # rows in flight per workgroup; per-wave partial arrays hold ROW_WAVES * nblk rows
+PAD_HEAD_DIM = _lib.const("PAD_HEAD_DIM")   # dp: the attention head dim the zero-padded head tensors run at
+REDUCE_MAX_ITEMS = _lib.const("COLSUM_REDUCE_MAX_ITEMS")   # reductions nvit_colsum_reduce_multi takes in one launch
+ATTN_BWD_PART_ROWS = _lib.const("ATTN_BWD_PART_ROWS")   # tokens per row of nvit_attn_bwd_qknorm's d(sqk) partials
+SWIGLU_BWD_TILE_ROWS = _lib.const("SWIGLU_BWD_TILE_ROWS")   # nvit_gemm_nt_swiglu_bwd: d(suv) partials, one row per
+SWIGLU_BWD_PART_ROWS = _lib.const("SWIGLU_BWD_PART_ROWS")   #   PART_ROWS rows of whole TILE_ROWS-row tiles
+PATCH_K_STEP = _lib.const("PATCH_EMBED_K_STEP")   # nvit_patch_embed_fwd: patch length padded to whole stages,
+PATCH_TILE_ROWS = _lib.const("PATCH_EMBED_TILE_ROWS")   #   saved patch rows to whole row tiles
+SHADOW_TILE = _lib.const("SHADOW_TILE")   # nvit_shadow_weights: edge of a work item
 
 
 def tdtype(dt: int) -> torch.dtype:
@@ -118,8 +129,8 @@ def gemm_nt_swiglu_bwd(A: Tensor, B: Tensor, uv: Tensor, M: int, F: int, K: int,
     """duv [M,2F] (interleaved) and the d(suv) partials from dy [M,K] and W^T [F,K] in one launch (bf16)."""
     _chk_dev(A, B, uv)
     duv = torch.empty((M, 2 * F), device=A.device, dtype=torch.bfloat16)
-    part = (torch.empty((2 * math.ceil(M / 256), 2 * F), device=A.device, dtype=torch.float32)
-            if gs is not None else None)
+    part = (torch.empty((round_up(M, SWIGLU_BWD_TILE_ROWS) // SWIGLU_BWD_PART_ROWS, 2 * F), device=A.device,
+                        dtype=torch.float32) if gs is not None else None)
     check(_lib.load().nvit_gemm_nt_swiglu_bwd(dt_of(A), _p(A), A.stride(0), _p(B), B.stride(0), _p(uv), _p(duv),
                                               _p(part), M, F, K, _p(gs), gscale, _s()), "nvit_gemm_nt_swiglu_bwd")
     return duv, part
@@ -217,7 +228,11 @@ def gemm_tn(A: Tensor, B: Tensor, G: Tensor, Mred: int, N: int, K: int, perm: in
 # ----------------------------------------------------------------------------- row ops
 _LERP_BWD_BLOCKS: dict = {}
 PART_BLOCKS = 1024   # workgroups of the backward row kernels
-MAX_PART_BLOCKS = 4096   # the most a backward row kernel accepts
+assert PART_BLOCKS <= MAX_PART_BLOCKS
+
+
+def _row_part_blocks(M: int) -> int:
+    return min(PART_BLOCKS, math.ceil(M / ROW_WAVES))
 
 
 def _part_blocks(nblk: Optional[int], default: int, name: str) -> int:
@@ -243,9 +258,9 @@ def lerp_fwd(dt: int, h: Tensor, y: Tensor, alpha: Tensor, c_a: float, skip_x: O
 def lerp_bwd(dt: int, dout: Tensor, h: Tensor, y: Tensor, alpha: Tensor, c_a: float, skip_x: Optional[Tensor],
              skip: Optional[Tensor], dh: Optional[Tensor], accum_dh: bool, want_dy_f32: bool, want_dy_lo: bool,
              dout_add: Optional[Tensor] = None, *, nblk: Optional[int] = None):
-    """-> dh, dy_f32|None, dy_lo|None, dskip_x|None, part_dlam [4*nblk,C], part_dskip|None.
+    """-> dh, dy_f32|None, dy_lo|None, dskip_x|None, part_dlam [ROW_WAVES*nblk,C], part_dskip|None.
     dout_add: optional bf16 [M,C] added to dout inside the kernel (a data-gradient GEMM's output).
-    nblk: workgroups to launch instead of the resident count (1..4096)."""
+    nblk: workgroups to launch instead of the resident count (1..MAX_PART_BLOCKS)."""
     if dout_add is not None and (dout_add.dtype != torch.bfloat16 or dout_add.shape != h.shape or not dout_add.is_contiguous()):
         raise ValueError("lerp_bwd: dout_add must be a contiguous bf16 [M,C] tensor")
     M, Cc = h.shape
@@ -260,12 +275,12 @@ def lerp_bwd(dt: int, dout: Tensor, h: Tensor, y: Tensor, alpha: Tensor, c_a: fl
     if nres is None:
         nres = int(_lib.load().nvit_lerp_bwd_blocks(dt, dt_of(y), Cc, int(key[3]), int(key[4]), int(key[5]))) or PART_BLOCKS
         _LERP_BWD_BLOCKS[key] = nres
-    nblk = _part_blocks(nblk, min(nres, math.ceil(M / 4)), "lerp_bwd")
+    nblk = _part_blocks(nblk, min(nres, math.ceil(M / ROW_WAVES)), "lerp_bwd")
     dy = torch.empty_like(h) if want_dy_f32 else None
     dy_lo = torch.empty((M, Cc), device=dev, dtype=tdtype(dt)) if want_dy_lo else None
     dskip_x = torch.empty_like(h) if skip_x is not None else None
-    part = torch.empty((4 * nblk, Cc), device=dev, dtype=torch.float32)      # one row of column partials per wave
-    pskip = torch.empty((4 * nblk,), device=dev, dtype=torch.float32) if skip_x is not None else None
+    part = torch.empty((ROW_WAVES * nblk, Cc), device=dev, dtype=torch.float32)   # one row of column partials per wave
+    pskip = torch.empty((ROW_WAVES * nblk,), device=dev, dtype=torch.float32) if skip_x is not None else None
     check(_lib.load().nvit_lerp_bwd(dt, _p(dout), _p(dout_add), _p(h), _p(y), dt_of(y), _p(alpha), c_a, _p(skip_x), _p(skip),
                                     _p(dh), int(accum_dh), _p(dy), _p(dy_lo), _p(dskip_x), _p(part), _p(pskip),
                                     nblk, M, Cc, _s()), "nvit_lerp_bwd")
@@ -283,7 +298,7 @@ def rmsnorm_fwd(x: Tensor, w: Tensor, eps: float):
 def rmsnorm_bwd(dout: Tensor, x: Tensor, w: Tensor, rstd: Tensor, *, nblk: Optional[int] = None):
     """-> dx [M,C], dw [C]"""
     M, Cc = x.shape
-    nblk = _part_blocks(nblk, min(PART_BLOCKS, math.ceil(M / 4)), "rmsnorm_bwd")
+    nblk = _part_blocks(nblk, _row_part_blocks(M), "rmsnorm_bwd")
     dx = torch.empty_like(x)
     part = torch.empty((nblk, Cc), device=x.device, dtype=torch.float32)
     check(_lib.load().nvit_rmsnorm_bwd(_p(dout), _p(x), _p(w), _p(rstd), _p(dx), _p(part), nblk, M, Cc, _s()),
@@ -332,14 +347,10 @@ def res_rmsnorm_fwd(dt: int, a: Tensor, y: Optional[Tensor], w: Tensor, eps: flo
     return out, out_lo, rstd
 
 
-def _row_part_blocks(M: int) -> int:
-    return min(PART_BLOCKS, math.ceil(M / 4))
-
-
 def res_rmsnorm_bwd(dt: int, g: Tensor, a: Tensor, y: Optional[Tensor], w: Tensor, rstd: Tensor,
                     g_add: Optional[Tensor] = None, dz: Optional[Tensor] = None, want_lo: bool = False, *,
                     nblk: Optional[int] = None):
-    """Backward of res_rmsnorm_fwd -> dz fp32 (added to `dz` when given), dz_lo (type dt) | None, part_dw [4*nblk, C].
+    """Backward of res_rmsnorm_fwd -> dz fp32 (added to `dz` when given), dz_lo (type dt) | None, part_dw [ROW_WAVES*nblk, C].
     g_add: optional type-dt [M,C] addend of the incoming gradient (a data-gradient GEMM's output)."""
     M, Cc = a.shape
     _chk_rows((M, Cc), y, g_add, f32=(a, g, dz), name="res_rmsnorm_bwd")
@@ -352,7 +363,7 @@ def res_rmsnorm_bwd(dt: int, g: Tensor, a: Tensor, y: Optional[Tensor], w: Tenso
         dz = torch.empty_like(a)
     nblk = _part_blocks(nblk, _row_part_blocks(M), "res_rmsnorm_bwd")
     dz_lo = torch.empty((M, Cc), device=a.device, dtype=tdtype(dt)) if want_lo else None
-    part = torch.empty((4 * nblk, Cc), device=a.device, dtype=torch.float32)
+    part = torch.empty((ROW_WAVES * nblk, Cc), device=a.device, dtype=torch.float32)
     check(_lib.load().nvit_res_rmsnorm_bwd(dt, _p(g), _p(g_add), _p(a), _p(y), dt_of(y) if y is not None else F32, _p(w),
                                            _p(rstd), _p(dz), int(accum), _p(dz_lo), _p(part), nblk, M, Cc, _s()),
           "nvit_res_rmsnorm_bwd")
@@ -373,7 +384,7 @@ def res_skip_fwd(dt: int, h: Tensor, y: Tensor, skip: Tensor, x: Tensor, want_lo
 
 def res_skip_bwd(dt: int, dout: Tensor, h: Tensor, y: Tensor, skip: Tensor, x: Tensor, want_lo: bool = True, *,
                  nblk: Optional[int] = None):
-    """Backward of res_skip_fwd -> dh = d(h + y) fp32, dh_lo (type dt) | None, dx fp32, part_dskip [4*nblk]."""
+    """Backward of res_skip_fwd -> dh = d(h + y) fp32, dh_lo (type dt) | None, dx fp32, part_dskip [ROW_WAVES*nblk]."""
     M, Cc = h.shape
     _chk_rows((M, Cc), y, f32=(dout, h, x), name="res_skip_bwd")
     _chk_vec(1, skip, name="res_skip_bwd")
@@ -381,7 +392,7 @@ def res_skip_bwd(dt: int, dout: Tensor, h: Tensor, y: Tensor, skip: Tensor, x: T
     dh = torch.empty_like(h)
     dx = torch.empty_like(h)
     dh_lo = torch.empty((M, Cc), device=h.device, dtype=tdtype(dt)) if want_lo else None
-    part = torch.empty((4 * nblk,), device=h.device, dtype=torch.float32)
+    part = torch.empty((ROW_WAVES * nblk,), device=h.device, dtype=torch.float32)
     check(_lib.load().nvit_res_skip_bwd(dt, _p(dout), _p(h), _p(y), dt_of(y), _p(skip), _p(x), _p(dh), _p(dh_lo), _p(dx),
                                         _p(part), nblk, M, Cc, _s()), "nvit_res_skip_bwd")
     return dh, dh_lo, dx, part
@@ -397,7 +408,7 @@ def norm_skip_fwd(src: Tensor, tgt: Optional[Tensor], skip: Tensor) -> Tensor:
 
 def norm_skip_bwd(dout: Tensor, src: Tensor, tgt: Optional[Tensor], skip: Tensor, *, nblk: Optional[int] = None):
     M, Cc = src.shape
-    nblk = _part_blocks(nblk, min(PART_BLOCKS, math.ceil(M / 4)), "norm_skip_bwd")
+    nblk = _part_blocks(nblk, _row_part_blocks(M), "norm_skip_bwd")
     dsrc = torch.empty_like(src)
     dtgt = torch.empty_like(src) if tgt is not None else None
     part = torch.empty((nblk,), device=src.device, dtype=torch.float32)
@@ -406,9 +417,6 @@ def norm_skip_bwd(dout: Tensor, src: Tensor, tgt: Optional[Tensor], skip: Tensor
     dskip = torch.empty_like(skip)
     colsum_reduce(part, dskip, False)
     return dsrc, dtgt, dskip
-
-
-PAD_HEAD_DIM = 128   # dp: the attention head dim the zero-padded head tensors run at (include/nvit_hip.h)
 
 
 def _pad_out(out, shape, dtype, device, name: str) -> Tensor:
@@ -438,7 +446,7 @@ def _heads_merge(name: str, dt: int, dqh, dkh, dvh, qh, kh, rq, rk, sqk, c_q, dq
                  out, post=()) -> Optional[Tensor]:
     """nvit_<name>: the backward of _heads_split into token-major dq/dk/dv (type dt) -> the d(sqk*c_q) partials
     [nblk, H*d] (out: optional buffer), or None for the head merge alone (sqk None).  post: what it takes behind d."""
-    nblk = _part_blocks(nblk, min(PART_BLOCKS, math.ceil(B * T / 4)), name)
+    nblk = _part_blocks(nblk, _row_part_blocks(B * T), name)
     part = _pad_out(out, (nblk, H * d), torch.float32, dq.device, name) if sqk is not None else None
     check(getattr(_lib.load(), "nvit_" + name)(dt, _p(dqh), _p(dkh), _p(dvh), _p(qh), _p(kh), _p(rq), _p(rk), _p(sqk), c_q,
                                                _p(dq), ldq, _p(dk), ldk, _p(dv), ldv, _p(part), nblk, B, T, H, d, *post,
@@ -542,7 +550,7 @@ class ReduceBatch:
     def add(self, part: Tensor, out: Tensor, accumulate: bool = False, kind: int = 0, ref: Optional[Tensor] = None,
             scale: float = 1.0, part_b: Optional[Tensor] = None) -> None:
         self.items.append((part, out, accumulate, kind, ref, scale, part_b))
-        if len(self.items) == 8:
+        if len(self.items) == REDUCE_MAX_ITEMS:
             self.flush()
 
     def flush(self) -> None:
@@ -672,8 +680,8 @@ def attn_bwd_qknorm(dout: Tensor, qh: Tensor, kh: Tensor, vh: Tensor, o: Tensor,
     if sqk is None:
         part_q = part_k = None
     else:
-        part_q = torch.empty((B * math.ceil(Tq / 128), H * d), device=dev, dtype=torch.float32)
-        part_k = torch.empty((B * math.ceil(Tk / 128), H * d), device=dev, dtype=torch.float32)
+        part_q = torch.empty((B * math.ceil(Tq / ATTN_BWD_PART_ROWS), H * d), device=dev, dtype=torch.float32)
+        part_k = torch.empty((B * math.ceil(Tk / ATTN_BWD_PART_ROWS), H * d), device=dev, dtype=torch.float32)
     delta = torch.empty((2, B, H, Tq), device=dev, dtype=torch.float32)   # workspace: -delta | -lse*log2(e)
     check(_lib.load().nvit_attn_bwd_qknorm(BF16, _p(dout), _p(qh), _p(kh), _p(vh), _p(o), _p(lse), scale, _p(rq),
                                            _p(rk), _p(sqk), c_q, q_prescale, _p(dq), ldq, _p(dk), _p(dv), ldkv, _p(part_q),
@@ -694,6 +702,7 @@ def attn_heads_fwd(dt: int, q: Tensor, ldq: int, k: Tensor, v: Tensor, ldkv: int
 
 
 ATTN_HEADS_BWD_BLOCKS = 4096   # one-wave workgroups of the head-axis backward (rows of its d(sqk) partials)
+assert ATTN_HEADS_BWD_BLOCKS <= _lib.const("ATTN_HEADS_BWD_MAX_BLOCKS")
 
 
 def attn_heads_bwd(dt: int, dout: Tensor, q: Tensor, ldq: int, k: Tensor, v: Tensor, ldkv: int, sqk: Optional[Tensor],
@@ -722,8 +731,8 @@ def im2col(dt: int, img: Tensor, Pl: int, Pg: int):
 
 
 def patch_kp(K: int) -> int:
-    """patch length padded to whole 32-element stages of nvit_patch_embed_fwd"""
-    return round_up(K, 32)
+    """patch length padded to whole stages of nvit_patch_embed_fwd (what nvit_patch_embed_kp returns)"""
+    return round_up(K, PATCH_K_STEP)
 
 
 def patch_embed_fwd(img: Tensor, w_l: Tensor, b_l: Optional[Tensor], pos_l: Tensor, w_g: Tensor, b_g: Optional[Tensor],
@@ -743,7 +752,7 @@ def patch_embed_fwd(img: Tensor, w_l: Tensor, b_l: Optional[Tensor], pos_l: Tens
     glo = torch.empty((M, Cc), device=dev, dtype=torch.float32)
     a_l = a_g = lo_l = lo_g = None
     if save_rows:
-        Mpad = round_up(M, 256)
+        Mpad = round_up(M, PATCH_TILE_ROWS)
         a_l = torch.empty((Mpad, Kpl), device=dev, dtype=torch.bfloat16)
         a_g = torch.empty((Mpad, Kpg), device=dev, dtype=torch.bfloat16)
     if twins:
@@ -778,7 +787,7 @@ def pool_ln_bwd(dln: Tensor, pooled: Tensor, w: Tensor, stats: Tensor, dw: Tenso
 
 def recon_loss(raw: Tensor, img: Tensor, P: int) -> Tensor:
     B, ch, S, _ = img.shape
-    nblk = 1024
+    nblk = PART_BLOCKS
     part = torch.empty((nblk,), device=img.device, dtype=torch.float32)
     loss = torch.empty((1,), device=img.device, dtype=torch.float32)
     check(_lib.load().nvit_recon_loss(_p(raw), _p(img), _p(part), nblk, _p(loss), B, ch, S, P, _s()),
@@ -854,7 +863,7 @@ def som_update(nodes: Tensor, x: Tensor, idx: Tensor, lr_alpha, sigma: float, gm
 
 def cos_consistency_fwd(a: Tensor, b: Tensor):
     M, Cc = a.shape
-    nblk = min(1024, math.ceil(M / 4))
+    nblk = min(PART_BLOCKS, math.ceil(M / 4))
     stats = torch.empty((M, 3), device=a.device, dtype=torch.float32)
     part = torch.empty((nblk,), device=a.device, dtype=torch.float32)
     loss = torch.empty((1,), device=a.device, dtype=torch.float32)
@@ -872,7 +881,7 @@ def cos_consistency_bwd(a: Tensor, b: Tensor, stats: Tensor, g: Tensor):
 
 
 def huber_fwd(a: Tensor, b: Tensor) -> Tensor:
-    nblk = 1024
+    nblk = PART_BLOCKS
     part = torch.empty((nblk,), device=a.device, dtype=torch.float32)
     loss = torch.empty((1,), device=a.device, dtype=torch.float32)
     check(_lib.load().nvit_huber_fwd(_p(a), _p(b), _p(part), nblk, _p(loss), a.numel(), _s()), "nvit_huber_fwd")
@@ -940,8 +949,8 @@ def shadow_table(entries, device) -> Tuple[Tensor, int]:
     for src, dst, dst_ld, dst_cols, dstT, dstT_ld, dstT_cols, perm in entries:
         assert src.dtype == torch.float32 and src.is_contiguous()
         r, c = src.shape[0], src.numel() // src.shape[0]
-        tiles_c = math.ceil(max(c, dst_cols if dst is not None else 0) / 64)
-        tiles_r = math.ceil(max(r, dstT_cols if dstT is not None else 0) / 64)
+        tiles_c = math.ceil(max(c, dst_cols if dst is not None else 0) / SHADOW_TILE)
+        tiles_r = math.ceil(max(r, dstT_cols if dstT is not None else 0) / SHADOW_TILE)
         rows_.append([src.data_ptr(), r, c, dst.data_ptr() if dst is not None else 0, dst_ld, dst_cols,
                       dstT.data_ptr() if dstT is not None else 0, dstT_ld, dstT_cols, perm, first, tiles_c])
         first += tiles_c * tiles_r

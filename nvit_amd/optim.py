@@ -24,27 +24,58 @@ from __future__ import annotations
 
 import math
 import struct
-from typing import Dict, List, Optional
+from typing import Dict, List, Optional, Tuple
 
 import torch
 
 from . import _lib
 from .ops import _p, _s, check
 
-_CHUNK = 8192
-_ROWS_PER_ITEM = 16
-_SLAB_COLS = 32        # column slab of a column-normalised matrix of at most _SLAB_ROWS rows,
-_SLAB_ROWS = 1152
-_TALL_COLS = 16        # of a taller one (at most _TALL_ROWS rows): the slab must fit the LDS of a CU
-_TALL_ROWS = 2048
-_ROW_COLS = 1536       # rows of a row-normalised matrix stay in registers up to this width,
-_WIDE_COLS = 2048      # wider ones (up to this) are parked in LDS, which must then hold 16 of them:
-_WIDE_LDS_ROWS = 1024  #   the LDS of a 1024-row slab does
-_NPART = 1024
+_TABLE_COLS = _lib.const("OPT_TABLE_COLS")  # the item geometry of nvit_grad_sqnorm / nvit_adamw_renorm (nvit_hip.h):
+_CHUNK = _lib.const("OPT_CHUNK")
+_ROWS_PER_ITEM = _lib.const("OPT_ROWS_PER_ITEM")
+_SLAB_COLS = _lib.const("OPT_SLAB_COLS")    # column slab of a column-normalised matrix of at most _SLAB_ROWS rows,
+_SLAB_ROWS = _lib.const("OPT_SLAB_ROWS")
+_TALL_COLS = _lib.const("OPT_TALL_COLS")    # of a taller one (at most _TALL_ROWS rows): the slab must fit the LDS of a CU
+_TALL_ROWS = _lib.const("OPT_TALL_ROWS")
+_ROW_COLS = _lib.const("OPT_ROW_COLS")      # rows of a row-normalised matrix stay in registers up to this width,
+_WIDE_COLS = _lib.const("OPT_WIDE_COLS")    # wider ones (up to this) are parked in LDS, which must then hold an item's rows:
+_WIDE_LDS_ROWS = _lib.const("OPT_WIDE_LDS_ROWS")   # the LDS of a slab of this many rows does
+_NPART = 1024                               # workgroups of the gradient-norm kernel (rows of its partials)
+assert _NPART <= _lib.const("OPT_MAX_PART")
 
 
-def _f32_bits(x: float) -> int:
-    return struct.unpack("<I", struct.pack("<f", float(x)))[0]
+def _hyper_bits(group) -> int:
+    """f32bits(lr) | f32bits(weight_decay) << 32 of a param group as the signed int64 of the table's last column."""
+    return struct.unpack("<q", struct.pack("<ff", float(group["lr"]), float(group["weight_decay"])))[0]
+
+
+def table_items(kind: int, rows: int, cols: int) -> Tuple[int, int, int]:
+    """One table entry -> (items of nvit_adamw_renorm, gradient-norm chunks, slab rows of LDS it needs); kind -1: plain
+    (rows * cols elements), 1: rows normalised, 0: columns normalised.  RuntimeError outside the kernel's range."""
+    chunks = math.ceil(rows * cols / _CHUNK)
+    if kind == 1:
+        if cols % 4 or cols > _WIDE_COLS:
+            raise RuntimeError(f"FusedAdamW: row-normalised matrix needs cols % 4 == 0 and <= {_WIDE_COLS} (got {cols})")
+        return math.ceil(rows / _ROWS_PER_ITEM), chunks, _WIDE_LDS_ROWS if cols > _ROW_COLS else 0
+    if kind == 0:
+        if rows > _TALL_ROWS:
+            raise RuntimeError(f"FusedAdamW: column-normalised matrix with {rows} rows exceeds the LDS slab ({_TALL_ROWS})")
+        return math.ceil(cols / (_SLAB_COLS if rows <= _SLAB_ROWS else _TALL_COLS)), chunks, rows
+    return chunks, chunks, 0
+
+
+def renorm_matrices(model):
+    """(weight, dim) of every matrix that Trainer.normalize_matrices re-normalises (reference train.py:461-480): dim 1 =
+    unit rows, 0 = unit columns; nothing for a plain ViT.  The one list behind train.normalize_matrices (its table rows,
+    hence the kernel's work order, follow this order) and the fused step."""
+    m = model.module if hasattr(model, "module") else model
+    if not m.config.use_nvit:
+        return
+    for blk in m.transformer.h:
+        for lin, dim in ((blk.query, 1), (blk.key, 1), (blk.value, 1), (blk.att_c_proj, 0), (blk.c_fc, 1),
+                         (blk.mlp_c_proj, 0)):
+            yield lin.weight, dim
 
 
 class FusedAdamW(torch.optim.AdamW):
@@ -73,7 +104,7 @@ class FusedAdamW(torch.optim.AdamW):
         """Device table for the current (param, grad, state) pointers; rebuilt only when one of them moves."""
         rows: List[List[int]] = []
         key = []
-        hypers: List[int] = []   # per row: lr | weight_decay bits (column 9 of the table)
+        hypers: List[int] = []   # per row: lr | weight_decay bits (the last column of the table)
         groups: List[int] = []   # per row: index of its param group
         first_item = first_chunk = 0
         max_slab_rows = 0
@@ -100,31 +131,16 @@ class FusedAdamW(torch.optim.AdamW):
                     r, c = p.shape
                 else:
                     kind, r, c = -1, 1, p.numel()
-                if kind == 1:
-                    if c % 4 or c > _WIDE_COLS:
-                        raise RuntimeError(f"FusedAdamW: row-normalised matrix needs cols % 4 == 0 and <= {_WIDE_COLS} "
-                                           f"(got {c})")
-                    items = math.ceil(r / _ROWS_PER_ITEM)
-                    if c > _ROW_COLS:
-                        max_slab_rows = max(max_slab_rows, _WIDE_LDS_ROWS)
-                elif kind == 0:
-                    if r > _TALL_ROWS:
-                        raise RuntimeError(f"FusedAdamW: column-normalised matrix with {r} rows exceeds the LDS slab "
-                                           f"({_TALL_ROWS})")
-                    items = math.ceil(c / (_SLAB_COLS if r <= _SLAB_ROWS else _TALL_COLS))
-                    max_slab_rows = max(max_slab_rows, r)
-                else:
-                    items = math.ceil(p.numel() / _CHUNK)
-                hyper = _f32_bits(group["lr"]) | (_f32_bits(group["weight_decay"]) << 32)
-                if hyper >= 1 << 63:
-                    hyper -= 1 << 64
+                items, chunks, slab = table_items(kind, r, c)
+                max_slab_rows = max(max_slab_rows, slab)
+                hyper = _hyper_bits(group)
                 rows.append([p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
                              r, c, kind, first_item, first_chunk, hyper])
                 key.append((p.data_ptr(), g.data_ptr(), kind))
                 hypers.append(hyper)
                 groups.append(gi)
                 first_item += items
-                first_chunk += math.ceil(p.numel() / _CHUNK)
+                first_chunk += chunks
         key = tuple(key)
         if self._cache is not None and self._cache["key"] == key and self._cache["hypers"] != hypers:
             # only lr / weight_decay moved (the reference trainer rewrites lr every iteration): update the hyper column in
@@ -133,16 +149,10 @@ class FusedAdamW(torch.optim.AdamW):
         if self._cache is None or self._cache["key"] != key:
             if not rows:
                 return None
-            dev = None
-            for group in self.param_groups:
-                for p in group["params"]:
-                    dev = p.device
-                    break
-                if dev is not None:
-                    break
+            dev = next(p.device for group in self.param_groups for p in group["params"])
             n = len(rows)
             host = torch.tensor(rows, dtype=torch.int64)
-            table = torch.empty((n, 10), dtype=torch.int64, device=dev)
+            table = torch.empty((n, _TABLE_COLS), dtype=torch.int64, device=dev)
             if torch.cuda.is_current_stream_capturing():
                 # Inside a hipGraph capture (the gradients autograd allocates there have new addresses, so the table is
                 # rebuilt once): pinned memory cannot be allocated now, so the image goes through the persistent
@@ -187,15 +197,7 @@ class FusedAdamW(torch.optim.AdamW):
         element is finite; and the reference re-runs normalize_matrices on the unchanged weights after a skipped step
         (a change of at most an ulp), while here nothing moves.  Under DataParallel every rank holds the same averaged
         gradients when this runs, hence takes the same decision."""
-        dims: Dict[int, int] = {}
-        if model is not None:
-            m = model.module if hasattr(model, "module") else model
-            if m.config.use_nvit:
-                for blk in m.transformer.h:
-                    for nme in ("query", "key", "value", "c_fc"):
-                        dims[id(getattr(blk, nme).weight)] = 1
-                    dims[id(blk.att_c_proj.weight)] = 0
-                    dims[id(blk.mlp_c_proj.weight)] = 0
+        dims: Dict[int, int] = {} if model is None else {id(w): dim for w, dim in renorm_matrices(model)}
         c = self._table(dims)
         if c is None:
             return None
@@ -269,7 +271,7 @@ class FusedAdamW(torch.optim.AdamW):
         hcol = torch.tensor(hypers, dtype=torch.int64)
         if c["staged"]:
             torch.cuda.current_stream().synchronize()   # no replay may be reading the staging buffer while it changes
-            self._staging[:c["n"], 9].copy_(hcol)
+            self._staging[:c["n"], _TABLE_COLS - 1].copy_(hcol)
             c["table"].copy_(self._staging[:c["n"]], non_blocking=True)
         else:
             # one persistent pinned column, guarded by an event: the previous async copy must have left it
@@ -279,7 +281,7 @@ class FusedAdamW(torch.optim.AdamW):
             else:
                 self._hyper_ev.synchronize()
             self._hyper_pin[:c["n"]].copy_(hcol)
-            c["table"][:, 9].copy_(self._hyper_pin[:c["n"]], non_blocking=True)
+            c["table"][:, _TABLE_COLS - 1].copy_(self._hyper_pin[:c["n"]], non_blocking=True)
             self._hyper_ev.record()
         c["hypers"] = list(hypers)
 
@@ -290,20 +292,13 @@ class FusedAdamW(torch.optim.AdamW):
         c = self._cache if cache is None else cache
         if c is None:
             return
-        col = []
-        for gi in c["groups"]:
-            group = self.param_groups[gi]
-            hyper = _f32_bits(group["lr"]) | (_f32_bits(group["weight_decay"]) << 32)
-            if hyper >= 1 << 63:
-                hyper -= 1 << 64
-            col.append(hyper)
-        self._write_hyper_column(col, c)
+        self._write_hyper_column([_hyper_bits(self.param_groups[gi]) for gi in c["groups"]], c)
 
     def reserve_staging(self) -> None:
         """Pinned host image for the parameter table, allocated ahead of a hipGraph capture."""
         n = sum(len(g["params"]) for g in self.param_groups)
         if self._staging is None or self._staging.shape[0] < n:
-            self._staging = torch.empty((max(n, 64), 10), dtype=torch.int64).pin_memory()
+            self._staging = torch.empty((max(n, 64), _TABLE_COLS), dtype=torch.int64).pin_memory()
 
     def note_replay(self, n: int = 1) -> None:
         """A captured step was replayed n times (the device counter advanced; keep the host mirror in sync)."""

@@ -20,10 +20,7 @@ import torch
 from . import ops
 from .augment import AugmentedBatch
 from .mix import MixedBatch, MixedTargets
-from .optim import FusedAdamW
-
-_RENORM_ROWS = ("query", "key", "value", "c_fc")     # dim=1
-_RENORM_COLS = ("att_c_proj", "mlp_c_proj")          # dim=0
+from .optim import FusedAdamW, renorm_matrices
 
 
 def _unwrap(model):
@@ -32,15 +29,9 @@ def _unwrap(model):
 
 def normalize_matrices(model) -> None:
     m = _unwrap(model)
-    if not m.config.use_nvit:
+    mats = [(w.data, dim) for w, dim in renorm_matrices(m)]
+    if not mats:
         return
-    mats = []
-    for blk in m.transformer.h:
-        for n in ("query", "key", "value"):
-            mats.append((getattr(blk, n).weight.data, 1))
-        mats.append((blk.att_c_proj.weight.data, 0))
-        mats.append((blk.c_fc.weight.data, 1))
-        mats.append((blk.mlp_c_proj.weight.data, 0))
     dev = mats[0][0].device
     if dev.type != "cuda":
         raise RuntimeError("normalize_matrices: parameters must live on the HIP device (no CPU fallback)")

@@ -1,5 +1,5 @@
 """CPU: the C-ABI shared library builds (hipcc cross-compiles gfx950 without a GPU), loads, and exports every
-symbol declared in include/nvit_hip.h with the argument counts the ctypes table binds.  No compute calls."""
+symbol declared in include/nvit_hip.h with the argument and return types the ctypes table binds.  No compute calls."""
 import ctypes
 import os
 import re
@@ -10,13 +10,31 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+_CTYPES_CLASS = {ctypes.c_void_p: "pointer", ctypes.c_char_p: "pointer", ctypes.c_int: "int", ctypes.c_uint: "unsigned",
+                 ctypes.c_int64: "int64_t", ctypes.c_uint64: "uint64_t", ctypes.c_float: "float", ctypes.c_double: "double",
+                 None: "void"}
+
+
+def _type_class(decl: str) -> str:
+    """The type class of a C parameter declaration (`const float* x`, `int64_t n`, `unsigned`) or of a return type."""
+    if "*" in decl:
+        return "pointer"
+    words = [w for w in decl.split() if w != "const"]
+    if len(words) > 1:   # a parameter: the last word is its name
+        words = words[:-1]
+    cls = " ".join(words)
+    assert cls in ("int", "unsigned", "int64_t", "uint64_t", "float", "double", "void"), decl
+    return cls
+
+
 def _declared():
+    """name -> (return type class, [argument type classes]) of every entry point the header declares."""
     h = open(os.path.join(ROOT, "include", "nvit_hip.h")).read()
     h = re.sub(r"/\*.*?\*/", "", h, flags=re.S)
     out = {}
-    for name, args in re.findall(r"(?:int64_t|int|void|const char\*)\s+(nvit_\w+)\s*\(([^;]*?)\)\s*;", h):
+    for ret, name, args in re.findall(r"(int64_t|int|void|const char\*)\s+(nvit_\w+)\s*\(([^;]*?)\)\s*;", h):
         a = args.strip()
-        out[name] = 0 if a in ("void", "") else len(a.split(","))
+        out[name] = (_type_class(ret), [] if a in ("void", "") else [_type_class(x) for x in a.split(",")])
     return out
 
 
@@ -34,10 +52,15 @@ def test_every_declared_symbol_is_exported_and_bound():
     decl = _declared()
     assert len(decl) >= 40
     lib = ctypes.CDLL(_lib_path())
-    for name, nargs in decl.items():
+    for name, (ret, args) in decl.items():
         assert hasattr(lib, name), f"{name} declared in include/nvit_hip.h but not exported"
         assert name in _lib.SIGNATURES, f"{name} has no ctypes binding"
-        assert len(_lib.SIGNATURES[name]) == nargs, f"{name}: header has {nargs} args, binding {len(_lib.SIGNATURES[name])}"
+        bound = [_CTYPES_CLASS[t] for t in _lib.SIGNATURES[name]]
+        assert len(bound) == len(args), f"{name}: header has {len(args)} args, binding {len(bound)}"
+        wrong = [(i, a, b) for i, (a, b) in enumerate(zip(args, bound)) if a != b]
+        assert not wrong, f"{name}: (argument index, header type, bound type) {wrong}"
+        bound_ret = _CTYPES_CLASS[_lib._RESTYPES.get(name, ctypes.c_int)]
+        assert bound_ret == ret, f"{name}: header returns {ret}, binding {bound_ret}"
     for name in _lib.SIGNATURES:
         assert name in decl, f"{name} bound in _lib.py but not declared in the header"
     assert lib.nvit_version() >= 100
