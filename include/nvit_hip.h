@@ -403,6 +403,54 @@ int nvit_mix_draw(uint64_t seed, int64_t* step, int64_t first_index, const float
  * (two rounded products, one add); CutMix: rows i and j exchange the pixels of [y0,y1) x [x0,x1) in every channel.  A row
  * of mode 0, a row that is its own partner, and a row whose partner does not name it back with the same mode is copied. */
 int nvit_mix_apply(const float* in, const int* table, float* out, int B, int C, int H, int W, void* stream);
+/* On-device RandomResizedCrop + horizontal flip (tests/crop_ref.py): a stored uint8 [B,Hs,Ws,C] batch ->
+ * uint8 [B,size,size,C], image b = Pillow's crop(box b).resize((size, size), BILINEAR | BICUBIC), mirrored if its flip
+ * bit is set, bit for bit.  Three launches per batch: the draw and the two passes of the apply.
+ * nvit_crop_draw: table int32 [B,NVIT_CROP_ROW] = (top, left, h, w, flip, 0, 0, 0), torchvision's get_params in fp64.
+ * Philox4x32-10, counter = (first_index + b, *step), key = seed with a domain constant + a xor-ed into its high word:
+ * a = 0..NVIT_CROP_ATTEMPTS-1 are the attempts (r0: area in [scale0, scale1], r1: aspect, r2: top, r3: left), a =
+ * NVIT_CROP_ATTEMPTS the flip bit (r0 against hflip).  aspect: device fp64 [NVIT_CROP_KNOTS + 1], exp(log ratio_min +
+ * k / NVIT_CROP_KNOTS * (log ratio_max - log ratio_min)), computed by the host and interpolated linearly: no
+ * transcendental runs on the device.  After the last failed attempt the box is torchvision's central fallback.  *step
+ * is a device int64 that the kernel reads and then advances by one, as nvit_augment_draw does. */
+#define NVIT_CROP_ROW 8
+#define NVIT_CROP_KNOTS 1024
+#define NVIT_CROP_ATTEMPTS 10
+#define NVIT_CROP_MAX_SRC 2048
+#define NVIT_CROP_MAX_BATCH 65535 /* images per call of nvit_crop_apply / nvit_erase_apply: the grids' second dimension */
+#define NVIT_CROP_BILINEAR 0
+#define NVIT_CROP_BICUBIC 1
+int nvit_crop_draw(uint64_t seed, int64_t* step, int64_t first_index, const double* aspect, double scale0, double scale1,
+                   double ratio_min, double ratio_max, float hflip, int* table, int B, int Hs, int Ws, void* stream);
+/* nvit_crop_apply: in uint8 [B,Hs,Ws,C], C in {1,3}, sides up to NVIT_CROP_MAX_SRC; out uint8 [B,size,size,C], size % 4
+ * == 0, size <= NVIT_AUG_MAX_SIDE.  Pillow's ImagingResample for 8-bit data on the box of table[b]: per axis the integer
+ * taps (22 fractional bits) are computed in fp64 by the workgroup that uses them, the horizontal pass writes a uint8
+ * [h,size,C] intermediate, the vertical pass reads it and folds the flip into its store index.  A table row whose box
+ * leaves the image counts as the whole image.  Taps and intermediate live in ws, ws_bytes >= nvit_crop_ws_bytes(...)
+ * (sized for the largest box, the whole image); every byte of out is written. */
+int64_t nvit_crop_ws_bytes(int B, int Hs, int Ws, int C, int size, int interp);
+int nvit_crop_apply(const void* in, const int* table, void* out, void* ws, int64_t ws_bytes, int B, int Hs, int Ws, int C,
+                    int size, int interp, void* stream);
+/* On-device RandomErasing (timm's, count 1, per image; tests/crop_ref.py) on the fp32 [B,C,H,W] model input.
+ * nvit_erase_draw: table int32 [B,NVIT_ERASE_ROW] = (on, top, left, h, w, noise key low, noise key high, 0).  Philox as in
+ * nvit_crop_draw under the erasing's own domain: a = NVIT_CROP_ATTEMPTS is the gate (r0 against prob), a = 0.. the attempts
+ * (area in [area0, area1] of H*W, aspect from the same kind of table, accepted if w < W and h < H; no fallback: after the
+ * last failed attempt nothing is erased), a = NVIT_CROP_ATTEMPTS + 1 the image's noise sub-key (r0, r1).  As in timm, an
+ * attempt whose h or w rounds to 0 (a tiny image or area) is accepted: the row then reads on = 1 with an empty box, whose
+ * top / left may equal H / W, and nvit_erase_apply erases nothing for it. */
+#define NVIT_ERASE_ROW 8
+#define NVIT_ERASE_KNOTS 1024
+#define NVIT_ERASE_CONST 0
+#define NVIT_ERASE_PIXEL 1
+int nvit_erase_draw(uint64_t seed, int64_t* step, int64_t first_index, const double* aspect, double area0, double area1,
+                    float prob, int* table, int B, int H, int W, void* stream);
+/* nvit_erase_apply: in, out fp32 [B,C,H,W], W % 4 == 0; out may be in (in place).  The box of table[b] is overwritten in
+ * every channel, by 0.0 (NVIT_ERASE_CONST) or by N(0,1) noise (NVIT_ERASE_PIXEL): float4 number e of the image takes
+ * Philox(counter = (e,0,0,0), key = the image's sub-key), and each of the four words indexes q, device fp32
+ * [NVIT_ERASE_KNOTS + 1] = the normal quantile at k / NVIT_ERASE_KNOTS with finite end knots, linearly between knots.
+ * Everything else is copied (left alone in place).  A row whose box leaves the image erases nothing. */
+int nvit_erase_apply(const float* in, const int* table, const float* q, float* out, int mode, int B, int C, int H, int W,
+                     void* stream);
 /* out[r,n] = a[r,n] * s[n] * c   (sz scaling model.py:466-468 and its backward); s == NULL: out = a * c */
 int nvit_scale_cols(const float* a, int lda, const float* s, float c, void* out, int out_dt, int ldo, int R, int N,
                     void* stream);

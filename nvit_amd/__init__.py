@@ -19,6 +19,9 @@ def __getattr__(name):
     if name in ("Mixup", "MixedBatch", "MixedTargets"):
         from . import mix
         return getattr(mix, name)
+    if name in ("RandomResizedCrop", "CroppedBatch", "RandomErasing", "ErasedBatch"):
+        from . import crop
+        return getattr(crop, name)
     if name == "FusedAdamW":
         from . import optim
         return optim.FusedAdamW

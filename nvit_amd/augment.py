@@ -222,10 +222,15 @@ def _check_images(u8: Tensor):
 
 class AugmentedBatch:
     """A uint8 [B,H,W,C] batch together with the AutoAugment that turns it into the model's input: what
-    `AutoAugment.batch(u8)` returns and `train_step` / `GraphedTrainStep` accept in place of X."""
+    `AutoAugment.batch(u8)` returns and `train_step` / `GraphedTrainStep` accept in place of X.  u8: the tensor, or a
+    `RandomResizedCrop.batch(u8)` (crop.py) whose crops are then what the policies see."""
 
-    def __init__(self, augment: "AutoAugment", u8: Tensor):
-        _check_images(u8)
+    def __init__(self, augment: "AutoAugment", u8):
+        from .crop import CroppedBatch   # (crop.py imports this module)
+        if isinstance(u8, CroppedBatch):
+            _check_hw(u8.shape[1], u8.shape[2])
+        else:
+            _check_images(u8)
         if u8.shape[2] % 4:
             raise ValueError("AutoAugment: the fp32 output needs W % 4 == 0")
         self.augment, self.u8 = augment, u8
@@ -239,7 +244,7 @@ class AugmentedBatch:
         return self.u8.device
 
     def augmented(self) -> Tensor:
-        return self.augment(self.u8)
+        return self.augment(self.u8 if isinstance(self.u8, Tensor) else self.u8.cropped())
 
 
 class DeviceStepCounter:

@@ -1,0 +1,382 @@
+"""RandomResizedCrop + horizontal flip and RandomErasing on the device: the per-image geometric half of the DeiT / timm
+from-scratch recipe (AutoAugment in augment.py is the augmentation half, Mixup / CutMix in mix.py the batch-level half).
+
+    RandomResizedCrop(224, interpolation="bicubic") -> flip -> AutoAugment -> normalize -> RandomErasing -> Mixup / CutMix
+    mix.batch(erase.batch(aug.batch(rrc.batch(u8))))
+
+A stored uint8 [B,Hs,Ws,C] batch becomes the mixed fp32 model input with no host work and no synchronisation, so the
+whole chain sits inside a captured train step.  Semantics (tests/crop_ref.py restates them in numpy):
+
+RandomResizedCrop: image b is `PIL.Image.crop(box).resize((size, size), BILINEAR | BICUBIC)`, bit for bit, then mirrored
+if its flip bit is set; the box is torchvision's `get_params` (ten attempts, then the central fallback).  Three launches
+(nvit_crop_draw, and the two passes of nvit_crop_apply).
+RandomErasing: timm's, count 1, per image, on the normalised fp32 batch: a box of `area` x the image at a log-uniform
+aspect is overwritten by 0 ("const") or by N(0,1) noise ("pixel").  Two launches (nvit_erase_draw, nvit_erase_apply).
+
+Both draws are the counter-based generator of augment.py (Philox4x32-10; counter = (first_index + image, step), key = seed
+with the class's own domain constant per attempt in its high word): an image's box depends only on (seed, global index,
+step), whatever the batch split.  No transcendental runs on the device: exp(U(log r0, log r1)) comes from a table of
+KNOTS + 1 fp64 values that the host computes and the kernel interpolates linearly (`aspect_table`), the noise from a
+table of normal quantiles (`normal_quantile_table`).
+"""
+from __future__ import annotations
+
+import functools
+import math
+import statistics
+from typing import Optional, Sequence
+
+import torch
+
+from . import _lib
+from ._lib import check
+from .augment import MAX_SIDE, AugmentedBatch, DeviceStepCounter
+from .ops import _chk_dev, _p, _s, normalize_images
+
+Tensor = torch.Tensor
+
+ROW = _lib.const("CROP_ROW")            # ints per row of the crop table: top, left, h, w, flip, 0, 0, 0
+KNOTS = _lib.const("CROP_KNOTS")        # the aspect table holds KNOTS + 1 values
+ATTEMPTS = _lib.const("CROP_ATTEMPTS")
+MAX_SRC = _lib.const("CROP_MAX_SRC")    # largest source side
+MAX_BATCH = _lib.const("CROP_MAX_BATCH")   # images per call of the two apply kernels (their grids' second dimension)
+INTERPOLATIONS = {"bilinear": _lib.const("CROP_BILINEAR"), "bicubic": _lib.const("CROP_BICUBIC")}
+ERASE_ROW = _lib.const("ERASE_ROW")     # on, top, left, h, w, noise key low, noise key high, 0
+ERASE_KNOTS = _lib.const("ERASE_KNOTS")
+ERASE_MODES = {"const": _lib.const("ERASE_CONST"), "pixel": _lib.const("ERASE_PIXEL")}
+NOISE_TAIL = 2.0 ** -15   # the end knots of the normal quantile table: the quantiles at NOISE_TAIL and 1 - NOISE_TAIL
+assert KNOTS == ERASE_KNOTS, "one interpolation (10 + 14 bits of a 24-bit uniform) serves both tables"
+
+
+# ---------------------------------------------------------------------------------------------- host tables (fp64)
+@functools.lru_cache(maxsize=None)
+def aspect_table(lo: float, hi: float) -> tuple:
+    """T[k] = exp(log lo + k / KNOTS * (log hi - log lo)), k = 0..KNOTS, in fp64: what exp(U(log lo, log hi)) is
+    interpolated from."""
+    l0, l1 = math.log(lo), math.log(hi)
+    return tuple(math.exp(l0 + k / KNOTS * (l1 - l0)) for k in range(KNOTS + 1))
+
+
+def aspect_table_deviation(lo: float, hi: float) -> float:
+    """The largest relative deviation of the chord through two neighbouring knots from the exponential it replaces
+    (always above it): with d the knots' distance in the logarithm and m = (e^d - 1) / d the chord's slope, the maximum of
+    (1 + m t) e^-t - 1 lies at t = (m - 1) / m and is m e^-((m - 1) / m) - 1, about d^2 / 8."""
+    d = (math.log(hi) - math.log(lo)) / KNOTS
+    if d == 0:
+        return 0.0
+    m = math.expm1(d) / d
+    return m * math.exp(-(m - 1.0) / m) - 1.0
+
+
+@functools.lru_cache(maxsize=None)
+def normal_quantile_table() -> tuple:
+    """Q[k] = the k / ERASE_KNOTS quantile of N(0,1), k = 1..ERASE_KNOTS-1, in fp64 (statistics.NormalDist), with the
+    finite end knots Q[0] = the NOISE_TAIL quantile = -Q[ERASE_KNOTS]; symmetric: Q[ERASE_KNOTS - k] = -Q[k]."""
+    nd = statistics.NormalDist()
+    q = [0.0] * (ERASE_KNOTS + 1)
+    q[0] = nd.inv_cdf(NOISE_TAIL)
+    for k in range(1, ERASE_KNOTS // 2):
+        q[k] = nd.inv_cdf(k / ERASE_KNOTS)
+    for k in range(ERASE_KNOTS // 2):
+        q[ERASE_KNOTS - k] = -q[k]
+    return tuple(q)
+
+
+# ---------------------------------------------------------------------------------------------- argument checks
+def _check_range(what: str, r, top: Optional[float] = None) -> tuple:
+    try:
+        lo, hi = r
+    except (TypeError, ValueError):
+        raise TypeError(f"{what} is a pair (low, high) (got {r!r})") from None
+    for v in (lo, hi):
+        if isinstance(v, bool) or not isinstance(v, (int, float)):
+            raise TypeError(f"{what} is a pair of numbers (got {r!r})")
+    if not (0.0 < lo <= hi < math.inf) or (top is not None and hi > top):   # also refuses NaN
+        raise ValueError(f"{what} must be 0 < low <= high{'' if top is None else f' <= {top}'} (got {r!r})")
+    return float(lo), float(hi)
+
+
+def _check_unit(what: str, p) -> float:
+    if isinstance(p, bool) or not isinstance(p, (int, float)):
+        raise TypeError(f"{what} must be a number (got {p!r})")
+    if not 0.0 <= p <= 1.0:   # also refuses NaN
+        raise ValueError(f"{what} must be in [0, 1] (got {p!r})")
+    return float(p)
+
+
+def _check_source(u8) -> tuple:
+    if not isinstance(u8, Tensor) or u8.dtype != torch.uint8:
+        raise TypeError("RandomResizedCrop takes a uint8 [B,Hs,Ws,C] batch")
+    if u8.dim() != 4:
+        raise ValueError(f"RandomResizedCrop takes a uint8 [B,Hs,Ws,C] batch (got rank {u8.dim()})")
+    B, Hs, Ws, C = u8.shape
+    if C not in (1, 3):
+        raise ValueError(f"RandomResizedCrop: C must be 1 or 3 (got {C}; the layout is [B,Hs,Ws,C])")
+    if not 1 <= B <= MAX_BATCH:
+        raise ValueError(f"RandomResizedCrop: a batch holds 1..{MAX_BATCH} images (got {B})")
+    _check_src_hw(Hs, Ws)
+    return B, Hs, Ws, C
+
+
+def _check_src_hw(Hs, Ws) -> None:
+    if not (isinstance(Hs, int) and isinstance(Ws, int) and 1 <= Hs <= MAX_SRC and 1 <= Ws <= MAX_SRC):
+        raise ValueError(f"RandomResizedCrop: source sides must be 1..{MAX_SRC} (got {Hs}x{Ws})")
+
+
+def _check_f32(X) -> tuple:
+    if not isinstance(X, Tensor) or X.dtype != torch.float32:
+        raise TypeError("RandomErasing takes an fp32 [B,C,H,W] batch")
+    if X.dim() != 4:
+        raise ValueError(f"RandomErasing takes an fp32 [B,C,H,W] batch (got rank {X.dim()})")
+    B, C, H, W = X.shape
+    if C < 1 or not 1 <= B <= MAX_BATCH:
+        raise ValueError(f"RandomErasing: a batch holds 1..{MAX_BATCH} images of at least one channel (got {B}, {C})")
+    _check_hw(H, W)
+    if W % 4:
+        raise ValueError("RandomErasing: W % 4 == 0 is required (as of every model input)")
+    return B, C, H, W
+
+
+def _check_hw(H, W) -> None:
+    if not (isinstance(H, int) and isinstance(W, int) and 1 <= H <= MAX_SIDE and 1 <= W <= MAX_SIDE):
+        raise ValueError(f"RandomErasing: image sides must be 1..{MAX_SIDE} (got {H}x{W})")
+
+
+# ---------------------------------------------------------------------------------------------- RandomResizedCrop
+class CroppedBatch:
+    """A stored uint8 [B,Hs,Ws,C] batch together with the RandomResizedCrop that cuts it: what `rrc.batch(u8)` returns
+    and `AutoAugment.batch` / `RandomErasing.batch` accept in place of a tensor.  `.shape` is that of its output."""
+
+    def __init__(self, crop: "RandomResizedCrop", u8: Tensor):
+        B, _, _, C = _check_source(u8)
+        self.crop, self.u8 = crop, u8
+        self._shape = torch.Size((B, crop.size, crop.size, C))
+
+    @property
+    def shape(self):
+        return self._shape
+
+    @property
+    def device(self):
+        return self.u8.device
+
+    def cropped(self) -> Tensor:
+        return self.crop(self.u8)
+
+
+class RandomResizedCrop(DeviceStepCounter):
+    """RandomResizedCrop(size, scale=(0.08, 1.0), ratio=(3/4, 4/3), interpolation="bilinear", hflip=0.5, seed=0,
+    first_index=0).to(device)
+
+    torchvision's RandomResizedCrop followed by RandomHorizontalFlip(hflip), on a uint8 [B,Hs,Ws,C] batch (C 1 or 3, one
+    source size per batch): uint8 [B,size,size,C] out, image b Pillow's crop(box).resize((size, size)) bit for bit.
+    size: a multiple of 4 up to MAX_SIDE (the fp32 stages behind it need W % 4 == 0); source sides up to MAX_SRC.
+    first_index: the global index of this batch's first image in the step; a data-parallel rank passes rank * B.
+
+    `rrc(u8)` draws the step's boxes and returns the crops; `draw` and `apply` are its halves; `params_for` writes a
+    table by hand.  The step counter lives on the device and the draw kernel advances it, so a captured graph that
+    contains the call draws fresh boxes at every replay."""
+
+    def __init__(self, size: int, scale=(0.08, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0), interpolation: str = "bilinear",
+                 hflip: float = 0.5, seed: int = 0, first_index: int = 0):
+        if isinstance(size, bool) or not isinstance(size, int):
+            raise TypeError(f"size must be an int (got {size!r})")
+        if not 4 <= size <= MAX_SIDE or size % 4:
+            raise ValueError(f"size must be a multiple of 4 in 4..{MAX_SIDE} (got {size})")
+        self.size = size
+        self.scale, self.ratio = _check_range("scale", scale), _check_range("ratio", ratio)
+        if not isinstance(interpolation, str):
+            raise TypeError(f"interpolation is a name: {', '.join(INTERPOLATIONS)} (got {interpolation!r})")
+        if interpolation not in INTERPOLATIONS:
+            raise ValueError(f"unknown interpolation {interpolation!r} (known: {', '.join(INTERPOLATIONS)})")
+        self.interpolation = interpolation
+        self.hflip = _check_unit("hflip", hflip)
+        super().__init__(seed, first_index)
+        self._aspect: Optional[Tensor] = None
+
+    def to(self, device) -> "RandomResizedCrop":
+        device = self._step_to(device)
+        self._aspect = torch.tensor(aspect_table(*self.ratio), dtype=torch.float64).to(device)
+        return self
+
+    # ------------------------------------------------------------------ the launches
+    def draw(self, B: int, Hs: int, Ws: int) -> Tensor:
+        """int32 [B,8] table of the next step (nvit_crop_draw): top, left, h, w, flip; advances the step counter."""
+        self._need_device()
+        if isinstance(B, bool) or not isinstance(B, int) or B < 1:
+            raise ValueError("RandomResizedCrop.draw: B must be an int >= 1")
+        _check_src_hw(Hs, Ws)
+        table = torch.empty((B, ROW), device=self.device, dtype=torch.int32)
+        check(_lib.load().nvit_crop_draw(self.seed, _p(self._step), self.first_index, _p(self._aspect), self.scale[0],
+                                         self.scale[1], self.ratio[0], self.ratio[1], self.hflip, _p(table), B, Hs, Ws,
+                                         _s()), "nvit_crop_draw")
+        return table
+
+    def apply(self, u8: Tensor, table: Tensor) -> Tensor:
+        """uint8 [B,size,size,C]: the box of table[b] of image b, resized and flipped (nvit_crop_apply, two launches).  A
+        row whose box leaves the image counts as the whole image."""
+        B, Hs, Ws, C = _check_source(u8)
+        if not isinstance(table, Tensor) or table.dtype != torch.int32 or tuple(table.shape) != (B, ROW):
+            raise ValueError(f"RandomResizedCrop.apply: the table must be int32 [{B},{ROW}]")
+        _chk_dev(u8, table)
+        u8, table = u8.contiguous(), table.contiguous()
+        lib, interp = _lib.load(), INTERPOLATIONS[self.interpolation]
+        ws_bytes = lib.nvit_crop_ws_bytes(B, Hs, Ws, C, self.size, interp)   # taps + the [Hs,size,C] intermediates
+        if ws_bytes < 0:
+            raise ValueError(f"RandomResizedCrop.apply: unsupported shape {tuple(u8.shape)} -> {self.size}")
+        ws = torch.empty(ws_bytes, device=u8.device, dtype=torch.uint8)
+        out = torch.empty((B, self.size, self.size, C), device=u8.device, dtype=torch.uint8)
+        check(lib.nvit_crop_apply(_p(u8), _p(table), _p(out), _p(ws), ws_bytes, B, Hs, Ws, C, self.size, interp, _s()),
+              "nvit_crop_apply")
+        return out
+
+    def __call__(self, u8: Tensor) -> Tensor:
+        B, Hs, Ws, _ = _check_source(u8)
+        _chk_dev(u8)
+        return self.apply(u8, self.draw(B, Hs, Ws))
+
+    def batch(self, u8: Tensor) -> CroppedBatch:
+        """What `AutoAugment.batch` / `RandomErasing.batch` take in place of a tensor: the crop then runs inside the
+        step (and inside its captured graph), once per batch."""
+        return CroppedBatch(self, u8)
+
+    # ------------------------------------------------------------------ tables by hand
+    def params_for(self, boxes: Sequence, flips: Optional[Sequence] = None) -> Tensor:
+        """int32 [B,8] from boxes[b] = (top, left, h, w) and flips[b] (default: none), as the draw writes them."""
+        boxes = [tuple(int(v) for v in box) for box in boxes]
+        if not boxes or any(len(box) != 4 for box in boxes):
+            raise ValueError("params_for: one (top, left, h, w) per image")
+        flips = [0] * len(boxes) if flips is None else [1 if f else 0 for f in flips]
+        if len(flips) != len(boxes):
+            raise ValueError("params_for: one flip per box")
+        t = torch.tensor([[*box, f, 0, 0, 0] for box, f in zip(boxes, flips)], dtype=torch.int32)
+        return t if self.device is None else t.to(self.device)
+
+
+# ---------------------------------------------------------------------------------------------- RandomErasing
+class ErasedBatch:
+    """A batch together with the RandomErasing that runs on it inside the step: what `erase.batch(X)` returns and
+    `Mixup.batch`, `train_step` and `GraphedTrainStep` accept in place of X.  X: an fp32 [B,C,H,W] tensor, an
+    `AutoAugment.batch(...)`, or a `RandomResizedCrop.batch(u8)` (then normalised with mean, std by
+    `ops.normalize_images`' kernel)."""
+
+    def __init__(self, erase: "RandomErasing", X, mean: float = 0.5, std: float = 0.5):
+        if isinstance(X, (AugmentedBatch, CroppedBatch)):
+            B, H, W, C = X.shape
+            _check_hw(H, W)
+            if W % 4:
+                raise ValueError("RandomErasing: W % 4 == 0 is required (as of every model input)")
+            self._shape = torch.Size((B, C, H, W))
+        else:
+            self._shape = torch.Size(_check_f32(X))
+        if std == 0:
+            raise ValueError("std must not be 0")
+        self.erase, self.X, self.mean, self.std = erase, X, float(mean), float(std)
+
+    @property
+    def shape(self):
+        return self._shape
+
+    @property
+    def device(self):
+        return self.X.device
+
+    def erased(self) -> Tensor:
+        """The launches of what X carries, then the draw and the apply; in place on a buffer made here."""
+        if isinstance(self.X, AugmentedBatch):
+            return self.erase(self.X.augmented(), inplace=True)
+        if isinstance(self.X, CroppedBatch):
+            return self.erase(normalize_images(self.X.cropped(), self.mean, self.std), inplace=True)
+        return self.erase(self.X)
+
+
+class RandomErasing(DeviceStepCounter):
+    """RandomErasing(prob=0.25, area=(0.02, 1/3), aspect=(0.3, 1/0.3), mode="pixel", seed=0, first_index=0).to(device)
+
+    timm's RandomErasing with count 1, per image, on the normalised fp32 [B,C,H,W] batch: with probability `prob` a box
+    of `area` x the image at a log-uniform aspect h/w in `aspect` is overwritten in every channel, by 0.0 ("const": the
+    mean after the normalise) or by per-element N(0,1) noise ("pixel").  Ten attempts to fit the box (w < W and h < H),
+    then nothing is erased.  first_index: as for RandomResizedCrop.
+
+    `erase(X)` returns the erased batch (a new tensor unless `inplace`); `draw` and `apply` are its halves; `params_for`
+    writes a table by hand."""
+
+    def __init__(self, prob: float = 0.25, area=(0.02, 1.0 / 3.0), aspect=(0.3, 1.0 / 0.3), mode: str = "pixel",
+                 seed: int = 0, first_index: int = 0):
+        self.prob = _check_unit("prob", prob)
+        self.area, self.aspect = _check_range("area", area, top=1.0), _check_range("aspect", aspect)
+        if not isinstance(mode, str):
+            raise TypeError(f"mode is a name: {', '.join(ERASE_MODES)} (got {mode!r})")
+        if mode not in ERASE_MODES:
+            raise ValueError(f"unknown mode {mode!r} (known: {', '.join(ERASE_MODES)})")
+        self.mode = mode
+        super().__init__(seed, first_index)
+        self._aspect: Optional[Tensor] = None
+        self._q: Optional[Tensor] = None
+
+    def to(self, device) -> "RandomErasing":
+        device = self._step_to(device)
+        self._aspect = torch.tensor(aspect_table(*self.aspect), dtype=torch.float64).to(device)
+        self._q = torch.tensor(normal_quantile_table(), dtype=torch.float64).to(torch.float32).to(device)
+        return self
+
+    def draw(self, B: int, H: int, W: int) -> Tensor:
+        """int32 [B,8] table of the next step (nvit_erase_draw): on, top, left, h, w, the image's noise sub-key; advances
+        the step counter."""
+        self._need_device()
+        if isinstance(B, bool) or not isinstance(B, int) or B < 1:
+            raise ValueError("RandomErasing.draw: B must be an int >= 1")
+        _check_hw(H, W)
+        table = torch.empty((B, ERASE_ROW), device=self.device, dtype=torch.int32)
+        check(_lib.load().nvit_erase_draw(self.seed, _p(self._step), self.first_index, _p(self._aspect), self.area[0],
+                                          self.area[1], self.prob, _p(table), B, H, W, _s()), "nvit_erase_draw")
+        return table
+
+    def apply(self, X: Tensor, table: Tensor, inplace: bool = False) -> Tensor:
+        """The erased fp32 [B,C,H,W] batch (nvit_erase_apply).  Out of place unless `inplace` (then X itself is returned,
+        erased): a caller's tensor is never modified behind their back."""
+        B, C, H, W = _check_f32(X)
+        if not isinstance(table, Tensor) or table.dtype != torch.int32 or tuple(table.shape) != (B, ERASE_ROW):
+            raise ValueError(f"RandomErasing.apply: the table must be int32 [{B},{ERASE_ROW}]")
+        self._need_device()
+        _chk_dev(X, table)
+        if inplace and not X.is_contiguous():
+            raise ValueError("RandomErasing.apply: in place needs a contiguous batch")
+        X, table = X.contiguous(), table.contiguous()
+        out = X if inplace else torch.empty_like(X)
+        check(_lib.load().nvit_erase_apply(_p(X), _p(table), _p(self._q), _p(out), ERASE_MODES[self.mode], B, C, H, W, _s()),
+              "nvit_erase_apply")
+        return out
+
+    def __call__(self, X: Tensor, inplace: bool = False) -> Tensor:
+        B, _, H, W = _check_f32(X)
+        _chk_dev(X)
+        return self.apply(X, self.draw(B, H, W), inplace=inplace)
+
+    def batch(self, X, mean: float = 0.5, std: float = 0.5) -> ErasedBatch:
+        """The X of `train_step(model, optimizer, erase.batch(X), y)`, of `GraphedTrainStep` and of `Mixup.batch`.  X: fp32
+        [B,C,H,W], an `AutoAugment.batch(...)`, or a `RandomResizedCrop.batch(u8)`; mean and std serve the last."""
+        return ErasedBatch(self, X, mean, std)
+
+    def params_for(self, boxes: Sequence, keys: Optional[Sequence] = None) -> Tensor:
+        """int32 [B,8] from boxes[b] = (top, left, h, w) or None (not erased) and keys[b] = the image's 64-bit noise
+        sub-key (default b), as the draw writes them."""
+        boxes = list(boxes)
+        if not boxes:
+            raise ValueError("params_for: no images")
+        keys = list(range(len(boxes))) if keys is None else [int(k) for k in keys]
+        if len(keys) != len(boxes):
+            raise ValueError("params_for: one key per box")
+
+        def i32(v):
+            v &= 0xFFFFFFFF
+            return v - (1 << 32) if v >= 1 << 31 else v
+
+        rows = []
+        for box, key in zip(boxes, keys):
+            on, box = (0, (0, 0, 0, 0)) if box is None else (1, tuple(int(v) for v in box))
+            if len(box) != 4:
+                raise ValueError("params_for: a box is (top, left, h, w) or None")
+            rows.append([on, *box, i32(key), i32(key >> 32), 0])
+        t = torch.tensor(rows, dtype=torch.int32)
+        return t if self.device is None else t.to(self.device)

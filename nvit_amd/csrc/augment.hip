@@ -16,10 +16,11 @@
 // (two per image, each used by this workgroup only, so they stay in L2), which makes one code path for every image size.
 //
 // Further down, the batch-level mixing that follows it (Mixup / CutMix, tests/mix_ref.py is the numpy twin), here for the
-// Philox and for the file-wide contract(off):
+// file-wide contract(off) (the Philox function is philox.h's, shared with crop.hip):
 //   nvit_mix_draw       one workgroup, one thread per pair of rows -> int32 [B,8] table, lambda and the partner's label
 //   nvit_mix_apply      fp32 [B,C,H,W] -> fp32 [B,C,H,W], float4 streaming over (pair, chunk of the image)
 #include "common.h"
+#include "philox.h"
 
 // a fused a + f*b changes truncations by one level: nothing in this file contracts, except normalize4 below.  (Plain
 // operators on purpose: the __fmul_rn/__fadd_rn of the HIP headers are inline a*b / a+b compiled under the headers' own
@@ -36,26 +37,6 @@ constexpr int AUG_NMAG = NVIT_AUG_NMAG;
 
 enum AugOp { OP_IDENTITY = 0, OP_SHEAR_X, OP_SHEAR_Y, OP_TRANSLATE_X, OP_TRANSLATE_Y, OP_ROTATE, OP_BRIGHTNESS, OP_COLOR,
              OP_CONTRAST, OP_SHARPNESS, OP_POSTERIZE, OP_SOLARIZE, OP_AUTOCONTRAST, OP_EQUALIZE, OP_INVERT };
-
-// ------------------------------------------------------------------------------------------------ Philox4x32-10
-struct Philox4 {
-  unsigned v[4];
-};
-__device__ __forceinline__ Philox4 philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0,
-                                                 unsigned k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
-    const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1;
-    c1 = (unsigned)p1;
-    c3 = (unsigned)p0;
-    c0 = n0;
-    c2 = n2;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  return Philox4{{c0, c1, c2, c3}};
-}
 
 // policy: int32 [P,2,3] = (op, probability as fp32 bits, magnitude index); argtab: int32 [15,10,2,8], the parameter row
 // of every (op, magnitude index, sign) for this image size, computed by the host in fp64.

@@ -23,6 +23,7 @@ import torch
 from . import _lib
 from ._lib import check
 from .augment import MAX_SIDE, AugmentedBatch, DeviceStepCounter, _f32_bits
+from .crop import ErasedBatch
 from .ops import _chk_dev, _p, _s
 
 Tensor = torch.Tensor
@@ -207,10 +208,11 @@ class MixedTargets:
 
 class MixedBatch:
     """A batch together with the Mixup that mixes it inside the step: what `Mixup.batch(X)` returns and `train_step` /
-    `GraphedTrainStep` accept in place of X.  X: an fp32 [B,C,H,W] tensor, or an `AutoAugment.batch(u8)`."""
+    `GraphedTrainStep` accept in place of X.  X: an fp32 [B,C,H,W] tensor, an `AutoAugment.batch(u8)`, or a
+    `RandomErasing.batch(...)` (crop.py)."""
 
     def __init__(self, mix: "Mixup", X):
-        if isinstance(X, AugmentedBatch):
+        if isinstance(X, (AugmentedBatch, ErasedBatch)):
             B = X.shape[0]
         else:
             B = _check_images(X)[0]
@@ -232,6 +234,8 @@ class MixedBatch:
         self.check_labels(y)
         if isinstance(self.X, AugmentedBatch):
             return self.mix(self.X.augmented(), y, inplace=True)   # a fresh buffer: mixed in place
+        if isinstance(self.X, ErasedBatch):
+            return self.mix(self.X.erased(), y, inplace=True)      # (the erasing never returns the caller's tensor)
         return self.mix(self.X, y)
 
 

@@ -19,6 +19,7 @@ import torch
 
 from . import ops
 from .augment import AugmentedBatch
+from .crop import CroppedBatch, ErasedBatch
 from .mix import MixedBatch, MixedTargets
 from .optim import FusedAdamW, renorm_matrices
 
@@ -112,13 +113,48 @@ def _check_step_args(optimizer, X, accumulation_steps, skip_nonfinite) -> None:
 
 
 def _unwrap_input(X):
-    """X of a step -> (Mixup or None, AutoAugment or None, the tensor underneath)."""
-    mix = aug = None
+    """X of a step -> ({"mix": Mixup, "erase": (RandomErasing, mean, std), "augment": AutoAugment, "crop":
+    RandomResizedCrop}, the stages it carries; the tensor underneath).  The wrappers only nest in this order."""
+    stages = {}
     if isinstance(X, MixedBatch):
-        mix, X = X.mix, X.X
+        stages["mix"], X = X.mix, X.X
+    if isinstance(X, ErasedBatch):
+        stages["erase"], X = (X.erase, X.mean, X.std), X.X
     if isinstance(X, AugmentedBatch):
-        aug, X = X.augment, X.u8
-    return mix, aug, X
+        stages["augment"], X = X.augment, X.u8
+    if isinstance(X, CroppedBatch):
+        if "augment" not in stages and "erase" not in stages:
+            raise TypeError("a RandomResizedCrop.batch(u8) is uint8: wrap it in AutoAugment.batch or RandomErasing.batch")
+        stages["crop"], X = X.crop, X.u8
+    return stages, X
+
+
+def _wrap_input(stages: dict, X):
+    """The chain of `_unwrap_input` around another tensor."""
+    if "crop" in stages:
+        X = stages["crop"].batch(X)
+    if "augment" in stages:
+        X = stages["augment"].batch(X)
+    if "erase" in stages:
+        erase, mean, std = stages["erase"]
+        X = erase.batch(X, mean, std)
+    if "mix" in stages:
+        X = stages["mix"].batch(X)
+    return X
+
+
+def _resolve_input(X, y):
+    """(X, y) of a step -> the model's input and the loss's target: every launch of the chain that X carries (crop,
+    AutoAugment, erasing, Mixup - each once, for the whole batch), in order.  A tensor X comes back as it is."""
+    if isinstance(X, MixedBatch):
+        return X.mixed(y)   # the launches of what it wraps, then draw + apply
+    if isinstance(X, ErasedBatch):
+        return X.erased(), y
+    if isinstance(X, AugmentedBatch):
+        return X.augmented(), y
+    if isinstance(X, CroppedBatch):
+        _unwrap_input(X)   # raises
+    return X, y
 
 
 def _forward_backward(model, X, y, n: int, before_micro=None):
@@ -182,13 +218,15 @@ def train_step(model, optimizer, X: torch.Tensor, y: torch.Tensor, grad_clip: fl
     micro-batch i takes rows [i*b, (i+1)*b) of the mixed batch and of the targets (a row's partner may lie in another
     micro-batch; the targets carry the partner's label).  The returned logits belong to the mixed batch.
 
+    The full input chain (crop.py) is `mix.batch(erase.batch(aug.batch(rrc.batch(u8))))`: RandomResizedCrop + flip on the
+    stored uint8 batch, AutoAugment on the crops, RandomErasing on the normalised batch, then Mixup / CutMix; any stage may
+    be left out (an erasing directly around a crop normalises it first).  Every stage's launches run once for the whole
+    batch, in this order, ahead of the forward and of any accumulation split, and every stage's counter advances by one.
+
     Wrong accumulation_steps (no int, < 1, no divisor of the batch) or skip_nonfinite with another optimizer raise
     ValueError before any device work."""
     _check_step_args(optimizer, X, accumulation_steps, skip_nonfinite)
-    if isinstance(X, MixedBatch):
-        X, y = X.mixed(y)   # the augmentation's launches if any, then draw + apply, ahead of any accumulation split
-    elif isinstance(X, AugmentedBatch):
-        X = X.augmented()   # two launches for the whole batch, ahead of any accumulation split
+    X, y = _resolve_input(X, y)   # the chain's launches for the whole batch, ahead of any accumulation split
     logits, loss, aux = _forward_backward(model, X, y, accumulation_steps)
     if sync_grads is not None:
         sync_grads()
@@ -243,6 +281,10 @@ class GraphedTrainStep:
     (or uint8 batch) and y; the Mixup's draw and apply are captured ahead of the forward and after the augmentation, and
     the same rule holds for its counter: warm-up steps advance it, the capture pass does not, every replay does.  Calls
     take the raw batch or a `batch(...)` of the same Mixup; one of another Mixup raises ValueError.
+
+    The same holds for every stage of the full chain `mix.batch(erase.batch(aug.batch(rrc.batch(u8))))` (crop.py): the
+    static inputs are the innermost tensor (the stored uint8 batch) and y, every stage's launches are captured in order,
+    and every replay draws fresh boxes.  Calls take the innermost tensor or a chain of the captured objects.
     """
 
     def __init__(self, model, optimizer, X: torch.Tensor, y: torch.Tensor, grad_clip: float = 1.0, warmup: int = 3,
@@ -257,7 +299,9 @@ class GraphedTrainStep:
             raise RuntimeError("GraphedTrainStep: inputs must live on the HIP device")
         if isinstance(X, MixedBatch):
             X.check_labels(y)
-        self.mix, self.augment, X = _unwrap_input(X)
+        self._stages, X = _unwrap_input(X)
+        self.mix, self.augment = self._stages.get("mix"), self._stages.get("augment")
+        self.erase, self.crop = self._stages.get("erase", (None,))[0], self._stages.get("crop")
         self.model, self.optimizer, self.grad_clip = model, optimizer, grad_clip
         self.accumulation_steps, self.skip_nonfinite = accumulation_steps, bool(skip_nonfinite)
         N = accumulation_steps
@@ -289,9 +333,7 @@ class GraphedTrainStep:
 
         try:
             with torch.cuda.graph(self.graph, stream=side):
-                Xin, yin = (self.augment(self.X) if self.augment is not None else self.X), self.y
-                if self.mix is not None:
-                    Xin, yin = self.mix(Xin, yin, inplace=self.augment is not None)
+                Xin, yin = _resolve_input(self._input(), self.y)
                 logits, loss, aux = _forward_backward(model, Xin, yin, N, hand_rates)
                 gnorm = optimizer.step_fused(model, grad_clip, skip_nonfinite=self.skip_nonfinite)
         finally:
@@ -309,8 +351,7 @@ class GraphedTrainStep:
         optimizer.zero_grad(set_to_none=True)
 
     def _input(self):
-        X = self.augment.batch(self.X) if self.augment is not None else self.X
-        return self.mix.batch(X) if self.mix is not None else X
+        return _wrap_input(self._stages, self.X)
 
     def set_lr(self, lr: float) -> None:
         for group in self.optimizer.param_groups:
@@ -341,9 +382,20 @@ class GraphedTrainStep:
             if X.mix is not self.mix:
                 raise ValueError("GraphedTrainStep: this graph was captured with another Mixup (or none)")
             X = X.X
+        if isinstance(X, ErasedBatch):
+            if X.erase is not self.erase:
+                raise ValueError("GraphedTrainStep: this graph was captured with another RandomErasing (or none)")
+            if (X.mean, X.std) != self._stages["erase"][1:]:
+                raise ValueError("GraphedTrainStep: this graph was captured with another mean / std of erase.batch "
+                                 f"{self._stages['erase'][1:]} (got {(X.mean, X.std)})")
+            X = X.X
         if isinstance(X, AugmentedBatch):
             if X.augment is not self.augment:
                 raise ValueError("GraphedTrainStep: this graph was captured with another augmentation (or none)")
+            X = X.u8
+        if isinstance(X, CroppedBatch):
+            if X.crop is not self.crop:
+                raise ValueError("GraphedTrainStep: this graph was captured with another RandomResizedCrop (or none)")
             X = X.u8
         self.X.copy_(X, non_blocking=True)
         self.y.copy_(y, non_blocking=True)
