@@ -14,8 +14,8 @@ from nvit_amd.config import named_config
 from nvit_amd.weights import formula_state_dict, synthetic_batch
 from oracle import nvit_oracle as O
 
-PAD = 4096          # elements of padding on each side (a multiple of 8: keeps 16-byte alignment)
-SENTINEL = -12288.0   # exact in bf16 and fp32
+# the padding harness (NaN operand margins, sentinel output margins); test_gpu_heads_pad.py takes it from here
+from attn_check import PAD, SENTINEL, Padded, operand, output, run_bwd, run_fwd   # noqa: F401
 
 
 def dev():
@@ -31,67 +31,6 @@ def _sdpa_ref(qh, kh, vh, scale):
     s = (qh @ kh.transpose(-1, -2)) * scale
     p = torch.softmax(s, dim=-1)
     return p @ vh, torch.logsumexp(s, dim=-1)
-
-
-class Padded:
-    """A tensor placed in the middle of a larger device buffer whose margins hold `fill`."""
-
-    def __init__(self, shape, dtype, fill, data=None):
-        n = math.prod(shape)
-        self.buf = torch.full((n + 2 * PAD,), fill, dtype=dtype, device=dev())
-        self.t = self.buf[PAD:PAD + n].view(shape)
-        if data is not None:
-            self.t.copy_(data)
-        self.fill = fill
-
-    def ptr(self):
-        return self.t.data_ptr()
-
-    def margins_intact(self):
-        m = torch.cat([self.buf[:PAD], self.buf[-PAD:]]).float()
-        return bool(torch.isnan(m).all()) if math.isnan(self.fill) else bool((m == self.fill).all())
-
-
-def operand(x):
-    return Padded(tuple(x.shape), x.dtype, float("nan"), x.to(dev()))
-
-
-def output(shape, dtype):
-    return Padded(shape, dtype, SENTINEL)
-
-
-def run_fwd(dt, impl, q, k, v, scale, sqk=None, c_q=0.0, q_prescale=1.0):
-    """nvit_attn_fwd / nvit_attn_fwd_bounded on padded operands and outputs; returns (o, lse) as plain tensors."""
-    from nvit_amd import _lib, ops
-    (B, H, Tq, d), Tk = q.shape, k.shape[2]
-    qp, kp, vp = operand(q), operand(k), operand(v)
-    o, lse = output((B * Tq, H * d), q.dtype), output((B, H, Tq), torch.float32)
-    lib = _lib.load()
-    if sqk is None:
-        rc = lib.nvit_attn_fwd(dt, impl, qp.ptr(), kp.ptr(), vp.ptr(), scale, o.ptr(), lse.ptr(), B, H, Tq, Tk, d, ops._s())
-    else:
-        sp = operand(sqk)
-        rc = lib.nvit_attn_fwd_bounded(dt, impl, qp.ptr(), kp.ptr(), vp.ptr(), scale, sp.ptr(), c_q, q_prescale, o.ptr(),
-                                       lse.ptr(), B, H, Tq, Tk, d, ops._s())
-    ops.check(rc, "nvit_attn_fwd")
-    torch.cuda.synchronize()
-    assert o.margins_intact() and lse.margins_intact()
-    return o.t.clone(), lse.t.clone()
-
-
-def run_bwd(dt, impl, g_tok, q, k, v, o, lse, scale):
-    from nvit_amd import _lib, ops
-    (B, H, Tq, d), Tk = q.shape, k.shape[2]
-    gp, qp, kp, vp, op, lp = (operand(x) for x in (g_tok, q, k, v, o, lse))
-    dq, dk, dv = (output((B, H, T, d), q.dtype) for T in (Tq, Tk, Tk))
-    delta = Padded((2, B, H, Tq), torch.float32, float("nan"))   # workspace: written before it is read
-    rc = _lib.load().nvit_attn_bwd(dt, impl, gp.ptr(), qp.ptr(), kp.ptr(), vp.ptr(), op.ptr(), lp.ptr(), scale, dq.ptr(),
-                                   dk.ptr(), dv.ptr(), delta.ptr(), B, H, Tq, Tk, d, ops._s())
-    ops.check(rc, "nvit_attn_bwd")
-    torch.cuda.synchronize()
-    for x in (dq, dk, dv):
-        assert x.margins_intact()
-    return dq.t.clone(), dk.t.clone(), dv.t.clone()
 
 
 def _inputs(dtype, B, H, T, d, Tk=None):
