@@ -78,6 +78,7 @@ const char* nvit_prof_name(int kid);
 #define NVIT_RENORM_TALL_ROWS 1152          /* dim=0 matrices with more rows take the narrow panel */
 #define NVIT_RENORM_TALL_COLS_PER_ITEM 32
 #define NVIT_RENORM_MAX_ROWS_DIM0 2048
+#define NVIT_RENORM_MAX_GRID 2048           /* workgroups of the launch: workgroup b takes the items b, b + grid, ... */
 int nvit_renorm_weights(const int64_t* table, int n, int total_items, void* stream);
 
 /* nvit_shadow_weights: builds the private MFMA-operand copies of the fp32 master weights
@@ -130,6 +131,7 @@ int nvit_shadow_weights(const int64_t* table, int n, int total_items, int dt, vo
 #define NVIT_OPT_WIDE_COLS 2048      /* a wider one (up to this) is parked in LDS, */
 #define NVIT_OPT_WIDE_LDS_ROWS 1024  /* which is then sized as for a slab of this many rows */
 #define NVIT_OPT_MAX_PART 4096
+#define NVIT_OPT_MAX_GRID 2048       /* workgroups of nvit_adamw_renorm: workgroup b takes the items b, b + grid, ... */
 int nvit_adamw_tick(float* hyper, double beta1, double beta2, void* stream);
 int nvit_grad_sqnorm(const int64_t* table, int n, int total_chunks, float* partial, int npart, void* stream);
 int nvit_adamw_renorm(const int64_t* table, int n, int total_items, int max_slab_rows, float beta1, float beta2,

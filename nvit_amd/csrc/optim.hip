@@ -417,7 +417,7 @@ static int adamw_renorm_launch(const int64_t* table, int n, int total_items, int
     if (e != hipSuccess) NVIT_FAIL((int)e, "adamw_renorm: cannot raise LDS limit: %s", hipGetErrorString(e));
     lds_set[which] = lds;
   }
-  int grid = total_items < 2048 ? total_items : 2048;
+  int grid = total_items < NVIT_OPT_MAX_GRID ? total_items : NVIT_OPT_MAX_GRID;
   ProfScope ps(NVIT_KID_OPTIM, 0.0, 0.0, s);
   if (skip_state)
     hipLaunchKernelGGL(adamw_renorm_kernel<const float*>, dim3(grid), dim3(1024), lds, s, table, n, total_items, partial, a,

@@ -222,7 +222,7 @@ extern "C" int nvit_renorm_weights(const int64_t* table, int n, int total_items,
     if (e != hipSuccess) NVIT_FAIL((int)e, "renorm: cannot raise LDS limit: %s", hipGetErrorString(e));
     attr_set = true;
   }
-  int grid = total_items < 2048 ? total_items : 2048;
+  int grid = total_items < NVIT_RENORM_MAX_GRID ? total_items : NVIT_RENORM_MAX_GRID;
   ProfScope ps(NVIT_KID_RENORM, 0.0, 0.0, s);
   hipLaunchKernelGGL(renorm_kernel, dim3(grid), dim3(RENORM_THREADS), kMaxLds, s, table, n, total_items);
   NVIT_CHECK_LAUNCH("renorm");

@@ -6,7 +6,6 @@ that straddle every boundary; whole model against numbers recorded from the refe
 (tests/golden/wide*_b2.npz, tools/make_golden_wide.py) with the bars the BASELINE sizes are held to
 (tests/test_gpu_model.py); several steps against the CPU oracle."""
 import os
-import types
 
 import numpy as np
 import pytest
@@ -20,6 +19,7 @@ from nvit_amd.config import named_config
 from nvit_amd.weights import formula_state_dict, synthetic_batch
 
 import vit_torch_ref
+from optim_check import _fake_model  # noqa: F401  (it lives there; kept importable from here)
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 DEV = "cuda:0"
@@ -34,19 +34,6 @@ ROW_SHAPES = [(40, 1536), (40, 1540), (24, 2048), (8 * 64, 1280)]
 def rnd(*shape, seed=0, scale=1.0):
     g = torch.Generator().manual_seed(seed)
     return torch.randn(*shape, generator=g) * scale
-
-
-def _fake_model(rows, cols):
-    """The renorm map step_fused builds from ViT blocks, for hand-made matrices: blocks of 4 row-normalised + 2
-    column-normalised slots, padded with repeats."""
-    W = lambda p: types.SimpleNamespace(weight=p)
-    blocks = []
-    for i in range(max(len(rows), len(cols), 1)):
-        r, c = rows[i % len(rows)], cols[i % len(cols)]
-        blocks.append(types.SimpleNamespace(query=W(r), key=W(r), value=W(r), c_fc=W(r), att_c_proj=W(c),
-                                            mlp_c_proj=W(c)))
-    return types.SimpleNamespace(config=types.SimpleNamespace(use_nvit=True),
-                                 transformer=types.SimpleNamespace(h=blocks))
 
 
 def build(cfg, precision, renormed=True):
