@@ -152,6 +152,27 @@ int nvit_adamw_renorm_guarded(const int64_t* table, int n, int total_items, int 
                               float eps, const float* partial, int npart, float max_norm, float* gnorm_out,
                               const float* hyper, const float* skip_state, void* stream);
 
+/* Exponential moving average of the weights (ModelEma), two launches per optimizer step: nvit_ema_tick, nvit_ema_update.
+ * state: 4 floats on the device, zeroed by the caller once: {t = updates applied so far, omd = 1 - d of the update about
+ *        to run, spare, spare}.  The count is a float, exact up to 2^24 updates, like hyper[0] of nvit_adamw_tick.
+ * nvit_ema_tick: one thread, in fp64: d = warmup ? min(decay, (1 + t) / (10 + t)) : decay with t the count before this
+ *        update; stores omd = (float)(1 - d) and t + 1.  skip_state (optional, the optimizer's own): when given and
+ *        skip_state[0] != 0 the count stays as it is and omd = 0 is stored.
+ * nvit_ema_update: table = n rows of NVIT_EMA_TABLE_COLS int64 {src, dst (fp32 device pointers), numel, first_chunk,
+ *        flags}; work items are chunks of NVIT_EMA_CHUNK elements, first_chunk = prefix sum, total_chunks = sum; at most
+ *        NVIT_EMA_MAX_GRID workgroups, workgroup b takes the chunks b, b + grid, ...  Per element dst = fma(omd, src -
+ *        dst, dst) with omd = state[1]; every workgroup returns before it touches memory when omd == 0.  A row with
+ *        NVIT_EMA_FLAG_COPY stores src unchanged.  A row whose numel is no multiple of 4, or whose src or dst is not
+ *        16-byte aligned, must carry NVIT_EMA_FLAG_SCALAR (element-wise accesses; the others use float4).  The src and
+ *        dst ranges of a table must not overlap.  state == NULL: only the copy rows run. */
+#define NVIT_EMA_TABLE_COLS 5
+#define NVIT_EMA_CHUNK 4096
+#define NVIT_EMA_MAX_GRID 2048
+#define NVIT_EMA_FLAG_COPY 1
+#define NVIT_EMA_FLAG_SCALAR 2
+int nvit_ema_tick(float* state, double decay, int warmup, const float* skip_state, void* stream);
+int nvit_ema_update(const int64_t* table, int n, int total_chunks, const float* state, void* stream);
+
 /* ---- GEMMs ------------------------------------------------------------------------
  * nvit_gemm_nt: C[M,N] = A[M,K] * B[N,K]^T  (nn.Linear: model.py:99-101,130,148,155,...)
  * A, B of type dt, K % (128/sizeof(dt)) == 0, lda/ldb multiples of 16 bytes.

@@ -22,6 +22,9 @@ def __getattr__(name):
     if name in ("RandomResizedCrop", "CroppedBatch", "RandomErasing", "ErasedBatch"):
         from . import crop
         return getattr(crop, name)
+    if name == "ModelEma":
+        from . import ema
+        return ema.ModelEma
     if name == "FusedAdamW":
         from . import optim
         return optim.FusedAdamW

@@ -45,9 +45,12 @@ def _numpy_safe_globals():
 
 
 def build_checkpoint(model, optimizer, iter_num: int, metrics: Dict[str, float], config: Optional[Dict[str, Any]] = None,
-                     rng_state_pytorch: Optional[torch.Tensor] = None) -> Dict[str, Any]:
+                     rng_state_pytorch: Optional[torch.Tensor] = None, *, ema=None) -> Dict[str, Any]:
+    """ema: a `ModelEma`; the checkpoint then gains the key "model_ema" = ema.state_dict() (tensors and plain values, so
+    the weights-only load takes it); restore with `ema.load_state_dict(ck["model_ema"])`.  Without it the key set is the
+    reference's."""
     m = model.module if hasattr(model, "module") else model
-    return {
+    ck = {
         "model": _model_state(m),
         "optimizer": optimizer.state_dict(),
         "model_args": asdict(m.config),
@@ -58,13 +61,16 @@ def build_checkpoint(model, optimizer, iter_num: int, metrics: Dict[str, float],
         "rng_state_numpy": np.random.get_state(),
         "timestamp": time.strftime("%d_%m_%Y-%Hh%Mm"),
     }
+    if ema is not None:
+        ck["model_ema"] = ema.state_dict()
+    return ck
 
 
 def save_checkpoint(path, model, optimizer, iter_num: int, metrics: Dict[str, float],
-                    config: Optional[Dict[str, Any]] = None) -> Path:
+                    config: Optional[Dict[str, Any]] = None, *, ema=None) -> Path:
     path = Path(path)
     path.parent.mkdir(parents=True, exist_ok=True)
-    torch.save(build_checkpoint(model, optimizer, iter_num, metrics, config), path)
+    torch.save(build_checkpoint(model, optimizer, iter_num, metrics, config, ema=ema), path)
     return path
 
 

@@ -961,6 +961,69 @@ def shadow_weights(table: Tensor, total_items: int, dt: int) -> None:
     check(_lib.load().nvit_shadow_weights(_p(table), table.shape[0], total_items, dt, _s()), "nvit_shadow_weights")
 
 
+# ----------------------------------------------------------------------------- weight EMA
+EMA_TABLE_COLS = _lib.const("EMA_TABLE_COLS")
+EMA_CHUNK = _lib.const("EMA_CHUNK")          # elements per work item of nvit_ema_update
+EMA_MAX_GRID = _lib.const("EMA_MAX_GRID")    # its workgroups: a table of more chunks takes several sweeps
+EMA_FLAG_COPY = _lib.const("EMA_FLAG_COPY")
+EMA_FLAG_SCALAR = _lib.const("EMA_FLAG_SCALAR")
+
+
+def ema_table(pairs, device) -> Tuple[Tensor, int]:
+    """pairs: list of (src, dst) or (src, dst, copy) with src, dst contiguous fp32 device tensors of equal, non-zero
+    numel -> (device table of nvit_ema_update, total_chunks).  copy=True flags a row that stores src unchanged.  A row
+    of numel % 4 != 0, or with a pointer that is not 16-byte aligned, is flagged for the element-wise path here.
+    ValueError when a dst range overlaps any other range of the table (its own src included); sources may repeat.
+    The host image is pinned, so do not call this during a stream capture."""
+    rows_, spans, first = [], [], 0
+    for pair in pairs:
+        src, dst = pair[0], pair[1]
+        copy = bool(pair[2]) if len(pair) > 2 else False
+        _chk_dev(src, dst)
+        for t in (src, dst):
+            if t.dtype != torch.float32 or not t.is_contiguous():
+                raise RuntimeError("ema_table: contiguous fp32 tensors expected")
+        n = src.numel()
+        if n == 0 or dst.numel() != n:
+            raise ValueError(f"ema_table: src and dst need the same non-zero numel (got {n} and {dst.numel()})")
+        sp, dp = src.data_ptr(), dst.data_ptr()
+        flags = (EMA_FLAG_COPY if copy else 0) | (EMA_FLAG_SCALAR if (n % 4 or sp % 16 or dp % 16) else 0)
+        rows_.append([sp, dp, n, first, flags])
+        spans += [(sp, sp + 4 * n, False), (dp, dp + 4 * n, True)]
+        first += math.ceil(n / EMA_CHUNK)
+    if not rows_:
+        raise ValueError("ema_table: no rows")
+    if first >= 2 ** 31:
+        raise ValueError("ema_table: too many chunks for one table")
+    end_any = end_dst = 0   # sweep over the ranges by start address: a dst may meet nothing, a src no dst
+    for lo, hi, is_dst in sorted(spans):
+        if lo < (end_any if is_dst else end_dst):
+            raise ValueError("ema_table: a destination overlaps another range of the table (src == dst included)")
+        end_any = max(end_any, hi)
+        if is_dst:
+            end_dst = max(end_dst, hi)
+    host = torch.tensor(rows_, dtype=torch.int64).pin_memory()
+    return host.to(device, non_blocking=True), first
+
+
+def ema_tick(state: Tensor, decay: float, warmup: bool, skip_state: Optional[Tensor] = None) -> None:
+    """state (fp32 device [4]: updates applied, omd, spare, spare): omd = 1 - d for the update about to run, d =
+    min(decay, (1 + t) / (10 + t)) with warmup and decay without, computed in fp64 on the device, and t += 1.  The count
+    is a float, exact up to 2^24 updates (like the optimizer's hyper[0]).  With skip_state (the optimizer's) and
+    skip_state[0] != 0 the count stays and omd = 0."""
+    _chk_dev(state, skip_state)
+    if state.dtype != torch.float32 or state.numel() < 4 or not state.is_contiguous():
+        raise RuntimeError("ema_tick: state must be a contiguous fp32 tensor of 4 elements")
+    check(_lib.load().nvit_ema_tick(_p(state), float(decay), int(bool(warmup)), _p(skip_state), _s()), "nvit_ema_tick")
+
+
+def ema_update(table: Tensor, total_chunks: int, state: Optional[Tensor] = None) -> None:
+    """dst = fma(omd, src - dst, dst) over the table's rows with omd = state[1] (nothing is touched when it is 0); copy
+    rows store src.  state=None: only the copy rows run."""
+    _chk_dev(table, state)
+    check(_lib.load().nvit_ema_update(_p(table), table.shape[0], total_chunks, _p(state), _s()), "nvit_ema_update")
+
+
 # ----------------------------------------------------------------------------- profiling
 def prof_enable(on: bool) -> None:
     _lib.load().nvit_prof_enable(int(on))

@@ -90,6 +90,7 @@ class FusedAdamW(torch.optim.AdamW):
         self._hyper_ev = None
         self._skip_state = None   # device float[2], see skip_state
         self._guarded = False     # a skip_nonfinite step has run: only the device knows how many steps were applied
+        self._ema = None          # attach_ema: a ModelEma that every step updates
 
     # ------------------------------------------------------------------ state
     def _ensure_state(self, p: torch.Tensor) -> Dict:
@@ -223,6 +224,8 @@ class FusedAdamW(torch.optim.AdamW):
                                                 _p(c["partial"]), _NPART, float(grad_clip) if clip else 0.0,
                                                 _p(c["gnorm"]), _p(self._hyper), _p(skip), _s()),
                   "nvit_adamw_renorm_guarded")
+            if self._ema is not None:
+                self._ema.update(skip)   # the tick reads the decision just taken: a step left out is no update
             return c["gnorm"]
         check(lib.nvit_adamw_tick(_p(self._hyper), b1, b2, _s()), "nvit_adamw_tick")
         self._t += 1
@@ -234,7 +237,24 @@ class FusedAdamW(torch.optim.AdamW):
                                     float(grad_clip) if clip else 0.0, _p(c["gnorm"]) if clip else None,
                                     _p(self._hyper), _s()),
               "nvit_adamw_renorm")
+        if self._ema is not None:
+            self._ema.update()
         return c["gnorm"] if clip else None
+
+    # ------------------------------------------------------------------ weight EMA
+    def attach_ema(self, ema) -> None:
+        """ema: a `ModelEma` of the model this optimizer steps, or None to detach.  Every step (step_fused, step()) then
+        ends with `ema.update()`, two more launches: one optimizer step is one update whatever accumulation_steps is, and a
+        step that skip_nonfinite leaves out leaves the average alone.  Attach before a GraphedTrainStep is built, so that
+        the captured step holds the update."""
+        if ema is not None and not (callable(getattr(ema, "update", None)) and callable(getattr(ema, "mark_dirty", None))):
+            raise TypeError("attach_ema: a ModelEma (or None) expected")
+        self._ema = ema
+
+    @property
+    def ema(self):
+        """The attached ModelEma, or None."""
+        return self._ema
 
     # ------------------------------------------------------------------ skipped steps
     @property
@@ -303,6 +323,8 @@ class FusedAdamW(torch.optim.AdamW):
     def note_replay(self, n: int = 1) -> None:
         """A captured step was replayed n times (the device counter advanced; keep the host mirror in sync)."""
         self._t += n
+        if self._ema is not None:
+            self._ema.mark_dirty()   # the replay updated the average on the device
 
     def _sync_state_steps(self) -> None:
         if self._guarded and self._hyper is not None:

@@ -285,6 +285,11 @@ class GraphedTrainStep:
     The same holds for every stage of the full chain `mix.batch(erase.batch(aug.batch(rrc.batch(u8))))` (crop.py): the
     static inputs are the innermost tensor (the stored uint8 batch) and y, every stage's launches are captured in order,
     and every replay draws fresh boxes.  Calls take the innermost tensor or a chain of the captured objects.
+
+    A `ModelEma` (ema.py) attached to the optimizer before this object is built is part of the captured step: its tick and
+    its update follow the optimizer's launches, and its count lives on the device.  The warm-up steps are updates, as they
+    are optimizer steps; the capture pass is not (it executes nothing).  A call with another EMA attached than at capture
+    time (or none, or one where there was none) raises ValueError.
     """
 
     def __init__(self, model, optimizer, X: torch.Tensor, y: torch.Tensor, grad_clip: float = 1.0, warmup: int = 3,
@@ -303,6 +308,7 @@ class GraphedTrainStep:
         self.mix, self.augment = self._stages.get("mix"), self._stages.get("augment")
         self.erase, self.crop = self._stages.get("erase", (None,))[0], self._stages.get("crop")
         self.model, self.optimizer, self.grad_clip = model, optimizer, grad_clip
+        self.ema = optimizer.ema   # the ModelEma (or none) whose update the warm-up steps run and the capture records
         self.accumulation_steps, self.skip_nonfinite = accumulation_steps, bool(skip_nonfinite)
         N = accumulation_steps
         self.X, self.y = X.clone(), y.clone()
@@ -397,6 +403,8 @@ class GraphedTrainStep:
             if X.crop is not self.crop:
                 raise ValueError("GraphedTrainStep: this graph was captured with another RandomResizedCrop (or none)")
             X = X.u8
+        if self.optimizer.ema is not self.ema:
+            raise ValueError("GraphedTrainStep: this graph was captured with another ModelEma (or none)")
         self.X.copy_(X, non_blocking=True)
         self.y.copy_(y, non_blocking=True)
         self._advance_som()
