@@ -611,7 +611,8 @@ int nvit_recon_bwd(int dt, const float* raw, const float* img, const float* g, v
 
 /* Loss side: F.cross_entropy(logits, Y) of train.py:906 with its gradient in the same pass.
  * rowloss[B] (workspace) = logsumexp(row) - row[label]; loss[0] = mean; dlogits[B,N] = (softmax - onehot) / B
- * (multiply by the upstream scalar gradient).  Labels outside [0,N) contribute 0 loss (and a plain softmax/B row). */
+ * (multiply by the upstream scalar gradient).  Labels outside [0,N) contribute 0 loss (and a plain softmax/B row); the
+ * range test is made on the 64-bit label (2^32 + 1 is outside, not class 1), here and in the two entries below. */
 int nvit_ce_loss(const float* logits, const int64_t* labels, float* rowloss, float* loss, float* dlogits, int B, int N,
                  void* stream);
 /* The same with a soft target (Mixup / CutMix / label smoothing, timm's mixup_target): row b's target is
@@ -623,7 +624,9 @@ int nvit_ce_loss_soft(const float* logits, const int64_t* labels, const int64_t*
                       float* rowloss, float* loss, float* dlogits, int B, int N, void* stream);
 /* Evaluation metrics of one batch in one launch (reference train.py:563-575, 595-613): per row the cross-entropy of
  * nvit_ce_loss and rank = #{j : logit_j > logit_y} + #{j < y : logit_j == logit_y} (a label outside [0,N): loss 0,
- * never correct).  ADDS to the device accumulator acc[0..3]: the batch-mean loss, 100 * #(rank < 1) / B,
+ * never correct).  NaN logits take the order of torch.topk: a NaN ranks above every number, NaNs tie with each other and
+ * the lower index wins.  So a NaN logit that is not the label's outranks the label, and a NaN label logit is a top-1 hit
+ * only when no NaN precedes it; the accumulated loss of such a batch is NaN.  ADDS to the device accumulator acc[0..3]: the batch-mean loss, 100 * #(rank < 1) / B,
  * 100 * #(rank < min(5,N)) / B, and 1 (the batch count) - the reference reports means over batches of per-batch
  * values.  Fixed-order reduction, no float atomics: reproducible run to run.  Nothing goes back to the host. */
 int nvit_eval_metrics(const float* logits, const int64_t* labels, float* acc, int B, int N, void* stream);

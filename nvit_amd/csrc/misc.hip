@@ -262,6 +262,12 @@ extern "C" int nvit_recon_loss(const float* raw, const float* img, float* part, 
 // a fixed order (deterministic).
 namespace {
 
+// The label as a class index, or -1 when it lies outside [0, N).  The range test is made on the 64-bit value: a label
+// such as 2^32 + 1 must not alias class 1 by narrowing first.
+__device__ __forceinline__ int label_in_range(int64_t label, int N) {
+  return label >= 0 && label < (int64_t)N ? (int)label : -1;
+}
+
 __global__ __launch_bounds__(256) void ce_rows_kernel(const float* logits, const int64_t* labels, float* rowloss,
                                                       float* dlogits, int B, int N) {
   __shared__ float red[4];
@@ -281,9 +287,9 @@ __global__ __launch_bounds__(256) void ce_rows_kernel(const float* logits, const
   if (lane == 0) red[wid] = s;
   __syncthreads();
   s = red[0] + red[1] + red[2] + red[3];
-  const int lab = (int)labels[b];
+  const int lab = label_in_range(labels[b], N);
   const float lse = mx + logf(s);
-  if (tid == 0) rowloss[b] = (lab >= 0 && lab < N) ? lse - row[lab] : 0.f;
+  if (tid == 0) rowloss[b] = lab >= 0 ? lse - row[lab] : 0.f;
   const float inv = 1.0f / s, invB = 1.0f / (float)B;
   float* drow = dlogits + (size_t)b * N;
   for (int n = tid; n < N; n += 256) drow[n] = (expf(row[n] - mx) * inv - (n == lab ? 1.0f : 0.0f)) * invB;
@@ -324,8 +330,8 @@ __global__ __launch_bounds__(256) void ce_soft_rows_kernel(const float* logits, 
     __syncthreads();
     mean = (red[0] + red[1] + red[2] + red[3]) / (float)N;
   }
-  const int lab = (int)labels[b], lab2 = (int)labels2[b];
-  const bool ok = lab >= 0 && lab < N, ok2 = lab2 >= 0 && lab2 < N;
+  const int lab = label_in_range(labels[b], N), lab2 = label_in_range(labels2[b], N);
+  const bool ok = lab >= 0, ok2 = lab2 >= 0;
   const float lam = lam_rows[b], om = 1.0f - lam, keep = 1.0f - eps, epsN = eps / (float)N;
   const float lse = mx + logf(s);
   if (tid == 0) rowloss[b] = lse - keep * (lam * (ok ? row[lab] : 0.f) + om * (ok2 ? row[lab2] : 0.f)) - eps * mean;
@@ -352,7 +358,7 @@ __global__ __launch_bounds__(256) void ce_mean_kernel(const float* rowloss, floa
 
 // Evaluation metrics (reference train.py:563-575, 595-613): cross-entropy as above plus the rank of the target, which
 // replaces topk: the label is among the k largest iff fewer than k logits beat it (ties broken towards the lower
-// index).  ONE workgroup of 16 waves: wave w takes rows w, w + 16, ... and keeps its own running sums, the waves'
+// index; a NaN logit ranks above every number, as in topk, so a diverged row is not counted as a hit).  ONE workgroup of 16 waves: wave w takes rows w, w + 16, ... and keeps its own running sums, the waves'
 // sums are added in wave order by thread 0 - a fixed order, no atomics, no per-row buffer.  The logits of an
 // evaluation batch are [B, classes] (0.5 MB at B = 128, 1000 classes): a sliver beside the forward that made them.
 constexpr int EVAL_WAVES = 16;
@@ -367,15 +373,19 @@ __global__ __launch_bounds__(64 * EVAL_WAVES) void eval_metrics_kernel(const flo
   int top1 = 0, topk = 0;
   for (int b = wid; b < B; b += EVAL_WAVES) {
     const float* row = logits + (size_t)b * N;
-    const int lab = (int)labels[b];
-    const bool ok = lab >= 0 && lab < N;
+    const int lab = label_in_range(labels[b], N);
+    const bool ok = lab >= 0;
     const float ly = ok ? row[lab] : INFINITY;
+    const bool ly_nan = ly != ly;
     float mx = -INFINITY;
     int rank = 0;
     for (int n = lane; n < N; n += 64) {
       const float v = row[n];
       mx = fmaxf(mx, v);
-      rank += (v > ly || (v == ly && n < lab)) ? 1 : 0;
+      // the order of topk: NaN above every number, NaNs tie with each other, a tie goes to the lower index
+      const bool v_nan = v != v;
+      const bool beats = ly_nan ? (v_nan && n < lab) : (v_nan || v > ly || (v == ly && n < lab));
+      rank += beats ? 1 : 0;
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
