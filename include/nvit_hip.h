@@ -259,6 +259,7 @@ int nvit_gemm_tn(int dt, const void* A, int lda, const void* B, int ldb, float* 
 #define NVIT_MAX_EMBD 2048
 #define NVIT_MAX_PART_BLOCKS 4096
 #define NVIT_ROW_WAVES 4
+#define NVIT_ROW_GRID_MAX 2048 /* the forward row kernels launch at most this many workgroups and stride over the rest */
 int nvit_lerp_fwd(int dt, const float* h, const void* y, int y_dt, const float* alpha, float c_a,
                   const float* skip_x, const float* skip, float* out, void* out_lo, int M, int C, void* stream);
 /* nvit_lerp_bwd: given dout, recomputes the forward and writes dh (fp32; += if accum_dh), dy (fp32
@@ -275,6 +276,20 @@ int nvit_lerp_bwd(int dt, const float* dout, const void* dout_add, const float* 
                   float c_a, const float* skip_x, const float* skip, float* dh, int accum_dh, float* dy,
                   void* dy_lo, float* dskip_x, float* part_dlam, float* part_dskip, int nblk, int M, int C,
                   void* stream);
+/* Gated LERP (stochastic depth): rows m*rows_per_sample .. belong to sample m, and gate[m] (fp32, one per sample: the row
+ * of nvit_droppath_draw's table for this block and branch) multiplies the step of the LERP for all of them:
+ * out = nrm(nrm(h) + (gate * |alpha*c_a|) * (nrm(y) - nrm(h))); the fused norm_skip is not gated.  The backward is that of
+ * the gated forward: dy and the part_dlam terms carry the gate.  With every gate 1.0f each output has the bits of the
+ * plain entry point.  M must be a multiple of rows_per_sample.  nvit_lerp_bwd_gated is built for the two calls of the
+ * block chain: skip_x without accum_dh (the MLP half) or accum_dh without skip_x (the attention half). */
+int nvit_lerp_fwd_gated(int dt, const float* h, const void* y, int y_dt, const float* alpha, float c_a,
+                        const float* skip_x, const float* skip, const float* gate, int rows_per_sample, float* out,
+                        void* out_lo, int M, int C, void* stream);
+int nvit_lerp_bwd_gated_blocks(int dt, int y_dt, int C, int has_add, int has_skip, int accum);
+int nvit_lerp_bwd_gated(int dt, const float* dout, const void* dout_add, const float* h, const void* y, int y_dt,
+                        const float* alpha, float c_a, const float* skip_x, const float* skip, const float* gate,
+                        int rows_per_sample, float* dh, int accum_dh, float* dy, void* dy_lo, float* dskip_x,
+                        float* part_dlam, float* part_dskip, int nblk, int M, int C, void* stream);
 
 /* RMSNorm (model.py:170-182; not on the nViT path, provided so that the public module works):
  * out = x * rsqrt(mean(x^2) + eps) * w, fp32 [M, C]; rstd [M] saved for the backward.
@@ -302,6 +317,22 @@ int nvit_res_skip_fwd(int dt, const float* h, const void* y, int y_dt, const flo
 int nvit_res_skip_bwd(int dt, const float* dout, const float* h, const void* y, int y_dt, const float* skip,
                       const float* x, float* dh, void* dh_lo, float* dx, float* part_dskip, int nblk, int M, int C,
                       void* stream);
+/* Gated forms (stochastic depth of the plain-ViT block chain): gate fp32, one per sample, rows m*rows_per_sample .. belong
+ * to sample m, M a multiple of rows_per_sample; the branch output enters as gate * y wherever the plain kernel adds y:
+ * z = a + gate * y (res_rmsnorm), (h + gate * y) (res_skip); y is required.  Backward: the fp32 outputs dz / dh stay the
+ * gradient of the sum, which goes on down the stream; the type-dt copies dz_lo / dh_lo are gate * that = d(y), what the
+ * branch's GEMMs read (fp32 mode included: there the caller can no longer alias the two).  nvit_res_rmsnorm_bwd_gated is
+ * built with the addend g_add only.  With every gate 1.0f each output has the bits of the plain entry point. */
+int nvit_res_rmsnorm_fwd_gated(int dt, const float* a, const void* y, int y_dt, const float* w, float eps, const float* gate,
+                               int rows_per_sample, float* out, void* out_lo, float* rstd, int M, int C, void* stream);
+int nvit_res_rmsnorm_bwd_gated(int dt, const float* g, const void* g_add, const float* a, const void* y, int y_dt,
+                               const float* w, const float* rstd, const float* gate, int rows_per_sample, float* dz,
+                               int accum, void* dz_lo, float* part_dw, int nblk, int M, int C, void* stream);
+int nvit_res_skip_fwd_gated(int dt, const float* h, const void* y, int y_dt, const float* skip, const float* x,
+                            const float* gate, int rows_per_sample, float* out, void* out_lo, int M, int C, void* stream);
+int nvit_res_skip_bwd_gated(int dt, const float* dout, const float* h, const void* y, int y_dt, const float* skip,
+                            const float* x, const float* gate, int rows_per_sample, float* dh, void* dh_lo, float* dx,
+                            float* part_dskip, int nblk, int M, int C, void* stream);
 /* Block.norm_skip on its own (model.py:84-87): out = nrm(src*skip[0] + tgt), fp32 [M,C]; backward writes dsrc, dtgt
  * (tgt == NULL / dtgt == NULL: the target term is absent, i.e. justnorm(src*skip[0]), model.py:43-44,89-90)
  * and part_dskip [nblk]. (ViT.forward uses the copy fused into nvit_lerp_fwd/bwd.) */
@@ -426,6 +457,15 @@ int nvit_mix_draw(uint64_t seed, int64_t* step, int64_t first_index, const float
  * (two rounded products, one add); CutMix: rows i and j exchange the pixels of [y0,y1) x [x0,x1) in every channel.  A row
  * of mode 0, a row that is its own partner, and a row whose partner does not name it back with the same mode is copied. */
 int nvit_mix_apply(const float* in, const int* table, float* out, int B, int C, int H, int W, void* stream);
+/* Stochastic depth (DropPath; tests/droppath_ref.py).  nvit_droppath_draw: table fp32 [2*n_layer, B], row
+ * 2*l + br = the gates of branch br (0 attention, 1 MLP) of block l, one per sample: 0.0f (dropped) or, kept, 1.0f /
+ * keep_l (scale_by_keep != 0) or 1.0f, keep_l = 1.0f - rates[l] (rates: device fp32 [n_layer], each in [0, 1)).  One
+ * Philox4x32-10 call per gate, counter = (first_index + b, *step), key = seed with (a domain constant + the row index)
+ * xor-ed into its high word; the sample is kept iff (r0 >> 8) * 2^-24 < keep_l.  At most NVIT_DROPPATH_MAX_GATES gates per
+ * call.  *step is a device int64 that the kernel reads and then advances by one, as nvit_augment_draw does. */
+#define NVIT_DROPPATH_MAX_GATES 1048576
+int nvit_droppath_draw(uint64_t seed, int64_t* step, int64_t first_index, const float* rates, int scale_by_keep,
+                       float* table, int n_layer, int B, void* stream);
 /* On-device RandomResizedCrop + horizontal flip (tests/crop_ref.py): a stored uint8 [B,Hs,Ws,C] batch ->
  * uint8 [B,size,size,C], image b = Pillow's crop(box b).resize((size, size), BILINEAR | BICUBIC), mirrored if its flip
  * bit is set, bit for bit.  Three launches per batch: the draw and the two passes of the apply.

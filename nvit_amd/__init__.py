@@ -25,6 +25,9 @@ def __getattr__(name):
     if name == "ModelEma":
         from . import ema
         return ema.ModelEma
+    if name == "DropPath":
+        from . import droppath
+        return droppath.DropPath
     if name == "FusedAdamW":
         from . import optim
         return optim.FusedAdamW

@@ -83,6 +83,10 @@ SIGNATURES = {
     "nvit_lerp_fwd": [_i, _vp, _vp, _i, _vp, _f, _vp, _vp, _vp, _vp, _i, _i, _vp],
     "nvit_lerp_bwd_blocks": [_i, _i, _i, _i, _i, _i],
     "nvit_lerp_bwd": [_i, _vp, _vp, _vp, _vp, _i, _vp, _f, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
+    "nvit_lerp_fwd_gated": [_i, _vp, _vp, _i, _vp, _f, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _vp],
+    "nvit_lerp_bwd_gated_blocks": [_i, _i, _i, _i, _i, _i],
+    "nvit_lerp_bwd_gated": [_i, _vp, _vp, _vp, _vp, _i, _vp, _f, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i,
+                            _i, _vp],
     "nvit_norm_skip_fwd": [_vp, _vp, _vp, _vp, _i, _i, _vp],
     "nvit_norm_skip_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
     "nvit_qknorm_fwd": [_i, _vp, _i, _vp, _i, _vp, _i, _vp, _f, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
@@ -104,6 +108,7 @@ SIGNATURES = {
     "nvit_augment_apply": [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _f, _f, _vp],
     "nvit_mix_draw": [C.c_uint64, _vp, _i64, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
     "nvit_mix_apply": [_vp, _vp, _vp, _i, _i, _i, _i, _vp],
+    "nvit_droppath_draw": [C.c_uint64, _vp, _i64, _vp, _i, _vp, _i, _i, _vp],
     "nvit_crop_draw": [C.c_uint64, _vp, _i64, _vp, C.c_double, C.c_double, C.c_double, C.c_double, _f, _vp, _i, _i, _i, _vp],
     "nvit_crop_ws_bytes": [_i, _i, _i, _i, _i, _i],
     "nvit_crop_apply": [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _vp],
@@ -133,6 +138,10 @@ SIGNATURES = {
     "nvit_res_rmsnorm_bwd": [_i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp],
     "nvit_res_skip_fwd": [_i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp],
     "nvit_res_skip_bwd": [_i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
+    "nvit_res_rmsnorm_fwd_gated": [_i, _vp, _vp, _i, _vp, _f, _vp, _i, _vp, _vp, _vp, _i, _i, _vp],
+    "nvit_res_rmsnorm_bwd_gated": [_i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _vp],
+    "nvit_res_skip_fwd_gated": [_i, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _vp],
+    "nvit_res_skip_bwd_gated": [_i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
     "nvit_som_update": [_vp, _vp, _vp, _f, _f, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp],
     "nvit_som_update_dev": [_vp, _vp, _vp, _vp, _f, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp],
     "nvit_cos_consistency_fwd": [_vp, _vp, _vp, _vp, _i, _vp, _i64, _i, _vp],

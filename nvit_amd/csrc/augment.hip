@@ -19,6 +19,8 @@
 // file-wide contract(off) (the Philox function is philox.h's, shared with crop.hip):
 //   nvit_mix_draw       one workgroup, one thread per pair of rows -> int32 [B,8] table, lambda and the partner's label
 //   nvit_mix_apply      fp32 [B,C,H,W] -> fp32 [B,C,H,W], float4 streaming over (pair, chunk of the image)
+// and the one draw that sits inside the model, stochastic depth (tests/droppath_ref.py is the numpy twin):
+//   nvit_droppath_draw  one workgroup -> fp32 [2*n_layer, B] gates of the gated row kernels (rowops.hip)
 #include "common.h"
 #include "philox.h"
 
@@ -407,7 +409,45 @@ __global__ __launch_bounds__(MIX_THREADS) void mix_apply_kernel(const float* in,
   }
 }
 
+// ------------------------------------------------------------------------------------------------ stochastic depth
+// (tests/droppath_ref.py is the numpy twin.)  table fp32 [2*n_layer, B]: row 2*l + br holds the gates of
+// branch br (0 attention, 1 MLP) of block l for every sample.  One Philox call per gate: the counter is (first_index + b,
+// step) as in the other draws, the row index is added to the domain constant in the key's high word (the 128-bit
+// counter is full), so a sample's gate depends on its global index, the step and the row only.
+constexpr unsigned DROPPATH_DOMAIN = 0x44525054u;
+
+__global__ __launch_bounds__(256) void droppath_draw_kernel(unsigned long long seed, long long* step_ctr, long long first_index,
+                                                            const float* __restrict__ rates, int scale_by_keep,
+                                                            float* __restrict__ table, int n_layer, int B) {
+  const unsigned long long step = (unsigned long long)*step_ctr;
+  const int n = 2 * n_layer * B;
+  for (int i = threadIdx.x; i < n; i += blockDim.x) {
+    const int row = i / B, b = i - row * B;
+    const unsigned long long g = (unsigned long long)(first_index + b);
+    const Philox4 r = philox4x32_10((unsigned)g, (unsigned)(g >> 32), (unsigned)step, (unsigned)(step >> 32),
+                                    (unsigned)seed, (unsigned)(seed >> 32) ^ (DROPPATH_DOMAIN + (unsigned)row));
+    const float keep = 1.0f - rates[row >> 1];
+    const bool kept = (float)(r.v[0] >> 8) * 0x1p-24f < keep;   // exact: 24 bits
+    table[i] = kept ? (scale_by_keep ? 1.0f / keep : 1.0f) : 0.0f;
+  }
+  __syncthreads();   // every thread has read the counter
+  if (threadIdx.x == 0) *step_ctr = (long long)(step + 1);
+}
+
 }  // namespace
+
+extern "C" int nvit_droppath_draw(uint64_t seed, int64_t* step, int64_t first_index, const float* rates, int scale_by_keep,
+                                  float* table, int n_layer, int B, void* stream) {
+  NVIT_REQUIRE(step && rates && table && first_index >= 0, "droppath_draw: bad arguments");
+  NVIT_REQUIRE(n_layer > 0 && B > 0 && (long long)n_layer * B <= NVIT_DROPPATH_MAX_GATES / 2,
+               "droppath_draw: 2 * n_layer * B must be in 1..%d", NVIT_DROPPATH_MAX_GATES);
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope ps(NVIT_KID_PATCHIFY, 0.0, 2.0 * n_layer * B * 4.0, s);
+  hipLaunchKernelGGL(droppath_draw_kernel, dim3(1), dim3(256), 0, s, (unsigned long long)seed, (long long*)step,
+                     (long long)first_index, rates, scale_by_keep, table, n_layer, B);
+  NVIT_CHECK_LAUNCH("droppath_draw");
+  return NVIT_OK;
+}
 
 extern "C" int nvit_mix_draw(uint64_t seed, int64_t* step, int64_t first_index, const float* q_mix, const float* q_cut,
                              float prob, float switch_prob, const int64_t* labels, int* table, float* lam, int64_t* y2,

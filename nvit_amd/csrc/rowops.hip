@@ -63,9 +63,22 @@ struct LerpFwdArgs {
   float* out;
   void* out_lo;
   int M, C;
+  const float* gate;   // GATED kernels: one fp32 gate per sample (DropPath), rows m*T .. m*T+T-1 belong to sample m
+  int T;
 };
 
-template <int NV, typename TY, typename TL>
+// The gate of row m's sample.  A wave owns one row, so m is the same in all its lanes: the index is taken from the first
+// lane and the table read through the constant address space (nothing writes it while a row kernel runs) - one scalar
+// load per row, no vector register.
+__device__ __forceinline__ float row_gate(const float* gate, int m, int T) {
+  typedef const __attribute__((address_space(4))) float* cfloat_p;
+  return ((cfloat_p)gate)[__builtin_amdgcn_readfirstlane(m) / T];
+}
+
+// GATED (stochastic depth): the row's step sizes are gate * |alpha*c_a|, so a dropped sample (gate 0) leaves nrm(h).  A
+// template switch like those of lerp_bwd_kernel; with gate 1.0f the products are exact and the bits those of the plain
+// kernel.
+template <int NV, typename TY, typename TL, bool GATED>
 __global__ __launch_bounds__(256) void lerp_fwd_kernel(LerpFwdArgs a) {
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   RowVec<NV> lam;
@@ -94,12 +107,15 @@ __global__ __launch_bounds__(256) void lerp_fwd_kernel(LerpFwdArgs a) {
       }
     }
     if (a.skip_x) row_load_f32_nt<NV>(xs, a.skip_x + (size_t)m * a.C, a.C, lane);   // with the others: one round trip per row
+    float gt = 1.0f;
+    if constexpr (GATED) gt = row_gate(a.gate, m, a.T);
     const float rsx = 1.0f / sqrtf(row_dot<NV>(x, x));
     const float rsy = 1.0f / sqrtf(row_dot<NV>(y, y));
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
       const f32x4 av = x.v[i] * rsx, bv = y.v[i] * rsy;
-      r.v[i] = av + lam.v[i] * (bv - av);
+      if constexpr (GATED) r.v[i] = av + (lam.v[i] * gt) * (bv - av);
+      else r.v[i] = av + lam.v[i] * (bv - av);
     }
     const float rsr = 1.0f / sqrtf(row_dot<NV>(r, r));
 #pragma unroll
@@ -138,6 +154,8 @@ struct LerpBwdArgs {
   float* part_dlam;
   float* part_dskip;
   int M, C;
+  const float* gate;   // GATED kernels: as in LerpFwdArgs
+  int T;
 };
 
 // ADD: the incoming gradient has a second, bf16 addend (a.dout_add).  A template switch, not a run-time test: with the test
@@ -157,7 +175,9 @@ __device__ __forceinline__ float dot4(const f32x4& a, const f32x4& b) {
 
 // SKIP (norm_skip fused behind the LERP: the MLP half of a block) and ACCUM (dh += : the attention half, whose dh already
 // holds the gradient of the skip path) are template switches as well: a row then keeps 5 vectors in flight instead of 6.
-template <int NV, typename TY, typename TL, bool ADD, bool SKIP, bool ACCUM>
+// GATED (stochastic depth, see lerp_fwd_kernel): the row's step sizes are gate * lam wherever lam is used, and the row's
+// term of d(lam) carries the gate; the gate sits in a scalar register and the products are formed where they are used.
+template <int NV, typename TY, typename TL, bool ADD, bool SKIP, bool ACCUM, bool GATED>
 __global__ __launch_bounds__(256, 1) void lerp_bwd_kernel(LerpBwdArgs a) {
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   RowVec<NV> lam, dlam;
@@ -186,6 +206,9 @@ __global__ __launch_bounds__(256, 1) void lerp_bwd_kernel(LerpBwdArgs a) {
       }
     }
     if constexpr (SKIP) row_load_f32_nt<NV>(t, a.skip_x + ro, a.C, lane);
+    float gt = 1.0f;
+    if constexpr (GATED) gt = row_gate(a.gate, m, a.T);
+#define NVIT_LAM(i_) (GATED ? lam.v[i_] * gt : lam.v[i_])   /* the row's step sizes */
     if constexpr (ADD) {   // incoming gradient = dout + dout_add: the GEMM that produced dout_add need not read-modify-write dout
 #pragma unroll
       for (int i = 0; i < NV; ++i) {
@@ -202,11 +225,11 @@ __global__ __launch_bounds__(256, 1) void lerp_bwd_kernel(LerpBwdArgs a) {
     for (int i = 0; i < NV; ++i) {
       av.v[i] = av.v[i] * rsx;
       bv.v[i] = bv.v[i] * rsy;
-      const f32x4 ou = av.v[i] + lam.v[i] * (bv.v[i] - av.v[i]);
+      const f32x4 ou = av.v[i] + NVIT_LAM(i) * (bv.v[i] - av.v[i]);
       ss += dot4<NV>(ou, ou);
     }
     const float rsr = 1.0f / sqrtf(wave_sum(ss));
-#define NVIT_LERP_O(i_) ((av.v[i_] + lam.v[i_] * (bv.v[i_] - av.v[i_])) * rsr)   /* o = lerp output (unit norm), recomputed */
+#define NVIT_LERP_O(i_) ((av.v[i_] + NVIT_LAM(i_) * (bv.v[i_] - av.v[i_])) * rsr)   /* o = lerp output (unit norm), recomputed */
     if constexpr (SKIP) {
       // t = o*skip + xs ; out = t/|t| ; dt = (g - out<out,g>)/|t| ; do = skip*dt ; dxs = dt ; dskip += <dt,o>
       float st = 0.f;
@@ -243,8 +266,8 @@ __global__ __launch_bounds__(256, 1) void lerp_bwd_kernel(LerpBwdArgs a) {
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
       g.v[i] = (g.v[i] - NVIT_LERP_O(i) * og) * rsr;   // g = dr
-      dlam.v[i] += g.v[i] * (bv.v[i] - av.v[i]);
-      const f32x4 db = lam.v[i] * g.v[i];
+      dlam.v[i] += (GATED ? g.v[i] * gt : g.v[i]) * (bv.v[i] - av.v[i]);
+      const f32x4 db = NVIT_LAM(i) * g.v[i];
       ada += dot4<NV>(av.v[i], g.v[i] - db);
       bdb += dot4<NV>(bv.v[i], db);
     }
@@ -254,7 +277,7 @@ __global__ __launch_bounds__(256, 1) void lerp_bwd_kernel(LerpBwdArgs a) {
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
       const int c = (i * 64 + lane) * 4;
-      const f32x4 db = lam.v[i] * g.v[i];
+      const f32x4 db = NVIT_LAM(i) * g.v[i];
       f32x4 dh = ((g.v[i] - db) - av.v[i] * ada) * rsx;
       const f32x4 dy = (db - bv.v[i] * bdb) * rsy;
       if constexpr (ACCUM) dh += old.v[i];
@@ -264,6 +287,7 @@ __global__ __launch_bounds__(256, 1) void lerp_bwd_kernel(LerpBwdArgs a) {
         if (a.dy_lo) store4<TL>(reinterpret_cast<TL*>(a.dy_lo) + ro + c, dy);
       }
     }
+#undef NVIT_LAM
   }
   // column partials: one row per wave (fixed layout, reduced in fixed order by nvit_colsum_reduce)
   const size_t prow = (size_t)blockIdx.x * ROW_WAVES + wid;
@@ -909,9 +933,12 @@ struct ResRmsFwdArgs {
   void* out_lo;
   float* rstd;
   int M, C;
+  const float* gate;   // GATED kernels: one fp32 gate per sample (DropPath), T rows per sample
+  int T;
 };
 
-template <int NV, typename TY, typename TL, bool HAS_Y>
+// GATED (stochastic depth of the plain-ViT blocks, with HAS_Y): z = a + gate * y, the gate folded into y where it is loaded.
+template <int NV, typename TY, typename TL, bool HAS_Y, bool GATED>
 __global__ __launch_bounds__(256) void res_rmsnorm_fwd_kernel(ResRmsFwdArgs a) {
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   RowVec<NV> wv;
@@ -922,6 +949,11 @@ __global__ __launch_bounds__(256) void res_rmsnorm_fwd_kernel(ResRmsFwdArgs a) {
     if constexpr (HAS_Y) {
       RowVec<NV> y;
       row_load<NV, TY>(y, reinterpret_cast<const TY*>(a.y) + (size_t)m * a.C, a.C, lane);
+      if constexpr (GATED) {
+        const float gt = row_gate(a.gate, m, a.T);
+#pragma unroll
+        for (int i = 0; i < NV; ++i) y.v[i] = y.v[i] * gt;
+      }
 #pragma unroll
       for (int i = 0; i < NV; ++i) z.v[i] = z.v[i] + y.v[i];
     }
@@ -949,9 +981,14 @@ struct ResRmsBwdArgs {
   void* dz_lo;
   float* part_dw;
   int M, C;
+  const float* gate;   // GATED kernels: as in ResRmsFwdArgs
+  int T;
 };
 
-template <int NV, typename TY, typename TL, bool HAS_Y, bool ADD>
+// GATED: z = a + gate * y as in the forward.  dz (fp32) stays d(z), the gradient that goes on down the stream into a; the
+// type-TL copy dz_lo is gate * d(z) = d(y), what the branch's GEMMs read - with a gate the two are different tensors in
+// fp32 mode too.
+template <int NV, typename TY, typename TL, bool HAS_Y, bool ADD, bool GATED>
 __global__ __launch_bounds__(256) void res_rmsnorm_bwd_kernel(ResRmsBwdArgs a) {
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   RowVec<NV> wv, dw;
@@ -962,9 +999,15 @@ __global__ __launch_bounds__(256) void res_rmsnorm_bwd_kernel(ResRmsBwdArgs a) {
     RowVec<NV> z, g;
     row_load<NV, float>(z, a.a + (size_t)m * a.C, a.C, lane);
     row_load_f32_nt<NV>(g, a.g + (size_t)m * a.C, a.C, lane);
+    float gt = 1.0f;
+    if constexpr (GATED) gt = row_gate(a.gate, m, a.T);
     if constexpr (HAS_Y) {
       RowVec<NV> y;
       row_load<NV, TY>(y, reinterpret_cast<const TY*>(a.y) + (size_t)m * a.C, a.C, lane);
+      if constexpr (GATED) {
+#pragma unroll
+        for (int i = 0; i < NV; ++i) y.v[i] = y.v[i] * gt;
+      }
 #pragma unroll
       for (int i = 0; i < NV; ++i) z.v[i] = z.v[i] + y.v[i];
     }
@@ -992,6 +1035,10 @@ __global__ __launch_bounds__(256) void res_rmsnorm_bwd_kernel(ResRmsBwdArgs a) {
       for (int i = 0; i < NV; ++i) g.v[i] = g.v[i] + old.v[i];
     }
     row_store<NV, float>(g, dz, a.C, lane);
+    if constexpr (GATED) {
+#pragma unroll
+      for (int i = 0; i < NV; ++i) g.v[i] = g.v[i] * gt;
+    }
     if (a.dz_lo) row_store<NV, TL>(g, reinterpret_cast<TL*>(a.dz_lo) + (size_t)m * a.C, a.C, lane);
   }
   row_store<NV, float>(dw, a.part_dw + ((size_t)blockIdx.x * ROW_WAVES + wid) * a.C, a.C, lane);
@@ -1009,9 +1056,12 @@ struct ResSkipArgs {
   float* dh;       // bwd: d(h + y), fp32
   float* part_dskip;
   int M, C;
+  const float* gate;   // GATED kernels: as in ResRmsFwdArgs
+  int T;
 };
 
-template <int NV, typename TY, typename TL>
+// GATED: out = nrm((h + gate * y) * skip + x), the gate folded into y where it is loaded.
+template <int NV, typename TY, typename TL, bool GATED>
 __global__ __launch_bounds__(256) void res_skip_fwd_kernel(ResSkipArgs a) {
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const float sk = a.skip[0];
@@ -1020,6 +1070,11 @@ __global__ __launch_bounds__(256) void res_skip_fwd_kernel(ResSkipArgs a) {
     row_load<NV, float>(r, a.h + (size_t)m * a.C, a.C, lane);
     row_load<NV, TY>(y, reinterpret_cast<const TY*>(a.y) + (size_t)m * a.C, a.C, lane);
     row_load<NV, float>(x, a.x + (size_t)m * a.C, a.C, lane);
+    if constexpr (GATED) {
+      const float gt = row_gate(a.gate, m, a.T);
+#pragma unroll
+      for (int i = 0; i < NV; ++i) y.v[i] = y.v[i] * gt;
+    }
 #pragma unroll
     for (int i = 0; i < NV; ++i) r.v[i] = (r.v[i] + y.v[i]) * sk + x.v[i];
     const float rs = 1.0f / sqrtf(row_dot<NV>(r, r));
@@ -1031,8 +1086,9 @@ __global__ __launch_bounds__(256) void res_skip_fwd_kernel(ResSkipArgs a) {
 }
 
 // res_skip_bwd: dr = (g - o (o.g)) / |r|;  d(x) = dr,  d(h + y) = dr * skip,  part_dskip [4*nblk] = per-wave sums of
-// dr . (h + y).
-template <int NV, typename TY, typename TL>
+// dr . (h + y).  GATED: h + gate * y throughout; dh (fp32) stays d(h + gate * y), the gradient that goes on into h, and its
+// type-TL copy is gate * dh = d(y), what the branch's GEMMs read (see res_rmsnorm_bwd_kernel).
+template <int NV, typename TY, typename TL, bool GATED>
 __global__ __launch_bounds__(256) void res_skip_bwd_kernel(ResSkipArgs a) {
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const float sk = a.skip[0];
@@ -1043,6 +1099,12 @@ __global__ __launch_bounds__(256) void res_skip_bwd_kernel(ResSkipArgs a) {
     row_load<NV, TY>(y, reinterpret_cast<const TY*>(a.y) + (size_t)m * a.C, a.C, lane);
     row_load<NV, float>(r, a.x + (size_t)m * a.C, a.C, lane);
     row_load_f32_nt<NV>(g, a.dout + (size_t)m * a.C, a.C, lane);
+    float gt = 1.0f;
+    if constexpr (GATED) {
+      gt = row_gate(a.gate, m, a.T);
+#pragma unroll
+      for (int i = 0; i < NV; ++i) y.v[i] = y.v[i] * gt;
+    }
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
       s.v[i] = s.v[i] + y.v[i];
@@ -1059,6 +1121,10 @@ __global__ __launch_bounds__(256) void res_skip_bwd_kernel(ResSkipArgs a) {
 #pragma unroll
     for (int i = 0; i < NV; ++i) g.v[i] = g.v[i] * sk;
     row_store<NV, float>(g, a.dh + (size_t)m * a.C, a.C, lane);
+    if constexpr (GATED) {
+#pragma unroll
+      for (int i = 0; i < NV; ++i) g.v[i] = g.v[i] * gt;
+    }
     if (a.out_lo) row_store<NV, TL>(g, reinterpret_cast<TL*>(a.out_lo) + (size_t)m * a.C, a.C, lane);
   }
   if (lane == 0) a.part_dskip[(size_t)blockIdx.x * ROW_WAVES + wid] = acc;
@@ -1066,7 +1132,7 @@ __global__ __launch_bounds__(256) void res_skip_bwd_kernel(ResSkipArgs a) {
 
 int row_grid(int M) {
   const int blocks = cdiv(M, ROW_WAVES);
-  return blocks > 2048 ? 2048 : blocks;
+  return blocks > NVIT_ROW_GRID_MAX ? NVIT_ROW_GRID_MAX : blocks;
 }
 
 }  // namespace
@@ -1097,11 +1163,28 @@ static auto lerp_bwd_select(int C, int y_dt, int dt, bool has_add, bool has_skip
     return with_bool(has_add, [&](auto add) {
       return with_bool(has_skip, [&](auto skip) {
         return with_bool(accum, [&](auto acc) {
-          return &lerp_bwd_kernel<nv, tag_t<decltype(ty)>, tag_t<decltype(tl)>, add, skip, acc>;
+          return &lerp_bwd_kernel<nv, tag_t<decltype(ty)>, tag_t<decltype(tl)>, add, skip, acc, false>;
         });
       });
     });
   });
+}
+
+// The gated instantiations are the two the block chain of ViT.forward launches: the MLP half (norm_skip fused, dh written)
+// and the attention half (no skip, dh accumulated), each with and without the bf16 addend.
+static auto lerp_bwd_gated_select(int C, int y_dt, int dt, bool has_add, bool mlp_half) -> void (*)(LerpBwdArgs) {
+  return with_row_types(C, y_dt, dt, [&](auto nv, auto ty, auto tl) {
+    return with_bool(has_add, [&](auto add) {
+      using TY = tag_t<decltype(ty)>;
+      using TL = tag_t<decltype(tl)>;
+      if (mlp_half) return &lerp_bwd_kernel<nv, TY, TL, add, true, false, true>;
+      return &lerp_bwd_kernel<nv, TY, TL, add, false, true, true>;
+    });
+  });
+}
+
+static bool gate_args_ok(const float* gate, int rows_per_sample, int M) {
+  return gate && rows_per_sample > 0 && M % rows_per_sample == 0;
 }
 
 extern "C" int nvit_lerp_fwd(int dt, const float* h, const void* y, int y_dt, const float* alpha, float c_a,
@@ -1109,15 +1192,32 @@ extern "C" int nvit_lerp_fwd(int dt, const float* h, const void* y, int y_dt, co
                              void* stream) {
   NVIT_REQUIRE(C % 4 == 0 && C <= NVIT_MAX_EMBD && M > 0, "lerp_fwd: C=%d must be a multiple of 4 and <= %d", C, NVIT_MAX_EMBD);
   NVIT_REQUIRE(!skip_x || skip, "lerp_fwd: skip_x without skip");
-  LerpFwdArgs a{h, y, alpha, c_a, skip_x, skip, out, out_lo, M, C};
+  LerpFwdArgs a{h, y, alpha, c_a, skip_x, skip, out, out_lo, M, C, nullptr, 1};
   hipStream_t s = (hipStream_t)stream;
   const int grid = row_grid(M);
   ProfScope ps(NVIT_KID_ROWOPS, 0.0, (double)M * C * (skip_x ? 16.0 : 12.0), s);
   const auto kernel = with_row_types(C, y_dt, dt, [](auto nv, auto ty, auto tl) {
-    return &lerp_fwd_kernel<nv, tag_t<decltype(ty)>, tag_t<decltype(tl)>>;
+    return &lerp_fwd_kernel<nv, tag_t<decltype(ty)>, tag_t<decltype(tl)>, false>;
   });
   launch(kernel, dim3(grid), dim3(256), 0, s, a);
   NVIT_CHECK_LAUNCH("lerp_fwd");
+  return NVIT_OK;
+}
+
+extern "C" int nvit_lerp_fwd_gated(int dt, const float* h, const void* y, int y_dt, const float* alpha, float c_a,
+                                   const float* skip_x, const float* skip, const float* gate, int rows_per_sample,
+                                   float* out, void* out_lo, int M, int C, void* stream) {
+  NVIT_REQUIRE(C % 4 == 0 && C <= NVIT_MAX_EMBD && M > 0, "lerp_fwd_gated: C=%d must be a multiple of 4 and <= %d", C, NVIT_MAX_EMBD);
+  NVIT_REQUIRE(!skip_x || skip, "lerp_fwd_gated: skip_x without skip");
+  NVIT_REQUIRE(gate_args_ok(gate, rows_per_sample, M), "lerp_fwd_gated: gate missing, or M=%d is no multiple of rows_per_sample=%d", M, rows_per_sample);
+  LerpFwdArgs a{h, y, alpha, c_a, skip_x, skip, out, out_lo, M, C, gate, rows_per_sample};
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope ps(NVIT_KID_ROWOPS, 0.0, (double)M * C * (skip_x ? 16.0 : 12.0) + 4.0 * M, s);
+  const auto kernel = with_row_types(C, y_dt, dt, [](auto nv, auto ty, auto tl) {
+    return &lerp_fwd_kernel<nv, tag_t<decltype(ty)>, tag_t<decltype(tl)>, true>;
+  });
+  launch(kernel, dim3(row_grid(M)), dim3(256), 0, s, a);
+  NVIT_CHECK_LAUNCH("lerp_fwd_gated");
   return NVIT_OK;
 }
 
@@ -1137,6 +1237,12 @@ extern "C" int nvit_lerp_bwd_blocks(int dt, int y_dt, int C, int has_add, int ha
   return n > NVIT_MAX_PART_BLOCKS ? NVIT_MAX_PART_BLOCKS : n;
 }
 
+extern "C" int nvit_lerp_bwd_gated_blocks(int dt, int y_dt, int C, int has_add, int has_skip, int accum) {
+  if (C % 4 != 0 || C <= 0 || C > NVIT_MAX_EMBD || (has_skip != 0) == (accum != 0)) return 0;
+  const int n = resident_blocks(lerp_bwd_gated_select(C, y_dt, dt, has_add, has_skip != 0));
+  return n > NVIT_MAX_PART_BLOCKS ? NVIT_MAX_PART_BLOCKS : n;
+}
+
 extern "C" int nvit_lerp_bwd(int dt, const float* dout, const void* dout_add, const float* h, const void* y, int y_dt, const float* alpha,
                              float c_a, const float* skip_x, const float* skip, float* dh, int accum_dh, float* dy,
                              void* dy_lo, float* dskip_x, float* part_dlam, float* part_dskip, int nblk, int M,
@@ -1144,7 +1250,7 @@ extern "C" int nvit_lerp_bwd(int dt, const float* dout, const void* dout_add, co
   NVIT_REQUIRE(C % 4 == 0 && C <= NVIT_MAX_EMBD && M > 0, "lerp_bwd: C=%d must be a multiple of 4 and <= %d", C, NVIT_MAX_EMBD);
   NVIT_REQUIRE(nblk > 0 && nblk <= NVIT_MAX_PART_BLOCKS, "lerp_bwd: nblk out of range");
   NVIT_REQUIRE(!skip_x || (skip && dskip_x && part_dskip), "lerp_bwd: skip buffers missing");
-  LerpBwdArgs a{dout, (const bf16*)dout_add, h, y, alpha, c_a, skip_x, skip, dh, accum_dh, dy, dy_lo, dskip_x, part_dlam, part_dskip, M, C};
+  LerpBwdArgs a{dout, (const bf16*)dout_add, h, y, alpha, c_a, skip_x, skip, dh, accum_dh, dy, dy_lo, dskip_x, part_dlam, part_dskip, M, C, nullptr, 1};
   hipStream_t s = (hipStream_t)stream;
   // algorithmic bytes: dout, h read, y read (2 or 4 B), dh written, dy_lo written (+ skip_x read, dskip_x written; + dout_add)
   const double lb_bytes = (double)M * C * (4.0 + 4.0 + (y_dt == NVIT_F32 ? 4.0 : 2.0) + 4.0 + (dy ? 4.0 : 0.0) + (dy_lo ? (dt == NVIT_F32 ? 4.0 : 2.0) : 0.0) +
@@ -1152,6 +1258,27 @@ extern "C" int nvit_lerp_bwd(int dt, const float* dout, const void* dout_add, co
   ProfScope ps(NVIT_KID_ROWOPS, 0.0, lb_bytes, s);
   launch(lerp_bwd_select(C, y_dt, dt, dout_add != nullptr, skip_x != nullptr, accum_dh != 0), dim3(nblk), dim3(256), 0, s, a);
   NVIT_CHECK_LAUNCH("lerp_bwd");
+  return NVIT_OK;
+}
+
+extern "C" int nvit_lerp_bwd_gated(int dt, const float* dout, const void* dout_add, const float* h, const void* y, int y_dt,
+                                   const float* alpha, float c_a, const float* skip_x, const float* skip,
+                                   const float* gate, int rows_per_sample, float* dh, int accum_dh, float* dy, void* dy_lo,
+                                   float* dskip_x, float* part_dlam, float* part_dskip, int nblk, int M, int C,
+                                   void* stream) {
+  NVIT_REQUIRE(C % 4 == 0 && C <= NVIT_MAX_EMBD && M > 0, "lerp_bwd_gated: C=%d must be a multiple of 4 and <= %d", C, NVIT_MAX_EMBD);
+  NVIT_REQUIRE(nblk > 0 && nblk <= NVIT_MAX_PART_BLOCKS, "lerp_bwd_gated: nblk out of range");
+  NVIT_REQUIRE(!skip_x || (skip && dskip_x && part_dskip), "lerp_bwd_gated: skip buffers missing");
+  NVIT_REQUIRE(gate_args_ok(gate, rows_per_sample, M), "lerp_bwd_gated: gate missing, or M=%d is no multiple of rows_per_sample=%d", M, rows_per_sample);
+  NVIT_REQUIRE((skip_x != nullptr) != (accum_dh != 0),
+               "lerp_bwd_gated: built for the two calls of the block chain, skip_x without accum_dh or accum_dh without skip_x");
+  LerpBwdArgs a{dout, (const bf16*)dout_add, h, y, alpha, c_a, skip_x, skip, dh, accum_dh, dy, dy_lo, dskip_x, part_dlam, part_dskip, M, C, gate, rows_per_sample};
+  hipStream_t s = (hipStream_t)stream;
+  const double lb_bytes = (double)M * C * (4.0 + 4.0 + (y_dt == NVIT_F32 ? 4.0 : 2.0) + 4.0 + (dy ? 4.0 : 0.0) + (dy_lo ? (dt == NVIT_F32 ? 4.0 : 2.0) : 0.0) +
+                                           (skip_x ? 8.0 : 0.0) + (accum_dh ? 4.0 : 0.0) + (dout_add ? 2.0 : 0.0)) + 4.0 * M;
+  ProfScope ps(NVIT_KID_ROWOPS, 0.0, lb_bytes, s);
+  launch(lerp_bwd_gated_select(C, y_dt, dt, dout_add != nullptr, skip_x != nullptr), dim3(nblk), dim3(256), 0, s, a);
+  NVIT_CHECK_LAUNCH("lerp_bwd_gated");
   return NVIT_OK;
 }
 
@@ -1202,7 +1329,7 @@ extern "C" int nvit_res_rmsnorm_fwd(int dt, const float* a, const void* y, int y
   NVIT_REQUIRE(C % 4 == 0 && C <= NVIT_MAX_EMBD && M > 0, "res_rmsnorm_fwd: C=%d must be a multiple of 4 and <= %d", C, NVIT_MAX_EMBD);
   NVIT_REQUIRE(dt == NVIT_F32 || dt == NVIT_BF16, "res_rmsnorm_fwd: bad dt %d", dt);
   NVIT_REQUIRE(!y || y_dt == NVIT_F32 || y_dt == NVIT_BF16, "res_rmsnorm_fwd: bad y_dt %d", y_dt);
-  ResRmsFwdArgs ar{a, y, w, eps, out, out_lo, rstd, M, C};
+  ResRmsFwdArgs ar{a, y, w, eps, out, out_lo, rstd, M, C, nullptr, 1};
   hipStream_t s = (hipStream_t)stream;
   const int grid = row_grid(M);
   ProfScope ps(NVIT_KID_ROWOPS, 0.0, (double)M * C * (8.0 + (y ? (y_dt == NVIT_F32 ? 4.0 : 2.0) : 0.0) +
@@ -1210,8 +1337,8 @@ extern "C" int nvit_res_rmsnorm_fwd(int dt, const float* a, const void* y, int y
   const auto kernel = with_row_vecs<8>(C, [&](auto nv) {
     return with_elem(dt, [&](auto tl) {
       using TL = tag_t<decltype(tl)>;
-      if (!y) return &res_rmsnorm_fwd_kernel<nv, float, TL, false>;   // without y, TY is float: no <bf16, false> is built
-      return with_elem(y_dt, [&](auto ty) { return &res_rmsnorm_fwd_kernel<nv, tag_t<decltype(ty)>, TL, true>; });
+      if (!y) return &res_rmsnorm_fwd_kernel<nv, float, TL, false, false>;   // without y, TY is float: no <bf16, false> is built
+      return with_elem(y_dt, [&](auto ty) { return &res_rmsnorm_fwd_kernel<nv, tag_t<decltype(ty)>, TL, true, false>; });
     });
   });
   launch(kernel, dim3(grid), dim3(256), 0, s, ar);
@@ -1226,7 +1353,7 @@ extern "C" int nvit_res_rmsnorm_bwd(int dt, const float* g, const void* g_add, c
   NVIT_REQUIRE(nblk > 0 && nblk <= NVIT_MAX_PART_BLOCKS, "res_rmsnorm_bwd: nblk out of range");
   NVIT_REQUIRE(dt == NVIT_F32 || dt == NVIT_BF16, "res_rmsnorm_bwd: bad dt %d", dt);
   NVIT_REQUIRE(!y || y_dt == NVIT_F32 || y_dt == NVIT_BF16, "res_rmsnorm_bwd: bad y_dt %d", y_dt);
-  ResRmsBwdArgs ar{g, g_add, a, y, w, rstd, dz, accum, dz_lo, part_dw, M, C};
+  ResRmsBwdArgs ar{g, g_add, a, y, w, rstd, dz, accum, dz_lo, part_dw, M, C, nullptr, 1};
   hipStream_t s = (hipStream_t)stream;
   const double tl = dt == NVIT_F32 ? 4.0 : 2.0;
   ProfScope ps(NVIT_KID_ROWOPS, 0.0, (double)M * C * (12.0 + (y ? (y_dt == NVIT_F32 ? 4.0 : 2.0) : 0.0) +
@@ -1235,8 +1362,8 @@ extern "C" int nvit_res_rmsnorm_bwd(int dt, const float* g, const void* g_add, c
     return with_elem(dt, [&](auto tlo) {
       return with_bool(g_add != nullptr, [&](auto add) {
         using TL = tag_t<decltype(tlo)>;
-        if (!y) return &res_rmsnorm_bwd_kernel<nv, float, TL, false, add>;   // as in the forward: TY is float without y
-        return with_elem(y_dt, [&](auto ty) { return &res_rmsnorm_bwd_kernel<nv, tag_t<decltype(ty)>, TL, true, add>; });
+        if (!y) return &res_rmsnorm_bwd_kernel<nv, float, TL, false, add, false>;   // as in the forward: TY is float without y
+        return with_elem(y_dt, [&](auto ty) { return &res_rmsnorm_bwd_kernel<nv, tag_t<decltype(ty)>, TL, true, add, false>; });
       });
     });
   });
@@ -1250,13 +1377,13 @@ extern "C" int nvit_res_skip_fwd(int dt, const float* h, const void* y, int y_dt
   NVIT_REQUIRE(C % 4 == 0 && C <= NVIT_MAX_EMBD && M > 0, "res_skip_fwd: C=%d must be a multiple of 4 and <= %d", C, NVIT_MAX_EMBD);
   NVIT_REQUIRE(dt == NVIT_F32 || dt == NVIT_BF16, "res_skip_fwd: bad dt %d", dt);
   NVIT_REQUIRE(y && (y_dt == NVIT_F32 || y_dt == NVIT_BF16), "res_skip_fwd: y missing or bad y_dt %d", y_dt);
-  ResSkipArgs ar{nullptr, h, y, skip, x, out, out_lo, nullptr, nullptr, M, C};
+  ResSkipArgs ar{nullptr, h, y, skip, x, out, out_lo, nullptr, nullptr, M, C, nullptr, 1};
   hipStream_t s = (hipStream_t)stream;
   const int grid = row_grid(M);
   ProfScope ps(NVIT_KID_ROWOPS, 0.0, (double)M * C * (12.0 + (y_dt == NVIT_F32 ? 4.0 : 2.0) +
                                                        (out_lo ? (dt == NVIT_F32 ? 4.0 : 2.0) : 0.0)), s);
   const auto kernel = with_row_types(C, y_dt, dt, [](auto nv, auto ty, auto tl) {
-    return &res_skip_fwd_kernel<nv, tag_t<decltype(ty)>, tag_t<decltype(tl)>>;
+    return &res_skip_fwd_kernel<nv, tag_t<decltype(ty)>, tag_t<decltype(tl)>, false>;
   });
   launch(kernel, dim3(grid), dim3(256), 0, s, ar);
   NVIT_CHECK_LAUNCH("res_skip_fwd");
@@ -1270,15 +1397,98 @@ extern "C" int nvit_res_skip_bwd(int dt, const float* dout, const float* h, cons
   NVIT_REQUIRE(nblk > 0 && nblk <= NVIT_MAX_PART_BLOCKS, "res_skip_bwd: nblk out of range");
   NVIT_REQUIRE(dt == NVIT_F32 || dt == NVIT_BF16, "res_skip_bwd: bad dt %d", dt);
   NVIT_REQUIRE(y && (y_dt == NVIT_F32 || y_dt == NVIT_BF16), "res_skip_bwd: y missing or bad y_dt %d", y_dt);
-  ResSkipArgs ar{dout, h, y, skip, x, dx, dh_lo, dh, part_dskip, M, C};
+  ResSkipArgs ar{dout, h, y, skip, x, dx, dh_lo, dh, part_dskip, M, C, nullptr, 1};
   hipStream_t s = (hipStream_t)stream;
   ProfScope ps(NVIT_KID_ROWOPS, 0.0, (double)M * C * (20.0 + (y_dt == NVIT_F32 ? 4.0 : 2.0) +
                                                        (dh_lo ? (dt == NVIT_F32 ? 4.0 : 2.0) : 0.0)), s);
   const auto kernel = with_row_types(C, y_dt, dt, [](auto nv, auto ty, auto tl) {
-    return &res_skip_bwd_kernel<nv, tag_t<decltype(ty)>, tag_t<decltype(tl)>>;
+    return &res_skip_bwd_kernel<nv, tag_t<decltype(ty)>, tag_t<decltype(tl)>, false>;
   });
   launch(kernel, dim3(nblk), dim3(256), 0, s, ar);
   NVIT_CHECK_LAUNCH("res_skip_bwd");
+  return NVIT_OK;
+}
+
+// ---- gated residual kernels of the plain-ViT block chain (stochastic depth).  Built for the calls _StdBlockFn makes: a
+// branch output y is always there, the rms_mlp backward always has its data-gradient addend. ----
+extern "C" int nvit_res_rmsnorm_fwd_gated(int dt, const float* a, const void* y, int y_dt, const float* w, float eps,
+                                          const float* gate, int rows_per_sample, float* out, void* out_lo, float* rstd,
+                                          int M, int C, void* stream) {
+  NVIT_REQUIRE(C % 4 == 0 && C <= NVIT_MAX_EMBD && M > 0, "res_rmsnorm_fwd_gated: C=%d must be a multiple of 4 and <= %d", C, NVIT_MAX_EMBD);
+  NVIT_REQUIRE(dt == NVIT_F32 || dt == NVIT_BF16, "res_rmsnorm_fwd_gated: bad dt %d", dt);
+  NVIT_REQUIRE(y && (y_dt == NVIT_F32 || y_dt == NVIT_BF16), "res_rmsnorm_fwd_gated: y missing or bad y_dt %d", y_dt);
+  NVIT_REQUIRE(gate_args_ok(gate, rows_per_sample, M), "res_rmsnorm_fwd_gated: gate missing, or M=%d is no multiple of rows_per_sample=%d", M, rows_per_sample);
+  ResRmsFwdArgs ar{a, y, w, eps, out, out_lo, rstd, M, C, gate, rows_per_sample};
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope ps(NVIT_KID_ROWOPS, 0.0, (double)M * C * (8.0 + (y_dt == NVIT_F32 ? 4.0 : 2.0) +
+                                                       (out_lo ? (dt == NVIT_F32 ? 4.0 : 2.0) : 0.0)) + 4.0 * M, s);
+  const auto kernel = with_row_types(C, y_dt, dt, [](auto nv, auto ty, auto tl) {
+    return &res_rmsnorm_fwd_kernel<nv, tag_t<decltype(ty)>, tag_t<decltype(tl)>, true, true>;
+  });
+  launch(kernel, dim3(row_grid(M)), dim3(256), 0, s, ar);
+  NVIT_CHECK_LAUNCH("res_rmsnorm_fwd_gated");
+  return NVIT_OK;
+}
+
+extern "C" int nvit_res_rmsnorm_bwd_gated(int dt, const float* g, const void* g_add, const float* a, const void* y, int y_dt,
+                                          const float* w, const float* rstd, const float* gate, int rows_per_sample,
+                                          float* dz, int accum, void* dz_lo, float* part_dw, int nblk, int M, int C,
+                                          void* stream) {
+  NVIT_REQUIRE(C % 4 == 0 && C <= NVIT_MAX_EMBD && M > 0, "res_rmsnorm_bwd_gated: C=%d must be a multiple of 4 and <= %d", C, NVIT_MAX_EMBD);
+  NVIT_REQUIRE(nblk > 0 && nblk <= NVIT_MAX_PART_BLOCKS, "res_rmsnorm_bwd_gated: nblk out of range");
+  NVIT_REQUIRE(dt == NVIT_F32 || dt == NVIT_BF16, "res_rmsnorm_bwd_gated: bad dt %d", dt);
+  NVIT_REQUIRE(y && (y_dt == NVIT_F32 || y_dt == NVIT_BF16), "res_rmsnorm_bwd_gated: y missing or bad y_dt %d", y_dt);
+  NVIT_REQUIRE(g_add, "res_rmsnorm_bwd_gated: built with the addend g_add only");
+  NVIT_REQUIRE(gate_args_ok(gate, rows_per_sample, M), "res_rmsnorm_bwd_gated: gate missing, or M=%d is no multiple of rows_per_sample=%d", M, rows_per_sample);
+  ResRmsBwdArgs ar{g, g_add, a, y, w, rstd, dz, accum, dz_lo, part_dw, M, C, gate, rows_per_sample};
+  hipStream_t s = (hipStream_t)stream;
+  const double tl = dt == NVIT_F32 ? 4.0 : 2.0;
+  ProfScope ps(NVIT_KID_ROWOPS, 0.0, (double)M * C * (12.0 + (y_dt == NVIT_F32 ? 4.0 : 2.0) + tl + (accum ? 4.0 : 0.0) +
+                                                       (dz_lo ? tl : 0.0)) + 4.0 * M, s);
+  const auto kernel = with_row_types(C, y_dt, dt, [](auto nv, auto ty, auto tlo) {
+    return &res_rmsnorm_bwd_kernel<nv, tag_t<decltype(ty)>, tag_t<decltype(tlo)>, true, true, true>;
+  });
+  launch(kernel, dim3(nblk), dim3(256), 0, s, ar);
+  NVIT_CHECK_LAUNCH("res_rmsnorm_bwd_gated");
+  return NVIT_OK;
+}
+
+extern "C" int nvit_res_skip_fwd_gated(int dt, const float* h, const void* y, int y_dt, const float* skip, const float* x,
+                                       const float* gate, int rows_per_sample, float* out, void* out_lo, int M, int C,
+                                       void* stream) {
+  NVIT_REQUIRE(C % 4 == 0 && C <= NVIT_MAX_EMBD && M > 0, "res_skip_fwd_gated: C=%d must be a multiple of 4 and <= %d", C, NVIT_MAX_EMBD);
+  NVIT_REQUIRE(dt == NVIT_F32 || dt == NVIT_BF16, "res_skip_fwd_gated: bad dt %d", dt);
+  NVIT_REQUIRE(y && (y_dt == NVIT_F32 || y_dt == NVIT_BF16), "res_skip_fwd_gated: y missing or bad y_dt %d", y_dt);
+  NVIT_REQUIRE(gate_args_ok(gate, rows_per_sample, M), "res_skip_fwd_gated: gate missing, or M=%d is no multiple of rows_per_sample=%d", M, rows_per_sample);
+  ResSkipArgs ar{nullptr, h, y, skip, x, out, out_lo, nullptr, nullptr, M, C, gate, rows_per_sample};
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope ps(NVIT_KID_ROWOPS, 0.0, (double)M * C * (12.0 + (y_dt == NVIT_F32 ? 4.0 : 2.0) +
+                                                       (out_lo ? (dt == NVIT_F32 ? 4.0 : 2.0) : 0.0)) + 4.0 * M, s);
+  const auto kernel = with_row_types(C, y_dt, dt, [](auto nv, auto ty, auto tl) {
+    return &res_skip_fwd_kernel<nv, tag_t<decltype(ty)>, tag_t<decltype(tl)>, true>;
+  });
+  launch(kernel, dim3(row_grid(M)), dim3(256), 0, s, ar);
+  NVIT_CHECK_LAUNCH("res_skip_fwd_gated");
+  return NVIT_OK;
+}
+
+extern "C" int nvit_res_skip_bwd_gated(int dt, const float* dout, const float* h, const void* y, int y_dt, const float* skip,
+                                       const float* x, const float* gate, int rows_per_sample, float* dh, void* dh_lo,
+                                       float* dx, float* part_dskip, int nblk, int M, int C, void* stream) {
+  NVIT_REQUIRE(C % 4 == 0 && C <= NVIT_MAX_EMBD && M > 0, "res_skip_bwd_gated: C=%d must be a multiple of 4 and <= %d", C, NVIT_MAX_EMBD);
+  NVIT_REQUIRE(nblk > 0 && nblk <= NVIT_MAX_PART_BLOCKS, "res_skip_bwd_gated: nblk out of range");
+  NVIT_REQUIRE(dt == NVIT_F32 || dt == NVIT_BF16, "res_skip_bwd_gated: bad dt %d", dt);
+  NVIT_REQUIRE(y && (y_dt == NVIT_F32 || y_dt == NVIT_BF16), "res_skip_bwd_gated: y missing or bad y_dt %d", y_dt);
+  NVIT_REQUIRE(gate_args_ok(gate, rows_per_sample, M), "res_skip_bwd_gated: gate missing, or M=%d is no multiple of rows_per_sample=%d", M, rows_per_sample);
+  ResSkipArgs ar{dout, h, y, skip, x, dx, dh_lo, dh, part_dskip, M, C, gate, rows_per_sample};
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope ps(NVIT_KID_ROWOPS, 0.0, (double)M * C * (20.0 + (y_dt == NVIT_F32 ? 4.0 : 2.0) +
+                                                       (dh_lo ? (dt == NVIT_F32 ? 4.0 : 2.0) : 0.0)) + 4.0 * M, s);
+  const auto kernel = with_row_types(C, y_dt, dt, [](auto nv, auto ty, auto tl) {
+    return &res_skip_bwd_kernel<nv, tag_t<decltype(ty)>, tag_t<decltype(tl)>, true>;
+  });
+  launch(kernel, dim3(nblk), dim3(256), 0, s, ar);
+  NVIT_CHECK_LAUNCH("res_skip_bwd_gated");
   return NVIT_OK;
 }
 

@@ -438,7 +438,9 @@ class _BlockFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, x_lo, rt, idx, with_skip, impl, skip_param, attn_alpha, mlp_alpha, sqk, suv, wq, wk, wv, wo,
-                wfc, wp, bq, bk_, bv, bo, bfc, bp, chained=False, lean=False):
+                wfc, wp, bq, bk_, bv, bo, bfc, bp, chained=False, lean=False, gates=None):
+        # gates: None, or (attention, MLP) fp32 [B] each, this block's two rows of the DropPath table: the gated LERP
+        # kernels then run in both directions (a dropped branch is still computed and discarded, as in timm)
         cfg = rt.model.config
         dims = _dims(rt, x.shape[0])
         B, T, C, H, d, M = dims
@@ -450,22 +452,25 @@ class _BlockFn(torch.autograd.Function):
         o, lse, att, att_saved = _attn_fwd(rt, impl, ((x_lo, pre + "qkv", 3),), sqk, c_q, math.sqrt(d), dims,
                                            lean)
         y = ops.gemm_nt(o, sh[pre + "o.W"], M, C, C, out_dtype=rt.y_dtype(), bias=sh.get(pre + "o.b"))
-        h1, h1_lo = ops.lerp_fwd(dt, x, y, attn_alpha, c_a, want_lo=(dt != F32))
+        g_att, g_mlp = gates if gates is not None else (None, None)
+        h1, h1_lo = ops.lerp_fwd(dt, x, y, attn_alpha, c_a, want_lo=(dt != F32), gate=g_att)
         if dt == F32:
             h1_lo = h1
         # c_fc GEMM with the suv scale + SwiGLU gate (writes raw uv for backward and x_mlp)
         uv, xm = _swiglu_fwd(rt, h1_lo, pre + "fc", M, 4 * C, C, suv, sh[pre + "suv_i"], math.sqrt(C), lean)
         y2 = ops.gemm_nt(xm, sh[pre + "p.W"], M, C, 4 * C, out_dtype=rt.y_dtype(), bias=sh.get(pre + "p.b"))
         if with_skip:
-            xn, xn_lo = ops.lerp_fwd(dt, h1, y2, mlp_alpha, c_a, skip_x=x, skip=skip_param, want_lo=(dt != F32))
+            xn, xn_lo = ops.lerp_fwd(dt, h1, y2, mlp_alpha, c_a, skip_x=x, skip=skip_param, want_lo=(dt != F32),
+                                     gate=g_mlp)
         else:
-            xn, xn_lo = ops.lerp_fwd(dt, h1, y2, mlp_alpha, c_a, want_lo=(dt != F32))
+            xn, xn_lo = ops.lerp_fwd(dt, h1, y2, mlp_alpha, c_a, want_lo=(dt != F32), gate=g_mlp)
         if dt == F32:
             xn_lo = xn.new_empty(0)  # placeholder: callers alias x itself in fp32 mode (see _lo())
         if lean:   # no backward follows (see _lean()): nothing to save
             return xn, xn_lo
         ctx.rt, ctx.idx, ctx.with_skip, ctx.has_b, ctx.attn = rt, idx, with_skip, has_b, att
         ctx.chained = bool(chained)   # called from ViT.forward's block chain: the consumer of dx is our own backward node
+        ctx.gates = (g_att, g_mlp)    # (rows of the step's gate table: B floats each, no gradient)
         ctx.dims = dims
         ctx.par = (skip_param, attn_alpha, mlp_alpha, sqk, suv, wq, wk, wv, wo, wfc, wp)   # gradient destinations
         ctx.save_for_backward(x, x_lo, o, lse, y, h1, h1_lo, uv, xm, y2, skip_param, attn_alpha, mlp_alpha, sqk, suv,
@@ -487,18 +492,21 @@ class _BlockFn(torch.autograd.Function):
         c_q, c_a = 1.0 / cfg.base_scale, 0.05 / cfg.base_scale
         pre = f"h{idx}."
         if dxn is None:
-            return (None,) * 25
+            return (None,) * 26
         dxn = dxn.contiguous()
+        g_att, g_mlp = ctx.gates
         lo_dgrad = dt != F32
         red = ops.ReduceBatch()   # the block's six parameter-gradient reductions go out as one launch at the end
         dxn, carry_in = _take_carry(rt, idx, ctx.chained, dxn)   # q/k/v data gradient of the block after this one (bf16), or None
         # ---- MLP half + norm_skip
         if ctx.with_skip:
             dh1, _, dy2_lo, dx, part_lam, part_skip = ops.lerp_bwd(dt, dxn, h1, y2, mlp_alpha, c_a, x, skip_param,
-                                                                   None, False, False, True, dout_add=carry_in)
+                                                                   None, False, False, True, dout_add=carry_in,
+                                                                   gate=g_mlp)
             dskip = rt.grad_buf((p_skip,), p_skip.shape)
             red.add(part_skip, dskip, False)
         else:
+            # (never gated: ViT.forward's chain, the only gated caller, always runs with_skip)
             dh1, _, dy2_lo, _, part_lam, _ = ops.lerp_bwd(dt, dxn, h1, y2, mlp_alpha, c_a, None, None, None, False,
                                                           False, True, dout_add=carry_in)
             dx, dskip = None, None
@@ -518,7 +526,7 @@ class _BlockFn(torch.autograd.Function):
                                                         False, True, dout_add=dh1_add)
         else:
             dx, _, dy_lo, _, part_lam, _ = ops.lerp_bwd(dt, dh1, x, y, attn_alpha, c_a, None, None, dx, True, False,
-                                                        True, dout_add=dh1_add)
+                                                        True, dout_add=dh1_add, gate=g_att)
         d_attn_alpha = _param_grad_alpha(rt, part_lam, p_aalpha, c_a, red)
         do = ops.gemm_nt(dy_lo, sh[pre + "o.Wt"], M, C, C, out_dtype=td)
         g_wo, g_bo = _wgrad(rt, dy_lo, o, (p_wo,), M, C, C, ctx.has_b)
@@ -540,7 +548,7 @@ class _BlockFn(torch.autograd.Function):
         else:
             gbq = gbk = gbv = None
         return (dx, None, None, None, None, None, dskip, d_attn_alpha, d_mlp_alpha, d_sqk, d_suv, gq, gk, gv, g_wo,
-                g_wfc, g_wp, gbq, gbk, gbv, g_bo, g_bfc, g_bp, None, None)
+                g_wfc, g_wp, gbq, gbk, gbv, g_bo, g_bfc, g_bp, None, None, None)
 
 
 class _CrossFn(torch.autograd.Function):
@@ -622,11 +630,15 @@ class _StdBlockFn(torch.autograd.Function):
     built) and, with_skip, the norm_skip after it (model.py:84-87,450-452):
         a = rms_att(x);  h1 = a + attn(a) W_o^T;  bm = rms_mlp(h1);  h2 = bm + swiglu(bm W_fc^T) W_p^T;
         out = nrm(h2 * skip + x)   (with_skip; else out = h2).
-    Attention is softmax(q k^T / sqrt(d)) v on the running-max kernels; the SwiGLU gate scale is 1 (no suv)."""
+    Attention is softmax(q k^T / sqrt(d)) v on the running-max kernels; the SwiGLU gate scale is 1 (no suv).
+    gates (stochastic depth, with_skip only): (g_att, g_mlp) fp32 [B], h1 = a + g_att * attn(..), h2 = bm + g_mlp * mlp(..)
+    per sample.  Backward: the gradient that goes on down the stream (d(h1) into a, d(h2) into bm) is that of the sum; the
+    copy the branch's GEMMs read is gate * it - the gated row kernels write both, so in fp32 mode, where the two are one
+    tensor without a gate, they are two."""
 
     @staticmethod
     def forward(ctx, x, rt, idx, with_skip, want_lo, impl, skip_param, w_att, w_mlp, wq, wk, wv, wo, wfc, wp, bq, bk_,
-                bv, bo, bfc, bp, lean=False):
+                bv, bo, bfc, bp, lean=False, gates=None):
         dims = _dims(rt, x.shape[0])
         B, T, C, H, d, M = dims
         dt = rt.dt
@@ -640,13 +652,14 @@ class _StdBlockFn(torch.autograd.Function):
         o, lse, att, att_saved = _attn_fwd(rt, impl, ((a_lo, pre + "qkv", 3),), None, 0.0, 1.0 / math.sqrt(d),
                                            dims, lean)
         y = ops.gemm_nt(o, sh[pre + "o.W"], M, C, C, out_dtype=rt.y_dtype(), bias=sh.get(pre + "o.b"))
-        bm, bm_lo, r_mlp = ops.res_rmsnorm_fwd(dt, a, y, w_mlp.detach(), RMS_EPS, want_lo=lo)
+        g_att, g_mlp = gates if gates is not None else (None, None)
+        bm, bm_lo, r_mlp = ops.res_rmsnorm_fwd(dt, a, y, w_mlp.detach(), RMS_EPS, want_lo=lo, gate=g_att)
         if not lo:
             bm_lo = bm
         uv, xm = _swiglu_fwd(rt, bm_lo, pre + "fc", M, 4 * C, C, None, None, 1.0, lean)
         if with_skip:
             y2 = ops.gemm_nt(xm, sh[pre + "p.W"], M, C, 4 * C, out_dtype=rt.y_dtype(), bias=sh.get(pre + "p.b"))
-            xn, xn_lo = ops.res_skip_fwd(dt, bm, y2, skip_param.detach(), x, want_lo=(lo and want_lo))
+            xn, xn_lo = ops.res_skip_fwd(dt, bm, y2, skip_param.detach(), x, want_lo=(lo and want_lo), gate=g_mlp)
         else:   # the block output itself: h2 = bm + y2 in the GEMM epilogue (row-add of bm)
             y2 = ops.gemm_nt(xm, sh[pre + "p.W"], M, C, 4 * C, out_dtype=torch.float32, bias=sh.get(pre + "p.b"),
                              rowadd=bm, rowadd_period=M)
@@ -657,6 +670,7 @@ class _StdBlockFn(torch.autograd.Function):
             return xn, xn_lo
         ctx.rt, ctx.idx, ctx.with_skip, ctx.has_b, ctx.attn = rt, idx, with_skip, has_b, att
         ctx.dims = dims
+        ctx.gates = (g_att, g_mlp)    # (rows of the step's gate table: B floats each, no gradient)
         ctx.par = (skip_param, w_att, w_mlp, wq, wk, wv, wo, wfc, wp)   # gradient destinations
         ctx.save_for_backward(x, a, a_lo, r_att, o, lse, y, bm, bm_lo, r_mlp, uv, xm, y2, skip_param, w_att, w_mlp,
                               *att_saved)
@@ -667,7 +681,8 @@ class _StdBlockFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dxn, _unused):
         if dxn is None:
-            return (None,) * 22
+            return (None,) * 23
+        g_att, g_mlp = ctx.gates
         (x, a, a_lo, r_att, o, lse, y, bm, bm_lo, r_mlp, uv, xm, y2, skip_param, w_att, w_mlp,
          *att_saved) = ctx.saved_tensors
         rt, idx = ctx.rt, ctx.idx
@@ -681,22 +696,25 @@ class _StdBlockFn(torch.autograd.Function):
         red = ops.ReduceBatch()
         # ---- norm_skip: d(h2) and the direct part of d(x)
         if ctx.with_skip:
-            dh2, dh2_lo, dx, part_skip = ops.res_skip_bwd(dt, dxn, bm, y2, skip_param, x, want_lo=lo)
+            # gated: dh2 = d(bm + g*y2) goes on into bm, its copy (made in fp32 mode too) is g * dh2 = d(y2)
+            dh2, dh2_lo, dx, part_skip = ops.res_skip_bwd(dt, dxn, bm, y2, skip_param, x,
+                                                          want_lo=lo or g_mlp is not None, gate=g_mlp)
             dskip = rt.grad_buf((p_skip,), p_skip.shape)
             red.add(part_skip, dskip, False)
         else:
             dh2, dh2_lo, dx, dskip = dxn, (ops.cast(dxn, dt) if lo else None), None, None
-        dy2_lo = dh2_lo if lo else dh2
+        dy2_lo = dh2_lo if dh2_lo is not None else dh2
         # ---- MLP branch
         duv, _ = _swiglu_bwd(rt, dy2_lo, pre + "p", uv, M, 4 * C, C, None, 1.0)
         g_wp, g_bp = _wgrad(rt, dy2_lo, xm, (p_wp,), M, C, 4 * C, ctx.has_b)
         dbm_add = ops.gemm_nt(duv, sh[pre + "fc.Wt"], M, C, 8 * C, out_dtype=td)   # added by the rms_mlp backward
         g_wfc, g_bfc = _wgrad(rt, duv, bm_lo, (p_wfc,), M, 8 * C, C, ctx.has_b, perm=1)
         # ---- rms_mlp: d(h1) = d(a + y)
-        dh1, dh1_lo, part_mlp = ops.res_rmsnorm_bwd(dt, dh2, a, y, w_mlp, r_mlp, g_add=dbm_add, want_lo=lo)
+        dh1, dh1_lo, part_mlp = ops.res_rmsnorm_bwd(dt, dh2, a, y, w_mlp, r_mlp, g_add=dbm_add,
+                                                    want_lo=lo or g_att is not None, gate=g_att)
         del dbm_add
         g_wmlp = _param_grad_scaled(rt, part_mlp, p_wmlp, 1.0, red)
-        dy_lo = dh1_lo if lo else dh1
+        dy_lo = dh1_lo if dh1_lo is not None else dh1
         # ---- attention branch
         do = ops.gemm_nt(dy_lo, sh[pre + "o.Wt"], M, C, C, out_dtype=td)
         g_wo, g_bo = _wgrad(rt, dy_lo, o, (p_wo,), M, C, C, ctx.has_b)
@@ -714,7 +732,7 @@ class _StdBlockFn(torch.autograd.Function):
         else:
             gbq = gbk = gbv = None
         return (dx, None, None, None, None, None, dskip, g_watt, g_wmlp, gq, gk, gv, g_wo, g_wfc, g_wp, gbq, gbk, gbv,
-                g_bo, g_bfc, g_bp, None)
+                g_bo, g_bfc, g_bp, None, None)
 
 
 class _StdCrossFn(torch.autograd.Function):
@@ -1010,15 +1028,22 @@ class Block(nn.Module):
                        self.mlp_c_proj.weight, b(self.query), b(self.key), b(self.value), b(self.att_c_proj),
                        b(self.c_fc), b(self.mlp_c_proj))
 
-    def _run(self, x: Tensor, x_lo: Tensor, with_skip: bool, chained: bool = False, want_lo: bool = True):
+    def _run(self, x: Tensor, x_lo: Tensor, with_skip: bool, chained: bool = False, want_lo: bool = True,
+             gates=None):
         """-> (new stream, its MFMA-operand copy).  Plain-ViT mode: the copy is made only when `want_lo` (the blocks
-        read their normalised inputs, not the stream; only the reconstruction head after the last block needs it)."""
+        read their normalised inputs, not the stream; only the reconstruction head after the last block needs it).
+        gates: this block's (attention, MLP) rows of the step's DropPath table, from ViT.forward's chain only
+        (with_skip)."""
         model, idx = self._owner
         rt = model._rt
+        if gates is not None and not with_skip:
+            raise ValueError("Block._run: gates go with the block chain of ViT.forward (with_skip) only")
         if not self.config.use_nvit:
-            xn, xn_lo = _StdBlockFn.apply(x, rt, idx, with_skip, want_lo, model._attn_impl(), *self._args(), _lean())
+            xn, xn_lo = _StdBlockFn.apply(x, rt, idx, with_skip, want_lo, model._attn_impl(), *self._args(), _lean(),
+                                          gates)
             return xn, (_lo(rt, xn, xn_lo) if want_lo else None)
-        xn, xn_lo = _BlockFn.apply(x, x_lo, rt, idx, with_skip, model._attn_impl(), *self._args(), chained, _lean())
+        xn, xn_lo = _BlockFn.apply(x, x_lo, rt, idx, with_skip, model._attn_impl(), *self._args(), chained, _lean(),
+                                   gates)
         return xn, _lo(rt, xn, xn_lo)
 
     def norm_skip(self, source: Tensor, target: Tensor) -> Tensor:
@@ -1145,6 +1170,7 @@ class ViT(nn.Module):
         object.__setattr__(self, "_node_sync", None)   # set by DataParallel: averages SOM nodes across ranks
         object.__setattr__(self, "_taps", None)        # tests: dict that receives the residual stream after each block
         object.__setattr__(self, "_grad_sink", None)   # set by DataParallel: gradients are produced inside its buckets
+        object.__setattr__(self, "drop_path", None)    # attach_drop_path: stochastic depth of the block chain (training only)
         object.__setattr__(self.cross_attention, "_owner", self)
         for i, blk in enumerate(self.transformer.h):
             object.__setattr__(blk, "_owner", (self, i))
@@ -1179,6 +1205,39 @@ class ViT(nn.Module):
         _dt_from_precision(precision)
         self.precision = precision
         return self
+
+    def attach_drop_path(self, drop_path) -> "ViT":
+        """Stochastic depth for the block chain of forward(): `drop_path` is a `DropPath` (droppath.py) moved to the
+        model's device, or None to detach.  While the model is in training mode and the rate is > 0, every forward calls
+        `drop_path.draw(n_layer, B)` exactly once and hands rows 2*l and 2*l + 1 of the fp32 [2*n_layer, B] table it
+        returns to block l (attention and MLP branch).  nViT: the gated LERP kernels multiply the step of every row of
+        sample b by gate[b]; plain ViT: the gated residual kernels add gate[b] * branch output.  The backward is that of the
+        gated forward.  The cross-attention block, the Kohonen head, the classifier head and stand-alone Block.forward are
+        not gated.  eval(), no attachment or rate 0 launch exactly what they launch without the feature.  A scale_by_keep
+        of None is resolved here: True for the plain ViT (timm's), False for nViT.
+        Not part of the state_dict or the config: save `drop_path.state_dict()` (checkpoint.py takes drop_path=)."""
+        if drop_path is None:
+            object.__setattr__(self, "drop_path", None)
+            return self
+        from .droppath import DropPath
+        if not isinstance(drop_path, DropPath):
+            raise TypeError("attach_drop_path takes a DropPath or None")
+        if drop_path.scale_by_keep is None:
+            drop_path.scale_by_keep = not self.config.use_nvit
+        object.__setattr__(self, "drop_path", drop_path)
+        return self
+
+    def _draw_gates(self, B: int):
+        """The step's gate table, or None when stochastic depth is off (eval, nothing attached, rate 0)."""
+        dp = self.drop_path
+        if dp is None or not self.training or dp.rate <= 0.0:
+            return None
+        L = self.config.n_layer
+        table = dp.draw(L, B)
+        if (not isinstance(table, Tensor) or table.dtype != torch.float32 or tuple(table.shape) != (2 * L, B)
+                or not table.is_cuda or not table.is_contiguous()):
+            raise ValueError(f"DropPath.draw must return a contiguous fp32 [{2 * L}, {B}] device tensor")
+        return table
 
     def _attn_impl(self) -> int:
         """1: the MFMA flash kernels (bf16 mode, every supported head dim: 32, 64, 128, and the PADDED_HEAD_DIMS, which
@@ -1340,8 +1399,10 @@ class ViT(nn.Module):
         taps = self._taps
         if taps is not None:
             taps["loc"], taps["glo"], taps["x0"] = loc.detach(), glo.detach(), x.detach()
+        table = self._draw_gates(B) if len(self.transformer.h) else None
         for i, blk in enumerate(self.transformer.h):
-            x, x_lo = blk._run(x, x_lo, True, chained=True)
+            x, x_lo = blk._run(x, x_lo, True, chained=True,
+                               gates=None if table is None else (table[2 * i], table[2 * i + 1]))
             if taps is not None:
                 taps[f"x{i + 1}"] = x.detach()
         logits = _HeadFn.apply(x, rt, self.mlp_head[0].weight, self.mlp_head[0].bias, self.mlp_head[1].weight,
@@ -1360,8 +1421,10 @@ class ViT(nn.Module):
             taps["loc"], taps["glo"], taps["x0"] = loc.detach(), glo.detach(), x.detach()
         blocks = self.transformer.h
         x_lo = _lo(rt, x, ops.cast(x, rt.dt) if rt.dt != F32 else None) if len(blocks) == 0 else None
+        table = self._draw_gates(x.shape[0] // self.n_tokens) if len(blocks) else None
         for i, blk in enumerate(blocks):
-            x, x_lo = blk._run(x, None, True, want_lo=(want_recon and i == len(blocks) - 1))
+            x, x_lo = blk._run(x, None, True, want_lo=(want_recon and i == len(blocks) - 1),
+                               gates=None if table is None else (table[2 * i], table[2 * i + 1]))
             if taps is not None:
                 taps[f"x{i + 1}"] = x.detach()
         logits = _HeadFn.apply(x, rt, self.mlp_head[0].weight, self.mlp_head[0].bias, self.mlp_head[1].weight,

@@ -19,6 +19,7 @@ Tensor = torch.Tensor
 # layout numbers shared with the kernels: each is written once, in include/nvit_hip.h
 MAX_PART_BLOCKS = _lib.const("MAX_PART_BLOCKS")   # the most workgroups a backward row kernel accepts
 ROW_WAVES = _lib.const("ROW_WAVES")   # rows in flight per workgroup; per-wave partial arrays hold ROW_WAVES * nblk rows
+ROW_GRID_MAX = _lib.const("ROW_GRID_MAX")   # workgroups of a forward row kernel's grid; more rows are walked with a stride
 PAD_HEAD_DIM = _lib.const("PAD_HEAD_DIM")   # dp: the attention head dim the zero-padded head tensors run at
 REDUCE_MAX_ITEMS = _lib.const("COLSUM_REDUCE_MAX_ITEMS")   # reductions nvit_colsum_reduce_multi takes in one launch
 ATTN_BWD_PART_ROWS = _lib.const("ATTN_BWD_PART_ROWS")   # tokens per row of nvit_attn_bwd_qknorm's d(sqk) partials
@@ -245,11 +246,27 @@ def _part_blocks(nblk: Optional[int], default: int, name: str) -> int:
     return nblk
 
 
+def _chk_gate(gate: Tensor, M: int, ref: Tensor, what: str) -> int:
+    """-> rows_per_sample of a gated row kernel: `gate` holds one fp32 gate per sample (a row of DropPath's table), the
+    [M, C] operands hold M / gate.numel() consecutive rows per sample.  The kernel indexes it unchecked."""
+    if (not isinstance(gate, Tensor) or gate.dtype != torch.float32 or gate.dim() != 1 or not gate.is_contiguous()
+            or gate.device != ref.device or gate.numel() < 1 or M % gate.numel()):
+        raise ValueError(f"{what}: gate must be a contiguous fp32 vector on {ref.device} whose length divides M={M}")
+    return M // gate.numel()
+
+
 def lerp_fwd(dt: int, h: Tensor, y: Tensor, alpha: Tensor, c_a: float, skip_x: Optional[Tensor] = None,
-             skip: Optional[Tensor] = None, want_lo: bool = True) -> Tuple[Tensor, Optional[Tensor]]:
+             skip: Optional[Tensor] = None, want_lo: bool = True, *,
+             gate: Optional[Tensor] = None) -> Tuple[Tensor, Optional[Tensor]]:
+    """gate (fp32 [B], M = B * rows per sample; stochastic depth): the gated kernel, out = nrm(a + gate * lam * (b - a))."""
     M, Cc = h.shape
     out = torch.empty_like(h)
     out_lo = torch.empty((M, Cc), device=h.device, dtype=tdtype(dt)) if want_lo else None
+    if gate is not None:
+        T = _chk_gate(gate, M, h, "lerp_fwd")
+        check(_lib.load().nvit_lerp_fwd_gated(dt, _p(h), _p(y), dt_of(y), _p(alpha), c_a, _p(skip_x), _p(skip), _p(gate),
+                                              T, _p(out), _p(out_lo), M, Cc, _s()), "nvit_lerp_fwd_gated")
+        return out, out_lo
     check(_lib.load().nvit_lerp_fwd(dt, _p(h), _p(y), dt_of(y), _p(alpha), c_a, _p(skip_x), _p(skip), _p(out),
                                     _p(out_lo), M, Cc, _s()), "nvit_lerp_fwd")
     return out, out_lo
@@ -257,10 +274,12 @@ def lerp_fwd(dt: int, h: Tensor, y: Tensor, alpha: Tensor, c_a: float, skip_x: O
 
 def lerp_bwd(dt: int, dout: Tensor, h: Tensor, y: Tensor, alpha: Tensor, c_a: float, skip_x: Optional[Tensor],
              skip: Optional[Tensor], dh: Optional[Tensor], accum_dh: bool, want_dy_f32: bool, want_dy_lo: bool,
-             dout_add: Optional[Tensor] = None, *, nblk: Optional[int] = None):
+             dout_add: Optional[Tensor] = None, *, nblk: Optional[int] = None, gate: Optional[Tensor] = None):
     """-> dh, dy_f32|None, dy_lo|None, dskip_x|None, part_dlam [ROW_WAVES*nblk,C], part_dskip|None.
     dout_add: optional bf16 [M,C] added to dout inside the kernel (a data-gradient GEMM's output).
-    nblk: workgroups to launch instead of the resident count (1..MAX_PART_BLOCKS)."""
+    nblk: workgroups to launch instead of the resident count (1..MAX_PART_BLOCKS).
+    gate: as in lerp_fwd; the gated kernel is built for the block chain's two calls only (skip_x without accum_dh, or
+    accum_dh without skip_x)."""
     if dout_add is not None and (dout_add.dtype != torch.bfloat16 or dout_add.shape != h.shape or not dout_add.is_contiguous()):
         raise ValueError("lerp_bwd: dout_add must be a contiguous bf16 [M,C] tensor")
     M, Cc = h.shape
@@ -268,12 +287,18 @@ def lerp_bwd(dt: int, dout: Tensor, h: Tensor, y: Tensor, alpha: Tensor, c_a: fl
     if dh is None:
         dh = torch.empty_like(h)
         accum_dh = False
+    gated = gate is not None
+    if gated:
+        T = _chk_gate(gate, M, h, "lerp_bwd")
+        if (skip_x is not None) == bool(accum_dh):
+            raise ValueError("lerp_bwd: the gated kernel takes skip_x without accum_dh, or accum_dh without skip_x")
     # grid = the workgroups resident at once for this kernel variant (a second, partly filled round of a 1024-block
     # grid cost 1.8 ms per Base step)
-    key = (dt, dt_of(y), Cc, dout_add is not None, skip_x is not None, bool(accum_dh))
+    key = (dt, dt_of(y), Cc, dout_add is not None, skip_x is not None, bool(accum_dh), gated)
     nres = _LERP_BWD_BLOCKS.get(key)
     if nres is None:
-        nres = int(_lib.load().nvit_lerp_bwd_blocks(dt, dt_of(y), Cc, int(key[3]), int(key[4]), int(key[5]))) or PART_BLOCKS
+        blocks = _lib.load().nvit_lerp_bwd_gated_blocks if gated else _lib.load().nvit_lerp_bwd_blocks
+        nres = int(blocks(dt, dt_of(y), Cc, int(key[3]), int(key[4]), int(key[5]))) or PART_BLOCKS
         _LERP_BWD_BLOCKS[key] = nres
     nblk = _part_blocks(nblk, min(nres, math.ceil(M / ROW_WAVES)), "lerp_bwd")
     dy = torch.empty_like(h) if want_dy_f32 else None
@@ -281,6 +306,11 @@ def lerp_bwd(dt: int, dout: Tensor, h: Tensor, y: Tensor, alpha: Tensor, c_a: fl
     dskip_x = torch.empty_like(h) if skip_x is not None else None
     part = torch.empty((ROW_WAVES * nblk, Cc), device=dev, dtype=torch.float32)   # one row of column partials per wave
     pskip = torch.empty((ROW_WAVES * nblk,), device=dev, dtype=torch.float32) if skip_x is not None else None
+    if gated:
+        check(_lib.load().nvit_lerp_bwd_gated(dt, _p(dout), _p(dout_add), _p(h), _p(y), dt_of(y), _p(alpha), c_a, _p(skip_x),
+                                              _p(skip), _p(gate), T, _p(dh), int(accum_dh), _p(dy), _p(dy_lo), _p(dskip_x),
+                                              _p(part), _p(pskip), nblk, M, Cc, _s()), "nvit_lerp_bwd_gated")
+        return dh, dy, dy_lo, dskip_x, part, pskip
     check(_lib.load().nvit_lerp_bwd(dt, _p(dout), _p(dout_add), _p(h), _p(y), dt_of(y), _p(alpha), c_a, _p(skip_x), _p(skip),
                                     _p(dh), int(accum_dh), _p(dy), _p(dy_lo), _p(dskip_x), _p(part), _p(pskip),
                                     nblk, M, Cc, _s()), "nvit_lerp_bwd")
@@ -334,14 +364,23 @@ def _chk_vec(C: int, *vs, name=""):
             raise ValueError(f"{name}: contiguous fp32 vector of {C} elements expected")
 
 
-def res_rmsnorm_fwd(dt: int, a: Tensor, y: Optional[Tensor], w: Tensor, eps: float, want_lo: bool = True):
-    """out = rms(a + y) * w (y None: rms(a) * w) -> out fp32, out_lo (type dt) | None, rstd [M]."""
+def res_rmsnorm_fwd(dt: int, a: Tensor, y: Optional[Tensor], w: Tensor, eps: float, want_lo: bool = True, *,
+                    gate: Optional[Tensor] = None):
+    """out = rms(a + y) * w (y None: rms(a) * w) -> out fp32, out_lo (type dt) | None, rstd [M].
+    gate (fp32 [B], M = B * rows per sample; stochastic depth, needs y): rms(a + gate * y) * w."""
     M, Cc = a.shape
     _chk_rows((M, Cc), y, f32=(a,), name="res_rmsnorm_fwd")
     _chk_vec(Cc, w, name="res_rmsnorm_fwd")
     out = torch.empty_like(a)
     out_lo = torch.empty((M, Cc), device=a.device, dtype=tdtype(dt)) if want_lo else None
     rstd = torch.empty((M,), device=a.device, dtype=torch.float32)
+    if gate is not None:
+        if y is None:
+            raise ValueError("res_rmsnorm_fwd: a gate needs the branch output y")
+        T = _chk_gate(gate, M, a, "res_rmsnorm_fwd")
+        check(_lib.load().nvit_res_rmsnorm_fwd_gated(dt, _p(a), _p(y), dt_of(y), _p(w), eps, _p(gate), T, _p(out), _p(out_lo),
+                                                     _p(rstd), M, Cc, _s()), "nvit_res_rmsnorm_fwd_gated")
+        return out, out_lo, rstd
     check(_lib.load().nvit_res_rmsnorm_fwd(dt, _p(a), _p(y), dt_of(y) if y is not None else F32, _p(w), eps, _p(out),
                                            _p(out_lo), _p(rstd), M, Cc, _s()), "nvit_res_rmsnorm_fwd")
     return out, out_lo, rstd
@@ -349,9 +388,10 @@ def res_rmsnorm_fwd(dt: int, a: Tensor, y: Optional[Tensor], w: Tensor, eps: flo
 
 def res_rmsnorm_bwd(dt: int, g: Tensor, a: Tensor, y: Optional[Tensor], w: Tensor, rstd: Tensor,
                     g_add: Optional[Tensor] = None, dz: Optional[Tensor] = None, want_lo: bool = False, *,
-                    nblk: Optional[int] = None):
+                    nblk: Optional[int] = None, gate: Optional[Tensor] = None):
     """Backward of res_rmsnorm_fwd -> dz fp32 (added to `dz` when given), dz_lo (type dt) | None, part_dw [ROW_WAVES*nblk, C].
-    g_add: optional type-dt [M,C] addend of the incoming gradient (a data-gradient GEMM's output)."""
+    g_add: optional type-dt [M,C] addend of the incoming gradient (a data-gradient GEMM's output).
+    gate: as in res_rmsnorm_fwd (needs y and g_add); dz stays d(a + gate * y), dz_lo becomes gate * dz = d(y)."""
     M, Cc = a.shape
     _chk_rows((M, Cc), y, g_add, f32=(a, g, dz), name="res_rmsnorm_bwd")
     _chk_vec(Cc, w, name="res_rmsnorm_bwd")
@@ -364,27 +404,43 @@ def res_rmsnorm_bwd(dt: int, g: Tensor, a: Tensor, y: Optional[Tensor], w: Tenso
     nblk = _part_blocks(nblk, _row_part_blocks(M), "res_rmsnorm_bwd")
     dz_lo = torch.empty((M, Cc), device=a.device, dtype=tdtype(dt)) if want_lo else None
     part = torch.empty((ROW_WAVES * nblk, Cc), device=a.device, dtype=torch.float32)
+    if gate is not None:
+        if y is None or g_add is None:
+            raise ValueError("res_rmsnorm_bwd: the gated kernel needs the branch output y and the addend g_add")
+        T = _chk_gate(gate, M, a, "res_rmsnorm_bwd")
+        check(_lib.load().nvit_res_rmsnorm_bwd_gated(dt, _p(g), _p(g_add), _p(a), _p(y), dt_of(y), _p(w), _p(rstd), _p(gate),
+                                                     T, _p(dz), int(accum), _p(dz_lo), _p(part), nblk, M, Cc, _s()),
+              "nvit_res_rmsnorm_bwd_gated")
+        return dz, dz_lo, part
     check(_lib.load().nvit_res_rmsnorm_bwd(dt, _p(g), _p(g_add), _p(a), _p(y), dt_of(y) if y is not None else F32, _p(w),
                                            _p(rstd), _p(dz), int(accum), _p(dz_lo), _p(part), nblk, M, Cc, _s()),
           "nvit_res_rmsnorm_bwd")
     return dz, dz_lo, part
 
 
-def res_skip_fwd(dt: int, h: Tensor, y: Tensor, skip: Tensor, x: Tensor, want_lo: bool = True):
-    """out = nrm((h + y) * skip + x) -> out fp32, out_lo (type dt) | None."""
+def res_skip_fwd(dt: int, h: Tensor, y: Tensor, skip: Tensor, x: Tensor, want_lo: bool = True, *,
+                 gate: Optional[Tensor] = None):
+    """out = nrm((h + y) * skip + x) -> out fp32, out_lo (type dt) | None.
+    gate (fp32 [B], M = B * rows per sample; stochastic depth): nrm((h + gate * y) * skip + x)."""
     M, Cc = h.shape
     _chk_rows((M, Cc), y, f32=(h, x), name="res_skip_fwd")
     _chk_vec(1, skip, name="res_skip_fwd")
     out = torch.empty_like(h)
     out_lo = torch.empty((M, Cc), device=h.device, dtype=tdtype(dt)) if want_lo else None
+    if gate is not None:
+        T = _chk_gate(gate, M, h, "res_skip_fwd")
+        check(_lib.load().nvit_res_skip_fwd_gated(dt, _p(h), _p(y), dt_of(y), _p(skip), _p(x), _p(gate), T, _p(out),
+                                                  _p(out_lo), M, Cc, _s()), "nvit_res_skip_fwd_gated")
+        return out, out_lo
     check(_lib.load().nvit_res_skip_fwd(dt, _p(h), _p(y), dt_of(y), _p(skip), _p(x), _p(out), _p(out_lo), M, Cc, _s()),
           "nvit_res_skip_fwd")
     return out, out_lo
 
 
 def res_skip_bwd(dt: int, dout: Tensor, h: Tensor, y: Tensor, skip: Tensor, x: Tensor, want_lo: bool = True, *,
-                 nblk: Optional[int] = None):
-    """Backward of res_skip_fwd -> dh = d(h + y) fp32, dh_lo (type dt) | None, dx fp32, part_dskip [ROW_WAVES*nblk]."""
+                 nblk: Optional[int] = None, gate: Optional[Tensor] = None):
+    """Backward of res_skip_fwd -> dh = d(h + y) fp32, dh_lo (type dt) | None, dx fp32, part_dskip [ROW_WAVES*nblk].
+    gate: as in res_skip_fwd; dh stays d(h + gate * y), dh_lo becomes gate * dh = d(y)."""
     M, Cc = h.shape
     _chk_rows((M, Cc), y, f32=(dout, h, x), name="res_skip_bwd")
     _chk_vec(1, skip, name="res_skip_bwd")
@@ -393,6 +449,11 @@ def res_skip_bwd(dt: int, dout: Tensor, h: Tensor, y: Tensor, skip: Tensor, x: T
     dx = torch.empty_like(h)
     dh_lo = torch.empty((M, Cc), device=h.device, dtype=tdtype(dt)) if want_lo else None
     part = torch.empty((ROW_WAVES * nblk,), device=h.device, dtype=torch.float32)
+    if gate is not None:
+        T = _chk_gate(gate, M, h, "res_skip_bwd")
+        check(_lib.load().nvit_res_skip_bwd_gated(dt, _p(dout), _p(h), _p(y), dt_of(y), _p(skip), _p(x), _p(gate), T, _p(dh),
+                                                  _p(dh_lo), _p(dx), _p(part), nblk, M, Cc, _s()), "nvit_res_skip_bwd_gated")
+        return dh, dh_lo, dx, part
     check(_lib.load().nvit_res_skip_bwd(dt, _p(dout), _p(h), _p(y), dt_of(y), _p(skip), _p(x), _p(dh), _p(dh_lo), _p(dx),
                                         _p(part), nblk, M, Cc, _s()), "nvit_res_skip_bwd")
     return dh, dh_lo, dx, part

@@ -223,6 +223,9 @@ def train_step(model, optimizer, X: torch.Tensor, y: torch.Tensor, grad_clip: fl
     be left out (an erasing directly around a crop normalises it first).  Every stage's launches run once for the whole
     batch, in this order, ahead of the forward and of any accumulation split, and every stage's counter advances by one.
 
+    A `DropPath` attached to the model (`ViT.attach_drop_path`) needs nothing here: every training forward draws its own
+    gate table, so with accumulation_steps = N its counter advances by N, each micro-batch drawing for its own rows.
+
     Wrong accumulation_steps (no int, < 1, no divisor of the batch) or skip_nonfinite with another optimizer raise
     ValueError before any device work."""
     _check_step_args(optimizer, X, accumulation_steps, skip_nonfinite)
@@ -290,6 +293,11 @@ class GraphedTrainStep:
     its update follow the optimizer's launches, and its count lives on the device.  The warm-up steps are updates, as they
     are optimizer steps; the capture pass is not (it executes nothing).  A call with another EMA attached than at capture
     time (or none, or one where there was none) raises ValueError.
+
+    A `DropPath` attached to the model (`ViT.attach_drop_path`) draws inside the forward, so its draw is captured with it:
+    the counter is a device int64 the draw kernel advances, every replay drops other branches, and with
+    accumulation_steps = N a replay is N draws.  Warm-up steps advance the counter, the capture pass does not.  A call
+    with another DropPath attached than at capture time (or none, or one where there was none) raises ValueError.
     """
 
     def __init__(self, model, optimizer, X: torch.Tensor, y: torch.Tensor, grad_clip: float = 1.0, warmup: int = 3,
@@ -309,6 +317,7 @@ class GraphedTrainStep:
         self.erase, self.crop = self._stages.get("erase", (None,))[0], self._stages.get("crop")
         self.model, self.optimizer, self.grad_clip = model, optimizer, grad_clip
         self.ema = optimizer.ema   # the ModelEma (or none) whose update the warm-up steps run and the capture records
+        self.drop_path = m.drop_path   # the DropPath (or none) whose draw the captured forwards contain
         self.accumulation_steps, self.skip_nonfinite = accumulation_steps, bool(skip_nonfinite)
         N = accumulation_steps
         self.X, self.y = X.clone(), y.clone()
@@ -405,6 +414,8 @@ class GraphedTrainStep:
             X = X.u8
         if self.optimizer.ema is not self.ema:
             raise ValueError("GraphedTrainStep: this graph was captured with another ModelEma (or none)")
+        if _unwrap(self.model).drop_path is not self.drop_path:
+            raise ValueError("GraphedTrainStep: this graph was captured with another DropPath (or none)")
         self.X.copy_(X, non_blocking=True)
         self.y.copy_(y, non_blocking=True)
         self._advance_som()
