@@ -466,6 +466,27 @@ int nvit_mix_apply(const float* in, const int* table, float* out, int B, int C, 
 #define NVIT_DROPPATH_MAX_GATES 1048576
 int nvit_droppath_draw(uint64_t seed, int64_t* step, int64_t first_index, const float* rates, int scale_by_keep,
                        float* table, int n_layer, int B, void* stream);
+/* Patch dropout (timm's PatchDropout / FLIP; tests/patchdrop_ref.py).  nvit_patchdrop_draw: keep int32 [B,K],
+ * the kept token indices of each sample, ascending; slot int32 [B,T], slot[b, keep[b,j]] = j and -1 for a dropped token.
+ * Token t of sample b gets the 24-bit word u = r >> 8, r = word t & 3 of one Philox4x32-10 call, counter = (first_index +
+ * b, *step), key = seed with (a domain constant + (t >> 2)) xor-ed into its high word; kept are the K tokens with the
+ * smallest (u << 32) | t, so a tie of u goes to the smaller t.  One workgroup per sample, 1 <= K <= T <=
+ * NVIT_PATCHDROP_MAX_TOKENS.  *step is a device int64 that every workgroup reads; a one-thread launch that the call puts
+ * behind the draw on the same stream advances it by one (nvit_augment_draw's contract, for a grid of more than one
+ * workgroup). */
+#define NVIT_PATCHDROP_MAX_TOKENS 4096
+int nvit_patchdrop_draw(uint64_t seed, int64_t* step, int64_t first_index, int* keep, int* slot, int B, int T, int K,
+                        void* stream);
+/* nvit_rows_gather: dstX[b*K + j, :] = srcX[b*T + keep[b,j], :], fp32 rows of C contiguous elements (C a multiple of 4,
+ * 16-byte aligned pointers), X = 0 and, src1 / dst1 non-NULL, 1: both embedding streams in one launch.  loX non-NULL
+ * (lo_dt NVIT_BF16; lo1 exactly when lo0 and src1): the row is also stored rounded to bf16, round to nearest even as
+ * nvit_cast does.  A keep entry outside [0, T) stores a row of zeros.  nvit_rows_scatter is its backward: gX[b*T + t, :] =
+ * dX[b*K + slot[b,t], :] where 0 <= slot[b,t] < K, else zeros; every element of gX is written exactly once (no memset,
+ * no atomics).  Grids as the forward row kernels': NVIT_ROW_WAVES rows per workgroup, at most NVIT_ROW_GRID_MAX. */
+int nvit_rows_gather(const float* src0, const float* src1, const int* keep, float* dst0, float* dst1, void* lo0, void* lo1,
+                     int lo_dt, int B, int T, int K, int C, void* stream);
+int nvit_rows_scatter(const float* d0, const float* d1, const int* slot, float* g0, float* g1, int B, int T, int K, int C,
+                      void* stream);
 /* On-device RandomResizedCrop + horizontal flip (tests/crop_ref.py): a stored uint8 [B,Hs,Ws,C] batch ->
  * uint8 [B,size,size,C], image b = Pillow's crop(box b).resize((size, size), BILINEAR | BICUBIC), mirrored if its flip
  * bit is set, bit for bit.  Three launches per batch: the draw and the two passes of the apply.

@@ -28,6 +28,9 @@ def __getattr__(name):
     if name == "DropPath":
         from . import droppath
         return droppath.DropPath
+    if name == "PatchDropout":
+        from . import patchdrop
+        return patchdrop.PatchDropout
     if name == "FusedAdamW":
         from . import optim
         return optim.FusedAdamW

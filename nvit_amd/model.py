@@ -108,6 +108,14 @@ class _Runtime:
         # (nvit_lerp_bwd dout_add).  `carry` hands the q/k/v addend to the backward of the PREVIOUS block of the chain
         # built by ViT.forward: (index of the consumer, tensor); -1 = the cross-attention block.
         self.carry = None
+        # tokens per sample of the forward that is running: None = model.n_tokens; a forward that drops patches
+        # (ViT.attach_patch_drop) sets the K it kept for the calls behind its gather and clears it when it returns.  A
+        # backward reads the count its own forward saw from ctx.dims, never from here.
+        self.tokens = None
+
+    @property
+    def n_tokens(self) -> int:
+        return self.model.n_tokens if self.tokens is None else self.tokens
 
     def y_dtype(self) -> torch.dtype:
         """Storage type of the branch outputs y (att_c_proj / mlp_c_proj / out_proj results, the second LERP input).
@@ -283,9 +291,9 @@ def _lean() -> bool:
 
 
 def _dims(rt: _Runtime, M: int):
-    """(B, T, C, H, d, M) of a block call over M = B*T token rows."""
+    """(B, T, C, H, d, M) of a block call over M = B*T token rows, T the running forward's count (_Runtime.tokens)."""
     cfg = rt.model.config
-    T = rt.model.n_tokens
+    T = rt.n_tokens
     return M // T, T, cfg.n_embd, cfg.n_head, cfg.n_embd // cfg.n_head, M
 
 
@@ -860,6 +868,32 @@ class _EmbedFn(torch.autograd.Function):
         return None, None, gwl.reshape(wls), dbl, dposl.reshape(ps), gwg.reshape(wgs), dbg, dposg.reshape(ps)
 
 
+class _TokenDropFn(torch.autograd.Function):
+    """Patch dropout between the embedding and the cross-attention block: the kept tokens of both embedding streams,
+    loc, glo fp32 [B*T, C] -> [B*K, C] by keep int32 [B, K] (nvit_rows_gather, one launch), with the bf16 twins of the
+    gathered rows when the embedding produced twins (want_lo).  Backward: nvit_rows_scatter hands _EmbedFn.backward
+    full-size [B*T, C] gradients whose rows of dropped tokens are zeros (slot int32 [B, T] is keep's inverse)."""
+
+    @staticmethod
+    def forward(ctx, loc, glo, keep, slot, want_lo):
+        B, T = slot.shape
+        K = keep.shape[1]
+        loc_k, glo_k, loc_lo, glo_lo = ops.rows_gather(loc, glo, keep, B, T, lo_dt=(BF16 if want_lo else None))
+        ctx.dims = (B, K)
+        ctx.save_for_backward(slot)
+        if not want_lo:
+            loc_lo, glo_lo = loc.new_empty(0), loc.new_empty(0)
+        ctx.mark_non_differentiable(loc_lo, glo_lo)
+        return loc_k, glo_k, loc_lo, glo_lo
+
+    @staticmethod
+    def backward(ctx, dloc, dglo, _lo1, _lo2):
+        slot, = ctx.saved_tensors
+        B, K = ctx.dims
+        gloc, gglo = ops.rows_scatter(dloc.contiguous(), dglo.contiguous(), slot, B, K)
+        return gloc, gglo, None, None, None
+
+
 class _HeadFn(torch.autograd.Function):
     """mean-pool -> LayerNorm -> Linear -> * sz (reference model.py:455-456,466-468); sz None (plain ViT): no scale."""
 
@@ -867,7 +901,7 @@ class _HeadFn(torch.autograd.Function):
     def forward(ctx, x, rt, ln_w, ln_b, wh, bh, sz):
         cfg = rt.model.config
         C, ncls = cfg.n_embd, cfg.num_classes
-        T = rt.model.n_tokens
+        T = rt.n_tokens   # (K behind a patch-dropout gather: the mean runs over the kept tokens)
         B = x.shape[0] // T
         c_sz = cfg.sz_init_value / cfg.sz_init_scaling
         pooled, ln, ln_lo, stats = ops.pool_ln_fwd(rt.dt, x, ln_w, ln_b, 1e-5, B, T, C)
@@ -1171,6 +1205,7 @@ class ViT(nn.Module):
         object.__setattr__(self, "_taps", None)        # tests: dict that receives the residual stream after each block
         object.__setattr__(self, "_grad_sink", None)   # set by DataParallel: gradients are produced inside its buckets
         object.__setattr__(self, "drop_path", None)    # attach_drop_path: stochastic depth of the block chain (training only)
+        object.__setattr__(self, "patch_drop", None)   # attach_patch_drop: patch dropout behind the embedding (training only)
         object.__setattr__(self.cross_attention, "_owner", self)
         for i, blk in enumerate(self.transformer.h):
             object.__setattr__(blk, "_owner", (self, i))
@@ -1238,6 +1273,44 @@ class ViT(nn.Module):
                 or not table.is_cuda or not table.is_contiguous()):
             raise ValueError(f"DropPath.draw must return a contiguous fp32 [{2 * L}, {B}] device tensor")
         return table
+
+    def attach_patch_drop(self, patch_drop) -> "ViT":
+        """Patch dropout for forward(): `patch_drop` is a `PatchDropout` (patchdrop.py) moved to the model's device, or
+        None to detach.  While the model is in training mode with gradients enabled and the rate is > 0, every forward
+        calls `patch_drop.draw(B, T)` exactly once, gathers the K kept tokens of both embedding streams directly behind the
+        patch embedding (position embeddings included) and runs the cross-attention block, the block chain, stochastic
+        depth and the mean-pool on K tokens per sample; the shape-dependent route choices decide by the K-token shapes.
+        The backward scatters the gradients back to [B*T, C] with zero rows for the dropped tokens.  Such a forward does
+        not evaluate the reconstruction head (see forward).  eval(), torch.no_grad(), nothing attached or rate 0 launch
+        exactly what they launch without the feature.  Not with the Kohonen head (ValueError): the SOM and the
+        reconstruction loss are defined per image patch.  A data-parallel rank passes first_index = rank * B.
+        Not part of the state_dict or the config: save `patch_drop.state_dict()` (checkpoint.py takes patch_drop=)."""
+        if patch_drop is None:
+            object.__setattr__(self, "patch_drop", None)
+            return self
+        from .patchdrop import PatchDropout
+        if not isinstance(patch_drop, PatchDropout):
+            raise TypeError("attach_patch_drop takes a PatchDropout or None")
+        if self.config.use_kohonen:
+            raise ValueError("attach_patch_drop: not with use_kohonen=True (the SOM and the reconstruction loss are "
+                             "defined per image patch)")
+        object.__setattr__(self, "patch_drop", patch_drop)
+        return self
+
+    def _draw_tokens(self, B: int):
+        """(keep, slot) of this forward, or None when patch dropout is off (eval, no_grad, nothing attached, rate 0)."""
+        pd = self.patch_drop
+        if pd is None or not self.training or pd.rate <= 0.0 or not torch.is_grad_enabled():
+            return None
+        T = self.n_tokens
+        keep, slot = pd.draw(B, T)
+        for t, n in ((keep, None), (slot, T)):
+            if (not isinstance(t, Tensor) or t.dtype != torch.int32 or t.dim() != 2 or t.shape[0] != B
+                    or (n is not None and t.shape[1] != n) or not t.is_cuda or not t.is_contiguous()):
+                raise ValueError(f"PatchDropout.draw must return contiguous int32 device tensors [{B}, K] and [{B}, {T}]")
+        if not 1 <= keep.shape[1] <= T:
+            raise ValueError(f"PatchDropout.draw: K = {keep.shape[1]} outside 1..{T}")
+        return keep, slot
 
     def _attn_impl(self) -> int:
         """1: the MFMA flash kernels (bf16 mode, every supported head dim: 32, 64, 128, and the PADDED_HEAD_DIMS, which
@@ -1345,7 +1418,10 @@ class ViT(nn.Module):
 
     def forward(self, img: Tensor) -> Tuple[Tensor, Dict[str, Tensor]]:
         """(logits, aux).  Under torch.no_grad / inference_mode the block functions take their forward-only route (see
-        _lean()): the same logits and aux values bit for bit, without the stores and tensors only a backward reads."""
+        _lean()): the same logits and aux values bit for bit, without the stores and tensors only a backward reads.
+        A training forward that drops patches (attach_patch_drop) does not evaluate the reconstruction head - its target
+        is every image patch - and its aux has no "reconstruction" entry; without the Kohonen head, which patch dropout
+        excludes, the loss never reads it (train.add_aux_losses)."""
         return self._forward(img, True)
 
     def _forward(self, img: Tensor, want_recon: bool) -> Tuple[Tensor, Dict[str, Tensor]]:
@@ -1353,6 +1429,14 @@ class ViT(nn.Module):
         if self.training:
             self.step += 1
         self._prepare(img.device)
+        rt = self._rt
+        rt.tokens = None
+        try:
+            return self._forward_body(img, want_recon)
+        finally:
+            rt.tokens = None   # a dropping forward's K is not left behind for stand-alone block calls
+
+    def _forward_body(self, img: Tensor, want_recon: bool) -> Tuple[Tensor, Dict[str, Tensor]]:
         rt = self._rt
         if rt.carry is not None:
             # a chained backward stopped before the node that was to consume the pending q/k/v data gradient (autograd.grad
@@ -1370,6 +1454,14 @@ class ViT(nn.Module):
                                                   self.global_patch_embed[1].bias, self.global_pos_embed)
         if loc_lo.numel() == 0:   # fp32 mode (or an embedding width the twin store does not cover): no bf16 copies
             loc_lo = glo_lo = None
+        drawn = self._draw_tokens(B)
+        if drawn is not None:
+            keep, slot = drawn
+            loc, glo, loc_k_lo, glo_k_lo = _TokenDropFn.apply(loc, glo, keep, slot, loc_lo is not None)
+            if loc_lo is not None:
+                loc_lo, glo_lo = loc_k_lo, glo_k_lo
+            rt.tokens = keep.shape[1]   # everything behind the gather runs on K tokens per sample
+            want_recon = False
         aux: Dict[str, Tensor] = {}
         if not cfg.use_nvit:
             return self._forward_std(img, loc, glo, aux, want_recon)
@@ -1421,7 +1513,7 @@ class ViT(nn.Module):
             taps["loc"], taps["glo"], taps["x0"] = loc.detach(), glo.detach(), x.detach()
         blocks = self.transformer.h
         x_lo = _lo(rt, x, ops.cast(x, rt.dt) if rt.dt != F32 else None) if len(blocks) == 0 else None
-        table = self._draw_gates(x.shape[0] // self.n_tokens) if len(blocks) else None
+        table = self._draw_gates(x.shape[0] // rt.n_tokens) if len(blocks) else None
         for i, blk in enumerate(blocks):
             x, x_lo = blk._run(x, None, True, want_lo=(want_recon and i == len(blocks) - 1),
                                gates=None if table is None else (table[2 * i], table[2 * i + 1]))

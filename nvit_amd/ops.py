@@ -660,6 +660,61 @@ def cast(src: Tensor, dt: int) -> Tensor:
     return dst
 
 
+def _chk_token_rows(name: str, table: Tensor, what: str, B: int, n: int, rows: int, s0: Tensor, s1: Optional[Tensor]):
+    """Operands of rows_gather / rows_scatter: fp32 [B*rows, C] row tensors, C a multiple of 4, and the int32 [B, n] index
+    table on their device.  -> C."""
+    if isinstance(B, bool) or not isinstance(B, int) or B < 1:
+        raise ValueError(f"{name}: B must be an int >= 1 (got {B!r})")
+    if not isinstance(s0, Tensor) or s0.dim() != 2 or s0.shape[1] % 4:
+        raise ValueError(f"{name}: [rows, C] operands with C a multiple of 4 expected")
+    _chk_rows((B * rows, s0.shape[1]), f32=(s0, s1), name=name)
+    if s1 is not None and (s1.dim() != 2 or s1.device != s0.device):
+        raise ValueError(f"{name}: the second stream must be a [rows, C] tensor on {s0.device}")
+    if (not isinstance(table, Tensor) or table.dtype != torch.int32 or tuple(table.shape) != (B, n)
+            or not table.is_contiguous() or table.device != s0.device):
+        raise ValueError(f"{name}: {what} must be a contiguous int32 [{B}, {n}] tensor on {s0.device}")
+    return s0.shape[1]
+
+
+def rows_gather(src0: Tensor, src1: Optional[Tensor], keep: Tensor, B: int, T: int, lo_dt: Optional[int] = None):
+    """Token gather of patch dropout (nvit_rows_gather): src fp32 [B*T, C], keep int32 [B, K] -> dst fp32 [B*K, C] with
+    dst[b*K + j] = src[b*T + keep[b, j]]; src1 None: one stream.  lo_dt BF16: also the bf16 twins of the gathered rows
+    (the bits of ops.cast).  -> (dst0, dst1, lo0, lo1), None where absent.  keep's values are the caller's: an index
+    outside [0, T) gathers a row of zeros."""
+    if not isinstance(keep, Tensor) or keep.dim() != 2:
+        raise ValueError("rows_gather: keep must be an int32 [B, K] tensor")
+    K = keep.shape[1]
+    if isinstance(T, bool) or not isinstance(T, int) or not 1 <= K <= T:
+        raise ValueError(f"rows_gather: 1 <= K <= T expected (K={K}, T={T!r})")
+    if lo_dt not in (None, BF16):
+        raise ValueError("rows_gather: the twins are bf16 (lo_dt None or BF16)")
+    Cc = _chk_token_rows("rows_gather", keep, "keep", B, K, T, src0, src1)
+    dev = src0.device
+    dst0 = torch.empty((B * K, Cc), device=dev, dtype=torch.float32)
+    dst1 = torch.empty_like(dst0) if src1 is not None else None
+    lo0 = torch.empty((B * K, Cc), device=dev, dtype=torch.bfloat16) if lo_dt is not None else None
+    lo1 = torch.empty_like(lo0) if lo_dt is not None and src1 is not None else None
+    check(_lib.load().nvit_rows_gather(_p(src0), _p(src1), _p(keep), _p(dst0), _p(dst1), _p(lo0), _p(lo1),
+                                       BF16 if lo_dt is not None else 0, B, T, K, Cc, _s()), "nvit_rows_gather")
+    return dst0, dst1, lo0, lo1
+
+
+def rows_scatter(d0: Tensor, d1: Optional[Tensor], slot: Tensor, B: int, K: int):
+    """Backward of rows_gather (nvit_rows_scatter): d fp32 [B*K, C], slot int32 [B, T] -> g fp32 [B*T, C] with g[b*T + t] =
+    d[b*K + slot[b, t]] where 0 <= slot[b, t] < K, else zeros; every element of g is written by the one launch.
+    -> (g0, g1), g1 None without d1."""
+    if not isinstance(slot, Tensor) or slot.dim() != 2:
+        raise ValueError("rows_scatter: slot must be an int32 [B, T] tensor")
+    T = slot.shape[1]
+    if isinstance(K, bool) or not isinstance(K, int) or not 1 <= K <= T:
+        raise ValueError(f"rows_scatter: 1 <= K <= T expected (K={K!r}, T={T})")
+    Cc = _chk_token_rows("rows_scatter", slot, "slot", B, T, K, d0, d1)
+    g0 = torch.empty((B * T, Cc), device=d0.device, dtype=torch.float32)
+    g1 = torch.empty_like(g0) if d1 is not None else None
+    check(_lib.load().nvit_rows_scatter(_p(d0), _p(d1), _p(slot), _p(g0), _p(g1), B, T, K, Cc, _s()), "nvit_rows_scatter")
+    return g0, g1
+
+
 def normalize_images(x: Tensor, mean: float = 0.5, std: float = 0.5) -> Tensor:
     """ToTensor + Normalize(mean, std) on the device (reference train.py:1084-1090, the deterministic part of its input
     pipeline): uint8 [B,H,W,C] (scaled by 1/255) or fp32 [B,C,H,W] in [0,1] -> fp32 [B,C,H,W]."""

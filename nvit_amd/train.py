@@ -224,7 +224,8 @@ def train_step(model, optimizer, X: torch.Tensor, y: torch.Tensor, grad_clip: fl
     batch, in this order, ahead of the forward and of any accumulation split, and every stage's counter advances by one.
 
     A `DropPath` attached to the model (`ViT.attach_drop_path`) needs nothing here: every training forward draws its own
-    gate table, so with accumulation_steps = N its counter advances by N, each micro-batch drawing for its own rows.
+    gate table, so with accumulation_steps = N its counter advances by N, each micro-batch drawing for its own rows.  The
+    same holds for a `PatchDropout` (`ViT.attach_patch_drop`): one draw of kept tokens per training forward.
 
     Wrong accumulation_steps (no int, < 1, no divisor of the batch) or skip_nonfinite with another optimizer raise
     ValueError before any device work."""
@@ -298,6 +299,10 @@ class GraphedTrainStep:
     the counter is a device int64 the draw kernel advances, every replay drops other branches, and with
     accumulation_steps = N a replay is N draws.  Warm-up steps advance the counter, the capture pass does not.  A call
     with another DropPath attached than at capture time (or none, or one where there was none) raises ValueError.
+
+    A `PatchDropout` (`ViT.attach_patch_drop`) likewise: its draw and the token gather are captured with the forward, every
+    replay keeps other tokens, accumulation_steps = N is N draws, and a call with another PatchDropout attached than at
+    capture time raises ValueError.  Its draw allocates, like every first call at a new shape: the warm-up steps cover it.
     """
 
     def __init__(self, model, optimizer, X: torch.Tensor, y: torch.Tensor, grad_clip: float = 1.0, warmup: int = 3,
@@ -318,6 +323,7 @@ class GraphedTrainStep:
         self.model, self.optimizer, self.grad_clip = model, optimizer, grad_clip
         self.ema = optimizer.ema   # the ModelEma (or none) whose update the warm-up steps run and the capture records
         self.drop_path = m.drop_path   # the DropPath (or none) whose draw the captured forwards contain
+        self.patch_drop = m.patch_drop   # the PatchDropout (or none), likewise
         self.accumulation_steps, self.skip_nonfinite = accumulation_steps, bool(skip_nonfinite)
         N = accumulation_steps
         self.X, self.y = X.clone(), y.clone()
@@ -416,6 +422,8 @@ class GraphedTrainStep:
             raise ValueError("GraphedTrainStep: this graph was captured with another ModelEma (or none)")
         if _unwrap(self.model).drop_path is not self.drop_path:
             raise ValueError("GraphedTrainStep: this graph was captured with another DropPath (or none)")
+        if _unwrap(self.model).patch_drop is not self.patch_drop:
+            raise ValueError("GraphedTrainStep: this graph was captured with another PatchDropout (or none)")
         self.X.copy_(X, non_blocking=True)
         self.y.copy_(y, non_blocking=True)
         self._advance_som()
