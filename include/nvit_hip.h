@@ -487,6 +487,23 @@ int nvit_rows_gather(const float* src0, const float* src1, const int* keep, floa
                      int lo_dt, int B, int T, int K, int C, void* stream);
 int nvit_rows_scatter(const float* d0, const float* d1, const int* slot, float* g0, float* g1, int B, int T, int K, int C,
                       void* stream);
+/* Resampling a position-embedding table to another token grid (timm's resample_abs_pos_embed; DESIGN.md §4;
+ * nvit_amd/resample.py builds the tables).  nvit_pos_resample_fwd: pX fp32 [g*g, C] -> outX fp32 [g2*g2, C], the bicubic
+ * (a = -0.5), antialiased, align_corners = false resize of the g x g grid of C-vectors: out[oy*g2 + ox, :] = sum over ty, tx
+ * of (wy[ty] * wx[tx]) * p[(y0 + ty)*g + x0 + tx, :], taps in this order, one product rounding for the weight and one fused
+ * multiply-add per tap.  taps: device int32 [g2, 2 + NVIT_POS_RESAMPLE_MAX_TAPS], row o = (first source index, tap count,
+ * the weights as fp32 bit patterns), computed by the host in fp64; the same row serves as y row and as x row.  X = 0 and,
+ * p1 / out1 non-NULL, 1: both tables of the model in one launch.  nvit_pos_resample_bwd is the exact adjoint, dX fp32
+ * [g2*g2, C] -> gX fp32 [g*g, C], the same gather driven by the transposed table taps_t int32 [g, 2 + MAX_TAPS] (row i = the
+ * outputs that read source i and their weights): every element of gX is written exactly once, no atomics, fixed order.
+ * C a multiple of 4, at most NVIT_MAX_EMBD; 16-byte aligned pointers; g != g2 (equal grids are the caller's no-op), both at
+ * most NVIT_POS_RESAMPLE_MAX_GRID.  A table entry that points outside the source grid is clipped to it, not followed. */
+#define NVIT_POS_RESAMPLE_MAX_TAPS 32
+#define NVIT_POS_RESAMPLE_MAX_GRID 1024
+int nvit_pos_resample_fwd(const float* p0, const float* p1, const int* taps, float* out0, float* out1, int g, int g2, int C,
+                          void* stream);
+int nvit_pos_resample_bwd(const float* d0, const float* d1, const int* taps_t, float* g0, float* g1, int g, int g2, int C,
+                          void* stream);
 /* On-device RandomResizedCrop + horizontal flip (tests/crop_ref.py): a stored uint8 [B,Hs,Ws,C] batch ->
  * uint8 [B,size,size,C], image b = Pillow's crop(box b).resize((size, size), BILINEAR | BICUBIC), mirrored if its flip
  * bit is set, bit for bit.  Three launches per batch: the draw and the two passes of the apply.

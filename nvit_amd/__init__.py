@@ -4,7 +4,7 @@ from .config import ViTConfig, named_config, train_flops_per_image  # noqa: F401
 
 def __getattr__(name):
     # model/ops import torch and bind the HIP library lazily
-    if name in ("ViT", "Block", "CrossAttentionBlock", "RMSNorm"):
+    if name in ("ViT", "Block", "CrossAttentionBlock", "RMSNorm", "resample_pos_embed"):
         from . import model
         return getattr(model, name)
     if name in ("normalize_matrices", "train_step", "GraphedTrainStep"):

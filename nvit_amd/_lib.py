@@ -112,6 +112,8 @@ SIGNATURES = {
     "nvit_patchdrop_draw": [C.c_uint64, _vp, _i64, _vp, _vp, _i, _i, _i, _vp],
     "nvit_rows_gather": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "nvit_rows_scatter": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
+    "nvit_pos_resample_fwd": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
+    "nvit_pos_resample_bwd": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
     "nvit_crop_draw": [C.c_uint64, _vp, _i64, _vp, C.c_double, C.c_double, C.c_double, C.c_double, _f, _vp, _i, _i, _i, _vp],
     "nvit_crop_ws_bytes": [_i, _i, _i, _i, _i, _i],
     "nvit_crop_apply": [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _vp],

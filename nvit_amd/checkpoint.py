@@ -82,9 +82,17 @@ def save_checkpoint(path, model, optimizer, iter_num: int, metrics: Dict[str, fl
     return path
 
 
-def load_checkpoint(path, device="cuda", optimizer_factory=None, restore_rng: bool = True, trusted: bool = False):
+def load_checkpoint(path, device="cuda", optimizer_factory=None, restore_rng: bool = True, trusted: bool = False,
+                    image_size: Optional[int] = None):
     """-> (model, optimizer | None, checkpoint dict).  `optimizer_factory(model)` builds the optimizer whose state is
-    then restored (e.g. `lambda m: m.configure_optimizers(0.1, 1e-3, (0.9, 0.95), "cuda")`)."""
+    then restored (e.g. `lambda m: m.configure_optimizers(0.1, 1e-3, (0.9, 0.95), "cuda")`).
+
+    image_size: load a checkpoint for use at another resolution (fine-tuning at 384 what was trained at 224).  The model is
+    built at the saved size, loaded and moved to the device, then `model.set_input_size(image_size)` resamples its two
+    position tables there; the returned checkpoint dict is the file's, untouched.  With another size than the saved one
+    the optimizer state no longer fits the two new parameters, so optimizer_factory must be None (ValueError otherwise):
+    build a fresh optimizer for the fine-tune.  A checkpoint saved after `set_input_size` carries the new image_size in
+    `model_args` and loads without the argument."""
     from .model import ViT
     import pickle
     allow = _numpy_safe_globals()      # built outside the try: an import problem here is not a property of the file
@@ -96,12 +104,17 @@ def load_checkpoint(path, device="cuda", optimizer_factory=None, restore_rng: bo
             raise RuntimeError(f"{path}: not loadable with weights_only=True ({type(e).__name__}: {e}); pass "
                                "trusted=True only for a file you wrote yourself") from e
         ck = torch.load(path, map_location="cpu", weights_only=False)
+    if image_size is not None and image_size != ck["model_args"].get("image_size") and optimizer_factory is not None:
+        raise ValueError("load_checkpoint: image_size differs from the saved one, so the saved optimizer state does not fit "
+                         "the resampled position embeddings; pass optimizer_factory=None and build a new optimizer")
     model = ViT(ViTConfig(**ck["model_args"]))
     res = model.load_state_dict(ck["model"], strict=False)
     bad = [k for k in res.missing_keys if not k.endswith((".locations", ".offsets"))]
     if bad or res.unexpected_keys:
         raise RuntimeError(f"checkpoint/model mismatch: missing {bad}, unexpected {list(res.unexpected_keys)}")
     model = model.to(device)
+    if image_size is not None:
+        model.set_input_size(image_size)
     opt = None
     if optimizer_factory is not None:
         opt = optimizer_factory(model)

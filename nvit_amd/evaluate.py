@@ -122,11 +122,17 @@ class GraphedEval:
     up.  Every call restores the model's `training` flag and leaves `model.step` and the SOM nodes alone.  The object is
     invalid after `model.set_precision(...)` and after anything that reallocates the parameters or the SOM nodes
     (`model.to(...)`, loading a state dict by assignment, a resize): the graphs hold their addresses; build a new one.
+
+    With `ViT.set_dynamic_img_size(True)` X may have another image size than the model's: the captured forward then holds
+    the resampling of the position tables, which reads the parameters on every replay like the weight shadows do, so
+    training between two calls is picked up.  `ViT.set_input_size` replaces the two parameters: every call afterwards
+    raises ValueError.
     """
 
     def __init__(self, model, X: Tensor, y: Tensor, consistency_weight: float = 0.1, smoothness_weight: float = 0.1):
         self.model = model
         self.cw, self.sw = consistency_weight, smoothness_weight
+        self._size_epoch = _unwrap(model)._size_epoch
         with _eval_mode(model) as m:   # (refuses a CPU-resident model before anything is changed)
             if X.device.type != "cuda" or y.device != X.device:
                 raise RuntimeError("GraphedEval: inputs must live on the HIP device")
@@ -163,6 +169,11 @@ class GraphedEval:
         ops.eval_metrics(logits, y, self._bacc)
         self._total += add_aux_losses(m.config, self._bacc[0], aux, self.cw, self.sw)
 
+    def _check_model(self) -> None:
+        if _unwrap(self.model)._size_epoch != self._size_epoch:
+            raise ValueError("GraphedEval: ViT.set_input_size replaced the position embeddings these graphs were captured "
+                             "with; build a new GraphedEval")
+
     def _fits(self, X: Tensor, y: Tensor) -> bool:
         return (X.shape == self.X.shape and X.dtype == self.X.dtype and X.device == self.X.device
                 and y.shape == self.y.shape and y.dtype == self.y.dtype and y.device == self.y.device)
@@ -173,6 +184,7 @@ class GraphedEval:
 
     def predict(self, X: Tensor) -> Tensor:
         """evaluate.predict(model, X); a new tensor."""
+        self._check_model()
         if not (X.shape == self.X.shape and X.dtype == self.X.dtype and X.device == self.X.device):
             return predict(self.model, X)
         with _eval_mode(self.model):
@@ -182,6 +194,7 @@ class GraphedEval:
 
     def validate(self, batches: Iterable[Tuple[Tensor, Tensor]]) -> Dict[str, float]:
         """evaluate.validate(model, batches)."""
+        self._check_model()
         with _eval_mode(self.model) as m:
             koh = m.config.use_kohonen
             self._acc.zero_()
@@ -205,6 +218,7 @@ class GraphedEval:
 
     def estimate_loss(self, batches: Iterable[Tuple[Tensor, Tensor]], eval_iters: int) -> float:
         """evaluate.estimate_loss(model, batches, eval_iters) with the weights given to the constructor."""
+        self._check_model()
         if eval_iters < 1:
             raise ValueError("estimate_loss: eval_iters must be at least 1")
         with _eval_mode(self.model) as m:

@@ -23,6 +23,7 @@ everywhere (parity mode, <=1e-5 against the CPU oracle).
 """
 from __future__ import annotations
 
+import dataclasses
 import math
 import os
 from typing import Dict, Optional, Tuple
@@ -30,7 +31,7 @@ from typing import Dict, Optional, Tuple
 import torch
 from torch import nn
 
-from . import ops
+from . import ops, resample
 from ._lib import ATTN_HEADS_MAX_H, BF16, BF16_F32IN, F32, MAX_EMBD
 from .config import ViTConfig
 from .kohonen import CosConsistencyFn, HuberFn, KohonenMap, MapSmoothnessFn
@@ -112,10 +113,19 @@ class _Runtime:
         # (ViT.attach_patch_drop) sets the K it kept for the calls behind its gather and clears it when it returns.  A
         # backward reads the count its own forward saw from ctx.dims, never from here.
         self.tokens = None
+        # side of the token grid of the forward that is running: None = the native one (config.image_size); a forward on
+        # an image of another size (ViT.set_dynamic_img_size) sets it for the whole call and clears it when it returns.
+        # Kept apart from `tokens`: patch dropout needs both, the T it draws from and the K it keeps.
+        self.grid = None
+
+    @property
+    def grid_tokens(self) -> int:
+        """Tokens per sample the running forward embeds (before any patch dropout)."""
+        return self.model.n_tokens if self.grid is None else self.grid * self.grid
 
     @property
     def n_tokens(self) -> int:
-        return self.model.n_tokens if self.tokens is None else self.tokens
+        return self.grid_tokens if self.tokens is None else self.tokens
 
     def y_dtype(self) -> torch.dtype:
         """Storage type of the branch outputs y (att_c_proj / mlp_c_proj / out_proj results, the second LERP input).
@@ -817,7 +827,7 @@ class _EmbedFn(torch.autograd.Function):
         C = cfg.n_embd
         Pl, Pg = cfg.local_patch_size, cfg.global_patch_size
         B = img.shape[0]
-        T = rt.model.n_tokens
+        T = rt.grid_tokens   # (posl, posg hold T rows: the parameters, or their resampled copies at another image size)
         M = B * T
         Kl, Kg = cfg.channels * Pl * Pl, cfg.channels * Pg * Pg
         # Precision policy of the bf16 mode: the two patch embeddings are computed to fp32 accuracy.  They are 0.55 % of
@@ -866,6 +876,48 @@ class _EmbedFn(torch.autograd.Function):
         (gwl, dbl, dposl), (gwg, dbg, dposg) = out
         wls, wgs, ps = ctx.shapes
         return None, None, gwl.reshape(wls), dbl, dposl.reshape(ps), gwg.reshape(wgs), dbg, dposg.reshape(ps)
+
+
+class _PosResampleFn(torch.autograd.Function):
+    """Position tables [1, g*g, C] or [g*g, C] (one or two) resampled to the grid g2 x g2, same rank: nvit_pos_resample_fwd,
+    both tables in one launch; backward its exact adjoint nvit_pos_resample_bwd (resample.py)."""
+
+    @staticmethod
+    def forward(ctx, g, g2, *tables):
+        flat = [t.detach().reshape(g * g, t.shape[-1]).contiguous().float() for t in tables]
+        outs = ops.pos_resample_fwd(flat[0], flat[1] if len(flat) > 1 else None, g, g2)
+        ctx.grids = (g, g2)
+        ctx.shapes = [t.shape for t in tables]
+        return tuple(o.reshape(t.shape[:-2] + (g2 * g2, t.shape[-1])) for o, t in zip(outs, tables))
+
+    @staticmethod
+    def backward(ctx, *douts):
+        g, g2 = ctx.grids
+        flat = [d.reshape(g2 * g2, d.shape[-1]).contiguous().float() for d in douts]
+        grads = ops.pos_resample_bwd(flat[0], flat[1] if len(flat) > 1 else None, g, g2)
+        return (None, None) + tuple(gr.reshape(shp) for gr, shp in zip(grads, ctx.shapes))
+
+
+def resample_pos_embed(pos: Tensor, grid: int) -> Tensor:
+    """A square position-embedding table pos, fp32 [1, g*g, C] or [g*g, C] on the HIP device, resampled to grid x grid
+    tokens: timm's resample_abs_pos_embed without prefix tokens, i.e. F.interpolate(mode="bicubic", antialias=True,
+    align_corners=False) of the [C, g, g] image, computed in fp32 by a HIP kernel.  Same rank as pos; differentiable (the
+    backward is the exact adjoint); grid == g returns pos itself.  C a multiple of 4, at most MAX_EMBD; a grid ratio beyond
+    the kernels' taps per row raises ValueError.  HIP device only."""
+    if not isinstance(pos, Tensor) or pos.dim() not in (2, 3) or (pos.dim() == 3 and pos.shape[0] != 1):
+        raise ValueError("resample_pos_embed: pos must be a [1, g*g, C] or [g*g, C] tensor")
+    if pos.dtype != torch.float32:
+        raise ValueError(f"resample_pos_embed: fp32 table expected, got {pos.dtype}")
+    g = resample.grid_of(pos.shape[-2])
+    resample.check_grids(g, grid)
+    if pos.shape[-1] % 4 or pos.shape[-1] > MAX_EMBD:
+        raise ValueError(f"resample_pos_embed: C must be a multiple of 4, at most {MAX_EMBD} (got {pos.shape[-1]})")
+    if grid == g:
+        return pos
+    resample.host_tables(g, grid)   # (ValueError for a ratio over the tap cap, before any device work)
+    if not pos.is_cuda:
+        raise RuntimeError("nvit_amd.resample_pos_embed runs only on the HIP device (no CPU fallback)")
+    return _PosResampleFn.apply(g, grid, pos)[0]
 
 
 class _TokenDropFn(torch.autograd.Function):
@@ -1206,6 +1258,10 @@ class ViT(nn.Module):
         object.__setattr__(self, "_grad_sink", None)   # set by DataParallel: gradients are produced inside its buckets
         object.__setattr__(self, "drop_path", None)    # attach_drop_path: stochastic depth of the block chain (training only)
         object.__setattr__(self, "patch_drop", None)   # attach_patch_drop: patch dropout behind the embedding (training only)
+        object.__setattr__(self, "_dynamic_img_size", False)   # set_dynamic_img_size: forward takes other image sizes
+        # set_input_size counts here: objects that hold the addresses of the parameters it replaced (GraphedTrainStep,
+        # GraphedEval) compare it with the value they were built at and refuse the model
+        object.__setattr__(self, "_size_epoch", 0)
         object.__setattr__(self.cross_attention, "_owner", self)
         for i, blk in enumerate(self.transformer.h):
             object.__setattr__(blk, "_owner", (self, i))
@@ -1240,6 +1296,81 @@ class ViT(nn.Module):
         _dt_from_precision(precision)
         self.precision = precision
         return self
+
+    def _check_image_size(self, S, what: str) -> int:
+        """The token-grid side of an S x S image, or ValueError: S a multiple of the local patch, larger than the reflect
+        pad of the global patch embedding (what the patch kernels accept)."""
+        cfg = self.config
+        Pl, Pg = cfg.local_patch_size, cfg.global_patch_size
+        if isinstance(S, bool) or not isinstance(S, int) or S < 4 or S % Pl != 0:
+            raise ValueError(f"{what}: the image side must be a positive multiple of local_patch_size = {Pl} (got {S!r})")
+        if (Pg - Pl) // 2 >= S:
+            raise ValueError(f"{what}: the image side {S} must exceed the reflect pad {(Pg - Pl) // 2} of the global patch "
+                             "embedding")
+        return S // Pl
+
+    def set_input_size(self, image_size: int) -> "ViT":
+        """Permanently change the model's image size (timm's set_input_size), to fine-tune at another resolution: both
+        position-embedding tables become NEW nn.Parameters holding the tables resampled to the new token grid
+        (resample_pos_embed: bicubic, antialiased, in fp32 on the device), and config.image_size (a copy of the config;
+        the object handed to the constructor is left alone) and n_tokens follow.  Every other parameter is untouched.
+        Because the two parameters are new objects, anything built on the old ones is stale: build a new optimizer and a
+        new ModelEma (their state is not resampled), a new DataParallel wrapper (its buckets hold the old parameters), and
+        a new GraphedTrainStep / GraphedEval (the old ones raise ValueError when called).  The current size is a no-op that changes no bit and replaces nothing.  The model must be
+        on the HIP device unless the size is the current one.  A checkpoint saved afterwards carries the new size."""
+        g2 = self._check_image_size(image_size, "set_input_size")
+        if image_size == self.config.image_size:
+            return self
+        g = resample.grid_of(self.n_tokens)
+        resample.host_tables(g, g2)   # (ValueError for a ratio over the tap cap, before any device work)
+        posl, posg = self.local_pos_embed, self.global_pos_embed
+        if not posl.is_cuda:
+            raise RuntimeError("ViT.set_input_size resamples the position embeddings on the HIP device: move the model "
+                               "there first (no CPU fallback)")
+        C = self.config.n_embd
+        with torch.no_grad():
+            outl, outg = ops.pos_resample_fwd(posl.detach().reshape(g * g, C).contiguous().float(),
+                                              posg.detach().reshape(g * g, C).contiguous().float(), g, g2)
+        self.local_pos_embed = nn.Parameter(outl.reshape(1, g2 * g2, C), requires_grad=posl.requires_grad)
+        self.global_pos_embed = nn.Parameter(outg.reshape(1, g2 * g2, C), requires_grad=posg.requires_grad)
+        config = dataclasses.replace(self.config, image_size=image_size)
+        for mod in self.modules():
+            if getattr(mod, "config", None) is self.config and mod is not self:
+                mod.config = config
+        self.config = config
+        self.n_tokens = g2 * g2
+        object.__setattr__(self, "_size_epoch", self._size_epoch + 1)
+        return self
+
+    def set_dynamic_img_size(self, flag: bool = True) -> "ViT":
+        """Off (the default): forward takes images of config.image_size only, anything else is a ValueError.  On (timm's
+        dynamic_img_size=True): forward takes [B, ch, S, S] for every S that is a multiple of local_patch_size and larger
+        than the global embedding's reflect pad; the two position tables are resampled to the (S / local_patch_size)^2
+        grid inside the forward (resample_pos_embed), their gradients land on the native-size parameters, and everything
+        behind the embedding runs on the forward's own token count - both model kinds, both attention forms, biases, the
+        Kohonen head, the no_grad route, DropPath and PatchDropout (K from the forward's T).  S == config.image_size
+        launches exactly what it launches with the flag off.  A method, not a config field: ViTConfig mirrors the
+        reference's dataclass.  A resize beyond the kernels' taps per row (about 8x either way) is a ValueError."""
+        object.__setattr__(self, "_dynamic_img_size", bool(flag))
+        return self
+
+    def _running_grid(self, img: Tensor) -> Optional[int]:
+        """None for an image of the native size, else the token-grid side of this forward; ValueError, before any device
+        work, for an image forward cannot take."""
+        if img.dim() != 4:
+            raise ValueError(f"ViT.forward: images [B, channels, S, S] expected, got shape {tuple(img.shape)}")
+        S = img.shape[-1]
+        if img.shape[-2] != S:
+            raise ValueError(f"ViT.forward: square images only, got {img.shape[-2]} x {S}")
+        if S == self.config.image_size:
+            return None
+        if not self._dynamic_img_size:
+            raise ValueError(f"ViT.forward: image side {S}, the model's is {self.config.image_size}; "
+                             "set_dynamic_img_size(True) resamples the position embeddings per forward, "
+                             "set_input_size changes the model")
+        g2 = self._check_image_size(S, "ViT.forward")
+        resample.host_tables(resample.grid_of(self.n_tokens), g2)   # (ValueError for a ratio over the tap cap)
+        return g2
 
     def attach_drop_path(self, drop_path) -> "ViT":
         """Stochastic depth for the block chain of forward(): `drop_path` is a `DropPath` (droppath.py) moved to the
@@ -1302,7 +1433,7 @@ class ViT(nn.Module):
         pd = self.patch_drop
         if pd is None or not self.training or pd.rate <= 0.0 or not torch.is_grad_enabled():
             return None
-        T = self.n_tokens
+        T = self._rt.grid_tokens
         keep, slot = pd.draw(B, T)
         for t, n in ((keep, None), (slot, T)):
             if (not isinstance(t, Tensor) or t.dtype != torch.int32 or t.dim() != 2 or t.shape[0] != B
@@ -1426,15 +1557,17 @@ class ViT(nn.Module):
 
     def _forward(self, img: Tensor, want_recon: bool) -> Tuple[Tensor, Dict[str, Tensor]]:
         """forward(); want_recon False (evaluate.predict) leaves the reconstruction head and aux["reconstruction"] out."""
+        grid = self._running_grid(img)
         if self.training:
             self.step += 1
         self._prepare(img.device)
         rt = self._rt
-        rt.tokens = None
+        rt.tokens, rt.grid = None, grid
         try:
             return self._forward_body(img, want_recon)
         finally:
-            rt.tokens = None   # a dropping forward's K is not left behind for stand-alone block calls
+            # a dropping forward's K and another image size's grid are not left behind for stand-alone block calls
+            rt.tokens, rt.grid = None, None
 
     def _forward_body(self, img: Tensor, want_recon: bool) -> Tuple[Tensor, Dict[str, Tensor]]:
         rt = self._rt
@@ -1447,11 +1580,14 @@ class ViT(nn.Module):
                                "differentiate up to an intermediate block input")
         cfg = self.config
         B = img.shape[0]
-        T, C = self.n_tokens, cfg.n_embd
+        T, C = rt.grid_tokens, cfg.n_embd
         img = img.contiguous().float()
+        posl, posg = self.local_pos_embed, self.global_pos_embed
+        if rt.grid is not None:   # another image size: the tables at this forward's grid, differentiable
+            posl, posg = _PosResampleFn.apply(resample.grid_of(self.n_tokens), rt.grid, posl, posg)
         loc, glo, loc_lo, glo_lo = _EmbedFn.apply(img, rt, self.local_patch_embed.weight, self.local_patch_embed.bias,
-                                                  self.local_pos_embed, self.global_patch_embed[1].weight,
-                                                  self.global_patch_embed[1].bias, self.global_pos_embed)
+                                                  posl, self.global_patch_embed[1].weight,
+                                                  self.global_patch_embed[1].bias, posg)
         if loc_lo.numel() == 0:   # fp32 mode (or an embedding width the twin store does not cover): no bf16 copies
             loc_lo = glo_lo = None
         drawn = self._draw_tokens(B)

@@ -12,7 +12,7 @@ from typing import Optional, Tuple
 
 import torch
 
-from . import _lib
+from . import _lib, resample
 from ._lib import BF16, F32, check
 
 Tensor = torch.Tensor
@@ -713,6 +713,50 @@ def rows_scatter(d0: Tensor, d1: Optional[Tensor], slot: Tensor, B: int, K: int)
     g1 = torch.empty_like(g0) if d1 is not None else None
     check(_lib.load().nvit_rows_scatter(_p(d0), _p(d1), _p(slot), _p(g0), _p(g1), B, T, K, Cc, _s()), "nvit_rows_scatter")
     return g0, g1
+
+
+def _pos_resample(name: str, fn, s0: Tensor, s1: Optional[Tensor], n_src: int, n_dst: int, g: int, g2: int, table: Tensor):
+    """Operands of pos_resample_fwd / bwd: fp32 [n_src^2, C] tables, C a multiple of 4 up to MAX_EMBD, and the packed tap
+    table int32 [n_dst, 2 + MAX_TAPS] on their device.  One launch for both tables."""
+    if not isinstance(s0, Tensor) or s0.dim() != 2 or s0.shape[1] % 4 or not 0 < s0.shape[1] <= _lib.MAX_EMBD:
+        raise ValueError(f"{name}: [rows, C] operands with C a multiple of 4, at most {_lib.MAX_EMBD}, expected")
+    _chk_rows((n_src * n_src, s0.shape[1]), f32=(s0, s1), name=name)
+    if s1 is not None and (s1.dim() != 2 or s1.device != s0.device):
+        raise ValueError(f"{name}: the second table must be a [rows, C] tensor on {s0.device}")
+    if (not isinstance(table, Tensor) or table.dtype != torch.int32 or tuple(table.shape) != (n_dst, resample.ROW)
+            or not table.is_contiguous() or table.device != s0.device):
+        raise ValueError(f"{name}: the tap table must be a contiguous int32 [{n_dst}, {resample.ROW}] tensor on {s0.device}")
+    d0 = torch.empty((n_dst * n_dst, s0.shape[1]), device=s0.device, dtype=torch.float32)
+    d1 = torch.empty_like(d0) if s1 is not None else None
+    check(fn(_p(s0), _p(s1), _p(table), _p(d0), _p(d1), g, g2, s0.shape[1], _s()), "nvit_" + name)
+    return d0, d1
+
+
+def pos_resample_fwd(p0: Tensor, p1: Optional[Tensor], g: int, g2: int):
+    """Position tables p fp32 [g*g, C] resampled to the grid g2 x g2 (nvit_pos_resample_fwd): what F.interpolate(...,
+    mode="bicubic", align_corners=False, antialias=True) computes on the [C, g, g] image, in fp32.  p1 None: one table,
+    else both in one launch.  -> (out0, out1) fp32 [g2*g2, C], out1 None without p1.  Equal grids launch nothing and
+    return the operands themselves.  ValueError for a grid ratio beyond the kernels' taps per row (resample.MAX_TAPS).
+    The first call for (g, g2) on a device sends the tap tables: not under graph capture."""
+    _chk_dev(p0)
+    resample.check_grids(g, g2)
+    if g == g2:
+        _chk_rows((g * g, p0.shape[1]), f32=(p0, p1), name="pos_resample_fwd")
+        return p0, p1
+    taps, _ = resample.tap_tables(g, g2, p0.device)
+    return _pos_resample("pos_resample_fwd", _lib.load().nvit_pos_resample_fwd, p0, p1, g, g2, g, g2, taps)
+
+
+def pos_resample_bwd(d0: Tensor, d1: Optional[Tensor], g: int, g2: int):
+    """The exact adjoint of pos_resample_fwd (nvit_pos_resample_bwd): d fp32 [g2*g2, C] -> gradients fp32 [g*g, C], every
+    element written once in a fixed order.  Equal grids return the operands themselves."""
+    _chk_dev(d0)
+    resample.check_grids(g, g2)
+    if g == g2:
+        _chk_rows((g * g, d0.shape[1]), f32=(d0, d1), name="pos_resample_bwd")
+        return d0, d1
+    _, taps_t = resample.tap_tables(g, g2, d0.device)
+    return _pos_resample("pos_resample_bwd", _lib.load().nvit_pos_resample_bwd, d0, d1, g2, g, g, g2, taps_t)
 
 
 def normalize_images(x: Tensor, mean: float = 0.5, std: float = 0.5) -> Tensor:

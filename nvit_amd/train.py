@@ -303,6 +303,11 @@ class GraphedTrainStep:
     A `PatchDropout` (`ViT.attach_patch_drop`) likewise: its draw and the token gather are captured with the forward, every
     replay keeps other tokens, accumulation_steps = N is N draws, and a call with another PatchDropout attached than at
     capture time raises ValueError.  Its draw allocates, like every first call at a new shape: the warm-up steps cover it.
+
+    With `ViT.set_dynamic_img_size(True)` X may have another image size than the model's: the resampling of the two
+    position tables and its backward are captured with the step (their tap tables are sent to the device by the warm-up
+    steps; a capture cannot).  The graph is bound to that size, as to the batch size.  After `ViT.set_input_size` changed
+    the model, a call raises ValueError: the graph and the optimizer hold the parameters it replaced.
     """
 
     def __init__(self, model, optimizer, X: torch.Tensor, y: torch.Tensor, grad_clip: float = 1.0, warmup: int = 3,
@@ -324,6 +329,7 @@ class GraphedTrainStep:
         self.ema = optimizer.ema   # the ModelEma (or none) whose update the warm-up steps run and the capture records
         self.drop_path = m.drop_path   # the DropPath (or none) whose draw the captured forwards contain
         self.patch_drop = m.patch_drop   # the PatchDropout (or none), likewise
+        self._size_epoch = m._size_epoch   # ViT.set_input_size replaces parameters whose addresses the graph holds
         self.accumulation_steps, self.skip_nonfinite = accumulation_steps, bool(skip_nonfinite)
         N = accumulation_steps
         self.X, self.y = X.clone(), y.clone()
@@ -424,6 +430,9 @@ class GraphedTrainStep:
             raise ValueError("GraphedTrainStep: this graph was captured with another DropPath (or none)")
         if _unwrap(self.model).patch_drop is not self.patch_drop:
             raise ValueError("GraphedTrainStep: this graph was captured with another PatchDropout (or none)")
+        if _unwrap(self.model)._size_epoch != self._size_epoch:
+            raise ValueError("GraphedTrainStep: ViT.set_input_size replaced the position embeddings this graph was "
+                             "captured with; build a new optimizer and a new GraphedTrainStep")
         self.X.copy_(X, non_blocking=True)
         self.y.copy_(y, non_blocking=True)
         self._advance_som()
