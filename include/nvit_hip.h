@@ -437,6 +437,38 @@ int nvit_augment_draw(const int* policy, int P, uint64_t seed, int64_t* step, in
  * workspace of ws_bytes >= 2 * B * round_up(H*W*C, 256) bytes. */
 int nvit_augment_apply(const void* in, const int* params, float* out_f32, void* out_u8, void* ws, int64_t ws_bytes, int B,
                        int H, int W, int C, float mean, float std_, void* stream);
+/* On-device RandAugment (tests/randaug_ref.py): timm's rand-m9-mstd0.5-inc1 family in AutoAugment's place.
+ * Parameter table int32 [B,num_layers,NVIT_RA_ROW], per row: [0] op id (0 = layer off; 1..14 AutoAugment's ids,
+ * NVIT_RA_SOLARIZE_ADD the one new op), [1] filter of a geometric op (NVIT_RA_BILINEAR / NVIT_RA_BICUBIC), then for the
+ * geometric ops (ids 1..5) six fp64 output-to-input coefficients a0..a5 in ints 2..13 (8-byte aligned), for every other
+ * op its argument in int 2 (fp32 bits of an enhancement factor, bits kept, threshold, or the amount added); the rest 0.
+ * nvit_randaug_draw: one Philox4x32-10 call per (image, layer), counter = (first_index + b, *step), key = seed with (a
+ * domain constant + layer) xor-ed into its high word: (r0 * NVIT_RA_NCHOICES) >> 32 picks the op in timm's list order,
+ * (r1 >> 8) * 2^-24 < prob switches it on, r2 >> 8 is the magnitude's 24-bit uniform, bit 0 of r3 the sign (1 negates),
+ * bit 1 of r3 the filter when interp == NVIT_RA_RANDOM.  Magnitude m: `magnitude` (mstd == 0), magnitude * u (mstd
+ * infinite), else magnitude + mstd * z with z interpolated from q, device fp64 [NVIT_ERASE_KNOTS + 1] normal quantiles;
+ * then clamped to [0, mmax].  The level maps are timm's, in fp64.  Rotate's cos / sin come from rot, device fp64
+ * [2, NVIT_RA_ROT_KNOTS + 1] (cos, then sin) over [0, 3 * mmax] degrees, linearly between knots: no transcendental runs
+ * on the device.  *step is a device int64 that the kernel reads and then advances by one, as nvit_augment_draw does. */
+#define NVIT_RA_ROW 16
+#define NVIT_RA_NCHOICES 15
+#define NVIT_RA_SOLARIZE_ADD 15
+#define NVIT_RA_NOPS 16 /* op ids known to nvit_randaug_apply: 0..15 */
+#define NVIT_RA_MAX_LAYERS 4
+#define NVIT_RA_ROT_KNOTS 1024
+#define NVIT_RA_BILINEAR 0
+#define NVIT_RA_BICUBIC 1
+#define NVIT_RA_RANDOM 2
+int nvit_randaug_draw(uint64_t seed, int64_t* step, int64_t first_index, const double* q, const double* rot, double magnitude,
+                      double mstd, double mmax, int increasing, float prob, int interp, double translate_pct, int* params,
+                      int B, int num_layers, int H, int W, void* stream);
+/* nvit_randaug_apply: in uint8 [B,H,W,C], C in {1,3}; per image the num_layers ops of params in sequence, each on the
+ * complete result of the one before.  Geometric ops are Pillow's ImagingGenericTransform in fp64 with the BILINEAR or
+ * BICUBIC filter; a pixel whose source lies outside the image takes fill0..fill2 (one value per channel).  The other ops
+ * are nvit_augment_apply's.  Outputs and workspace as for nvit_augment_apply. */
+int nvit_randaug_apply(const void* in, const int* params, float* out_f32, void* out_u8, void* ws, int64_t ws_bytes, int B,
+                       int H, int W, int C, int num_layers, int fill0, int fill1, int fill2, float mean, float std_,
+                       void* stream);
 /* On-device Mixup / CutMix (tests/mix_ref.py): rows p and B-1-p of the batch form pair p (the middle row of
  * an odd batch is its own partner and stays unmixed).
  * nvit_mix_draw: one Philox4x32-10 call per pair, key = seed with a domain constant xor-ed into its high word, counter =

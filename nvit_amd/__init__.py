@@ -16,6 +16,9 @@ def __getattr__(name):
     if name in ("AutoAugment", "AugmentedBatch"):
         from . import augment
         return getattr(augment, name)
+    if name == "RandAugment":
+        from . import randaug
+        return randaug.RandAugment
     if name in ("Mixup", "MixedBatch", "MixedTargets"):
         from . import mix
         return getattr(mix, name)

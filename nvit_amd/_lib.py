@@ -106,6 +106,9 @@ SIGNATURES = {
     "nvit_normalize_images": [_vp, _i, _vp, _i, _i, _i, _i, _f, _f, _vp],
     "nvit_augment_draw": [_vp, _i, C.c_uint64, _vp, _i64, _vp, _vp, _i, _vp],
     "nvit_augment_apply": [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _f, _f, _vp],
+    "nvit_randaug_draw": [C.c_uint64, _vp, _i64, _vp, _vp, C.c_double, C.c_double, C.c_double, _i, _f, _i, C.c_double, _vp,
+                          _i, _i, _i, _i, _vp],
+    "nvit_randaug_apply": [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _vp],
     "nvit_mix_draw": [C.c_uint64, _vp, _i64, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
     "nvit_mix_apply": [_vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "nvit_droppath_draw": [C.c_uint64, _vp, _i64, _vp, _i, _vp, _i, _i, _vp],

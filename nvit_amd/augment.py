@@ -221,8 +221,9 @@ def _check_images(u8: Tensor):
 
 
 class AugmentedBatch:
-    """A uint8 [B,H,W,C] batch together with the AutoAugment that turns it into the model's input: what
-    `AutoAugment.batch(u8)` returns and `train_step` / `GraphedTrainStep` accept in place of X.  u8: the tensor, or a
+    """A uint8 [B,H,W,C] batch together with the AutoAugment (or the RandAugment of randaug.py: anything whose call
+    turns such a batch into fp32 [B,C,H,W]) that makes it the model's input: what `AutoAugment.batch(u8)` /
+    `RandAugment.batch(u8)` return and `train_step` / `GraphedTrainStep` accept in place of X.  u8: the tensor, or a
     `RandomResizedCrop.batch(u8)` (crop.py) whose crops are then what the policies see."""
 
     def __init__(self, augment: "AutoAugment", u8):

@@ -4,7 +4,7 @@ from-scratch recipe (AutoAugment in augment.py is the augmentation half, Mixup /
     RandomResizedCrop(224, interpolation="bicubic") -> flip -> AutoAugment -> normalize -> RandomErasing -> Mixup / CutMix
     mix.batch(erase.batch(aug.batch(rrc.batch(u8))))
 
-A stored uint8 [B,Hs,Ws,C] batch becomes the mixed fp32 model input with no host work and no synchronisation, so the
+(`aug` an `AutoAugment`, or the recipes' own `RandAugment` of randaug.py, which has the same interface.)  A stored uint8 [B,Hs,Ws,C] batch becomes the mixed fp32 model input with no host work and no synchronisation, so the
 whole chain sits inside a captured train step.  Semantics (tests/crop_ref.py restates them in numpy):
 
 RandomResizedCrop: image b is `PIL.Image.crop(box).resize((size, size), BILINEAR | BICUBIC)`, bit for bit, then mirrored
