@@ -151,6 +151,26 @@ int nvit_adamw_tick_guarded(float* hyper, double beta1, double beta2, const floa
 int nvit_adamw_renorm_guarded(const int64_t* table, int n, int total_items, int max_slab_rows, float beta1, float beta2,
                               float eps, const float* partial, int npart, float max_norm, float* gnorm_out,
                               const float* hyper, const float* skip_state, void* stream);
+/* Learning-rate schedule on the device (LRSchedule): one workgroup of NVIT_LR_SCHEDULE_THREADS threads, once per
+ * optimizer step, after the table is in place and before nvit_grad_sqnorm / nvit_adamw_renorm*.  With s = step[0] (an
+ * int64 on the device, optimizer steps attempted so far), W = warmup_iters, D = decay_iters, all converted to double:
+ *        s <  W : L = warmup_init + (lr - warmup_init) * s / W
+ *        else, kind NVIT_LR_CONSTANT: L = lr (D is ignored)
+ *        s >  D : L = min_lr
+ *        else   : r = (s - W) / (D - W);  NVIT_LR_COSINE: L = min_lr + (0.5 * (1.0 + cos(pi * r))) * (lr - min_lr),
+ *                 NVIT_LR_LINEAR: L = lr + (min_lr - lr) * r
+ *        in fp64, in this operation order, without fused multiply-adds (the trainer's get_lr, train.py:1025-1035, for
+ *        kind NVIT_LR_COSINE and warmup_init = 0).  Then step[0] = s + 1, last_lr[0] = (float)L, last_lr64[0] = L, and row
+ *        i of the table (the one of nvit_adamw_renorm; n rows, n == 0 with table == NULL only advances the counter)
+ *        receives (float)(L * (double)lr_scale[i]) in the lr half of its last column; its weight_decay half and all
+ *        other columns stay as they are.  Needs W >= 0, D > W unless the kind is constant, finite rates >= 0. */
+#define NVIT_LR_COSINE 0
+#define NVIT_LR_LINEAR 1
+#define NVIT_LR_CONSTANT 2
+#define NVIT_LR_SCHEDULE_THREADS 256
+int nvit_lr_schedule(int64_t* table, int n, const float* lr_scale, int64_t* step, int kind, double lr, double min_lr,
+                     double warmup_init, int64_t warmup_iters, int64_t decay_iters, float* last_lr, double* last_lr64,
+                     void* stream);
 
 /* Exponential moving average of the weights (ModelEma), two launches per optimizer step: nvit_ema_tick, nvit_ema_update.
  * state: 4 floats on the device, zeroed by the caller once: {t = updates applied so far, omd = 1 - d of the update about

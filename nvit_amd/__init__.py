@@ -34,6 +34,9 @@ def __getattr__(name):
     if name == "PatchDropout":
         from . import patchdrop
         return patchdrop.PatchDropout
+    if name in ("LRSchedule", "layer_decay_groups"):
+        from . import schedule
+        return getattr(schedule, name)
     if name == "FusedAdamW":
         from . import optim
         return optim.FusedAdamW

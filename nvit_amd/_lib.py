@@ -62,6 +62,7 @@ SIGNATURES = {
     "nvit_adamw_tick": [_vp, C.c_double, C.c_double, _vp],
     "nvit_adamw_tick_guarded": [_vp, C.c_double, C.c_double, _vp, _i, _vp, _vp],
     "nvit_adamw_renorm_guarded": [_vp, _i, _i, _i, _f, _f, _f, _vp, _i, _f, _vp, _vp, _vp, _vp],
+    "nvit_lr_schedule": [_vp, _i, _vp, _vp, _i, C.c_double, C.c_double, C.c_double, _i64, _i64, _vp, _vp, _vp],
     "nvit_ema_tick": [_vp, C.c_double, _i, _vp, _vp],
     "nvit_ema_update": [_vp, _i, _i, _vp, _vp],
     "nvit_set_gemm_sched": [_i],

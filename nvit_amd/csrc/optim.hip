@@ -455,3 +455,67 @@ extern "C" int nvit_adamw_renorm_guarded(const int64_t* table, int n, int total_
   return adamw_renorm_launch(table, n, total_items, max_slab_rows, beta1, beta2, eps, 0.0, 0.0, partial, npart, max_norm,
                              gnorm_out, hyper, skip_state, stream);
 }
+
+// ---- learning-rate schedule (LRSchedule) --------------------------------------------------------------------------------
+// One workgroup per optimizer step, ahead of nvit_grad_sqnorm / nvit_adamw_renorm*: every thread reads the device step
+// counter s and evaluates L(s) in fp64, thread 0 stores s + 1 (after a barrier: no thread may still have the load ahead
+// of it), and the threads walk the table rows, storing (float)(L * lr_scale[i]) into the lr half of the row's last column.
+// The weight-decay half and every other column are not touched.  L(s) is the reference trainer's get_lr
+// (train.py:1025-1035) with its operation order kept, since the host restates it bit for bit
+// (schedule.py): nothing from here to the end of the file contracts a multiply into an add.
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int LRS_THREADS = NVIT_LR_SCHEDULE_THREADS;
+
+__global__ __launch_bounds__(LRS_THREADS) void lr_schedule_kernel(int64_t* table, int n, const float* lr_scale,
+                                                                  int64_t* step, int kind, double lr, double min_lr,
+                                                                  double warmup_init, int64_t W, int64_t D,
+                                                                  float* last_lr, double* last_lr64) {
+  const int64_t s = step[0];
+  double L;
+  if (s < W) {
+    L = warmup_init + (lr - warmup_init) * (double)s / (double)W;
+  } else if (kind == NVIT_LR_CONSTANT) {
+    L = lr;
+  } else if (s > D) {
+    L = min_lr;
+  } else {
+    const double r = (double)(s - W) / (double)(D - W);
+    if (kind == NVIT_LR_COSINE)
+      L = min_lr + (0.5 * (1.0 + cos(3.141592653589793 * r))) * (lr - min_lr);
+    else
+      L = lr + (min_lr - lr) * r;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    step[0] = s + 1;
+    last_lr[0] = (float)L;
+    last_lr64[0] = L;
+  }
+  for (int i = threadIdx.x; i < n; i += LRS_THREADS) {
+    const float v = (float)(L * (double)lr_scale[i]);
+    // the low word of the little-endian int64 {f32bits(lr) | f32bits(weight_decay) << 32}
+    reinterpret_cast<float*>(table + (size_t)i * OPT_COLS + (OPT_COLS - 1))[0] = v;
+  }
+}
+
+}  // namespace
+
+extern "C" int nvit_lr_schedule(int64_t* table, int n, const float* lr_scale, int64_t* step, int kind, double lr,
+                                double min_lr, double warmup_init, int64_t warmup_iters, int64_t decay_iters,
+                                float* last_lr, double* last_lr64, void* stream) {
+  NVIT_REQUIRE(step && last_lr && last_lr64 && n >= 0 && (n == 0 || (table && lr_scale)), "lr_schedule: bad arguments");
+  NVIT_REQUIRE(kind == NVIT_LR_COSINE || kind == NVIT_LR_LINEAR || kind == NVIT_LR_CONSTANT, "lr_schedule: unknown kind %d",
+               kind);
+  NVIT_REQUIRE(warmup_iters >= 0 && (kind == NVIT_LR_CONSTANT || decay_iters > warmup_iters),
+               "lr_schedule: needs warmup_iters >= 0 and decay_iters > warmup_iters");
+  NVIT_REQUIRE(lr >= 0.0 && min_lr >= 0.0 && warmup_init >= 0.0 && lr <= 1.79e308 && min_lr <= 1.79e308 &&
+               warmup_init <= 1.79e308, "lr_schedule: rates must be finite and >= 0");
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(lr_schedule_kernel, dim3(1), dim3(LRS_THREADS), 0, s, table, n, lr_scale, step, kind, lr, min_lr,
+                     warmup_init, warmup_iters, decay_iters, last_lr, last_lr64);
+  NVIT_CHECK_LAUNCH("lr_schedule");
+  return NVIT_OK;
+}

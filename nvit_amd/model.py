@@ -1464,12 +1464,19 @@ class ViT(nn.Module):
 
     # ---- reference API
     def configure_optimizers(self, weight_decay: float, learning_rate: float, betas: Tuple[float, float],
-                             device_type: str) -> torch.optim.AdamW:
+                             device_type: str, *, layer_decay: Optional[float] = None) -> torch.optim.AdamW:
         """Same parameter groups as reference model.py:369-385 (three with sz in nViT mode, two without).  On the HIP
         device the optimizer is FusedAdamW (torch.optim.AdamW subclass, same state_dict); the torch class is only
-        returned for a CPU-resident model, which cannot run forward anyway (no CPU path)."""
+        returned for a CPU-resident model, which cannot run forward anyway (no CPU path).
+
+        layer_decay (None: exactly the groups above): layer-wise lr decay, the groups of
+        `schedule.layer_decay_groups` - the same split, further split by depth, each group with lr_scale = layer_decay **
+        (n_layer + 2 - depth) and lr = learning_rate * lr_scale; an attached LRSchedule applies lr_scale at every step."""
         pd = {n: p for n, p in self.named_parameters() if p.requires_grad}
-        if self.config.use_nvit:
+        if layer_decay is not None:
+            from .schedule import layer_decay_groups
+            groups = layer_decay_groups(self, weight_decay, learning_rate, layer_decay)
+        elif self.config.use_nvit:
             groups = [
                 {"params": [p for n, p in pd.items() if "sz" not in n and p.dim() >= 2], "weight_decay": weight_decay},
                 {"params": [p for n, p in pd.items() if "sz" not in n and p.dim() < 2], "weight_decay": 0.0},

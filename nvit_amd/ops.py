@@ -1103,6 +1103,25 @@ def renorm_weights(table: Tensor, total_items: int) -> None:
     check(_lib.load().nvit_renorm_weights(_p(table), table.shape[0], total_items, _s()), "nvit_renorm_weights")
 
 
+def lr_schedule(table: Optional[Tensor], n: int, lr_scale: Optional[Tensor], step: Tensor, kind: int, lr: float,
+                min_lr: float, warmup_init: float, warmup_iters: int, decay_iters: int, last_lr: Tensor,
+                last_lr64: Tensor) -> None:
+    """One step of a learning-rate schedule (nvit_lr_schedule): L(step[0]) in fp64 -> last_lr / last_lr64, (float)(L *
+    lr_scale[i]) into the lr half of the last column of table row i < n, step[0] += 1.  n == 0: no table is touched."""
+    _chk_dev(table, lr_scale, step, last_lr, last_lr64)
+    if step.dtype != torch.int64 or last_lr.dtype != torch.float32 or last_lr64.dtype != torch.float64:
+        raise ValueError("lr_schedule: step int64[1], last_lr fp32[1], last_lr64 fp64[1]")
+    if n:
+        if table.dtype != torch.int64 or lr_scale.dtype != torch.float32 or not table.is_contiguous() \
+                or not lr_scale.is_contiguous() or table.numel() < n * _lib.const("OPT_TABLE_COLS") or lr_scale.numel() < n:
+            raise ValueError("lr_schedule: table must be contiguous int64 [n, cols] and lr_scale contiguous fp32 [n]")
+        if table.device != step.device or lr_scale.device != step.device:
+            raise RuntimeError("lr_schedule: the table lives on another device than the schedule")
+    check(_lib.load().nvit_lr_schedule(_p(table) if n else None, n, _p(lr_scale) if n else None, _p(step), kind, lr, min_lr,
+                                       warmup_init, warmup_iters, decay_iters, _p(last_lr), _p(last_lr64), _s()),
+          "nvit_lr_schedule")
+
+
 def shadow_table(entries, device) -> Tuple[Tensor, int]:
     """entries: list of (src fp32 2-D view, dst|None, dst_ld, dst_cols, dstT|None, dstT_ld, dstT_cols, perm)."""
     rows_, first = [], 0

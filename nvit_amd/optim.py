@@ -12,7 +12,8 @@ in two HIP launches (`nvit_grad_sqnorm`, `nvit_adamw_renorm`) over a device-side
 p, g, m, v once and writing p, m, v once; with `skip_nonfinite=True` a guarded tick between them decides, on the device,
 whether the step is applied at all (GradScaler.step of the reference, train.py:930-942).  Plain `step()` (no clip, no renorm) uses the same kernel, so code that
 calls `optimizer.step()` followed by `normalize_matrices(model)` gives identical weights.  There is no torch
-fallback: the parameters must live on the HIP device.
+fallback: the parameters must live on the HIP device.  With an `LRSchedule` attached (`attach_schedule`, schedule.py) one
+more launch ahead of them (`nvit_lr_schedule`) writes the step's learning rate into the table, instead of the host.
 
 One step counter serves all parameters (it lives on the device so that a captured step replays correctly).  torch
 keeps one per parameter; the two agree as long as every parameter that is ever updated receives a gradient from the
@@ -91,6 +92,8 @@ class FusedAdamW(torch.optim.AdamW):
         self._skip_state = None   # device float[2], see skip_state
         self._guarded = False     # a skip_nonfinite step has run: only the device knows how many steps were applied
         self._ema = None          # attach_ema: a ModelEma that every step updates
+        self._schedule = None     # attach_schedule: an LRSchedule whose launch writes every step's lr into the table
+        self._scale_staging = None   # pinned host image of the rows' lr_scale (a captured step under a schedule)
 
     # ------------------------------------------------------------------ state
     def _ensure_state(self, p: torch.Tensor) -> Dict:
@@ -107,6 +110,7 @@ class FusedAdamW(torch.optim.AdamW):
         key = []
         hypers: List[int] = []   # per row: lr | weight_decay bits (the last column of the table)
         groups: List[int] = []   # per row: index of its param group
+        scales: List[float] = []  # per row: its group's lr_scale (layer-wise lr decay; read by an attached schedule)
         first_item = first_chunk = 0
         max_slab_rows = 0
         beta_eps = None
@@ -140,13 +144,16 @@ class FusedAdamW(torch.optim.AdamW):
                 key.append((p.data_ptr(), g.data_ptr(), kind))
                 hypers.append(hyper)
                 groups.append(gi)
+                scales.append(float(group.get("lr_scale", 1.0)))
                 first_item += items
                 first_chunk += chunks
         key = tuple(key)
         if self._cache is not None and self._cache["key"] == key and self._cache["hypers"] != hypers:
             # only lr / weight_decay moved (the reference trainer rewrites lr every iteration): update the hyper column in
-            # place instead of rebuilding table, workspaces and a pinned image
-            self._write_hyper_column(hypers)
+            # place instead of rebuilding table, workspaces and a pinned image.  Under an attached schedule the lr half
+            # belongs to the device (group["lr"] is the peak rate, kept for the record): only a weight_decay counts.
+            if self._schedule is None or [h >> 32 for h in self._cache["hypers"]] != [h >> 32 for h in hypers]:
+                self._write_hyper_column(hypers)
         if self._cache is None or self._cache["key"] != key:
             if not rows:
                 return None
@@ -164,16 +171,25 @@ class FusedAdamW(torch.optim.AdamW):
                 self._staging[:n].copy_(host)
                 table.copy_(self._staging[:n], non_blocking=True)
                 staged = True
+                if self._schedule is not None:   # the rows' lr_scale follows the table's rule
+                    if self._scale_staging is None or self._scale_staging.shape[0] < n:
+                        raise RuntimeError("FusedAdamW: call reserve_staging() before capturing a step")
+                    self._scale_staging[:n].copy_(torch.tensor(scales, dtype=torch.float32))
+                    lr_scale = torch.empty(n, dtype=torch.float32, device=dev)
+                    lr_scale.copy_(self._scale_staging[:n], non_blocking=True)
             else:
                 # eager: a fresh pinned image per rebuild (the host allocator keeps it alive until the async copy has
                 # run; re-using one buffer would race with copies still queued behind a GPU that runs steps behind)
                 table.copy_(host.pin_memory(), non_blocking=True)
                 staged = False
+                if self._schedule is not None:
+                    lr_scale = torch.tensor(scales, dtype=torch.float32).pin_memory().to(dev, non_blocking=True)
             self._cache = {
                 "key": key,
                 "hypers": hypers,
                 "groups": groups,
                 "table": table,
+                "lr_scale": lr_scale if self._schedule is not None else None,   # fp32 [n], built with the table
                 "n": len(rows), "items": first_item, "chunks": first_chunk, "slab": max_slab_rows,
                 "partial": torch.empty(_NPART, device=dev, dtype=torch.float32),
                 "gnorm": torch.empty(1, device=dev, dtype=torch.float32),
@@ -209,6 +225,10 @@ class FusedAdamW(torch.optim.AdamW):
             self._t = self._loaded_step()
             self._hyper = torch.tensor([float(self._t), 0.0, 0.0], dtype=torch.float32).pin_memory().to(
                 dev, non_blocking=True)
+        if self._schedule is not None:
+            # this step's lr into the table, ahead of everything that reads it; also when skip_nonfinite then leaves the
+            # step out (the reference's iter_num advances on a skipped step too)
+            self._schedule.apply(c["table"], c["n"], c["lr_scale"])
         # the step counter lives on the device (bias corrections are computed there), so a captured step replays
         # correctly; the host mirror only feeds state_dict()
         clip = grad_clip is not None and grad_clip > 0.0
@@ -255,6 +275,34 @@ class FusedAdamW(torch.optim.AdamW):
     def ema(self):
         """The attached ModelEma, or None."""
         return self._ema
+
+    # ------------------------------------------------------------------ learning-rate schedule
+    def attach_schedule(self, schedule) -> None:
+        """schedule: an `LRSchedule` on the parameters' device, or None to detach.  Every step (step_fused, step()) then
+        starts with one more launch (nvit_lr_schedule) that writes lr = L(s) * lr_scale into every row of the device table
+        and advances the schedule's counter: one optimizer step is one schedule step whatever accumulation_steps is, and a
+        step that skip_nonfinite leaves out is one too.  lr_scale is the row's `group.get("lr_scale", 1.0)`
+        (`layer_decay_groups`).  While a schedule is attached the host pushes no lr: `group["lr"]` keeps the value it was
+        given (the peak rate) and changing it does nothing; `current_lr()` reads the rate in use.  Attach before a
+        GraphedTrainStep is built, so that the captured step holds the launch.  Attaching or detaching rebuilds the table
+        on the next step, from the groups' lr."""
+        if schedule is not None and not (callable(getattr(schedule, "apply", None)) and hasattr(schedule, "lr_at")):
+            raise TypeError("attach_schedule: an LRSchedule (or None) expected")
+        if schedule is not self._schedule:
+            self._cache = None
+        self._schedule = schedule
+
+    @property
+    def schedule(self):
+        """The attached LRSchedule, or None."""
+        return self._schedule
+
+    def current_lr(self) -> float:
+        """The L(s) of the last step under the attached schedule, before any lr_scale (one host synchronisation); 0.0
+        before the first step.  `schedule.last_lr` is the same value as a device tensor."""
+        if self._schedule is None:
+            raise RuntimeError("FusedAdamW.current_lr: no schedule attached (the groups' lr is the rate in use)")
+        return float(self._schedule.last_lr.item())
 
     # ------------------------------------------------------------------ skipped steps
     @property
@@ -319,6 +367,8 @@ class FusedAdamW(torch.optim.AdamW):
         n = sum(len(g["params"]) for g in self.param_groups)
         if self._staging is None or self._staging.shape[0] < n:
             self._staging = torch.empty((max(n, 64), _TABLE_COLS), dtype=torch.int64).pin_memory()
+        if self._schedule is not None and (self._scale_staging is None or self._scale_staging.shape[0] < n):
+            self._scale_staging = torch.empty(max(n, 64), dtype=torch.float32).pin_memory()
 
     def note_replay(self, n: int = 1) -> None:
         """A captured step was replayed n times (the device counter advanced; keep the host mirror in sync)."""

@@ -227,6 +227,10 @@ def train_step(model, optimizer, X: torch.Tensor, y: torch.Tensor, grad_clip: fl
     gate table, so with accumulation_steps = N its counter advances by N, each micro-batch drawing for its own rows.  The
     same holds for a `PatchDropout` (`ViT.attach_patch_drop`): one draw of kept tokens per training forward.
 
+    An `LRSchedule` attached to the optimizer (`FusedAdamW.attach_schedule`, schedule.py) needs nothing here either: the
+    fused step starts with its launch, which writes this step's lr into the optimizer's device table and advances the
+    schedule's device counter - once per call whatever accumulation_steps is, also when skip_nonfinite leaves the update out.
+
     Wrong accumulation_steps (no int, < 1, no divisor of the batch) or skip_nonfinite with another optimizer raise
     ValueError before any device work."""
     _check_step_args(optimizer, X, accumulation_steps, skip_nonfinite)
@@ -304,6 +308,14 @@ class GraphedTrainStep:
     replay keeps other tokens, accumulation_steps = N is N draws, and a call with another PatchDropout attached than at
     capture time raises ValueError.  Its draw allocates, like every first call at a new shape: the warm-up steps cover it.
 
+    An `LRSchedule` (schedule.py) attached to the optimizer before this object is built is part of the captured step: its
+    launch follows the captured table copy and precedes the optimizer's, its counter is a device int64 the launch
+    advances, and every replay steps at the next lr with no host code in between.  The warm-up steps are schedule steps, as
+    they are optimizer steps; the capture pass is not (it executes nothing).  One replay is one schedule step whatever
+    accumulation_steps is, also when skip_nonfinite leaves the update out.  A call with another schedule attached than at
+    capture time (or none, or one where there was none) raises ValueError, and so does `set_lr` while one is attached: the
+    next replay would overwrite what it wrote.
+
     With `ViT.set_dynamic_img_size(True)` X may have another image size than the model's: the resampling of the two
     position tables and its backward are captured with the step (their tap tables are sent to the device by the warm-up
     steps; a capture cannot).  The graph is bound to that size, as to the batch size.  After `ViT.set_input_size` changed
@@ -327,6 +339,7 @@ class GraphedTrainStep:
         self.erase, self.crop = self._stages.get("erase", (None,))[0], self._stages.get("crop")
         self.model, self.optimizer, self.grad_clip = model, optimizer, grad_clip
         self.ema = optimizer.ema   # the ModelEma (or none) whose update the warm-up steps run and the capture records
+        self.schedule = optimizer.schedule   # the LRSchedule (or none) whose launch the captured optimizer step contains
         self.drop_path = m.drop_path   # the DropPath (or none) whose draw the captured forwards contain
         self.patch_drop = m.patch_drop   # the PatchDropout (or none), likewise
         self._size_epoch = m._size_epoch   # ViT.set_input_size replaces parameters whose addresses the graph holds
@@ -381,6 +394,9 @@ class GraphedTrainStep:
         return _wrap_input(self._stages, self.X)
 
     def set_lr(self, lr: float) -> None:
+        if self.optimizer.schedule is not None:
+            raise ValueError("GraphedTrainStep.set_lr: an LRSchedule is attached to the optimizer; the next replay would "
+                             "overwrite the rate")
         for group in self.optimizer.param_groups:
             group["lr"] = lr
         self.optimizer.rewrite_hyper(self._table)
@@ -426,6 +442,8 @@ class GraphedTrainStep:
             X = X.u8
         if self.optimizer.ema is not self.ema:
             raise ValueError("GraphedTrainStep: this graph was captured with another ModelEma (or none)")
+        if self.optimizer.schedule is not self.schedule:
+            raise ValueError("GraphedTrainStep: this graph was captured with another LRSchedule (or none)")
         if _unwrap(self.model).drop_path is not self.drop_path:
             raise ValueError("GraphedTrainStep: this graph was captured with another DropPath (or none)")
         if _unwrap(self.model).patch_drop is not self.patch_drop:
