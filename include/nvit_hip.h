@@ -217,7 +217,15 @@ int nvit_gemm_nt(int dt, const void* A, int lda, const void* B, int ldb, void* C
  *   uv[M,2F] (interleaved, as written by nvit_gemm_nt_swiglu) it writes duv[M,2F] (same layout) and, when gs != NULL
  *   (suv, natural order [u(F)|v(F)]), part[R, 2F] = partial sums of d(suv) over NVIT_SWIGLU_BWD_PART_ROWS rows each, for
  *   whole row tiles: R = ceil(M / NVIT_SWIGLU_BWD_TILE_ROWS) * NVIT_SWIGLU_BWD_TILE_ROWS / NVIT_SWIGLU_BWD_PART_ROWS (natural
- *   order; reduce with nvit_colsum_reduce).  Replaces nvit_gemm_nt + nvit_swiglu_bwd.  Requires F % 256 == 0. */
+ *   order; reduce with nvit_colsum_reduce).  Replaces nvit_gemm_nt + nvit_swiglu_bwd.  Requires F % 256 == 0.
+ * bias (optional) of the three forward forms: fp32, 16-byte aligned, NULL = none.  bias[n] is added to the fp32 accumulator
+ * of output column n FIRST, before anything else in the epilogue, so every later step sees A B^T + bias:
+ *   _swiglu / _swiglu_act: bias[2F] in the interleaved (perm=1, u16|v16) column order of the weight shadow, like gs.  The
+ *     raw uv that is stored (the pre-activation nvit_gemm_nt_swiglu_bwd / nvit_swiglu_bwd differentiate) includes it, and
+ *     the gate is computed from the same biased sums: xm of the two forms stays bit-identical.
+ *   _qknorm: bias[nparts*C], the stacked biases of exactly the nparts projections of this launch, indexed by the launch's
+ *     own output column (NOT offset by part0).  Added for every part (v too) before the sum of squares; the normalise,
+ *     rq/rk, the sqk*c_q scale, q_prescale and the head split (also with sqk == NULL) run on the biased sums. */
 #define NVIT_SWIGLU_BWD_TILE_ROWS 256
 #define NVIT_SWIGLU_BWD_PART_ROWS 128
 /* Tile scheduling of the persistent NT GEMM kernels: 0 = static round-robin (default), 1 = dynamic per-XCD ticket
@@ -231,34 +239,17 @@ int nvit_gemm_nt_fusable(int dt, int M, int N, int K);
 int nvit_gemm_nt_swiglu_bwd(int dt, const void* A, int lda, const void* B, int ldb, const void* uv, void* duv,
                             float* part, int M, int F, int K, const float* gs, float gscale, void* stream);
 int nvit_gemm_nt_swiglu(int dt, const void* A, int lda, const void* B, int ldb, void* uv, void* xm, int M, int F,
-                        int K, const float* gs, float gscale, void* stream);
+                        int K, const float* gs, float gscale, const float* bias, void* stream);
 /* nvit_gemm_nt_swiglu_act: nvit_gemm_nt_swiglu for a forward that no backward follows (no_grad / evaluation): the same
  * kernel, operands and gate arithmetic, but only xm[M,F] is written - the raw uv[M,2F], two thirds of the epilogue's
  * stores, is not.  xm is bit-identical to nvit_gemm_nt_swiglu's.  Same eligibility (nvit_gemm_nt_fusable(dt, M, 2F, K)). */
 int nvit_gemm_nt_swiglu_act(int dt, const void* A, int lda, const void* B, int ldb, void* xm, int M, int F, int K,
-                            const float* gs, float gscale, void* stream);
+                            const float* gs, float gscale, const float* bias, void* stream);
 /* q_prescale: extra factor folded into the q part (qh = q_prescale * sqk*c_q * unit vector, one rounding); pass the same
  * value to nvit_attn_fwd_bounded / nvit_attn_bwd_qknorm.  1 = plain. */
 int nvit_gemm_nt_qknorm(int dt, const void* A, int lda, const void* B, int ldb, int M, int K, int nparts, int part0,
                         const float* sqk, float c_q, float q_prescale, void* qh, void* kh, void* vh, float* rq, float* rk,
-                        int T, int H, int d, void* stream);
-/* The three fused forward GEMMs with a bias (fp32, 16-byte aligned; NULL = none, and then they ARE their siblings above,
- * which forward here).  bias[n] is added to the fp32 accumulator of output column n FIRST, before anything else in the
- * epilogue, so every later step sees A B^T + bias:
- *   _swiglu_bias / _swiglu_act_bias: bias[2F] in the interleaved (perm=1, u16|v16) column order of the weight shadow, like
- *     gs.  The raw uv that is stored (the pre-activation nvit_gemm_nt_swiglu_bwd / nvit_swiglu_bwd differentiate) includes
- *     it, and the gate is computed from the same biased sums: xm of the two forms stays bit-identical.
- *   _qknorm_bias: bias[nparts*C], the stacked biases of exactly the nparts projections of this launch, indexed by the
- *     launch's own output column (NOT offset by part0).  Added for every part (v too) before the sum of squares; the
- *     normalise, rq/rk, the sqk*c_q scale, q_prescale and the head split (also with sqk == NULL) run on the biased sums.
- * Same eligibility (nvit_gemm_nt_fusable) and the same kernel-family ids as the siblings. */
-int nvit_gemm_nt_swiglu_bias(int dt, const void* A, int lda, const void* B, int ldb, void* uv, void* xm, int M, int F,
-                             int K, const float* gs, float gscale, const float* bias, void* stream);
-int nvit_gemm_nt_swiglu_act_bias(int dt, const void* A, int lda, const void* B, int ldb, void* xm, int M, int F, int K,
-                                 const float* gs, float gscale, const float* bias, void* stream);
-int nvit_gemm_nt_qknorm_bias(int dt, const void* A, int lda, const void* B, int ldb, int M, int K, int nparts, int part0,
-                             const float* sqk, float c_q, float q_prescale, void* qh, void* kh, void* vh, float* rq,
-                             float* rk, int T, int H, int d, const float* bias, void* stream);
+                        int T, int H, int d, const float* bias, void* stream);
 
 /* nvit_gemm_tn: weight gradient  G[N,K] (+)= sum_m A[m,N-col] * B[m,K-col]  over Mred rows.
  * A [Mred, N] (lda), B [Mred, K] (ldb) of type dt.  Split over `splits` row chunks into the
@@ -272,7 +263,8 @@ int nvit_gemm_tn(int dt, const void* A, int lda, const void* B, int ldb, float* 
 /* ---- row-wise fused ops on the fp32 residual stream --------------------------------
  * nvit_lerp_fwd: out = nrm(nrm(h) + |alpha*c_a| * (nrm(y) - nrm(h)))   (model.py:134-142,159-167)
  * if skip_x != NULL additionally out = nrm(out*skip[0] + skip_x)         (norm_skip, model.py:84-87,452)
- * h, skip_x fp32 [M,C]; y of type y_dt; out fp32; out_lo (type dt, may be NULL) = cast(out).
+ * h, skip_x fp32 [M,C]; y of type y_dt; out fp32; out_lo (type dt, may be NULL) = cast(out).  gate, rows_per_sample: the
+ * "gate (optional)" paragraph under nvit_lerp_bwd below.
  * Every row kernel of this section (and nvit_pool_ln_*, nvit_scatter_rows) holds a row of at most NVIT_MAX_EMBD columns.
  * The backward kernels that leave per-workgroup partial sums take nblk <= NVIT_MAX_PART_BLOCKS workgroups; those that
  * leave them per WAVE write NVIT_ROW_WAVES rows per workgroup. */
@@ -281,35 +273,29 @@ int nvit_gemm_tn(int dt, const void* A, int lda, const void* B, int ldb, float* 
 #define NVIT_ROW_WAVES 4
 #define NVIT_ROW_GRID_MAX 2048 /* the forward row kernels launch at most this many workgroups and stride over the rest */
 int nvit_lerp_fwd(int dt, const float* h, const void* y, int y_dt, const float* alpha, float c_a,
-                  const float* skip_x, const float* skip, float* out, void* out_lo, int M, int C, void* stream);
+                  const float* skip_x, const float* skip, const float* gate, int rows_per_sample, float* out,
+                  void* out_lo, int M, int C, void* stream);
 /* nvit_lerp_bwd: given dout, recomputes the forward and writes dh (fp32; += if accum_dh), dy (fp32
  * and/or type-dt copy, either may be NULL), dskip_x (fp32, written, only if skip_x), and per-WAVE
  * partial sums part_dlam [NVIT_ROW_WAVES*nblk, C] (d/d|alpha*c_a|) and part_dskip [NVIT_ROW_WAVES*nblk] (if skip_x).
  * nblk = number of workgroups the caller sizes the partial buffers for (<= NVIT_MAX_PART_BLOCKS).
  * dout_add (bf16 [M,C] or NULL): the incoming gradient is dout + dout_add - lets the data-gradient GEMM that produced
  * dout_add store bf16 once instead of read-modify-writing the fp32 dout (the reference's autocast nn.Linear hands its
- * input gradient back in bf16 as well). */
-/* nvit_lerp_bwd_blocks: the nblk that fills the device exactly once for the kernel variant these options select (0 on
- * error); callers size the partial buffers with it. */
-int nvit_lerp_bwd_blocks(int dt, int y_dt, int C, int has_add, int has_skip, int accum);
-int nvit_lerp_bwd(int dt, const float* dout, const void* dout_add, const float* h, const void* y, int y_dt, const float* alpha,
-                  float c_a, const float* skip_x, const float* skip, float* dh, int accum_dh, float* dy,
-                  void* dy_lo, float* dskip_x, float* part_dlam, float* part_dskip, int nblk, int M, int C,
-                  void* stream);
-/* Gated LERP (stochastic depth): rows m*rows_per_sample .. belong to sample m, and gate[m] (fp32, one per sample: the row
- * of nvit_droppath_draw's table for this block and branch) multiplies the step of the LERP for all of them:
+ * input gradient back in bf16 as well).
+ * gate (optional; stochastic depth): NULL = none, and rows_per_sample is ignored.  Otherwise rows m*rows_per_sample ..
+ * belong to sample m, M is a multiple of rows_per_sample, and gate[m] (fp32, one per sample: the row of
+ * nvit_droppath_draw's table for this block and branch) multiplies the step of the LERP for all of them:
  * out = nrm(nrm(h) + (gate * |alpha*c_a|) * (nrm(y) - nrm(h))); the fused norm_skip is not gated.  The backward is that of
- * the gated forward: dy and the part_dlam terms carry the gate.  With every gate 1.0f each output has the bits of the
- * plain entry point.  M must be a multiple of rows_per_sample.  nvit_lerp_bwd_gated is built for the two calls of the
- * block chain: skip_x without accum_dh (the MLP half) or accum_dh without skip_x (the attention half). */
-int nvit_lerp_fwd_gated(int dt, const float* h, const void* y, int y_dt, const float* alpha, float c_a,
-                        const float* skip_x, const float* skip, const float* gate, int rows_per_sample, float* out,
-                        void* out_lo, int M, int C, void* stream);
-int nvit_lerp_bwd_gated_blocks(int dt, int y_dt, int C, int has_add, int has_skip, int accum);
-int nvit_lerp_bwd_gated(int dt, const float* dout, const void* dout_add, const float* h, const void* y, int y_dt,
-                        const float* alpha, float c_a, const float* skip_x, const float* skip, const float* gate,
-                        int rows_per_sample, float* dh, int accum_dh, float* dy, void* dy_lo, float* dskip_x,
-                        float* part_dlam, float* part_dskip, int nblk, int M, int C, void* stream);
+ * the gated forward: dy and the part_dlam terms carry the gate.  With every gate 1.0f the bits are those of gate == NULL.
+ * With a gate nvit_lerp_bwd is built for the two calls of the block chain: skip_x without accum_dh (the MLP half) or
+ * accum_dh without skip_x (the attention half); any other gated call is an error. */
+/* nvit_lerp_bwd_blocks: the nblk that fills the device exactly once for the kernel variant these options select (0 on
+ * error, and for a gated variant that is not built); callers size the partial buffers with it. */
+int nvit_lerp_bwd_blocks(int dt, int y_dt, int C, int has_add, int has_skip, int accum, int gated);
+int nvit_lerp_bwd(int dt, const float* dout, const void* dout_add, const float* h, const void* y, int y_dt, const float* alpha,
+                  float c_a, const float* skip_x, const float* skip, const float* gate, int rows_per_sample, float* dh,
+                  int accum_dh, float* dy, void* dy_lo, float* dskip_x, float* part_dlam, float* part_dskip, int nblk,
+                  int M, int C, void* stream);
 
 /* RMSNorm (model.py:170-182; not on the nViT path, provided so that the public module works):
  * out = x * rsqrt(mean(x^2) + eps) * w, fp32 [M, C]; rstd [M] saved for the backward.
@@ -322,37 +308,28 @@ int nvit_rmsnorm_bwd(const float* dout, const float* x, const float* w, const fl
  * [M,C], out_lo (type dt, may be NULL) = cast(out), rstd [M].  z itself is not stored.
  * nvit_res_rmsnorm_bwd: from g (+ g_add, type dt, may be NULL: a data-gradient GEMM's output) recomputes z = a + y and
  * writes dz fp32 (added to dz if accum), dz_lo (type dt, may be NULL) = cast(dz), and per-WAVE partial sums part_dw
- * [NVIT_ROW_WAVES*nblk, C] of d(w) (reduce with nvit_colsum_reduce).  nblk <= NVIT_MAX_PART_BLOCKS workgroups. */
-int nvit_res_rmsnorm_fwd(int dt, const float* a, const void* y, int y_dt, const float* w, float eps, float* out,
-                         void* out_lo, float* rstd, int M, int C, void* stream);
-int nvit_res_rmsnorm_bwd(int dt, const float* g, const void* g_add, const float* a, const void* y, int y_dt,
-                         const float* w, const float* rstd, float* dz, int accum, void* dz_lo, float* part_dw, int nblk,
-                         int M, int C, void* stream);
-/* nvit_res_skip_fwd: out = nrm((h + y) * skip[0] + x)  (norm_skip after a plain-ViT block, model.py:84-87,450-452);
+ * [NVIT_ROW_WAVES*nblk, C] of d(w) (reduce with nvit_colsum_reduce).  nblk <= NVIT_MAX_PART_BLOCKS workgroups.
+ * nvit_res_skip_fwd: out = nrm((h + y) * skip[0] + x)  (norm_skip after a plain-ViT block, model.py:84-87,450-452);
  * h, x fp32 [M,C], y of type y_dt; out fp32, out_lo (type dt, may be NULL) = cast(out).
  * nvit_res_skip_bwd: dx = d(x) fp32 (written), dh = d(h + y) fp32, dh_lo (type dt, may be NULL) = cast(dh), and per-WAVE
- * partial sums part_dskip [NVIT_ROW_WAVES*nblk] of d(skip). */
-int nvit_res_skip_fwd(int dt, const float* h, const void* y, int y_dt, const float* skip, const float* x, float* out,
-                      void* out_lo, int M, int C, void* stream);
+ * partial sums part_dskip [NVIT_ROW_WAVES*nblk] of d(skip).
+ * gate (optional; stochastic depth of the plain-ViT block chain): NULL = none, and rows_per_sample is ignored.  Otherwise
+ * gate is fp32, one per sample, rows m*rows_per_sample .. belong to sample m, M is a multiple of rows_per_sample, and the
+ * branch output enters as gate * y wherever the kernel adds y: z = a + gate * y (res_rmsnorm, which then requires y),
+ * (h + gate * y) (res_skip).  Backward: the fp32 outputs dz / dh stay the gradient of the sum, which goes on down the
+ * stream; the type-dt copies dz_lo / dh_lo are gate * that = d(y), what the branch's GEMMs read (fp32 mode included:
+ * there the caller can no longer alias the two).  With a gate nvit_res_rmsnorm_bwd is built with the addend g_add only.
+ * With every gate 1.0f the bits are those of gate == NULL. */
+int nvit_res_rmsnorm_fwd(int dt, const float* a, const void* y, int y_dt, const float* w, float eps, const float* gate,
+                         int rows_per_sample, float* out, void* out_lo, float* rstd, int M, int C, void* stream);
+int nvit_res_rmsnorm_bwd(int dt, const float* g, const void* g_add, const float* a, const void* y, int y_dt,
+                         const float* w, const float* rstd, const float* gate, int rows_per_sample, float* dz, int accum,
+                         void* dz_lo, float* part_dw, int nblk, int M, int C, void* stream);
+int nvit_res_skip_fwd(int dt, const float* h, const void* y, int y_dt, const float* skip, const float* x,
+                      const float* gate, int rows_per_sample, float* out, void* out_lo, int M, int C, void* stream);
 int nvit_res_skip_bwd(int dt, const float* dout, const float* h, const void* y, int y_dt, const float* skip,
-                      const float* x, float* dh, void* dh_lo, float* dx, float* part_dskip, int nblk, int M, int C,
-                      void* stream);
-/* Gated forms (stochastic depth of the plain-ViT block chain): gate fp32, one per sample, rows m*rows_per_sample .. belong
- * to sample m, M a multiple of rows_per_sample; the branch output enters as gate * y wherever the plain kernel adds y:
- * z = a + gate * y (res_rmsnorm), (h + gate * y) (res_skip); y is required.  Backward: the fp32 outputs dz / dh stay the
- * gradient of the sum, which goes on down the stream; the type-dt copies dz_lo / dh_lo are gate * that = d(y), what the
- * branch's GEMMs read (fp32 mode included: there the caller can no longer alias the two).  nvit_res_rmsnorm_bwd_gated is
- * built with the addend g_add only.  With every gate 1.0f each output has the bits of the plain entry point. */
-int nvit_res_rmsnorm_fwd_gated(int dt, const float* a, const void* y, int y_dt, const float* w, float eps, const float* gate,
-                               int rows_per_sample, float* out, void* out_lo, float* rstd, int M, int C, void* stream);
-int nvit_res_rmsnorm_bwd_gated(int dt, const float* g, const void* g_add, const float* a, const void* y, int y_dt,
-                               const float* w, const float* rstd, const float* gate, int rows_per_sample, float* dz,
-                               int accum, void* dz_lo, float* part_dw, int nblk, int M, int C, void* stream);
-int nvit_res_skip_fwd_gated(int dt, const float* h, const void* y, int y_dt, const float* skip, const float* x,
-                            const float* gate, int rows_per_sample, float* out, void* out_lo, int M, int C, void* stream);
-int nvit_res_skip_bwd_gated(int dt, const float* dout, const float* h, const void* y, int y_dt, const float* skip,
-                            const float* x, const float* gate, int rows_per_sample, float* dh, void* dh_lo, float* dx,
-                            float* part_dskip, int nblk, int M, int C, void* stream);
+                      const float* x, const float* gate, int rows_per_sample, float* dh, void* dh_lo, float* dx,
+                      float* part_dskip, int nblk, int M, int C, void* stream);
 /* Block.norm_skip on its own (model.py:84-87): out = nrm(src*skip[0] + tgt), fp32 [M,C]; backward writes dsrc, dtgt
  * (tgt == NULL / dtgt == NULL: the target term is absent, i.e. justnorm(src*skip[0]), model.py:43-44,89-90)
  * and part_dskip [nblk]. (ViT.forward uses the copy fused into nvit_lerp_fwd/bwd.) */

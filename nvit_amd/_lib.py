@@ -72,22 +72,16 @@ SIGNATURES = {
     "nvit_eval_metrics": [_vp, _vp, _vp, _i, _i, _vp],
     "nvit_gemm_nt": [_i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp],
     "nvit_gemm_nt_fusable": [_i, _i, _i, _i],
-    "nvit_gemm_nt_swiglu": [_i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _f, _vp],
-    "nvit_gemm_nt_swiglu_act": [_i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _f, _vp],
+    "nvit_gemm_nt_swiglu": [_i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _f, _vp, _vp],
+    "nvit_gemm_nt_swiglu_act": [_i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _f, _vp, _vp],
     "nvit_gemm_nt_swiglu_bwd": [_i, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _f, _vp],
-    "nvit_gemm_nt_qknorm": [_i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
-    "nvit_gemm_nt_swiglu_bias": [_i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _f, _vp, _vp],
-    "nvit_gemm_nt_swiglu_act_bias": [_i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _f, _vp, _vp],
-    "nvit_gemm_nt_qknorm_bias": [_i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp,
-                                 _vp],
+    "nvit_gemm_nt_qknorm": [_i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp,
+                            _vp],
     "nvit_gemm_tn": [_i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _i64, _i, _i, _vp],
-    "nvit_lerp_fwd": [_i, _vp, _vp, _i, _vp, _f, _vp, _vp, _vp, _vp, _i, _i, _vp],
-    "nvit_lerp_bwd_blocks": [_i, _i, _i, _i, _i, _i],
-    "nvit_lerp_bwd": [_i, _vp, _vp, _vp, _vp, _i, _vp, _f, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
-    "nvit_lerp_fwd_gated": [_i, _vp, _vp, _i, _vp, _f, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _vp],
-    "nvit_lerp_bwd_gated_blocks": [_i, _i, _i, _i, _i, _i],
-    "nvit_lerp_bwd_gated": [_i, _vp, _vp, _vp, _vp, _i, _vp, _f, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i,
-                            _i, _vp],
+    "nvit_lerp_fwd": [_i, _vp, _vp, _i, _vp, _f, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _vp],
+    "nvit_lerp_bwd_blocks": [_i, _i, _i, _i, _i, _i, _i],
+    "nvit_lerp_bwd": [_i, _vp, _vp, _vp, _vp, _i, _vp, _f, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i,
+                      _vp],
     "nvit_norm_skip_fwd": [_vp, _vp, _vp, _vp, _i, _i, _vp],
     "nvit_norm_skip_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
     "nvit_qknorm_fwd": [_i, _vp, _i, _vp, _i, _vp, _i, _vp, _f, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
@@ -143,14 +137,10 @@ SIGNATURES = {
     "nvit_onehot": [_vp, _vp, _i64, _i, _vp],
     "nvit_rmsnorm_fwd": [_vp, _vp, _f, _vp, _vp, _i, _i, _vp],
     "nvit_rmsnorm_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
-    "nvit_res_rmsnorm_fwd": [_i, _vp, _vp, _i, _vp, _f, _vp, _vp, _vp, _i, _i, _vp],
-    "nvit_res_rmsnorm_bwd": [_i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp],
-    "nvit_res_skip_fwd": [_i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp],
-    "nvit_res_skip_bwd": [_i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
-    "nvit_res_rmsnorm_fwd_gated": [_i, _vp, _vp, _i, _vp, _f, _vp, _i, _vp, _vp, _vp, _i, _i, _vp],
-    "nvit_res_rmsnorm_bwd_gated": [_i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _vp],
-    "nvit_res_skip_fwd_gated": [_i, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _vp],
-    "nvit_res_skip_bwd_gated": [_i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
+    "nvit_res_rmsnorm_fwd": [_i, _vp, _vp, _i, _vp, _f, _vp, _i, _vp, _vp, _vp, _i, _i, _vp],
+    "nvit_res_rmsnorm_bwd": [_i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _vp],
+    "nvit_res_skip_fwd": [_i, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _vp],
+    "nvit_res_skip_bwd": [_i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
     "nvit_som_update": [_vp, _vp, _vp, _f, _f, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp],
     "nvit_som_update_dev": [_vp, _vp, _vp, _vp, _f, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp],
     "nvit_cos_consistency_fwd": [_vp, _vp, _vp, _vp, _i, _vp, _i64, _i, _vp],

@@ -480,8 +480,8 @@ extern "C" int nvit_gemm_nt_fusable(int dt, int M, int N, int K) {
   return (dt == NVIT_BF16 && M >= 1 && N % 256 == 0 && K % 64 == 0) ? 1 : 0;
 }
 
-extern "C" int nvit_gemm_nt_swiglu_bias(int dt, const void* A, int lda, const void* B, int ldb, void* uv, void* xm, int M,
-                                        int F, int K, const float* gs, float gscale, const float* bias, void* stream) {
+extern "C" int nvit_gemm_nt_swiglu(int dt, const void* A, int lda, const void* B, int ldb, void* uv, void* xm, int M,
+                                   int F, int K, const float* gs, float gscale, const float* bias, void* stream) {
   NVIT_REQUIRE(nvit_gemm_nt_fusable(dt, M, 2 * F, K), "gemm_nt_swiglu: shape/dtype not eligible for the fused kernel");
   NVIT_REQUIRE((lda * 2) % 16 == 0 && (ldb * 2) % 16 == 0 && lda >= K && ldb >= K, "gemm_nt_swiglu: bad leading dims");
   NVIT_REQUIRE((((uintptr_t)A | (uintptr_t)B | (uintptr_t)uv | (uintptr_t)xm | (uintptr_t)gs | (uintptr_t)bias) & 15) == 0,
@@ -508,14 +508,9 @@ extern "C" int nvit_gemm_nt_swiglu_bias(int dt, const void* A, int lda, const vo
   return nvit_gemm_nt_fused_launch(g, 3, s);
 }
 
-extern "C" int nvit_gemm_nt_swiglu(int dt, const void* A, int lda, const void* B, int ldb, void* uv, void* xm, int M,
-                                   int F, int K, const float* gs, float gscale, void* stream) {
-  return nvit_gemm_nt_swiglu_bias(dt, A, lda, B, ldb, uv, xm, M, F, K, gs, gscale, nullptr, stream);
-}
-
 // The forward-only form of nvit_gemm_nt_swiglu: the same launch without the raw uv store (EPI 6).
-extern "C" int nvit_gemm_nt_swiglu_act_bias(int dt, const void* A, int lda, const void* B, int ldb, void* xm, int M, int F,
-                                            int K, const float* gs, float gscale, const float* bias, void* stream) {
+extern "C" int nvit_gemm_nt_swiglu_act(int dt, const void* A, int lda, const void* B, int ldb, void* xm, int M, int F,
+                                       int K, const float* gs, float gscale, const float* bias, void* stream) {
   NVIT_REQUIRE(nvit_gemm_nt_fusable(dt, M, 2 * F, K), "gemm_nt_swiglu_act: shape/dtype not eligible for the fused kernel");
   NVIT_REQUIRE((lda * 2) % 16 == 0 && (ldb * 2) % 16 == 0 && lda >= K && ldb >= K,
                "gemm_nt_swiglu_act: bad leading dims");
@@ -539,11 +534,6 @@ extern "C" int nvit_gemm_nt_swiglu_act_bias(int dt, const void* A, int lda, cons
   // algorithmic bytes: A, B read; the gated x [M,F] written (bf16)
   ProfScope ps(NVIT_KID_GEMM_SWIGLU_ACT, 2.0 * M * (2.0 * F) * K, 2.0 * ((double)M * K + 2.0 * F * K + (double)M * F), s);
   return nvit_gemm_nt_fused_launch(g, 6, s);
-}
-
-extern "C" int nvit_gemm_nt_swiglu_act(int dt, const void* A, int lda, const void* B, int ldb, void* xm, int M, int F, int K,
-                                       const float* gs, float gscale, void* stream) {
-  return nvit_gemm_nt_swiglu_act_bias(dt, A, lda, B, ldb, xm, M, F, K, gs, gscale, nullptr, stream);
 }
 
 extern "C" int nvit_gemm_nt_swiglu_bwd(int dt, const void* A, int lda, const void* B, int ldb, const void* uv,
@@ -579,10 +569,9 @@ extern "C" int nvit_gemm_nt_swiglu_bwd(int dt, const void* A, int lda, const voi
   return nvit_gemm_nt_fused_launch(g, 5, s);
 }
 
-extern "C" int nvit_gemm_nt_qknorm_bias(int dt, const void* A, int lda, const void* B, int ldb, int M, int K, int nparts,
-                                        int part0, const float* sqk, float c_q, float q_prescale, void* qh, void* kh,
-                                        void* vh, float* rq, float* rk, int T, int H, int d, const float* bias,
-                                        void* stream) {
+extern "C" int nvit_gemm_nt_qknorm(int dt, const void* A, int lda, const void* B, int ldb, int M, int K, int nparts,
+                                   int part0, const float* sqk, float c_q, float q_prescale, void* qh, void* kh, void* vh,
+                                   float* rq, float* rk, int T, int H, int d, const float* bias, void* stream) {
   const int C = H * d;
   NVIT_REQUIRE(d == 64 && C % 256 == 0 && nparts >= 1 && part0 >= 0 && part0 + nparts <= 3,
                "gemm_nt_qknorm: needs head dim 64 and n_embd %% 256 == 0");
@@ -622,9 +611,3 @@ extern "C" int nvit_gemm_nt_qknorm_bias(int dt, const void* A, int lda, const vo
   return nvit_gemm_nt_fused_launch(g, 4, s);
 }
 
-extern "C" int nvit_gemm_nt_qknorm(int dt, const void* A, int lda, const void* B, int ldb, int M, int K, int nparts,
-                                   int part0, const float* sqk, float c_q, float q_prescale, void* qh, void* kh, void* vh,
-                                   float* rq, float* rk, int T, int H, int d, void* stream) {
-  return nvit_gemm_nt_qknorm_bias(dt, A, lda, B, ldb, M, K, nparts, part0, sqk, c_q, q_prescale, qh, kh, vh, rq, rk, T, H,
-                                  d, nullptr, stream);
-}

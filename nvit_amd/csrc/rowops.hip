@@ -1157,67 +1157,46 @@ static auto with_in_out_elems(int dt, F&& f) {
 }
 
 // The lerp_bwd instantiation for a call's options: nvit_lerp_bwd launches it and nvit_lerp_bwd_blocks sizes that launch's
-// grid from its occupancy, so both go through here.
-static auto lerp_bwd_select(int C, int y_dt, int dt, bool has_add, bool has_skip, bool accum) -> void (*)(LerpBwdArgs) {
+// grid from its occupancy, so both go through here.  The gated instantiations are the two the block chain of ViT.forward
+// launches: the MLP half (norm_skip fused, dh written) and the attention half (no skip, dh accumulated), each with and
+// without the bf16 addend; both callers refuse a gated call with has_skip == accum before they come here.
+static auto lerp_bwd_select(int C, int y_dt, int dt, bool has_add, bool has_skip, bool accum, bool gated) -> void (*)(LerpBwdArgs) {
   return with_row_types(C, y_dt, dt, [&](auto nv, auto ty, auto tl) {
     return with_bool(has_add, [&](auto add) {
+      using TY = tag_t<decltype(ty)>;
+      using TL = tag_t<decltype(tl)>;
+      if (gated && has_skip) return &lerp_bwd_kernel<nv, TY, TL, add, true, false, true>;
+      if (gated) return &lerp_bwd_kernel<nv, TY, TL, add, false, true, true>;
       return with_bool(has_skip, [&](auto skip) {
-        return with_bool(accum, [&](auto acc) {
-          return &lerp_bwd_kernel<nv, tag_t<decltype(ty)>, tag_t<decltype(tl)>, add, skip, acc, false>;
-        });
+        return with_bool(accum, [&](auto acc) { return &lerp_bwd_kernel<nv, TY, TL, add, skip, acc, false>; });
       });
     });
   });
 }
 
-// The gated instantiations are the two the block chain of ViT.forward launches: the MLP half (norm_skip fused, dh written)
-// and the attention half (no skip, dh accumulated), each with and without the bf16 addend.
-static auto lerp_bwd_gated_select(int C, int y_dt, int dt, bool has_add, bool mlp_half) -> void (*)(LerpBwdArgs) {
-  return with_row_types(C, y_dt, dt, [&](auto nv, auto ty, auto tl) {
-    return with_bool(has_add, [&](auto add) {
-      using TY = tag_t<decltype(ty)>;
-      using TL = tag_t<decltype(tl)>;
-      if (mlp_half) return &lerp_bwd_kernel<nv, TY, TL, add, true, false, true>;
-      return &lerp_bwd_kernel<nv, TY, TL, add, false, true, true>;
-    });
-  });
-}
-
+// ---- the gate of stochastic depth, optional in the six entry points below: NULL launches the GATED = false instantiation
+// (rows_per_sample is then ignored), a gate the GATED = true one, which reads one float per sample on top of the rows. ----
 static bool gate_args_ok(const float* gate, int rows_per_sample, int M) {
-  return gate && rows_per_sample > 0 && M % rows_per_sample == 0;
+  return !gate || (rows_per_sample > 0 && M % rows_per_sample == 0);
 }
+static double gate_bytes(const float* gate, int M) { return gate ? 4.0 * M : 0.0; }
+static double elem_bytes(int dt) { return dt == NVIT_F32 ? 4.0 : 2.0; }
 
 extern "C" int nvit_lerp_fwd(int dt, const float* h, const void* y, int y_dt, const float* alpha, float c_a,
-                             const float* skip_x, const float* skip, float* out, void* out_lo, int M, int C,
-                             void* stream) {
+                             const float* skip_x, const float* skip, const float* gate, int rows_per_sample, float* out,
+                             void* out_lo, int M, int C, void* stream) {
   NVIT_REQUIRE(C % 4 == 0 && C <= NVIT_MAX_EMBD && M > 0, "lerp_fwd: C=%d must be a multiple of 4 and <= %d", C, NVIT_MAX_EMBD);
   NVIT_REQUIRE(!skip_x || skip, "lerp_fwd: skip_x without skip");
-  LerpFwdArgs a{h, y, alpha, c_a, skip_x, skip, out, out_lo, M, C, nullptr, 1};
+  NVIT_REQUIRE(gate_args_ok(gate, rows_per_sample, M), "lerp_fwd: with a gate, M=%d must be a multiple of rows_per_sample=%d", M,
+               rows_per_sample);
+  LerpFwdArgs a{h, y, alpha, c_a, skip_x, skip, out, out_lo, M, C, gate, gate ? rows_per_sample : 1};
   hipStream_t s = (hipStream_t)stream;
-  const int grid = row_grid(M);
-  ProfScope ps(NVIT_KID_ROWOPS, 0.0, (double)M * C * (skip_x ? 16.0 : 12.0), s);
-  const auto kernel = with_row_types(C, y_dt, dt, [](auto nv, auto ty, auto tl) {
-    return &lerp_fwd_kernel<nv, tag_t<decltype(ty)>, tag_t<decltype(tl)>, false>;
-  });
-  launch(kernel, dim3(grid), dim3(256), 0, s, a);
-  NVIT_CHECK_LAUNCH("lerp_fwd");
-  return NVIT_OK;
-}
-
-extern "C" int nvit_lerp_fwd_gated(int dt, const float* h, const void* y, int y_dt, const float* alpha, float c_a,
-                                   const float* skip_x, const float* skip, const float* gate, int rows_per_sample,
-                                   float* out, void* out_lo, int M, int C, void* stream) {
-  NVIT_REQUIRE(C % 4 == 0 && C <= NVIT_MAX_EMBD && M > 0, "lerp_fwd_gated: C=%d must be a multiple of 4 and <= %d", C, NVIT_MAX_EMBD);
-  NVIT_REQUIRE(!skip_x || skip, "lerp_fwd_gated: skip_x without skip");
-  NVIT_REQUIRE(gate_args_ok(gate, rows_per_sample, M), "lerp_fwd_gated: gate missing, or M=%d is no multiple of rows_per_sample=%d", M, rows_per_sample);
-  LerpFwdArgs a{h, y, alpha, c_a, skip_x, skip, out, out_lo, M, C, gate, rows_per_sample};
-  hipStream_t s = (hipStream_t)stream;
-  ProfScope ps(NVIT_KID_ROWOPS, 0.0, (double)M * C * (skip_x ? 16.0 : 12.0) + 4.0 * M, s);
-  const auto kernel = with_row_types(C, y_dt, dt, [](auto nv, auto ty, auto tl) {
-    return &lerp_fwd_kernel<nv, tag_t<decltype(ty)>, tag_t<decltype(tl)>, true>;
+  ProfScope ps(NVIT_KID_ROWOPS, 0.0, (double)M * C * (skip_x ? 16.0 : 12.0) + gate_bytes(gate, M), s);
+  const auto kernel = with_row_types(C, y_dt, dt, [&](auto nv, auto ty, auto tl) {
+    return with_bool(gate != nullptr, [&](auto gated) { return &lerp_fwd_kernel<nv, tag_t<decltype(ty)>, tag_t<decltype(tl)>, gated>; });
   });
   launch(kernel, dim3(row_grid(M)), dim3(256), 0, s, a);
-  NVIT_CHECK_LAUNCH("lerp_fwd_gated");
+  NVIT_CHECK_LAUNCH("lerp_fwd");
   return NVIT_OK;
 }
 
@@ -1231,54 +1210,31 @@ static int resident_blocks(void (*kernel)(LerpBwdArgs)) {
   return per_cu * nvit_num_cu();
 }
 
-extern "C" int nvit_lerp_bwd_blocks(int dt, int y_dt, int C, int has_add, int has_skip, int accum) {
-  if (C % 4 != 0 || C <= 0 || C > NVIT_MAX_EMBD) return 0;
-  const int n = resident_blocks(lerp_bwd_select(C, y_dt, dt, has_add, has_skip, accum));
-  return n > NVIT_MAX_PART_BLOCKS ? NVIT_MAX_PART_BLOCKS : n;
-}
-
-extern "C" int nvit_lerp_bwd_gated_blocks(int dt, int y_dt, int C, int has_add, int has_skip, int accum) {
-  if (C % 4 != 0 || C <= 0 || C > NVIT_MAX_EMBD || (has_skip != 0) == (accum != 0)) return 0;
-  const int n = resident_blocks(lerp_bwd_gated_select(C, y_dt, dt, has_add, has_skip != 0));
+extern "C" int nvit_lerp_bwd_blocks(int dt, int y_dt, int C, int has_add, int has_skip, int accum, int gated) {
+  if (C % 4 != 0 || C <= 0 || C > NVIT_MAX_EMBD || (gated && (has_skip != 0) == (accum != 0))) return 0;
+  const int n = resident_blocks(lerp_bwd_select(C, y_dt, dt, has_add, has_skip, accum, gated));
   return n > NVIT_MAX_PART_BLOCKS ? NVIT_MAX_PART_BLOCKS : n;
 }
 
 extern "C" int nvit_lerp_bwd(int dt, const float* dout, const void* dout_add, const float* h, const void* y, int y_dt, const float* alpha,
-                             float c_a, const float* skip_x, const float* skip, float* dh, int accum_dh, float* dy,
-                             void* dy_lo, float* dskip_x, float* part_dlam, float* part_dskip, int nblk, int M,
-                             int C, void* stream) {
+                             float c_a, const float* skip_x, const float* skip, const float* gate, int rows_per_sample,
+                             float* dh, int accum_dh, float* dy, void* dy_lo, float* dskip_x, float* part_dlam,
+                             float* part_dskip, int nblk, int M, int C, void* stream) {
   NVIT_REQUIRE(C % 4 == 0 && C <= NVIT_MAX_EMBD && M > 0, "lerp_bwd: C=%d must be a multiple of 4 and <= %d", C, NVIT_MAX_EMBD);
   NVIT_REQUIRE(nblk > 0 && nblk <= NVIT_MAX_PART_BLOCKS, "lerp_bwd: nblk out of range");
   NVIT_REQUIRE(!skip_x || (skip && dskip_x && part_dskip), "lerp_bwd: skip buffers missing");
-  LerpBwdArgs a{dout, (const bf16*)dout_add, h, y, alpha, c_a, skip_x, skip, dh, accum_dh, dy, dy_lo, dskip_x, part_dlam, part_dskip, M, C, nullptr, 1};
+  NVIT_REQUIRE(gate_args_ok(gate, rows_per_sample, M), "lerp_bwd: with a gate, M=%d must be a multiple of rows_per_sample=%d", M,
+               rows_per_sample);
+  NVIT_REQUIRE(!gate || (skip_x != nullptr) != (accum_dh != 0),
+               "lerp_bwd: with a gate, built for the two calls of the block chain, skip_x without accum_dh or accum_dh without skip_x");
+  LerpBwdArgs a{dout, (const bf16*)dout_add, h, y, alpha, c_a, skip_x, skip, dh, accum_dh, dy, dy_lo, dskip_x, part_dlam, part_dskip, M, C, gate, gate ? rows_per_sample : 1};
   hipStream_t s = (hipStream_t)stream;
   // algorithmic bytes: dout, h read, y read (2 or 4 B), dh written, dy_lo written (+ skip_x read, dskip_x written; + dout_add)
-  const double lb_bytes = (double)M * C * (4.0 + 4.0 + (y_dt == NVIT_F32 ? 4.0 : 2.0) + 4.0 + (dy ? 4.0 : 0.0) + (dy_lo ? (dt == NVIT_F32 ? 4.0 : 2.0) : 0.0) +
-                                           (skip_x ? 8.0 : 0.0) + (accum_dh ? 4.0 : 0.0) + (dout_add ? 2.0 : 0.0));
+  const double lb_bytes = (double)M * C * (4.0 + 4.0 + elem_bytes(y_dt) + 4.0 + (dy ? 4.0 : 0.0) + (dy_lo ? elem_bytes(dt) : 0.0) +
+                                           (skip_x ? 8.0 : 0.0) + (accum_dh ? 4.0 : 0.0) + (dout_add ? 2.0 : 0.0)) + gate_bytes(gate, M);
   ProfScope ps(NVIT_KID_ROWOPS, 0.0, lb_bytes, s);
-  launch(lerp_bwd_select(C, y_dt, dt, dout_add != nullptr, skip_x != nullptr, accum_dh != 0), dim3(nblk), dim3(256), 0, s, a);
+  launch(lerp_bwd_select(C, y_dt, dt, dout_add != nullptr, skip_x != nullptr, accum_dh != 0, gate != nullptr), dim3(nblk), dim3(256), 0, s, a);
   NVIT_CHECK_LAUNCH("lerp_bwd");
-  return NVIT_OK;
-}
-
-extern "C" int nvit_lerp_bwd_gated(int dt, const float* dout, const void* dout_add, const float* h, const void* y, int y_dt,
-                                   const float* alpha, float c_a, const float* skip_x, const float* skip,
-                                   const float* gate, int rows_per_sample, float* dh, int accum_dh, float* dy, void* dy_lo,
-                                   float* dskip_x, float* part_dlam, float* part_dskip, int nblk, int M, int C,
-                                   void* stream) {
-  NVIT_REQUIRE(C % 4 == 0 && C <= NVIT_MAX_EMBD && M > 0, "lerp_bwd_gated: C=%d must be a multiple of 4 and <= %d", C, NVIT_MAX_EMBD);
-  NVIT_REQUIRE(nblk > 0 && nblk <= NVIT_MAX_PART_BLOCKS, "lerp_bwd_gated: nblk out of range");
-  NVIT_REQUIRE(!skip_x || (skip && dskip_x && part_dskip), "lerp_bwd_gated: skip buffers missing");
-  NVIT_REQUIRE(gate_args_ok(gate, rows_per_sample, M), "lerp_bwd_gated: gate missing, or M=%d is no multiple of rows_per_sample=%d", M, rows_per_sample);
-  NVIT_REQUIRE((skip_x != nullptr) != (accum_dh != 0),
-               "lerp_bwd_gated: built for the two calls of the block chain, skip_x without accum_dh or accum_dh without skip_x");
-  LerpBwdArgs a{dout, (const bf16*)dout_add, h, y, alpha, c_a, skip_x, skip, dh, accum_dh, dy, dy_lo, dskip_x, part_dlam, part_dskip, M, C, gate, rows_per_sample};
-  hipStream_t s = (hipStream_t)stream;
-  const double lb_bytes = (double)M * C * (4.0 + 4.0 + (y_dt == NVIT_F32 ? 4.0 : 2.0) + 4.0 + (dy ? 4.0 : 0.0) + (dy_lo ? (dt == NVIT_F32 ? 4.0 : 2.0) : 0.0) +
-                                           (skip_x ? 8.0 : 0.0) + (accum_dh ? 4.0 : 0.0) + (dout_add ? 2.0 : 0.0)) + 4.0 * M;
-  ProfScope ps(NVIT_KID_ROWOPS, 0.0, lb_bytes, s);
-  launch(lerp_bwd_gated_select(C, y_dt, dt, dout_add != nullptr, skip_x != nullptr), dim3(nblk), dim3(256), 0, s, a);
-  NVIT_CHECK_LAUNCH("lerp_bwd_gated");
   return NVIT_OK;
 }
 
@@ -1324,44 +1280,56 @@ extern "C" int nvit_rmsnorm_bwd(const float* dout, const float* x, const float* 
   return NVIT_OK;
 }
 
-extern "C" int nvit_res_rmsnorm_fwd(int dt, const float* a, const void* y, int y_dt, const float* w, float eps, float* out,
-                                    void* out_lo, float* rstd, int M, int C, void* stream) {
+// ---- residual kernels of the plain-ViT block chain.  The gated instantiations are built for the calls _StdBlockFn makes:
+// a branch output y is always there, the rms_mlp backward always has its data-gradient addend. ----
+extern "C" int nvit_res_rmsnorm_fwd(int dt, const float* a, const void* y, int y_dt, const float* w, float eps,
+                                    const float* gate, int rows_per_sample, float* out, void* out_lo, float* rstd, int M,
+                                    int C, void* stream) {
   NVIT_REQUIRE(C % 4 == 0 && C <= NVIT_MAX_EMBD && M > 0, "res_rmsnorm_fwd: C=%d must be a multiple of 4 and <= %d", C, NVIT_MAX_EMBD);
   NVIT_REQUIRE(dt == NVIT_F32 || dt == NVIT_BF16, "res_rmsnorm_fwd: bad dt %d", dt);
   NVIT_REQUIRE(!y || y_dt == NVIT_F32 || y_dt == NVIT_BF16, "res_rmsnorm_fwd: bad y_dt %d", y_dt);
-  ResRmsFwdArgs ar{a, y, w, eps, out, out_lo, rstd, M, C, nullptr, 1};
+  NVIT_REQUIRE(!gate || y, "res_rmsnorm_fwd: a gate needs y");
+  NVIT_REQUIRE(gate_args_ok(gate, rows_per_sample, M), "res_rmsnorm_fwd: with a gate, M=%d must be a multiple of rows_per_sample=%d", M,
+               rows_per_sample);
+  ResRmsFwdArgs ar{a, y, w, eps, out, out_lo, rstd, M, C, gate, gate ? rows_per_sample : 1};
   hipStream_t s = (hipStream_t)stream;
-  const int grid = row_grid(M);
-  ProfScope ps(NVIT_KID_ROWOPS, 0.0, (double)M * C * (8.0 + (y ? (y_dt == NVIT_F32 ? 4.0 : 2.0) : 0.0) +
-                                                       (out_lo ? (dt == NVIT_F32 ? 4.0 : 2.0) : 0.0)), s);
+  ProfScope ps(NVIT_KID_ROWOPS, 0.0, (double)M * C * (8.0 + (y ? elem_bytes(y_dt) : 0.0) + (out_lo ? elem_bytes(dt) : 0.0)) +
+                                         gate_bytes(gate, M), s);
   const auto kernel = with_row_vecs<8>(C, [&](auto nv) {
     return with_elem(dt, [&](auto tl) {
       using TL = tag_t<decltype(tl)>;
       if (!y) return &res_rmsnorm_fwd_kernel<nv, float, TL, false, false>;   // without y, TY is float: no <bf16, false> is built
-      return with_elem(y_dt, [&](auto ty) { return &res_rmsnorm_fwd_kernel<nv, tag_t<decltype(ty)>, TL, true, false>; });
+      return with_elem(y_dt, [&](auto ty) {
+        return with_bool(gate != nullptr, [&](auto gated) { return &res_rmsnorm_fwd_kernel<nv, tag_t<decltype(ty)>, TL, true, gated>; });
+      });
     });
   });
-  launch(kernel, dim3(grid), dim3(256), 0, s, ar);
+  launch(kernel, dim3(row_grid(M)), dim3(256), 0, s, ar);
   NVIT_CHECK_LAUNCH("res_rmsnorm_fwd");
   return NVIT_OK;
 }
 
 extern "C" int nvit_res_rmsnorm_bwd(int dt, const float* g, const void* g_add, const float* a, const void* y, int y_dt,
-                                    const float* w, const float* rstd, float* dz, int accum, void* dz_lo, float* part_dw,
-                                    int nblk, int M, int C, void* stream) {
+                                    const float* w, const float* rstd, const float* gate, int rows_per_sample, float* dz,
+                                    int accum, void* dz_lo, float* part_dw, int nblk, int M, int C, void* stream) {
   NVIT_REQUIRE(C % 4 == 0 && C <= NVIT_MAX_EMBD && M > 0, "res_rmsnorm_bwd: C=%d must be a multiple of 4 and <= %d", C, NVIT_MAX_EMBD);
   NVIT_REQUIRE(nblk > 0 && nblk <= NVIT_MAX_PART_BLOCKS, "res_rmsnorm_bwd: nblk out of range");
   NVIT_REQUIRE(dt == NVIT_F32 || dt == NVIT_BF16, "res_rmsnorm_bwd: bad dt %d", dt);
   NVIT_REQUIRE(!y || y_dt == NVIT_F32 || y_dt == NVIT_BF16, "res_rmsnorm_bwd: bad y_dt %d", y_dt);
-  ResRmsBwdArgs ar{g, g_add, a, y, w, rstd, dz, accum, dz_lo, part_dw, M, C, nullptr, 1};
+  NVIT_REQUIRE(!gate || y, "res_rmsnorm_bwd: a gate needs y");
+  NVIT_REQUIRE(!gate || g_add, "res_rmsnorm_bwd: with a gate, built with the addend g_add only");
+  NVIT_REQUIRE(gate_args_ok(gate, rows_per_sample, M), "res_rmsnorm_bwd: with a gate, M=%d must be a multiple of rows_per_sample=%d", M,
+               rows_per_sample);
+  ResRmsBwdArgs ar{g, g_add, a, y, w, rstd, dz, accum, dz_lo, part_dw, M, C, gate, gate ? rows_per_sample : 1};
   hipStream_t s = (hipStream_t)stream;
-  const double tl = dt == NVIT_F32 ? 4.0 : 2.0;
-  ProfScope ps(NVIT_KID_ROWOPS, 0.0, (double)M * C * (12.0 + (y ? (y_dt == NVIT_F32 ? 4.0 : 2.0) : 0.0) +
-                                                       (g_add ? tl : 0.0) + (accum ? 4.0 : 0.0) + (dz_lo ? tl : 0.0)), s);
+  const double tl = elem_bytes(dt);
+  ProfScope ps(NVIT_KID_ROWOPS, 0.0, (double)M * C * (12.0 + (y ? elem_bytes(y_dt) : 0.0) + (g_add ? tl : 0.0) + (accum ? 4.0 : 0.0) +
+                                                       (dz_lo ? tl : 0.0)) + gate_bytes(gate, M), s);
   const auto kernel = with_row_vecs<8>(C, [&](auto nv) {
     return with_elem(dt, [&](auto tlo) {
+      using TL = tag_t<decltype(tlo)>;
+      if (gate) return with_elem(y_dt, [&](auto ty) { return &res_rmsnorm_bwd_kernel<nv, tag_t<decltype(ty)>, TL, true, true, true>; });
       return with_bool(g_add != nullptr, [&](auto add) {
-        using TL = tag_t<decltype(tlo)>;
         if (!y) return &res_rmsnorm_bwd_kernel<nv, float, TL, false, add, false>;   // as in the forward: TY is float without y
         return with_elem(y_dt, [&](auto ty) { return &res_rmsnorm_bwd_kernel<nv, tag_t<decltype(ty)>, TL, true, add, false>; });
       });
@@ -1373,122 +1341,41 @@ extern "C" int nvit_res_rmsnorm_bwd(int dt, const float* g, const void* g_add, c
 }
 
 extern "C" int nvit_res_skip_fwd(int dt, const float* h, const void* y, int y_dt, const float* skip, const float* x,
-                                 float* out, void* out_lo, int M, int C, void* stream) {
+                                 const float* gate, int rows_per_sample, float* out, void* out_lo, int M, int C,
+                                 void* stream) {
   NVIT_REQUIRE(C % 4 == 0 && C <= NVIT_MAX_EMBD && M > 0, "res_skip_fwd: C=%d must be a multiple of 4 and <= %d", C, NVIT_MAX_EMBD);
   NVIT_REQUIRE(dt == NVIT_F32 || dt == NVIT_BF16, "res_skip_fwd: bad dt %d", dt);
   NVIT_REQUIRE(y && (y_dt == NVIT_F32 || y_dt == NVIT_BF16), "res_skip_fwd: y missing or bad y_dt %d", y_dt);
-  ResSkipArgs ar{nullptr, h, y, skip, x, out, out_lo, nullptr, nullptr, M, C, nullptr, 1};
+  NVIT_REQUIRE(gate_args_ok(gate, rows_per_sample, M), "res_skip_fwd: with a gate, M=%d must be a multiple of rows_per_sample=%d", M,
+               rows_per_sample);
+  ResSkipArgs ar{nullptr, h, y, skip, x, out, out_lo, nullptr, nullptr, M, C, gate, gate ? rows_per_sample : 1};
   hipStream_t s = (hipStream_t)stream;
-  const int grid = row_grid(M);
-  ProfScope ps(NVIT_KID_ROWOPS, 0.0, (double)M * C * (12.0 + (y_dt == NVIT_F32 ? 4.0 : 2.0) +
-                                                       (out_lo ? (dt == NVIT_F32 ? 4.0 : 2.0) : 0.0)), s);
-  const auto kernel = with_row_types(C, y_dt, dt, [](auto nv, auto ty, auto tl) {
-    return &res_skip_fwd_kernel<nv, tag_t<decltype(ty)>, tag_t<decltype(tl)>, false>;
+  ProfScope ps(NVIT_KID_ROWOPS, 0.0, (double)M * C * (12.0 + elem_bytes(y_dt) + (out_lo ? elem_bytes(dt) : 0.0)) + gate_bytes(gate, M), s);
+  const auto kernel = with_row_types(C, y_dt, dt, [&](auto nv, auto ty, auto tl) {
+    return with_bool(gate != nullptr, [&](auto gated) { return &res_skip_fwd_kernel<nv, tag_t<decltype(ty)>, tag_t<decltype(tl)>, gated>; });
   });
-  launch(kernel, dim3(grid), dim3(256), 0, s, ar);
+  launch(kernel, dim3(row_grid(M)), dim3(256), 0, s, ar);
   NVIT_CHECK_LAUNCH("res_skip_fwd");
   return NVIT_OK;
 }
 
 extern "C" int nvit_res_skip_bwd(int dt, const float* dout, const float* h, const void* y, int y_dt, const float* skip,
-                                 const float* x, float* dh, void* dh_lo, float* dx, float* part_dskip, int nblk, int M,
-                                 int C, void* stream) {
+                                 const float* x, const float* gate, int rows_per_sample, float* dh, void* dh_lo, float* dx,
+                                 float* part_dskip, int nblk, int M, int C, void* stream) {
   NVIT_REQUIRE(C % 4 == 0 && C <= NVIT_MAX_EMBD && M > 0, "res_skip_bwd: C=%d must be a multiple of 4 and <= %d", C, NVIT_MAX_EMBD);
   NVIT_REQUIRE(nblk > 0 && nblk <= NVIT_MAX_PART_BLOCKS, "res_skip_bwd: nblk out of range");
   NVIT_REQUIRE(dt == NVIT_F32 || dt == NVIT_BF16, "res_skip_bwd: bad dt %d", dt);
   NVIT_REQUIRE(y && (y_dt == NVIT_F32 || y_dt == NVIT_BF16), "res_skip_bwd: y missing or bad y_dt %d", y_dt);
-  ResSkipArgs ar{dout, h, y, skip, x, dx, dh_lo, dh, part_dskip, M, C, nullptr, 1};
+  NVIT_REQUIRE(gate_args_ok(gate, rows_per_sample, M), "res_skip_bwd: with a gate, M=%d must be a multiple of rows_per_sample=%d", M,
+               rows_per_sample);
+  ResSkipArgs ar{dout, h, y, skip, x, dx, dh_lo, dh, part_dskip, M, C, gate, gate ? rows_per_sample : 1};
   hipStream_t s = (hipStream_t)stream;
-  ProfScope ps(NVIT_KID_ROWOPS, 0.0, (double)M * C * (20.0 + (y_dt == NVIT_F32 ? 4.0 : 2.0) +
-                                                       (dh_lo ? (dt == NVIT_F32 ? 4.0 : 2.0) : 0.0)), s);
-  const auto kernel = with_row_types(C, y_dt, dt, [](auto nv, auto ty, auto tl) {
-    return &res_skip_bwd_kernel<nv, tag_t<decltype(ty)>, tag_t<decltype(tl)>, false>;
+  ProfScope ps(NVIT_KID_ROWOPS, 0.0, (double)M * C * (20.0 + elem_bytes(y_dt) + (dh_lo ? elem_bytes(dt) : 0.0)) + gate_bytes(gate, M), s);
+  const auto kernel = with_row_types(C, y_dt, dt, [&](auto nv, auto ty, auto tl) {
+    return with_bool(gate != nullptr, [&](auto gated) { return &res_skip_bwd_kernel<nv, tag_t<decltype(ty)>, tag_t<decltype(tl)>, gated>; });
   });
   launch(kernel, dim3(nblk), dim3(256), 0, s, ar);
   NVIT_CHECK_LAUNCH("res_skip_bwd");
-  return NVIT_OK;
-}
-
-// ---- gated residual kernels of the plain-ViT block chain (stochastic depth).  Built for the calls _StdBlockFn makes: a
-// branch output y is always there, the rms_mlp backward always has its data-gradient addend. ----
-extern "C" int nvit_res_rmsnorm_fwd_gated(int dt, const float* a, const void* y, int y_dt, const float* w, float eps,
-                                          const float* gate, int rows_per_sample, float* out, void* out_lo, float* rstd,
-                                          int M, int C, void* stream) {
-  NVIT_REQUIRE(C % 4 == 0 && C <= NVIT_MAX_EMBD && M > 0, "res_rmsnorm_fwd_gated: C=%d must be a multiple of 4 and <= %d", C, NVIT_MAX_EMBD);
-  NVIT_REQUIRE(dt == NVIT_F32 || dt == NVIT_BF16, "res_rmsnorm_fwd_gated: bad dt %d", dt);
-  NVIT_REQUIRE(y && (y_dt == NVIT_F32 || y_dt == NVIT_BF16), "res_rmsnorm_fwd_gated: y missing or bad y_dt %d", y_dt);
-  NVIT_REQUIRE(gate_args_ok(gate, rows_per_sample, M), "res_rmsnorm_fwd_gated: gate missing, or M=%d is no multiple of rows_per_sample=%d", M, rows_per_sample);
-  ResRmsFwdArgs ar{a, y, w, eps, out, out_lo, rstd, M, C, gate, rows_per_sample};
-  hipStream_t s = (hipStream_t)stream;
-  ProfScope ps(NVIT_KID_ROWOPS, 0.0, (double)M * C * (8.0 + (y_dt == NVIT_F32 ? 4.0 : 2.0) +
-                                                       (out_lo ? (dt == NVIT_F32 ? 4.0 : 2.0) : 0.0)) + 4.0 * M, s);
-  const auto kernel = with_row_types(C, y_dt, dt, [](auto nv, auto ty, auto tl) {
-    return &res_rmsnorm_fwd_kernel<nv, tag_t<decltype(ty)>, tag_t<decltype(tl)>, true, true>;
-  });
-  launch(kernel, dim3(row_grid(M)), dim3(256), 0, s, ar);
-  NVIT_CHECK_LAUNCH("res_rmsnorm_fwd_gated");
-  return NVIT_OK;
-}
-
-extern "C" int nvit_res_rmsnorm_bwd_gated(int dt, const float* g, const void* g_add, const float* a, const void* y, int y_dt,
-                                          const float* w, const float* rstd, const float* gate, int rows_per_sample,
-                                          float* dz, int accum, void* dz_lo, float* part_dw, int nblk, int M, int C,
-                                          void* stream) {
-  NVIT_REQUIRE(C % 4 == 0 && C <= NVIT_MAX_EMBD && M > 0, "res_rmsnorm_bwd_gated: C=%d must be a multiple of 4 and <= %d", C, NVIT_MAX_EMBD);
-  NVIT_REQUIRE(nblk > 0 && nblk <= NVIT_MAX_PART_BLOCKS, "res_rmsnorm_bwd_gated: nblk out of range");
-  NVIT_REQUIRE(dt == NVIT_F32 || dt == NVIT_BF16, "res_rmsnorm_bwd_gated: bad dt %d", dt);
-  NVIT_REQUIRE(y && (y_dt == NVIT_F32 || y_dt == NVIT_BF16), "res_rmsnorm_bwd_gated: y missing or bad y_dt %d", y_dt);
-  NVIT_REQUIRE(g_add, "res_rmsnorm_bwd_gated: built with the addend g_add only");
-  NVIT_REQUIRE(gate_args_ok(gate, rows_per_sample, M), "res_rmsnorm_bwd_gated: gate missing, or M=%d is no multiple of rows_per_sample=%d", M, rows_per_sample);
-  ResRmsBwdArgs ar{g, g_add, a, y, w, rstd, dz, accum, dz_lo, part_dw, M, C, gate, rows_per_sample};
-  hipStream_t s = (hipStream_t)stream;
-  const double tl = dt == NVIT_F32 ? 4.0 : 2.0;
-  ProfScope ps(NVIT_KID_ROWOPS, 0.0, (double)M * C * (12.0 + (y_dt == NVIT_F32 ? 4.0 : 2.0) + tl + (accum ? 4.0 : 0.0) +
-                                                       (dz_lo ? tl : 0.0)) + 4.0 * M, s);
-  const auto kernel = with_row_types(C, y_dt, dt, [](auto nv, auto ty, auto tlo) {
-    return &res_rmsnorm_bwd_kernel<nv, tag_t<decltype(ty)>, tag_t<decltype(tlo)>, true, true, true>;
-  });
-  launch(kernel, dim3(nblk), dim3(256), 0, s, ar);
-  NVIT_CHECK_LAUNCH("res_rmsnorm_bwd_gated");
-  return NVIT_OK;
-}
-
-extern "C" int nvit_res_skip_fwd_gated(int dt, const float* h, const void* y, int y_dt, const float* skip, const float* x,
-                                       const float* gate, int rows_per_sample, float* out, void* out_lo, int M, int C,
-                                       void* stream) {
-  NVIT_REQUIRE(C % 4 == 0 && C <= NVIT_MAX_EMBD && M > 0, "res_skip_fwd_gated: C=%d must be a multiple of 4 and <= %d", C, NVIT_MAX_EMBD);
-  NVIT_REQUIRE(dt == NVIT_F32 || dt == NVIT_BF16, "res_skip_fwd_gated: bad dt %d", dt);
-  NVIT_REQUIRE(y && (y_dt == NVIT_F32 || y_dt == NVIT_BF16), "res_skip_fwd_gated: y missing or bad y_dt %d", y_dt);
-  NVIT_REQUIRE(gate_args_ok(gate, rows_per_sample, M), "res_skip_fwd_gated: gate missing, or M=%d is no multiple of rows_per_sample=%d", M, rows_per_sample);
-  ResSkipArgs ar{nullptr, h, y, skip, x, out, out_lo, nullptr, nullptr, M, C, gate, rows_per_sample};
-  hipStream_t s = (hipStream_t)stream;
-  ProfScope ps(NVIT_KID_ROWOPS, 0.0, (double)M * C * (12.0 + (y_dt == NVIT_F32 ? 4.0 : 2.0) +
-                                                       (out_lo ? (dt == NVIT_F32 ? 4.0 : 2.0) : 0.0)) + 4.0 * M, s);
-  const auto kernel = with_row_types(C, y_dt, dt, [](auto nv, auto ty, auto tl) {
-    return &res_skip_fwd_kernel<nv, tag_t<decltype(ty)>, tag_t<decltype(tl)>, true>;
-  });
-  launch(kernel, dim3(row_grid(M)), dim3(256), 0, s, ar);
-  NVIT_CHECK_LAUNCH("res_skip_fwd_gated");
-  return NVIT_OK;
-}
-
-extern "C" int nvit_res_skip_bwd_gated(int dt, const float* dout, const float* h, const void* y, int y_dt, const float* skip,
-                                       const float* x, const float* gate, int rows_per_sample, float* dh, void* dh_lo,
-                                       float* dx, float* part_dskip, int nblk, int M, int C, void* stream) {
-  NVIT_REQUIRE(C % 4 == 0 && C <= NVIT_MAX_EMBD && M > 0, "res_skip_bwd_gated: C=%d must be a multiple of 4 and <= %d", C, NVIT_MAX_EMBD);
-  NVIT_REQUIRE(nblk > 0 && nblk <= NVIT_MAX_PART_BLOCKS, "res_skip_bwd_gated: nblk out of range");
-  NVIT_REQUIRE(dt == NVIT_F32 || dt == NVIT_BF16, "res_skip_bwd_gated: bad dt %d", dt);
-  NVIT_REQUIRE(y && (y_dt == NVIT_F32 || y_dt == NVIT_BF16), "res_skip_bwd_gated: y missing or bad y_dt %d", y_dt);
-  NVIT_REQUIRE(gate_args_ok(gate, rows_per_sample, M), "res_skip_bwd_gated: gate missing, or M=%d is no multiple of rows_per_sample=%d", M, rows_per_sample);
-  ResSkipArgs ar{dout, h, y, skip, x, dx, dh_lo, dh, part_dskip, M, C, gate, rows_per_sample};
-  hipStream_t s = (hipStream_t)stream;
-  ProfScope ps(NVIT_KID_ROWOPS, 0.0, (double)M * C * (20.0 + (y_dt == NVIT_F32 ? 4.0 : 2.0) +
-                                                       (dh_lo ? (dt == NVIT_F32 ? 4.0 : 2.0) : 0.0)) + 4.0 * M, s);
-  const auto kernel = with_row_types(C, y_dt, dt, [](auto nv, auto ty, auto tl) {
-    return &res_skip_bwd_kernel<nv, tag_t<decltype(ty)>, tag_t<decltype(tl)>, true>;
-  });
-  launch(kernel, dim3(nblk), dim3(256), 0, s, ar);
-  NVIT_CHECK_LAUNCH("res_skip_bwd_gated");
   return NVIT_OK;
 }
 

@@ -2,7 +2,7 @@
 
 One gate per sample, block and branch (0 attention, 1 MLP): 0.0 when the branch is dropped for that sample, else 1.0, or
 1 / keep with scale_by_keep.  `DropPath.draw` is one launch (nvit_droppath_draw) that writes the whole fp32 table
-[2*n_layer, B]; the gated row kernels (nvit_lerp_fwd_gated / nvit_lerp_bwd_gated) read row 2*l + br for block l.  Like the
+[2*n_layer, B]; the row kernels read row 2*l + br for block l (their `gate` argument: nvit_lerp_*, nvit_res_*).  Like the
 input pipeline's draws it is counter based (Philox4x32-10 over the sample's global index, the step and the row) and its
 step counter lives on the device, advanced by the draw kernel: a captured train step draws afresh at every replay with
 no host code in between, and (seed, step) resumes a run exactly.  DESIGN.md §4 has the semantics.

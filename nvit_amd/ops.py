@@ -88,7 +88,8 @@ FUSE_MIN_ELEMS = 256 * 256 * 64   # below this output size the fused persistent 
 
 
 def fusable(dt: int, M: int, N: int, K: int) -> bool:
-    """True when the fused-epilogue persistent GEMM (nvit_gemm_nt_swiglu / _qknorm) can and should be used."""
+    """True when the fused-epilogue persistent GEMM (nvit_gemm_nt_swiglu / _swiglu_act / _qknorm, each with or without a
+    bias) can and should be used."""
     return bool(_lib.load().nvit_gemm_nt_fusable(dt, M, N, K)) and M * N >= FUSE_MIN_ELEMS
 
 
@@ -110,8 +111,8 @@ def gemm_nt_swiglu(A: Tensor, B: Tensor, M: int, F: int, K: int, gs: Optional[Te
     _chk_fused_bias(bias, 2 * F, A, "gemm_nt_swiglu")
     uv = torch.empty((M, 2 * F), device=A.device, dtype=torch.bfloat16)
     xm = torch.empty((M, F), device=A.device, dtype=torch.bfloat16)
-    check(_lib.load().nvit_gemm_nt_swiglu_bias(dt_of(A), _p(A), A.stride(0), _p(B), B.stride(0), _p(uv), _p(xm), M, F, K,
-                                               _p(gs), gscale, _p(bias), _s()), "nvit_gemm_nt_swiglu_bias")
+    check(_lib.load().nvit_gemm_nt_swiglu(dt_of(A), _p(A), A.stride(0), _p(B), B.stride(0), _p(uv), _p(xm), M, F, K,
+                                          _p(gs), gscale, _p(bias), _s()), "nvit_gemm_nt_swiglu")
     return uv, xm
 
 
@@ -121,8 +122,8 @@ def gemm_nt_swiglu_act(A: Tensor, B: Tensor, M: int, F: int, K: int, gs: Optiona
     _chk_dev(A, B)
     _chk_fused_bias(bias, 2 * F, A, "gemm_nt_swiglu_act")
     xm = torch.empty((M, F), device=A.device, dtype=torch.bfloat16)
-    check(_lib.load().nvit_gemm_nt_swiglu_act_bias(dt_of(A), _p(A), A.stride(0), _p(B), B.stride(0), _p(xm), M, F, K,
-                                                   _p(gs), gscale, _p(bias), _s()), "nvit_gemm_nt_swiglu_act_bias")
+    check(_lib.load().nvit_gemm_nt_swiglu_act(dt_of(A), _p(A), A.stride(0), _p(B), B.stride(0), _p(xm), M, F, K,
+                                              _p(gs), gscale, _p(bias), _s()), "nvit_gemm_nt_swiglu_act")
     return xm
 
 
@@ -169,9 +170,9 @@ def gemm_nt_qknorm(A: Tensor, B: Tensor, M: int, K: int, nparts: int, part0: int
     if bufs is None:
         bufs = qk_buffers(dt_of(A), Bsz, T, H, d, A.device, norm=sqk is not None)
     qh, kh, vh, rq, rk = bufs
-    check(_lib.load().nvit_gemm_nt_qknorm_bias(dt_of(A), _p(A), A.stride(0), _p(B), B.stride(0), M, K, nparts, part0,
-                                               _p(sqk), c_q, q_prescale, _p(qh), _p(kh), _p(vh), _p(rq), _p(rk), T, H,
-                                               d, _p(bias), _s()), "nvit_gemm_nt_qknorm_bias")
+    check(_lib.load().nvit_gemm_nt_qknorm(dt_of(A), _p(A), A.stride(0), _p(B), B.stride(0), M, K, nparts, part0,
+                                          _p(sqk), c_q, q_prescale, _p(qh), _p(kh), _p(vh), _p(rq), _p(rk), T, H, d,
+                                          _p(bias), _s()), "nvit_gemm_nt_qknorm")
     return bufs
 
 
@@ -246,9 +247,12 @@ def _part_blocks(nblk: Optional[int], default: int, name: str) -> int:
     return nblk
 
 
-def _chk_gate(gate: Tensor, M: int, ref: Tensor, what: str) -> int:
-    """-> rows_per_sample of a gated row kernel: `gate` holds one fp32 gate per sample (a row of DropPath's table), the
-    [M, C] operands hold M / gate.numel() consecutive rows per sample.  The kernel indexes it unchecked."""
+def _chk_gate(gate: Optional[Tensor], M: int, ref: Tensor, what: str) -> int:
+    """-> rows_per_sample of a row kernel's optional gate (1 without one): `gate` holds one fp32 gate per sample (a row of
+    DropPath's table), the [M, C] operands hold M / gate.numel() consecutive rows per sample.  The kernel indexes it
+    unchecked."""
+    if gate is None:
+        return 1
     if (not isinstance(gate, Tensor) or gate.dtype != torch.float32 or gate.dim() != 1 or not gate.is_contiguous()
             or gate.device != ref.device or gate.numel() < 1 or M % gate.numel()):
         raise ValueError(f"{what}: gate must be a contiguous fp32 vector on {ref.device} whose length divides M={M}")
@@ -262,13 +266,9 @@ def lerp_fwd(dt: int, h: Tensor, y: Tensor, alpha: Tensor, c_a: float, skip_x: O
     M, Cc = h.shape
     out = torch.empty_like(h)
     out_lo = torch.empty((M, Cc), device=h.device, dtype=tdtype(dt)) if want_lo else None
-    if gate is not None:
-        T = _chk_gate(gate, M, h, "lerp_fwd")
-        check(_lib.load().nvit_lerp_fwd_gated(dt, _p(h), _p(y), dt_of(y), _p(alpha), c_a, _p(skip_x), _p(skip), _p(gate),
-                                              T, _p(out), _p(out_lo), M, Cc, _s()), "nvit_lerp_fwd_gated")
-        return out, out_lo
-    check(_lib.load().nvit_lerp_fwd(dt, _p(h), _p(y), dt_of(y), _p(alpha), c_a, _p(skip_x), _p(skip), _p(out),
-                                    _p(out_lo), M, Cc, _s()), "nvit_lerp_fwd")
+    T = _chk_gate(gate, M, h, "lerp_fwd")
+    check(_lib.load().nvit_lerp_fwd(dt, _p(h), _p(y), dt_of(y), _p(alpha), c_a, _p(skip_x), _p(skip), _p(gate), T,
+                                    _p(out), _p(out_lo), M, Cc, _s()), "nvit_lerp_fwd")
     return out, out_lo
 
 
@@ -288,17 +288,16 @@ def lerp_bwd(dt: int, dout: Tensor, h: Tensor, y: Tensor, alpha: Tensor, c_a: fl
         dh = torch.empty_like(h)
         accum_dh = False
     gated = gate is not None
-    if gated:
-        T = _chk_gate(gate, M, h, "lerp_bwd")
-        if (skip_x is not None) == bool(accum_dh):
-            raise ValueError("lerp_bwd: the gated kernel takes skip_x without accum_dh, or accum_dh without skip_x")
+    T = _chk_gate(gate, M, h, "lerp_bwd")
+    if gated and (skip_x is not None) == bool(accum_dh):
+        raise ValueError("lerp_bwd: the gated kernel takes skip_x without accum_dh, or accum_dh without skip_x")
     # grid = the workgroups resident at once for this kernel variant (a second, partly filled round of a 1024-block
     # grid cost 1.8 ms per Base step)
     key = (dt, dt_of(y), Cc, dout_add is not None, skip_x is not None, bool(accum_dh), gated)
     nres = _LERP_BWD_BLOCKS.get(key)
     if nres is None:
-        blocks = _lib.load().nvit_lerp_bwd_gated_blocks if gated else _lib.load().nvit_lerp_bwd_blocks
-        nres = int(blocks(dt, dt_of(y), Cc, int(key[3]), int(key[4]), int(key[5]))) or PART_BLOCKS
+        nres = int(_lib.load().nvit_lerp_bwd_blocks(dt, dt_of(y), Cc, int(key[3]), int(key[4]), int(key[5]),
+                                                    int(gated))) or PART_BLOCKS
         _LERP_BWD_BLOCKS[key] = nres
     nblk = _part_blocks(nblk, min(nres, math.ceil(M / ROW_WAVES)), "lerp_bwd")
     dy = torch.empty_like(h) if want_dy_f32 else None
@@ -306,13 +305,8 @@ def lerp_bwd(dt: int, dout: Tensor, h: Tensor, y: Tensor, alpha: Tensor, c_a: fl
     dskip_x = torch.empty_like(h) if skip_x is not None else None
     part = torch.empty((ROW_WAVES * nblk, Cc), device=dev, dtype=torch.float32)   # one row of column partials per wave
     pskip = torch.empty((ROW_WAVES * nblk,), device=dev, dtype=torch.float32) if skip_x is not None else None
-    if gated:
-        check(_lib.load().nvit_lerp_bwd_gated(dt, _p(dout), _p(dout_add), _p(h), _p(y), dt_of(y), _p(alpha), c_a, _p(skip_x),
-                                              _p(skip), _p(gate), T, _p(dh), int(accum_dh), _p(dy), _p(dy_lo), _p(dskip_x),
-                                              _p(part), _p(pskip), nblk, M, Cc, _s()), "nvit_lerp_bwd_gated")
-        return dh, dy, dy_lo, dskip_x, part, pskip
     check(_lib.load().nvit_lerp_bwd(dt, _p(dout), _p(dout_add), _p(h), _p(y), dt_of(y), _p(alpha), c_a, _p(skip_x), _p(skip),
-                                    _p(dh), int(accum_dh), _p(dy), _p(dy_lo), _p(dskip_x), _p(part), _p(pskip),
+                                    _p(gate), T, _p(dh), int(accum_dh), _p(dy), _p(dy_lo), _p(dskip_x), _p(part), _p(pskip),
                                     nblk, M, Cc, _s()), "nvit_lerp_bwd")
     return dh, dy, dy_lo, dskip_x, part, pskip
 
@@ -374,15 +368,11 @@ def res_rmsnorm_fwd(dt: int, a: Tensor, y: Optional[Tensor], w: Tensor, eps: flo
     out = torch.empty_like(a)
     out_lo = torch.empty((M, Cc), device=a.device, dtype=tdtype(dt)) if want_lo else None
     rstd = torch.empty((M,), device=a.device, dtype=torch.float32)
-    if gate is not None:
-        if y is None:
-            raise ValueError("res_rmsnorm_fwd: a gate needs the branch output y")
-        T = _chk_gate(gate, M, a, "res_rmsnorm_fwd")
-        check(_lib.load().nvit_res_rmsnorm_fwd_gated(dt, _p(a), _p(y), dt_of(y), _p(w), eps, _p(gate), T, _p(out), _p(out_lo),
-                                                     _p(rstd), M, Cc, _s()), "nvit_res_rmsnorm_fwd_gated")
-        return out, out_lo, rstd
-    check(_lib.load().nvit_res_rmsnorm_fwd(dt, _p(a), _p(y), dt_of(y) if y is not None else F32, _p(w), eps, _p(out),
-                                           _p(out_lo), _p(rstd), M, Cc, _s()), "nvit_res_rmsnorm_fwd")
+    if gate is not None and y is None:
+        raise ValueError("res_rmsnorm_fwd: a gate needs the branch output y")
+    T = _chk_gate(gate, M, a, "res_rmsnorm_fwd")
+    check(_lib.load().nvit_res_rmsnorm_fwd(dt, _p(a), _p(y), dt_of(y) if y is not None else F32, _p(w), eps, _p(gate), T,
+                                           _p(out), _p(out_lo), _p(rstd), M, Cc, _s()), "nvit_res_rmsnorm_fwd")
     return out, out_lo, rstd
 
 
@@ -404,17 +394,12 @@ def res_rmsnorm_bwd(dt: int, g: Tensor, a: Tensor, y: Optional[Tensor], w: Tenso
     nblk = _part_blocks(nblk, _row_part_blocks(M), "res_rmsnorm_bwd")
     dz_lo = torch.empty((M, Cc), device=a.device, dtype=tdtype(dt)) if want_lo else None
     part = torch.empty((ROW_WAVES * nblk, Cc), device=a.device, dtype=torch.float32)
-    if gate is not None:
-        if y is None or g_add is None:
-            raise ValueError("res_rmsnorm_bwd: the gated kernel needs the branch output y and the addend g_add")
-        T = _chk_gate(gate, M, a, "res_rmsnorm_bwd")
-        check(_lib.load().nvit_res_rmsnorm_bwd_gated(dt, _p(g), _p(g_add), _p(a), _p(y), dt_of(y), _p(w), _p(rstd), _p(gate),
-                                                     T, _p(dz), int(accum), _p(dz_lo), _p(part), nblk, M, Cc, _s()),
-              "nvit_res_rmsnorm_bwd_gated")
-        return dz, dz_lo, part
+    if gate is not None and (y is None or g_add is None):
+        raise ValueError("res_rmsnorm_bwd: the gated kernel needs the branch output y and the addend g_add")
+    T = _chk_gate(gate, M, a, "res_rmsnorm_bwd")
     check(_lib.load().nvit_res_rmsnorm_bwd(dt, _p(g), _p(g_add), _p(a), _p(y), dt_of(y) if y is not None else F32, _p(w),
-                                           _p(rstd), _p(dz), int(accum), _p(dz_lo), _p(part), nblk, M, Cc, _s()),
-          "nvit_res_rmsnorm_bwd")
+                                           _p(rstd), _p(gate), T, _p(dz), int(accum), _p(dz_lo), _p(part), nblk, M, Cc,
+                                           _s()), "nvit_res_rmsnorm_bwd")
     return dz, dz_lo, part
 
 
@@ -427,13 +412,9 @@ def res_skip_fwd(dt: int, h: Tensor, y: Tensor, skip: Tensor, x: Tensor, want_lo
     _chk_vec(1, skip, name="res_skip_fwd")
     out = torch.empty_like(h)
     out_lo = torch.empty((M, Cc), device=h.device, dtype=tdtype(dt)) if want_lo else None
-    if gate is not None:
-        T = _chk_gate(gate, M, h, "res_skip_fwd")
-        check(_lib.load().nvit_res_skip_fwd_gated(dt, _p(h), _p(y), dt_of(y), _p(skip), _p(x), _p(gate), T, _p(out),
-                                                  _p(out_lo), M, Cc, _s()), "nvit_res_skip_fwd_gated")
-        return out, out_lo
-    check(_lib.load().nvit_res_skip_fwd(dt, _p(h), _p(y), dt_of(y), _p(skip), _p(x), _p(out), _p(out_lo), M, Cc, _s()),
-          "nvit_res_skip_fwd")
+    T = _chk_gate(gate, M, h, "res_skip_fwd")
+    check(_lib.load().nvit_res_skip_fwd(dt, _p(h), _p(y), dt_of(y), _p(skip), _p(x), _p(gate), T, _p(out), _p(out_lo), M, Cc,
+                                        _s()), "nvit_res_skip_fwd")
     return out, out_lo
 
 
@@ -449,13 +430,9 @@ def res_skip_bwd(dt: int, dout: Tensor, h: Tensor, y: Tensor, skip: Tensor, x: T
     dx = torch.empty_like(h)
     dh_lo = torch.empty((M, Cc), device=h.device, dtype=tdtype(dt)) if want_lo else None
     part = torch.empty((ROW_WAVES * nblk,), device=h.device, dtype=torch.float32)
-    if gate is not None:
-        T = _chk_gate(gate, M, h, "res_skip_bwd")
-        check(_lib.load().nvit_res_skip_bwd_gated(dt, _p(dout), _p(h), _p(y), dt_of(y), _p(skip), _p(x), _p(gate), T, _p(dh),
-                                                  _p(dh_lo), _p(dx), _p(part), nblk, M, Cc, _s()), "nvit_res_skip_bwd_gated")
-        return dh, dh_lo, dx, part
-    check(_lib.load().nvit_res_skip_bwd(dt, _p(dout), _p(h), _p(y), dt_of(y), _p(skip), _p(x), _p(dh), _p(dh_lo), _p(dx),
-                                        _p(part), nblk, M, Cc, _s()), "nvit_res_skip_bwd")
+    T = _chk_gate(gate, M, h, "res_skip_bwd")
+    check(_lib.load().nvit_res_skip_bwd(dt, _p(dout), _p(h), _p(y), dt_of(y), _p(skip), _p(x), _p(gate), T, _p(dh), _p(dh_lo),
+                                        _p(dx), _p(part), nblk, M, Cc, _s()), "nvit_res_skip_bwd")
     return dh, dh_lo, dx, part
 
 

@@ -1,6 +1,6 @@
 """Oracles of the fused-epilogue GEMM tests (a plain helper module; test_epilogue_check.py checks it on the CPU,
 test_gpu_epilogue_bounds.py uses it against the four fused launches of the persistent 256x256 NT GEMM:
-nvit_gemm_nt_swiglu[_bias] (EPI 3), nvit_gemm_nt_swiglu_act[_bias] (EPI 6), nvit_gemm_nt_qknorm[_bias] (EPI 4) and
+nvit_gemm_nt_swiglu (EPI 3), nvit_gemm_nt_swiglu_act (EPI 6), nvit_gemm_nt_qknorm (EPI 4), each with and without a bias, and
 nvit_gemm_nt_swiglu_bwd (EPI 5)).
 
 The composition of two oracles that exist: A and B are the bf16 integers of gemm_check.nt_exact (|a|, |b| <= 2; a case

@@ -1,14 +1,13 @@
-"""CPU: the interface of the bias-taking fused GEMM epilogues - the three C entry points are declared, exported and
-bound (test_cabi_symbols.py checks that header and binding agree on every symbol; this one names them), the ops
-wrappers take `bias`, and the Base-with-bias configuration exists.  No compute calls."""
+"""CPU: the interface of the bias-taking fused GEMM epilogues - the three C entry points take an optional bias and
+are declared, exported and bound (test_cabi_symbols.py checks that header and binding agree on every symbol; this one
+names them), the ops wrappers take `bias`, and the Base-with-bias configuration exists.  No compute calls."""
 import ctypes
 import inspect
 import os
 import re
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW = {"nvit_gemm_nt_swiglu_bias": "nvit_gemm_nt_swiglu", "nvit_gemm_nt_swiglu_act_bias": "nvit_gemm_nt_swiglu_act",
-       "nvit_gemm_nt_qknorm_bias": "nvit_gemm_nt_qknorm"}
+FUSED = ("nvit_gemm_nt_swiglu", "nvit_gemm_nt_swiglu_act", "nvit_gemm_nt_qknorm")
 
 
 def test_bias_entry_points_are_declared_exported_and_bound():
@@ -16,16 +15,22 @@ def test_bias_entry_points_are_declared_exported_and_bound():
     h = open(os.path.join(ROOT, "include", "nvit_hip.h")).read()
     h = re.sub(r"/\*.*?\*/", "", h, flags=re.S)
     lib = _lib.load()
-    for name, sibling in NEW.items():
+    for name in FUSED:
         m = re.search(r"\bint\s+%s\s*\(([^;]*?)\)\s*;" % name, h)
         assert m, f"{name} is not declared in include/nvit_hip.h"
         args = [a.strip() for a in m.group(1).split(",")]
-        # the sibling's arguments plus `const float* bias` before the stream
+        # `const float* bias` (NULL: none) before the stream
         assert re.fullmatch(r"const\s+float\s*\*\s*bias", args[-2]), (name, args[-2:])
         assert re.fullmatch(r"void\s*\*\s*stream", args[-1]), (name, args[-1])
         assert hasattr(lib, name), f"{name} is not exported"
-        sig, sib = _lib.SIGNATURES[name], _lib.SIGNATURES[sibling]
-        assert sig[:-2] == sib[:-1] and sig[-2] is ctypes.c_void_p and sig[-1] is sib[-1], name
+        sig = _lib.SIGNATURES[name]
+        assert len(sig) == len(args) and sig[-2] is ctypes.c_void_p and sig[-1] is ctypes.c_void_p, name
+    # one name per epilogue: no second entry point for the biased form, in the header, the binding or the library
+    twin = re.compile(r"nvit_gemm_nt_\w+_bias\b")
+    assert not twin.search(h)
+    assert not [n for n in _lib.SIGNATURES if twin.fullmatch(n)]
+    binary = open(_lib.LIB_PATH, "rb").read()           # the dynamic string table holds every exported name
+    assert b"\0nvit_gemm_nt_swiglu\0" in binary and not re.search(rb"nvit_gemm_nt_\w+_bias\b", binary)
 
 
 def test_ops_wrappers_take_a_bias():

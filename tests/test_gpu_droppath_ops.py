@@ -1,6 +1,6 @@
 """GPU tests, op level, of stochastic depth: nvit_droppath_draw against its numpy twin (droppath_ref.draw) bit for bit,
-and the six gated row kernels (nvit_lerp_*_gated of the nViT blocks, nvit_res_rmsnorm_*_gated and nvit_res_skip_*_gated of
-the plain-ViT blocks) through nvit_amd.ops - every width class, 1, 3 and 49 rows per sample with M no multiple of the rows
+and the six row kernels with a gate (nvit_lerp_* of the nViT blocks, nvit_res_rmsnorm_* and nvit_res_skip_* of the
+plain-ViT blocks) through nvit_amd.ops - every width class, 1, 3 and 49 rows per sample with M no multiple of the rows
 per workgroup, waves that walk rows of several samples (explicit nblk), a forward grid that wraps, fp32 and bf16 y and
 copies, and the switch combinations the block chain launches - against: gates all 1 = the plain kernel's bits; gates all
 0 = no gradient into the branch and the plain kernel's output at alpha = 0 (LERP) or y = 0 (residual); mixed gates inside

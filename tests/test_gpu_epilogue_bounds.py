@@ -1,5 +1,5 @@
 """The four fused-epilogue launches of the persistent 256x256 NT GEMM against the fp64 oracles of epilogue_check.py:
-nvit_gemm_nt_swiglu[_bias] (EPI 3), nvit_gemm_nt_swiglu_act[_bias] (EPI 6), nvit_gemm_nt_qknorm[_bias] (EPI 4) and
+nvit_gemm_nt_swiglu (EPI 3), nvit_gemm_nt_swiglu_act (EPI 6), nvit_gemm_nt_qknorm (EPI 4), each with and without a bias, and
 nvit_gemm_nt_swiglu_bwd (EPI 5), called through the C entry points on buffers of this test.
 
 Operands are exact integers (the accumulator entering the epilogue is known exactly), views inside NaN-filled buffers
@@ -132,15 +132,15 @@ class SwigluFwd:
         r1 = self.M if r1 is None else r1
         A = self.A[r0:r1]
         if epi == 3:
-            _check(lib().nvit_gemm_nt_swiglu_bias(DT_BF16, p(A), A.stride(0), p(self.B), self.B.stride(0),
-                                                  p(o["uv"].view[r0:]), p(o["xm"].view[r0:]), r1 - r0, self.F, self.K,
-                                                  p(self.gs), self.d["gscale"], p(self.bias), stream()),
-                   "nvit_gemm_nt_swiglu_bias")
+            _check(lib().nvit_gemm_nt_swiglu(DT_BF16, p(A), A.stride(0), p(self.B), self.B.stride(0),
+                                             p(o["uv"].view[r0:]), p(o["xm"].view[r0:]), r1 - r0, self.F, self.K,
+                                             p(self.gs), self.d["gscale"], p(self.bias), stream()),
+                   "nvit_gemm_nt_swiglu")
         else:
-            _check(lib().nvit_gemm_nt_swiglu_act_bias(DT_BF16, p(A), A.stride(0), p(self.B), self.B.stride(0),
-                                                      p(o["xm"].view[r0:]), r1 - r0, self.F, self.K, p(self.gs),
-                                                      self.d["gscale"], p(self.bias), stream()),
-                   "nvit_gemm_nt_swiglu_act_bias")
+            _check(lib().nvit_gemm_nt_swiglu_act(DT_BF16, p(A), A.stride(0), p(self.B), self.B.stride(0),
+                                                 p(o["xm"].view[r0:]), r1 - r0, self.F, self.K, p(self.gs),
+                                                 self.d["gscale"], p(self.bias), stream()),
+                   "nvit_gemm_nt_swiglu_act")
 
     def verify(self, o, launch, label, rows=None):
         c = ec.swiglu_fwd_c(self.d, rows)
@@ -221,11 +221,11 @@ class QkFused:
         assert r0 % self.T == 0 and (r1 - r0) % self.T == 0
         A = self.A[r0:r1]
         h0 = r0 // self.T * self.H * self.T                # first row of batch r0 / T in the [B * H * T, 64] view
-        _check(lib().nvit_gemm_nt_qknorm_bias(DT_BF16, p(A), A.stride(0), p(self.B), self.B.stride(0), r1 - r0, self.K,
-                                              self.d["nparts"], self.d["part0"], p(self.sqk), self.d["c_q"], prescale(),
-                                              p(o["qh"].view[h0:]), p(o["kh"].view[h0:]), p(o["vh"].view[h0:]),
-                                              p(o["rq"].view[r0:]), p(o["rk"].view[r0:]), self.T, self.H, ec.HEAD,
-                                              p(self.bias), stream()), "nvit_gemm_nt_qknorm_bias")
+        _check(lib().nvit_gemm_nt_qknorm(DT_BF16, p(A), A.stride(0), p(self.B), self.B.stride(0), r1 - r0, self.K,
+                                         self.d["nparts"], self.d["part0"], p(self.sqk), self.d["c_q"], prescale(),
+                                         p(o["qh"].view[h0:]), p(o["kh"].view[h0:]), p(o["vh"].view[h0:]),
+                                         p(o["rq"].view[r0:]), p(o["rk"].view[r0:]), self.T, self.H, ec.HEAD,
+                                         p(self.bias), stream()), "nvit_gemm_nt_qknorm")
 
     def verify(self, o, label, rows=None):
         c = ec.qk_fused_c(self.d, rows)

@@ -68,7 +68,7 @@ def test_gemm_nt_swiglu_act_is_the_fused_gate_bit_for_bit(M, F, K, use_gs, dynam
     buf = torch.full(((M + 2 * PAD) * F,), 0x7F7F, dtype=torch.int16, device=d_)
     inner = buf[PAD * F:(PAD + M) * F]
     check(load().nvit_gemm_nt_swiglu_act(BF16, A.data_ptr(), K, W.data_ptr(), K, inner.data_ptr(), M, F, K,
-                                         None if gs is None else gs.data_ptr(), gscale,
+                                         None if gs is None else gs.data_ptr(), gscale, None,
                                          torch.cuda.current_stream().cuda_stream), "nvit_gemm_nt_swiglu_act")
     torch.cuda.synchronize()
     assert torch.equal(inner.view(torch.bfloat16).reshape(M, F), xm)
