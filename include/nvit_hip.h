@@ -561,6 +561,21 @@ int nvit_crop_draw(uint64_t seed, int64_t* step, int64_t first_index, const doub
 int64_t nvit_crop_ws_bytes(int B, int Hs, int Ws, int C, int size, int interp);
 int nvit_crop_apply(const void* in, const int* table, void* out, void* ws, int64_t ws_bytes, int B, int Hs, int Ws, int C,
                     int size, int interp, void* stream);
+/* On-device Resize + CenterCrop for evaluation batches (tests/center_crop_ref.py): in uint8 [B,Hs,Ws,C], C in
+ * {1,3}, one source size per batch, sides up to NVIT_CROP_MAX_SRC.  Image b is Pillow's resize((W2, H2), BILINEAR |
+ * BICUBIC).crop((left, top, left + size, top + size)), bit for bit, of which only the window is computed: two launches,
+ * the horizontal pass over the window's columns of the source rows that the window's vertical taps read (uint8
+ * intermediate), the vertical pass over the window's rows.  H2, W2, top, left, size are host integers: size % 4 == 0 in
+ * 4..NVIT_AUG_MAX_SIDE, size <= H2, W2 <= NVIT_AUG_MAX_SIDE, 0 <= top <= H2 - size, 0 <= left <= W2 - size, B up to
+ * NVIT_CROP_MAX_BATCH; anything else is refused, nothing is clamped.  There is no table, no draw and no device state.
+ * Outputs, either may be NULL but not both, both written by the vertical pass: out_u8 uint8 [B,size,size,C] (4-byte
+ * aligned) and out_f32 fp32 [B,C,size,size] (16-byte aligned) = (x / 255 - mean) / std with the roundings of
+ * nvit_normalize_images (std > 0).  ws (16-byte aligned) holds the tap sets and the intermediate, ws_bytes >=
+ * nvit_center_crop_ws_bytes(...), which is -1 for a refused shape and is sized by the rows read, not by Hs. */
+int64_t nvit_center_crop_ws_bytes(int B, int Hs, int Ws, int C, int H2, int W2, int top, int left, int size, int interp);
+int nvit_center_crop_apply(const void* in, void* out_u8, float* out_f32, void* ws, int64_t ws_bytes, int B, int Hs, int Ws,
+                           int C, int H2, int W2, int top, int left, int size, int interp, float mean, float std,
+                           void* stream);
 /* On-device RandomErasing (timm's, count 1, per image; tests/crop_ref.py) on the fp32 [B,C,H,W] model input.
  * nvit_erase_draw: table int32 [B,NVIT_ERASE_ROW] = (on, top, left, h, w, noise key low, noise key high, 0).  Philox as in
  * nvit_crop_draw under the erasing's own domain: a = NVIT_CROP_ATTEMPTS is the gate (r0 against prob), a = 0.. the attempts

@@ -22,7 +22,7 @@ def __getattr__(name):
     if name in ("Mixup", "MixedBatch", "MixedTargets"):
         from . import mix
         return getattr(mix, name)
-    if name in ("RandomResizedCrop", "CroppedBatch", "RandomErasing", "ErasedBatch"):
+    if name in ("RandomResizedCrop", "CroppedBatch", "RandomErasing", "ErasedBatch", "ResizeCenterCrop", "CenterCroppedBatch"):
         from . import crop
         return getattr(crop, name)
     if name == "ModelEma":

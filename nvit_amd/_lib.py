@@ -115,6 +115,8 @@ SIGNATURES = {
     "nvit_crop_draw": [C.c_uint64, _vp, _i64, _vp, C.c_double, C.c_double, C.c_double, C.c_double, _f, _vp, _i, _i, _i, _vp],
     "nvit_crop_ws_bytes": [_i, _i, _i, _i, _i, _i],
     "nvit_crop_apply": [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _vp],
+    "nvit_center_crop_ws_bytes": [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i],
+    "nvit_center_crop_apply": [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _vp],
     "nvit_erase_draw": [C.c_uint64, _vp, _i64, _vp, C.c_double, C.c_double, _f, _vp, _i, _i, _i, _vp],
     "nvit_erase_apply": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "nvit_scale_cols": [_vp, _i, _vp, _f, _vp, _i, _i, _i, _i, _vp],
@@ -169,7 +171,8 @@ SIGNATURES = {
     "nvit_set_attn_dkv_asm": [_i],
 }
 _RESTYPES = {"nvit_last_error": C.c_char_p, "nvit_prof_name": C.c_char_p, "nvit_prof_enable": None, "nvit_prof_select": None,
-             "nvit_xgmi_chunk": C.c_int64, "nvit_xgmi_flag_bytes": C.c_int64, "nvit_crop_ws_bytes": C.c_int64}
+             "nvit_xgmi_chunk": C.c_int64, "nvit_xgmi_flag_bytes": C.c_int64, "nvit_crop_ws_bytes": C.c_int64,
+             "nvit_center_crop_ws_bytes": C.c_int64}
 
 _lib = None
 

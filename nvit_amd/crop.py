@@ -13,6 +13,10 @@ if its flip bit is set; the box is torchvision's `get_params` (ten attempts, the
 RandomErasing: timm's, count 1, per image, on the normalised fp32 batch: a box of `area` x the image at a log-uniform
 aspect is overwritten by 0 ("const") or by N(0,1) noise ("pixel").  Two launches (nvit_erase_draw, nvit_erase_apply).
 
+ResizeCenterCrop: evaluation's side of the same pipeline, timm's `transforms_imagenet_eval` for a square target: image b
+is `PIL.Image.resize((W2, H2)).crop(window)`, bit for bit, normalised; only the window is computed, nothing is drawn.  Two
+launches (nvit_center_crop_apply).  `predict`, `validate`, `estimate_loss` and `GraphedEval` take `rcc.batch(u8)` as X.
+
 Both draws are the counter-based generator of augment.py (Philox4x32-10; counter = (first_index + image, step), key = seed
 with the class's own domain constant per attempt in its high word): an image's box depends only on (seed, global index,
 step), whatever the batch split.  No transcendental runs on the device: exp(U(log r0, log r1)) comes from a table of
@@ -251,6 +255,142 @@ class RandomResizedCrop(DeviceStepCounter):
             raise ValueError("params_for: one flip per box")
         t = torch.tensor([[*box, f, 0, 0, 0] for box, f in zip(boxes, flips)], dtype=torch.int32)
         return t if self.device is None else t.to(self.device)
+
+
+# ---------------------------------------------------------------------------------------------- Resize + CenterCrop
+CROP_MODES = ("center", "squash")
+
+
+class CenterCroppedBatch:
+    """A stored uint8 [B,Hs,Ws,C] batch together with the ResizeCenterCrop that cuts it: what `rcc.batch(u8)` returns and
+    `predict`, `validate`, `estimate_loss` and `GraphedEval` accept in place of X.  `.shape` is that of the model input,
+    [B,C,size,size]."""
+
+    def __init__(self, crop: "ResizeCenterCrop", u8: Tensor):
+        B, Hs, Ws, C = crop._check_source(u8)
+        self.crop, self.u8 = crop, u8
+        self._shape = torch.Size((B, C, crop.size, crop.size))
+
+    @property
+    def shape(self):
+        return self._shape
+
+    @property
+    def device(self):
+        return self.u8.device
+
+    def cropped(self) -> Tensor:
+        """The fp32 model input: the transform's two launches on the current stream."""
+        return self.crop(self.u8)
+
+
+class ResizeCenterCrop:
+    """ResizeCenterCrop(size, crop_pct=0.875, interpolation="bilinear", crop_mode="center", mean=0.5, std=0.5)
+
+    timm's `transforms_imagenet_eval` for a square target, on a uint8 [B,Hs,Ws,C] batch (C 1 or 3, one source size per
+    batch): Resize to scale_size = floor(size / crop_pct) (crop_mode "center": the shorter side, aspect kept, torchvision's
+    Resize(int); "squash": both sides), CenterCrop(size), ToTensor, Normalize(mean, std).  Image b is Pillow's
+    resize((W2, H2)).crop(window) bit for bit, normalised with `ops.normalize_images`' arithmetic; only the window is
+    computed (nvit_center_crop_apply, two launches).  size: a multiple of 4 up to MAX_SIDE; source sides up to MAX_SRC.
+
+    Stateless: nothing is drawn and nothing lives on the device, so there is no `.to()` and no `state_dict`.
+    `rcc(u8)` returns the fp32 [B,C,size,size] model input, `rcc(u8, return_u8=True)` the uint8 [B,size,size,C] crop;
+    `geometry` is the host arithmetic, `apply` the raw window."""
+
+    def __init__(self, size: int, crop_pct: float = 0.875, interpolation: str = "bilinear", crop_mode: str = "center",
+                 mean: float = 0.5, std: float = 0.5):
+        if isinstance(size, bool) or not isinstance(size, int):
+            raise TypeError(f"size must be an int (got {size!r})")
+        if not 4 <= size <= MAX_SIDE or size % 4:
+            raise ValueError(f"size must be a multiple of 4 in 4..{MAX_SIDE} (got {size})")
+        if isinstance(crop_pct, bool) or not isinstance(crop_pct, (int, float)):
+            raise TypeError(f"crop_pct must be a number (got {crop_pct!r})")
+        if not 0.0 < crop_pct <= 1.0:   # also refuses NaN
+            raise ValueError(f"crop_pct must be in (0, 1] (got {crop_pct!r})")
+        for what, names, v in (("interpolation", INTERPOLATIONS, interpolation), ("crop_mode", CROP_MODES, crop_mode)):
+            if not isinstance(v, str):
+                raise TypeError(f"{what} is a name: {', '.join(names)} (got {v!r})")
+            if v not in names:
+                raise ValueError(f"unknown {what} {v!r} (known: {', '.join(names)})")
+        for what, v in (("mean", mean), ("std", std)):
+            if isinstance(v, bool) or not isinstance(v, (int, float)):
+                raise TypeError(f"{what} must be a number (got {v!r})")
+        if not math.isfinite(mean):
+            raise ValueError(f"mean must be finite (got {mean!r})")
+        if not 0.0 < std < math.inf:   # also refuses NaN
+            raise ValueError(f"std must be positive (got {std!r})")
+        self.size, self.crop_pct, self.interpolation, self.crop_mode = size, float(crop_pct), interpolation, crop_mode
+        self.mean, self.std = float(mean), float(std)
+        self.scale_size = math.floor(size / crop_pct)
+
+    def params(self) -> tuple:
+        """What two transforms must share to give the same output on the same source."""
+        return self.size, self.crop_pct, self.interpolation, self.crop_mode, self.mean, self.std
+
+    # ------------------------------------------------------------------ host arithmetic
+    def geometry(self, Hs: int, Ws: int) -> tuple:
+        """(H2, W2, top, left): the size the source is resized to and the window's corner in it.  torchvision's
+        Resize(scale_size) / Resize((scale_size, scale_size)) and center_crop: int() truncates, round() is Python's (half
+        to even)."""
+        _check_src_hw(Hs, Ws)
+        s = self.scale_size
+        if self.crop_mode == "squash":
+            H2 = W2 = s
+        elif Ws <= Hs:
+            H2, W2 = int(s * Hs / Ws), s
+        else:
+            H2, W2 = s, int(s * Ws / Hs)
+        if H2 > MAX_SIDE or W2 > MAX_SIDE:
+            raise ValueError(f"ResizeCenterCrop: a {Hs}x{Ws} source is resized to {H2}x{W2}; sides up to {MAX_SIDE}")
+        return H2, W2, int(round((H2 - self.size) / 2.0)), int(round((W2 - self.size) / 2.0))
+
+    def _check_source(self, u8) -> tuple:
+        if not isinstance(u8, Tensor) or u8.dtype != torch.uint8:
+            raise TypeError("ResizeCenterCrop takes a uint8 [B,Hs,Ws,C] batch")
+        if u8.dim() != 4:
+            raise ValueError(f"ResizeCenterCrop takes a uint8 [B,Hs,Ws,C] batch (got rank {u8.dim()})")
+        B, Hs, Ws, C = u8.shape
+        if C not in (1, 3):
+            raise ValueError(f"ResizeCenterCrop: C must be 1 or 3 (got {C}; the layout is [B,Hs,Ws,C])")
+        if not 1 <= B <= MAX_BATCH:
+            raise ValueError(f"ResizeCenterCrop: a batch holds 1..{MAX_BATCH} images (got {B})")
+        self.geometry(Hs, Ws)   # raises for a source it cannot take
+        return B, Hs, Ws, C
+
+    # ------------------------------------------------------------------ the launches
+    def apply(self, u8: Tensor, H2: int, W2: int, top: int, left: int, return_u8: bool = False, both: bool = False):
+        """The size x size window at (top, left) of every image resized to [H2,W2] (nvit_center_crop_apply, two launches):
+        fp32 [B,C,size,size] normalised, uint8 [B,size,size,C] with return_u8, (fp32, uint8) from the one call with both."""
+        B, Hs, Ws, C = self._check_source(u8)
+        for what, v in (("H2", H2), ("W2", W2), ("top", top), ("left", left)):
+            if isinstance(v, bool) or not isinstance(v, int):
+                raise TypeError(f"ResizeCenterCrop.apply: {what} must be an int (got {v!r})")
+        if not (self.size <= H2 <= MAX_SIDE and self.size <= W2 <= MAX_SIDE):
+            raise ValueError(f"ResizeCenterCrop.apply: H2 and W2 must be {self.size}..{MAX_SIDE} (got {H2}x{W2})")
+        if not (0 <= top <= H2 - self.size and 0 <= left <= W2 - self.size):
+            raise ValueError(f"ResizeCenterCrop.apply: the window at ({top}, {left}) leaves the {H2}x{W2} image")
+        _chk_dev(u8)
+        u8 = u8.contiguous()
+        lib, interp, size = _lib.load(), INTERPOLATIONS[self.interpolation], self.size
+        ws_bytes = lib.nvit_center_crop_ws_bytes(B, Hs, Ws, C, H2, W2, top, left, size, interp)
+        if ws_bytes < 0:
+            raise ValueError(f"ResizeCenterCrop.apply: unsupported shape {tuple(u8.shape)} -> {H2}x{W2} -> {size}")
+        ws = torch.empty(ws_bytes, device=u8.device, dtype=torch.uint8)   # taps + the [rows read,size,C] intermediates
+        o8 = torch.empty((B, size, size, C), device=u8.device, dtype=torch.uint8) if return_u8 or both else None
+        of = torch.empty((B, C, size, size), device=u8.device, dtype=torch.float32) if both or not return_u8 else None
+        check(lib.nvit_center_crop_apply(_p(u8), _p(o8) if o8 is not None else None, _p(of) if of is not None else None,
+                                         _p(ws), ws_bytes, B, Hs, Ws, C, H2, W2, top, left, size, interp, self.mean,
+                                         self.std, _s()), "nvit_center_crop_apply")
+        return (of, o8) if both else (o8 if return_u8 else of)
+
+    def __call__(self, u8: Tensor, return_u8: bool = False):
+        _, Hs, Ws, _ = self._check_source(u8)
+        return self.apply(u8, *self.geometry(Hs, Ws), return_u8=return_u8)
+
+    def batch(self, u8: Tensor) -> CenterCroppedBatch:
+        """The X of `predict`, `validate`, `estimate_loss` and `GraphedEval`: the transform then runs in front of the
+        forward (and inside its captured graph)."""
+        return CenterCroppedBatch(self, u8)
 
 
 # ---------------------------------------------------------------------------------------------- RandomErasing

@@ -6,6 +6,9 @@
 //                       horizontal  grid (tile of output columns, image): the tile's taps, then box rows -> uint8 [h,size,C]
 //                       vertical    grid (tile of output rows, image): the tile's taps, then the output, flip folded
 //                                   into the store index
+//   nvit_center_crop_apply   evaluation's Resize + CenterCrop, the same two passes on a window the host gives:
+//                       horizontal  the window's columns of the source rows that its vertical taps read
+//                       vertical    the window as uint8 [size,size,C] and / or normalised fp32 [C,size,size]
 //   nvit_erase_draw   one workgroup, one thread per image: timm's RandomErasing box -> int32 [B,8] table
 //   nvit_erase_apply  fp32 [B,C,H,W] -> fp32 [B,C,H,W], float4 streaming over (chunk of the image, image)
 //
@@ -158,22 +161,12 @@ __device__ __forceinline__ unsigned clip8(int acc) {
   return (unsigned)(v < 0 ? 0 : (v > 255 ? 255 : v));
 }
 
-// taps: int32 [B,2,size,set_stride(kstride)] (axis 0 horizontal, 1 vertical); mid: uint8 [B,Hs,size,C], rows 0..h-1 used.
-__global__ __launch_bounds__(CROP_THREADS) void crop_h_kernel(const unsigned char* __restrict__ in,
-                                                              const int* __restrict__ table, int* taps,
-                                                              unsigned char* __restrict__ mid, int Hs, int Ws, int C,
-                                                              int size, int kstride, int interp) {
-  const int b = blockIdx.y, c0 = blockIdx.x * CROP_TILE;
-  const int ncols = size - c0 < CROP_TILE ? size - c0 : CROP_TILE;
-  const CropBox bx = box_of(table + (size_t)b * CROP_ROW, Hs, Ws);
-  const int st = set_stride(kstride);
-  int* sets = taps + (((size_t)b * 2 + 0) * size + c0) * st;
-  if ((int)threadIdx.x < ncols) tap_set(sets + (size_t)threadIdx.x * st, kstride, c0 + threadIdx.x, bx.w, size, interp);
-  __syncthreads();   // this workgroup's tap sets are in memory (a workgroup-scope release/acquire)
-  const unsigned char* src = in + (((size_t)b * Hs + bx.top) * Ws + bx.left) * C;
-  unsigned char* dst = mid + (size_t)b * Hs * size * C;
-  // one thread per (box row, output column): a tap is loaded once for the pixel's channels
-  const int total = bx.h * ncols;
+// The body of both horizontal passes: `rows` source rows of Ws pixels -> columns c0 .. c0 + ncols - 1 of `rows` rows of
+// `size` pixels, by this workgroup's tap sets.  One thread per (row, output column): a tap is loaded once for the pixel's
+// channels.
+__device__ __forceinline__ void resample_rows(const unsigned char* src, unsigned char* dst, const int* sets, int st,
+                                              int rows, int ncols, int c0, int Ws, int C, int size) {
+  const int total = rows * ncols;
   for (int i = threadIdx.x; i < total; i += CROP_THREADS) {
     const int y = i / ncols, xc = i - y * ncols;
     const int* set = sets + (size_t)xc * st;
@@ -196,6 +189,23 @@ __global__ __launch_bounds__(CROP_THREADS) void crop_h_kernel(const unsigned cha
       o[0] = (unsigned char)clip8(a0);
     }
   }
+}
+
+// taps: int32 [B,2,size,set_stride(kstride)] (axis 0 horizontal, 1 vertical); mid: uint8 [B,Hs,size,C], rows 0..h-1 used.
+__global__ __launch_bounds__(CROP_THREADS) void crop_h_kernel(const unsigned char* __restrict__ in,
+                                                              const int* __restrict__ table, int* taps,
+                                                              unsigned char* __restrict__ mid, int Hs, int Ws, int C,
+                                                              int size, int kstride, int interp) {
+  const int b = blockIdx.y, c0 = blockIdx.x * CROP_TILE;
+  const int ncols = size - c0 < CROP_TILE ? size - c0 : CROP_TILE;
+  const CropBox bx = box_of(table + (size_t)b * CROP_ROW, Hs, Ws);
+  const int st = set_stride(kstride);
+  int* sets = taps + (((size_t)b * 2 + 0) * size + c0) * st;
+  if ((int)threadIdx.x < ncols) tap_set(sets + (size_t)threadIdx.x * st, kstride, c0 + threadIdx.x, bx.w, size, interp);
+  __syncthreads();   // this workgroup's tap sets are in memory (a workgroup-scope release/acquire)
+  const unsigned char* src = in + (((size_t)b * Hs + bx.top) * Ws + bx.left) * C;
+  unsigned char* dst = mid + (size_t)b * Hs * size * C;
+  resample_rows(src, dst, sets, st, bx.h, ncols, c0, Ws, C, size);
 }
 
 __global__ __launch_bounds__(CROP_THREADS) void crop_v_kernel(const unsigned char* __restrict__ mid,
@@ -237,6 +247,95 @@ __global__ __launch_bounds__(CROP_THREADS) void crop_v_kernel(const unsigned cha
       for (int e = 0; e < 4; ++e) {
         const int idx = 4 * j + e, col = idx / C, ch = idx - col * C;
         orow[(size - 1 - col) * C + ch] = (unsigned char)clip8(acc[e]);
+      }
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ Resize + CenterCrop
+// Evaluation's transform: every image is resampled to a virtual [H2,W2] and only the size x size window at (top, left)
+// of it is computed.  The geometry is the host's, one per batch.  A window is the whole resize with the output index
+// shifted, tap_set(left + j, Ws, W2): resizing and then cutting gives the same bytes (tests/center_crop_ref.py).
+struct CenterGeom {
+  int Hs, Ws, H2, W2, top, left, size, interp;
+  int row0, nrows;    // the source rows that the window's vertical taps read: row0 .. row0 + nrows - 1
+  int kst_w, kst_h;   // taps per set of each axis
+};
+
+// taps: int32 [B,size,set_stride(kst_w)]; mid: uint8 [B,nrows,size,C], source rows row0 .. of the window's columns.
+__global__ __launch_bounds__(CROP_THREADS) void center_h_kernel(const unsigned char* __restrict__ in, int* taps,
+                                                                unsigned char* __restrict__ mid, int C, CenterGeom g) {
+  const int b = blockIdx.y, c0 = blockIdx.x * CROP_TILE;
+  const int ncols = g.size - c0 < CROP_TILE ? g.size - c0 : CROP_TILE;
+  const int st = set_stride(g.kst_w);
+  int* sets = taps + ((size_t)b * g.size + c0) * st;
+  if ((int)threadIdx.x < ncols)
+    tap_set(sets + (size_t)threadIdx.x * st, g.kst_w, g.left + c0 + threadIdx.x, g.Ws, g.W2, g.interp);
+  __syncthreads();   // this workgroup's tap sets are in memory (a workgroup-scope release/acquire)
+  const unsigned char* src = in + ((size_t)b * g.Hs + g.row0) * g.Ws * C;   // xmin + n <= Ws: inside the image
+  unsigned char* dst = mid + (size_t)b * g.nrows * g.size * C;
+  resample_rows(src, dst, sets, st, g.nrows, ncols, c0, g.Ws, C, g.size);
+}
+
+// ToTensor + Normalize of one byte with nvit_normalize_images' roundings.  rowops.hip compiles (x * (1/255) - mean) *
+// inv_std under the default contraction, which fuses the first two; this file contracts nothing, so the fusion is written.
+__device__ __forceinline__ float normalize1(unsigned x, float mean, float inv_std) {
+  return __builtin_fmaf((float)x, 1.0f / 255.0f, -mean) * inv_std;
+}
+
+// taps: int32 [B,size,set_stride(kst_h)].  A thread owns four neighbouring pixels of an output row, C 4-byte words of
+// the HWC intermediate: packed, they are C words of the uint8 output; taken apart by channel, one float4 of each of the C
+// planes of the fp32 output, so that neighbouring threads store neighbouring 16 bytes of a plane's row.
+template <int C>
+__global__ __launch_bounds__(CROP_THREADS) void center_v_kernel(const unsigned char* __restrict__ mid, int* taps,
+                                                                unsigned char* __restrict__ out_u8,
+                                                                float* __restrict__ out_f32, CenterGeom g, float mean,
+                                                                float inv_std) {
+  const int b = blockIdx.y, r0 = blockIdx.x * CROP_TILE;
+  const int nrows = g.size - r0 < CROP_TILE ? g.size - r0 : CROP_TILE;
+  const int st = set_stride(g.kst_h);
+  int* sets = taps + ((size_t)b * g.size + r0) * st;
+  if ((int)threadIdx.x < nrows)
+    tap_set(sets + (size_t)threadIdx.x * st, g.kst_h, g.top + r0 + threadIdx.x, g.Hs, g.H2, g.interp);
+  __syncthreads();
+  const int row_b = g.size * C, q = g.size / 4;   // size % 4 == 0
+  const unsigned char* src = mid + (size_t)b * g.nrows * row_b;
+  for (int i = threadIdx.x; i < nrows * q; i += CROP_THREADS) {
+    const int ry = i / q, j = i - ry * q;
+    const int* set = sets + (size_t)ry * st;
+    const int y0 = set[0] - g.row0;
+    // the host found row0 and nrows with tap_set's own expressions, so the test never fails; it keeps every read inside
+    const int n = y0 >= 0 && y0 + set[1] <= g.nrows ? set[1] : 0;
+    int acc[4 * C];
+#pragma unroll
+    for (int k = 0; k < 4 * C; ++k) acc[k] = 1 << (PRECISION_BITS - 1);
+    for (int y = 0; y < n; ++y) {
+      const unsigned* p = reinterpret_cast<const unsigned*>(src + (size_t)(y0 + y) * row_b) + C * j;
+      const int t = set[2 + y];
+#pragma unroll
+      for (int w = 0; w < C; ++w) {
+        const unsigned v = p[w];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[4 * w + e] += t * (int)((v >> (8 * e)) & 255u);
+      }
+    }
+    unsigned px[4 * C];   // byte k = channel k % C of pixel k / C
+#pragma unroll
+    for (int k = 0; k < 4 * C; ++k) px[k] = clip8(acc[k]);
+    if (out_u8) {
+      unsigned* o = reinterpret_cast<unsigned*>(out_u8 + ((size_t)b * g.size + r0 + ry) * row_b) + C * j;
+#pragma unroll
+      for (int w = 0; w < C; ++w)   // v_perm_b32, as in crop_v_kernel
+        o[w] = __builtin_amdgcn_perm(px[4 * w + 1], px[4 * w], 0x0c0c0400u) |
+               __builtin_amdgcn_perm(px[4 * w + 3], px[4 * w + 2], 0x04000c0cu);
+    }
+    if (out_f32) {
+#pragma unroll
+      for (int c = 0; c < C; ++c) {
+        f32x4 v;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = normalize1(px[e * C + c], mean, inv_std);
+        *reinterpret_cast<f32x4*>(out_f32 + (((size_t)b * C + c) * g.size + r0 + ry) * g.size + 4 * j) = v;
       }
     }
   }
@@ -342,7 +441,89 @@ bool crop_shape_ok(int B, int Hs, int Ws, int C, int size, int interp) {
          size > 0 && size <= NVIT_AUG_MAX_SIDE && size % 4 == 0 && (interp == NVIT_CROP_BILINEAR || interp == NVIT_CROP_BICUBIC);
 }
 
+
+// ---- Resize + CenterCrop: the host's half
+int axis_kstride(int in_size, int out_size, int interp) {
+  const double scale = (double)in_size / (double)out_size;
+  const double support = (interp == NVIT_CROP_BICUBIC ? 2.0 : 1.0) * (scale < 1.0 ? 1.0 : scale);
+  return (int)ceil(support) * 2 + 1;
+}
+// [first, end) of the input indices that the taps of output index xx read: tap_set's expressions, in fp64 like them
+// (the pragma above covers the host's code too).  Both ends grow with xx.
+void tap_range(int xx, int in_size, int out_size, int interp, int* first, int* end) {
+  const double scale = (double)in_size / (double)out_size;
+  const double fs = scale < 1.0 ? 1.0 : scale;
+  const double support = (interp == NVIT_CROP_BICUBIC ? 2.0 : 1.0) * fs;
+  const double center = ((double)xx + 0.5) * scale;
+  int xmin = (int)(center - support + 0.5);
+  xmin = xmin < 0 ? 0 : xmin;
+  int xmax = (int)(center + support + 0.5);
+  xmax = xmax > in_size ? in_size : xmax;
+  *first = xmin;
+  *end = xmax < xmin ? xmin : xmax;
+}
+bool center_shape_ok(int B, int Hs, int Ws, int C, int H2, int W2, int top, int left, int size, int interp) {
+  return B > 0 && B <= NVIT_CROP_MAX_BATCH && Hs > 0 && Ws > 0 && Hs <= NVIT_CROP_MAX_SRC && Ws <= NVIT_CROP_MAX_SRC &&
+         (C == 1 || C == 3) && size >= 4 && size <= NVIT_AUG_MAX_SIDE && size % 4 == 0 && H2 <= NVIT_AUG_MAX_SIDE &&
+         W2 <= NVIT_AUG_MAX_SIDE && H2 >= size && W2 >= size && top >= 0 && top <= H2 - size && left >= 0 &&
+         left <= W2 - size && (interp == NVIT_CROP_BILINEAR || interp == NVIT_CROP_BICUBIC);
+}
+CenterGeom center_geom(int Hs, int Ws, int H2, int W2, int top, int left, int size, int interp) {
+  CenterGeom g{Hs, Ws, H2, W2, top, left, size, interp, 0, 0, axis_kstride(Ws, W2, interp), axis_kstride(Hs, H2, interp)};
+  int first, end, unused;
+  tap_range(top, Hs, H2, interp, &first, &unused);
+  tap_range(top + size - 1, Hs, H2, interp, &unused, &end);
+  g.row0 = first;
+  g.nrows = end - first;
+  return g;
+}
+// the two tap tables, each rounded up to 256 bytes: the horizontal one, then the vertical one, then the intermediate
+size_t center_taps_bytes(int B, const CenterGeom& g, int kst) {
+  return ((size_t)B * g.size * set_stride(kst) * sizeof(int) + 255) / 256 * 256;
+}
+
 }  // namespace
+
+extern "C" int64_t nvit_center_crop_ws_bytes(int B, int Hs, int Ws, int C, int H2, int W2, int top, int left, int size,
+                                             int interp) {
+  if (!center_shape_ok(B, Hs, Ws, C, H2, W2, top, left, size, interp)) return -1;
+  const CenterGeom g = center_geom(Hs, Ws, H2, W2, top, left, size, interp);
+  return (int64_t)(center_taps_bytes(B, g, g.kst_w) + center_taps_bytes(B, g, g.kst_h) + (size_t)B * g.nrows * size * C);
+}
+
+extern "C" int nvit_center_crop_apply(const void* in, void* out_u8, float* out_f32, void* ws, int64_t ws_bytes, int B, int Hs,
+                                      int Ws, int C, int H2, int W2, int top, int left, int size, int interp, float mean,
+                                      float std_, void* stream) {
+  NVIT_REQUIRE(in && ws && (out_u8 || out_f32), "center_crop_apply: bad arguments (at least one output)");
+  NVIT_REQUIRE(center_shape_ok(B, Hs, Ws, C, H2, W2, top, left, size, interp),
+               "center_crop_apply: needs C in {1,3}, source sides up to %d, size %% 4 == 0 in 4..%d, size <= H2, W2 <= %d, "
+               "0 <= top <= H2 - size, 0 <= left <= W2 - size, B up to %d and a known filter",
+               NVIT_CROP_MAX_SRC, NVIT_AUG_MAX_SIDE, NVIT_AUG_MAX_SIDE, NVIT_CROP_MAX_BATCH);
+  NVIT_REQUIRE(!out_f32 || std_ > 0.f, "center_crop_apply: std must be positive");
+  NVIT_REQUIRE(ws_bytes >= nvit_center_crop_ws_bytes(B, Hs, Ws, C, H2, W2, top, left, size, interp),
+               "center_crop_apply: workspace needs nvit_center_crop_ws_bytes(...) bytes");
+  NVIT_REQUIRE(((uintptr_t)out_u8 & 3) == 0 && ((uintptr_t)out_f32 & 15) == 0 && ((uintptr_t)ws & 15) == 0,
+               "center_crop_apply: out_u8 4-byte, out_f32 and ws 16-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  const CenterGeom g = center_geom(Hs, Ws, H2, W2, top, left, size, interp);
+  int* taps_w = (int*)ws;
+  int* taps_h = (int*)((unsigned char*)ws + center_taps_bytes(B, g, g.kst_w));
+  unsigned char* mid = (unsigned char*)taps_h + center_taps_bytes(B, g, g.kst_h);
+  const double px = (double)B * C, out_b = (out_u8 ? 1.0 : 0.0) + (out_f32 ? 4.0 : 0.0);
+  ProfScope ps(NVIT_KID_PATCHIFY, 0.0, px * ((double)g.nrows * Ws + 2.0 * g.nrows * size + out_b * size * size), s);
+  const dim3 grid(cdiv(size, CROP_TILE), B);
+  hipLaunchKernelGGL(center_h_kernel, grid, dim3(CROP_THREADS), 0, s, (const unsigned char*)in, taps_w, mid, C, g);
+  NVIT_CHECK_LAUNCH("center_crop_apply (horizontal)");
+  const float inv_std = out_f32 ? 1.0f / std_ : 0.f;
+  if (C == 3)
+    hipLaunchKernelGGL(center_v_kernel<3>, grid, dim3(CROP_THREADS), 0, s, (const unsigned char*)mid, taps_h,
+                       (unsigned char*)out_u8, out_f32, g, mean, inv_std);
+  else
+    hipLaunchKernelGGL(center_v_kernel<1>, grid, dim3(CROP_THREADS), 0, s, (const unsigned char*)mid, taps_h,
+                       (unsigned char*)out_u8, out_f32, g, mean, inv_std);
+  NVIT_CHECK_LAUNCH("center_crop_apply (vertical)");
+  return NVIT_OK;
+}
 
 extern "C" int nvit_crop_draw(uint64_t seed, int64_t* step, int64_t first_index, const double* aspect, double scale0,
                               double scale1, double ratio_min, double ratio_max, float hflip, int* table, int B, int Hs,

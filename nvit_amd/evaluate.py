@@ -6,6 +6,9 @@ the block functions take their forward-only route (model._lean): the logits are 
 nothing that only a backward reads is stored.  The per-batch metrics come from one launch (nvit_eval_metrics: loss
 and the rank of the target, which replaces F.cross_entropy + topk) and are summed on the device; the host waits once
 per call, not up to seven times per batch.
+
+Wherever X stands, a `ResizeCenterCrop.batch(u8)` (crop.py) may stand instead: evaluation from the stored uint8 data.  The
+transform's two launches then run in front of the forward on the current stream, with no host synchronisation.
 """
 from __future__ import annotations
 
@@ -14,12 +17,18 @@ from typing import Dict, Iterable, Tuple
 import torch
 
 from . import ops
+from .crop import CenterCroppedBatch
 from .train import _unwrap, add_aux_losses
 
 Tensor = torch.Tensor
 _KOHONEN_KEYS = (("val/consistency_loss", "kohonen_consistency"), ("val/smoothness_loss", "kohonen_smoothness"),
                  ("val/local_quantization_loss", "local_quantization"),
                  ("val/global_quantization_loss", "global_quantization"))
+
+
+def _model_input(X):
+    """X of an evaluation call -> the model's input: a `ResizeCenterCrop.batch(u8)` runs its two launches here."""
+    return X.cropped() if isinstance(X, CenterCroppedBatch) else X
 
 
 class _eval_mode:
@@ -49,7 +58,7 @@ def predict(model, X: Tensor) -> Tensor:
     """Logits of `model(X)` (bit-identical) from the forward-only route, without the reconstruction head: its GEMM,
     its loss kernel and the stream's bf16 copy that only it reads (plain ViT) are skipped."""
     with _eval_mode(model) as m:
-        return m._forward(X, False)[0]
+        return m._forward(_model_input(X), False)[0]
 
 
 def validate(model, batches: Iterable[Tuple[Tensor, Tensor]], consistency_weight: float = 0.1,
@@ -64,7 +73,7 @@ def validate(model, batches: Iterable[Tuple[Tensor, Tensor]], consistency_weight
         acc = aux_acc = None
         for X, y in batches:
             # (the reconstruction term is not among the reported ones: the head is left out with the Kohonen head too)
-            logits, aux = m._forward(X, False)
+            logits, aux = m._forward(_model_input(X), False)
             if acc is None:
                 acc = torch.zeros(4, device=logits.device, dtype=torch.float32)
                 aux_acc = torch.zeros(len(_KOHONEN_KEYS), device=logits.device, dtype=torch.float32)
@@ -94,7 +103,8 @@ def estimate_loss(model, batches: Iterable[Tuple[Tensor, Tensor]], eval_iters: i
         for X, y in batches:
             if n >= eval_iters:
                 break
-            logits, aux = m._forward(X, koh)   # the reconstruction loss is a term of the sum only with the head
+            # (the reconstruction loss is a term of the sum only with the head)
+            logits, aux = m._forward(_model_input(X), koh)
             acc = torch.zeros(4, device=logits.device, dtype=torch.float32)
             ops.eval_metrics(logits, y, acc)
             loss = add_aux_losses(m.config, acc[0], aux, consistency_weight, smoothness_weight)
@@ -127,16 +137,24 @@ class GraphedEval:
     the resampling of the position tables, which reads the parameters on every replay like the weight shadows do, so
     training between two calls is picked up.  `ViT.set_input_size` replaces the two parameters: every call afterwards
     raises ValueError.
+
+    X may be a `ResizeCenterCrop.batch(u8)`: the transform's two launches are captured with the forward, and the static
+    input is the uint8 source.  A batch then fits the graphs if it is such an object with the same source shape and the
+    same transform parameters; anything else (a plain tensor too) runs eagerly, as a `ResizeCenterCrop.batch(u8)` does on
+    graphs that were built on a tensor.
     """
 
-    def __init__(self, model, X: Tensor, y: Tensor, consistency_weight: float = 0.1, smoothness_weight: float = 0.1):
+    def __init__(self, model, X, y: Tensor, consistency_weight: float = 0.1, smoothness_weight: float = 0.1):
         self.model = model
         self.cw, self.sw = consistency_weight, smoothness_weight
         self._size_epoch = _unwrap(model)._size_epoch
         with _eval_mode(model) as m:   # (refuses a CPU-resident model before anything is changed)
             if X.device.type != "cuda" or y.device != X.device:
                 raise RuntimeError("GraphedEval: inputs must live on the HIP device")
-            self.X, self.y = X.clone(), y.clone()
+            # the static input: the tensor, or the uint8 source under the transform that `_static` wraps around it
+            self._crop = X.crop if isinstance(X, CenterCroppedBatch) else None
+            self.X = X.clone() if self._crop is None else X.u8.clone(memory_format=torch.contiguous_format)
+            self.y = y.clone()
             dev = X.device
             self._acc = torch.zeros(4, device=dev, dtype=torch.float32)
             self._aux_acc = torch.zeros(len(_KOHONEN_KEYS), device=dev, dtype=torch.float32)
@@ -145,26 +163,29 @@ class GraphedEval:
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):   # builds every cache (shadow tables, LDS attributes) ahead of the capture
-                self._metrics_batch(m, self.X, self.y)
-                self._loss_batch(m, self.X, self.y)
+                self._metrics_batch(m, self._static(), self.y)
+                self._loss_batch(m, self._static(), self.y)
             torch.cuda.current_stream().wait_stream(side)
             torch.cuda.synchronize()
             self._g_metrics, self._g_loss = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
             with torch.cuda.graph(self._g_metrics, stream=side):
-                self._logits = self._metrics_batch(m, self.X, self.y)
+                self._logits = self._metrics_batch(m, self._static(), self.y)
             with torch.cuda.graph(self._g_loss, stream=side):
-                self._loss_batch(m, self.X, self.y)
+                self._loss_batch(m, self._static(), self.y)
 
     # ---- one batch, eagerly or under capture: the loop bodies of validate / estimate_loss on this object's accumulators
-    def _metrics_batch(self, m, X: Tensor, y: Tensor) -> Tensor:
-        logits, aux = m._forward(X, False)
+    def _static(self):
+        return self.X if self._crop is None else self._crop.batch(self.X)
+
+    def _metrics_batch(self, m, X, y: Tensor) -> Tensor:
+        logits, aux = m._forward(_model_input(X), False)
         ops.eval_metrics(logits, y, self._acc)
         if m.config.use_kohonen:
             self._aux_acc += torch.stack([aux[k].reshape(()) for _, k in _KOHONEN_KEYS])
         return logits
 
-    def _loss_batch(self, m, X: Tensor, y: Tensor) -> None:
-        logits, aux = m._forward(X, m.config.use_kohonen)
+    def _loss_batch(self, m, X, y: Tensor) -> None:
+        logits, aux = m._forward(_model_input(X), m.config.use_kohonen)
         self._bacc.zero_()
         ops.eval_metrics(logits, y, self._bacc)
         self._total += add_aux_losses(m.config, self._bacc[0], aux, self.cw, self.sw)
@@ -174,21 +195,32 @@ class GraphedEval:
             raise ValueError("GraphedEval: ViT.set_input_size replaced the position embeddings these graphs were captured "
                              "with; build a new GraphedEval")
 
-    def _fits(self, X: Tensor, y: Tensor) -> bool:
-        return (X.shape == self.X.shape and X.dtype == self.X.dtype and X.device == self.X.device
-                and y.shape == self.y.shape and y.dtype == self.y.dtype and y.device == self.y.device)
+    def _fits_x(self, X) -> bool:
+        if isinstance(X, CenterCroppedBatch):
+            if self._crop is None or X.crop.params() != self._crop.params():
+                return False
+            X = X.u8
+        elif self._crop is not None:
+            return False
+        return X.shape == self.X.shape and X.dtype == self.X.dtype and X.device == self.X.device
 
-    def _load(self, X: Tensor, y: Tensor) -> None:
-        self.X.copy_(X, non_blocking=True)
+    def _fits(self, X, y: Tensor) -> bool:
+        return self._fits_x(X) and y.shape == self.y.shape and y.dtype == self.y.dtype and y.device == self.y.device
+
+    def _load_x(self, X) -> None:
+        self.X.copy_(X.u8 if isinstance(X, CenterCroppedBatch) else X, non_blocking=True)
+
+    def _load(self, X, y: Tensor) -> None:
+        self._load_x(X)
         self.y.copy_(y, non_blocking=True)
 
-    def predict(self, X: Tensor) -> Tensor:
+    def predict(self, X) -> Tensor:
         """evaluate.predict(model, X); a new tensor."""
         self._check_model()
-        if not (X.shape == self.X.shape and X.dtype == self.X.dtype and X.device == self.X.device):
+        if not self._fits_x(X):
             return predict(self.model, X)
         with _eval_mode(self.model):
-            self.X.copy_(X, non_blocking=True)
+            self._load_x(X)
             self._g_metrics.replay()
             return self._logits.clone()
 

@@ -19,7 +19,7 @@ import torch
 
 from . import ops
 from .augment import AugmentedBatch
-from .crop import CroppedBatch, ErasedBatch
+from .crop import CenterCroppedBatch, CroppedBatch, ErasedBatch
 from .mix import MixedBatch, MixedTargets
 from .optim import FusedAdamW, renorm_matrices
 
@@ -102,7 +102,11 @@ def add_aux_losses(config, loss: torch.Tensor, aux, consistency_weight: float = 
 
 
 def _check_step_args(optimizer, X, accumulation_steps, skip_nonfinite) -> None:
-    """The argument checks of train_step / GraphedTrainStep: ValueError, before any device work."""
+    """The argument checks of train_step / GraphedTrainStep: ValueError (TypeError for evaluation's batch object), before
+    any device work."""
+    if isinstance(X, CenterCroppedBatch):
+        raise TypeError("a ResizeCenterCrop.batch(u8) (CenterCroppedBatch) is evaluation's input; a train step takes a tensor "
+                        "or the chain of RandomResizedCrop.batch(u8)")
     n = accumulation_steps
     if not isinstance(n, int) or isinstance(n, bool) or n < 1:
         raise ValueError(f"accumulation_steps must be an int >= 1 (got {n!r})")
