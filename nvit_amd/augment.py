@@ -20,6 +20,7 @@ import torch
 from . import _lib
 from ._lib import check
 from .ops import _chk_dev, _p, _s, round_up
+from .stages import DeviceStepCounter, StagedBatch, check_sides, check_u8_batch   # noqa: F401 (DeviceStepCounter: re-exported)
 
 Tensor = torch.Tensor
 
@@ -126,25 +127,31 @@ def _f32_bits(f: float) -> int:
     return struct.unpack("<i", struct.pack("<f", f))[0]
 
 
+def affine_coefficients(name: str, value: float, H: int, W: int) -> tuple:
+    """Pillow's six coefficients (a, b, c, d, e, f) of a geometric op, output to input: x_in = a x + b y + c, y_in = d x +
+    e y + f.  value: the shear factor, the pixels, or Image.rotate's degrees about (W/2, H/2)."""
+    value = float(value)
+    if name == "ShearX":
+        return 1.0, value, 0.0, 0.0, 1.0, 0.0
+    if name == "ShearY":
+        return 1.0, 0.0, 0.0, value, 1.0, 0.0
+    if name == "TranslateX":
+        return 1.0, 0.0, value, 0.0, 1.0, 0.0
+    if name == "TranslateY":
+        return 1.0, 0.0, 0.0, 0.0, 1.0, value
+    r = -math.radians(value)
+    c, s = round(math.cos(r), 15), round(math.sin(r), 15)
+    cx, cy = W / 2.0, H / 2.0
+    return c, s, c * -cx + s * -cy + 0.0 + cx, -s, c, -s * -cx + c * -cy + 0.0 + cy
+
+
 def op_row(op, value, H: int, W: int):
     """The eight ints of one op in the parameter table: id, then Pillow's six 16.16 affine coefficients (output to
     input, the half-pixel centre folded into the two offsets), or the argument's bits and zeros."""
     name = OPS[_op_id(op)]
     row = [_ID[name]] + [0] * (ROW - 1)
     if name in _AFFINE:
-        if name == "ShearX":
-            a = (1.0, float(value), 0.0, 0.0, 1.0, 0.0)
-        elif name == "ShearY":
-            a = (1.0, 0.0, 0.0, float(value), 1.0, 0.0)
-        elif name == "TranslateX":
-            a = (1.0, 0.0, float(value), 0.0, 1.0, 0.0)
-        elif name == "TranslateY":
-            a = (1.0, 0.0, 0.0, 0.0, 1.0, float(value))
-        else:   # Image.rotate about (W/2, H/2)
-            r = -math.radians(value)
-            c, s = round(math.cos(r), 15), round(math.sin(r), 15)
-            cx, cy = W / 2.0, H / 2.0
-            a = (c, s, c * -cx + s * -cy + 0.0 + cx, -s, c, -s * -cx + c * -cy + 0.0 + cy)
+        a = affine_coefficients(name, value, H, W)
         row[1:7] = [_fix(a[0]), _fix(a[1]), _fix(a[2] + a[0] * 0.5 + a[1] * 0.5),
                     _fix(a[3]), _fix(a[4]), _fix(a[5] + a[3] * 0.5 + a[4] * 0.5)]
         # offset + coefficient * y + coefficient * x stays inside 32 bits for sides up to MAX_SIDE
@@ -163,9 +170,8 @@ def op_row(op, value, H: int, W: int):
     return row
 
 
-def _check_hw(H: int, W: int) -> None:
-    if not (1 <= H <= MAX_SIDE and 1 <= W <= MAX_SIDE):
-        raise ValueError(f"image sides must be 1..{MAX_SIDE} (got {H}x{W})")
+def _check_hw(H: int, W: int, name: str = "AutoAugment") -> None:
+    check_sides(name, H, W, MAX_SIDE)
 
 
 def arg_table(H: int, W: int) -> Tensor:
@@ -206,93 +212,40 @@ def validate_policy(policy) -> tuple:
     return tuple(out)
 
 
-def _check_images(u8: Tensor):
-    if not isinstance(u8, Tensor) or u8.dtype != torch.uint8:
-        raise TypeError("AutoAugment takes a uint8 [B,H,W,C] batch")
-    if u8.dim() != 4:
-        raise ValueError(f"AutoAugment takes a uint8 [B,H,W,C] batch (got rank {u8.dim()})")
+def _check_images(u8, name: str = "AutoAugment") -> tuple:
+    return check_u8_batch(name, u8, MAX_SIDE)
+
+
+def _apply_buffers(u8: Tensor, return_u8: bool) -> tuple:
+    """(workspace, its bytes, fp32 [B,C,H,W] output or None, uint8 [B,H,W,C] output or None) of an apply kernel."""
     B, H, W, C = u8.shape
-    if C not in (1, 3):
-        raise ValueError(f"AutoAugment: C must be 1 or 3 (got {C}; the layout is [B,H,W,C])")
-    if B < 1:
-        raise ValueError("AutoAugment: empty batch")
-    _check_hw(H, W)
-    return B, H, W, C
+    ws_bytes = 2 * B * round_up(H * W * C, 256)
+    ws = torch.empty(ws_bytes, device=u8.device, dtype=torch.uint8)
+    if return_u8:
+        return ws, ws_bytes, None, torch.empty_like(u8)
+    return ws, ws_bytes, torch.empty((B, C, H, W), device=u8.device, dtype=torch.float32), None
 
 
-class AugmentedBatch:
+class AugmentedBatch(StagedBatch):
     """A uint8 [B,H,W,C] batch together with the AutoAugment (or the RandAugment of randaug.py: anything whose call
     turns such a batch into fp32 [B,C,H,W]) that makes it the model's input: what `AutoAugment.batch(u8)` /
     `RandAugment.batch(u8)` return and `train_step` / `GraphedTrainStep` accept in place of X.  u8: the tensor, or a
-    `RandomResizedCrop.batch(u8)` (crop.py) whose crops are then what the policies see."""
+    `RandomResizedCrop.batch(u8)` (crop.py) whose crops are then what the policies see.  `.shape` is u8's."""
+
+    key, word, accepts, names = "augment", "augmentation", ("crop",), ("augment", "u8")
 
     def __init__(self, augment: "AutoAugment", u8):
-        from .crop import CroppedBatch   # (crop.py imports this module)
-        if isinstance(u8, CroppedBatch):
-            _check_hw(u8.shape[1], u8.shape[2])
+        name = type(augment).__name__
+        if self.takes(u8):
+            _check_hw(u8.shape[1], u8.shape[2], name)
         else:
-            _check_images(u8)
+            _check_images(u8, name)
         if u8.shape[2] % 4:
-            raise ValueError("AutoAugment: the fp32 output needs W % 4 == 0")
-        self.augment, self.u8 = augment, u8
-
-    @property
-    def shape(self):
-        return self.u8.shape
-
-    @property
-    def device(self):
-        return self.u8.device
+            raise ValueError(f"{name}: the fp32 output needs W % 4 == 0")
+        super().__init__(augment, u8, u8.shape)
 
     def augmented(self) -> Tensor:
-        return self.augment(self.u8 if isinstance(self.u8, Tensor) else self.u8.cropped())
-
-
-class DeviceStepCounter:
-    """What the counter-based draws (AutoAugment, Mixup) share: seed, first_index and the step counter, a device int64 that
-    the draw kernel advances (a host int until `.to(device)`); `state_dict()` is (seed, step)."""
-
-    def __init__(self, seed: int, first_index: int):
-        for what, v, hi in (("seed", seed, 2 ** 64), ("first_index", first_index, 2 ** 62)):
-            if isinstance(v, bool) or not isinstance(v, int):
-                raise TypeError(f"{what} must be an int")
-            if not 0 <= v < hi:
-                raise ValueError(f"{what} must be in [0, {hi})")
-        self.seed, self.first_index = seed, first_index
-        self.device: Optional[torch.device] = None
-        self._step_host = 0          # until .to(device)
-        self._step: Optional[Tensor] = None
-
-    def _step_to(self, device) -> torch.device:   # the common half of `.to(device)`: the counter moves, keeping its count
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise RuntimeError(f"{type(self).__name__} runs on the HIP device (no CPU path)")
-        step = self.step
-        self.device = device
-        self._step = torch.tensor([step], dtype=torch.int64).to(device)
-        return device
-
-    @property
-    def step(self) -> int:
-        """Steps drawn so far (reads the device counter: synchronises)."""
-        return self._step_host if self._step is None else int(self._step.item())
-
-    def state_dict(self) -> dict:
-        return {"seed": self.seed, "step": self.step}
-
-    def load_state_dict(self, state: dict) -> None:
-        seed, step = int(state["seed"]), int(state["step"])
-        if not 0 <= seed < 2 ** 64 or not 0 <= step < 2 ** 63:
-            raise ValueError(f"{type(self).__name__}.load_state_dict: seed or step out of range")
-        self.seed = seed
-        if self._step is None:
-            self._step_host = step
-        else:
-            self._step.fill_(step)   # in place: a captured graph holds this address
-
-    def _need_device(self):
-        if self._step is None:
-            raise RuntimeError(f"{type(self).__name__}: call .to(device) first (it runs on the HIP device, no CPU path)")
+        return self._launch(None)[0]
 
 
 class AutoAugment(DeviceStepCounter):
@@ -353,17 +306,10 @@ class AutoAugment(DeviceStepCounter):
             raise ValueError("AutoAugment.apply: the fp32 output needs W % 4 == 0")
         _chk_dev(u8, params)
         u8, params = u8.contiguous(), params.contiguous()
-        ws_bytes = 2 * B * round_up(H * W * C, 256)
-        ws = torch.empty(ws_bytes, device=u8.device, dtype=torch.uint8)
-        if return_u8:
-            out = torch.empty_like(u8)
-            f32, o8 = None, out
-        else:
-            out = torch.empty((B, C, H, W), device=u8.device, dtype=torch.float32)
-            f32, o8 = out, None
+        ws, ws_bytes, f32, o8 = _apply_buffers(u8, return_u8)
         check(_lib.load().nvit_augment_apply(_p(u8), _p(params), _p(f32), _p(o8), _p(ws), ws_bytes, B, H, W, C,
                                              self.mean, self.std, _s()), "nvit_augment_apply")
-        return out
+        return o8 if return_u8 else f32
 
     def __call__(self, u8: Tensor) -> Tensor:
         B, H, W, C = _check_images(u8)

@@ -34,8 +34,10 @@ import torch
 
 from . import _lib
 from ._lib import check
-from .augment import MAX_SIDE, AugmentedBatch, DeviceStepCounter
+from .augment import MAX_SIDE
 from .ops import _chk_dev, _p, _s, normalize_images
+from .stages import (DeviceStepCounter, StagedBatch, check_f32_batch, check_finite, check_name, check_number, check_sides,
+                     check_u8_batch, check_unit)
 
 Tensor = torch.Tensor
 
@@ -100,72 +102,46 @@ def _check_range(what: str, r, top: Optional[float] = None) -> tuple:
     return float(lo), float(hi)
 
 
-def _check_unit(what: str, p) -> float:
-    if isinstance(p, bool) or not isinstance(p, (int, float)):
-        raise TypeError(f"{what} must be a number (got {p!r})")
-    if not 0.0 <= p <= 1.0:   # also refuses NaN
-        raise ValueError(f"{what} must be in [0, 1] (got {p!r})")
-    return float(p)
+def _check_size(size) -> int:
+    if isinstance(size, bool) or not isinstance(size, int):
+        raise TypeError(f"size must be an int (got {size!r})")
+    if not 4 <= size <= MAX_SIDE or size % 4:
+        raise ValueError(f"size must be a multiple of 4 in 4..{MAX_SIDE} (got {size})")
+    return size
 
 
-def _check_source(u8) -> tuple:
-    if not isinstance(u8, Tensor) or u8.dtype != torch.uint8:
-        raise TypeError("RandomResizedCrop takes a uint8 [B,Hs,Ws,C] batch")
-    if u8.dim() != 4:
-        raise ValueError(f"RandomResizedCrop takes a uint8 [B,Hs,Ws,C] batch (got rank {u8.dim()})")
-    B, Hs, Ws, C = u8.shape
-    if C not in (1, 3):
-        raise ValueError(f"RandomResizedCrop: C must be 1 or 3 (got {C}; the layout is [B,Hs,Ws,C])")
-    if not 1 <= B <= MAX_BATCH:
-        raise ValueError(f"RandomResizedCrop: a batch holds 1..{MAX_BATCH} images (got {B})")
-    _check_src_hw(Hs, Ws)
-    return B, Hs, Ws, C
+def _check_source(u8, name: str = "RandomResizedCrop") -> tuple:
+    return check_u8_batch(name, u8, MAX_SRC, MAX_BATCH, source=True)
 
 
-def _check_src_hw(Hs, Ws) -> None:
-    if not (isinstance(Hs, int) and isinstance(Ws, int) and 1 <= Hs <= MAX_SRC and 1 <= Ws <= MAX_SRC):
-        raise ValueError(f"RandomResizedCrop: source sides must be 1..{MAX_SRC} (got {Hs}x{Ws})")
+def _check_src_hw(Hs, Ws, name: str = "RandomResizedCrop") -> None:
+    check_sides(name, Hs, Ws, MAX_SRC, "source")
 
 
 def _check_f32(X) -> tuple:
-    if not isinstance(X, Tensor) or X.dtype != torch.float32:
-        raise TypeError("RandomErasing takes an fp32 [B,C,H,W] batch")
-    if X.dim() != 4:
-        raise ValueError(f"RandomErasing takes an fp32 [B,C,H,W] batch (got rank {X.dim()})")
-    B, C, H, W = X.shape
-    if C < 1 or not 1 <= B <= MAX_BATCH:
-        raise ValueError(f"RandomErasing: a batch holds 1..{MAX_BATCH} images of at least one channel (got {B}, {C})")
-    _check_hw(H, W)
-    if W % 4:
-        raise ValueError("RandomErasing: W % 4 == 0 is required (as of every model input)")
-    return B, C, H, W
+    return check_f32_batch("RandomErasing", X, MAX_SIDE, MAX_BATCH)
 
 
 def _check_hw(H, W) -> None:
-    if not (isinstance(H, int) and isinstance(W, int) and 1 <= H <= MAX_SIDE and 1 <= W <= MAX_SIDE):
-        raise ValueError(f"RandomErasing: image sides must be 1..{MAX_SIDE} (got {H}x{W})")
+    check_sides("RandomErasing", H, W, MAX_SIDE)
 
 
 # ---------------------------------------------------------------------------------------------- RandomResizedCrop
-class CroppedBatch:
+class CroppedBatch(StagedBatch):
     """A stored uint8 [B,Hs,Ws,C] batch together with the RandomResizedCrop that cuts it: what `rrc.batch(u8)` returns
     and `AutoAugment.batch` / `RandomErasing.batch` accept in place of a tensor.  `.shape` is that of its output."""
 
+    key, word, accepts, names = "crop", "RandomResizedCrop", (), ("crop", "u8")
+
     def __init__(self, crop: "RandomResizedCrop", u8: Tensor):
         B, _, _, C = _check_source(u8)
-        self.crop, self.u8 = crop, u8
-        self._shape = torch.Size((B, crop.size, crop.size, C))
+        super().__init__(crop, u8, (B, crop.size, crop.size, C))
 
-    @property
-    def shape(self):
-        return self._shape
-
-    @property
-    def device(self):
-        return self.u8.device
+    def check_step(self) -> None:
+        raise TypeError("a RandomResizedCrop.batch(u8) is uint8: wrap it in AutoAugment.batch or RandomErasing.batch")
 
     def cropped(self) -> Tensor:
-        return self.crop(self.u8)
+        return self._launch(None)[0]
 
 
 class RandomResizedCrop(DeviceStepCounter):
@@ -183,18 +159,10 @@ class RandomResizedCrop(DeviceStepCounter):
 
     def __init__(self, size: int, scale=(0.08, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0), interpolation: str = "bilinear",
                  hflip: float = 0.5, seed: int = 0, first_index: int = 0):
-        if isinstance(size, bool) or not isinstance(size, int):
-            raise TypeError(f"size must be an int (got {size!r})")
-        if not 4 <= size <= MAX_SIDE or size % 4:
-            raise ValueError(f"size must be a multiple of 4 in 4..{MAX_SIDE} (got {size})")
-        self.size = size
+        self.size = _check_size(size)
         self.scale, self.ratio = _check_range("scale", scale), _check_range("ratio", ratio)
-        if not isinstance(interpolation, str):
-            raise TypeError(f"interpolation is a name: {', '.join(INTERPOLATIONS)} (got {interpolation!r})")
-        if interpolation not in INTERPOLATIONS:
-            raise ValueError(f"unknown interpolation {interpolation!r} (known: {', '.join(INTERPOLATIONS)})")
-        self.interpolation = interpolation
-        self.hflip = _check_unit("hflip", hflip)
+        self.interpolation = check_name("interpolation", interpolation, INTERPOLATIONS)
+        self.hflip = check_unit("hflip", hflip)
         super().__init__(seed, first_index)
         self._aspect: Optional[Tensor] = None
 
@@ -261,27 +229,23 @@ class RandomResizedCrop(DeviceStepCounter):
 CROP_MODES = ("center", "squash")
 
 
-class CenterCroppedBatch:
+class CenterCroppedBatch(StagedBatch):
     """A stored uint8 [B,Hs,Ws,C] batch together with the ResizeCenterCrop that cuts it: what `rcc.batch(u8)` returns and
     `predict`, `validate`, `estimate_loss` and `GraphedEval` accept in place of X.  `.shape` is that of the model input,
-    [B,C,size,size]."""
+    [B,C,size,size].  Two of them fit one captured graph if their transforms' parameters are equal."""
+
+    key, word, accepts, names = None, "ResizeCenterCrop", (), ("crop", "u8")
 
     def __init__(self, crop: "ResizeCenterCrop", u8: Tensor):
-        B, Hs, Ws, C = crop._check_source(u8)
-        self.crop, self.u8 = crop, u8
-        self._shape = torch.Size((B, C, crop.size, crop.size))
+        B, _, _, C = crop._check_source(u8)
+        super().__init__(crop, u8, (B, C, crop.size, crop.size))
 
-    @property
-    def shape(self):
-        return self._shape
-
-    @property
-    def device(self):
-        return self.u8.device
+    def fit_key(self) -> tuple:
+        return self.crop.params()
 
     def cropped(self) -> Tensor:
         """The fp32 model input: the transform's two launches on the current stream."""
-        return self.crop(self.u8)
+        return self._launch(None)[0]
 
 
 class ResizeCenterCrop:
@@ -299,24 +263,13 @@ class ResizeCenterCrop:
 
     def __init__(self, size: int, crop_pct: float = 0.875, interpolation: str = "bilinear", crop_mode: str = "center",
                  mean: float = 0.5, std: float = 0.5):
-        if isinstance(size, bool) or not isinstance(size, int):
-            raise TypeError(f"size must be an int (got {size!r})")
-        if not 4 <= size <= MAX_SIDE or size % 4:
-            raise ValueError(f"size must be a multiple of 4 in 4..{MAX_SIDE} (got {size})")
-        if isinstance(crop_pct, bool) or not isinstance(crop_pct, (int, float)):
-            raise TypeError(f"crop_pct must be a number (got {crop_pct!r})")
-        if not 0.0 < crop_pct <= 1.0:   # also refuses NaN
+        _check_size(size)
+        if not 0.0 < check_number("crop_pct", crop_pct) <= 1.0:   # also refuses NaN
             raise ValueError(f"crop_pct must be in (0, 1] (got {crop_pct!r})")
-        for what, names, v in (("interpolation", INTERPOLATIONS, interpolation), ("crop_mode", CROP_MODES, crop_mode)):
-            if not isinstance(v, str):
-                raise TypeError(f"{what} is a name: {', '.join(names)} (got {v!r})")
-            if v not in names:
-                raise ValueError(f"unknown {what} {v!r} (known: {', '.join(names)})")
-        for what, v in (("mean", mean), ("std", std)):
-            if isinstance(v, bool) or not isinstance(v, (int, float)):
-                raise TypeError(f"{what} must be a number (got {v!r})")
-        if not math.isfinite(mean):
-            raise ValueError(f"mean must be finite (got {mean!r})")
+        check_name("interpolation", interpolation, INTERPOLATIONS)
+        check_name("crop_mode", crop_mode, CROP_MODES)
+        check_number("std", std)
+        check_finite("mean", mean)
         if not 0.0 < std < math.inf:   # also refuses NaN
             raise ValueError(f"std must be positive (got {std!r})")
         self.size, self.crop_pct, self.interpolation, self.crop_mode = size, float(crop_pct), interpolation, crop_mode
@@ -332,7 +285,7 @@ class ResizeCenterCrop:
         """(H2, W2, top, left): the size the source is resized to and the window's corner in it.  torchvision's
         Resize(scale_size) / Resize((scale_size, scale_size)) and center_crop: int() truncates, round() is Python's (half
         to even)."""
-        _check_src_hw(Hs, Ws)
+        _check_src_hw(Hs, Ws, "ResizeCenterCrop")
         s = self.scale_size
         if self.crop_mode == "squash":
             H2 = W2 = s
@@ -345,15 +298,7 @@ class ResizeCenterCrop:
         return H2, W2, int(round((H2 - self.size) / 2.0)), int(round((W2 - self.size) / 2.0))
 
     def _check_source(self, u8) -> tuple:
-        if not isinstance(u8, Tensor) or u8.dtype != torch.uint8:
-            raise TypeError("ResizeCenterCrop takes a uint8 [B,Hs,Ws,C] batch")
-        if u8.dim() != 4:
-            raise ValueError(f"ResizeCenterCrop takes a uint8 [B,Hs,Ws,C] batch (got rank {u8.dim()})")
-        B, Hs, Ws, C = u8.shape
-        if C not in (1, 3):
-            raise ValueError(f"ResizeCenterCrop: C must be 1 or 3 (got {C}; the layout is [B,Hs,Ws,C])")
-        if not 1 <= B <= MAX_BATCH:
-            raise ValueError(f"ResizeCenterCrop: a batch holds 1..{MAX_BATCH} images (got {B})")
+        B, Hs, Ws, C = _check_source(u8, "ResizeCenterCrop")
         self.geometry(Hs, Ws)   # raises for a source it cannot take
         return B, Hs, Ws, C
 
@@ -394,40 +339,36 @@ class ResizeCenterCrop:
 
 
 # ---------------------------------------------------------------------------------------------- RandomErasing
-class ErasedBatch:
+class ErasedBatch(StagedBatch):
     """A batch together with the RandomErasing that runs on it inside the step: what `erase.batch(X)` returns and
     `Mixup.batch`, `train_step` and `GraphedTrainStep` accept in place of X.  X: an fp32 [B,C,H,W] tensor, an
     `AutoAugment.batch(...)`, or a `RandomResizedCrop.batch(u8)` (then normalised with mean, std by
     `ops.normalize_images`' kernel)."""
 
+    key, word, accepts, names = "erase", "RandomErasing", ("augment", "crop"), ("erase", "X")
+
     def __init__(self, erase: "RandomErasing", X, mean: float = 0.5, std: float = 0.5):
-        if isinstance(X, (AugmentedBatch, CroppedBatch)):
+        if self.takes(X):
             B, H, W, C = X.shape
             _check_hw(H, W)
             if W % 4:
                 raise ValueError("RandomErasing: W % 4 == 0 is required (as of every model input)")
-            self._shape = torch.Size((B, C, H, W))
+            shape = (B, C, H, W)
         else:
-            self._shape = torch.Size(_check_f32(X))
+            shape = _check_f32(X)
         if std == 0:
             raise ValueError("std must not be 0")
-        self.erase, self.X, self.mean, self.std = erase, X, float(mean), float(std)
+        self.mean, self.std = float(mean), float(std)
+        super().__init__(erase, X, shape, (self.mean, self.std))
 
-    @property
-    def shape(self):
-        return self._shape
-
-    @property
-    def device(self):
-        return self.X.device
+    def _run(self, x: Tensor, y, inplace: bool):
+        if x.dtype == torch.uint8:   # a crop's output: normalised here
+            x = normalize_images(x, self.mean, self.std)
+        return self.erase(x, inplace=inplace), y
 
     def erased(self) -> Tensor:
         """The launches of what X carries, then the draw and the apply; in place on a buffer made here."""
-        if isinstance(self.X, AugmentedBatch):
-            return self.erase(self.X.augmented(), inplace=True)
-        if isinstance(self.X, CroppedBatch):
-            return self.erase(normalize_images(self.X.cropped(), self.mean, self.std), inplace=True)
-        return self.erase(self.X)
+        return self._launch(None)[0]
 
 
 class RandomErasing(DeviceStepCounter):
@@ -443,13 +384,9 @@ class RandomErasing(DeviceStepCounter):
 
     def __init__(self, prob: float = 0.25, area=(0.02, 1.0 / 3.0), aspect=(0.3, 1.0 / 0.3), mode: str = "pixel",
                  seed: int = 0, first_index: int = 0):
-        self.prob = _check_unit("prob", prob)
+        self.prob = check_unit("prob", prob)
         self.area, self.aspect = _check_range("area", area, top=1.0), _check_range("aspect", aspect)
-        if not isinstance(mode, str):
-            raise TypeError(f"mode is a name: {', '.join(ERASE_MODES)} (got {mode!r})")
-        if mode not in ERASE_MODES:
-            raise ValueError(f"unknown mode {mode!r} (known: {', '.join(ERASE_MODES)})")
-        self.mode = mode
+        self.mode = check_name("mode", mode, ERASE_MODES)
         super().__init__(seed, first_index)
         self._aspect: Optional[Tensor] = None
         self._q: Optional[Tensor] = None

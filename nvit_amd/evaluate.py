@@ -17,7 +17,7 @@ from typing import Dict, Iterable, Tuple
 import torch
 
 from . import ops
-from .crop import CenterCroppedBatch
+from .stages import StagedBatch
 from .train import _unwrap, add_aux_losses
 
 Tensor = torch.Tensor
@@ -26,9 +26,15 @@ _KOHONEN_KEYS = (("val/consistency_loss", "kohonen_consistency"), ("val/smoothne
                  ("val/global_quantization_loss", "global_quantization"))
 
 
+def _split(X) -> tuple:
+    """X of an evaluation call -> (its fit key, its tensor): those of a `ResizeCenterCrop.batch(u8)`, the one batch object
+    that is no stage of a train step (stages.py); (None, X) for anything else."""
+    return (X.fit_key(), X.source()) if isinstance(X, StagedBatch) and X.key is None else (None, X)
+
+
 def _model_input(X):
     """X of an evaluation call -> the model's input: a `ResizeCenterCrop.batch(u8)` runs its two launches here."""
-    return X.cropped() if isinstance(X, CenterCroppedBatch) else X
+    return X.resolve()[0] if _split(X)[0] is not None else X
 
 
 class _eval_mode:
@@ -139,9 +145,8 @@ class GraphedEval:
     raises ValueError.
 
     X may be a `ResizeCenterCrop.batch(u8)`: the transform's two launches are captured with the forward, and the static
-    input is the uint8 source.  A batch then fits the graphs if it is such an object with the same source shape and the
-    same transform parameters; anything else (a plain tensor too) runs eagerly, as a `ResizeCenterCrop.batch(u8)` does on
-    graphs that were built on a tensor.
+    input is the uint8 source.  Which batches then fit the graphs, and that anything else (a plain tensor too, or such an
+    object on graphs built on a tensor) runs eagerly: DESIGN.md §7, "The batch-object protocol".
     """
 
     def __init__(self, model, X, y: Tensor, consistency_weight: float = 0.1, smoothness_weight: float = 0.1):
@@ -152,8 +157,9 @@ class GraphedEval:
             if X.device.type != "cuda" or y.device != X.device:
                 raise RuntimeError("GraphedEval: inputs must live on the HIP device")
             # the static input: the tensor, or the uint8 source under the transform that `_static` wraps around it
-            self._crop = X.crop if isinstance(X, CenterCroppedBatch) else None
-            self.X = X.clone() if self._crop is None else X.u8.clone(memory_format=torch.contiguous_format)
+            self._fit, src = _split(X)
+            self.X = X.clone() if self._fit is None else src.clone(memory_format=torch.contiguous_format)
+            self._static = self.X if self._fit is None else X.rebind(self.X)
             self.y = y.clone()
             dev = X.device
             self._acc = torch.zeros(4, device=dev, dtype=torch.float32)
@@ -163,20 +169,17 @@ class GraphedEval:
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):   # builds every cache (shadow tables, LDS attributes) ahead of the capture
-                self._metrics_batch(m, self._static(), self.y)
-                self._loss_batch(m, self._static(), self.y)
+                self._metrics_batch(m, self._static, self.y)
+                self._loss_batch(m, self._static, self.y)
             torch.cuda.current_stream().wait_stream(side)
             torch.cuda.synchronize()
             self._g_metrics, self._g_loss = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
             with torch.cuda.graph(self._g_metrics, stream=side):
-                self._logits = self._metrics_batch(m, self._static(), self.y)
+                self._logits = self._metrics_batch(m, self._static, self.y)
             with torch.cuda.graph(self._g_loss, stream=side):
-                self._loss_batch(m, self._static(), self.y)
+                self._loss_batch(m, self._static, self.y)
 
     # ---- one batch, eagerly or under capture: the loop bodies of validate / estimate_loss on this object's accumulators
-    def _static(self):
-        return self.X if self._crop is None else self._crop.batch(self.X)
-
     def _metrics_batch(self, m, X, y: Tensor) -> Tensor:
         logits, aux = m._forward(_model_input(X), False)
         ops.eval_metrics(logits, y, self._acc)
@@ -196,19 +199,14 @@ class GraphedEval:
                              "with; build a new GraphedEval")
 
     def _fits_x(self, X) -> bool:
-        if isinstance(X, CenterCroppedBatch):
-            if self._crop is None or X.crop.params() != self._crop.params():
-                return False
-            X = X.u8
-        elif self._crop is not None:
-            return False
-        return X.shape == self.X.shape and X.dtype == self.X.dtype and X.device == self.X.device
+        fit, X = _split(X)
+        return fit == self._fit and X.shape == self.X.shape and X.dtype == self.X.dtype and X.device == self.X.device
 
     def _fits(self, X, y: Tensor) -> bool:
         return self._fits_x(X) and y.shape == self.y.shape and y.dtype == self.y.dtype and y.device == self.y.device
 
     def _load_x(self, X) -> None:
-        self.X.copy_(X.u8 if isinstance(X, CenterCroppedBatch) else X, non_blocking=True)
+        self.X.copy_(_split(X)[1], non_blocking=True)
 
     def _load(self, X, y: Tensor) -> None:
         self._load_x(X)

@@ -22,9 +22,9 @@ import torch
 
 from . import _lib
 from ._lib import check
-from .augment import MAX_SIDE, AugmentedBatch, DeviceStepCounter, _f32_bits
-from .crop import ErasedBatch
+from .augment import MAX_SIDE, _f32_bits
 from .ops import _chk_dev, _p, _s
+from .stages import DeviceStepCounter, StagedBatch, check_f32_batch, check_number, check_sides, check_unit
 
 Tensor = torch.Tensor
 
@@ -129,38 +129,17 @@ def _f32(v: float) -> float:
 
 # ---------------------------------------------------------------------------------------------- argument checks
 def _check_alpha(what: str, a) -> float:
-    if isinstance(a, bool) or not isinstance(a, (int, float)):
-        raise TypeError(f"{what} must be a number (got {a!r})")
-    if a != 0 and not ALPHA_MIN <= a <= ALPHA_MAX:   # also refuses NaN
+    if check_number(what, a) != 0 and not ALPHA_MIN <= a <= ALPHA_MAX:   # also refuses NaN
         raise ValueError(f"{what} must be 0 (off) or in [{ALPHA_MIN}, {ALPHA_MAX}] (got {a!r})")
     return float(a)
 
 
-def _check_unit(what: str, p, open_top: bool = False) -> float:
-    if isinstance(p, bool) or not isinstance(p, (int, float)):
-        raise TypeError(f"{what} must be a number (got {p!r})")
-    if not (0.0 <= p < 1.0 if open_top else 0.0 <= p <= 1.0):   # also refuses NaN
-        raise ValueError(f"{what} must be in [0, 1{')' if open_top else ']'} (got {p!r})")
-    return float(p)
-
-
 def _check_images(X) -> tuple:
-    if not isinstance(X, Tensor) or X.dtype != torch.float32:
-        raise TypeError("Mixup takes an fp32 [B,C,H,W] batch")
-    if X.dim() != 4:
-        raise ValueError(f"Mixup takes an fp32 [B,C,H,W] batch (got rank {X.dim()})")
-    B, C, H, W = X.shape
-    if B < 1 or C < 1:
-        raise ValueError("Mixup: empty batch")
-    _check_hw(H, W)
-    if W % 4:
-        raise ValueError("Mixup: W % 4 == 0 is required (as of every model input)")
-    return B, C, H, W
+    return check_f32_batch("Mixup", X, MAX_SIDE)
 
 
 def _check_hw(H, W) -> None:
-    if not (isinstance(H, int) and isinstance(W, int) and 1 <= H <= MAX_SIDE and 1 <= W <= MAX_SIDE):
-        raise ValueError(f"Mixup: image sides must be 1..{MAX_SIDE} (got {H}x{W})")
+    check_sides("Mixup", H, W, MAX_SIDE)
 
 
 def _check_labels(y, B: Optional[int] = None) -> int:
@@ -184,7 +163,7 @@ class MixedTargets:
         if y.dim() != 1 or y2.shape != y.shape or lam.shape != y.shape:
             raise ValueError("MixedTargets: y, y2 and lam must be [B]")
         self.y, self.y2, self.lam = y, y2, lam
-        self.smoothing = _check_unit("smoothing", smoothing, open_top=True)
+        self.smoothing = check_unit("smoothing", smoothing, open_top=True)
 
     @property
     def shape(self):
@@ -206,37 +185,30 @@ class MixedTargets:
         return MixedTargets(self.y.to(device), self.y2.to(device), self.lam.to(device), self.smoothing)
 
 
-class MixedBatch:
+class MixedBatch(StagedBatch):
     """A batch together with the Mixup that mixes it inside the step: what `Mixup.batch(X)` returns and `train_step` /
     `GraphedTrainStep` accept in place of X.  X: an fp32 [B,C,H,W] tensor, an `AutoAugment.batch(u8)`, or a
-    `RandomErasing.batch(...)` (crop.py)."""
+    `RandomErasing.batch(...)` (crop.py).  `.shape` is X's."""
+
+    key, word, accepts, names = "mix", "Mixup", ("augment", "erase"), ("mix", "X")
 
     def __init__(self, mix: "Mixup", X):
-        if isinstance(X, (AugmentedBatch, ErasedBatch)):
-            B = X.shape[0]
-        else:
-            B = _check_images(X)[0]
-        self.mix, self.X, self.B = mix, X, B
-
-    @property
-    def shape(self):
-        return self.X.shape
-
-    @property
-    def device(self):
-        return self.X.device
+        self.B = X.shape[0] if self.takes(X) else _check_images(X)[0]
+        super().__init__(mix, X, X.shape)
 
     def check_labels(self, y) -> None:
         _check_labels(y, self.B)
 
+    def resolve(self, y=None):
+        self.check_labels(y)   # before any launch of what X carries
+        return super().resolve(y)
+
+    def _run(self, x: Tensor, y, inplace: bool):
+        return self.mix(x, y, inplace=inplace)
+
     def mixed(self, y: Tensor):
-        """(X', MixedTargets): the augmentation's launches if X has one, then the draw and the apply."""
-        self.check_labels(y)
-        if isinstance(self.X, AugmentedBatch):
-            return self.mix(self.X.augmented(), y, inplace=True)   # a fresh buffer: mixed in place
-        if isinstance(self.X, ErasedBatch):
-            return self.mix(self.X.erased(), y, inplace=True)      # (the erasing never returns the caller's tensor)
-        return self.mix(self.X, y)
+        """(X', MixedTargets): the launches of what X carries, then the draw and the apply."""
+        return self.resolve(y)
 
 
 class Mixup(DeviceStepCounter):
@@ -257,9 +229,9 @@ class Mixup(DeviceStepCounter):
                  label_smoothing: float = 0.1, seed: int = 0, first_index: int = 0):
         self.mixup_alpha = _check_alpha("mixup_alpha", mixup_alpha)
         self.cutmix_alpha = _check_alpha("cutmix_alpha", cutmix_alpha)
-        self.prob = _check_unit("prob", prob)
-        self.switch_prob = _check_unit("switch_prob", switch_prob)
-        self.label_smoothing = _check_unit("label_smoothing", label_smoothing, open_top=True)
+        self.prob = check_unit("prob", prob)
+        self.switch_prob = check_unit("switch_prob", switch_prob)
+        self.label_smoothing = check_unit("label_smoothing", label_smoothing, open_top=True)
         super().__init__(seed, first_index)
         self._q_mix: Optional[Tensor] = None
         self._q_cut: Optional[Tensor] = None

@@ -29,10 +29,11 @@ import torch
 
 from . import _lib
 from ._lib import check
-from .augment import OPS as _AA_OPS, AugmentedBatch, DeviceStepCounter, _check_hw, _f32_bits
-from .augment import _check_images as _check_u8_batch
+from .augment import OPS as _AA_OPS, AugmentedBatch, _apply_buffers, _f32_bits, affine_coefficients
+from .augment import _check_hw as _aa_check_hw, _check_images as _aa_check_images
 from .crop import normal_quantile_table
-from .ops import _chk_dev, _p, _s, round_up
+from .ops import _chk_dev, _p, _s
+from .stages import DeviceStepCounter, check_finite, check_name, check_number, check_unit
 
 Tensor = torch.Tensor
 
@@ -104,14 +105,6 @@ def _f64_ints(v: float) -> list:
     return list(struct.unpack("<ii", struct.pack("<d", float(v))))
 
 
-def _number(what: str, v) -> float:
-    if isinstance(v, bool) or not isinstance(v, (int, float)):
-        raise TypeError(f"{what} must be a number (got {v!r})")
-    if v != v or math.isinf(v):
-        raise ValueError(f"{what} must be finite (got {v!r})")
-    return float(v)
-
-
 def op_row(op: str, value=0, filter: str = "bilinear", H: Optional[int] = None, W: Optional[int] = None) -> list:
     """The ROW ints of one op with its raw argument (what `level_arg` returns): id, filter, then Pillow's six fp64
     coefficients (Image.rotate's exact matrix for Rotate), or the argument in int 2."""
@@ -125,26 +118,15 @@ def op_row(op: str, value=0, filter: str = "bilinear", H: Optional[int] = None, 
             raise TypeError(f"a filter is a name (got {filter!r})")
         if filter not in ("bilinear", "bicubic"):
             raise ValueError(f"the filter of an op is bilinear or bicubic (got {filter!r})")
-        value = _number(f"{op}'s argument", value)
+        value = check_finite(f"{op}'s argument", value)
         row[1] = INTERPOLATIONS[filter]
-        if op == "ShearX":
-            a = (1.0, value, 0.0, 0.0, 1.0, 0.0)
-        elif op == "ShearY":
-            a = (1.0, 0.0, 0.0, value, 1.0, 0.0)
-        elif op == "TranslateX":
-            a = (1.0, 0.0, value, 0.0, 1.0, 0.0)
-        elif op == "TranslateY":
-            a = (1.0, 0.0, 0.0, 0.0, 1.0, value)
-        else:   # Image.rotate about (W/2, H/2)
+        if op == "Rotate":   # Image.rotate reduces the angle first
             _check_hw(H, W)
-            r = -math.radians(value % 360.0)
-            c, s = round(math.cos(r), 15), round(math.sin(r), 15)
-            cx, cy = W / 2.0, H / 2.0
-            a = (c, s, c * -cx + s * -cy + 0.0 + cx, -s, c, -s * -cx + c * -cy + 0.0 + cy)
-        for j, v in enumerate(a):
+            value %= 360.0
+        for j, v in enumerate(affine_coefficients(op, value, H, W)):
             row[2 + 2 * j:4 + 2 * j] = _f64_ints(v)
     elif op in _ENHANCE:
-        row[2] = _f32_bits(_number(f"{op}'s factor", value))
+        row[2] = _f32_bits(check_finite(f"{op}'s factor", value))
     elif op in ("Posterize", "Solarize", "SolarizeAdd"):
         top = {"Posterize": 8, "Solarize": 256, "SolarizeAdd": 255}[op]
         if isinstance(value, bool) or not isinstance(value, int) or not 0 <= value <= top:
@@ -169,10 +151,11 @@ def _check_fill(fill) -> tuple:
 
 
 def _check_images(u8) -> tuple:
-    try:
-        return _check_u8_batch(u8)
-    except (TypeError, ValueError) as e:   # the same checks, under this stage's name
-        raise type(e)(str(e).replace("AutoAugment", "RandAugment")) from None
+    return _aa_check_images(u8, "RandAugment")
+
+
+def _check_hw(H, W) -> None:
+    _aa_check_hw(H, W, "RandAugment")
 
 
 def parse_config(config: str) -> dict:
@@ -238,29 +221,21 @@ class RandAugment(DeviceStepCounter):
             raise TypeError(f"num_layers must be an int (got {num_layers!r})")
         if not 1 <= num_layers <= MAX_LAYERS:
             raise ValueError(f"num_layers must be in 1..{MAX_LAYERS} (got {num_layers})")
-        for what, v in (("magnitude", magnitude), ("magnitude_std", magnitude_std), ("magnitude_max", magnitude_max),
-                        ("prob", prob), ("translate_pct", translate_pct)):
-            if isinstance(v, bool) or not isinstance(v, (int, float)):
-                raise TypeError(f"{what} must be a number (got {v!r})")
+        for what, v in (("magnitude", magnitude), ("magnitude_std", magnitude_std), ("magnitude_max", magnitude_max)):
+            check_number(what, v)
         if not 0.0 < magnitude_max <= LEVEL_DENOM:   # (every comparison also refuses NaN)
             raise ValueError(f"magnitude_max must be in (0, {LEVEL_DENOM:g}] (got {magnitude_max!r})")
         if not 0.0 <= magnitude <= LEVEL_DENOM:
             raise ValueError(f"magnitude must be in [0, {LEVEL_DENOM:g}] (got {magnitude!r})")
         if not magnitude_std >= 0.0:
             raise ValueError(f"magnitude_std must be >= 0, math.inf for the uniform magnitude (got {magnitude_std!r})")
-        if not 0.0 <= prob <= 1.0:
-            raise ValueError(f"prob must be in [0, 1] (got {prob!r})")
-        if not 0.0 <= translate_pct <= 1.0:
-            raise ValueError(f"translate_pct must be in [0, 1] (got {translate_pct!r})")
+        check_unit("prob", prob)
+        check_unit("translate_pct", translate_pct)
         if not isinstance(increasing, (bool, int)):
             raise TypeError(f"increasing must be a bool (got {increasing!r})")
-        if not isinstance(interpolation, str):
-            raise TypeError(f"interpolation is a name: {', '.join(INTERPOLATIONS)} (got {interpolation!r})")
-        if interpolation not in INTERPOLATIONS:
-            raise ValueError(f"unknown interpolation {interpolation!r} (known: {', '.join(INTERPOLATIONS)})")
-        for what, v in (("mean", mean), ("std", std)):
-            _number(what, v)
-        if std == 0:
+        check_name("interpolation", interpolation, INTERPOLATIONS)
+        check_finite("mean", mean)
+        if check_finite("std", std) == 0:
             raise ValueError("std must not be 0")
         self.magnitude, self.num_layers, self.magnitude_std = float(magnitude), num_layers, float(magnitude_std)
         self.magnitude_max, self.increasing, self.prob = float(magnitude_max), bool(increasing), float(prob)
@@ -318,18 +293,11 @@ class RandAugment(DeviceStepCounter):
         fill = self._fill3(C)
         _chk_dev(u8, params)
         u8, params = u8.contiguous(), params.contiguous()
-        ws_bytes = 2 * B * round_up(H * W * C, 256)
-        ws = torch.empty(ws_bytes, device=u8.device, dtype=torch.uint8)
-        if return_u8:
-            out = torch.empty_like(u8)
-            f32, o8 = None, out
-        else:
-            out = torch.empty((B, C, H, W), device=u8.device, dtype=torch.float32)
-            f32, o8 = out, None
+        ws, ws_bytes, f32, o8 = _apply_buffers(u8, return_u8)
         check(_lib.load().nvit_randaug_apply(_p(u8), _p(params), _p(f32), _p(o8), _p(ws), ws_bytes, B, H, W, C,
                                              params.shape[1], fill[0], fill[1], fill[2], self.mean, self.std, _s()),
               "nvit_randaug_apply")
-        return out
+        return o8 if return_u8 else f32
 
     def __call__(self, u8: Tensor) -> Tensor:
         B, H, W, C = _check_images(u8)
@@ -371,7 +339,7 @@ class RandAugment(DeviceStepCounter):
                     rows.append(op_row(e[0], e[1]["value"], *(e[2:3] or ("bilinear",)), H=H, W=W))
                     continue
                 op, m, sign, filt = (e + (0, 0, "bilinear")[len(e) - 1:])[:4]
-                m = _number("a magnitude", m)
+                m = check_finite("a magnitude", m)
                 if not 0.0 <= m <= LEVEL_DENOM:
                     raise ValueError(f"magnitude {m} outside [0, {LEVEL_DENOM:g}]")
                 if sign not in (0, 1):

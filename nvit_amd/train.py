@@ -18,10 +18,10 @@ from contextlib import nullcontext
 import torch
 
 from . import ops
-from .augment import AugmentedBatch
-from .crop import CenterCroppedBatch, CroppedBatch, ErasedBatch
-from .mix import MixedBatch, MixedTargets
+from .crop import CenterCroppedBatch
+from .mix import MixedTargets
 from .optim import FusedAdamW, renorm_matrices
+from .stages import StagedBatch, chain
 
 
 def _unwrap(model):
@@ -118,47 +118,24 @@ def _check_step_args(optimizer, X, accumulation_steps, skip_nonfinite) -> None:
 
 def _unwrap_input(X):
     """X of a step -> ({"mix": Mixup, "erase": (RandomErasing, mean, std), "augment": AutoAugment, "crop":
-    RandomResizedCrop}, the stages it carries; the tensor underneath).  The wrappers only nest in this order."""
-    stages = {}
-    if isinstance(X, MixedBatch):
-        stages["mix"], X = X.mix, X.X
-    if isinstance(X, ErasedBatch):
-        stages["erase"], X = (X.erase, X.mean, X.std), X.X
-    if isinstance(X, AugmentedBatch):
-        stages["augment"], X = X.augment, X.u8
-    if isinstance(X, CroppedBatch):
-        if "augment" not in stages and "erase" not in stages:
-            raise TypeError("a RandomResizedCrop.batch(u8) is uint8: wrap it in AutoAugment.batch or RandomErasing.batch")
-        stages["crop"], X = X.crop, X.u8
-    return stages, X
+    RandomResizedCrop}, the stages it carries, outermost first; the tensor underneath): the chain as a dict."""
+    if isinstance(X, StagedBatch):
+        X.check_step()
+    batches = chain(X)
+    return {b.key: b.fit_key() if b.extra else b.stage for b in batches}, (batches[-1].inner if batches else X)
 
 
 def _wrap_input(stages: dict, X):
     """The chain of `_unwrap_input` around another tensor."""
-    if "crop" in stages:
-        X = stages["crop"].batch(X)
-    if "augment" in stages:
-        X = stages["augment"].batch(X)
-    if "erase" in stages:
-        erase, mean, std = stages["erase"]
-        X = erase.batch(X, mean, std)
-    if "mix" in stages:
-        X = stages["mix"].batch(X)
+    for fit in reversed(stages.values()):
+        X = fit[0].batch(X, *fit[1:]) if isinstance(fit, tuple) else fit.batch(X)
     return X
 
 
 def _resolve_input(X, y):
     """(X, y) of a step -> the model's input and the loss's target: every launch of the chain that X carries (crop,
-    AutoAugment, erasing, Mixup - each once, for the whole batch), in order.  A tensor X comes back as it is."""
-    if isinstance(X, MixedBatch):
-        return X.mixed(y)   # the launches of what it wraps, then draw + apply
-    if isinstance(X, ErasedBatch):
-        return X.erased(), y
-    if isinstance(X, AugmentedBatch):
-        return X.augmented(), y
-    if isinstance(X, CroppedBatch):
-        _unwrap_input(X)   # raises
-    return X, y
+    augmentation, erasing, Mixup - each once, for the whole batch), in order.  A tensor X comes back as it is."""
+    return X.resolve(y) if isinstance(X, StagedBatch) else (X, y)
 
 
 def _forward_backward(model, X, y, n: int, before_micro=None):
@@ -211,21 +188,12 @@ def train_step(model, optimizer, X: torch.Tensor, y: torch.Tensor, grad_clip: fl
     skipped step; `optimizer.skipped_steps()` counts them.  Under DataParallel every rank sees the same averaged
     gradients, hence the same decision.  Needs FusedAdamW.
 
-    X may be an `AutoAugment.batch(u8)` (augment.py): the uint8 [B,H,W,C] batch together with the augmentation that
-    turns it into the model's input.  Its two launches (draw, apply) then run ahead of the forward, once for the whole
-    batch, before any accumulation split; the augmentation's step counter advances by one per call.  A tensor X takes
-    exactly the launches it always took.
-
-    X may also be a `Mixup.batch(X)` (mix.py) around a tensor or around an `AutoAugment.batch(u8)`: Mixup / CutMix with
-    label smoothing.  Its draw and apply run once for the whole batch, after the augmentation's launches and ahead of the
-    forward; the loss is then the soft-target cross-entropy of the drawn `MixedTargets`, and under accumulation
-    micro-batch i takes rows [i*b, (i+1)*b) of the mixed batch and of the targets (a row's partner may lie in another
-    micro-batch; the targets carry the partner's label).  The returned logits belong to the mixed batch.
-
-    The full input chain (crop.py) is `mix.batch(erase.batch(aug.batch(rrc.batch(u8))))`: RandomResizedCrop + flip on the
-    stored uint8 batch, AutoAugment on the crops, RandomErasing on the normalised batch, then Mixup / CutMix; any stage may
-    be left out (an erasing directly around a crop normalises it first).  Every stage's launches run once for the whole
-    batch, in this order, ahead of the forward and of any accumulation split, and every stage's counter advances by one.
+    X may be a chain of the input stages, `mix.batch(erase.batch(aug.batch(rrc.batch(u8))))` or any part of it in that
+    order (stages.py; DESIGN.md §7, "The batch-object protocol"): every stage's launches run once for the whole batch, ahead
+    of the forward and of any accumulation split, and every stage's counter advances by one per call.  With a Mixup the loss
+    is the soft-target cross-entropy of the drawn `MixedTargets`, the returned logits belong to the mixed batch, and under
+    accumulation micro-batch i takes rows [i*b, (i+1)*b) of the mixed batch and of the targets (a row's partner may lie in
+    another micro-batch; the targets carry the partner's label).  A tensor X takes exactly the launches it always took.
 
     A `DropPath` attached to the model (`ViT.attach_drop_path`) needs nothing here: every training forward draws its own
     gate table, so with accumulation_steps = N its counter advances by N, each micro-batch drawing for its own rows.  The
@@ -283,20 +251,11 @@ class GraphedTrainStep:
     out (no host code runs between backward and update, so only the device can): `optimizer.skipped_steps()` and
     `state_dict()` read the counts back.
 
-    With X an `AutoAugment.batch(u8)` the static input buffer is the uint8 batch and the augmentation's two launches
-    are captured ahead of the forward: its step counter is a device int64 that the draw kernel advances itself, so
-    every replay draws fresh parameters with no host code in between.  The warm-up steps are steps of the augmentation
-    too (they advance its counter, as they advance the weights); the capture pass is not.  Calls then take the uint8
-    batch (or another `batch(u8)` of the same augmentation).
-
-    With X a `Mixup.batch(...)` (around a tensor or around an `AutoAugment.batch(u8)`) the static inputs stay the raw X
-    (or uint8 batch) and y; the Mixup's draw and apply are captured ahead of the forward and after the augmentation, and
-    the same rule holds for its counter: warm-up steps advance it, the capture pass does not, every replay does.  Calls
-    take the raw batch or a `batch(...)` of the same Mixup; one of another Mixup raises ValueError.
-
-    The same holds for every stage of the full chain `mix.batch(erase.batch(aug.batch(rrc.batch(u8))))` (crop.py): the
-    static inputs are the innermost tensor (the stored uint8 batch) and y, every stage's launches are captured in order,
-    and every replay draws fresh boxes.  Calls take the innermost tensor or a chain of the captured objects.
+    With X a chain of the input stages (stages.py; DESIGN.md §7, "The batch-object protocol", also for what a call may
+    then carry) the static inputs are the chain's innermost tensor and y, and every stage's launches are captured in order
+    ahead of the forward.  A stage's step counter is a device int64 that its draw kernel advances itself, so every replay
+    draws afresh with no host code in between: the warm-up steps are steps of every stage (they advance its counter, as
+    they advance the weights), the capture pass is not, every replay is.
 
     A `ModelEma` (ema.py) attached to the optimizer before this object is built is part of the captured step: its tick and
     its update follow the optimizer's launches, and its count lives on the device.  The warm-up steps are updates, as they
@@ -336,25 +295,37 @@ class GraphedTrainStep:
             raise RuntimeError("GraphedTrainStep: wrap the bare model (data-parallel steps run eagerly)")
         if X.device.type != "cuda":
             raise RuntimeError("GraphedTrainStep: inputs must live on the HIP device")
-        if isinstance(X, MixedBatch):
+        # the captured chain: per stage key what a call's stage must match, and the chain itself around the static input
+        self._fit = {b.key: b.fit_key() for b in chain(X)}
+        self.mix, self.erase, self.augment, self.crop = (self._fit.get(k, (None,))[0]
+                                                         for k in ("mix", "erase", "augment", "crop"))
+        if self.mix is not None:
             X.check_labels(y)
-        self._stages, X = _unwrap_input(X)
-        self.mix, self.augment = self._stages.get("mix"), self._stages.get("augment")
-        self.erase, self.crop = self._stages.get("erase", (None,))[0], self._stages.get("crop")
+        if self._fit:
+            X.check_step()
+        self.X, self.y = (X.source() if self._fit else X).clone(), y.clone()
+        self._input = X.rebind(self.X) if self._fit else self.X
         self.model, self.optimizer, self.grad_clip = model, optimizer, grad_clip
         self.ema = optimizer.ema   # the ModelEma (or none) whose update the warm-up steps run and the capture records
         self.schedule = optimizer.schedule   # the LRSchedule (or none) whose launch the captured optimizer step contains
         self.drop_path = m.drop_path   # the DropPath (or none) whose draw the captured forwards contain
         self.patch_drop = m.patch_drop   # the PatchDropout (or none), likewise
         self._size_epoch = m._size_epoch   # ViT.set_input_size replaces parameters whose addresses the graph holds
+        # what a call must find as it was at capture time: (the refusal's words, where a call finds it, what it was)
+        self._attached = (
+            ("this graph was captured with another ModelEma (or none)", lambda: optimizer.ema, self.ema),
+            ("this graph was captured with another LRSchedule (or none)", lambda: optimizer.schedule, self.schedule),
+            ("this graph was captured with another DropPath (or none)", lambda: m.drop_path, self.drop_path),
+            ("this graph was captured with another PatchDropout (or none)", lambda: m.patch_drop, self.patch_drop),
+            ("ViT.set_input_size replaced the position embeddings this graph was captured with; build a new optimizer and "
+             "a new GraphedTrainStep", lambda: m._size_epoch, self._size_epoch))
         self.accumulation_steps, self.skip_nonfinite = accumulation_steps, bool(skip_nonfinite)
         N = accumulation_steps
-        self.X, self.y = X.clone(), y.clone()
         side = torch.cuda.Stream()   # warm-up and capture share one stream: autograd's gradient accumulators are
         side.wait_stream(torch.cuda.current_stream())   # bound to the stream they are first used on
         with torch.cuda.stream(side):
             for _ in range(max(1, warmup)):   # builds every cache (shadow/renorm tables, LDS attributes, workspaces)
-                train_step(model, optimizer, self._input(), self.y, grad_clip, accumulation_steps=N,
+                train_step(model, optimizer, self._input, self.y, grad_clip, accumulation_steps=N,
                            skip_nonfinite=self.skip_nonfinite)
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
@@ -377,7 +348,7 @@ class GraphedTrainStep:
 
         try:
             with torch.cuda.graph(self.graph, stream=side):
-                Xin, yin = _resolve_input(self._input(), self.y)
+                Xin, yin = _resolve_input(self._input, self.y)
                 logits, loss, aux = _forward_backward(model, Xin, yin, N, hand_rates)
                 gnorm = optimizer.step_fused(model, grad_clip, skip_nonfinite=self.skip_nonfinite)
         finally:
@@ -393,9 +364,6 @@ class GraphedTrainStep:
         self._grads = [p.grad for p in m.parameters() if p.grad is not None]
         self._table = optimizer._cache
         optimizer.zero_grad(set_to_none=True)
-
-    def _input(self):
-        return _wrap_input(self._stages, self.X)
 
     def set_lr(self, lr: float) -> None:
         if self.optimizer.schedule is not None:
@@ -425,36 +393,17 @@ class GraphedTrainStep:
     def __call__(self, X: torch.Tensor, y: torch.Tensor):
         """One optimizer step on (X, y); returns (logits, loss, aux, grad_norm) as static device tensors that the
         next call overwrites."""
-        if isinstance(X, MixedBatch):
-            if X.mix is not self.mix:
-                raise ValueError("GraphedTrainStep: this graph was captured with another Mixup (or none)")
-            X = X.X
-        if isinstance(X, ErasedBatch):
-            if X.erase is not self.erase:
-                raise ValueError("GraphedTrainStep: this graph was captured with another RandomErasing (or none)")
-            if (X.mean, X.std) != self._stages["erase"][1:]:
-                raise ValueError("GraphedTrainStep: this graph was captured with another mean / std of erase.batch "
-                                 f"{self._stages['erase'][1:]} (got {(X.mean, X.std)})")
-            X = X.X
-        if isinstance(X, AugmentedBatch):
-            if X.augment is not self.augment:
-                raise ValueError("GraphedTrainStep: this graph was captured with another augmentation (or none)")
-            X = X.u8
-        if isinstance(X, CroppedBatch):
-            if X.crop is not self.crop:
-                raise ValueError("GraphedTrainStep: this graph was captured with another RandomResizedCrop (or none)")
-            X = X.u8
-        if self.optimizer.ema is not self.ema:
-            raise ValueError("GraphedTrainStep: this graph was captured with another ModelEma (or none)")
-        if self.optimizer.schedule is not self.schedule:
-            raise ValueError("GraphedTrainStep: this graph was captured with another LRSchedule (or none)")
-        if _unwrap(self.model).drop_path is not self.drop_path:
-            raise ValueError("GraphedTrainStep: this graph was captured with another DropPath (or none)")
-        if _unwrap(self.model).patch_drop is not self.patch_drop:
-            raise ValueError("GraphedTrainStep: this graph was captured with another PatchDropout (or none)")
-        if _unwrap(self.model)._size_epoch != self._size_epoch:
-            raise ValueError("GraphedTrainStep: ViT.set_input_size replaced the position embeddings this graph was "
-                             "captured with; build a new optimizer and a new GraphedTrainStep")
+        for b in chain(X):   # any of the captured stages, each the captured object (DESIGN.md §7, the batch-object protocol)
+            fit = self._fit.get(b.key, (None,))
+            if b.stage is not fit[0]:
+                raise ValueError(f"GraphedTrainStep: this graph was captured with another {b.word} (or none)")
+            if b.fit_key() != fit:
+                raise ValueError(f"GraphedTrainStep: this graph was captured with another mean / std of {b.key}.batch "
+                                 f"{fit[1:]} (got {b.extra})")
+            X = b.inner
+        for words, now, captured in self._attached:
+            if now() != captured:
+                raise ValueError(f"GraphedTrainStep: {words}")
         self.X.copy_(X, non_blocking=True)
         self.y.copy_(y, non_blocking=True)
         self._advance_som()
