@@ -17,6 +17,9 @@
  *     parameters, gradients and all reductions are fp32 in both modes.
  *   - token-major activations are [M, C] with M = B*T rows; per-head tensors are
  *     [B, H, T, d] contiguous.
+ *   - Python binds from this text (nvit_amd/_lib.py), so a prototype is written `<return> nvit_<name>(<type> <name>, ...);`
+ *     outside comments: every parameter named; pointers, int, unsigned, int64_t, uint64_t, float, double; returns of
+ *     those, void or const char*.  Anything else fails the import.
  */
 #ifndef NVIT_HIP_H
 #define NVIT_HIP_H

@@ -18,8 +18,8 @@ from typing import Optional, Sequence
 import torch
 
 from . import _lib
-from ._lib import check
-from .ops import _chk_dev, _p, _s, round_up
+from ._lib import call
+from .ops import _chk_dev, _s, round_up
 from .stages import DeviceStepCounter, StagedBatch, check_sides, check_u8_batch   # noqa: F401 (DeviceStepCounter: re-exported)
 
 Tensor = torch.Tensor
@@ -292,8 +292,8 @@ class AutoAugment(DeviceStepCounter):
             raise ValueError("AutoAugment.draw: B must be >= 1")
         tab = self._argtab(H, W)
         params = torch.empty((B, 2, ROW), device=self.device, dtype=torch.int32)
-        check(_lib.load().nvit_augment_draw(_p(self._policy_dev), len(self.policy), self.seed, _p(self._step),
-                                            self.first_index, _p(tab), _p(params), B, _s()), "nvit_augment_draw")
+        call("nvit_augment_draw", self._policy_dev, len(self.policy), self.seed, self._step, self.first_index, tab, params,
+             B, _s())
         return params
 
     def apply(self, u8: Tensor, params: Tensor, return_u8: bool = False):
@@ -307,8 +307,7 @@ class AutoAugment(DeviceStepCounter):
         _chk_dev(u8, params)
         u8, params = u8.contiguous(), params.contiguous()
         ws, ws_bytes, f32, o8 = _apply_buffers(u8, return_u8)
-        check(_lib.load().nvit_augment_apply(_p(u8), _p(params), _p(f32), _p(o8), _p(ws), ws_bytes, B, H, W, C,
-                                             self.mean, self.std, _s()), "nvit_augment_apply")
+        call("nvit_augment_apply", u8, params, f32, o8, ws, ws_bytes, B, H, W, C, self.mean, self.std, _s())
         return o8 if return_u8 else f32
 
     def __call__(self, u8: Tensor) -> Tensor:

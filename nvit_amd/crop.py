@@ -33,9 +33,9 @@ from typing import Optional, Sequence
 import torch
 
 from . import _lib
-from ._lib import check
+from ._lib import call
 from .augment import MAX_SIDE
-from .ops import _chk_dev, _p, _s, normalize_images
+from .ops import _chk_dev, _s, normalize_images
 from .stages import (DeviceStepCounter, StagedBatch, check_f32_batch, check_finite, check_name, check_number, check_sides,
                      check_u8_batch, check_unit)
 
@@ -179,9 +179,8 @@ class RandomResizedCrop(DeviceStepCounter):
             raise ValueError("RandomResizedCrop.draw: B must be an int >= 1")
         _check_src_hw(Hs, Ws)
         table = torch.empty((B, ROW), device=self.device, dtype=torch.int32)
-        check(_lib.load().nvit_crop_draw(self.seed, _p(self._step), self.first_index, _p(self._aspect), self.scale[0],
-                                         self.scale[1], self.ratio[0], self.ratio[1], self.hflip, _p(table), B, Hs, Ws,
-                                         _s()), "nvit_crop_draw")
+        call("nvit_crop_draw", self.seed, self._step, self.first_index, self._aspect, self.scale[0], self.scale[1],
+             self.ratio[0], self.ratio[1], self.hflip, table, B, Hs, Ws, _s())
         return table
 
     def apply(self, u8: Tensor, table: Tensor) -> Tensor:
@@ -192,14 +191,13 @@ class RandomResizedCrop(DeviceStepCounter):
             raise ValueError(f"RandomResizedCrop.apply: the table must be int32 [{B},{ROW}]")
         _chk_dev(u8, table)
         u8, table = u8.contiguous(), table.contiguous()
-        lib, interp = _lib.load(), INTERPOLATIONS[self.interpolation]
-        ws_bytes = lib.nvit_crop_ws_bytes(B, Hs, Ws, C, self.size, interp)   # taps + the [Hs,size,C] intermediates
+        interp = INTERPOLATIONS[self.interpolation]
+        ws_bytes = _lib.load().nvit_crop_ws_bytes(B, Hs, Ws, C, self.size, interp)   # taps + the [Hs,size,C] intermediates
         if ws_bytes < 0:
             raise ValueError(f"RandomResizedCrop.apply: unsupported shape {tuple(u8.shape)} -> {self.size}")
         ws = torch.empty(ws_bytes, device=u8.device, dtype=torch.uint8)
         out = torch.empty((B, self.size, self.size, C), device=u8.device, dtype=torch.uint8)
-        check(lib.nvit_crop_apply(_p(u8), _p(table), _p(out), _p(ws), ws_bytes, B, Hs, Ws, C, self.size, interp, _s()),
-              "nvit_crop_apply")
+        call("nvit_crop_apply", u8, table, out, ws, ws_bytes, B, Hs, Ws, C, self.size, interp, _s())
         return out
 
     def __call__(self, u8: Tensor) -> Tensor:
@@ -316,16 +314,15 @@ class ResizeCenterCrop:
             raise ValueError(f"ResizeCenterCrop.apply: the window at ({top}, {left}) leaves the {H2}x{W2} image")
         _chk_dev(u8)
         u8 = u8.contiguous()
-        lib, interp, size = _lib.load(), INTERPOLATIONS[self.interpolation], self.size
-        ws_bytes = lib.nvit_center_crop_ws_bytes(B, Hs, Ws, C, H2, W2, top, left, size, interp)
+        interp, size = INTERPOLATIONS[self.interpolation], self.size
+        ws_bytes = _lib.load().nvit_center_crop_ws_bytes(B, Hs, Ws, C, H2, W2, top, left, size, interp)
         if ws_bytes < 0:
             raise ValueError(f"ResizeCenterCrop.apply: unsupported shape {tuple(u8.shape)} -> {H2}x{W2} -> {size}")
         ws = torch.empty(ws_bytes, device=u8.device, dtype=torch.uint8)   # taps + the [rows read,size,C] intermediates
         o8 = torch.empty((B, size, size, C), device=u8.device, dtype=torch.uint8) if return_u8 or both else None
         of = torch.empty((B, C, size, size), device=u8.device, dtype=torch.float32) if both or not return_u8 else None
-        check(lib.nvit_center_crop_apply(_p(u8), _p(o8) if o8 is not None else None, _p(of) if of is not None else None,
-                                         _p(ws), ws_bytes, B, Hs, Ws, C, H2, W2, top, left, size, interp, self.mean,
-                                         self.std, _s()), "nvit_center_crop_apply")
+        call("nvit_center_crop_apply", u8, o8, of, ws, ws_bytes, B, Hs, Ws, C, H2, W2, top, left, size, interp, self.mean,
+             self.std, _s())
         return (of, o8) if both else (o8 if return_u8 else of)
 
     def __call__(self, u8: Tensor, return_u8: bool = False):
@@ -405,8 +402,8 @@ class RandomErasing(DeviceStepCounter):
             raise ValueError("RandomErasing.draw: B must be an int >= 1")
         _check_hw(H, W)
         table = torch.empty((B, ERASE_ROW), device=self.device, dtype=torch.int32)
-        check(_lib.load().nvit_erase_draw(self.seed, _p(self._step), self.first_index, _p(self._aspect), self.area[0],
-                                          self.area[1], self.prob, _p(table), B, H, W, _s()), "nvit_erase_draw")
+        call("nvit_erase_draw", self.seed, self._step, self.first_index, self._aspect, self.area[0], self.area[1], self.prob,
+             table, B, H, W, _s())
         return table
 
     def apply(self, X: Tensor, table: Tensor, inplace: bool = False) -> Tensor:
@@ -421,8 +418,7 @@ class RandomErasing(DeviceStepCounter):
             raise ValueError("RandomErasing.apply: in place needs a contiguous batch")
         X, table = X.contiguous(), table.contiguous()
         out = X if inplace else torch.empty_like(X)
-        check(_lib.load().nvit_erase_apply(_p(X), _p(table), _p(self._q), _p(out), ERASE_MODES[self.mode], B, C, H, W, _s()),
-              "nvit_erase_apply")
+        call("nvit_erase_apply", X, table, self._q, out, ERASE_MODES[self.mode], B, C, H, W, _s())
         return out
 
     def __call__(self, X: Tensor, inplace: bool = False) -> Tensor:

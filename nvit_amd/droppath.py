@@ -15,9 +15,9 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import check
+from ._lib import call
 from .augment import DeviceStepCounter
-from .ops import _p, _s
+from .ops import _s
 
 Tensor = torch.Tensor
 MAX_GATES = _lib.const("DROPPATH_MAX_GATES")
@@ -75,7 +75,6 @@ class DropPath(DeviceStepCounter):
             raise ValueError(f"DropPath.draw: B must be an int >= 1 with 2 * n_layer * B <= {MAX_GATES}")
         rates = self._rates(n_layer)
         table = torch.empty((2 * n_layer, B), device=self.device, dtype=torch.float32)
-        check(_lib.load().nvit_droppath_draw(self.seed, _p(self._step), self.first_index, _p(rates),
-                                             int(bool(self.scale_by_keep)), _p(table), n_layer, B, _s()),
-              "nvit_droppath_draw")
+        call("nvit_droppath_draw", self.seed, self._step, self.first_index, rates, int(bool(self.scale_by_keep)), table,
+             n_layer, B, _s())
         return table

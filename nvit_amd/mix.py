@@ -21,9 +21,9 @@ from typing import Optional, Sequence
 import torch
 
 from . import _lib
-from ._lib import check
+from ._lib import call
 from .augment import MAX_SIDE, _f32_bits
-from .ops import _chk_dev, _p, _s
+from .ops import _chk_dev, _s
 from .stages import DeviceStepCounter, StagedBatch, check_f32_batch, check_number, check_sides, check_unit
 
 Tensor = torch.Tensor
@@ -263,9 +263,8 @@ class Mixup(DeviceStepCounter):
         table = torch.empty((B, ROW), device=y.device, dtype=torch.int32)
         lam = torch.empty(B, device=y.device, dtype=torch.float32)
         y2 = torch.empty_like(y)
-        check(_lib.load().nvit_mix_draw(self.seed, _p(self._step), self.first_index, _p(self._q_mix), _p(self._q_cut),
-                                        self.prob, self.switch_prob, _p(y), _p(table), _p(lam), _p(y2), B, H, W, _s()),
-              "nvit_mix_draw")
+        call("nvit_mix_draw", self.seed, self._step, self.first_index, self._q_mix, self._q_cut, self.prob, self.switch_prob,
+             y, table, lam, y2, B, H, W, _s())
         return table, MixedTargets(y, y2, lam, self.label_smoothing)
 
     def apply(self, X: Tensor, table: Tensor, inplace: bool = False) -> Tensor:
@@ -279,7 +278,7 @@ class Mixup(DeviceStepCounter):
             raise ValueError("Mixup.apply: in place needs a contiguous batch")
         X, table = X.contiguous(), table.contiguous()
         out = X if inplace else torch.empty_like(X)
-        check(_lib.load().nvit_mix_apply(_p(X), _p(table), _p(out), B, C, H, W, _s()), "nvit_mix_apply")
+        call("nvit_mix_apply", X, table, out, B, C, H, W, _s())
         return out
 
     def __call__(self, X: Tensor, y: Tensor, inplace: bool = False):

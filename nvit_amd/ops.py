@@ -13,7 +13,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib, resample
-from ._lib import BF16, F32, check
+from ._lib import BF16, F32, call, check  # noqa: F401 (check: tests make raw calls through ops.check)
 
 Tensor = torch.Tensor
 # layout numbers shared with the kernels: each is written once, in include/nvit_hip.h
@@ -79,8 +79,8 @@ def gemm_nt(A: Tensor, B: Tensor, M: int, N: int, K: int, out: Optional[Tensor] 
     if out is None:
         out = torch.empty((M, N), device=A.device, dtype=out_dtype)
     ldc = out.stride(0) if ldc is None else ldc
-    check(_lib.load().nvit_gemm_nt(dt, _p(A), lda, _p(B), ldb, _p(out), ldc, dt_of(out), M, N, K, _p(bias),
-                                   _p(colscale), _p(rowadd), rowadd_period, int(accumulate), _s()), "nvit_gemm_nt")
+    call("nvit_gemm_nt", dt, A, lda, B, ldb, out, ldc, dt_of(out), M, N, K, bias, colscale, rowadd, rowadd_period,
+         int(accumulate), _s())
     return out
 
 
@@ -111,8 +111,7 @@ def gemm_nt_swiglu(A: Tensor, B: Tensor, M: int, F: int, K: int, gs: Optional[Te
     _chk_fused_bias(bias, 2 * F, A, "gemm_nt_swiglu")
     uv = torch.empty((M, 2 * F), device=A.device, dtype=torch.bfloat16)
     xm = torch.empty((M, F), device=A.device, dtype=torch.bfloat16)
-    check(_lib.load().nvit_gemm_nt_swiglu(dt_of(A), _p(A), A.stride(0), _p(B), B.stride(0), _p(uv), _p(xm), M, F, K,
-                                          _p(gs), gscale, _p(bias), _s()), "nvit_gemm_nt_swiglu")
+    call("nvit_gemm_nt_swiglu", dt_of(A), A, A.stride(0), B, B.stride(0), uv, xm, M, F, K, gs, gscale, bias, _s())
     return uv, xm
 
 
@@ -122,8 +121,7 @@ def gemm_nt_swiglu_act(A: Tensor, B: Tensor, M: int, F: int, K: int, gs: Optiona
     _chk_dev(A, B)
     _chk_fused_bias(bias, 2 * F, A, "gemm_nt_swiglu_act")
     xm = torch.empty((M, F), device=A.device, dtype=torch.bfloat16)
-    check(_lib.load().nvit_gemm_nt_swiglu_act(dt_of(A), _p(A), A.stride(0), _p(B), B.stride(0), _p(xm), M, F, K,
-                                              _p(gs), gscale, _p(bias), _s()), "nvit_gemm_nt_swiglu_act")
+    call("nvit_gemm_nt_swiglu_act", dt_of(A), A, A.stride(0), B, B.stride(0), xm, M, F, K, gs, gscale, bias, _s())
     return xm
 
 
@@ -133,8 +131,7 @@ def gemm_nt_swiglu_bwd(A: Tensor, B: Tensor, uv: Tensor, M: int, F: int, K: int,
     duv = torch.empty((M, 2 * F), device=A.device, dtype=torch.bfloat16)
     part = (torch.empty((round_up(M, SWIGLU_BWD_TILE_ROWS) // SWIGLU_BWD_PART_ROWS, 2 * F), device=A.device,
                         dtype=torch.float32) if gs is not None else None)
-    check(_lib.load().nvit_gemm_nt_swiglu_bwd(dt_of(A), _p(A), A.stride(0), _p(B), B.stride(0), _p(uv), _p(duv),
-                                              _p(part), M, F, K, _p(gs), gscale, _s()), "nvit_gemm_nt_swiglu_bwd")
+    call("nvit_gemm_nt_swiglu_bwd", dt_of(A), A, A.stride(0), B, B.stride(0), uv, duv, part, M, F, K, gs, gscale, _s())
     return duv, part
 
 
@@ -170,9 +167,8 @@ def gemm_nt_qknorm(A: Tensor, B: Tensor, M: int, K: int, nparts: int, part0: int
     if bufs is None:
         bufs = qk_buffers(dt_of(A), Bsz, T, H, d, A.device, norm=sqk is not None)
     qh, kh, vh, rq, rk = bufs
-    check(_lib.load().nvit_gemm_nt_qknorm(dt_of(A), _p(A), A.stride(0), _p(B), B.stride(0), M, K, nparts, part0,
-                                          _p(sqk), c_q, q_prescale, _p(qh), _p(kh), _p(vh), _p(rq), _p(rk), T, H, d,
-                                          _p(bias), _s()), "nvit_gemm_nt_qknorm")
+    call("nvit_gemm_nt_qknorm", dt_of(A), A, A.stride(0), B, B.stride(0), M, K, nparts, part0, sqk, c_q, q_prescale, qh, kh,
+         vh, rq, rk, T, H, d, bias, _s())
     return bufs
 
 
@@ -222,8 +218,7 @@ def gemm_tn(A: Tensor, B: Tensor, G: Tensor, Mred: int, N: int, K: int, perm: in
     splits = tn_splits(Mred, N, K, dt)
     nbytes = splits * N * K * 4 + 256
     ws = _workspace(nbytes, A.device)
-    check(_lib.load().nvit_gemm_tn(dt, _p(A), lda, _p(B), ldb, _p(G), ldg, Mred, N, K, splits, _p(ws),
-                                   ws.numel() * 4, perm, int(accumulate), _s()), "nvit_gemm_tn")
+    call("nvit_gemm_tn", dt, A, lda, B, ldb, G, ldg, Mred, N, K, splits, ws, ws.numel() * 4, perm, int(accumulate), _s())
     return G
 
 
@@ -267,8 +262,7 @@ def lerp_fwd(dt: int, h: Tensor, y: Tensor, alpha: Tensor, c_a: float, skip_x: O
     out = torch.empty_like(h)
     out_lo = torch.empty((M, Cc), device=h.device, dtype=tdtype(dt)) if want_lo else None
     T = _chk_gate(gate, M, h, "lerp_fwd")
-    check(_lib.load().nvit_lerp_fwd(dt, _p(h), _p(y), dt_of(y), _p(alpha), c_a, _p(skip_x), _p(skip), _p(gate), T,
-                                    _p(out), _p(out_lo), M, Cc, _s()), "nvit_lerp_fwd")
+    call("nvit_lerp_fwd", dt, h, y, dt_of(y), alpha, c_a, skip_x, skip, gate, T, out, out_lo, M, Cc, _s())
     return out, out_lo
 
 
@@ -305,9 +299,8 @@ def lerp_bwd(dt: int, dout: Tensor, h: Tensor, y: Tensor, alpha: Tensor, c_a: fl
     dskip_x = torch.empty_like(h) if skip_x is not None else None
     part = torch.empty((ROW_WAVES * nblk, Cc), device=dev, dtype=torch.float32)   # one row of column partials per wave
     pskip = torch.empty((ROW_WAVES * nblk,), device=dev, dtype=torch.float32) if skip_x is not None else None
-    check(_lib.load().nvit_lerp_bwd(dt, _p(dout), _p(dout_add), _p(h), _p(y), dt_of(y), _p(alpha), c_a, _p(skip_x), _p(skip),
-                                    _p(gate), T, _p(dh), int(accum_dh), _p(dy), _p(dy_lo), _p(dskip_x), _p(part), _p(pskip),
-                                    nblk, M, Cc, _s()), "nvit_lerp_bwd")
+    call("nvit_lerp_bwd", dt, dout, dout_add, h, y, dt_of(y), alpha, c_a, skip_x, skip, gate, T, dh, int(accum_dh), dy,
+         dy_lo, dskip_x, part, pskip, nblk, M, Cc, _s())
     return dh, dy, dy_lo, dskip_x, part, pskip
 
 
@@ -315,7 +308,7 @@ def rmsnorm_fwd(x: Tensor, w: Tensor, eps: float):
     M, Cc = x.shape
     out = torch.empty_like(x)
     rstd = torch.empty((M,), device=x.device, dtype=torch.float32)
-    check(_lib.load().nvit_rmsnorm_fwd(_p(x), _p(w), eps, _p(out), _p(rstd), M, Cc, _s()), "nvit_rmsnorm_fwd")
+    call("nvit_rmsnorm_fwd", x, w, eps, out, rstd, M, Cc, _s())
     return out, rstd
 
 
@@ -325,8 +318,7 @@ def rmsnorm_bwd(dout: Tensor, x: Tensor, w: Tensor, rstd: Tensor, *, nblk: Optio
     nblk = _part_blocks(nblk, _row_part_blocks(M), "rmsnorm_bwd")
     dx = torch.empty_like(x)
     part = torch.empty((nblk, Cc), device=x.device, dtype=torch.float32)
-    check(_lib.load().nvit_rmsnorm_bwd(_p(dout), _p(x), _p(w), _p(rstd), _p(dx), _p(part), nblk, M, Cc, _s()),
-          "nvit_rmsnorm_bwd")
+    call("nvit_rmsnorm_bwd", dout, x, w, rstd, dx, part, nblk, M, Cc, _s())
     dw = torch.empty((Cc,), device=x.device, dtype=torch.float32)
     colsum_reduce(part, dw, False)
     return dx, dw
@@ -371,8 +363,8 @@ def res_rmsnorm_fwd(dt: int, a: Tensor, y: Optional[Tensor], w: Tensor, eps: flo
     if gate is not None and y is None:
         raise ValueError("res_rmsnorm_fwd: a gate needs the branch output y")
     T = _chk_gate(gate, M, a, "res_rmsnorm_fwd")
-    check(_lib.load().nvit_res_rmsnorm_fwd(dt, _p(a), _p(y), dt_of(y) if y is not None else F32, _p(w), eps, _p(gate), T,
-                                           _p(out), _p(out_lo), _p(rstd), M, Cc, _s()), "nvit_res_rmsnorm_fwd")
+    call("nvit_res_rmsnorm_fwd", dt, a, y, dt_of(y) if y is not None else F32, w, eps, gate, T, out, out_lo, rstd, M, Cc,
+         _s())
     return out, out_lo, rstd
 
 
@@ -397,9 +389,8 @@ def res_rmsnorm_bwd(dt: int, g: Tensor, a: Tensor, y: Optional[Tensor], w: Tenso
     if gate is not None and (y is None or g_add is None):
         raise ValueError("res_rmsnorm_bwd: the gated kernel needs the branch output y and the addend g_add")
     T = _chk_gate(gate, M, a, "res_rmsnorm_bwd")
-    check(_lib.load().nvit_res_rmsnorm_bwd(dt, _p(g), _p(g_add), _p(a), _p(y), dt_of(y) if y is not None else F32, _p(w),
-                                           _p(rstd), _p(gate), T, _p(dz), int(accum), _p(dz_lo), _p(part), nblk, M, Cc,
-                                           _s()), "nvit_res_rmsnorm_bwd")
+    call("nvit_res_rmsnorm_bwd", dt, g, g_add, a, y, dt_of(y) if y is not None else F32, w, rstd, gate, T, dz, int(accum),
+         dz_lo, part, nblk, M, Cc, _s())
     return dz, dz_lo, part
 
 
@@ -413,8 +404,7 @@ def res_skip_fwd(dt: int, h: Tensor, y: Tensor, skip: Tensor, x: Tensor, want_lo
     out = torch.empty_like(h)
     out_lo = torch.empty((M, Cc), device=h.device, dtype=tdtype(dt)) if want_lo else None
     T = _chk_gate(gate, M, h, "res_skip_fwd")
-    check(_lib.load().nvit_res_skip_fwd(dt, _p(h), _p(y), dt_of(y), _p(skip), _p(x), _p(gate), T, _p(out), _p(out_lo), M, Cc,
-                                        _s()), "nvit_res_skip_fwd")
+    call("nvit_res_skip_fwd", dt, h, y, dt_of(y), skip, x, gate, T, out, out_lo, M, Cc, _s())
     return out, out_lo
 
 
@@ -431,8 +421,7 @@ def res_skip_bwd(dt: int, dout: Tensor, h: Tensor, y: Tensor, skip: Tensor, x: T
     dh_lo = torch.empty((M, Cc), device=h.device, dtype=tdtype(dt)) if want_lo else None
     part = torch.empty((ROW_WAVES * nblk,), device=h.device, dtype=torch.float32)
     T = _chk_gate(gate, M, h, "res_skip_bwd")
-    check(_lib.load().nvit_res_skip_bwd(dt, _p(dout), _p(h), _p(y), dt_of(y), _p(skip), _p(x), _p(gate), T, _p(dh), _p(dh_lo),
-                                        _p(dx), _p(part), nblk, M, Cc, _s()), "nvit_res_skip_bwd")
+    call("nvit_res_skip_bwd", dt, dout, h, y, dt_of(y), skip, x, gate, T, dh, dh_lo, dx, part, nblk, M, Cc, _s())
     return dh, dh_lo, dx, part
 
 
@@ -440,7 +429,7 @@ def norm_skip_fwd(src: Tensor, tgt: Optional[Tensor], skip: Tensor) -> Tensor:
     """nrm(src*skip + tgt); tgt None = justnorm(src*skip)."""
     M, Cc = src.shape
     out = torch.empty_like(src)
-    check(_lib.load().nvit_norm_skip_fwd(_p(src), _p(tgt), _p(skip), _p(out), M, Cc, _s()), "nvit_norm_skip_fwd")
+    call("nvit_norm_skip_fwd", src, tgt, skip, out, M, Cc, _s())
     return out
 
 
@@ -450,8 +439,7 @@ def norm_skip_bwd(dout: Tensor, src: Tensor, tgt: Optional[Tensor], skip: Tensor
     dsrc = torch.empty_like(src)
     dtgt = torch.empty_like(src) if tgt is not None else None
     part = torch.empty((nblk,), device=src.device, dtype=torch.float32)
-    check(_lib.load().nvit_norm_skip_bwd(_p(dout), _p(src), _p(tgt), _p(skip), _p(dsrc), _p(dtgt), _p(part), nblk, M,
-                                         Cc, _s()), "nvit_norm_skip_bwd")
+    call("nvit_norm_skip_bwd", dout, src, tgt, skip, dsrc, dtgt, part, nblk, M, Cc, _s())
     dskip = torch.empty_like(skip)
     colsum_reduce(part, dskip, False)
     return dsrc, dtgt, dskip
@@ -475,8 +463,7 @@ def _heads_split(name: str, dp: int, dt: int, q, ldq, k, ldk, v, ldv, sqk, c_q, 
     o = tuple(out) if out is not None else (None,) * 5
     qh, kh, vh = (_pad_out(o[i], (B, H, T, dp), td, dev, name) for i in range(3))
     rq, rk = (_pad_out(o[i], (B * T, H), torch.float32, dev, name) for i in (3, 4)) if sqk is not None else (None, None)
-    check(getattr(_lib.load(), "nvit_" + name)(dt, _p(q), ldq, _p(k), ldk, _p(v), ldv, _p(sqk), c_q, _p(qh), _p(kh), _p(vh),
-                                               _p(rq), _p(rk), *mid, B, T, H, d, *post, _s()), "nvit_" + name)
+    call("nvit_" + name, dt, q, ldq, k, ldk, v, ldv, sqk, c_q, qh, kh, vh, rq, rk, *mid, B, T, H, d, *post, _s())
     return qh, kh, vh, rq, rk
 
 
@@ -486,9 +473,8 @@ def _heads_merge(name: str, dt: int, dqh, dkh, dvh, qh, kh, rq, rk, sqk, c_q, dq
     [nblk, H*d] (out: optional buffer), or None for the head merge alone (sqk None).  post: what it takes behind d."""
     nblk = _part_blocks(nblk, _row_part_blocks(B * T), name)
     part = _pad_out(out, (nblk, H * d), torch.float32, dq.device, name) if sqk is not None else None
-    check(getattr(_lib.load(), "nvit_" + name)(dt, _p(dqh), _p(dkh), _p(dvh), _p(qh), _p(kh), _p(rq), _p(rk), _p(sqk), c_q,
-                                               _p(dq), ldq, _p(dk), ldk, _p(dv), ldv, _p(part), nblk, B, T, H, d, *post,
-                                               _s()), "nvit_" + name)
+    call("nvit_" + name, dt, dqh, dkh, dvh, qh, kh, rq, rk, sqk, c_q, dq, ldq, dk, ldk, dv, ldv, part, nblk, B, T, H, d,
+         *post, _s())
     return part
 
 
@@ -516,7 +502,7 @@ def heads_pad_fwd(dt: int, q: Tensor, ldq: int, k: Tensor, ldk: int, v: Tensor, 
     dp = PAD_HEAD_DIM
     o = tuple(out) if out is not None else (None,) * 6
     sqk_pad = _pad_out(o[5], (H * dp,), torch.float32, q.device, "heads_pad_fwd") if sqk is not None else None
-    return (*_heads_split("heads_pad_fwd", dp, dt, q, ldq, k, ldk, v, ldv, sqk, c_q, B, T, H, d, o, (_p(sqk_pad),), (dp,)),
+    return (*_heads_split("heads_pad_fwd", dp, dt, q, ldq, k, ldk, v, ldv, sqk, c_q, B, T, H, d, o, (sqk_pad,), (dp,)),
             sqk_pad)
 
 
@@ -537,7 +523,7 @@ def pad_cols(src: Tensor, M: int, H: int, d: int, *, out: Optional[Tensor] = Non
     if tuple(src.shape) != (M, H * d) or not src.is_contiguous():
         raise ValueError(f"pad_cols: src must be a contiguous [{M}, {H * d}] tensor, got {tuple(src.shape)}")
     dst = _pad_out(out, (M, H * PAD_HEAD_DIM), src.dtype, src.device, "pad_cols")
-    check(_lib.load().nvit_pad_cols(dt_of(src), _p(src), _p(dst), M, H, d, PAD_HEAD_DIM, _s()), "nvit_pad_cols")
+    call("nvit_pad_cols", dt_of(src), src, dst, M, H, d, PAD_HEAD_DIM, _s())
     return dst
 
 
@@ -547,14 +533,14 @@ def unpad_cols(src: Tensor, M: int, H: int, d: int, *, out: Optional[Tensor] = N
     if tuple(src.shape) != (M, H * PAD_HEAD_DIM) or not src.is_contiguous():
         raise ValueError(f"unpad_cols: src must be a contiguous [{M}, {H * PAD_HEAD_DIM}] tensor, got {tuple(src.shape)}")
     dst = _pad_out(out, (M, H * d), src.dtype, src.device, "unpad_cols")
-    check(_lib.load().nvit_unpad_cols(dt_of(src), _p(src), _p(dst), M, H, d, PAD_HEAD_DIM, _s()), "nvit_unpad_cols")
+    call("nvit_unpad_cols", dt_of(src), src, dst, M, H, d, PAD_HEAD_DIM, _s())
     return dst
 
 
 def swiglu_fwd(dt: int, uv: Tensor, suv: Optional[Tensor], gscale: float, M: int, F: int) -> Tensor:
     """dt = BF16_F32IN: fp32 pre-activations in, bf16 gated output."""
     x = torch.empty((M, F), device=uv.device, dtype=tdtype(BF16 if dt == _lib.BF16_F32IN else dt))
-    check(_lib.load().nvit_swiglu_fwd(dt, _p(uv), _p(suv), gscale, _p(x), M, F, _s()), "nvit_swiglu_fwd")
+    call("nvit_swiglu_fwd", dt, uv, suv, gscale, x, M, F, _s())
     return x
 
 
@@ -565,16 +551,14 @@ def swiglu_bwd(dt: int, dx: Tensor, uv: Tensor, suv: Optional[Tensor], gscale: f
     rpb = math.ceil(M / rowblocks)
     nrb = math.ceil(M / rpb)
     part = torch.empty((nrb, 2 * F), device=uv.device, dtype=torch.float32) if suv is not None else None
-    check(_lib.load().nvit_swiglu_bwd(dt, _p(dx), _p(uv), _p(suv), gscale, _p(duv), _p(part), rpb, M, F, _s()),
-          "nvit_swiglu_bwd")
+    call("nvit_swiglu_bwd", dt, dx, uv, suv, gscale, duv, part, rpb, M, F, _s())
     return duv, part
 
 
 def colsum_reduce(part: Tensor, out: Tensor, accumulate: bool, kind: int = 0, ref: Optional[Tensor] = None,
                   scale: float = 1.0) -> None:
     nblk, N = part.shape if part.dim() == 2 else (part.shape[0], 1)
-    check(_lib.load().nvit_colsum_reduce(_p(part), nblk, N, _p(out), int(accumulate), kind, _p(ref), scale, _s()),
-          "nvit_colsum_reduce")
+    call("nvit_colsum_reduce", part, nblk, N, out, int(accumulate), kind, ref, scale, _s())
 
 
 class ReduceBatch:
@@ -603,22 +587,20 @@ class ReduceBatch:
         I64, I32, F32_ = C.c_int64 * n, C.c_int * n, C.c_float * n
         rows = lambda t: t.shape[0]
         cols = lambda t: t.shape[1] if t.dim() == 2 else 1
-        check(_lib.load().nvit_colsum_reduce_multi(
-            I64(*[it[0].data_ptr() for it in items]), I32(*[rows(it[0]) for it in items]),
-            I64(*[(it[6].data_ptr() if it[6] is not None else 0) for it in items]),
-            I32(*[(rows(it[6]) if it[6] is not None else 0) for it in items]),
-            I32(*[cols(it[0]) for it in items]), I64(*[it[1].data_ptr() for it in items]),
-            I32(*[int(it[2]) for it in items]), I32(*[it[3] for it in items]),
-            I64(*[(it[4].data_ptr() if it[4] is not None else 0) for it in items]), F32_(*[float(it[5]) for it in items]),
-            n, _s()), "nvit_colsum_reduce_multi")
+        call("nvit_colsum_reduce_multi", I64(*[it[0].data_ptr() for it in items]), I32(*[rows(it[0]) for it in items]),
+             I64(*[(it[6].data_ptr() if it[6] is not None else 0) for it in items]),
+             I32(*[(rows(it[6]) if it[6] is not None else 0) for it in items]), I32(*[cols(it[0]) for it in items]),
+             I64(*[it[1].data_ptr() for it in items]), I32(*[int(it[2]) for it in items]), I32(*[it[3] for it in items]),
+             I64(*[(it[4].data_ptr() if it[4] is not None else 0) for it in items]), F32_(*[float(it[5]) for it in items]),
+             n, _s())
 
 
 def colsum(a: Tensor, R: int, N: int, out: Tensor, accumulate: bool, b: Optional[Tensor] = None, period: int = 0,
            scale: float = 1.0, lda: Optional[int] = None, ldb: Optional[int] = None) -> None:
     lda = a.stride(0) if lda is None else lda
     ldb = (b.stride(0) if ldb is None else ldb) if b is not None else 0
-    check(_lib.load().nvit_colsum(_p(a), dt_of(a), lda, _p(b), dt_of(b) if b is not None else F32, ldb, R, N,
-                                  period, _p(out), int(accumulate), scale, _s()), "nvit_colsum")
+    call("nvit_colsum", a, dt_of(a), lda, b, dt_of(b) if b is not None else F32, ldb, R, N, period, out, int(accumulate),
+         scale, _s())
 
 
 def colsum_big(a: Tensor, R: int, N: int, out: Tensor, accumulate: bool, lda: Optional[int] = None) -> None:
@@ -633,7 +615,7 @@ def colsum_big(a: Tensor, R: int, N: int, out: Tensor, accumulate: bool, lda: Op
 
 def cast(src: Tensor, dt: int) -> Tensor:
     dst = torch.empty(src.shape, device=src.device, dtype=tdtype(dt))
-    check(_lib.load().nvit_cast(_p(src), _p(dst), dt, src.numel(), _s()), "nvit_cast")
+    call("nvit_cast", src, dst, dt, src.numel(), _s())
     return dst
 
 
@@ -671,8 +653,7 @@ def rows_gather(src0: Tensor, src1: Optional[Tensor], keep: Tensor, B: int, T: i
     dst1 = torch.empty_like(dst0) if src1 is not None else None
     lo0 = torch.empty((B * K, Cc), device=dev, dtype=torch.bfloat16) if lo_dt is not None else None
     lo1 = torch.empty_like(lo0) if lo_dt is not None and src1 is not None else None
-    check(_lib.load().nvit_rows_gather(_p(src0), _p(src1), _p(keep), _p(dst0), _p(dst1), _p(lo0), _p(lo1),
-                                       BF16 if lo_dt is not None else 0, B, T, K, Cc, _s()), "nvit_rows_gather")
+    call("nvit_rows_gather", src0, src1, keep, dst0, dst1, lo0, lo1, BF16 if lo_dt is not None else 0, B, T, K, Cc, _s())
     return dst0, dst1, lo0, lo1
 
 
@@ -688,11 +669,11 @@ def rows_scatter(d0: Tensor, d1: Optional[Tensor], slot: Tensor, B: int, K: int)
     Cc = _chk_token_rows("rows_scatter", slot, "slot", B, T, K, d0, d1)
     g0 = torch.empty((B * T, Cc), device=d0.device, dtype=torch.float32)
     g1 = torch.empty_like(g0) if d1 is not None else None
-    check(_lib.load().nvit_rows_scatter(_p(d0), _p(d1), _p(slot), _p(g0), _p(g1), B, T, K, Cc, _s()), "nvit_rows_scatter")
+    call("nvit_rows_scatter", d0, d1, slot, g0, g1, B, T, K, Cc, _s())
     return g0, g1
 
 
-def _pos_resample(name: str, fn, s0: Tensor, s1: Optional[Tensor], n_src: int, n_dst: int, g: int, g2: int, table: Tensor):
+def _pos_resample(name: str, s0: Tensor, s1: Optional[Tensor], n_src: int, n_dst: int, g: int, g2: int, table: Tensor):
     """Operands of pos_resample_fwd / bwd: fp32 [n_src^2, C] tables, C a multiple of 4 up to MAX_EMBD, and the packed tap
     table int32 [n_dst, 2 + MAX_TAPS] on their device.  One launch for both tables."""
     if not isinstance(s0, Tensor) or s0.dim() != 2 or s0.shape[1] % 4 or not 0 < s0.shape[1] <= _lib.MAX_EMBD:
@@ -705,7 +686,7 @@ def _pos_resample(name: str, fn, s0: Tensor, s1: Optional[Tensor], n_src: int, n
         raise ValueError(f"{name}: the tap table must be a contiguous int32 [{n_dst}, {resample.ROW}] tensor on {s0.device}")
     d0 = torch.empty((n_dst * n_dst, s0.shape[1]), device=s0.device, dtype=torch.float32)
     d1 = torch.empty_like(d0) if s1 is not None else None
-    check(fn(_p(s0), _p(s1), _p(table), _p(d0), _p(d1), g, g2, s0.shape[1], _s()), "nvit_" + name)
+    call("nvit_" + name, s0, s1, table, d0, d1, g, g2, s0.shape[1], _s())
     return d0, d1
 
 
@@ -721,7 +702,7 @@ def pos_resample_fwd(p0: Tensor, p1: Optional[Tensor], g: int, g2: int):
         _chk_rows((g * g, p0.shape[1]), f32=(p0, p1), name="pos_resample_fwd")
         return p0, p1
     taps, _ = resample.tap_tables(g, g2, p0.device)
-    return _pos_resample("pos_resample_fwd", _lib.load().nvit_pos_resample_fwd, p0, p1, g, g2, g, g2, taps)
+    return _pos_resample("pos_resample_fwd", p0, p1, g, g2, g, g2, taps)
 
 
 def pos_resample_bwd(d0: Tensor, d1: Optional[Tensor], g: int, g2: int):
@@ -733,7 +714,7 @@ def pos_resample_bwd(d0: Tensor, d1: Optional[Tensor], g: int, g2: int):
         _chk_rows((g * g, d0.shape[1]), f32=(d0, d1), name="pos_resample_bwd")
         return d0, d1
     _, taps_t = resample.tap_tables(g, g2, d0.device)
-    return _pos_resample("pos_resample_bwd", _lib.load().nvit_pos_resample_bwd, d0, d1, g2, g, g, g2, taps_t)
+    return _pos_resample("pos_resample_bwd", d0, d1, g2, g, g, g2, taps_t)
 
 
 def normalize_images(x: Tensor, mean: float = 0.5, std: float = 0.5) -> Tensor:
@@ -750,7 +731,7 @@ def normalize_images(x: Tensor, mean: float = 0.5, std: float = 0.5) -> Tensor:
     else:
         raise TypeError("normalize_images: uint8 [B,H,W,C] or float32 [B,C,H,W]")
     out = torch.empty((B, Cc, H, W), device=x.device, dtype=torch.float32)
-    check(_lib.load().nvit_normalize_images(_p(x), u8, _p(out), B, Cc, H, W, mean, std, _s()), "nvit_normalize_images")
+    call("nvit_normalize_images", x, u8, out, B, Cc, H, W, mean, std, _s())
     return out
 
 
@@ -758,7 +739,7 @@ def scale_cols(a: Tensor, s: Tensor, c: float, R: int, N: int, out: Tensor, lda:
                ldo: Optional[int] = None) -> Tensor:
     lda = a.stride(0) if lda is None else lda
     ldo = out.stride(0) if ldo is None else ldo
-    check(_lib.load().nvit_scale_cols(_p(a), lda, _p(s), c, _p(out), dt_of(out), ldo, R, N, _s()), "nvit_scale_cols")
+    call("nvit_scale_cols", a, lda, s, c, out, dt_of(out), ldo, R, N, _s())
     return out
 
 
@@ -771,7 +752,7 @@ def eval_metrics(logits: Tensor, y: Tensor, acc: Tensor) -> None:
     B, N = logits.shape
     if y.numel() != B or not acc.is_contiguous():
         raise RuntimeError("eval_metrics: one label per row and a contiguous accumulator")
-    check(_lib.load().nvit_eval_metrics(_p(logits), _p(y), _p(acc), B, N, _s()), "nvit_eval_metrics")
+    call("nvit_eval_metrics", logits, y, acc, B, N, _s())
 
 
 # ----------------------------------------------------------------------------- attention
@@ -784,11 +765,9 @@ def attn_fwd(dt: int, impl: int, qh: Tensor, kh: Tensor, vh: Tensor, scale: floa
     o = torch.empty((B * Tq, H * d), device=qh.device, dtype=tdtype(dt))
     lse = torch.empty((B, H, Tq), device=qh.device, dtype=torch.float32)
     if sqk is not None or q_prescale != 1.0:
-        check(_lib.load().nvit_attn_fwd_bounded(dt, impl, _p(qh), _p(kh), _p(vh), scale, _p(sqk), c_q, q_prescale, _p(o),
-                                                _p(lse), B, H, Tq, Tk, d, _s()), "nvit_attn_fwd_bounded")
+        call("nvit_attn_fwd_bounded", dt, impl, qh, kh, vh, scale, sqk, c_q, q_prescale, o, lse, B, H, Tq, Tk, d, _s())
     else:
-        check(_lib.load().nvit_attn_fwd(dt, impl, _p(qh), _p(kh), _p(vh), scale, _p(o), _p(lse), B, H, Tq, Tk, d, _s()),
-              "nvit_attn_fwd")
+        call("nvit_attn_fwd", dt, impl, qh, kh, vh, scale, o, lse, B, H, Tq, Tk, d, _s())
     return o, lse
 
 
@@ -800,8 +779,7 @@ def attn_bwd(dt: int, impl: int, dout: Tensor, qh: Tensor, kh: Tensor, vh: Tenso
     dkh = torch.empty_like(kh)
     dvh = torch.empty_like(vh)
     delta = torch.empty((2, B, H, Tq), device=qh.device, dtype=torch.float32)   # workspace: -delta | -lse*log2(e)
-    check(_lib.load().nvit_attn_bwd(dt, impl, _p(dout), _p(qh), _p(kh), _p(vh), _p(o), _p(lse), scale, _p(dqh),
-                                    _p(dkh), _p(dvh), _p(delta), B, H, Tq, Tk, d, _s()), "nvit_attn_bwd")
+    call("nvit_attn_bwd", dt, impl, dout, qh, kh, vh, o, lse, scale, dqh, dkh, dvh, delta, B, H, Tq, Tk, d, _s())
     return dqh, dkh, dvh
 
 
@@ -820,9 +798,8 @@ def attn_bwd_qknorm(dout: Tensor, qh: Tensor, kh: Tensor, vh: Tensor, o: Tensor,
         part_q = torch.empty((B * math.ceil(Tq / ATTN_BWD_PART_ROWS), H * d), device=dev, dtype=torch.float32)
         part_k = torch.empty((B * math.ceil(Tk / ATTN_BWD_PART_ROWS), H * d), device=dev, dtype=torch.float32)
     delta = torch.empty((2, B, H, Tq), device=dev, dtype=torch.float32)   # workspace: -delta | -lse*log2(e)
-    check(_lib.load().nvit_attn_bwd_qknorm(BF16, _p(dout), _p(qh), _p(kh), _p(vh), _p(o), _p(lse), scale, _p(rq),
-                                           _p(rk), _p(sqk), c_q, q_prescale, _p(dq), ldq, _p(dk), _p(dv), ldkv, _p(part_q),
-                                           _p(part_k), _p(delta), B, H, Tq, Tk, d, _s()), "nvit_attn_bwd_qknorm")
+    call("nvit_attn_bwd_qknorm", BF16, dout, qh, kh, vh, o, lse, scale, rq, rk, sqk, c_q, q_prescale, dq, ldq, dk, dv, ldkv,
+         part_q, part_k, delta, B, H, Tq, Tk, d, _s())
     return part_q, part_k
 
 
@@ -833,8 +810,7 @@ def attn_heads_fwd(dt: int, q: Tensor, ldq: int, k: Tensor, v: Tensor, ldkv: int
     _chk_dev(q, k, v)
     o = torch.empty((M, H * d), device=q.device, dtype=tdtype(dt))
     lse = torch.empty((M, H), device=q.device, dtype=torch.float32)
-    check(_lib.load().nvit_attn_heads_fwd(dt, _p(q), ldq, _p(k), _p(v), ldkv, _p(sqk), c_q, scale, _p(o), _p(lse), M, H, d,
-                                          _s()), "nvit_attn_heads_fwd")
+    call("nvit_attn_heads_fwd", dt, q, ldq, k, v, ldkv, sqk, c_q, scale, o, lse, M, H, d, _s())
     return o, lse
 
 
@@ -850,9 +826,8 @@ def attn_heads_bwd(dt: int, dout: Tensor, q: Tensor, ldq: int, k: Tensor, v: Ten
     _chk_dev(dout, q, k, v, lse, dq, dk, dv)
     nblk = max(1, min(ATTN_HEADS_BWD_BLOCKS, M))
     part = torch.empty((nblk, H * d), device=q.device, dtype=torch.float32) if sqk is not None else None
-    check(_lib.load().nvit_attn_heads_bwd(dt, _p(dout), _p(q), ldq, _p(k), _p(v), ldkv, _p(sqk), c_q, scale, _p(lse),
-                                          _p(dq), lddq, _p(dk), _p(dv), lddkv, _p(part), nblk, M, H, d, _s()),
-          "nvit_attn_heads_bwd")
+    call("nvit_attn_heads_bwd", dt, dout, q, ldq, k, v, ldkv, sqk, c_q, scale, lse, dq, lddq, dk, dv, lddkv, part, nblk, M,
+         H, d, _s())
     return part
 
 
@@ -863,7 +838,7 @@ def im2col(dt: int, img: Tensor, Pl: int, Pg: int):
     td = tdtype(dt)
     A_l = torch.empty((B * T, ch * Pl * Pl), device=img.device, dtype=td)
     A_g = torch.empty((B * T, ch * Pg * Pg), device=img.device, dtype=td)
-    check(_lib.load().nvit_im2col(dt, _p(img), _p(A_l), _p(A_g), B, ch, S, Pl, Pg, _s()), "nvit_im2col")
+    call("nvit_im2col", dt, img, A_l, A_g, B, ch, S, Pl, Pg, _s())
     return A_l, A_g
 
 
@@ -895,9 +870,8 @@ def patch_embed_fwd(img: Tensor, w_l: Tensor, b_l: Optional[Tensor], pos_l: Tens
     if twins:
         lo_l = torch.empty((M, Cc), device=dev, dtype=torch.bfloat16)
         lo_g = torch.empty((M, Cc), device=dev, dtype=torch.bfloat16)
-    check(_lib.load().nvit_patch_embed_fwd(_p(img), _p(w_l), _p(b_l), _p(pos_l), _p(loc), _p(lo_l), _p(a_l), _p(w_g),
-                                           _p(b_g), _p(pos_g), _p(glo), _p(lo_g), _p(a_g), B, ch, S, Pl, Pg, Cc, _s()),
-          "nvit_patch_embed_fwd")
+    call("nvit_patch_embed_fwd", img, w_l, b_l, pos_l, loc, lo_l, a_l, w_g, b_g, pos_g, glo, lo_g, a_g, B, ch, S, Pl, Pg, Cc,
+         _s())
     return loc, glo, a_l, a_g, lo_l, lo_g
 
 
@@ -909,16 +883,14 @@ def pool_ln_fwd(dt: int, x: Tensor, w: Tensor, b: Tensor, eps: float, B: int, T:
     ln_lo = torch.empty((B, Cc), device=dev, dtype=tdtype(dt))
     stats = torch.empty((B, 2), device=dev, dtype=torch.float32)
     ws = torch.empty((B, nchunk, Cc), device=dev, dtype=torch.float32)
-    check(_lib.load().nvit_pool_ln_fwd(dt, _p(x), _p(w), _p(b), eps, _p(pooled), _p(ln), _p(ln_lo), _p(stats), _p(ws),
-                                       nchunk, B, T, Cc, _s()), "nvit_pool_ln_fwd")
+    call("nvit_pool_ln_fwd", dt, x, w, b, eps, pooled, ln, ln_lo, stats, ws, nchunk, B, T, Cc, _s())
     return pooled, ln, ln_lo, stats
 
 
 def pool_ln_bwd(dln: Tensor, pooled: Tensor, w: Tensor, stats: Tensor, dw: Tensor, db: Tensor, accumulate: bool,
                 B: int, T: int, Cc: int) -> Tensor:
     dx = torch.empty((B * T, Cc), device=dln.device, dtype=torch.float32)
-    check(_lib.load().nvit_pool_ln_bwd(_p(dln), _p(pooled), _p(w), _p(stats), _p(dx), _p(dw), _p(db),
-                                       int(accumulate), B, T, Cc, _s()), "nvit_pool_ln_bwd")
+    call("nvit_pool_ln_bwd", dln, pooled, w, stats, dx, dw, db, int(accumulate), B, T, Cc, _s())
     return dx
 
 
@@ -927,8 +899,7 @@ def recon_loss(raw: Tensor, img: Tensor, P: int) -> Tensor:
     nblk = PART_BLOCKS
     part = torch.empty((nblk,), device=img.device, dtype=torch.float32)
     loss = torch.empty((1,), device=img.device, dtype=torch.float32)
-    check(_lib.load().nvit_recon_loss(_p(raw), _p(img), _p(part), nblk, _p(loss), B, ch, S, P, _s()),
-          "nvit_recon_loss")
+    call("nvit_recon_loss", raw, img, part, nblk, loss, B, ch, S, P, _s())
     return loss.reshape(())
 
 
@@ -945,14 +916,14 @@ def som_bmu(x: Tensor, nodes: Tensor) -> Tensor:
     scores = gemm_nt(xs, ns, M, N, Kp)                        # fp32 operands -> v_mfma_f32_16x16x4_f32
     nn_ws = torch.empty((N,), device=x.device, dtype=torch.float32)
     idx = torch.empty((M,), device=x.device, dtype=torch.int64)
-    check(_lib.load().nvit_som_bmu(_p(scores), _p(nodes), _p(nn_ws), M, N, Cc, _p(idx), _s()), "nvit_som_bmu")
+    call("nvit_som_bmu", scores, nodes, nn_ws, M, N, Cc, idx, _s())
     return idx
 
 
 def gather_rows(nodes: Tensor, idx: Tensor) -> Tensor:
     M, Cc = idx.numel(), nodes.shape[1]
     out = torch.empty((M, Cc), device=nodes.device, dtype=torch.float32)
-    check(_lib.load().nvit_gather_rows(_p(nodes), _p(idx), _p(out), M, Cc, _s()), "nvit_gather_rows")
+    call("nvit_gather_rows", nodes, idx, out, M, Cc, _s())
     return out
 
 
@@ -960,7 +931,7 @@ def onehot(idx: Tensor, N: int) -> Tensor:
     """fp32 [M, N] rows with a single 1 at idx[m] (N a multiple of 4)."""
     M = idx.numel()
     oh = torch.empty((M, N), device=idx.device, dtype=torch.float32)
-    check(_lib.load().nvit_onehot(_p(idx), _p(oh), M, N, _s()), "nvit_onehot")
+    call("nvit_onehot", idx, oh, M, N, _s())
     return oh
 
 
@@ -971,7 +942,7 @@ def scatter_rows(dout: Tensor, idx: Tensor, N: int) -> Tensor:
     M, Cc = dout.shape
     dn = torch.empty((N, Cc), device=dout.device, dtype=torch.float32)
     if N % 4 != 0 or Cc % 4 != 0:
-        check(_lib.load().nvit_scatter_rows(_p(dout), _p(idx), _p(dn), M, N, Cc, _s()), "nvit_scatter_rows")
+        call("nvit_scatter_rows", dout, idx, dn, M, N, Cc, _s())
         return dn
     return gemm_tn(onehot(idx, N), dout.float().contiguous(), dn, M, N, Cc)
 
@@ -991,11 +962,9 @@ def som_update(nodes: Tensor, x: Tensor, idx: Tensor, lr_alpha, sigma: float, gm
     v_ws = torch.empty((B, Cc), device=nodes.device, dtype=torch.float32)
     s_ws = torch.empty((B, gm * gn), device=nodes.device, dtype=torch.float32)
     if dev_rate:
-        check(_lib.load().nvit_som_update_dev(_p(nodes), _p(x), _p(idx), _p(lr_alpha), sigma, gm, gn, int(periodic),
-                                              _p(v_ws), _p(s_ws), B, T, Cc, _s()), "nvit_som_update_dev")
+        call("nvit_som_update_dev", nodes, x, idx, lr_alpha, sigma, gm, gn, int(periodic), v_ws, s_ws, B, T, Cc, _s())
         return
-    check(_lib.load().nvit_som_update(_p(nodes), _p(x), _p(idx), lr_alpha, sigma, gm, gn, int(periodic), _p(v_ws), _p(s_ws),
-                                      B, T, Cc, _s()), "nvit_som_update")
+    call("nvit_som_update", nodes, x, idx, lr_alpha, sigma, gm, gn, int(periodic), v_ws, s_ws, B, T, Cc, _s())
 
 
 def cos_consistency_fwd(a: Tensor, b: Tensor):
@@ -1004,16 +973,14 @@ def cos_consistency_fwd(a: Tensor, b: Tensor):
     stats = torch.empty((M, 3), device=a.device, dtype=torch.float32)
     part = torch.empty((nblk,), device=a.device, dtype=torch.float32)
     loss = torch.empty((1,), device=a.device, dtype=torch.float32)
-    check(_lib.load().nvit_cos_consistency_fwd(_p(a), _p(b), _p(stats), _p(part), nblk, _p(loss), M, Cc, _s()),
-          "nvit_cos_consistency_fwd")
+    call("nvit_cos_consistency_fwd", a, b, stats, part, nblk, loss, M, Cc, _s())
     return loss.reshape(()), stats
 
 
 def cos_consistency_bwd(a: Tensor, b: Tensor, stats: Tensor, g: Tensor):
     M, Cc = a.shape
     da, db = torch.empty_like(a), torch.empty_like(b)
-    check(_lib.load().nvit_cos_consistency_bwd(_p(a), _p(b), _p(stats), _p(g), _p(da), _p(db), M, Cc, _s()),
-          "nvit_cos_consistency_bwd")
+    call("nvit_cos_consistency_bwd", a, b, stats, g, da, db, M, Cc, _s())
     return da, db
 
 
@@ -1021,13 +988,13 @@ def huber_fwd(a: Tensor, b: Tensor) -> Tensor:
     nblk = PART_BLOCKS
     part = torch.empty((nblk,), device=a.device, dtype=torch.float32)
     loss = torch.empty((1,), device=a.device, dtype=torch.float32)
-    check(_lib.load().nvit_huber_fwd(_p(a), _p(b), _p(part), nblk, _p(loss), a.numel(), _s()), "nvit_huber_fwd")
+    call("nvit_huber_fwd", a, b, part, nblk, loss, a.numel(), _s())
     return loss.reshape(())
 
 
 def huber_bwd(a: Tensor, b: Tensor, g: Tensor):
     da, db = torch.empty_like(a), torch.empty_like(b)
-    check(_lib.load().nvit_huber_bwd(_p(a), _p(b), _p(g), _p(da), _p(db), a.numel(), _s()), "nvit_huber_bwd")
+    call("nvit_huber_bwd", a, b, g, da, db, a.numel(), _s())
     return da, db
 
 
@@ -1036,23 +1003,21 @@ def som_smooth_fwd(nodes: Tensor, idx: Tensor, map_size: int):
     cnt = torch.empty((Nn,), device=nodes.device, dtype=torch.int32)
     D = torch.empty((Nn, 8), device=nodes.device, dtype=torch.float32)
     loss = torch.empty((1,), device=nodes.device, dtype=torch.float32)
-    check(_lib.load().nvit_som_smooth_fwd(_p(nodes), _p(idx), _p(cnt), _p(D), _p(loss), idx.numel(), Nn, Cc, map_size,
-                                          _s()), "nvit_som_smooth_fwd")
+    call("nvit_som_smooth_fwd", nodes, idx, cnt, D, loss, idx.numel(), Nn, Cc, map_size, _s())
     return loss.reshape(()), cnt, D
 
 
 def som_smooth_bwd(nodes: Tensor, D: Tensor, cnt: Tensor, g: Tensor, M: int, map_size: int) -> Tensor:
     Nn, Cc = nodes.shape
     dn = torch.empty_like(nodes)
-    check(_lib.load().nvit_som_smooth_bwd(_p(nodes), _p(D), _p(cnt), _p(g), _p(dn), 0, M, Nn, Cc, map_size, _s()),
-          "nvit_som_smooth_bwd")
+    call("nvit_som_smooth_bwd", nodes, D, cnt, g, dn, 0, M, Nn, Cc, map_size, _s())
     return dn
 
 
 def recon_bwd(dt: int, raw: Tensor, img: Tensor, g: Tensor, P: int) -> Tensor:
     B, ch, S, _ = img.shape
     draw = torch.empty(raw.shape, device=raw.device, dtype=tdtype(dt))
-    check(_lib.load().nvit_recon_bwd(dt, _p(raw), _p(img), _p(g), _p(draw), B, ch, S, P, _s()), "nvit_recon_bwd")
+    call("nvit_recon_bwd", dt, raw, img, g, draw, B, ch, S, P, _s())
     return draw
 
 
@@ -1077,7 +1042,7 @@ def renorm_table(mats, device) -> Tuple[Tensor, int]:
 
 
 def renorm_weights(table: Tensor, total_items: int) -> None:
-    check(_lib.load().nvit_renorm_weights(_p(table), table.shape[0], total_items, _s()), "nvit_renorm_weights")
+    call("nvit_renorm_weights", table, table.shape[0], total_items, _s())
 
 
 def lr_schedule(table: Optional[Tensor], n: int, lr_scale: Optional[Tensor], step: Tensor, kind: int, lr: float,
@@ -1094,9 +1059,8 @@ def lr_schedule(table: Optional[Tensor], n: int, lr_scale: Optional[Tensor], ste
             raise ValueError("lr_schedule: table must be contiguous int64 [n, cols] and lr_scale contiguous fp32 [n]")
         if table.device != step.device or lr_scale.device != step.device:
             raise RuntimeError("lr_schedule: the table lives on another device than the schedule")
-    check(_lib.load().nvit_lr_schedule(_p(table) if n else None, n, _p(lr_scale) if n else None, _p(step), kind, lr, min_lr,
-                                       warmup_init, warmup_iters, decay_iters, _p(last_lr), _p(last_lr64), _s()),
-          "nvit_lr_schedule")
+    call("nvit_lr_schedule", table if n else None, n, lr_scale if n else None, step, kind, lr, min_lr, warmup_init,
+         warmup_iters, decay_iters, last_lr, last_lr64, _s())
 
 
 def shadow_table(entries, device) -> Tuple[Tensor, int]:
@@ -1114,7 +1078,7 @@ def shadow_table(entries, device) -> Tuple[Tensor, int]:
 
 
 def shadow_weights(table: Tensor, total_items: int, dt: int) -> None:
-    check(_lib.load().nvit_shadow_weights(_p(table), table.shape[0], total_items, dt, _s()), "nvit_shadow_weights")
+    call("nvit_shadow_weights", table, table.shape[0], total_items, dt, _s())
 
 
 # ----------------------------------------------------------------------------- weight EMA
@@ -1170,14 +1134,14 @@ def ema_tick(state: Tensor, decay: float, warmup: bool, skip_state: Optional[Ten
     _chk_dev(state, skip_state)
     if state.dtype != torch.float32 or state.numel() < 4 or not state.is_contiguous():
         raise RuntimeError("ema_tick: state must be a contiguous fp32 tensor of 4 elements")
-    check(_lib.load().nvit_ema_tick(_p(state), float(decay), int(bool(warmup)), _p(skip_state), _s()), "nvit_ema_tick")
+    call("nvit_ema_tick", state, float(decay), int(bool(warmup)), skip_state, _s())
 
 
 def ema_update(table: Tensor, total_chunks: int, state: Optional[Tensor] = None) -> None:
     """dst = fma(omd, src - dst, dst) over the table's rows with omd = state[1] (nothing is touched when it is 0); copy
     rows store src.  state=None: only the copy rows run."""
     _chk_dev(table, state)
-    check(_lib.load().nvit_ema_update(_p(table), table.shape[0], total_chunks, _p(state), _s()), "nvit_ema_update")
+    call("nvit_ema_update", table, table.shape[0], total_chunks, state, _s())
 
 
 # ----------------------------------------------------------------------------- profiling
@@ -1199,5 +1163,5 @@ def prof_collect():
     fl = (C.c_double * n)()
     by = (C.c_double * n)()
     ln = (C.c_int64 * n)()
-    check(_lib.load().nvit_prof_collect(ms, fl, by, ln), "nvit_prof_collect")
+    call("nvit_prof_collect", ms, fl, by, ln)
     return {_lib.KID_NAMES[i]: {"ms": ms[i], "flops": fl[i], "bytes": by[i], "launches": ln[i]} for i in range(n)}

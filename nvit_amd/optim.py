@@ -30,7 +30,8 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from . import _lib
-from .ops import _p, _s, check
+from ._lib import call
+from .ops import _s
 
 _TABLE_COLS = _lib.const("OPT_TABLE_COLS")  # the item geometry of nvit_grad_sqnorm / nvit_adamw_renorm (nvit_hip.h):
 _CHUNK = _lib.const("OPT_CHUNK")
@@ -219,7 +220,6 @@ class FusedAdamW(torch.optim.AdamW):
         if c is None:
             return None
         b1, b2, eps = c["betas_eps"]
-        lib = _lib.load()
         dev = c["table"].device
         if self._hyper is None:
             self._t = self._loaded_step()
@@ -236,27 +236,20 @@ class FusedAdamW(torch.optim.AdamW):
             skip = self.skip_state
             self._guarded = True
             self._t += 1   # as if applied; state_dict() reads the count of applied steps back from the device
-            check(lib.nvit_grad_sqnorm(_p(c["table"]), c["n"], c["chunks"], _p(c["partial"]), _NPART, _s()),
-                  "nvit_grad_sqnorm")
-            check(lib.nvit_adamw_tick_guarded(_p(self._hyper), b1, b2, _p(c["partial"]), _NPART, _p(skip), _s()),
-                  "nvit_adamw_tick_guarded")
-            check(lib.nvit_adamw_renorm_guarded(_p(c["table"]), c["n"], c["items"], c["slab"], b1, b2, eps,
-                                                _p(c["partial"]), _NPART, float(grad_clip) if clip else 0.0,
-                                                _p(c["gnorm"]), _p(self._hyper), _p(skip), _s()),
-                  "nvit_adamw_renorm_guarded")
+            call("nvit_grad_sqnorm", c["table"], c["n"], c["chunks"], c["partial"], _NPART, _s())
+            call("nvit_adamw_tick_guarded", self._hyper, b1, b2, c["partial"], _NPART, skip, _s())
+            call("nvit_adamw_renorm_guarded", c["table"], c["n"], c["items"], c["slab"], b1, b2, eps, c["partial"], _NPART,
+                 float(grad_clip) if clip else 0.0, c["gnorm"], self._hyper, skip, _s())
             if self._ema is not None:
                 self._ema.update(skip)   # the tick reads the decision just taken: a step left out is no update
             return c["gnorm"]
-        check(lib.nvit_adamw_tick(_p(self._hyper), b1, b2, _s()), "nvit_adamw_tick")
+        call("nvit_adamw_tick", self._hyper, b1, b2, _s())
         self._t += 1
         if clip:
-            check(lib.nvit_grad_sqnorm(_p(c["table"]), c["n"], c["chunks"], _p(c["partial"]), _NPART, _s()),
-                  "nvit_grad_sqnorm")
-        check(lib.nvit_adamw_renorm(_p(c["table"]), c["n"], c["items"], c["slab"], b1, b2, eps, 0.0, 0.0,
-                                    _p(c["partial"]) if clip else None, _NPART if clip else 0,
-                                    float(grad_clip) if clip else 0.0, _p(c["gnorm"]) if clip else None,
-                                    _p(self._hyper), _s()),
-              "nvit_adamw_renorm")
+            call("nvit_grad_sqnorm", c["table"], c["n"], c["chunks"], c["partial"], _NPART, _s())
+        call("nvit_adamw_renorm", c["table"], c["n"], c["items"], c["slab"], b1, b2, eps, 0.0, 0.0,
+             c["partial"] if clip else None, _NPART if clip else 0, float(grad_clip) if clip else 0.0,
+             c["gnorm"] if clip else None, self._hyper, _s())
         if self._ema is not None:
             self._ema.update()
         return c["gnorm"] if clip else None

@@ -116,8 +116,8 @@ class DataParallel(nn.Module):
         # parallelism (NVIT_GEMM_SCHED=s keeps the static deal; the single-process default stays static).
         self.gemm_sched = os.environ.get("NVIT_GEMM_SCHED", "d" if self.world > 1 else "s")
         if next(module.parameters()).is_cuda:
-            from . import _lib
-            _lib.load().nvit_set_gemm_sched(1 if self.gemm_sched[:1] in ("d", "1") else 0)
+            from ._lib import call
+            call("nvit_set_gemm_sched", 1 if self.gemm_sched[:1] in ("d", "1") else 0)
 
     def forward(self, *args, **kwargs):
         return self.module(*args, **kwargs)

@@ -15,9 +15,9 @@ from typing import Tuple
 import torch
 
 from . import _lib
-from ._lib import check
+from ._lib import call
 from .augment import DeviceStepCounter
-from .ops import _p, _s
+from .ops import _s
 
 Tensor = torch.Tensor
 MAX_TOKENS = _lib.const("PATCHDROP_MAX_TOKENS")
@@ -61,6 +61,5 @@ class PatchDropout(DeviceStepCounter):
         K = self.num_keep(T)
         keep = torch.empty((B, K), device=self.device, dtype=torch.int32)
         slot = torch.empty((B, T), device=self.device, dtype=torch.int32)
-        check(_lib.load().nvit_patchdrop_draw(self.seed, _p(self._step), self.first_index, _p(keep), _p(slot), B, T, K,
-                                              _s()), "nvit_patchdrop_draw")
+        call("nvit_patchdrop_draw", self.seed, self._step, self.first_index, keep, slot, B, T, K, _s())
         return keep, slot

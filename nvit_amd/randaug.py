@@ -28,11 +28,11 @@ from typing import Optional, Sequence
 import torch
 
 from . import _lib
-from ._lib import check
+from ._lib import call
 from .augment import OPS as _AA_OPS, AugmentedBatch, _apply_buffers, _f32_bits, affine_coefficients
 from .augment import _check_hw as _aa_check_hw, _check_images as _aa_check_images
 from .crop import normal_quantile_table
-from .ops import _chk_dev, _p, _s
+from .ops import _chk_dev, _s
 from .stages import DeviceStepCounter, check_finite, check_name, check_number, check_unit
 
 Tensor = torch.Tensor
@@ -274,10 +274,9 @@ class RandAugment(DeviceStepCounter):
             raise ValueError("RandAugment.draw: B must be an int >= 1")
         _check_hw(H, W)
         params = torch.empty((B, self.num_layers, ROW), device=self.device, dtype=torch.int32)
-        check(_lib.load().nvit_randaug_draw(self.seed, _p(self._step), self.first_index, _p(self._q), _p(self._rot),
-                                            self.magnitude, self.magnitude_std, self.magnitude_max, int(self.increasing),
-                                            self.prob, INTERPOLATIONS[self.interpolation], self.translate_pct, _p(params), B,
-                                            self.num_layers, H, W, _s()), "nvit_randaug_draw")
+        call("nvit_randaug_draw", self.seed, self._step, self.first_index, self._q, self._rot, self.magnitude,
+             self.magnitude_std, self.magnitude_max, int(self.increasing), self.prob, INTERPOLATIONS[self.interpolation],
+             self.translate_pct, params, B, self.num_layers, H, W, _s())
         return params
 
     def apply(self, u8: Tensor, params: Tensor, return_u8: bool = False):
@@ -294,9 +293,8 @@ class RandAugment(DeviceStepCounter):
         _chk_dev(u8, params)
         u8, params = u8.contiguous(), params.contiguous()
         ws, ws_bytes, f32, o8 = _apply_buffers(u8, return_u8)
-        check(_lib.load().nvit_randaug_apply(_p(u8), _p(params), _p(f32), _p(o8), _p(ws), ws_bytes, B, H, W, C,
-                                             params.shape[1], fill[0], fill[1], fill[2], self.mean, self.std, _s()),
-              "nvit_randaug_apply")
+        call("nvit_randaug_apply", u8, params, f32, o8, ws, ws_bytes, B, H, W, C, params.shape[1], fill[0], fill[1], fill[2],
+             self.mean, self.std, _s())
         return o8 if return_u8 else f32
 
     def __call__(self, u8: Tensor) -> Tensor:

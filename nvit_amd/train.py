@@ -18,8 +18,10 @@ from contextlib import nullcontext
 import torch
 
 from . import ops
+from ._lib import call
 from .crop import CenterCroppedBatch
 from .mix import MixedTargets
+from .ops import _s
 from .optim import FusedAdamW, renorm_matrices
 from .stages import StagedBatch, chain
 
@@ -66,12 +68,10 @@ class CrossEntropyFn(torch.autograd.Function):
             if soft.y.shape[0] != B:
                 raise ValueError(f"CrossEntropyFn: {soft.y.shape[0]} targets for {B} rows of logits")
             ops._chk_dev(soft.y2, soft.lam)
-            ops.check(ops._lib.load().nvit_ce_loss_soft(ops._p(logits), ops._p(y.contiguous()), ops._p(soft.y2.contiguous()),
-                                                        ops._p(soft.lam.contiguous()), soft.smoothing, ops._p(rowloss),
-                                                        ops._p(loss), ops._p(dlogits), B, N, ops._s()), "nvit_ce_loss_soft")
+            call("nvit_ce_loss_soft", logits, y.contiguous(), soft.y2.contiguous(), soft.lam.contiguous(), soft.smoothing,
+                 rowloss, loss, dlogits, B, N, _s())
         else:
-            ops.check(ops._lib.load().nvit_ce_loss(ops._p(logits), ops._p(y.contiguous()), ops._p(rowloss), ops._p(loss),
-                                                   ops._p(dlogits), B, N, ops._s()), "nvit_ce_loss")
+            call("nvit_ce_loss", logits, y.contiguous(), rowloss, loss, dlogits, B, N, _s())
         ctx.save_for_backward(dlogits)
         return loss[0]
 

@@ -35,7 +35,8 @@ import torch
 import torch.distributed as dist
 
 from . import _lib
-from .ops import _s, check
+from ._lib import call
+from .ops import _s
 
 MAX_SLOTS = 64
 
@@ -63,13 +64,12 @@ class XgmiAllReduce:
         self.slots = slots
         self.numel = (numel + 3) // 4 * 4
         self.buffer = torch.zeros(self.numel, device=device, dtype=torch.float32)
-        lib = _lib.load()
         if timeout_s is None:
             timeout_s = float(os.environ.get("NVIT_XGMI_TIMEOUT_S", "1800"))
         self.timeout_s = float(timeout_s)
-        check(lib.nvit_xgmi_set_timeout(self.timeout_s), "nvit_xgmi_set_timeout")
+        call("nvit_xgmi_set_timeout", self.timeout_s)
         hp, dp = C.c_void_p(), C.c_void_p()
-        check(lib.nvit_xgmi_errword_alloc(C.byref(hp), C.byref(dp)), "nvit_xgmi_errword_alloc")
+        call("nvit_xgmi_errword_alloc", C.byref(hp), C.byref(dp))
         self._err_host, self._err_dev = hp.value, dp.value
         self._err_view = C.cast(self._err_host, C.POINTER(C.c_uint))
         # ---- which device is every rank on?  Ranks on different devices need peer access (xGMI / PCIe P2P).
@@ -93,7 +93,7 @@ class XgmiAllReduce:
         # ---- flag block: uncached device memory from the library, raw 64-byte IPC handle
         own = C.c_void_p()
         hbuf = (C.c_char * 64)()
-        check(lib.nvit_xgmi_flags_alloc(slots, C.byref(own), hbuf), "nvit_xgmi_flags_alloc")
+        call("nvit_xgmi_flags_alloc", slots, C.byref(own), hbuf)
         self._own_flags = own.value
         handles: List[Optional[tuple]] = [None] * self.world
         dist.all_gather_object(handles, (mine, bytes(hbuf.raw)), group=group)
@@ -110,11 +110,11 @@ class XgmiAllReduce:
                 raise RuntimeError("XgmiAllReduce: ranks disagree on the buffer size")
             self._peers.append(t)
             p = C.c_void_p()
-            check(lib.nvit_xgmi_flags_open(C.create_string_buffer(fh, 64), C.byref(p)), "nvit_xgmi_flags_open")
+            call("nvit_xgmi_flags_open", C.create_string_buffer(fh, 64), C.byref(p))
             self._flag_ptrs.append(p.value)
         self._ptrs = (C.c_int64 * self.world)(*[t.data_ptr() for t in self._peers])
         self._fptrs = (C.c_int64 * self.world)(*self._flag_ptrs)
-        self.chunk = int(lib.nvit_xgmi_chunk(self.numel, self.world))
+        self.chunk = int(_lib.load().nvit_xgmi_chunk(self.numel, self.world))
         self._epoch = [0] * slots
         self._closed = False
         self._host_barrier()   # nobody may start before every rank has opened every handle
@@ -140,15 +140,13 @@ class XgmiAllReduce:
     def reduce_scatter_(self, slot: int, epoch: int, scale: float = 1.0, off: int = 0, numel: Optional[int] = None,
                         stream=None) -> None:
         off, n = self._region(off, numel)
-        check(_lib.load().nvit_xgmi_reduce_scatter_sync(self._ptrs, self._fptrs, self.world, self.rank, self.slots, slot,
-                                                        epoch, off, n, float(scale), _s() if stream is None else stream),
-              "nvit_xgmi_reduce_scatter_sync")
+        call("nvit_xgmi_reduce_scatter_sync", self._ptrs, self._fptrs, self.world, self.rank, self.slots, slot, epoch, off,
+             n, float(scale), _s() if stream is None else stream)
 
     def all_gather_(self, slot: int, epoch: int, off: int = 0, numel: Optional[int] = None, stream=None) -> None:
         off, n = self._region(off, numel)
-        check(_lib.load().nvit_xgmi_all_gather_sync(self._ptrs, self._fptrs, self.world, self.rank, self.slots, slot, epoch,
-                                                    off, n, _s() if stream is None else stream),
-              "nvit_xgmi_all_gather_sync")
+        call("nvit_xgmi_all_gather_sync", self._ptrs, self._fptrs, self.world, self.rank, self.slots, slot, epoch, off, n,
+             _s() if stream is None else stream)
 
     def wait_gathered(self, slots: Sequence[int], stream=None) -> None:
         """Enqueue (on the current stream, or `stream`) the wait for every peer to have finished reading this rank's
@@ -160,9 +158,8 @@ class XgmiAllReduce:
         # torch follows with a stream synchronise), nothing to keep alive, capturable in a hipGraph
         h_slots = (C.c_int * len(slots))(*slots)
         h_epochs = (C.c_uint * len(slots))(*[self._epoch[s] & 0xFFFFFFFF for s in slots])
-        check(_lib.load().nvit_xgmi_wait_gathered(self._fptrs, self.world, self.rank, self.slots, h_slots, h_epochs,
-                                                  len(slots), self._err_dev, _s() if stream is None else stream),
-              "nvit_xgmi_wait_gathered")
+        call("nvit_xgmi_wait_gathered", self._fptrs, self.world, self.rank, self.slots, h_slots, h_epochs, len(slots),
+             self._err_dev, _s() if stream is None else stream)
 
     def all_reduce_(self, scale: float = 1.0, numel: Optional[int] = None, slot: int = 0, off: int = 0) -> torch.Tensor:
         """buffer[off : off + numel] <- scale * sum over ranks (bit-identical on every rank), stream-ordered on the current
@@ -191,7 +188,7 @@ class XgmiAllReduce:
     def check_error(self) -> None:
         """Synchronise the current stream and raise if any device-side wait timed out on any rank."""
         w = C.c_uint(0)
-        check(_lib.load().nvit_xgmi_flags_error(self._own_flags, self.slots, C.byref(w), _s()), "nvit_xgmi_flags_error")
+        call("nvit_xgmi_flags_error", self._own_flags, self.slots, C.byref(w), _s())
         if w.value:
             self._raise(w.value)
 
@@ -201,13 +198,12 @@ class XgmiAllReduce:
             return
         self._closed = True
         self._host_barrier()     # every rank has finished its device work on the mapped buffers
-        lib = _lib.load()
         for r, p in enumerate(self._flag_ptrs):
             if r != self.rank:
-                check(lib.nvit_xgmi_flags_close(p), "nvit_xgmi_flags_close")
+                call("nvit_xgmi_flags_close", p)
         self._peers = [self.buffer]
         self._host_barrier()     # nobody still maps this rank's flag block
-        check(lib.nvit_xgmi_flags_free(self._own_flags), "nvit_xgmi_flags_free")
+        call("nvit_xgmi_flags_free", self._own_flags)
         self._own_flags = None
-        check(lib.nvit_xgmi_errword_free(self._err_host), "nvit_xgmi_errword_free")
+        call("nvit_xgmi_errword_free", self._err_host)
         self._err_host = self._err_dev = self._err_view = None

@@ -6,12 +6,7 @@ import ctypes
 import torch
 from nvit_amd import _lib
 if os.environ.get("NVIT_LIB"):   # an older build may lack newer entry points: bind what it has
-    _l = ctypes.CDLL(os.environ["NVIT_LIB"])
-    for _n, _a in _lib.SIGNATURES.items():
-        if hasattr(_l, _n):
-            getattr(_l, _n).argtypes = _a
-            getattr(_l, _n).restype = _lib._RESTYPES.get(_n, ctypes.c_int)
-    _lib._lib = _l
+    _lib._lib = _lib.bind(ctypes.CDLL(os.environ["NVIT_LIB"]), partial=True)
 from nvit_amd import ops
 from attn_dkv_asm_ab import make, dev, t_of
 
