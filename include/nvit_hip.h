@@ -519,6 +519,26 @@ int nvit_rows_gather(const float* src0, const float* src1, const int* keep, floa
                      int lo_dt, int B, int T, int K, int C, void* stream);
 int nvit_rows_scatter(const float* d0, const float* d1, const int* slot, float* g0, float* g1, int B, int T, int K, int C,
                       void* stream);
+/* The device-resident dataset ("The device-resident dataset"; tests/loader_ref.py).  nvit_loader_draw: idx
+ * int64 [B], the images of rows [first_row, first_row + B) of the global batch at step s = *step.  With S =
+ * steps_per_epoch and G = global_batch: epoch = s / S, row i sits at position q = (s % S) * G + first_row + i and shows
+ * image perm(q / repeats), or q / repeats itself with shuffle == 0; S * G <= N * repeats, so q / repeats < N.  perm is a
+ * bijection of [0, N) per (seed, epoch): a 4-round balanced Feistel network on w bits, w the smallest even number of bits
+ * that holds N - 1 (at least 2), round j mapping (L, R) to (R, L ^ (v[0] & mask)) with v = Philox4x32-10 of counter (R,
+ * j, epoch low, epoch high) and key = seed with a domain constant xor-ed into its high word; the network is re-applied
+ * while the value is >= N.  record int64 [NVIT_LOADER_RECORD] receives {epoch, s % S}.  One workgroup: every thread reads
+ * *step, then, behind a barrier, one thread stores s + 1 (no tick launch).
+ * nvit_loader_gather: out[b, :] = images[idx[b], :], rows of row_bytes bytes, and y[b] = labels[idx[b]]; offsets are 64
+ * bits wide.  16-byte loads and stores when row_bytes % 16 == 0 and both bases are 16-byte aligned, bytes otherwise.  An
+ * index outside [0, N) reads nothing: the row becomes zeros and the label 0. */
+#define NVIT_LOADER_MAX_IMAGES 1099511627776 /* 2^40 */
+#define NVIT_LOADER_MAX_BATCH 65536
+#define NVIT_LOADER_MAX_REPEATS 1024
+#define NVIT_LOADER_RECORD 2
+int nvit_loader_draw(uint64_t seed, int64_t* step, int64_t N, int64_t steps_per_epoch, int64_t global_batch,
+                     int64_t first_row, int repeats, int shuffle, int64_t* idx, int64_t* record, int B, void* stream);
+int nvit_loader_gather(const void* images, const int64_t* labels, const int64_t* idx, void* out, int64_t* y, int64_t N,
+                       int64_t row_bytes, int B, void* stream);
 /* Resampling a position-embedding table to another token grid (timm's resample_abs_pos_embed; DESIGN.md §4;
  * nvit_amd/resample.py builds the tables).  nvit_pos_resample_fwd: pX fp32 [g*g, C] -> outX fp32 [g2*g2, C], the bicubic
  * (a = -0.5), antialiased, align_corners = false resize of the g x g grid of C-vectors: out[oy*g2 + ox, :] = sum over ty, tx

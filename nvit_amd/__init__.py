@@ -25,6 +25,9 @@ def __getattr__(name):
     if name in ("RandomResizedCrop", "CroppedBatch", "RandomErasing", "ErasedBatch", "ResizeCenterCrop", "CenterCroppedBatch"):
         from . import crop
         return getattr(crop, name)
+    if name in ("DeviceDataset", "DeviceLoader", "LoaderBatch"):
+        from . import data
+        return getattr(data, name)
     if name == "ModelEma":
         from . import ema
         return ema.ModelEma

@@ -230,9 +230,10 @@ class AugmentedBatch(StagedBatch):
     """A uint8 [B,H,W,C] batch together with the AutoAugment (or the RandAugment of randaug.py: anything whose call
     turns such a batch into fp32 [B,C,H,W]) that makes it the model's input: what `AutoAugment.batch(u8)` /
     `RandAugment.batch(u8)` return and `train_step` / `GraphedTrainStep` accept in place of X.  u8: the tensor, or a
-    `RandomResizedCrop.batch(u8)` (crop.py) whose crops are then what the policies see.  `.shape` is u8's."""
+    `RandomResizedCrop.batch(u8)` (crop.py) whose crops are then what the policies see, or a `DeviceLoader.batch()` (data.py)
+    whose gathered batch is.  `.shape` is u8's."""
 
-    key, word, accepts, names = "augment", "augmentation", ("crop",), ("augment", "u8")
+    key, word, accepts, names = "augment", "augmentation", ("crop", "data"), ("augment", "u8")
 
     def __init__(self, augment: "AutoAugment", u8):
         name = type(augment).__name__

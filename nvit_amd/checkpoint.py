@@ -46,7 +46,7 @@ def _numpy_safe_globals():
 
 def build_checkpoint(model, optimizer, iter_num: int, metrics: Dict[str, float], config: Optional[Dict[str, Any]] = None,
                      rng_state_pytorch: Optional[torch.Tensor] = None, *, ema=None, drop_path=None,
-                     patch_drop=None, rand_augment=None, lr_schedule=None) -> Dict[str, Any]:
+                     patch_drop=None, rand_augment=None, lr_schedule=None, loader=None) -> Dict[str, Any]:
     """ema: a `ModelEma`; the checkpoint then gains the key "model_ema" = ema.state_dict() (tensors and plain values, so
     the weights-only load takes it); restore with `ema.load_state_dict(ck["model_ema"])`.  drop_path: a `DropPath`; the
     key "drop_path" = drop_path.state_dict() (seed and step: the resumed run draws what the uninterrupted one would);
@@ -54,7 +54,10 @@ def build_checkpoint(model, optimizer, iter_num: int, metrics: Dict[str, float],
     patch_drop.state_dict(), likewise (seed, step).  rand_augment: a `RandAugment`; the key "rand_augment" =
     rand_augment.state_dict(), likewise (seed, step).  lr_schedule: an `LRSchedule`; the key "lr_schedule" =
     lr_schedule.state_dict() (its parameters and step: the resumed run steps at the rates the uninterrupted one would);
-    restore with `sched.load_state_dict(ck["lr_schedule"])`.  Without them the key set is the reference's."""
+    restore with `sched.load_state_dict(ck["lr_schedule"])`.  loader: a `DeviceLoader` (data.py); the key "loader" =
+    loader.state_dict() (seed, step and the parameters that fix its sequence: the resumed run sees the batches the
+    uninterrupted one would); restore with `ld.load_state_dict(ck["loader"])`.  Without them the key set is the
+    reference's."""
     m = model.module if hasattr(model, "module") else model
     ck = {
         "model": _model_state(m),
@@ -77,16 +80,19 @@ def build_checkpoint(model, optimizer, iter_num: int, metrics: Dict[str, float],
         ck["rand_augment"] = rand_augment.state_dict()
     if lr_schedule is not None:
         ck["lr_schedule"] = lr_schedule.state_dict()
+    if loader is not None:
+        ck["loader"] = loader.state_dict()
     return ck
 
 
 def save_checkpoint(path, model, optimizer, iter_num: int, metrics: Dict[str, float],
                     config: Optional[Dict[str, Any]] = None, *, ema=None, drop_path=None, patch_drop=None,
-                    rand_augment=None, lr_schedule=None) -> Path:
+                    rand_augment=None, lr_schedule=None, loader=None) -> Path:
     path = Path(path)
     path.parent.mkdir(parents=True, exist_ok=True)
     torch.save(build_checkpoint(model, optimizer, iter_num, metrics, config, ema=ema, drop_path=drop_path,
-                                patch_drop=patch_drop, rand_augment=rand_augment, lr_schedule=lr_schedule), path)
+                                patch_drop=patch_drop, rand_augment=rand_augment, lr_schedule=lr_schedule,
+                                loader=loader), path)
     return path
 
 

@@ -129,12 +129,19 @@ def _check_hw(H, W) -> None:
 # ---------------------------------------------------------------------------------------------- RandomResizedCrop
 class CroppedBatch(StagedBatch):
     """A stored uint8 [B,Hs,Ws,C] batch together with the RandomResizedCrop that cuts it: what `rrc.batch(u8)` returns
-    and `AutoAugment.batch` / `RandomErasing.batch` accept in place of a tensor.  `.shape` is that of its output."""
+    and `AutoAugment.batch` / `RandomErasing.batch` accept in place of a tensor.  u8: the tensor, or a `DeviceLoader.batch()`
+    (data.py) whose gathered batch is then what is cut.  `.shape` is that of its output."""
 
-    key, word, accepts, names = "crop", "RandomResizedCrop", (), ("crop", "u8")
+    key, word, accepts, names = "crop", "RandomResizedCrop", ("data",), ("crop", "u8")
 
-    def __init__(self, crop: "RandomResizedCrop", u8: Tensor):
-        B, _, _, C = _check_source(u8)
+    def __init__(self, crop: "RandomResizedCrop", u8):
+        if self.takes(u8):   # a loader's batch (data.py): the gathered [B,Hs,Ws,C]
+            B, Hs, Ws, C = u8.shape
+            if B > MAX_BATCH:
+                raise ValueError(f"RandomResizedCrop: a batch holds 1..{MAX_BATCH} images (got {B})")
+            _check_src_hw(Hs, Ws)
+        else:
+            B, _, _, C = _check_source(u8)
         super().__init__(crop, u8, (B, crop.size, crop.size, C))
 
     def check_step(self) -> None:

@@ -17,7 +17,7 @@ from typing import Dict, Iterable, Tuple
 import torch
 
 from . import ops
-from .stages import StagedBatch
+from .stages import StagedBatch, chain
 from .train import _unwrap, add_aux_losses
 
 Tensor = torch.Tensor
@@ -28,7 +28,10 @@ _KOHONEN_KEYS = (("val/consistency_loss", "kohonen_consistency"), ("val/smoothne
 
 def _split(X) -> tuple:
     """X of an evaluation call -> (its fit key, its tensor): those of a `ResizeCenterCrop.batch(u8)`, the one batch object
-    that is no stage of a train step (stages.py); (None, X) for anything else."""
+    that is no stage of a train step (stages.py); (None, X) for anything else.  A chain on a `DeviceLoader.batch()` (data.py)
+    is refused: it draws a training batch and advances the loader."""
+    if any(b.key == "data" for b in chain(X)):
+        raise TypeError("a DeviceLoader.batch() is a train step's input; evaluation takes DeviceDataset.eval_batches(...)")
     return (X.fit_key(), X.source()) if isinstance(X, StagedBatch) and X.key is None else (None, X)
 
 
@@ -63,6 +66,7 @@ class _eval_mode:
 def predict(model, X: Tensor) -> Tensor:
     """Logits of `model(X)` (bit-identical) from the forward-only route, without the reconstruction head: its GEMM,
     its loss kernel and the stream's bf16 copy that only it reads (plain ViT) are skipped."""
+    _split(X)   # (refuses a loader's batch before anything else)
     with _eval_mode(model) as m:
         return m._forward(_model_input(X), False)[0]
 
@@ -150,6 +154,7 @@ class GraphedEval:
     """
 
     def __init__(self, model, X, y: Tensor, consistency_weight: float = 0.1, smoothness_weight: float = 0.1):
+        _split(X)   # (refuses a loader's batch before anything else)
         self.model = model
         self.cw, self.sw = consistency_weight, smoothness_weight
         self._size_epoch = _unwrap(model)._size_epoch

@@ -197,7 +197,7 @@ class MixedBatch(StagedBatch):
         super().__init__(mix, X, X.shape)
 
     def check_labels(self, y) -> None:
-        _check_labels(y, self.B)
+        _check_labels(self.labels() if y is None else y, self.B)   # (y None: those of a loader batch inside, if there is one)
 
     def resolve(self, y=None):
         self.check_labels(y)   # before any launch of what X carries

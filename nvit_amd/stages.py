@@ -2,11 +2,12 @@
 the argument checks.  augment.py, randaug.py, crop.py and mix.py import this module; it imports none of them.
 
     mix.batch(erase.batch(aug.batch(rrc.batch(u8)), mean, std))      training: any stage may be left out
+    mix.batch(erase.batch(aug.batch(rrc.batch(ld.batch())), mean, std))   the same on a device-resident dataset (data.py)
     rcc.batch(u8)                                                     evaluation
 
 A `stage.batch(X)` is a `StagedBatch`: the stage object together with what it runs on, a tensor or another StagedBatch.
 The protocol ("The batch-object protocol") is `resolve`, `rebind`, `source` and `fit_key`; the one legal
-nesting order is what the five subclasses declare in `accepts`.
+nesting order is what the six subclasses declare in `accepts`.
 """
 from __future__ import annotations
 
@@ -174,6 +175,11 @@ class StagedBatch:
     def rebind(self, tensor: Tensor) -> "StagedBatch":
         """The same chain of the same stage objects around another innermost tensor."""
         return self.stage.batch(self.inner.rebind(tensor) if isinstance(self.inner, StagedBatch) else tensor, *self.extra)
+
+    def labels(self):
+        """The labels that the chain itself supplies, as far as a check of them needs (int64 [B]): those of a loader batch
+        (data.py), None for a chain around a tensor, whose step is handed its y."""
+        return self.inner.labels() if isinstance(self.inner, StagedBatch) else None
 
     def check_step(self) -> None:
         """Raises if this object cannot be the X of a step by itself."""

@@ -101,12 +101,20 @@ def add_aux_losses(config, loss: torch.Tensor, aux, consistency_weight: float = 
     return loss
 
 
-def _check_step_args(optimizer, X, accumulation_steps, skip_nonfinite) -> None:
+def _loader_batch(X):
+    """The `DeviceLoader.batch()` (data.py) that the chain X stands on, or None."""
+    batches = chain(X)
+    return batches[-1] if batches and batches[-1].key == "data" else None
+
+
+def _check_step_args(optimizer, X, accumulation_steps, skip_nonfinite, y=None) -> None:
     """The argument checks of train_step / GraphedTrainStep: ValueError (TypeError for evaluation's batch object), before
     any device work."""
     if isinstance(X, CenterCroppedBatch):
         raise TypeError("a ResizeCenterCrop.batch(u8) (CenterCroppedBatch) is evaluation's input; a train step takes a tensor "
                         "or the chain of RandomResizedCrop.batch(u8)")
+    if y is not None and _loader_batch(X) is not None:
+        raise ValueError("the labels of a DeviceLoader.batch() come from the dataset: pass y=None")
     n = accumulation_steps
     if not isinstance(n, int) or isinstance(n, bool) or n < 1:
         raise ValueError(f"accumulation_steps must be an int >= 1 (got {n!r})")
@@ -118,7 +126,8 @@ def _check_step_args(optimizer, X, accumulation_steps, skip_nonfinite) -> None:
 
 def _unwrap_input(X):
     """X of a step -> ({"mix": Mixup, "erase": (RandomErasing, mean, std), "augment": AutoAugment, "crop":
-    RandomResizedCrop}, the stages it carries, outermost first; the tensor underneath): the chain as a dict."""
+    RandomResizedCrop, "data": DeviceLoader}, the stages it carries, outermost first; the tensor underneath - under a
+    loader its dataset's own): the chain as a dict."""
     if isinstance(X, StagedBatch):
         X.check_step()
     batches = chain(X)
@@ -189,8 +198,10 @@ def train_step(model, optimizer, X: torch.Tensor, y: torch.Tensor, grad_clip: fl
     gradients, hence the same decision.  Needs FusedAdamW.
 
     X may be a chain of the input stages, `mix.batch(erase.batch(aug.batch(rrc.batch(u8))))` or any part of it in that
-    order (stages.py; DESIGN.md §7, "The batch-object protocol"): every stage's launches run once for the whole batch, ahead
-    of the forward and of any accumulation split, and every stage's counter advances by one per call.  With a Mixup the loss
+    order, with a `DeviceLoader.batch()` (data.py) where the uint8 tensor stands - y is then None, batch and labels are
+    drawn and gathered on the device by the chain's first two launches (stages.py; DESIGN.md §7, "The batch-object
+    protocol"): every stage's launches run once for the whole batch, ahead of the forward and of any accumulation split,
+    and every stage's counter advances by one per call.  With a Mixup the loss
     is the soft-target cross-entropy of the drawn `MixedTargets`, the returned logits belong to the mixed batch, and under
     accumulation micro-batch i takes rows [i*b, (i+1)*b) of the mixed batch and of the targets (a row's partner may lie in
     another micro-batch; the targets carry the partner's label).  A tensor X takes exactly the launches it always took.
@@ -205,7 +216,7 @@ def train_step(model, optimizer, X: torch.Tensor, y: torch.Tensor, grad_clip: fl
 
     Wrong accumulation_steps (no int, < 1, no divisor of the batch) or skip_nonfinite with another optimizer raise
     ValueError before any device work."""
-    _check_step_args(optimizer, X, accumulation_steps, skip_nonfinite)
+    _check_step_args(optimizer, X, accumulation_steps, skip_nonfinite, y)
     X, y = _resolve_input(X, y)   # the chain's launches for the whole batch, ahead of any accumulation split
     logits, loss, aux = _forward_backward(model, X, y, accumulation_steps)
     if sync_grads is not None:
@@ -257,6 +268,16 @@ class GraphedTrainStep:
     draws afresh with no host code in between: the warm-up steps are steps of every stage (they advance its counter, as
     they advance the weights), the capture pass is not, every replay is.
 
+    With a `DeviceLoader.batch()` (data.py) as the chain's innermost stage the static input is the dataset's own tensor
+    (`self.X` is it, not a copy) and there is no static y: a call copies nothing to the device, and K steps are K replays.
+    The call takes the chain around the captured loader's batch and y=None; another loader or another dataset tensor is
+    refused.  The loader's counter counts like every stage's: warm-up steps yes, the capture pass no.  `ld.record` holds
+    the (epoch, step in the epoch) of the last replay, readable whenever the host chooses to wait.
+
+    `self.targets` (every captured step has it, beside `self.logits` and `self.loss`) is the static target that the
+    captured loss reads, as of the last replay: the static y itself for a tensor X or a chain without a Mixup, the
+    `MixedTargets` a Mixup drew, a loader's gathered labels (or the `MixedTargets` drawn from them).
+
     A `ModelEma` (ema.py) attached to the optimizer before this object is built is part of the captured step: its tick and
     its update follow the optimizer's launches, and its count lives on the device.  The warm-up steps are updates, as they
     are optimizer steps; the capture pass is not (it executes nothing).  A call with another EMA attached than at capture
@@ -287,7 +308,7 @@ class GraphedTrainStep:
 
     def __init__(self, model, optimizer, X: torch.Tensor, y: torch.Tensor, grad_clip: float = 1.0, warmup: int = 3,
                  *, accumulation_steps: int = 1, skip_nonfinite: bool = False):
-        _check_step_args(optimizer, X, accumulation_steps, skip_nonfinite)
+        _check_step_args(optimizer, X, accumulation_steps, skip_nonfinite, y)
         m = _unwrap(model)
         if not isinstance(optimizer, FusedAdamW):
             raise RuntimeError("GraphedTrainStep needs the FusedAdamW returned by ViT.configure_optimizers")
@@ -303,7 +324,10 @@ class GraphedTrainStep:
             X.check_labels(y)
         if self._fit:
             X.check_step()
-        self.X, self.y = (X.source() if self._fit else X).clone(), y.clone()
+        if "data" in self._fit:   # the dataset's own tensor, not a copy of it, and no y: nothing is sent per call
+            self.X, self.y = X.source(), None
+        else:
+            self.X, self.y = (X.source() if self._fit else X).clone(), y.clone()
         self._input = X.rebind(self.X) if self._fit else self.X
         self.model, self.optimizer, self.grad_clip = model, optimizer, grad_clip
         self.ema = optimizer.ema   # the ModelEma (or none) whose update the warm-up steps run and the capture records
@@ -355,6 +379,7 @@ class GraphedTrainStep:
             for km in self._maps:
                 object.__setattr__(km, "_rate_dev", None)
         self.logits, self.loss = logits.detach(), loss.detach()
+        self.targets = yin   # the loss's target of the last replay: y, a Mixup's MixedTargets, a loader's gathered labels
         self.aux = {k: v.detach() for k, v in aux.items()}
         self.gnorm = gnorm
         optimizer.note_replay(-1)   # the capture pass records the step but does not execute it,
@@ -404,8 +429,13 @@ class GraphedTrainStep:
         for words, now, captured in self._attached:
             if now() != captured:
                 raise ValueError(f"GraphedTrainStep: {words}")
-        self.X.copy_(X, non_blocking=True)
-        self.y.copy_(y, non_blocking=True)
+        if "data" in self._fit:
+            if not isinstance(X, torch.Tensor) or X.data_ptr() != self.X.data_ptr() or X.shape != self.X.shape or y is not None:
+                raise ValueError("GraphedTrainStep: this graph was captured with another dataset tensor: call it with the "
+                                 "chain around the captured DeviceLoader.batch() and y=None")
+        else:
+            self.X.copy_(X, non_blocking=True)
+            self.y.copy_(y, non_blocking=True)
         self._advance_som()
         self.graph.replay()
         self.optimizer.note_replay()
